@@ -261,6 +261,38 @@ def timed_steps(step_fn, barrier_fn, steps, device):
     return elapsed, per_step, host * 1e3, last
 
 
+DUMP_BYTES = 64 * 10**6         # --dump-outputs: everything written, .npy headers included
+DUMP_WHOLE_BYTES = 1 << 20      # arrays up to this size are always written whole
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy -- floating point as float32 (float64 stays float64), integers as float64
+    (exact) -- so that two builds can be compared output for output.  When the arrays do not fit in `budget` bytes, each one larger than
+    DUMP_WHOLE_BYTES keeps the same fraction of its rows: a sorted sample drawn by a generator seeded with 0, so runs whose arrays have
+    equal shapes keep equal rows; the row indices are written beside it as <name>_rows.npy."""
+    def host(a):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        return a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype != np.float64 else np.float64)
+    arrays = {k: host(v) for k, v in arrays.items()}
+    big = [k for k, a in arrays.items() if a.nbytes > DUMP_WHOLE_BYTES]
+    room = budget - sum(a.nbytes for k, a in arrays.items() if k not in big) - 2 * 256 * len(arrays)
+    need = sum(arrays[k].nbytes + 8 * len(arrays[k]) for k in big)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if name in big and need > room:
+            rows = np.unique(np.random.default_rng(0).integers(0, len(a), max(1, int(len(a) * room / need))))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def describe_outputs(tb, ld):
+    """what Engine.describe_lines hands its caller for a batch: line_desc and the TokenBatch fields it fills (the dense per-token tensors
+    are not materialised on this path)"""
+    return {"line_desc": ld, "klines": tb.klines, "length": tb.length, "angles": tb.angles, "sublines": tb.sublines, "resp": tb.resp,
+            "angle_sub": tb.angle_sub, "sub2line": tb.sub2line, "cu_k": tb.cu_k, "cu_n": tb.cu_n}
+
+
 def cpu_baseline(workload, budget_s=14.0):
     """The CPU oracle (a faithful port of the reference's as-executed PyTorch-CPU/NumPy path, incl. the per-line Python
     tokeniser loop and the full 22-token descriptive layer) timed on this box over a sweep of torch thread counts
@@ -872,6 +904,18 @@ class Cfg4Job:
         self.last = (gs, ld, cu_n, cu_k, res, queries, cands)
         return int(cu_n[-1])
 
+    def outputs(self):
+        """what the last step() computed on this rank: its descriptors and the global matches of its queries, the matcher's chunks
+        joined (offsets rebased onto the joined arrays)"""
+        _gs, ld, cu_n, cu_k, res, _q, _c = self.last
+        off_dk, off_k0 = [np.zeros(1, np.int64)], [np.zeros(1, np.int64)]
+        for _dk, o_dk, _m01, o_k0 in res:
+            off_dk.append(np.asarray(o_dk[1:], np.int64) - int(o_dk[0]) + off_dk[-1][-1])
+            off_k0.append(np.asarray(o_k0[1:], np.int64) - int(o_k0[0]) + off_k0[-1][-1])
+        return {"line_desc": ld, "cu_n": cu_n, "cu_k": cu_k, "match_dist": torch.cat([r[0] for r in res]),
+                "match_dist_offsets": np.concatenate(off_dk), "match01": torch.cat([r[2] for r in res]),
+                "match01_offsets": np.concatenate(off_k0)}
+
     def phase_ms(self):
         torch.cuda.synchronize()
         e0, e1, e2, e3 = self.ev
@@ -923,6 +967,8 @@ def run_cfg4(args, eng, device, rank, world, dist):
     for _ in range(args.warmup):
         job.step()
     elapsed, per_step, host_ms, n_local = timed_steps(job.step, barrier, args.steps, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job.outputs())
     phases = np.array(job.phase_ms())
     if world > 1:
         t = torch.tensor([elapsed, float(n_local), *phases], dtype=torch.float64, device=device)
@@ -1092,8 +1138,13 @@ def main():
     ap.add_argument("--pairs-total", type=int, default=1024, help="cfg4: pairs of the whole job")
     ap.add_argument("--candidates", type=int, default=4, help="cfg4: gathered candidate images matched per query image")
     ap.add_argument("--homography-strength", type=float, default=1.0, help="cfg4: 1 = the yaml's recipe, <1 milder views")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's arrays) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_BYTES // 10**6} MB in all (a fixed seeded sample of rows beyond that)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)      # internal: one process of cpu_baseline_socket
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker:
         wl, th, sec = args.cpu_worker.split(",")
@@ -1176,6 +1227,8 @@ def main():
         # fall behind the last event: the per-step statistics are taken over the K - depth completion-to-completion intervals in between
         tb, ld, _g = pipe.last_joined
         per_step = per_step[args.pipeline:] if len(per_step) > args.pipeline + 1 else (per_step[per_step > 0.05] if (per_step > 0.05).any() else per_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, describe_outputs(tb, ld))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -7,9 +7,18 @@ The reference's SuperPoint constructor loads `weights/superpoint_v1.pth`, which 
 data, so `torch.load` is pointed at the seeded state_dict of `workloads.synth.superpoint_state_dict` for the
 duration of the constructor.  Forward hooks capture the raw head outputs (convPb / convDb); the fixture holds those
 inputs plus everything `SuperPoint.forward` returns.  Only data is written.
+
+torch's CPU softmax / normalize round differently per ATen CPU kernel path (ATEN_CPU_CAPABILITY) and, for softmax, per thread
+count.  So superpoint_heads_paths.npz holds, for every path of an x86 build, the dense maps `SuperPoint.forward` computes on ONE thread
+from the stored head inputs (hooks hand convPb / convDb's outputs back as the stored arrays), PATH as
+torch.backends.cpu.get_cpu_capability() names it.  They differ from the fixture's dense_score / dense_descriptor by a few units in the
+last place, so each is stored as those bit differences: ulps_dense_score_<PATH> / ulps_dense_descriptor_<PATH> (int8,
+map = (fixture map viewed as int32 + ulps) viewed as float32).  `--kernel-paths` writes only that file.
 """
 import os
+import subprocess
 import sys
+import tempfile
 import types
 
 sys.dont_write_bytecode = True
@@ -39,6 +48,41 @@ def build(seed, **cfg):
     return m
 
 
+KERNEL_PATHS = ("default", "avx2", "avx512")      # ATEN_CPU_CAPABILITY values of an x86 torch build
+
+
+def heads_on_stored_inputs(path, out):
+    """(run with ATEN_CPU_CAPABILITY set) this process's kernel path, one thread, on the fixture's stored head inputs"""
+    g = np.load(path)
+    torch.set_num_threads(1)
+    m = build(0, max_keypoints=-1, keypoint_threshold=0.005, nms_radius=4, remove_borders=4)
+    m.convPb.register_forward_hook(lambda mod, i, o: torch.from_numpy(g["score_logits"]))
+    m.convDb.register_forward_hook(lambda mod, i, o: torch.from_numpy(g["desc_raw"]))
+    r = m({"image": torch.from_numpy(g["image"])})
+    np.savez(out, path=np.str_(torch.backends.cpu.get_cpu_capability()), dense_score=r["dense_score"].numpy(),
+             dense_descriptor=r["dense_descriptor"].numpy())
+
+
+def add_kernel_paths(path):
+    fx = np.load(path)
+    ulps = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for cap in KERNEL_PATHS:
+            out = os.path.join(tmp, cap + ".npz")
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--heads", path, out], check=True,
+                           env=dict(os.environ, ATEN_CPU_CAPABILITY=cap))
+            r = np.load(out)
+            name = str(r["path"])
+            assert name.lower() == cap, (name, cap)
+            for k in ("dense_score", "dense_descriptor"):
+                d = r[k].view(np.int32).astype(np.int64) - fx[k].view(np.int32).astype(np.int64)
+                assert np.abs(d).max() <= 127, (name, k, np.abs(d).max())
+                ulps[f"ulps_{k}_{name}"] = d.astype(np.int8)
+    out = os.path.join(HERE, "superpoint_heads_paths.npz")
+    np.savez_compressed(out, **ulps)
+    print(out, {k: int(np.abs(v).max()) for k, v in ulps.items()})
+
+
 def main():
     m = build(0, max_keypoints=-1, keypoint_threshold=0.005, nms_radius=4, remove_borders=4)
     cap = {}
@@ -57,7 +101,13 @@ def main():
     path = os.path.join(HERE, "superpoint_heads.npz")
     np.savez_compressed(path, **fx)
     print(path, {k: getattr(v, "shape", None) for k, v in fx.items()})
+    add_kernel_paths(path)
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["--heads"]:
+        heads_on_stored_inputs(*sys.argv[2:4])
+    elif sys.argv[1:2] == ["--kernel-paths"]:
+        add_kernel_paths(os.path.join(HERE, "superpoint_heads.npz"))
+    else:
+        main()

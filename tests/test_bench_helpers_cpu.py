@@ -75,3 +75,44 @@ def test_socket_filling_cpu_baseline_adds_up_process_rates(bench):
     r = bench.cpu_baseline_socket("cfg2", 1, 2, seconds=1.0)
     assert r["processes"] == 2 and r["threads_per_process"] == 1 and r["cores"] == 2 and r["physical_cores"] == 2
     assert r["value"] > 100 and r["unit"] == "line-descriptors/s"
+
+
+def test_dumped_outputs_are_float32_or_float64_and_exact(bench, tmp_path):
+    """--dump-outputs under its budget: every array whole, floating point as float32 (float64 kept), integers as float64, values exact."""
+    import numpy as np
+    import torch
+    ld = torch.randn(300, 256)
+    s2l = torch.arange(300, dtype=torch.int32) // 3
+    cu = np.array([0, 120, 300], np.int32)
+    ang = np.linspace(0, 1, 7)
+    bench.dump_outputs(str(tmp_path), {"line_desc": ld, "sub2line": s2l, "cu_n": cu, "angles": ang})
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(got) == ["angles", "cu_n", "line_desc", "sub2line"]
+    assert got["line_desc"].dtype == np.float32 and np.array_equal(got["line_desc"], ld.numpy())
+    assert got["sub2line"].dtype == np.float64 and np.array_equal(got["sub2line"], s2l.numpy())
+    assert got["cu_n"].dtype == np.float64 and np.array_equal(got["cu_n"], cu)
+    assert got["angles"].dtype == np.float64 and np.array_equal(got["angles"], ang)
+
+
+def test_dumped_outputs_beyond_the_budget_are_a_fixed_sample_of_rows(bench, tmp_path):
+    """An array too large for the budget keeps a seeded, sorted sample of its rows (the same rows in every run with the same shapes),
+    its row indices beside it; small arrays stay whole; everything written fits the budget."""
+    import numpy as np
+    big = np.random.default_rng(5).standard_normal((4096, 256)).astype(np.float32)          # 4 MiB
+    small = np.arange(10, dtype=np.int64)
+    budget = 2 * 10**6
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"line_desc": big, "cu_n": small}, budget=budget)
+        assert sum(p.stat().st_size for p in (tmp_path / d).iterdir()) <= budget
+    rows = np.load(tmp_path / "a" / "line_desc_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < len(big) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "line_desc.npy"), big[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "line_desc_rows.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "cu_n.npy"), small) and not (tmp_path / "a" / "cu_n_rows.npy").exists()
+
+
+def test_steps_below_one_are_refused(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2

@@ -47,32 +47,34 @@ def test_cfg4_self_launch():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
 
 
-# ---- world size 8: the only size the driver's scaling run ends on (one node, eight MI355X).  Same one-device / gloo plumbing mode,
-# tiny workloads: eight ranks, pre-flight, uneven shards, the slab gather, global matching, the one-JSON-line contract.
+# ---- more than two ranks: a ring of three (rank r's next rank is not also its previous one), an odd world and uneven shards.  Same
+# one-device / gloo plumbing mode, tiny workloads: pre-flight, uneven shards, the slab gather, global matching, the one-JSON-line
+# contract.  Three is the most one device takes here: pytest and bench.py's launching process hold the GPU as well, and at most six
+# processes may have it open at once.
 
-def test_eight_ranks_default_workload():
-    d = _run(["--pairs", "2"], gpus=8)
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["steps"] == 3
-    assert d["config"]["descriptors_per_step"] > 8 * 2 * 2 * 150            # all eight ranks' descriptors are counted
+def test_three_ranks_default_workload():
+    d = _run(["--pairs", "2"], gpus=3)
+    assert d["n_gpus"] == 3 and d["scaling"] == "weak" and d["steps"] == 3
+    assert d["config"]["descriptors_per_step"] > 3 * 2 * 2 * 150            # all three ranks' descriptors are counted
     assert d["gathered_rows_checked"] is True and d["collective_backend"] == "gloo"
-    assert d["preflight"]["ranks_seen"] == 8 and len(d["preflight"]["devices"]) == 8 and len(d["gather_ms_per_rank"]) == 8
+    assert d["preflight"]["ranks_seen"] == 3 and len(d["preflight"]["devices"]) == 3 and len(d["gather_ms_per_rank"]) == 3
     assert d["global_match"]["matches"] > 0 and "rank 1" in d["global_match"]["against"]
     assert "cpu_baseline" not in d               # (the CPU baseline is reported at N = 1 only, as the contract asks)
 
 
-def test_eight_ranks_cfg4_uneven_shards():
-    """19 pairs over 8 ranks: ranks 0-2 own 3 pairs, ranks 3-7 own 2 -- slab heights agreed by the MAX all-reduce, every rank's
+def test_three_ranks_cfg4_uneven_shards():
+    """19 pairs over 3 ranks: rank 0 owns 7 pairs, ranks 1-2 own 6 -- slab heights agreed by the MAX all-reduce, every rank's
     queries matched against candidates other ranks own."""
-    d = _run(["--workload", "cfg4", "--pairs-total", "19", "--pairs", "2", "--candidates", "3"], gpus=8)
-    assert d["n_gpus"] == 8 and d["scaling"] == "strong"
+    d = _run(["--workload", "cfg4", "--pairs-total", "19", "--pairs", "2", "--candidates", "3"], gpus=3)
+    assert d["n_gpus"] == 3 and d["scaling"] == "strong"
     assert d["config"]["pairs_total"] == 19 and d["config"]["collective"] == "all_gather(slab)"
     assert d["config"]["pair_matches_per_step"] == 19 * 3
     assert d["config"]["descriptors_per_step"] > 19 * 2 * 150
-    assert d["preflight"]["ranks_seen"] == 8
+    assert d["preflight"]["ranks_seen"] == 3
     assert d["recall_vs_homography_rank0"]["matches"] > 0
 
 
-def test_eight_ranks_a_bad_rank_fails_with_exit_code_3():
-    d = _run(["--pairs", "2"], expect_failure=True, gpus=8, LINETR_BENCH_INJECT="bad_gather")
-    assert d["value"] is None and "gathered_rows_checked" in d["error"] and d["n_gpus"] == 8
+def test_three_ranks_a_bad_rank_fails_with_exit_code_3():
+    d = _run(["--pairs", "2"], expect_failure=True, gpus=3, LINETR_BENCH_INJECT="bad_gather")
+    assert d["value"] is None and "gathered_rows_checked" in d["error"] and d["n_gpus"] == 3
     assert _run.returncode != 0
