@@ -191,7 +191,7 @@ int run_gemm_norm(LinetrHandle* h, hipStream_t st, const float* A, int lda, cons
                   const float* W, const float* bias, const float* R, float* tmp, float* Y, int M, int K,
                   const NormSpec& ns) {
   const bool no_fuse = LT_XENV("LINETR_NO_FUSED_NORM") != nullptr;   // tuning / test aid (read per call)
-  bool fuse = !no_fuse && h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_GEMM_TILE") && !LT_XENV("LINETR_GEMM_NARROW_EPI");
+  bool fuse = !no_fuse && h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_GEMM_TILE");
   if (fuse) {
     GemmArgs g{};
     g.M = M; g.N = D; g.K = K; g.lda = lda; g.ldy = D; g.ldr = D; g.R = R; g.A2 = A2; g.lda2 = lda2; g.K1 = K1;
@@ -485,19 +485,21 @@ struct TokenStage {            // how the token stage (word MLP + CLS pooling) i
   PipeStages* pipe = nullptr;  // pipelined call (linetr_describe_submit): where the launch sequence moves on to the next stream
 };
 
-bool fused_mlp_enabled(const LinetrModelConfig& c) {
-  static const bool off = LT_XENV("LINETR_NO_FUSED_MLP") != nullptr;   // tuning aid: the three-launch chain
-  return !off && c.enc_channels[1] == 64 && c.enc_channels[2] == 128;
-}
+bool fused_mlp_enabled(const LinetrModelConfig& c) { return c.enc_channels[1] == 64 && c.enc_channels[2] == 128; }
 
 // rows handled by one wave of mlp123_kernel (multiples of the 32-row MFMA step).  The kernel holds 160 weights per lane,
 // so one wave fits a SIMD (1024 on the chip) and workgroup dispatch is slow for such fat blocks (~10 blocks/us
 // measured): give every wave one long run of rows -- a single round of <= 256 blocks -- rather than many short ones.
 int mlp123_rows_per_wave(int64_t rows) {
-  static const char* env = LT_XENV("LINETR_MLP_RPW");   // tuning aid
-  if (env) return atoi(env);
   const int64_t waves = 256 * 4;
   return (int)std::max<int64_t>(cdiv((int)cdiv((int)rows, (int)waves), 32) * 32, 32);
+}
+
+// flops of one signature layer's attention: q k^T and p v of every (image, head)
+double attn_flops(const int32_t* h_cu, int n_images) {
+  double fl = 0;
+  for (int i = 0; i < n_images; ++i) { const double n = h_cu[i + 1] - h_cu[i]; fl += 2.0 * 2.0 * n * n * D; }
+  return fl;
 }
 
 #ifdef LINETR_EXPERIMENTS
@@ -528,8 +530,7 @@ int sig_network_st(LinetrHandle* h, hipStream_t st, FwdWs& w, const int32_t* h_c
     LT_LAUNCH_CHECK();
   }
   unsigned char *z = w.zsA, *zn = w.zsB;
-  double attn_fl = 0;
-  for (int i = 0; i < n_images; ++i) { const double n = h_cu[i + 1] - h_cu[i]; attn_fl += 2.0 * 2.0 * n * n * D; }
+  const double attn_fl = attn_flops(h_cu, n_images);
   for (size_t l = 0; l < h->sig.size(); ++l) {
     const SigLayer& S = h->sig[l];
     if ((e = gemm("gemm_st_bf16x6_qkv", z, D, nullptr, 0, S.Wqkv, S.bqkv, nullptr, w.qkvs, nullptr, 3 * D, ACT_NONE))) return e;
@@ -557,39 +558,75 @@ int sig_network_st(LinetrHandle* h, hipStream_t st, FwdWs& w, const int32_t* h_c
 }
 
 #endif  // LINETR_EXPERIMENTS
-int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const float* sublines, const float* resp,
-                 const float* angle_sub, const int32_t* h_cu, const int* cu_dev, int n_images, int N, int T,
-                 float* d_line_desc, FwdWs& w) {
+
+// ---- positional encoders, training mode (train.py:127): conv -> BatchNorm(batch statistics) -> ReLU, layer by layer, on the
+// unfolded convolutions of a bn_batch_stats handle.  Statistics run over ALL rows of the batch: B*N*T token positions (padding
+// tokens included, as the reference's [B*N, 3, T] input has them) for the word encoder, B*N sub-lines for the line encoder.
+int pos_encoders_bn(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const float* sublines, const float* resp,
+                    const float* angle_sub, int N, FwdWs& w) {
   const LinetrModelConfig& c = h->cfg;
-  int max_n = 0;
-  for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
-  const int64_t rows = ts.rows;
   const int e0 = c.enc_channels[0], e1 = c.enc_channels[1], e2 = c.enc_channels[2], e3 = c.enc_channels[3];
   const float cx = c.norm_width / 2.f, cy = c.norm_height / 2.f;           // line_transformer.py:30-32
   const float scale = (float)std::max(c.norm_width, c.norm_height) * 0.7f;
+  const int64_t rows = ts.rows;
+  const BnTrain& bt = *ts.bn;
+  int64_t off = 0;
   int e;
-  // experiment (LINETR_PAIRNET=1; measured and not shipped, DESIGN.md 12): the whole signature network of a single pair as ONE
-  // persistent launch (lt_pairnet.h); its arrival counters are zeroed here, far ahead of it on the stream
-#ifdef LINETR_EXPERIMENTS
-  const bool pairnet = pairnet_fits(h, n_images, N, h_cu);
-  if (pairnet && (e = pairnet_prepare(h, st, N, w.pn))) return e;
-#endif
-  // ---- word positional encoder up to the last ReLU (a4); its final linear layer is applied after pooling
+  auto bn = [&](int layer, float* zbuf, int64_t r, int C) {
+    const int64_t o = off; off += 2 * C;
+    return bn_train_layer(st, bt, zbuf, r, C, C, h->bn_g[layer], h->bn_b[layer], o);
+  };
+#define LT_BN(layer, zbuf, r, C) do { if ((e = bn(layer, zbuf, r, C))) return e; } while (0)
+  hipLaunchKernelGGL(word_mlp1_kernel<false>, dim3((unsigned)cdiv((int)(rows * 8), 256)), dim3(256), 0, st, ts.pnt, ts.score, rows,
+                     cx, cy, scale, h->wW1, h->wb1, w.a1);
+  LT_LAUNCH_CHECK();
+  LT_BN(0, w.a1, rows, e0);
+  if ((e = run_gemm(h, st, w.a1, e0, nullptr, 0, 0, h->wW2, h->wb2, nullptr, 0, w.a2, e1, (int)rows, e1, e0, ACT_NONE))) return e;
+  LT_BN(1, w.a2, rows, e1);
+  if ((e = run_gemm(h, st, w.a2, e1, nullptr, 0, 0, h->wW3, h->wb3, nullptr, 0, w.a3, e2, (int)rows, e2, e1, ACT_NONE))) return e;
+  LT_BN(2, w.a3, rows, e2);
+  if ((e = run_gemm(h, st, w.a3, e2, nullptr, 0, 0, h->wW4, h->wb4, nullptr, 0, w.a4, e3, (int)rows, e3, e2, ACT_NONE))) return e;
+  LT_BN(3, w.a4, rows, e3);
+  hipLaunchKernelGGL(line_mlp1_kernel<false>, dim3(cdiv(N * 8, 256)), dim3(256), 0, st, sublines, resp, angle_sub, N, cx, cy, scale,
+                     h->lW1, h->lb1, w.l1);
+  LT_LAUNCH_CHECK();
+  LT_BN(4, w.l1, N, e0);
+  if ((e = run_gemm(h, st, w.l1, e0, nullptr, 0, 0, h->lW2, h->lb2, nullptr, 0, w.l2, e1, N, e1, e0, ACT_NONE))) return e;
+  LT_BN(5, w.l2, N, e1);
+  if ((e = run_gemm(h, st, w.l2, e1, nullptr, 0, 0, h->lW3, h->lb3, nullptr, 0, w.l3, e2, N, e2, e1, ACT_NONE))) return e;
+  LT_BN(6, w.l3, N, e2);
+  if ((e = run_gemm(h, st, w.l3, e2, nullptr, 0, 0, h->lW4, h->lb4, nullptr, 0, w.l4, e3, N, e3, e2, ACT_NONE))) return e;
+  LT_BN(7, w.l4, N, e3);
+#undef LT_BN
+  return LINETR_OK;
+}
+
+// ---- positional encoders (up to CUT_MLP): the word encoder up to its last ReLU (a4; its final linear layer is applied after
+// pooling), the line encoder to its output (lpos)
+int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const float* sublines, const float* resp,
+                 const float* angle_sub, int N, FwdWs& w) {
+  const LinetrModelConfig& c = h->cfg;
+  const int e0 = c.enc_channels[0], e1 = c.enc_channels[1], e2 = c.enc_channels[2], e3 = c.enc_channels[3];
+  const float cx = c.norm_width / 2.f, cy = c.norm_height / 2.f;           // line_transformer.py:30-32
+  const float scale = (float)std::max(c.norm_width, c.norm_height) * 0.7f;
+  const int64_t rows = ts.rows;
+  const float* p0 = ts.cpnt ? ts.cpnt : ts.pnt;   // token coordinates and scores: compact (describe) or dense (forward)
+  const float* p1 = ts.cpnt ? ts.cscore : ts.score;
+  int e;
   const bool fused_mlp = fused_mlp_enabled(c);
-  // layers 1-4 in one kernel (lt_tokmlp.h): large batches in the default precision, the reference's channel widths
+  // layers 1-4 in one kernel (lt_tokmlp.h): the default precision and the reference's channel widths, at any size (a single pair,
+  // 4 k token rows and 400 sub-lines, gains too: 42 -> 31 us for the two encoders)
   auto st_of = [&](const float* W) -> const unsigned char* {
     auto it = h->split.find(W);
     return it != h->split.end() && it->second.offst ? h->split_arena + it->second.offst : nullptr;
   };
-  int64_t tok_mlp_min_rows = 0;      // any size: a single pair (4 k token rows, 400 sub-lines) gains too: 42 -> 31 us for the two encoders
-  if (const char* v = LT_XENV("LINETR_TOKMLP_MIN_ROWS")) tok_mlp_min_rows = atoll(v);   // tuning aid (experiments build)
   const bool tok_mlp_ok = fused_mlp && h->precision == LINETR_PREC_BF16X6 && e0 == 32 && e1 == 64 && e2 == 128 && e3 == 256 &&
                           !LT_XENV("LINETR_NO_TOKMLP");
-  const bool tok_mlp = tok_mlp_ok && rows >= tok_mlp_min_rows && st_of(h->wW2) && st_of(h->wW3) && st_of(h->wW4);
-  const bool line_mlp = tok_mlp_ok && N >= tok_mlp_min_rows && st_of(h->lW2) && st_of(h->lW3) && st_of(h->lW4);
+  const bool tok_mlp = tok_mlp_ok && st_of(h->wW2) && st_of(h->wW3) && st_of(h->wW4);
+  const bool line_mlp = tok_mlp_ok && st_of(h->lW2) && st_of(h->lW3) && st_of(h->lW4);
   TokMlpArgs amw, aml;
   if (tok_mlp) {
-    amw.p0 = ts.cpnt ? ts.cpnt : ts.pnt; amw.p1 = ts.cpnt ? ts.cscore : ts.score; amw.rows = rows; amw.cx = cx; amw.cy = cy; amw.scale = scale;
+    amw.p0 = p0; amw.p1 = p1; amw.rows = rows; amw.cx = cx; amw.cy = cy; amw.scale = scale;
     amw.W1 = h->wW1; amw.b1 = h->wb1; amw.W2st = st_of(h->wW2); amw.b2 = h->wb2; amw.W3st = st_of(h->wW3); amw.b3 = h->wb3;
     amw.W4st = st_of(h->wW4); amw.b4 = h->wb4; amw.Y = w.a4; amw.ldy = e3;
   }
@@ -598,131 +635,78 @@ int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const fl
     aml.W1 = h->lW1; aml.b1 = h->lb1; aml.W2st = st_of(h->lW2); aml.b2 = h->lb2; aml.W3st = st_of(h->lW3); aml.b3 = h->lb3;
     aml.W4st = st_of(h->lW4); aml.b4 = h->lb4; aml.Y = w.l4; aml.ldy = e3;
   }
-  bool line_done = false;
   if (ts.bn) {
-    // training mode (train.py:127): conv -> BatchNorm(batch statistics) -> ReLU, layer by layer, on the unfolded convolutions of a
-    // bn_batch_stats handle.  Statistics run over ALL rows of the batch: B*N*T token positions (padding tokens included, as the
-    // reference's [B*N, 3, T] input has them) for the word encoder, B*N sub-lines for the line encoder.
-    const BnTrain& bt = *ts.bn;
-    int64_t off = 0;
-    auto bn = [&](int layer, float* zbuf, int64_t r, int C) {
-      const int64_t o = off; off += 2 * C;
-      return bn_train_layer(st, bt, zbuf, r, C, C, h->bn_g[layer], h->bn_b[layer], o);
-    };
-#define LT_BN(layer, zbuf, r, C) do { if ((e = bn(layer, zbuf, r, C))) return e; } while (0)
-    hipLaunchKernelGGL(word_mlp1_kernel<false>, dim3((unsigned)cdiv((int)(rows * 8), 256)), dim3(256), 0, st, ts.pnt, ts.score, rows,
-                       cx, cy, scale, h->wW1, h->wb1, w.a1);
-    LT_LAUNCH_CHECK();
-    LT_BN(0, w.a1, rows, e0);
-    if ((e = run_gemm(h, st, w.a1, e0, nullptr, 0, 0, h->wW2, h->wb2, nullptr, 0, w.a2, e1, (int)rows, e1, e0, ACT_NONE))) return e;
-    LT_BN(1, w.a2, rows, e1);
-    if ((e = run_gemm(h, st, w.a2, e1, nullptr, 0, 0, h->wW3, h->wb3, nullptr, 0, w.a3, e2, (int)rows, e2, e1, ACT_NONE))) return e;
-    LT_BN(2, w.a3, rows, e2);
-    if ((e = run_gemm(h, st, w.a3, e2, nullptr, 0, 0, h->wW4, h->wb4, nullptr, 0, w.a4, e3, (int)rows, e3, e2, ACT_NONE))) return e;
-    LT_BN(3, w.a4, rows, e3);
-    hipLaunchKernelGGL(line_mlp1_kernel<false>, dim3(cdiv(N * 8, 256)), dim3(256), 0, st, sublines, resp, angle_sub, N, cx, cy, scale,
-                       h->lW1, h->lb1, w.l1);
-    LT_LAUNCH_CHECK();
-    LT_BN(4, w.l1, N, e0);
-    if ((e = run_gemm(h, st, w.l1, e0, nullptr, 0, 0, h->lW2, h->lb2, nullptr, 0, w.l2, e1, N, e1, e0, ACT_NONE))) return e;
-    LT_BN(5, w.l2, N, e1);
-    if ((e = run_gemm(h, st, w.l2, e1, nullptr, 0, 0, h->lW3, h->lb3, nullptr, 0, w.l3, e2, N, e2, e1, ACT_NONE))) return e;
-    LT_BN(6, w.l3, N, e2);
-    if ((e = run_gemm(h, st, w.l3, e2, nullptr, 0, 0, h->lW4, h->lb4, nullptr, 0, w.l4, e3, N, e3, e2, ACT_NONE))) return e;
-    LT_BN(7, w.l4, N, e3);
-#undef LT_BN
-    line_done = true;
-  } else
-  // both encoders in ONE launch: side by side for a small batch, one after the other inside every persistent block for a large one
-  if (tok_mlp && line_mlp && rows > 0 && N > 0 && !LT_XENV("LINETR_NO_DUAL_MLP")) {
+    if ((e = pos_encoders_bn(h, st, ts, sublines, resp, angle_sub, N, w))) return e;
+  } else if (tok_mlp && line_mlp && rows > 0 && N > 0) {
+    // both encoders in ONE launch: side by side for a small batch, one after the other inside every persistent block for a large one
     ProfScope ps(h, st, "pos_mlp_dual_bf16x6", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2 + e2 * e3) + 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2 + e2 * e3),
                  (double)rows * (12 + 4 * e3) + (double)N * (28 + 4 * e3));
     if ((e = tok_mlp_launch_dual(amw, aml, st))) return e;
-    line_done = true;
-  }
-  if (line_done) {
-  } else if (tok_mlp) {
-    ProfScope ps(h, st, "tok_mlp_bf16x6", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)rows * (12 + 4 * e3));
-    if ((e = tok_mlp_launch(amw, true, st))) return e;
   } else {
-  if (fused_mlp) {   // layers 1-3 in one exact-fp32 MFMA kernel (lt_model.h)
-    ProfScope ps(h, st, "mlp123", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2), (double)rows * (12 + 4 * e2));
-    const int rpw = mlp123_rows_per_wave(rows);
-    hipLaunchKernelGGL(mlp123_kernel<true>, dim3((unsigned)cdiv((int)cdiv((int)rows, rpw), 4)), dim3(256), 0, st,
-                       ts.cpnt ? ts.cpnt : ts.pnt, ts.cpnt ? ts.cscore : ts.score, (const float*)nullptr, rows, rpw, cx, cy,
-                       scale, h->wW1, h->wb1, h->wW2, h->wb2, h->wW3, h->wb3, w.a3);
-    LT_LAUNCH_CHECK();
-  } else {
-    {
-      ProfScope ps(h, st, "mlp_first", 2.0 * rows * 3 * e0, (double)rows * (12 + 4 * e0));
-      hipLaunchKernelGGL(word_mlp1_kernel<true>, dim3((unsigned)cdiv((int)(rows * 8), 256)), dim3(256), 0, st,
-                         ts.cpnt ? ts.cpnt : ts.pnt, ts.cpnt ? ts.cscore : ts.score, rows, cx, cy, scale, h->wW1, h->wb1, w.a1);
-      LT_LAUNCH_CHECK();
+    // word encoder
+    if (tok_mlp) {
+      ProfScope ps(h, st, "tok_mlp_bf16x6", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)rows * (12 + 4 * e3));
+      if ((e = tok_mlp_launch(amw, true, st))) return e;
+    } else {
+      if (fused_mlp) {   // layers 1-3 in one exact-fp32 MFMA kernel (lt_model.h)
+        ProfScope ps(h, st, "mlp123", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2), (double)rows * (12 + 4 * e2));
+        const int rpw = mlp123_rows_per_wave(rows);
+        hipLaunchKernelGGL(mlp123_kernel<true>, dim3((unsigned)cdiv((int)cdiv((int)rows, rpw), 4)), dim3(256), 0, st, p0, p1,
+                           (const float*)nullptr, rows, rpw, cx, cy, scale, h->wW1, h->wb1, h->wW2, h->wb2, h->wW3, h->wb3, w.a3);
+        LT_LAUNCH_CHECK();
+      } else {
+        {
+          ProfScope ps(h, st, "mlp_first", 2.0 * rows * 3 * e0, (double)rows * (12 + 4 * e0));
+          hipLaunchKernelGGL(word_mlp1_kernel<true>, dim3((unsigned)cdiv((int)(rows * 8), 256)), dim3(256), 0, st, p0, p1, rows, cx, cy,
+                             scale, h->wW1, h->wb1, w.a1);
+          LT_LAUNCH_CHECK();
+        }
+        if ((e = run_gemm(h, st, w.a1, e0, nullptr, 0, 0, h->wW2, h->wb2, nullptr, 0, w.a2, e1, (int)rows, e1, e0, ACT_RELU))) return e;
+        if ((e = run_gemm(h, st, w.a2, e1, nullptr, 0, 0, h->wW3, h->wb3, nullptr, 0, w.a3, e2, (int)rows, e2, e1, ACT_RELU))) return e;
+      }
+      if ((e = run_gemm(h, st, w.a3, e2, nullptr, 0, 0, h->wW4, h->wb4, nullptr, 0, w.a4, e3, (int)rows, e3, e2, ACT_RELU))) return e;
     }
-    if ((e = run_gemm(h, st, w.a1, e0, nullptr, 0, 0, h->wW2, h->wb2, nullptr, 0, w.a2, e1, (int)rows, e1, e0, ACT_RELU))) return e;
-    if ((e = run_gemm(h, st, w.a2, e1, nullptr, 0, 0, h->wW3, h->wb3, nullptr, 0, w.a3, e2, (int)rows, e2, e1, ACT_RELU))) return e;
-  }
-  if ((e = run_gemm(h, st, w.a3, e2, nullptr, 0, 0, h->wW4, h->wb4, nullptr, 0, w.a4, e3, (int)rows, e3, e2, ACT_RELU))) return e;
-  }
-  // ---- line positional encoder
-  hipStream_t ls = st;
-  if (line_done) {
-  } else if (line_mlp) {   // layers 1-4 in one kernel, as for the word encoder
-    ProfScope ps(h, ls, "line_mlp_bf16x6", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)N * (28 + 4 * e3));
-    if ((e = tok_mlp_launch(aml, false, ls))) return e;
-  } else {
-  if (fused_mlp) {
-    ProfScope ps(h, ls, "mlp123_line", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2), (double)N * (28 + 4 * e2));
-    const int rpw = mlp123_rows_per_wave(N);
-    hipLaunchKernelGGL(mlp123_kernel<false>, dim3((unsigned)cdiv(cdiv(N, rpw), 4)), dim3(256), 0, ls, sublines, resp, angle_sub,
-                       (int64_t)N, rpw, cx, cy, scale, h->lW1, h->lb1, h->lW2, h->lb2, h->lW3, h->lb3, w.l3);
-    LT_LAUNCH_CHECK();
-  } else {
-    {
-      ProfScope ps(h, ls, "mlp_first", 2.0 * N * 5 * e0, (double)N * (28 + 4 * e0));
-      hipLaunchKernelGGL(line_mlp1_kernel<true>, dim3(cdiv(N * 8, 256)), dim3(256), 0, ls, sublines, resp, angle_sub, N, cx, cy,
-                         scale, h->lW1, h->lb1, w.l1);
-      LT_LAUNCH_CHECK();
+    // line encoder, as the word encoder
+    if (line_mlp) {
+      ProfScope ps(h, st, "line_mlp_bf16x6", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)N * (28 + 4 * e3));
+      if ((e = tok_mlp_launch(aml, false, st))) return e;
+    } else {
+      if (fused_mlp) {
+        ProfScope ps(h, st, "mlp123_line", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2), (double)N * (28 + 4 * e2));
+        const int rpw = mlp123_rows_per_wave(N);
+        hipLaunchKernelGGL(mlp123_kernel<false>, dim3((unsigned)cdiv(cdiv(N, rpw), 4)), dim3(256), 0, st, sublines, resp, angle_sub,
+                           (int64_t)N, rpw, cx, cy, scale, h->lW1, h->lb1, h->lW2, h->lb2, h->lW3, h->lb3, w.l3);
+        LT_LAUNCH_CHECK();
+      } else {
+        {
+          ProfScope ps(h, st, "mlp_first", 2.0 * N * 5 * e0, (double)N * (28 + 4 * e0));
+          hipLaunchKernelGGL(line_mlp1_kernel<true>, dim3(cdiv(N * 8, 256)), dim3(256), 0, st, sublines, resp, angle_sub, N, cx, cy,
+                             scale, h->lW1, h->lb1, w.l1);
+          LT_LAUNCH_CHECK();
+        }
+        if ((e = run_gemm(h, st, w.l1, e0, nullptr, 0, 0, h->lW2, h->lb2, nullptr, 0, w.l2, e1, N, e1, e0, ACT_RELU))) return e;
+        if ((e = run_gemm(h, st, w.l2, e1, nullptr, 0, 0, h->lW3, h->lb3, nullptr, 0, w.l3, e2, N, e2, e1, ACT_RELU))) return e;
+      }
+      if ((e = run_gemm(h, st, w.l3, e2, nullptr, 0, 0, h->lW4, h->lb4, nullptr, 0, w.l4, e3, N, e3, e2, ACT_RELU))) return e;
     }
-    if ((e = run_gemm(h, ls, w.l1, e0, nullptr, 0, 0, h->lW2, h->lb2, nullptr, 0, w.l2, e1, N, e1, e0, ACT_RELU))) return e;
-    if ((e = run_gemm(h, ls, w.l2, e1, nullptr, 0, 0, h->lW3, h->lb3, nullptr, 0, w.l3, e2, N, e2, e1, ACT_RELU))) return e;
   }
-  if ((e = run_gemm(h, ls, w.l3, e2, nullptr, 0, 0, h->lW4, h->lb4, nullptr, 0, w.l4, e3, N, e3, e2, ACT_RELU))) return e;
-  }
-  if ((e = run_gemm(h, ls, w.l4, e3, nullptr, 0, 0, h->lW5, h->lb5, nullptr, 0, w.lpos, D, N, D, e3, ACT_NONE))) return e;
-  if ((e = pipe_boundary(ts.pipe, CUT_MLP, st))) return e;
-  // ---- CLS-row attention pooling + value/last-MLP projection
+  return run_gemm(h, st, w.l4, e3, nullptr, 0, 0, h->lW5, h->lb5, nullptr, 0, w.lpos, D, N, D, e3, ACT_NONE);
+}
+
+// ---- CLS-row attention pooling + value / last-MLP projection (up to CUT_POOL)
+int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_images, int N, int T, FwdWs& w) {
+  const int64_t rows = ts.rows;
   if (ts.cpnt) {
-#ifdef LINETR_EXPERIMENTS
-    static const bool two_pass = LT_XENV("LINETR_POOL_TWO_PASS") != nullptr;  // tuning aid: the LDS two-pass variant
-#else
-    constexpr bool two_pass = false;
-#endif
-    if (!two_pass) {
-      // algorithmic bytes: the dense map once (or the four taps of every token, whichever is less), one a4 row per token, the pooled rows out
-      const double tap_bytes = std::min((double)n_images * ts.Hc * ts.Wc * D * 4, (double)rows * D * 4 * 4);
-      ProfScope ps(h, st, "cls_pool_online", 2.0 * rows * (2.0 * HEADS * D * 2), tap_bytes + (double)rows * D * 4 + (double)N * HEADS * POOLW * 4);
-      // few sub-lines (a single pair): four waves per sub-line, so that the chip is covered and the token chain is a quarter as long
-      if (N <= 2048 && !LT_XENV("LINETR_POOL_NO_SPLIT"))
-        hipLaunchKernelGGL(cls_pool_online_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                           w.a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 0);
-      else
-        hipLaunchKernelGGL(cls_pool_online_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                           w.a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled,
-                           LT_XENV("LINETR_POOL_FORWARD") ? 0 : 1);
-    }
-#ifdef LINETR_EXPERIMENTS
-    else {
-      ProfScope ps(h, st, "cls_pool_fused", 2.0 * rows * (2.0 * HEADS * D * 2), (double)rows * D * 4 * 5);
-      const size_t lds = ((size_t)(T + 1) * D + HEADS * (T + 2)) * sizeof(float);
-      if (lds > 160 * 1024) return fail(LINETR_E_ARG, "describe: max_tokens too large for the fused pooling kernel");
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cls_pool_fused_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(cls_pool_fused_kernel, dim3(N), dim3(256), lds, st, ts.recs, ts.sub2line_g, ts.cpnt, w.a4,
-                         ts.first_pad, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled);
-    }
-#endif
+    // algorithmic bytes: the dense map once (or the four taps of every token, whichever is less), one a4 row per token, the pooled rows out
+    const double tap_bytes = std::min((double)n_images * ts.Hc * ts.Wc * D * 4, (double)rows * D * 4 * 4);
+    ProfScope ps(h, st, "cls_pool_online", 2.0 * rows * (2.0 * HEADS * D * 2), tap_bytes + (double)rows * D * 4 + (double)N * HEADS * POOLW * 4);
+    // few sub-lines (a single pair): four waves per sub-line, so that the chip is covered and the token chain is a quarter as long
+    if (N <= 2048)
+      hipLaunchKernelGGL(cls_pool_online_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
+                         w.a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 0);
+    else   // (reverse = 1: the last sub-lines first, see the kernel)
+      hipLaunchKernelGGL(cls_pool_online_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
+                         w.a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 1);
     LT_LAUNCH_CHECK();
   } else {
     ProfScope ps(h, st, "cls_pool", 2.0 * rows * (2.0 * HEADS * D * 2), (double)rows * D * 8);
@@ -730,15 +714,14 @@ int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const fl
                        h->pool, w.pooled);
     LT_LAUNCH_CHECK();
   }
-  if ((e = run_gemm(h, st, w.pooled, HEADS * POOLW, nullptr, 0, 0, h->Watt, h->batt, nullptr, 0, w.att, D, N, DH, POOLW,
-                    ACT_NONE, HEADS, POOLW, (int64_t)DH * POOLW, DH, DH))) return e;
-  if ((e = pipe_boundary(ts.pipe, CUT_POOL, st))) return e;
-#ifdef LINETR_EXPERIMENTS
-  const bool chain = chain_wins(h, N) && !h->sig.empty();
-#else
-  constexpr bool chain = false;
-#endif
-  float *z = w.zA, *zn = w.zB;
+  return run_gemm(h, st, w.pooled, HEADS * POOLW, nullptr, 0, 0, h->Watt, h->batt, nullptr, 0, w.att, D, N, DH, POOLW,
+                  ACT_NONE, HEADS, POOLW, (int64_t)DH * POOLW, DH, DH);
+}
+
+// ---- the descriptive layer's tail (up to CUT_SENTENCE): the sentence rows zA, input of the line-signature network
+int sentence(LinetrHandle* h, hipStream_t& st, int N, FwdWs& w, bool chain) {
+  const LinetrModelConfig& c = h->cfg;
+  int e;
 #ifdef LINETR_EXPERIMENTS
   if (chain) {
     // [fc + LN] -> [w_1, GELU] -> [w_2 + residual + LN (+ line position)] -> [q/k/v of signature layer 0]: one launch
@@ -749,120 +732,99 @@ int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const fl
     cb.add(w.o, D, nullptr, 0, 0, h->Wf1, h->bf1, nullptr, w.f1, N, c.d_inner, D, ACT_GELU);
     cb.add(w.f1, c.d_inner, nullptr, 0, 0, h->Wf2, h->bf2, w.o, w.zA, N, D, c.d_inner, ACT_NONE, &ns2);
     cb.add(w.zA, D, nullptr, 0, 0, h->sig[0].Wqkv, h->sig[0].bqkv, nullptr, w.qkv, N, 3 * D, D, ACT_NONE);
-    if ((e = cb.run(st, "gemm_chain_bf16x6_cls"))) return e;
-  } else
+    return cb.run(st, "gemm_chain_bf16x6_cls");
+  }
 #endif
-  {
   {  // o = LN(fc(att) + cls)  (line_attention.py:36-40; the CLS residual sits in the bias)
     NormSpec ns; ns.mode = 1; ns.gamma = h->ln1g; ns.beta = h->ln1b; ns.eps = 1e-6f;
     if ((e = run_gemm_norm(h, st, w.att, D, nullptr, 0, 0, h->Wfc, h->bfc, nullptr, w.fc, w.o, N, D, ns))) return e;
   }
   if ((e = run_gemm(h, st, w.o, D, nullptr, 0, 0, h->Wf1, h->bf1, nullptr, 0, w.f1, c.d_inner, N, c.d_inner, D, ACT_GELU))) return e;
-  {  // sentence = line_pos + LN(w_2(gelu(w_1 o)) + o)  (line_attention.py:79-83, line_transformer.py:128)
-    NormSpec ns; ns.mode = 1; ns.gamma = h->ln2g; ns.beta = h->ln2b; ns.add2 = w.lpos; ns.eps = 1e-6f;
-    if ((e = run_gemm_norm(h, st, w.f1, c.d_inner, nullptr, 0, 0, h->Wf2, h->bf2, w.o, w.f2, w.zA, N, c.d_inner, ns))) return e;
+  // sentence = line_pos + LN(w_2(gelu(w_1 o)) + o)  (line_attention.py:79-83, line_transformer.py:128)
+  NormSpec ns; ns.mode = 1; ns.gamma = h->ln2g; ns.beta = h->ln2b; ns.add2 = w.lpos; ns.eps = 1e-6f;
+  return run_gemm_norm(h, st, w.f1, c.d_inner, nullptr, 0, 0, h->Wf2, h->bf2, w.o, w.f2, w.zA, N, c.d_inner, ns);
+}
+
+// one signature layer's attention, q/k/v rows at qkv (row stride ldq) -> msg: exact-fp32 MFMA attention in f32 mode, fp32-faithful
+// split-bf16 (6 products) otherwise.  small: few (image, head) pairs, 32-query blocks whose 4 waves also split the KV range (a single
+// pair spreads over 56 CUs and the critical path is 2 KV chunks instead of 7); the only kernel that takes ldq != 3 D.
+int sig_attention(LinetrHandle* h, hipStream_t st, const float* qkv, int ldq, const int* cu_dev, int n_images, int N, int max_n,
+                  double fl, bool small, float* msg) {
+  if (h->precision == LINETR_PREC_F32) {
+    ProfScope ps(h, st, "sig_attn", fl, (double)N * D * 16);
+    hipLaunchKernelGGL(sig_attn_kernel, dim3(n_images, HEADS, cdiv(max_n, ATT_QT)), dim3(256), 0, st, qkv, cu_dev, msg);
+  } else {
+    ProfScope ps(h, st, "sig_attn_bf16x6", fl, (double)N * D * 16);
+    if (small)
+      // (r04: an eight-wave form -- one key chunk per wave, K fragments straight from global memory -- measured level with this
+      // one, 12.6 us per launch for a cfg2 pair either way, and was not kept)
+      hipLaunchKernelGGL(sig_attn_small_kernel, dim3(n_images, HEADS, cdiv(max_n, 32)), dim3(256), 0, st, qkv, cu_dev, msg, ldq);
+    else if (max_n <= 128)
+      hipLaunchKernelGGL(sig_attn_split_kernel<4>, dim3(n_images, HEADS, cdiv(max_n, ATT_QT)), dim3(256), 0, st, qkv, cu_dev, msg);
+    else
+      hipLaunchKernelGGL(sig_attn_split_kernel<8>, dim3(n_images, HEADS, cdiv(max_n, 256)), dim3(512), 0, st, qkv, cu_dev, msg);
   }
-  }
-  // ---- line signature network
-  if ((e = pipe_boundary(ts.pipe, CUT_SENTENCE, st))) return e;
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+// ---- line-signature network + final projection and L2 normalisation (CUT_SIG0 + l behind layer l).
+// models/line_transformer.py:132-183, 245-246
+int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const int32_t* h_cu, const int* cu_dev, int n_images, int N,
+                float* d_line_desc, FwdWs& w, bool pairnet, bool chain) {
+  const LinetrModelConfig& c = h->cfg;
+  int max_n = 0;
+  for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
+  int e;
 #ifdef LINETR_EXPERIMENTS
   if (pairnet && !chain) return pairnet_run(h, st, w.zA, d_line_desc, h_cu, n_images, N, w.pn);
-#endif
   // LINETR_SIG_PATH=st (experiment): activations stay in HBM as split-tile images and every K step travels by LDS-DMA
   // (lt_gemm_st.h, lt_attn_st.h).  Measured at cfg3 on one box: the ST GEMMs are 5-7 % faster than the register-staged
   // ones in isolation, but inside the step the 6-byte activations cost more at the kernel boundaries (the L2 write-back of
   // 273 MB instead of 182 MB of fresh activations per layer) than the main loops save: 2.92 vs 2.69 ms per step.
-#ifdef LINETR_EXPERIMENTS
   const char* sig_path = LT_XENV("LINETR_SIG_PATH");      // read per call (tests switch it)
   if (!chain && h->precision == LINETR_PREC_BF16X6 && !h->sig.empty() && sig_path && !strcmp(sig_path, "st"))
     return sig_network_st(h, st, w, h_cu, cu_dev, n_images, N, max_n, d_line_desc);
-#endif
-  const int qtiles = cdiv(max_n, ATT_QT);
-  const int64_t sig_bn_off = 4 * (int64_t)(e0 + e1 + e2 + e3);   // the signature layers' slots behind the two encoders' in the packed statistics
   // layers but the last: W1 -> ReLU -> W2 + residual in one kernel, hidden activations in registers (lt_mlp_fused.h)
-#ifdef LINETR_EXPERIMENTS
   const bool fused_sig_mlp = h->precision != LINETR_PREC_F32 && N >= 4096 && !LT_XENV("LINETR_NO_FUSED_SIG_MLP") &&
                              LT_XENV("LINETR_FUSED_SIG_MLP") != nullptr;   // opt-in: measured slower
 #endif
-  // single-pair sizes (the 32-query attention below is taken): x_out and the NEXT layer's q/k/v come out of ONE contraction over
+  const double attn_fl = attn_flops(h_cu, n_images);
+  // the signature layers' slots behind the two encoders' in the packed BatchNorm statistics
+  const int64_t sig_bn_off = 4 * (int64_t)(c.enc_channels[0] + c.enc_channels[1] + c.enc_channels[2] + c.enc_channels[3]);
+  const bool small_attn = h->precision != LINETR_PREC_F32 && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
+  // single-pair sizes (the 32-query attention is taken): x_out and the NEXT layer's q/k/v come out of ONE contraction over
   // [z ; hid] (SigLayer::Wnext) -- one dependent launch less per layer where a launch costs more than its flops
-  const bool small_attn = h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_ATTN_F32") && !LT_XENV("LINETR_ATTN_4WAVE") &&
-                          !LT_XENV("LINETR_NO_SMALL_ATTN") && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
   const bool fold_next = !chain && small_attn && N <= SIG_FOLD_MAX_ROWS && !LT_XENV("LINETR_NO_SIG_FOLD");
-  const float* qkv_in = w.qkv;     // where the current layer's q/k/v sit, and their row stride
-  int ldq = 3 * D, ldz = D;        // (z's row stride: D, or 4 D when z is the head of a [x_out | q/k/v] row)
-  float *zq = w.zqA, *zq_next = w.zqB;
-  const float* zc = z;             // the layer's input rows
+  // q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h): images of up to 256 sub-lines, and
+  // enough (image, head) blocks to fill the chip; q, k, v never reach HBM
+  const bool fused_qkv_attn = !fold_next && !chain && !LT_XENV("LINETR_NO_FUSED_QKV_ATTN") && h->precision == LINETR_PREC_BF16X6 &&
+                              max_n <= 256 && (int64_t)n_images * HEADS >= 128;
+  float *z = w.zA, *zn = w.zB;     // the layer's input rows (row stride ldz) and the next layer's
+  int ldz = D;
+  float *zq = w.zqA, *zq_next = w.zqB;   // fold_next: [x_out | q/k/v of the next layer] rows; z is the head of one (ldz = 4 D)
+  const float* qkv = w.qkv;        // where the layer's q/k/v sit, and their row stride
+  int ldq = 3 * D;
   for (size_t l = 0; l < h->sig.size(); ++l) {
     const SigLayer& S = h->sig[l];
-    if (fold_next) {
-      if (l == 0) {
-        if ((e = run_gemm(h, st, zc, ldz, nullptr, 0, 0, S.Wqkv, S.bqkv, nullptr, 0, w.qkv, 3 * D, N, 3 * D, D, ACT_NONE))) return e;
-      }
-      {
-        double fl = 0;
-        for (int i = 0; i < n_images; ++i) { double n = h_cu[i + 1] - h_cu[i]; fl += 2.0 * 2.0 * n * n * D; }
-        ProfScope ps(h, st, "sig_attn_bf16x6", fl, (double)N * D * 16);
-        hipLaunchKernelGGL(sig_attn_small_kernel, dim3(n_images, HEADS, cdiv(max_n, 32)), dim3(256), 0, st, qkv_in, cu_dev, w.msgp, ldq);
-        LT_LAUNCH_CHECK();
-      }
-      if ((e = run_gemm(h, st, zc, ldz, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ts.bn ? ACT_NONE : ACT_RELU))) return e;
-      if (ts.bn && (e = bn_train_layer(st, *ts.bn, w.hid, N, 2 * D, 2 * D, h->bn_g[8 + l], h->bn_b[8 + l], sig_bn_off + (int64_t)l * 4 * D))) return e;
-      if (l + 1 == h->sig.size()) break;
-      if ((e = run_gemm(h, st, zc, ldz, w.hid, 2 * D, D, S.Wnext, S.bnext, nullptr, 0, zq, 4 * D, N, 4 * D, 3 * D, ACT_NONE))) return e;
-      zc = zq; ldz = 4 * D; qkv_in = zq + D; ldq = 4 * D;
-      std::swap(zq, zq_next);
-      if ((e = pipe_boundary(ts.pipe, CUT_SIG0 + (int)l, st))) return e;
-      continue;
-    }
-    // q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h): images of up to 256 sub-lines, and
-    // enough (image, head) blocks to fill the chip; q, k, v never reach HBM
-    const bool no_fqa = LT_XENV("LINETR_NO_FUSED_QKV_ATTN") != nullptr;     // A/B switch (experiments build; read per call)
-    if (!chain && !no_fqa && h->precision == LINETR_PREC_BF16X6 && max_n <= 256 && (int64_t)n_images * HEADS >= 128) {
+    if (fused_qkv_attn) {
       auto it = h->split.find(S.Wqkv);
       if (it == h->split.end() || !it->second.offst) return fail(LINETR_E_ARG, "signature layer: q/k/v weight has no split-tile image");
-      double fl = 2.0 * N * 3.0 * D * D;
-      for (int i = 0; i < n_images; ++i) { double n = h_cu[i + 1] - h_cu[i]; fl += 2.0 * 2.0 * n * n * D; }
       static unsigned long long attr_done = 0;
       const unsigned long long dev_bit = current_device_bit();
       if (!(attr_done & dev_bit)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sig_qkv_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FQA_LDS);
         attr_done |= dev_bit;
       }
-      ProfScope ps(h, st, "sig_qkv_attn_bf16x6", fl, (double)N * D * 8);
+      ProfScope ps(h, st, "sig_qkv_attn_bf16x6", 2.0 * N * 3.0 * D * D + attn_fl, (double)N * D * 8);
       hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, h->split_arena + it->second.offst,
                          S.bqkv, cu_dev, w.msgp);
       LT_LAUNCH_CHECK();
     } else {
-    if (!chain)
-      if ((e = run_gemm(h, st, z, D, nullptr, 0, 0, S.Wqkv, S.bqkv, nullptr, 0, w.qkv, 3 * D, N, 3 * D, D, ACT_NONE))) return e;
-    {
-      double fl = 0;
-      for (int i = 0; i < n_images; ++i) { double n = h_cu[i + 1] - h_cu[i]; fl += 2.0 * 2.0 * n * n * D; }
-      // exact-fp32 MFMA attention in f32 mode, fp32-faithful split-bf16 (6 products) otherwise
-      static const bool force_f32_attn = LT_XENV("LINETR_ATTN_F32") != nullptr;
-      if (h->precision == LINETR_PREC_F32 || force_f32_attn) {
-        ProfScope ps(h, st, "sig_attn", fl, (double)N * D * 16);
-        hipLaunchKernelGGL(sig_attn_kernel, dim3(n_images, HEADS, qtiles), dim3(256), 0, st, w.qkv, cu_dev, w.msgp);
-      } else {
-        ProfScope ps(h, st, "sig_attn_bf16x6", fl, (double)N * D * 16);
-        static const bool attn4 = LT_XENV("LINETR_ATTN_4WAVE") != nullptr;   // tuning aid: 128-query blocks
-        // few (image, head) pairs: 64-query blocks, so that a single pair still spreads over 32 CUs instead of 8
-        static const bool no_small_attn = LT_XENV("LINETR_NO_SMALL_ATTN") != nullptr;   // tuning aid
-        // few (image, head) pairs: 32-query blocks whose 4 waves also split the KV range (a single pair spreads over 56 CUs
-        // and the critical path is 2 KV chunks instead of 7)
-        if (!attn4 && !no_small_attn && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64)
-          // (r04: an eight-wave form -- one key chunk per wave, K fragments straight from global memory -- measured level with this
-          // one, 12.6 us per launch for a cfg2 pair either way, and was not kept)
-          hipLaunchKernelGGL(sig_attn_small_kernel, dim3(n_images, HEADS, cdiv(max_n, 32)), dim3(256), 0, st, w.qkv, cu_dev, w.msgp, 3 * D);
-        else if (attn4 || max_n <= 128)
-          hipLaunchKernelGGL(sig_attn_split_kernel<4>, dim3(n_images, HEADS, qtiles), dim3(256), 0, st, w.qkv, cu_dev, w.msgp);
-        else
-          hipLaunchKernelGGL(sig_attn_split_kernel<8>, dim3(n_images, HEADS, cdiv(max_n, 256)), dim3(512), 0, st, w.qkv, cu_dev,
-                             w.msgp);
-      }
-      LT_LAUNCH_CHECK();
-    }
+      // (a chain, or with fold_next the previous layer, has made them already)
+      if (!chain && (!fold_next || l == 0))
+        if ((e = run_gemm(h, st, z, ldz, nullptr, 0, 0, S.Wqkv, S.bqkv, nullptr, 0, w.qkv, 3 * D, N, 3 * D, D, ACT_NONE))) return e;
+      if ((e = sig_attention(h, st, qkv, ldq, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
     }
 #ifdef LINETR_EXPERIMENTS
     if (chain) {
@@ -883,8 +845,7 @@ int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const fl
       // last layer: W1 -> [final projection with W2 folded in] -> L2 normalisation
       NormSpec nl2; nl2.mode = 2;
       cb.add(z, D, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, d_line_desc, N, D, 3 * D, ACT_NONE, &nl2);
-      if ((e = cb.run(st, "gemm_chain_bf16x6_final"))) return e;
-      return LINETR_OK;
+      return cb.run(st, "gemm_chain_bf16x6_final");
     }
     if (fused_sig_mlp && l + 1 < h->sig.size()) {
       if ((e = run_sig_mlp(h, st, z, w.msgp, S, zn, N))) return e;
@@ -892,23 +853,46 @@ int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const fl
       continue;
     }
 #endif
-    if ((e = run_gemm(h, st, z, D, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ts.bn ? ACT_NONE : ACT_RELU))) return e;
+    if ((e = run_gemm(h, st, z, ldz, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ts.bn ? ACT_NONE : ACT_RELU))) return e;
     if (ts.bn && (e = bn_train_layer(st, *ts.bn, w.hid, N, 2 * D, 2 * D, h->bn_g[8 + l], h->bn_b[8 + l], sig_bn_off + (int64_t)l * 4 * D))) return e;
     if (l + 1 == h->sig.size()) break;   // the last layer's second MLP GEMM is folded into the final projection below
-    if ((e = run_gemm(h, st, w.hid, 2 * D, nullptr, 0, 0, S.W2, S.b2, z, D, zn, D, N, D, 2 * D, ACT_NONE))) return e;
-    std::swap(z, zn);
+    if (fold_next) {
+      if ((e = run_gemm(h, st, z, ldz, w.hid, 2 * D, D, S.Wnext, S.bnext, nullptr, 0, zq, 4 * D, N, 4 * D, 3 * D, ACT_NONE))) return e;
+      z = zq; ldz = 4 * D; qkv = zq + D; ldq = 4 * D;
+      std::swap(zq, zq_next);
+    } else {
+      if ((e = run_gemm(h, st, w.hid, 2 * D, nullptr, 0, 0, S.W2, S.b2, z, D, zn, D, N, D, 2 * D, ACT_NONE))) return e;
+      std::swap(z, zn);
+    }
     if ((e = pipe_boundary(ts.pipe, CUT_SIG0 + (int)l, st))) return e;
   }
   NormSpec l2; l2.mode = 2;      // F.normalize(final_proj(.), dim=1)  (line_transformer.py:245-246)
-  if (h->sig.empty()) {
-    if ((e = run_gemm_norm(h, st, z, D, nullptr, 0, 0, h->Wfin, h->bfin, nullptr, zn, d_line_desc, N, D, l2))) return e;
-  } else {
-    // final_proj(z + W2 hid + b2) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin): one K = 768 GEMM instead of two launches
-    if (!fold_next) { zc = z; ldz = D; }
-    if ((e = run_gemm_norm(h, st, zc, ldz, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, zn, d_line_desc, N, 3 * D, l2))) return e;
-  }
-  return LINETR_OK;
+  if (h->sig.empty()) return run_gemm_norm(h, st, z, D, nullptr, 0, 0, h->Wfin, h->bfin, nullptr, zn, d_line_desc, N, D, l2);
+  // final_proj(z + W2 hid + b2) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin): one K = 768 GEMM instead of two launches
+  return run_gemm_norm(h, st, z, ldz, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, zn, d_line_desc, N, 3 * D, l2);
 }
+
+int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const float* sublines, const float* resp,
+                 const float* angle_sub, const int32_t* h_cu, const int* cu_dev, int n_images, int N, int T,
+                 float* d_line_desc, FwdWs& w) {
+  int e;
+  bool pairnet = false, chain = false;
+#ifdef LINETR_EXPERIMENTS
+  // experiment (LINETR_PAIRNET=1; measured and not shipped, DESIGN.md 12): the whole signature network of a single pair as ONE
+  // persistent launch (lt_pairnet.h); its arrival counters are zeroed here, far ahead of it on the stream
+  pairnet = pairnet_fits(h, n_images, N, h_cu);
+  if (pairnet && (e = pairnet_prepare(h, st, N, w.pn))) return e;
+  chain = chain_wins(h, N) && !h->sig.empty();
+#endif
+  if ((e = pos_encoders(h, st, ts, sublines, resp, angle_sub, N, w))) return e;
+  if ((e = pipe_boundary(ts.pipe, CUT_MLP, st))) return e;
+  if ((e = cls_pooling(h, st, ts, n_images, N, T, w))) return e;
+  if ((e = pipe_boundary(ts.pipe, CUT_POOL, st))) return e;
+  if ((e = sentence(h, st, N, w, chain))) return e;
+  if ((e = pipe_boundary(ts.pipe, CUT_SENTENCE, st))) return e;
+  return sig_network(h, st, ts, h_cu, cu_dev, n_images, N, d_line_desc, w, pairnet, chain);
+}
+
 
 int check_cu(const int32_t* h_cu, int n_images) {
   if (!h_cu || n_images < 1) return fail(LINETR_E_ARG, "null / empty cu_sub");

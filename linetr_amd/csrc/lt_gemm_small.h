@@ -174,14 +174,12 @@ template <int PL, int FMT>
 inline void gemm_split_small_launch(const SplitGemmArgs& sa, int groups, hipStream_t st) {
   dim3 grid((unsigned)((sa.g.N / 32) * cdiv(sa.g.M, 32)), (unsigned)groups);
   // K >= 256: eight waves split K (half the loads, splits and MFMAs on every wave's critical path)
-  static const bool w4 = LT_XENV("LINETR_SMALL_GEMM_4WAVE") != nullptr;   // tuning aid
-  static const bool no2 = LT_XENV("LINETR_SMALL_GEMM_NO_2PERCU") != nullptr;   // tuning aid
   // the 8-wave block claims 121 KB of LDS = one block per CU: a grid of 257..512 blocks (q/k/v of a single pair: 312) would
   // run two rounds; four waves with one staging buffer (62 KB) put two blocks on a CU and finish it in one
   const int64_t blocks = (int64_t)grid.x * grid.y;
-  if (!no2 && !w4 && sa.g.K >= 256 && blocks > 256 && blocks <= 512)
+  if (sa.g.K >= 256 && blocks > 256 && blocks <= 512)
     hipLaunchKernelGGL((gemm_split_small_kernel<PL, FMT, 4, 1>), grid, dim3(256), 0, st, sa);
-  else if (!w4 && sa.g.K >= 256) hipLaunchKernelGGL((gemm_split_small_kernel<PL, FMT, 8>), grid, dim3(512), 0, st, sa);
+  else if (sa.g.K >= 256) hipLaunchKernelGGL((gemm_split_small_kernel<PL, FMT, 8>), grid, dim3(512), 0, st, sa);
   else hipLaunchKernelGGL((gemm_split_small_kernel<PL, FMT, 4>), grid, dim3(256), 0, st, sa);
 }
 

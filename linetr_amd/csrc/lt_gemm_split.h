@@ -662,11 +662,10 @@ inline void gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t
   constexpr size_t lds_epi = (size_t)BM * BN * sizeof(float);    // every wave's TM x TN accumulator tile
   constexpr bool epi_fits = lds_epi <= 160 * 1024;
   constexpr size_t lds = (epi_fits && lds_epi > lds_main) ? lds_epi : lds_main;
-  static const bool narrow = LT_XENV("LINETR_GEMM_NARROW_EPI") != nullptr;   // tuning aid: direct dword stores
   SplitGemmArgs sa2 = sa;
   // the LDS epilogue needs 16-byte aligned rows (ldy / ldr multiples of 4 floats; the entry points guarantee it for
   // their own buffers, debug_gemm checks it)
-  sa2.wide_epi = !narrow && sa.g.ldy % 4 == 0 && (!sa.g.R || sa.g.ldr % 4 == 0) && epi_fits;
+  sa2.wide_epi = sa.g.ldy % 4 == 0 && (!sa.g.R || sa.g.ldr % 4 == 0) && epi_fits;
   static unsigned long long attr_done = 0;   // one bit per device: the opt-in is a per-device function attribute
   const unsigned long long dev_bit = current_device_bit();
   if (!(attr_done & dev_bit)) {
@@ -733,23 +732,21 @@ inline bool small_gemm_wins(const GemmArgs& g, int groups);
 inline const char* split_tile_name(const GemmArgs& g, int groups, int pl = 3) {
   if (small_gemm_wins(g, groups)) return "32x32k4";   // latency-bound sizes: barrier-free K-split kernel
   if (g.N % 128 != 0) return "128x64";
-  static const bool no112 = LT_XENV("LINETR_NO_TILE112") != nullptr;   // tuning aid
-  if (!no112 && pl == 2 && split16_wins(g, groups)) return "112x256";   // saves a round of blocks (lt_gemm_split16.h)
+  if (pl == 2 && split16_wins(g, groups)) return "112x256";   // saves a round of blocks (lt_gemm_split16.h)
   const int64_t r128 = cdiv(g.M, 128), r64 = cdiv(g.M, 64);
   // short K, wide N, many tiles: the single-buffered 128x128 tile (64 KB of LDS, eight waves at 102 VGPRs: two blocks =
   // 4 waves per SIMD whose prologues / epilogues overlap each other's main loops) beats the one-block-per-CU pipeline:
   // 25472x768x256 73 vs 80 us, 291208x256x128 (the word-MLP layer) 192 vs 225 us; in the cfg3 step its nine launches take
   // 0.75 ms (0.85 ms with the earlier four-wave layout at 212 VGPRs = 2 waves per SIMD).  For the other shapes the two
   // tiles are level inside the step.
-  static const bool no128s = LT_XENV("LINETR_NO_TILE128S") != nullptr;   // tuning aid
   // r04 (profiles/r04_tiles_probe.txt): with K <= 256 and N >= 768 it already wins from ~400 tiles (9584 rows, cfg5 at 8 pairs:
   // 9584x1024x256 45.6 vs 55.4 us, 9584x768x256 30.0 vs 31.8 us)
   const int64_t t128 = r128 * (g.N / 128) * groups;
-  if (!no128s && pl == 3 && ((g.K <= 256 && g.N >= 768 && t128 >= 400) || (g.K <= 128 && t128 >= 1024))) return "128x128s";
+  if (pl == 3 && ((g.K <= 256 && g.N >= 768 && t128 >= 400) || (g.K <= 128 && t128 >= 1024))) return "128x128s";
   if (g.N % 256 == 0 && r128 * (g.N / 256) * groups >= 140) return "128x256";
   // r04 probe, 9584 rows x N = 256 (75 row tiles: too few 128 x 256 blocks): two 128 x 128 s blocks per CU beat the 64 x 64 tile for
   // K <= 512 (27.7 vs 29.5 us at K = 512, 17.0 vs 18.0 at K = 256); at K = 1024 the tiles are level
-  if (!no128s && pl == 3 && g.K <= 512 && t128 >= 140) return "128x128s";
+  if (pl == 3 && g.K <= 512 && t128 >= 140) return "128x128s";
   if (g.N % 256 != 0 && (int64_t)cdiv(g.M, 256) * (g.N / 128) * groups >= 192) return "256x128";
   if (r64 * (g.N / 64) * groups <= 768) return "64x64";
   if (r64 * (g.N / 128) * groups <= 512) return "64x128";
@@ -768,21 +765,13 @@ inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, hipStream_t st
   // the launcher is authoritative about the fused row normalisation: only the 128x256 tile with the LDS epilogue owns
   // complete rows of an N = 256 problem; anything else would silently skip the normalisation
   if (g.norm != 0) {
-    static const bool narrow_env = LT_XENV("LINETR_GEMM_NARROW_EPI") != nullptr;
-    if (strcmp(tile, "128x256") != 0 || g.N != 256 || narrow_env || g.ldy % 4 != 0 || (g.R && g.ldr % 4 != 0))
+    if (strcmp(tile, "128x256") != 0 || g.N != 256 || g.ldy % 4 != 0 || (g.R && g.ldr % 4 != 0))
       return fail(LINETR_E_ARG, "gemm_split: fused row normalisation asked of tile %s (N=%d): dispatcher bug", tile, g.N);
   }
   if (!strcmp(tile, "32x32k4")) gemm_split_small_launch<PL, FMT>(sa, groups, st);
   else if (!strcmp(tile, "112x256")) gemm_split16_launch<PL, FMT>(sa, st);
   else if (g.N % 128 != 0 || !strcmp(tile, "128x64")) gemm_split_launch_t<128, 64, 4, 1, PL, true, FMT>(sa, groups, st);
-  else if (!strcmp(tile, "256x128")) {
-#ifdef LINETR_EXPERIMENTS
-    static const bool nopipe = LT_XENV("LINETR_GEMM_NOPIPE") != nullptr;   // tuning aid: the pre-pipelining main loop
-    if (nopipe) gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT>(sa, groups, st);
-    else
-#endif
-    gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT, 1, true>(sa, groups, st);
-  }
+  else if (!strcmp(tile, "256x128")) gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT, 1, true>(sa, groups, st);
   // (16 waves of 32 x 64 or 64 x 32 on this tile, without the software pipeline, run the cfg3 step within noise of this
   // one: at one block per CU the extra waves meet at the same barriers)
   else if (!strcmp(tile, "128x256") && g.N % 256 == 0) gemm_split_launch_t<128, 256, 2, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st);
@@ -790,14 +779,7 @@ inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, hipStream_t st
   else if (!strcmp(tile, "128x128")) gemm_split_launch_t<128, 128, 2, 2, PL, true, FMT>(sa, groups, st);
   // single LDS buffer, EIGHT waves of 64 x 32 (102 VGPRs): two blocks = 4 waves per SIMD.  With four waves of 64 x 64
   // (212 VGPRs, 2 waves per SIMD) 25472x768x256 took 76.4 us (now 73.2), 291208x256x128 206 us (now 192)
-  else if (!strcmp(tile, "128x128s")) {
-#ifdef LINETR_EXPERIMENTS
-    static const bool w4 = LT_XENV("LINETR_TILE128S_4WAVE") != nullptr;   // tuning aid: the four-wave layout
-    if (w4) gemm_split_launch_t<128, 128, 2, 2, PL, false, FMT>(sa, groups, st);
-    else
-#endif
-    gemm_split_launch_t<128, 128, 2, 4, PL, false, FMT>(sa, groups, st);
-  }
+  else if (!strcmp(tile, "128x128s")) gemm_split_launch_t<128, 128, 2, 4, PL, false, FMT>(sa, groups, st);
 #ifdef LINETR_EXPERIMENTS
   else if (PL == 2 && !strcmp(tile, "256x256") && g.N % 256 == 0) gemm_split_launch_t<256, 256, 4, 2, 2, true, FMT>(sa, groups, st);
 #endif

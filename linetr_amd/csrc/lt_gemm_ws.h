@@ -12,7 +12,7 @@
 //   * the accumulators start at the bias (kept in LDS); a half-wave swap per register pair leaves a lane with two runs of 8
 //     consecutive channels of its token: ReLU and four dwordx4 stores, no LDS in the epilogue, and the epilogue of one 32-token
 //     half runs in the MFMA slots of the other.  A wave writes complete 128-byte lines.
-// cfg3 (291 208 rows, tools/ubench/ws_gemm_bench.hip): 110-114 us = 170 TF-eq, 4.0 TB/s of its 447 MB; the tiled kernel it replaces:
+// cfg3 (291 208 rows; HISTORY.md 10.3c): 110-114 us = 170 TF-eq, 4.0 TB/s of its 447 MB; the tiled kernel it replaces:
 // 187 us.  Ablations: no MFMAs 96 us (the memory side alone: the kernel sits 15 % above it), no loads and no stores 92 us (MFMAs + LDS
 // fragment reads: eight waves each read the whole tile, 50 % of the LDS read bandwidth), neither 31 us.  Plain stores: write-through
 // (sc1) or nontemporal ones double the time (a wave writes 32-byte runs; the L2 has to merge them into lines).

@@ -21,7 +21,7 @@
 // (25 472 rows): 29 against 16.5 + 23 us; a single pair (4 378 / 398 rows): 15.7 us each, mostly the weight prologue, against 21 us each.  A software-pipelined
 // variant (tiles of 32 rows, every image double-buffered, layer 4 of tile s - 3 / layer 3 of s - 2 on waves 4-7 / layer 2 of s - 1 on
 // waves 0-1 / layer 1 of s in ONE barrier interval) was built and measured on the same box: 165 us -- the matrix pipe is not idle
-// for lack of work here, the MFMAs alone take 80 us of layer 4's 110 at the clock the power cap allows (tools/ubench/ws_gemm_bench.hip:
+// for lack of work here, the MFMAs alone take 80 us of layer 4's 110 at the clock the power cap allows (HISTORY.md 10.3d:
 // removing every B-fragment read changes nothing), so filling the A / B / C gaps buys nothing and the extra barriers cost.
 #pragma once
 #include "lt_gemm_ws.h"

@@ -1,5 +1,5 @@
-"""Time one GEMM shape through linetr_debug_gemm with HIP events (used by tools/gemm_skip_sweep.sh, which points
-LINETR_LIB at its ablation builds):   python tools/gemm_time_one.py bf16x6 8192 4096 4096     (LABEL=... names the line)"""
+"""Time one GEMM shape through linetr_debug_gemm with HIP events (LINETR_LIB selects the library, e.g. an A/B build):
+python tools/gemm_time_one.py bf16x6 8192 4096 4096     (LABEL=... names the line)"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
