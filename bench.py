@@ -12,14 +12,21 @@ already resident in HBM in the layout the repo's own producer (linetr_superpoint
 channel-last descriptor map) emits, detected lines are resident on the host.  A "step" is one pass of
 that path over one batch of P synthetic image pairs per GPU (weak scaling: every rank gets its own P
 pairs).  Default workload = cfg3 of BASELINE.json (64 pairs of 640x480, 200 lines -> 199 sub-lines x
-21 tokens per image), the configuration the roofline is defined on.  The same JSON line carries
-`cfg2` (single pair: latency) and `cfg5` (1280x960, 600 lines x 41 tokens) sub-objects, pair-match ms,
-the step fed with the reference's NCHW map, and the CPU baseline.
+21 tokens per image), the configuration the roofline is defined on.
+
+A plain run does only what the headline needs: set-up, settle + W warm-up steps, the K timed steps,
+--dump-outputs if given, and the JSON line (value, ms_per_step, per-step statistics).  --full also
+measures and checks everything else after the timed steps, as extra keys of the same line: pair-match
+ms, the oracle check and argmin margins, the per-kernel profile and roofline, the one-stream step, the
+step fed with the other dense layout, the producer, `cfg2` (single pair: latency), `cfg5` (1280x960,
+600 lines x 41 tokens) and `cfg4` sub-objects, the CPU baseline; with N > 1 the gathered-rows check,
+the collective alone and global matching on the gathered set.
 
 --workload cfg4 runs BASELINE.json's fourth configuration instead: 1024 homography-augmented pairs,
 STRONG-sharded round-robin over the ranks (pair p -> rank p mod R), ONE all-gather of the descriptor
 slabs, then global matching of every local query image against candidates taken from the gathered set;
-a step is the whole job and the JSON carries compute_ms / gather_ms / global_match_ms.
+a step is the whole job and the JSON carries compute_ms / gather_ms / global_match_ms (--full: and the
+recall against the known homographies).
 
 One JSON line is printed by rank 0.
 """
@@ -977,7 +984,6 @@ def run_cfg4(args, eng, device, rank, world, dist):
         elapsed, n_total, phases = float(mx[0]), float(sm[1]), mx[2:].cpu().numpy()
     else:
         n_total = float(n_local)
-    rec = job.recall()
     H, W, n_lines, _, _, T, _ = WORKLOADS["cfg4"]
     out = {
         "metric": "line_descriptors_per_sec", "value": round(n_total * args.steps / elapsed, 1), "unit": "line-descriptors/s",
@@ -993,10 +999,11 @@ def run_cfg4(args, eng, device, rank, world, dist):
         "compute_ms": round(float(phases[0]), 3), "gather_ms": round(float(phases[1]), 3),
         "global_match_ms": round(float(phases[2]), 3),
         "ms_per_step_median": round(float(np.median(per_step)), 3), "host_ms_per_step": round(float(np.median(host_ms)), 3),
-        "recall_vs_homography_rank0": rec,
-        "recall_note": "seeded, untrained weights are not viewpoint-invariant: recall is only meaningful for mild views "
-                       "(--homography-strength 0.05 gives > 0.8; tests/test_gpu_cfg4.py)",
     }
+    if args.full:
+        out["recall_vs_homography_rank0"] = job.recall()
+        out["recall_note"] = ("seeded, untrained weights are not viewpoint-invariant: recall is only meaningful for mild views "
+                              "(--homography-strength 0.05 gives > 0.8; tests/test_gpu_cfg4.py)")
     return out
 
 
@@ -1067,6 +1074,15 @@ def fail_line(msg, world, rank, code=3):
     os._exit(code)
 
 
+def finish(out, rank, world, dist):
+    """rank 0 prints the line; with several ranks every rank leaves the process group together."""
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def preflight(dist, world, rank, device, backend):
     """Before anything is timed on N > 1 ranks: the process group really has N ranks that see each other (an all-reduce of ones and an
     all-gather of the rank ids through the SAME backend the benchmark uses), and -- unless the one-device test hook is on -- every rank
@@ -1128,13 +1144,17 @@ def main():
                     help="batches in flight: 2-4 = consecutive steps as the software pipeline (linetr_describe_submit / _join: the front "
                          "of step i + 1 under the signature network of step i, full batch in every GEMM); 0: one step after the other on one stream")
     ap.add_argument("--settle-s", type=float, default=2.0, help="minimum seconds of load before anything is timed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline (profile and roofline, oracle "
+                         "check, matcher, other layout, producer, cfg2 / cfg5 / cfg4 sub-objects, CPU baseline; N > 1: gathered-rows "
+                         "check, collective alone, global match; cfg4: recall)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle check")
     ap.add_argument("--alt-precisions", action="store_true",
-                    help="also time the step in the other MFMA modes (their fast kernels differ from bf16x6's: not a like-for-like "
+                    help="--full: also time the step in the other MFMA modes (their fast kernels differ from bf16x6's: not a like-for-like "
                          "cost of the six products, so no longer part of the default line)")
-    ap.add_argument("--no-sub-workloads", action="store_true", help="skip the cfg2 / cfg5 / cfg4 sub-objects")
-    ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg4 sub-object (the 1024-pair job on this GPU) of the default line")
-    ap.add_argument("--cpu-budget", type=float, default=14.0)
+    ap.add_argument("--no-sub-workloads", action="store_true", help="--full: skip the cfg2 / cfg5 / cfg4 sub-objects")
+    ap.add_argument("--no-cfg4", action="store_true", help="--full: skip the cfg4 sub-object (the 1024-pair job on this GPU)")
+    ap.add_argument("--cpu-budget", type=float, default=14.0, help="--full: seconds of the CPU baseline's thread sweep")
     ap.add_argument("--pairs-total", type=int, default=1024, help="cfg4: pairs of the whole job")
     ap.add_argument("--candidates", type=int, default=4, help="cfg4: gathered candidate images matched per query image")
     ap.add_argument("--homography-strength", type=float, default=1.0, help="cfg4: 1 = the yaml's recipe, <1 milder views")
@@ -1187,11 +1207,7 @@ def main():
     if args.workload == "cfg4":
         out = run_cfg4(args, eng, device, rank, world, dist)
         out["preflight"] = pre
-        if rank == 0:
-            print(json.dumps(out), flush=True)
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
+        finish(out, rank, world, dist)
         return
 
     lines, dd_nchw, dd_nhwc, ds, hw, T = make_inputs(args.workload, pairs, rank, device, eng)
@@ -1240,6 +1256,40 @@ def main():
         n_desc_step = float(tb.N)
     ms_per_step = elapsed / args.steps * 1e3
     value = n_desc_step * args.steps / elapsed
+    n_img = 2 * pairs
+    out = {
+        "metric": "line_descriptors_per_sec", "value": round(value, 1), "unit": "line-descriptors/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32 (v_mfma_f32_32x32x2_f32)", "bf16x6": "f32 in/out; GEMMs as 6 bf16-split MFMA products, fp32 accumulate (fp32-faithful)",
+                  "bf16x3": "f32 in/out; GEMMs as 3 bf16-split MFMA products, fp32 accumulate (~1e-5)",
+                  "f16x3": "f32 in/out; GEMMs as 3 fp16-split MFMA products, fp32 accumulate (~1e-6)"}[args.precision],
+        "precision": args.precision, "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {pairs} pairs/GPU of {W}x{H}, {n_lines} lines/image -> "
+                               f"{int(tb.N / n_img)} sub-lines x {T} tokens, d_model=256, seeded weights",
+                   "pairs_per_gpu": pairs, "descriptors_per_step": int(n_desc_step),
+                   "dense_layout": args.dense_layout + (" (the reference's 'dense_descriptor' [B,256,H/8,W/8]: the step includes the layout pass; "
+                                                        "fed with the channel-last map the repo's producer linetr_superpoint_heads emits it is "
+                                                        "--full's ms_per_step_fed_nhwc / value_fed_nhwc)" if args.dense_layout == "nchw" else
+                                                        " (channel-last map of the repo's own producer; the reference's layout: --full's value_fed_nchw)"),
+                   "collective": "all_gather(line_desc + counts + key-line maps)" if world > 1 else "none"},
+        "ms_per_step_median": round(float(np.median(per_step)), 4), "ms_per_step_p10": round(float(np.percentile(per_step, 10)), 4),
+        "ms_per_step_p90": round(float(np.percentile(per_step, 90)), 4),
+        "ms_per_step_each": [round(float(v), 3) for v in per_step],
+        "host_ms_each": [round(float(v), 3) for v in host_ms],
+        # median: once the host is a launch queue ahead of the GPU the runtime blocks it for a whole GPU step (host_ms_each)
+        "host_ms_per_step": round(float(np.median(host_ms)), 4),
+        "settle": {"seconds_min": args.settle_s, "windows": len(settle_hist), "first_ms": round(settle_hist[0], 4),
+                   "last3_ms": [round(v, 4) for v in settle_hist[-3:]]},
+        "preflight": pre, "collective_backend": (None if world == 1 else os.environ.get("LINETR_BENCH_BACKEND", "nccl")),
+        "rccl_version": (".".join(str(v) for v in torch.cuda.nccl.version()) if world > 1 and hasattr(torch.cuda, "nccl") else None),
+    }
+    if not args.full:
+        finish(out, rank, world, dist)
+        return
+
+    # ---- --full: everything else, measured and checked after the timed steps --------------------------------------------
     # host side of a step alone (C++ pre-filter on the worker pool; the rest of host_ms_per_step is Python + launches)
     t0 = time.perf_counter()
     for _ in range(10):
@@ -1355,38 +1405,12 @@ def main():
          if k in ("kernel", "avg_launch_us", "launches_per_step", "share_of_gpu_time", "bound", "achieved", "peak", "unit", "frac",
                   "fp32_equivalent_tflops", "traffic", "mfma_busy")}
         for e in prof[1:] if e["ms"] / tot_ms >= 0.03]
-    n_img = 2 * pairs
     alg_flops_step = sum(algorithmic_flops_per_image(int(n), T) for n in np.diff(tb.cu_n))
 
-    out = {
-        "metric": "line_descriptors_per_sec", "value": round(value, 1), "unit": "line-descriptors/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": {"f32": "f32 (v_mfma_f32_32x32x2_f32)", "bf16x6": "f32 in/out; GEMMs as 6 bf16-split MFMA products, fp32 accumulate (fp32-faithful)",
-                  "bf16x3": "f32 in/out; GEMMs as 3 bf16-split MFMA products, fp32 accumulate (~1e-5)",
-                  "f16x3": "f32 in/out; GEMMs as 3 fp16-split MFMA products, fp32 accumulate (~1e-6)"}[args.precision],
-        "precision": args.precision, "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {pairs} pairs/GPU of {W}x{H}, {n_lines} lines/image -> "
-                               f"{int(tb.N / n_img)} sub-lines x {T} tokens, d_model=256, seeded weights",
-                   "pairs_per_gpu": pairs, "descriptors_per_step": int(n_desc_step),
-                   "dense_layout": args.dense_layout + (" (the reference's 'dense_descriptor' [B,256,H/8,W/8]: the step includes the layout pass; "
-                                                        "fed with the channel-last map the repo's producer linetr_superpoint_heads emits it is "
-                                                        "ms_per_step_fed_nhwc / value_fed_nhwc)" if args.dense_layout == "nchw" else
-                                                        " (channel-last map of the repo's own producer; the reference's layout: value_fed_nchw)"),
-                   "collective": "all_gather(line_desc + counts + key-line maps)" if world > 1 else "none"},
-        "ms_per_step_median": round(float(np.median(per_step)), 4), "ms_per_step_p10": round(float(np.percentile(per_step, 10)), 4),
-        "ms_per_step_p90": round(float(np.percentile(per_step, 90)), 4),
-        "ms_per_step_each": [round(float(v), 3) for v in per_step],
-        "host_ms_each": [round(float(v), 3) for v in host_ms],
-        # median: once the host is a launch queue ahead of the GPU the runtime blocks it for a whole GPU step (host_ms_each)
-        "host_ms_per_step": round(float(np.median(host_ms)), 4), "host_prefilter_ms": round(host_prefilter_ms, 4),
-        "settle": {"seconds_min": args.settle_s, "windows": len(settle_hist), "first_ms": round(settle_hist[0], 4),
-                   "last3_ms": [round(v, 4) for v in settle_hist[-3:]]},
+    out.update({
+        "host_prefilter_ms": round(host_prefilter_ms, 4),
         "gathered_rows_checked": gathered_ok, "global_match": global_match, "gather_ms": gather_ms,
-        "gather_ms_per_rank": gather_ms_per_rank, "preflight": pre, "native_collective": native_collective,
-        "collective_backend": (None if world == 1 else os.environ.get("LINETR_BENCH_BACKEND", "nccl")),
-        "rccl_version": (".".join(str(v) for v in torch.cuda.nccl.version()) if world > 1 and hasattr(torch.cuda, "nccl") else None),
+        "gather_ms_per_rank": gather_ms_per_rank, "native_collective": native_collective,
         "pair_match_ms": round(pair_match_ms, 4), "pair_match_latency_ms": round(pair_match_latency_ms, 4),
         "matches_per_step": n_matches, "argmin": argmin, "oracle_check": oracle_chk,
         "whole_step": {**whole_step_executed(prof, prof_steps, ms_per_step),
@@ -1395,7 +1419,7 @@ def main():
                                       "V / W5 after pooling, padding key with multiplicity) executes less -- not a roofline input"},
         "gpu_ms_per_step_profiled": round(tot_ms / prof_steps, 3),
         "roofline": roofline, "kernels": breakdown_of(prof, prof_steps),
-    }
+    })
     if world == 1 and args.pipeline:
         # the same step on ONE stream, step after step (what r01-r05 measured), in the same process on the same inputs
         pipe.drain()
@@ -1481,11 +1505,7 @@ def main():
         # oracle_check and the consistency verdict as the last keys of the last object of the line
         tail_keys = ("recall_mild_views", "global_match_equals_pairwise_call", "oracle_check")
         out["cfg4"] = {**{k: v for k, v in cfg4_obj.items() if k not in tail_keys}, **{k: cfg4_obj[k] for k in tail_keys if k in cfg4_obj}}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out, rank, world, dist)
 
 
 if __name__ == "__main__":

@@ -16,9 +16,9 @@ cd "$(dirname "$0")/.." && mkdir -p "$out"
 export HSA_ENABLE_IPC_MODE_LEGACY=${HSA_ENABLE_IPC_MODE_LEGACY:-0}
 rc=0
 for n in $ns; do
-  timeout 900 python bench.py --gpus $n ${SWEEP_PAIRS:+--pairs $SWEEP_PAIRS} --steps 10 --warmup 3 --settle-s 1 --no-cpu-baseline --no-sub-workloads \
+  timeout 900 python bench.py --full --gpus $n ${SWEEP_PAIRS:+--pairs $SWEEP_PAIRS} --steps 10 --warmup 3 --settle-s 1 --no-cpu-baseline --no-sub-workloads \
       > "$out/cfg3_n$n.json" 2> "$out/cfg3_n$n.log" || { echo "cfg3 N=$n: bench.py failed (see $out/cfg3_n$n.log)"; rc=1; continue; }
-  timeout 900 python bench.py --gpus $n --workload cfg4 --pairs-total ${CFG4_PAIRS:-1024} ${SWEEP_PAIRS:+--pairs $SWEEP_PAIRS} --steps 3 --warmup 1 --settle-s 1 \
+  timeout 900 python bench.py --full --gpus $n --workload cfg4 --pairs-total ${CFG4_PAIRS:-1024} ${SWEEP_PAIRS:+--pairs $SWEEP_PAIRS} --steps 3 --warmup 1 --settle-s 1 \
       > "$out/cfg4_n$n.json" 2> "$out/cfg4_n$n.log" || { echo "cfg4 N=$n: bench.py failed (see $out/cfg4_n$n.log)"; rc=1; continue; }
 done
 python - "$out" $ns <<'PY' || rc=1
