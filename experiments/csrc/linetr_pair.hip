@@ -4,7 +4,7 @@
 #ifdef LINETR_EXPERIMENTS
 #include <algorithm>
 
-#include "lt_handle.h"
+#include "lt_pairnet_host.h"
 #include "lt_pairnet.h"
 
 using namespace lt;

@@ -55,13 +55,21 @@ def test_fused_signature_mlp_equals_two_gemms(eng, monkeypatch, mode):
         plain = plain.clone()
         monkeypatch.delenv("LINETR_NO_FUSED_SIG_MLP", raising=False)
         monkeypatch.setenv("LINETR_FUSED_SIG_MLP", "1")
+        eng.set_profiling(True)
         _, fused = describe(eng, cat, off, dd, ds)
+        prof = {e["name"]: e["calls"] for e in eng.get_profile()}
     finally:
+        eng.set_profiling(False)
         eng.set_precision("bf16x6")
+    assert prof.get(f"sig_mlp_{mode}", 0) > 0, prof      # the fused path ran, not the two GEMMs again
     assert fused.shape == plain.shape and fused.shape[0] == 128 * 199
     tol = {"bf16x6": 1e-6, "bf16x3": 5e-5, "f16x3": 5e-6}[mode]
     assert (fused - plain).abs().max().item() <= tol
     assert ((fused.norm(dim=1) - 1).abs() < 1e-5).all()
+
+
+# the shapes below that take the pipelined 128x256 tile, whose last round of tiles gets a stream-K tail on 256 CUs (lt_gemm_split.h)
+_STREAM_K_TAIL_SHAPES = {(25472, 512, 512), (9584, 512, 512), (25473, 512, 256)}
 
 
 @pytest.mark.parametrize("M,N,K,act", [(25472, 512, 512, 1), (25472, 768, 256, 0), (9584, 512, 512, 2), (25473, 512, 256, 0),
@@ -84,6 +92,10 @@ def test_gemm_stream_k_tail(eng, M, N, K, act, monkeypatch):
     Y0 = eng.debug_gemm(A, W, b, R, act)                 # the plain launch: same products, different summation tree
     assert torch.equal(Y1, Y2)
     assert (Y1 - Y0).abs().max().item() < 1e-4 * max(1.0, Y0.abs().max().item())
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        # the tail was taken exactly where the launcher gives one: it sums the shared tiles' K ranges in another order than the
+        # plain launch, so some bits differ.  The other shapes go to the 128x128s and 64x256 tiles (split_tile_name), which have none.
+        assert torch.equal(Y1, Y0) != ((M, N, K) in _STREAM_K_TAIL_SHAPES), (M, N, K)
     x = A.double() @ W.double().t() + b.double()
     x = [x, torch.relu(x), torch.nn.functional.gelu(x)][act] + R.double()
     assert ((Y1.double() - x).abs().max() / x.abs().max()).item() < 2e-6
@@ -159,7 +171,15 @@ def test_alternative_signature_paths_equal_the_shipped_one(eng, monkeypatch, pat
     plain = plain.clone()
     for k, v in path_env.items():
         monkeypatch.setenv(k, v)
+    eng.set_profiling(True)
     _, alt = describe(eng, cat, off, dd, ds)
+    prof = {e["name"]: e["calls"] for e in eng.get_profile()}
+    eng.set_profiling(False)
+    # the alternative path ran (a dropped switch would compare the shipped path with itself)
+    expect = (["gemm_st_bf16x6_", "sig_attn_st"] if path_env.get("LINETR_SIG_PATH") == "st" else
+              ["gemm_chain_bf16x6_"] if "LINETR_GEMM_CHAIN" in path_env else [])
+    for name in expect:
+        assert any(k.startswith(name) for k in prof), (name, prof)
     assert alt.shape == plain.shape and alt.shape[0] == 128 * 199
     assert (alt - plain).abs().max().item() <= 2e-6
     assert ((alt.norm(dim=1) - 1).abs() < 1e-5).all()

@@ -9,9 +9,6 @@
 #include <thread>
 
 #include "lt_handle.h"
-#ifdef LINETR_EXPERIMENTS
-#include "lt_mlp_fused.h"   // sig_mlp_kperm
-#endif
 
 using namespace lt;
 
@@ -369,14 +366,6 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
     place_w(&S.Wqkv, Wqkv, 3 * D, D, true); place(&S.bqkv, bqkv);
     place_w(&S.W1, W1m, 2 * D, 2 * D); place(&S.b1, b1f);
     place_w(&S.W2, to_d(W2, (size_t)2 * D * D), D, 2 * D); place(&S.b2, to_d(b2, D));
-#ifdef LINETR_EXPERIMENTS
-    {
-      std::vector<double> W2perm((size_t)2 * D * D);
-      for (int o = 0; o < D; ++o)
-        for (int k = 0; k < 2 * D; ++k) W2perm[(size_t)o * 2 * D + k] = W2[(size_t)o * 2 * D + sig_mlp_kperm(k)];
-      place_w(&S.W2p, W2perm, D, 2 * D);
-    }
-#endif
   }
   // x_out = z + W2 hid + b2 (line_transformer.py:180-183) and the next layer's q/k/v projection is linear in x_out (:141-143), so
   //   [x_out ; qkv_next] = [[I, W2], [Wqkv, Wqkv W2]] [z ; hid] + [b2 ; Wqkv b2 + bqkv]                      (float64, once)
@@ -477,6 +466,7 @@ extern "C" void linetr_destroy(LinetrHandle* h) {
   if (h->arena) (void)hipFree(h->arena);
   if (h->split_arena) (void)hipFree(h->split_arena);
   if (h->zeros) (void)hipFree(h->zeros);
+  if (h->w2p_arena) (void)hipFree(h->w2p_arena);
   if (h->sk_ws) (void)hipFree(h->sk_ws);
   if (h->sk_flags) (void)hipFree(h->sk_flags);
   if (h->pn_abort) (void)hipHostFree(h->pn_abort);

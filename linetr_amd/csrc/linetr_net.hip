@@ -1,5 +1,6 @@
 // liblinetr_hip.so, translation unit 2 of 4: tokenise / forward / describe and the diagnostics entry points of the C ABI, the
-// GEMM dispatcher, and every kernel of the descriptor network (csrc/lt_*.h).
+// GEMM dispatcher, and every kernel of the descriptor network (csrc/lt_*.h).  The experiments build adds its paths through a
+// few hooks, defined in experiments/csrc/lt_x_net.h, which this file includes behind sig_network.
 #include <algorithm>
 #include <numeric>
 
@@ -8,22 +9,11 @@
 #include "lt_gemm_split.h"
 #include "lt_gemm_split16.h"
 #include "lt_st_image.h"
-#ifdef LINETR_EXPERIMENTS
-#include "lt_gemm_st.h"
-#include "lt_gemm_ro.h"
-#include "lt_gemm_chain.h"
-#endif
 #include "lt_gemm_small.h"
-#ifdef LINETR_EXPERIMENTS
-#include "lt_mlp_fused.h"
-#endif
 #include "lt_model.h"
 #include "lt_attn_fused.h"
 #include "lt_gemm_ws.h"
 #include "lt_tokmlp.h"
-#ifdef LINETR_EXPERIMENTS
-#include "lt_attn_st.h"
-#endif
 #include "lt_token.h"
 #include "lt_bntrain.h"
 
@@ -59,6 +49,13 @@ struct NormSpec {          // row normalisation that follows a [M,256] GEMM (see
   float eps = 0.f;
 };
 
+// the experiments build's hooks (experiments/csrc/lt_x_net.h)
+#ifdef LINETR_EXPERIMENTS
+int x_gemm(LinetrHandle*, hipStream_t, SplitGemmArgs& sa, const LinetrHandle::SplitW&, int groups, const NormSpec*, double fl, double by, bool& done);
+int x_split_weights(LinetrHandle* H, std::vector<GemmWSpec>& weights);
+int64_t x_ws_bytes(const LinetrHandle* h, int N);
+#endif
+
 int run_gemm(LinetrHandle* h, hipStream_t st, const float* A, int lda, const float* A2, int lda2, int K1,
              const float* W, const float* bias, const float* R, int ldr, float* Y, int ldy, int M, int N,
              int K, int act, int groups = 1, int64_t gA = 0, int64_t gW = 0, int64_t gBias = 0, int64_t gY = 0,
@@ -83,16 +80,8 @@ int run_gemm(LinetrHandle* h, hipStream_t st, const float* A, int lda, const flo
   SplitGemmArgs sa;
   sa.g = g;
 #ifdef LINETR_EXPERIMENTS
-  if (LT_XENV("LINETR_STREAMK")) {   // opt-in experiment (lt_gemm_split.h): the 32 MB workspace is only allocated when asked for
-    if (!h->sk_ws) {
-      constexpr size_t slots = 256, slot_bytes = 128 * 256 * sizeof(float);
-      LT_HIP(hipMalloc((void**)&h->sk_ws, slots * slot_bytes));
-      LT_HIP(hipMalloc((void**)&h->sk_flags, (slots + 1) * sizeof(unsigned)));
-      LT_HIP(hipMemset(h->sk_flags, 0, (slots + 1) * sizeof(unsigned)));
-      LT_HIP(hipDeviceSynchronize());
-    }
-    sa.sk_ws = h->sk_ws; sa.sk_flags = h->sk_flags; sa.sk_epoch = ++h->sk_epoch;
-  }
+  bool done = false;   // hands out the stream-K workspace; done: the row-owner GEMM took the launch
+  if (int e = x_gemm(h, st, sa, it->second, groups, fused_norm, fl, by, done); e || done) return e;
 #endif
   if (h->precision == LINETR_PREC_BF16X3) {
     sa.Wsp = h->split_arena + it->second.off2;
@@ -106,20 +95,6 @@ int run_gemm(LinetrHandle* h, hipStream_t st, const float* A, int lda, const flo
     ProfScope ps(h, st, gemm_class_name(g, groups, "gemm_f16x3"), fl, by);
     return gemm_split_launch<2, 1>(sa, groups, st);
   }
-#ifdef LINETR_EXPERIMENTS
-  // row-owner kernel (lt_gemm_ro.h): 4-wave blocks, two per CU, operands by LDS-DMA.  Measured at cfg3: 117 TF-eq against 137 for
-  // the register-staged tiles (a two-slot ring leaves a DMA one K step to land, and the barrier comes every 48 MFMAs), so opt-in.
-  if (LT_XENV("LINETR_GEMM_RO") != nullptr && groups == 1 && N % 256 == 0 && K % 32 == 0 && it->second.offst && lda % 4 == 0 && ldy % 4 == 0 &&
-      (!A2 || (lda2 % 4 == 0 && K1 % 16 == 0)) && (!R || ldr % 4 == 0) && act != ACT_DIST && cdiv(M, 128) * (N / 256) >= 140) {
-    RoGemmArgs a;
-    a.A1 = A; a.lda1 = lda; a.nk1 = (A2 ? K1 : K) / 16; a.A2 = A2; a.lda2 = lda2; a.nk2 = A2 ? (K - K1) / 16 : 0;
-    a.Wst = h->split_arena + it->second.offst; a.bias = bias ? bias : h->zeros; a.R = R; a.ldr = ldr; a.Y = Y; a.ldy = ldy;
-    a.M = M; a.N = N; a.act = act;
-    if (fused_norm) { a.norm = fused_norm->mode; a.gamma = fused_norm->gamma; a.beta = fused_norm->beta; a.add2 = fused_norm->add2; a.ldadd2 = D; a.eps = fused_norm->eps; }
-    ProfScope ps(h, st, "gemm_bf16x6_ro128x256", fl, by);
-    return gemm_ro_launch(a, st);
-  }
-#endif
   // every token row of the batch through a K = 128 layer: weights stay in registers, rows stream (lt_gemm_ws.h)
   if (groups == 1 && !A2 && !R && !fused_norm && it->second.offst && gemm_ws_fits(M, N, K, lda, ldy, act) && !LT_XENV("LINETR_NO_GEMM_WS")) {
     WsGemmArgs a;
@@ -133,57 +108,6 @@ int run_gemm(LinetrHandle* h, hipStream_t st, const float* A, int lda, const flo
   return gemm_split_launch<3>(sa, groups, st);
 }
 
-#ifdef LINETR_EXPERIMENTS
-// ---- row-tile-local GEMM chains (lt_gemm_chain.h) ----------------------------------------------------------------
-struct ChainBuilder {
-  LinetrHandle* h;
-  ChainArgs c;
-  double flops = 0, bytes = 0;
-  int err = 0;
-  explicit ChainBuilder(LinetrHandle* h_) : h(h_) {}
-  // Y[M,N] = norm(act(A (| A2) W^T + bias) (+ R)) (+ add2)
-  void add(const float* A, int lda, const float* A2, int lda2, int K1, const float* W, const float* bias, const float* R,
-           float* Y, int M, int N, int K, int act, const NormSpec* ns = nullptr) {
-    if (err) return;
-    if (c.n >= CHAIN_MAX) { err = fail(LINETR_E_ARG, "gemm chain: too many stages"); return; }
-    auto it = h->split.find(W);
-    if (it == h->split.end()) { err = fail(LINETR_E_ARG, "gemm chain: weight has no split-bf16 copy"); return; }
-    SplitGemmArgs& sa = c.st[c.n++];
-    sa = SplitGemmArgs{};
-    GemmArgs& g = sa.g;
-    g = GemmArgs{};
-    g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = K1; g.W = W; g.ldw = K; g.bias = bias; g.R = R; g.ldr = N; g.Y = Y; g.ldy = N;
-    g.M = M; g.N = N; g.K = K; g.act = act;
-    if (ns) { g.norm = ns->mode; g.gamma = ns->gamma; g.beta = ns->beta; g.add2 = ns->add2; g.ldadd2 = D; g.eps = ns->eps; }
-    sa.Wsp = h->split_arena + it->second.off3;
-    sa.wide_epi = 1;
-    flops += 2.0 * M * (double)N * K;
-    bytes += 4.0 * ((double)M * K + (double)N * K + (double)M * N);
-  }
-  int run(hipStream_t st, const char* name) {
-    if (err) return err;
-    ProfScope ps(h, st, name, flops, bytes);
-    return gemm_chain_launch(c, st);
-  }
-};
-
-// A chain is one block per 128-row tile for the WHOLE chain: worth it when the row tiles fill the chip in one round (the
-// partly empty second round of a plain launch would be a whole chain long) or there are many rounds.
-bool chain_wins(const LinetrHandle* h, int rows) {
-  // opt-in (read per call): measured at cfg3, 2.70 vs 2.60 ms per step -- a chain keeps 199 of the 256 CUs busy for all of its
-  // stages and the per-tile prologue / epilogue cost, not the launch, is what a GEMM of this size pays
-  if (LT_XENV("LINETR_GEMM_CHAIN") == nullptr || h->precision != LINETR_PREC_BF16X6) return false;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  const int gy = cdiv(rows, 128);
-  return (gy >= 140 && gy <= n_cu) || gy >= 4 * n_cu;
-}
-
-#endif  // LINETR_EXPERIMENTS
 // Y[M,256] = norm(epi(A W^T + bias) (+ R)) (+ add2).  The split-bf16 128x256 tile owns complete rows and normalises them
 // in its epilogue (one launch and one [M,256] round trip less); every other case runs the GEMM into `tmp` and then
 // row_norm_kernel.  Same arithmetic either way.
@@ -206,36 +130,13 @@ int run_gemm_norm(LinetrHandle* h, hipStream_t st, const float* A, int lda, cons
   return 0;
 }
 
-#ifdef LINETR_EXPERIMENTS
-// z' = z + W2 relu(W1 [z ; msg] + b1) + b2 in one launch (split-bf16 modes only)
-int run_sig_mlp(LinetrHandle* h, hipStream_t st, const float* z, const float* msg, const SigLayer& S, float* out, int M) {
-  auto i1 = h->split.find(S.W1), i2 = h->split.find(S.W2p);
-  if (i1 == h->split.end() || i2 == h->split.end()) return fail(LINETR_E_ARG, "sig_mlp: weight has no split copy");
-  SigMlpArgs a;
-  a.z = z; a.ldz = D; a.msg = msg; a.ldm = D; a.b1 = S.b1; a.b2 = S.b2; a.out = out; a.ldo = D; a.M = M;
-  const double fl = 2.0 * M * (2.0 * D * 2 * D + 2.0 * D * D), by = 4.0 * M * 3.0 * D;
-  if (h->precision == LINETR_PREC_BF16X3) {
-    a.W1sp = h->split_arena + i1->second.off2; a.W2sp = h->split_arena + i2->second.off2;
-    ProfScope ps(h, st, "sig_mlp_bf16x3", fl, by);
-    sig_mlp_fused_launch<2, 0>(a, st);
-  } else if (h->precision == LINETR_PREC_F16X3) {
-    a.W1sp = h->split_arena + i1->second.offh; a.W2sp = h->split_arena + i2->second.offh;
-    ProfScope ps(h, st, "sig_mlp_f16x3", fl, by);
-    sig_mlp_fused_launch<2, 1>(a, st);
-  } else {
-    a.W1sp = h->split_arena + i1->second.off3; a.W2sp = h->split_arena + i2->second.off3;
-    ProfScope ps(h, st, "sig_mlp_bf16x6", fl, by);
-    sig_mlp_fused_launch<3, 0>(a, st);
-  }
-  LT_LAUNCH_CHECK();
-  return 0;
-}
-
-#endif  // LINETR_EXPERIMENTS
 }  // namespace
 
 // split-bf16 / fp16 / split-tile copies of the prepared GEMM weights (called once by linetr_create)
-int lt::make_split_copies(LinetrHandle* H, const std::vector<GemmWSpec>& weights) {
+int lt::make_split_copies(LinetrHandle* H, std::vector<GemmWSpec> weights) {
+#ifdef LINETR_EXPERIMENTS
+  if (int e = x_split_weights(H, weights)) return e;
+#endif
   size_t total = 0;
   for (auto& w : weights) {
     LinetrHandle::SplitW sw;
@@ -243,12 +144,8 @@ int lt::make_split_copies(LinetrHandle* H, const std::vector<GemmWSpec>& weights
     sw.off2 = total; total += align_up(w.rows * w.K * 4, 256);
     sw.off3 = total; total += align_up(w.rows * w.K * 6, 256);
     sw.offh = total; total += align_up(w.rows * w.K * 4, 256);
-#ifdef LINETR_EXPERIMENTS
-    const bool want_st = true;
-#else
-    const bool want_st = w.st;                          // the weights that travel by LDS-DMA or stay in registers / LDS
-#endif
-    if (want_st && w.rows % 16 == 0 && w.K % 32 == 0) { total = align_up(total, 1024); sw.offst = total; total += st_bytes(w.rows, w.K); }   // ST image (rows padded to 128)
+    // the weights that travel by LDS-DMA or stay in registers / LDS
+    if (w.st && w.rows % 16 == 0 && w.K % 32 == 0) { total = align_up(total, 1024); sw.offst = total; total += st_bytes(w.rows, w.K); }   // ST image (rows padded to 128)
     H->split[w.W] = sw;
   }
   LT_HIP(hipMalloc((void**)&H->split_arena, total));
@@ -400,9 +297,8 @@ constexpr int SIG_FOLD_MAX_ROWS = 960;
 struct FwdWs {
   float *a1, *a2, *a3, *a4, *pooled, *att, *fc, *o, *f1, *f2, *l1, *l2, *l3, *l4, *lpos, *zA, *zB, *qkv, *msgp, *msg, *hid;
   float *zqA, *zqB;                                // [N][4D] = [x_out | q/k/v of the next layer] (single-pair sizes: SigLayer::Wnext)
-  unsigned char *zsA, *zsB, *qkvs, *msgs, *hids;   // split-tile images of the signature network's activations (experiments: lt_gemm_st.h)
   int* cu;
-  char* pn;                                        // activations + arrival counters of the single-pair persistent network (lt_pairnet.h)
+  char* x = nullptr;                               // experiments build: where its own buffers start (lt_x_net.h)
   int64_t total;
 };
 FwdWs fwd_layout(const LinetrHandle* h, int N, int64_t rows, int n_images, char* base) {
@@ -423,17 +319,9 @@ FwdWs fwd_layout(const LinetrHandle* h, int N, int64_t rows, int n_images, char*
   w.hid = take((int64_t)N * 2 * D);
   const int64_t nq = N <= SIG_FOLD_MAX_ROWS ? (int64_t)N * 4 * D : 0;
   w.zqA = take(nq); w.zqB = take(nq);
-#ifdef LINETR_EXPERIMENTS
-  auto take_st = [&](int cols) { unsigned char* p = (unsigned char*)(base + off); off += align_up(st_bytes(N, cols), 1024); return p; };
-  off = align_up(off, 1024);
-  w.zsA = take_st(D); w.zsB = take_st(D); w.qkvs = take_st(3 * D); w.msgs = take_st(D); w.hids = take_st(2 * D);
-#else
-  w.zsA = w.zsB = w.qkvs = w.msgs = w.hids = nullptr;
-#endif
   w.cu = (int*)take(n_images + 1);
-  w.pn = base + off;
 #ifdef LINETR_EXPERIMENTS
-  off += pairnet_ws_bytes(h, N);                   // 0 for batches the path does not take (too many rows)
+  w.x = base + off; off += x_ws_bytes(h, N);
 #endif
   w.total = off;
   return w;
@@ -501,63 +389,6 @@ double attn_flops(const int32_t* h_cu, int n_images) {
   for (int i = 0; i < n_images; ++i) { const double n = h_cu[i + 1] - h_cu[i]; fl += 2.0 * 2.0 * n * n * D; }
   return fl;
 }
-
-#ifdef LINETR_EXPERIMENTS
-// Signature network on split-tile operands: z -> [q|k|v] -> attention -> W1 [z ; message] -> W2 + z, seven times, then the
-// final projection (with the last W2 folded in) and the L2 normalisation.  models/line_transformer.py:132-183, 245-246.
-int sig_network_st(LinetrHandle* h, hipStream_t st, FwdWs& w, const int32_t* h_cu, const int* cu_dev, int n_images, int N,
-                   int max_n, float* d_line_desc) {
-  auto wst = [&](const float* W) -> const unsigned char* {
-    auto it = h->split.find(W);
-    return (it == h->split.end() || !it->second.offst) ? nullptr : h->split_arena + it->second.offst;
-  };
-  auto gemm = [&](const char* role, const unsigned char* A1, int K1, const unsigned char* A2, int K2, const float* W, const float* bias,
-                  const unsigned char* R, unsigned char* Yst, float* Y, int Nout, int act) -> int {
-    StGemmArgs a;
-    a.A1 = A1; a.nk1 = K1 / 16; a.A2 = A2; a.nk2 = A2 ? K2 / 16 : 0;
-    a.W = wst(W); a.bias = bias ? bias : h->zeros; a.R = R; a.Yst = Yst; a.Y = Y; a.ldy = D; a.M = N; a.N = Nout; a.act = act;
-    if (!a.W) return fail(LINETR_E_ARG, "sig_network_st: weight has no split-tile image");
-    const double K = K1 + (A2 ? K2 : 0);
-    ProfScope ps(h, st, role, 2.0 * N * Nout * K, 6.0 * ((double)N * K + (double)Nout * K + (double)N * Nout));
-    return gemm_st_launch(a, st);
-  };
-  if (st_bytes(N, 3 * D) >= (int64_t)1 << 32) return fail(LINETR_E_ARG, "sig_network_st: batch too large (q/k/v image >= 4 GiB)");
-  int e;
-  {
-    ProfScope ps(h, st, "to_st", 0, (double)N * D * 10);
-    const int64_t thr = st_row_blocks(N) * (D / 16) * 32;
-    hipLaunchKernelGGL(to_st_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st, w.zA, D, N, D / 16, w.zsA);
-    LT_LAUNCH_CHECK();
-  }
-  unsigned char *z = w.zsA, *zn = w.zsB;
-  const double attn_fl = attn_flops(h_cu, n_images);
-  for (size_t l = 0; l < h->sig.size(); ++l) {
-    const SigLayer& S = h->sig[l];
-    if ((e = gemm("gemm_st_bf16x6_qkv", z, D, nullptr, 0, S.Wqkv, S.bqkv, nullptr, w.qkvs, nullptr, 3 * D, ACT_NONE))) return e;
-    {
-      ProfScope ps(h, st, "sig_attn_st", attn_fl, (double)N * D * 24);
-      const bool occ1 = LT_XENV("LINETR_ATTN_ST_OCC1") != nullptr;   // tuning aid: one block per CU, 256 VGPRs
-      if (occ1) hipLaunchKernelGGL(sig_attn_st_kernel<1>, dim3(n_images, HEADS, cdiv(max_n, 256)), dim3(512), 0, st, w.qkvs, cu_dev,
-                                   n_images, N, w.msgs);
-      else hipLaunchKernelGGL(sig_attn_st_kernel<2>, dim3(n_images, HEADS, cdiv(max_n, 256)), dim3(512), 0, st, w.qkvs, cu_dev,
-                              n_images, N, w.msgs);
-      LT_LAUNCH_CHECK();
-    }
-    if ((e = gemm("gemm_st_bf16x6_w1", z, D, w.msgs, D, S.W1, S.b1, nullptr, w.hids, nullptr, 2 * D, ACT_RELU))) return e;
-    if (l + 1 == h->sig.size()) break;   // the last layer's second MLP GEMM is folded into the final projection
-    if ((e = gemm("gemm_st_bf16x6_w2", w.hids, 2 * D, nullptr, 0, S.W2, S.b2, z, zn, nullptr, D, ACT_NONE))) return e;
-    std::swap(z, zn);
-  }
-  // final_proj(z + W2 hid + b2) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin), then F.normalize
-  if ((e = gemm("gemm_st_bf16x6_final", z, D, w.hids, 2 * D, h->Wfin2, h->bfin2, nullptr, nullptr, w.zB, D, ACT_NONE))) return e;
-  ProfScope ps(h, st, "row_norm", 0, (double)N * D * 8);
-  hipLaunchKernelGGL(row_norm_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, w.zB, N, 1, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, 0.f, d_line_desc);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
-}
-
-#endif  // LINETR_EXPERIMENTS
 
 // ---- positional encoders, training mode (train.py:127): conv -> BatchNorm(batch statistics) -> ReLU, layer by layer, on the
 // unfolded convolutions of a bn_batch_stats handle.  Statistics run over ALL rows of the batch: B*N*T token positions (padding
@@ -719,22 +550,9 @@ int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_im
 }
 
 // ---- the descriptive layer's tail (up to CUT_SENTENCE): the sentence rows zA, input of the line-signature network
-int sentence(LinetrHandle* h, hipStream_t& st, int N, FwdWs& w, bool chain) {
+int sentence(LinetrHandle* h, hipStream_t& st, int N, FwdWs& w) {
   const LinetrModelConfig& c = h->cfg;
   int e;
-#ifdef LINETR_EXPERIMENTS
-  if (chain) {
-    // [fc + LN] -> [w_1, GELU] -> [w_2 + residual + LN (+ line position)] -> [q/k/v of signature layer 0]: one launch
-    ChainBuilder cb(h);
-    NormSpec ns1; ns1.mode = 1; ns1.gamma = h->ln1g; ns1.beta = h->ln1b; ns1.eps = 1e-6f;
-    NormSpec ns2; ns2.mode = 1; ns2.gamma = h->ln2g; ns2.beta = h->ln2b; ns2.add2 = w.lpos; ns2.eps = 1e-6f;
-    cb.add(w.att, D, nullptr, 0, 0, h->Wfc, h->bfc, nullptr, w.o, N, D, D, ACT_NONE, &ns1);
-    cb.add(w.o, D, nullptr, 0, 0, h->Wf1, h->bf1, nullptr, w.f1, N, c.d_inner, D, ACT_GELU);
-    cb.add(w.f1, c.d_inner, nullptr, 0, 0, h->Wf2, h->bf2, w.o, w.zA, N, D, c.d_inner, ACT_NONE, &ns2);
-    cb.add(w.zA, D, nullptr, 0, 0, h->sig[0].Wqkv, h->sig[0].bqkv, nullptr, w.qkv, N, 3 * D, D, ACT_NONE);
-    return cb.run(st, "gemm_chain_bf16x6_cls");
-  }
-#endif
   {  // o = LN(fc(att) + cls)  (line_attention.py:36-40; the CLS residual sits in the bias)
     NormSpec ns; ns.mode = 1; ns.gamma = h->ln1g; ns.beta = h->ln1b; ns.eps = 1e-6f;
     if ((e = run_gemm_norm(h, st, w.att, D, nullptr, 0, 0, h->Wfc, h->bfc, nullptr, w.fc, w.o, N, D, ns))) return e;
@@ -768,37 +586,41 @@ int sig_attention(LinetrHandle* h, hipStream_t st, const float* qkv, int ldq, co
   return LINETR_OK;
 }
 
+// q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h), z -> msg: q, k, v never reach HBM
+int sig_qkv_attention(LinetrHandle* h, hipStream_t st, const SigLayer& S, const float* z, const int* cu_dev, int n_images, int N,
+                      double attn_fl, float* msg) {
+  auto it = h->split.find(S.Wqkv);
+  if (it == h->split.end() || !it->second.offst) return fail(LINETR_E_ARG, "signature layer: q/k/v weight has no split-tile image");
+  static unsigned long long attr_done = 0;
+  const unsigned long long dev_bit = current_device_bit();
+  if (!(attr_done & dev_bit)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sig_qkv_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FQA_LDS);
+    attr_done |= dev_bit;
+  }
+  ProfScope ps(h, st, "sig_qkv_attn_bf16x6", 2.0 * N * 3.0 * D * D + attn_fl, (double)N * D * 8);
+  hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, h->split_arena + it->second.offst,
+                     S.bqkv, cu_dev, msg);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
 // ---- line-signature network + final projection and L2 normalisation (CUT_SIG0 + l behind layer l).
 // models/line_transformer.py:132-183, 245-246
 int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const int32_t* h_cu, const int* cu_dev, int n_images, int N,
-                float* d_line_desc, FwdWs& w, bool pairnet, bool chain) {
+                float* d_line_desc, FwdWs& w) {
   const LinetrModelConfig& c = h->cfg;
   int max_n = 0;
   for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
   int e;
-#ifdef LINETR_EXPERIMENTS
-  if (pairnet && !chain) return pairnet_run(h, st, w.zA, d_line_desc, h_cu, n_images, N, w.pn);
-  // LINETR_SIG_PATH=st (experiment): activations stay in HBM as split-tile images and every K step travels by LDS-DMA
-  // (lt_gemm_st.h, lt_attn_st.h).  Measured at cfg3 on one box: the ST GEMMs are 5-7 % faster than the register-staged
-  // ones in isolation, but inside the step the 6-byte activations cost more at the kernel boundaries (the L2 write-back of
-  // 273 MB instead of 182 MB of fresh activations per layer) than the main loops save: 2.92 vs 2.69 ms per step.
-  const char* sig_path = LT_XENV("LINETR_SIG_PATH");      // read per call (tests switch it)
-  if (!chain && h->precision == LINETR_PREC_BF16X6 && !h->sig.empty() && sig_path && !strcmp(sig_path, "st"))
-    return sig_network_st(h, st, w, h_cu, cu_dev, n_images, N, max_n, d_line_desc);
-  // layers but the last: W1 -> ReLU -> W2 + residual in one kernel, hidden activations in registers (lt_mlp_fused.h)
-  const bool fused_sig_mlp = h->precision != LINETR_PREC_F32 && N >= 4096 && !LT_XENV("LINETR_NO_FUSED_SIG_MLP") &&
-                             LT_XENV("LINETR_FUSED_SIG_MLP") != nullptr;   // opt-in: measured slower
-#endif
   const double attn_fl = attn_flops(h_cu, n_images);
   // the signature layers' slots behind the two encoders' in the packed BatchNorm statistics
   const int64_t sig_bn_off = 4 * (int64_t)(c.enc_channels[0] + c.enc_channels[1] + c.enc_channels[2] + c.enc_channels[3]);
   const bool small_attn = h->precision != LINETR_PREC_F32 && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
   // single-pair sizes (the 32-query attention is taken): x_out and the NEXT layer's q/k/v come out of ONE contraction over
   // [z ; hid] (SigLayer::Wnext) -- one dependent launch less per layer where a launch costs more than its flops
-  const bool fold_next = !chain && small_attn && N <= SIG_FOLD_MAX_ROWS && !LT_XENV("LINETR_NO_SIG_FOLD");
-  // q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h): images of up to 256 sub-lines, and
-  // enough (image, head) blocks to fill the chip; q, k, v never reach HBM
-  const bool fused_qkv_attn = !fold_next && !chain && !LT_XENV("LINETR_NO_FUSED_QKV_ATTN") && h->precision == LINETR_PREC_BF16X6 &&
+  const bool fold_next = small_attn && N <= SIG_FOLD_MAX_ROWS && !LT_XENV("LINETR_NO_SIG_FOLD");
+  // fused q/k/v projection + attention: images of up to 256 sub-lines, and enough (image, head) blocks to fill the chip
+  const bool fused_qkv_attn = !fold_next && !LT_XENV("LINETR_NO_FUSED_QKV_ATTN") && h->precision == LINETR_PREC_BF16X6 &&
                               max_n <= 256 && (int64_t)n_images * HEADS >= 128;
   float *z = w.zA, *zn = w.zB;     // the layer's input rows (row stride ldz) and the next layer's
   int ldz = D;
@@ -808,51 +630,13 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
   for (size_t l = 0; l < h->sig.size(); ++l) {
     const SigLayer& S = h->sig[l];
     if (fused_qkv_attn) {
-      auto it = h->split.find(S.Wqkv);
-      if (it == h->split.end() || !it->second.offst) return fail(LINETR_E_ARG, "signature layer: q/k/v weight has no split-tile image");
-      static unsigned long long attr_done = 0;
-      const unsigned long long dev_bit = current_device_bit();
-      if (!(attr_done & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sig_qkv_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FQA_LDS);
-        attr_done |= dev_bit;
-      }
-      ProfScope ps(h, st, "sig_qkv_attn_bf16x6", 2.0 * N * 3.0 * D * D + attn_fl, (double)N * D * 8);
-      hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, h->split_arena + it->second.offst,
-                         S.bqkv, cu_dev, w.msgp);
-      LT_LAUNCH_CHECK();
+      if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, attn_fl, w.msgp))) return e;
     } else {
-      // (a chain, or with fold_next the previous layer, has made them already)
-      if (!chain && (!fold_next || l == 0))
+      // (with fold_next the previous layer has made them already)
+      if (!fold_next || l == 0)
         if ((e = run_gemm(h, st, z, ldz, nullptr, 0, 0, S.Wqkv, S.bqkv, nullptr, 0, w.qkv, 3 * D, N, 3 * D, D, ACT_NONE))) return e;
       if ((e = sig_attention(h, st, qkv, ldq, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
     }
-#ifdef LINETR_EXPERIMENTS
-    if (chain) {
-      ChainBuilder cb(h);
-      const bool w1_alone = LT_XENV("LINETR_CHAIN_W1_ALONE") != nullptr;     // A/B: W1 as its own launch (all 256 CUs)
-      if (w1_alone && l + 1 < h->sig.size()) {
-        if ((e = run_gemm(h, st, z, D, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ACT_RELU))) return e;
-      } else
-      cb.add(z, D, w.msgp, D, D, S.W1, S.b1, nullptr, w.hid, N, 2 * D, 2 * D, ACT_RELU);
-      if (l + 1 < h->sig.size()) {
-        // W1 -> W2 + residual -> the NEXT layer's q/k/v projection
-        cb.add(w.hid, 2 * D, nullptr, 0, 0, S.W2, S.b2, z, zn, N, D, 2 * D, ACT_NONE);
-        cb.add(zn, D, nullptr, 0, 0, h->sig[l + 1].Wqkv, h->sig[l + 1].bqkv, nullptr, w.qkv, N, 3 * D, D, ACT_NONE);
-        if ((e = cb.run(st, "gemm_chain_bf16x6_sig"))) return e;
-        std::swap(z, zn);
-        continue;
-      }
-      // last layer: W1 -> [final projection with W2 folded in] -> L2 normalisation
-      NormSpec nl2; nl2.mode = 2;
-      cb.add(z, D, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, d_line_desc, N, D, 3 * D, ACT_NONE, &nl2);
-      return cb.run(st, "gemm_chain_bf16x6_final");
-    }
-    if (fused_sig_mlp && l + 1 < h->sig.size()) {
-      if ((e = run_sig_mlp(h, st, z, w.msgp, S, zn, N))) return e;
-      std::swap(z, zn);
-      continue;
-    }
-#endif
     if ((e = run_gemm(h, st, z, ldz, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ts.bn ? ACT_NONE : ACT_RELU))) return e;
     if (ts.bn && (e = bn_train_layer(st, *ts.bn, w.hid, N, 2 * D, 2 * D, h->bn_g[8 + l], h->bn_b[8 + l], sig_bn_off + (int64_t)l * 4 * D))) return e;
     if (l + 1 == h->sig.size()) break;   // the last layer's second MLP GEMM is folded into the final projection below
@@ -871,28 +655,32 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
   // final_proj(z + W2 hid + b2) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin): one K = 768 GEMM instead of two launches
   return run_gemm_norm(h, st, z, ldz, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, zn, d_line_desc, N, 3 * D, l2);
 }
+}  // namespace
 
+#ifdef LINETR_EXPERIMENTS
+#include "lt_x_net.h"
+#endif
+
+namespace {
 int forward_core(LinetrHandle* h, hipStream_t st, const TokenStage& ts, const float* sublines, const float* resp,
                  const float* angle_sub, const int32_t* h_cu, const int* cu_dev, int n_images, int N, int T,
                  float* d_line_desc, FwdWs& w) {
   int e;
-  bool pairnet = false, chain = false;
 #ifdef LINETR_EXPERIMENTS
-  // experiment (LINETR_PAIRNET=1; measured and not shipped): the whole signature network of a single pair as ONE
-  // persistent launch (lt_pairnet.h); its arrival counters are zeroed here, far ahead of it on the stream
-  pairnet = pairnet_fits(h, n_images, N, h_cu);
-  if (pairnet && (e = pairnet_prepare(h, st, N, w.pn))) return e;
-  chain = chain_wins(h, N) && !h->sig.empty();
+  XPath xp;   // which path takes the signature network (lt_x_net.h)
+  if ((e = x_begin(h, st, n_images, N, h_cu, w, xp))) return e;
 #endif
   if ((e = pos_encoders(h, st, ts, sublines, resp, angle_sub, N, w))) return e;
   if ((e = pipe_boundary(ts.pipe, CUT_MLP, st))) return e;
   if ((e = cls_pooling(h, st, ts, n_images, N, T, w))) return e;
   if ((e = pipe_boundary(ts.pipe, CUT_POOL, st))) return e;
-  if ((e = sentence(h, st, N, w, chain))) return e;
+#ifdef LINETR_EXPERIMENTS
+  if (xp != X_NONE) return x_rest(h, st, ts, h_cu, cu_dev, n_images, N, d_line_desc, w, xp);
+#endif
+  if ((e = sentence(h, st, N, w))) return e;
   if ((e = pipe_boundary(ts.pipe, CUT_SENTENCE, st))) return e;
-  return sig_network(h, st, ts, h_cu, cu_dev, n_images, N, d_line_desc, w, pairnet, chain);
+  return sig_network(h, st, ts, h_cu, cu_dev, n_images, N, d_line_desc, w);
 }
-
 
 int check_cu(const int32_t* h_cu, int n_images) {
   if (!h_cu || n_images < 1) return fail(LINETR_E_ARG, "null / empty cu_sub");
@@ -1234,45 +1022,3 @@ extern "C" int linetr_debug_gemm(LinetrHandle* h, const float* A, int32_t lda, c
   }
   return e;
 }
-
-#ifdef LINETR_EXPERIMENTS
-// ---- split-tile (ST) format and GEMM (lt_gemm_st.h), for the unit tests and micro-benchmarks
-extern "C" int64_t linetr_st_bytes(int64_t rows, int32_t K) { return (K % 16 || rows < 0) ? -1 : st_bytes(rows, K); }
-
-extern "C" int linetr_debug_to_st(LinetrHandle* h, const float* d_X, int32_t ld, int32_t rows, int32_t K, void* d_st,
-                                  void* stream) {
-  if (!h || !d_X || !d_st || K % 16 || ld < K || ld % 4 || rows < 1) return fail(LINETR_E_ARG, "debug_to_st: bad argument");
-  LT_HIP(hipSetDevice(h->device));
-  const int64_t thr = st_row_blocks(rows) * (K / 16) * 32;
-  hipLaunchKernelGGL(to_st_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_X, ld, rows, K / 16,
-                     (unsigned char*)d_st);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
-}
-
-extern "C" int linetr_debug_from_st(LinetrHandle* h, const void* d_st, int32_t rows, int32_t K, float* d_X, int32_t ld,
-                                    void* stream) {
-  if (!h || !d_X || !d_st || K % 16 || ld < K || ld % 4 || rows < 1) return fail(LINETR_E_ARG, "debug_from_st: bad argument");
-  LT_HIP(hipSetDevice(h->device));
-  const int64_t thr = st_row_blocks(rows) * (K / 16) * 32;
-  hipLaunchKernelGGL(from_st_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const unsigned char*)d_st, rows, K / 16, d_X, ld);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
-}
-
-extern "C" int linetr_debug_gemm_st(LinetrHandle* h, const void* d_A1, int32_t K1, const void* d_A2, int32_t K2,
-                                    const void* d_W, const float* d_bias, const void* d_R, void* d_Yst, float* d_Y,
-                                    int32_t ldy, int32_t M, int32_t N, int32_t act, void* stream) {
-  if (!h || !d_A1 || !d_W || (!d_Yst && !d_Y) || K1 % 16 || K2 % 16 || N > 4096)
-    return fail(LINETR_E_ARG, "debug_gemm_st: bad argument");
-  LT_HIP(hipSetDevice(h->device));
-  StGemmArgs a;
-  a.A1 = (const unsigned char*)d_A1; a.nk1 = K1 / 16;
-  a.A2 = (const unsigned char*)d_A2; a.nk2 = d_A2 ? K2 / 16 : 0;
-  a.W = (const unsigned char*)d_W; a.bias = d_bias ? d_bias : h->zeros; a.R = (const unsigned char*)d_R;
-  a.Yst = (unsigned char*)d_Yst; a.Y = d_Y; a.ldy = ldy; a.M = M; a.N = N; a.act = act;
-  return gemm_st_launch(a, (hipStream_t)stream);
-}
-
-#endif  // LINETR_EXPERIMENTS

@@ -27,8 +27,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // were measured and lost.  `python -m linetr_amd.build --experiments` builds liblinetr_hip_experiments.so from the same sources
 // plus experiments/csrc: the stream-K tail, the 256x256 tile, the fused signature MLP, the split-tile / LDS-DMA path, the
 // row-owner GEMM, GEMM chains and the single-pair persistent network, and the switches that select them or that tools/ and
-// experiments/test_experiments.py read.  LT_XENV is getenv there and a constant null pointer in the product, so every switch
-// folds away.
+// experiments/test_experiments.py read.  Apart from the two kernel-side blocks of lt_gemm_split.h, the host code of those paths
+// lives in experiments/csrc/lt_x_net.h and reaches the forward pass through a few one-line hooks in linetr_net.hip.  LT_XENV is
+// getenv there and a constant null pointer in the product, so every switch on a shipped path folds away.
 #ifdef LINETR_EXPERIMENTS
 #define LT_XENV(name) getenv(name)
 #else

@@ -1,9 +1,10 @@
 // The library handle and what every translation unit of liblinetr_hip.so shares: the prepared-weight table, the per-kernel-class
 // HIP-event profiler and the declarations of the few host functions that cross translation units.
 //   linetr_core.hip   lifetime (float64 weight preparation), host pre-filter, collective, profiling entry points
-//   linetr_net.hip    tokenise / forward / describe + the GEMM dispatcher and every model kernel
+//   linetr_net.hip    tokenise / forward / describe + the GEMM dispatcher and every model kernel (the experiments build includes
+//                     experiments/csrc/lt_x_net.h into it: the host code of its alternative paths and the hooks that select them)
 //   linetr_match.hip  matcher, dense-map producer, slab packing
-//   linetr_pair.hip   (experiments build only) the single-pair persistent signature network
+//   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once
 #include <map>
 #include <memory>
@@ -15,7 +16,7 @@
 
 struct SigLayer {
   const float *Wqkv, *bqkv, *W1, *b1, *W2, *b2;  // merge conv folded into W1
-  const float* W2p = nullptr;                    // W2 with K permuted inside 16-groups (lt_mlp_fused.h)
+  const float* W2p = nullptr;                    // experiments build: W2 with K permuted inside 16-groups (lt_mlp_fused.h)
   // [x_out | q/k/v of the NEXT layer] = Wnext [z ; hid] + bnext: W2 + residual and the next projection as ONE contraction
   // ([4D x 3D]; all layers but the last).  Used for single-pair sizes only, where a dependent launch costs more than its flops.
   const float *Wnext = nullptr, *bnext = nullptr;
@@ -62,8 +63,9 @@ struct LinetrHandle {
     bool submitted[PIPE_SLOTS] = {false, false, false, false};
     bool failed = false;
   } pipe;
-  // stream-K workspace of the 128x256 GEMM (partial accumulator tiles + flags, one slot per CU; lt_gemm_split.h)
   float* zeros = nullptr;   // 4096 zero floats: the "no bias" vector of the split-tile GEMM (experiments/csrc/lt_gemm_st.h)
+  float* w2p_arena = nullptr;   // experiments build: every SigLayer::W2p, one allocation (experiments/csrc/lt_x_net.h)
+  // stream-K workspace of the 128x256 GEMM (partial accumulator tiles + flags, one slot per CU; lt_gemm_split.h)
   float* sk_ws = nullptr;
   unsigned* sk_flags = nullptr;
   unsigned sk_epoch = 0;
@@ -132,17 +134,6 @@ struct ProfScope {
 
 // one GEMM weight of the prepared arena that needs split-precision copies (made on the device by linetr_net.hip)
 struct GemmWSpec { const float* W; int64_t rows; int K; bool st; };
-int make_split_copies(LinetrHandle* H, const std::vector<GemmWSpec>& weights);
-
-// Experiments build: the line-signature network of a single pair (a few small images) as ONE persistent launch (lt_pairnet.h):
-//   pairnet_fits      does this batch take the path (precision, image count, row count)?  h_cu may be NULL (size check only)
-//   pairnet_ws_bytes  bytes of workspace it needs for N rows (0 when N is out of range)
-//   pairnet_prepare   zeroes the arrival counters on the stream (call it EARLY, well ahead of the launch)
-//   pairnet_run       z0 [N,256] -> line_desc [N,256]
-constexpr int PN_MAX_ROWS = 1024;
-bool pairnet_fits(LinetrHandle* h, int n_images, int N, const int32_t* h_cu);
-int64_t pairnet_ws_bytes(const LinetrHandle* h, int N);
-int pairnet_prepare(LinetrHandle* h, hipStream_t st, int N, void* ws);
-int pairnet_run(LinetrHandle* h, hipStream_t st, const float* z0, float* out, const int32_t* h_cu, int n_images, int N, void* ws);
+int make_split_copies(LinetrHandle* H, std::vector<GemmWSpec> weights);
 
 }  // namespace lt
