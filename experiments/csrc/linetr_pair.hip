@@ -84,17 +84,11 @@ int lt::pairnet_run(LinetrHandle* h, hipStream_t st, const float* z0, float* out
   a.img_rt0[n_images] = rt;
   a.n_rt = rt;
   flops += 2.0 * N * ((double)L * (3.0 * D * D + 4.0 * D * D) + (L - 1) * 2.0 * D * D + 3.0 * D * D);
-  auto sp = [&](const float* W) -> const unsigned char* {
-    auto it = h->split.find(W);
-    return it == h->split.end() ? nullptr : h->split_arena + it->second.off3;
-  };
   for (int l = 0; l < L; ++l) {
     const SigLayer& S = h->sig[l];
-    a.layer[l] = PnLayer{sp(S.Wqkv), sp(S.W1), sp(S.W2), S.bqkv, S.b1, S.b2};
-    if (!a.layer[l].Wqkv || !a.layer[l].W1 || !a.layer[l].W2) return fail(LINETR_E_ARG, "pair network: weight has no split copy");
+    a.layer[l] = PnLayer{S.Wqkv.s3, S.W1.s3, S.W2.s3, S.Wqkv.b, S.W1.b, S.W2.b};
   }
-  a.Wfin = sp(h->Wfin2); a.bfin = h->bfin2;
-  if (!a.Wfin) return fail(LINETR_E_ARG, "pair network: final projection has no split copy");
+  a.Wfin = h->Wfin2.s3; a.bfin = h->Wfin2.b;
   a.z0 = z0; a.out = out;
   a.ws = (float*)ws;
   a.cnt = (int*)((char*)ws + align_up(pn_ws_floats(std::max(N, 1), L) * 4, 256));

@@ -17,7 +17,7 @@
 
 namespace {
 
-int x_gemm(LinetrHandle* h, hipStream_t st, SplitGemmArgs& sa, const LinetrHandle::SplitW& sw, int groups, const NormSpec* fused_norm,
+int x_gemm(LinetrHandle* h, hipStream_t st, SplitGemmArgs& sa, const GemmW& w, int groups, const NormSpec* fused_norm,
            double fl, double by, bool& done) {
   if (LT_XENV("LINETR_STREAMK")) {   // opt-in experiment (lt_gemm_split.h): the 32 MB workspace is only allocated when asked for
     if (!h->sk_ws) {
@@ -33,11 +33,11 @@ int x_gemm(LinetrHandle* h, hipStream_t st, SplitGemmArgs& sa, const LinetrHandl
   // the register-staged tiles (a two-slot ring leaves a DMA one K step to land, and the barrier comes every 48 MFMAs), so opt-in.
   const GemmArgs& g = sa.g;
   if (h->precision == LINETR_PREC_BF16X6 && LT_XENV("LINETR_GEMM_RO") != nullptr && groups == 1 && g.N % 256 == 0 && g.K % 32 == 0 &&
-      sw.offst && g.lda % 4 == 0 && g.ldy % 4 == 0 && (!g.A2 || (g.lda2 % 4 == 0 && g.K1 % 16 == 0)) && (!g.R || g.ldr % 4 == 0) &&
+      w.st && g.lda % 4 == 0 && g.ldy % 4 == 0 && (!g.A2 || (g.lda2 % 4 == 0 && g.K1 % 16 == 0)) && (!g.R || g.ldr % 4 == 0) &&
       g.act != ACT_DIST && cdiv(g.M, 128) * (g.N / 256) >= 140) {
     RoGemmArgs a;
     a.A1 = g.A; a.lda1 = g.lda; a.nk1 = (g.A2 ? g.K1 : g.K) / 16; a.A2 = g.A2; a.lda2 = g.lda2; a.nk2 = g.A2 ? (g.K - g.K1) / 16 : 0;
-    a.Wst = h->split_arena + sw.offst; a.bias = g.bias ? g.bias : h->zeros; a.R = g.R; a.ldr = g.ldr; a.Y = g.Y; a.ldy = g.ldy;
+    a.Wst = w.st; a.bias = g.bias ? g.bias : h->zeros; a.R = g.R; a.ldr = g.ldr; a.Y = g.Y; a.ldy = g.ldy;
     a.M = g.M; a.N = g.N; a.act = g.act;
     if (fused_norm) { a.norm = fused_norm->mode; a.gamma = fused_norm->gamma; a.beta = fused_norm->beta; a.add2 = fused_norm->add2; a.ldadd2 = D; a.eps = fused_norm->eps; }
     done = true;
@@ -57,12 +57,12 @@ int x_split_weights(LinetrHandle* H, std::vector<GemmWSpec>& weights) {
   std::vector<float> w2(n), w2p(n);
   for (size_t l = 0; l < H->sig.size(); ++l) {
     SigLayer& S = H->sig[l];
-    LT_HIP(hipMemcpy(w2.data(), S.W2, n * sizeof(float), hipMemcpyDeviceToHost));
+    LT_HIP(hipMemcpy(w2.data(), S.W2.W, n * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) w2p[i] = w2[sig_mlp_kperm((int)i)];   // (rows of 2 D: the permutation stays inside a row)
     float* dst = H->w2p_arena + l * n;
     LT_HIP(hipMemcpy(dst, w2p.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    S.W2p = dst;
-    weights.push_back({S.W2p, D, 2 * D, true});
+    S.W2p.W = dst; S.W2p.b = S.W2.b; S.W2p.rows = D; S.W2p.K = 2 * D;
+    weights.push_back({&S.W2p, true});
   }
   return LINETR_OK;
 }
@@ -93,24 +93,18 @@ struct ChainBuilder {
   double flops = 0, bytes = 0;
   int err = 0;
   explicit ChainBuilder(LinetrHandle* h_) : h(h_) {}
-  // Y[M,N] = norm(act(A (| A2) W^T + bias) (+ R)) (+ add2)
-  void add(const float* A, int lda, const float* A2, int lda2, int K1, const float* W, const float* bias, const float* R,
-           float* Y, int M, int N, int K, int act, const NormSpec* ns = nullptr) {
+  // Y[M,N] = norm(act(A (| A2) W^T + bias) (+ R)) (+ add2), Y and R with row stride N
+  void add(const GemmW& w, int M, const GemmA& A, float* Y, int act, const float* R = nullptr, const NormSpec* ns = nullptr) {
     if (err) return;
     if (c.n >= CHAIN_MAX) { err = fail(LINETR_E_ARG, "gemm chain: too many stages"); return; }
-    auto it = h->split.find(W);
-    if (it == h->split.end()) { err = fail(LINETR_E_ARG, "gemm chain: weight has no split-bf16 copy"); return; }
     SplitGemmArgs& sa = c.st[c.n++];
     sa = SplitGemmArgs{};
     GemmArgs& g = sa.g;
-    g = GemmArgs{};
-    g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = K1; g.W = W; g.ldw = K; g.bias = bias; g.R = R; g.ldr = N; g.Y = Y; g.ldy = N;
-    g.M = M; g.N = N; g.K = K; g.act = act;
-    if (ns) { g.norm = ns->mode; g.gamma = ns->gamma; g.beta = ns->beta; g.add2 = ns->add2; g.ldadd2 = D; g.eps = ns->eps; }
-    sa.Wsp = h->split_arena + it->second.off3;
+    if ((err = gemm_args(w, M, A, {Y, w.rows}, act, R, nullptr, ns, g))) return;
+    sa.Wsp = w.s3;
     sa.wide_epi = 1;
-    flops += 2.0 * M * (double)N * K;
-    bytes += 4.0 * ((double)M * K + (double)N * K + (double)M * N);
+    flops += 2.0 * M * (double)g.N * g.K;
+    bytes += 4.0 * ((double)M * g.K + (double)g.N * g.K + (double)M * g.N);
   }
   int run(hipStream_t st, const char* name) {
     if (err) return err;
@@ -142,10 +136,10 @@ int sentence_chain(LinetrHandle* h, hipStream_t st, int N, FwdWs& w) {
   ChainBuilder cb(h);
   NormSpec ns1; ns1.mode = 1; ns1.gamma = h->ln1g; ns1.beta = h->ln1b; ns1.eps = 1e-6f;
   NormSpec ns2; ns2.mode = 1; ns2.gamma = h->ln2g; ns2.beta = h->ln2b; ns2.add2 = w.lpos; ns2.eps = 1e-6f;
-  cb.add(w.att, D, nullptr, 0, 0, h->Wfc, h->bfc, nullptr, w.o, N, D, D, ACT_NONE, &ns1);
-  cb.add(w.o, D, nullptr, 0, 0, h->Wf1, h->bf1, nullptr, w.f1, N, c.d_inner, D, ACT_GELU);
-  cb.add(w.f1, c.d_inner, nullptr, 0, 0, h->Wf2, h->bf2, w.o, w.zA, N, D, c.d_inner, ACT_NONE, &ns2);
-  cb.add(w.zA, D, nullptr, 0, 0, h->sig[0].Wqkv, h->sig[0].bqkv, nullptr, w.qkv, N, 3 * D, D, ACT_NONE);
+  cb.add(h->Wfc, N, {w.att, D}, w.o, ACT_NONE, nullptr, &ns1);
+  cb.add(h->Wf1, N, {w.o, D}, w.f1, ACT_GELU);
+  cb.add(h->Wf2, N, {w.f1, c.d_inner}, w.zA, ACT_NONE, w.o, &ns2);
+  cb.add(h->sig[0].Wqkv, N, {w.zA, D}, w.qkv, ACT_NONE);
   return cb.run(st, "gemm_chain_bf16x6_cls");
 }
 
@@ -164,16 +158,16 @@ int sig_network_chain(LinetrHandle* h, hipStream_t st, const int32_t* h_cu, cons
     ChainBuilder cb(h);
     const bool w1_alone = LT_XENV("LINETR_CHAIN_W1_ALONE") != nullptr;     // A/B: W1 as its own launch (all 256 CUs)
     if (w1_alone && l + 1 < h->sig.size()) {
-      if ((e = run_gemm(h, st, z, D, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ACT_RELU))) return e;
+      if ((e = run_gemm(h, st, S.W1, N, {z, D, w.msgp, D, D}, {w.hid, 2 * D}, ACT_RELU))) return e;
     } else
-    cb.add(z, D, w.msgp, D, D, S.W1, S.b1, nullptr, w.hid, N, 2 * D, 2 * D, ACT_RELU);
+    cb.add(S.W1, N, {z, D, w.msgp, D, D}, w.hid, ACT_RELU);
     if (l + 1 == h->sig.size()) {
       NormSpec nl2; nl2.mode = 2;
-      cb.add(z, D, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, d_line_desc, N, D, 3 * D, ACT_NONE, &nl2);
+      cb.add(h->Wfin2, N, {z, D, w.hid, 2 * D, D}, d_line_desc, ACT_NONE, nullptr, &nl2);
       return cb.run(st, "gemm_chain_bf16x6_final");
     }
-    cb.add(w.hid, 2 * D, nullptr, 0, 0, S.W2, S.b2, z, zn, N, D, 2 * D, ACT_NONE);
-    cb.add(zn, D, nullptr, 0, 0, h->sig[l + 1].Wqkv, h->sig[l + 1].bqkv, nullptr, w.qkv, N, 3 * D, D, ACT_NONE);
+    cb.add(S.W2, N, {w.hid, 2 * D}, zn, ACT_NONE, z);
+    cb.add(h->sig[l + 1].Wqkv, N, {zn, D}, w.qkv, ACT_NONE);
     if ((e = cb.run(st, "gemm_chain_bf16x6_sig"))) return e;
     std::swap(z, zn);
   }
@@ -181,21 +175,19 @@ int sig_network_chain(LinetrHandle* h, hipStream_t st, const int32_t* h_cu, cons
 
 // ---- fused signature MLP (lt_mlp_fused.h): z' = z + W2 relu(W1 [z ; msg] + b1) + b2 in one launch (split-bf16 modes only)
 int run_sig_mlp(LinetrHandle* h, hipStream_t st, const float* z, const float* msg, const SigLayer& S, float* out, int M) {
-  auto i1 = h->split.find(S.W1), i2 = h->split.find(S.W2p);
-  if (i1 == h->split.end() || i2 == h->split.end()) return fail(LINETR_E_ARG, "sig_mlp: weight has no split copy");
   SigMlpArgs a;
-  a.z = z; a.ldz = D; a.msg = msg; a.ldm = D; a.b1 = S.b1; a.b2 = S.b2; a.out = out; a.ldo = D; a.M = M;
+  a.z = z; a.ldz = D; a.msg = msg; a.ldm = D; a.b1 = S.W1.b; a.b2 = S.W2.b; a.out = out; a.ldo = D; a.M = M;
   const double fl = 2.0 * M * (2.0 * D * 2 * D + 2.0 * D * D), by = 4.0 * M * 3.0 * D;
   if (h->precision == LINETR_PREC_BF16X3) {
-    a.W1sp = h->split_arena + i1->second.off2; a.W2sp = h->split_arena + i2->second.off2;
+    a.W1sp = S.W1.s2; a.W2sp = S.W2p.s2;
     ProfScope ps(h, st, "sig_mlp_bf16x3", fl, by);
     sig_mlp_fused_launch<2, 0>(a, st);
   } else if (h->precision == LINETR_PREC_F16X3) {
-    a.W1sp = h->split_arena + i1->second.offh; a.W2sp = h->split_arena + i2->second.offh;
+    a.W1sp = S.W1.h2; a.W2sp = S.W2p.h2;
     ProfScope ps(h, st, "sig_mlp_f16x3", fl, by);
     sig_mlp_fused_launch<2, 1>(a, st);
   } else {
-    a.W1sp = h->split_arena + i1->second.off3; a.W2sp = h->split_arena + i2->second.off3;
+    a.W1sp = S.W1.s3; a.W2sp = S.W2p.s3;
     ProfScope ps(h, st, "sig_mlp_bf16x6", fl, by);
     sig_mlp_fused_launch<3, 0>(a, st);
   }
@@ -216,10 +208,10 @@ int sig_network_fused_mlp(LinetrHandle* h, hipStream_t st, const TokenStage& ts,
   int e;
   for (size_t l = 0;; ++l) {
     const SigLayer& S = h->sig[l];
-    if (fused_qkv_attn) {
+    if (fused_qkv_attn && S.Wqkv.st) {
       if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, attn_fl, w.msgp))) return e;
     } else {
-      if ((e = run_gemm(h, st, z, D, nullptr, 0, 0, S.Wqkv, S.bqkv, nullptr, 0, w.qkv, 3 * D, N, 3 * D, D, ACT_NONE))) return e;
+      if ((e = run_gemm(h, st, S.Wqkv, N, {z, D}, {w.qkv, 3 * D}, ACT_NONE))) return e;
       if ((e = sig_attention(h, st, w.qkv, 3 * D, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
     }
     if (l + 1 == h->sig.size()) break;
@@ -227,10 +219,10 @@ int sig_network_fused_mlp(LinetrHandle* h, hipStream_t st, const TokenStage& ts,
     std::swap(z, zn);
   }
   const size_t l = h->sig.size() - 1;
-  if ((e = run_gemm(h, st, z, D, w.msgp, D, D, h->sig[l].W1, h->sig[l].b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ts.bn ? ACT_NONE : ACT_RELU))) return e;
+  if ((e = run_gemm(h, st, h->sig[l].W1, N, {z, D, w.msgp, D, D}, {w.hid, 2 * D}, ts.bn ? ACT_NONE : ACT_RELU))) return e;
   if (ts.bn && (e = bn_train_layer(st, *ts.bn, w.hid, N, 2 * D, 2 * D, h->bn_g[8 + l], h->bn_b[8 + l], sig_bn_off + (int64_t)l * 4 * D))) return e;
   NormSpec l2; l2.mode = 2;
-  return run_gemm_norm(h, st, z, D, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, zn, d_line_desc, N, 3 * D, l2);
+  return run_gemm_norm(h, st, h->Wfin2, N, {z, D, w.hid, 2 * D, D}, nullptr, zn, d_line_desc, l2);
 }
 
 // ---- split-tile signature network (lt_gemm_st.h, lt_attn_st.h)
@@ -238,15 +230,12 @@ int sig_network_fused_mlp(LinetrHandle* h, hipStream_t st, const TokenStage& ts,
 // final projection (with the last W2 folded in) and the L2 normalisation.  models/line_transformer.py:132-183, 245-246.
 int sig_network_st(LinetrHandle* h, hipStream_t st, FwdWs& w, const XWs& x, const int32_t* h_cu, const int* cu_dev, int n_images,
                    int N, int max_n, float* d_line_desc) {
-  auto wst = [&](const float* W) -> const unsigned char* {
-    auto it = h->split.find(W);
-    return (it == h->split.end() || !it->second.offst) ? nullptr : h->split_arena + it->second.offst;
-  };
-  auto gemm = [&](const char* role, const unsigned char* A1, int K1, const unsigned char* A2, int K2, const float* W, const float* bias,
-                  const unsigned char* R, unsigned char* Yst, float* Y, int Nout, int act) -> int {
+  auto gemm = [&](const char* role, const unsigned char* A1, int K1, const unsigned char* A2, int K2, const GemmW& W,
+                  const unsigned char* R, unsigned char* Yst, float* Y, int act) -> int {
+    const int Nout = W.rows;
     StGemmArgs a;
     a.A1 = A1; a.nk1 = K1 / 16; a.A2 = A2; a.nk2 = A2 ? K2 / 16 : 0;
-    a.W = wst(W); a.bias = bias ? bias : h->zeros; a.R = R; a.Yst = Yst; a.Y = Y; a.ldy = D; a.M = N; a.N = Nout; a.act = act;
+    a.W = W.st; a.bias = W.b ? W.b : h->zeros; a.R = R; a.Yst = Yst; a.Y = Y; a.ldy = D; a.M = N; a.N = Nout; a.act = act;
     if (!a.W) return fail(LINETR_E_ARG, "sig_network_st: weight has no split-tile image");
     const double K = K1 + (A2 ? K2 : 0);
     ProfScope ps(h, st, role, 2.0 * N * Nout * K, 6.0 * ((double)N * K + (double)Nout * K + (double)N * Nout));
@@ -264,7 +253,7 @@ int sig_network_st(LinetrHandle* h, hipStream_t st, FwdWs& w, const XWs& x, cons
   const double attn_fl = attn_flops(h_cu, n_images);
   for (size_t l = 0; l < h->sig.size(); ++l) {
     const SigLayer& S = h->sig[l];
-    if ((e = gemm("gemm_st_bf16x6_qkv", z, D, nullptr, 0, S.Wqkv, S.bqkv, nullptr, x.qkvs, nullptr, 3 * D, ACT_NONE))) return e;
+    if ((e = gemm("gemm_st_bf16x6_qkv", z, D, nullptr, 0, S.Wqkv, nullptr, x.qkvs, nullptr, ACT_NONE))) return e;
     {
       ProfScope ps(h, st, "sig_attn_st", attn_fl, (double)N * D * 24);
       const bool occ1 = LT_XENV("LINETR_ATTN_ST_OCC1") != nullptr;   // tuning aid: one block per CU, 256 VGPRs
@@ -274,13 +263,13 @@ int sig_network_st(LinetrHandle* h, hipStream_t st, FwdWs& w, const XWs& x, cons
                               n_images, N, x.msgs);
       LT_LAUNCH_CHECK();
     }
-    if ((e = gemm("gemm_st_bf16x6_w1", z, D, x.msgs, D, S.W1, S.b1, nullptr, x.hids, nullptr, 2 * D, ACT_RELU))) return e;
+    if ((e = gemm("gemm_st_bf16x6_w1", z, D, x.msgs, D, S.W1, nullptr, x.hids, nullptr, ACT_RELU))) return e;
     if (l + 1 == h->sig.size()) break;   // the last layer's second MLP GEMM is folded into the final projection
-    if ((e = gemm("gemm_st_bf16x6_w2", x.hids, 2 * D, nullptr, 0, S.W2, S.b2, z, zn, nullptr, D, ACT_NONE))) return e;
+    if ((e = gemm("gemm_st_bf16x6_w2", x.hids, 2 * D, nullptr, 0, S.W2, z, zn, nullptr, ACT_NONE))) return e;
     std::swap(z, zn);
   }
   // final_proj(z + W2 hid + b2) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin), then F.normalize
-  if ((e = gemm("gemm_st_bf16x6_final", z, D, x.hids, 2 * D, h->Wfin2, h->bfin2, nullptr, nullptr, w.zB, D, ACT_NONE))) return e;
+  if ((e = gemm("gemm_st_bf16x6_final", z, D, x.hids, 2 * D, h->Wfin2, nullptr, nullptr, w.zB, ACT_NONE))) return e;
   ProfScope ps(h, st, "row_norm", 0, (double)N * D * 8);
   hipLaunchKernelGGL(row_norm_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, w.zB, N, 1, (const float*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, 0.f, d_line_desc);

@@ -94,7 +94,7 @@ def test_gemm_stream_k_tail(eng, M, N, K, act, monkeypatch):
     assert (Y1 - Y0).abs().max().item() < 1e-4 * max(1.0, Y0.abs().max().item())
     if torch.cuda.get_device_properties(0).multi_processor_count == 256:
         # the tail was taken exactly where the launcher gives one: it sums the shared tiles' K ranges in another order than the
-        # plain launch, so some bits differ.  The other shapes go to the 128x128s and 64x256 tiles (split_tile_name), which have none.
+        # plain launch, so some bits differ.  The other shapes go to the 128x128s and 64x256 tiles (split_tile), which have none.
         assert torch.equal(Y1, Y0) != ((M, N, K) in _STREAM_K_TAIL_SHAPES), (M, N, K)
     x = A.double() @ W.double().t() + b.double()
     x = [x, torch.relu(x), torch.nn.functional.gelu(x)][act] + R.double()

@@ -161,13 +161,15 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
   struct Fix { const float** dst; size_t off; };
   std::vector<Fix> fix;
   auto place = [&](const float** dst, const std::vector<double>& v) { fix.push_back({dst, ar.put(v)}); };
-  struct GemmW { const float** dst; int64_t rows; int K; bool st; };
-  std::vector<GemmW> gemm_w;
-  // st: the weight also gets a split-tile image (lt_st_image.h) -- the q/k/v projections, which the fused projection +
-  // attention kernel streams by LDS-DMA (lt_attn_fused.h); in the experiments build every eligible weight gets one
-  auto place_w = [&](const float** dst, const std::vector<double>& v, int64_t rows, int K, bool st = false) {
-    place(dst, v);
-    gemm_w.push_back({dst, rows, K, st});
+  std::vector<GemmWSpec> gemm_w;
+  // a GEMM weight [rows, K] and its bias.  st: the weight also gets a split-tile image (lt_st_image.h) -- the q/k/v projections,
+  // which the fused projection + attention kernel streams by LDS-DMA (lt_attn_fused.h); in the experiments build every eligible
+  // weight gets one
+  auto place_w = [&](GemmW* dst, const std::vector<double>& W, const std::vector<double>& b, int rows, int K, bool st = false) {
+    place(&dst->W, W);
+    place(&dst->b, b);
+    dst->rows = rows; dst->K = K;
+    gemm_w.push_back({dst, st});
   };
 
   // training-mode handle: gamma / beta of the 8 + n_sig_layers BatchNorm layers (the vectors are sized up front: place() keeps
@@ -186,10 +188,8 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
   for (int enc = 0; enc < 2; ++enc) {
     const std::string pre = enc == 0 ? "klenc.word_position_enc.encoder." : "klenc.line_position_enc.encoder.";
     const int* ch = enc == 0 ? ch_w : ch_l;
-    const float** Wdst[4] = {enc == 0 ? &H->wW1 : &H->lW1, enc == 0 ? &H->wW2 : &H->lW2,
-                             enc == 0 ? &H->wW3 : &H->lW3, enc == 0 ? &H->wW4 : &H->lW4};
-    const float** bdst[4] = {enc == 0 ? &H->wb1 : &H->lb1, enc == 0 ? &H->wb2 : &H->lb2,
-                             enc == 0 ? &H->wb3 : &H->lb3, enc == 0 ? &H->wb4 : &H->lb4};
+    GemmW* const Wdst[4] = {nullptr, enc == 0 ? &H->wW2 : &H->lW2, enc == 0 ? &H->wW3 : &H->lW3,
+                            enc == 0 ? &H->wW4 : &H->lW4};   // (layer 1 is no GEMM)
     for (int i = 0; i < 4; ++i) {
       const std::string c = pre + std::to_string(3 * i), bn = pre + std::to_string(3 * i + 1);
       const float* W = tm.get(c + ".weight", (int64_t)ch[i + 1] * ch[i], err);
@@ -209,14 +209,14 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
       fold_bn(W, b, g, be, mu, va, ch[i + 1], ch[i], Wf, bf);
       // layers 2-4 also get split-tile images: the one-kernel MLP of lt_tokmlp.h keeps layers 2 / 3 in LDS and layer 4 in registers as
       // such, and the weight-stationary GEMM of lt_gemm_ws.h reads layer 4's planes from one
-      if (i == 0) place(Wdst[i], Wf); else place_w(Wdst[i], Wf, ch[i + 1], ch[i], true);
-      place(bdst[i], bf);
+      if (i == 0) { place(enc == 0 ? &H->wW1 : &H->lW1, Wf); place(enc == 0 ? &H->wb1 : &H->lb1, bf); }
+      else place_w(Wdst[i], Wf, bf, ch[i + 1], ch[i], true);
     }
     const float* W = tm.get(pre + "12.weight", (int64_t)D * e3, err);
     const float* b = tm.get(pre + "12.bias", D, err);
     if (err) return err;
     if (enc == 0) { W5w = to_d(W, (size_t)D * D); b5w = to_d(b, D); }
-    else { place_w(&H->lW5, to_d(W, (size_t)D * D), D, e3); place(&H->lb5, to_d(b, D)); }
+    else place_w(&H->lW5, to_d(W, (size_t)D * D), to_d(b, D), D, e3);
   }
 
   // ---- line-descriptive layer: only the last one matters (line_transformer.py:123-125) ----------
@@ -288,15 +288,13 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
         row[2 * D] = r;
         batt[o] = bb;
       }
-    place_w(&H->Watt, Watt, HEADS * DH, POOLW);
-    place(&H->batt, batt);
-    place_w(&H->Wfc, to_d(Wfc, D * D), D, D);
+    place_w(&H->Watt, Watt, batt, HEADS * DH, POOLW);
     std::vector<double> bfc2(D);
     for (int i = 0; i < D; ++i) bfc2[i] = (double)bfc[i] + cls[i];  // residual of the CLS row is the constant token
-    place(&H->bfc, bfc2);
+    place_w(&H->Wfc, to_d(Wfc, D * D), bfc2, D, D);
     place(&H->ln1g, to_d(g1, D)); place(&H->ln1b, to_d(b1, D));
-    place_w(&H->Wf1, to_d(W1, (size_t)DI * D), DI, D); place(&H->bf1, to_d(bb1, DI));
-    place_w(&H->Wf2, to_d(W2, (size_t)D * DI), D, DI); place(&H->bf2, to_d(bb2, D));
+    place_w(&H->Wf1, to_d(W1, (size_t)DI * D), to_d(bb1, DI), DI, D);
+    place_w(&H->Wf2, to_d(W2, (size_t)D * DI), to_d(bb2, D), D, DI);
     place(&H->ln2g, to_d(g2, D)); place(&H->ln2b, to_d(b2, D));
   }
 
@@ -363,9 +361,9 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
     SigLayer& S = H->sig[l];
     sig_qkv_d.push_back(Wqkv); sig_bqkv_d.push_back(bqkv);
     sig_w2_d.push_back(to_d(W2, (size_t)2 * D * D)); sig_b2_d.push_back(to_d(b2, D));
-    place_w(&S.Wqkv, Wqkv, 3 * D, D, true); place(&S.bqkv, bqkv);
-    place_w(&S.W1, W1m, 2 * D, 2 * D); place(&S.b1, b1f);
-    place_w(&S.W2, to_d(W2, (size_t)2 * D * D), D, 2 * D); place(&S.b2, to_d(b2, D));
+    place_w(&S.Wqkv, Wqkv, bqkv, 3 * D, D, true);
+    place_w(&S.W1, W1m, b1f, 2 * D, 2 * D);
+    place_w(&S.W2, to_d(W2, (size_t)2 * D * D), to_d(b2, D), D, 2 * D);
   }
   // x_out = z + W2 hid + b2 (line_transformer.py:180-183) and the next layer's q/k/v projection is linear in x_out (:141-143), so
   //   [x_out ; qkv_next] = [[I, W2], [Wqkv, Wqkv W2]] [z ; hid] + [b2 ; Wqkv b2 + bqkv]                      (float64, once)
@@ -391,15 +389,13 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
       }
       bn[D + r] = bacc;
     }
-    place_w(&H->sig[l].Wnext, Wn, 4 * D, 3 * D);
-    place(&H->sig[l].bnext, bn);
+    place_w(&H->sig[l].Wnext, Wn, bn, 4 * D, 3 * D);
   }
   {
     const float* W = tm.get("final_proj.weight", D * D, err);
     const float* b = tm.get("final_proj.bias", D, err);
     if (err) return err;
-    place_w(&H->Wfin, to_d(W, D * D), D, D);
-    place(&H->bfin, to_d(b, D));
+    place_w(&H->Wfin, to_d(W, D * D), to_d(b, D), D, D);
     if (cfg->n_sig_layers > 0) {
       // x_out = z + W2 hid + b2 (line_transformer.py:180-183) and final_proj is linear (:245), so
       //   final_proj(x_out) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin)          (float64, once)
@@ -419,19 +415,15 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
         for (int m = 0; m < D; ++m) bacc += (double)W[o * D + m] * (double)b2[m];
         bf[o] = bacc;
       }
-      place_w(&H->Wfin2, Wf, D, 3 * D);
-      place(&H->bfin2, bf);
+      place_w(&H->Wfin2, Wf, bf, D, 3 * D);
     }
   }
 
   LT_HIP(hipMalloc((void**)&H->arena, ar.host.size() * sizeof(float)));
   LT_HIP(hipMemcpy(H->arena, ar.host.data(), ar.host.size() * sizeof(float), hipMemcpyHostToDevice));
   for (auto& f : fix) *f.dst = H->arena + f.off;
-  {  // split-precision copies of the GEMM weights: made on the device (linetr_net.hip owns the kernels)
-    std::vector<GemmWSpec> specs;
-    for (auto& w : gemm_w) specs.push_back({*w.dst, w.rows, w.K, w.st});
-    if (int e = make_split_copies(H.get(), specs)) return e;
-  }
+  // split-precision copies of the GEMM weights: made on the device (linetr_net.hip owns the kernels)
+  if (int e = make_split_copies(H.get(), gemm_w)) return e;
   if (const char* e = getenv("LINETR_PRECISION")) {
     if (!strcmp(e, "f32")) H->precision = LINETR_PREC_F32;
     else if (!strcmp(e, "bf16x3")) H->precision = LINETR_PREC_BF16X3;

@@ -2,7 +2,9 @@
 // GEMM dispatcher, and every kernel of the descriptor network (csrc/lt_*.h).  The experiments build adds its paths through a
 // few hooks, defined in experiments/csrc/lt_x_net.h, which this file includes behind sig_network.
 #include <algorithm>
+#include <array>
 #include <numeric>
+#include <set>
 
 #include "lt_handle.h"
 #include "lt_gemm.h"
@@ -21,25 +23,35 @@ using namespace lt;
 
 namespace {
 
-const char* gemm_class_name(const GemmArgs& g, int groups, const char* kind) {
-  const char* tile;
-  if (strcmp(kind, "gemm_f32") != 0) {
-    static const char* tile_env = LT_XENV("LINETR_GEMM_TILE");
-    tile = tile_env ? tile_env : split_tile_name(g, groups, strcmp(kind, "gemm_bf16x6") == 0 ? 3 : 2);
-  } else if (g.N % 128 != 0) tile = "128x64";
-  else {
-    int64_t big = (int64_t)cdiv(g.M, 128) * (g.N / 128) * groups;
-    tile = big >= 384 ? "128x128" : "64x128";
-  }
+// profile class of a GEMM launch, "<kind>_<tile>" (bench.py maps these names to kernel symbols), from a table made once.  tile:
+// an F32Tile in the f32 mode (LINETR_PREC_F32 = 0), a SplitTile otherwise
+const char* gemm_class_name(int precision, int tile, const GemmArgs& g, int groups) {
+  static const auto names = [] {
+    const char* kind[4] = {"gemm_f32", "gemm_bf16x3", "gemm_bf16x6", "gemm_f16x3"};   // by LINETR_PREC_*
+    std::array<std::array<std::string, (int)SplitTile::count>, 4> n;
+    for (int p = 0; p < 4; ++p)
+      for (int t = 0; t < (p ? (int)SplitTile::count : (int)F32Tile::count); ++t)
+        n[p][t] = std::string(kind[p]) + "_" + (p ? tile_name((SplitTile)t) : tile_name((F32Tile)t));
+    return n;
+  }();
+  const std::string& name = names[precision][tile];
   // LINETR_PROFILE_SHAPES=1: one profile class per GEMM shape (tuning aid)
   static const bool by_shape = LT_XENV("LINETR_PROFILE_SHAPES") != nullptr;
-  static std::map<std::string, std::string> names;
+  if (!by_shape) return name.c_str();
+  static std::mutex mu;
+  static std::set<std::string> shapes;
   char buf[160];
-  if (by_shape) snprintf(buf, sizeof buf, "%s_%s[M=%d,N=%d,K=%d,g=%d]", kind, tile, g.M, g.N, g.K, groups);
-  else snprintf(buf, sizeof buf, "%s_%s", kind, tile);
-  auto it = names.emplace(buf, buf).first;
-  return it->second.c_str();
+  snprintf(buf, sizeof buf, "%s[M=%d,N=%d,K=%d,g=%d]", name.c_str(), g.M, g.N, g.K, groups);
+  std::lock_guard<std::mutex> lock(mu);
+  return shapes.insert(buf).first->c_str();
 }
+
+// Operands of run_gemm, row-major with row strides in floats.  A: the left operand; with p2 its columns K1.. come from a second
+// matrix ([A | A2]).  Y: the output.
+struct GemmA { const float* p; int ld; const float* p2 = nullptr; int ld2 = 0, K1 = 0; };
+struct GemmY { float* p; int ld; };
+// n independent products over consecutive N-row blocks of the weight (and of its bias); group i reads A + i gA, writes Y + i gY
+struct GemmGroups { int n, N; int64_t gA, gY; };
 
 struct NormSpec {          // row normalisation that follows a [M,256] GEMM (see GemmArgs::norm)
   int mode = 0;            // 1 LayerNorm, 2 L2
@@ -51,83 +63,105 @@ struct NormSpec {          // row normalisation that follows a [M,256] GEMM (see
 
 // the experiments build's hooks (experiments/csrc/lt_x_net.h)
 #ifdef LINETR_EXPERIMENTS
-int x_gemm(LinetrHandle*, hipStream_t, SplitGemmArgs& sa, const LinetrHandle::SplitW&, int groups, const NormSpec*, double fl, double by, bool& done);
+int x_gemm(LinetrHandle*, hipStream_t, SplitGemmArgs& sa, const GemmW& w, int groups, const NormSpec*, double fl, double by, bool& done);
 int x_split_weights(LinetrHandle* H, std::vector<GemmWSpec>& weights);
 int64_t x_ws_bytes(const LinetrHandle* h, int N);
 #endif
 
-int run_gemm(LinetrHandle* h, hipStream_t st, const float* A, int lda, const float* A2, int lda2, int K1,
-             const float* W, const float* bias, const float* R, int ldr, float* Y, int ldy, int M, int N,
-             int K, int act, int groups = 1, int64_t gA = 0, int64_t gW = 0, int64_t gBias = 0, int64_t gY = 0,
-             const NormSpec* fused_norm = nullptr) {
+// the kernels' arguments of Y = norm(act(A W^T + b) (+ R)), R with Y's row stride; fails on a shape the weight w does not have
+int gemm_args(const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, const float* R, const GemmGroups* grp,
+              const NormSpec* ns, GemmArgs& g) {
+  const int groups = grp ? grp->n : 1, N = grp ? grp->N : w.rows;
+  if (A.p2 && (A.K1 <= 0 || A.K1 >= w.K)) return fail(LINETR_E_ARG, "gemm: split point K1 = %d outside (0, K = %d)", A.K1, w.K);
+  if ((int64_t)N * groups > w.rows) return fail(LINETR_E_ARG, "gemm: %d groups of %d rows exceed the weight's %d", groups, N, w.rows);
+  g = GemmArgs{};
+  g.A = A.p; g.lda = A.ld; g.A2 = A.p2; g.lda2 = A.ld2; g.K1 = A.K1;
+  g.W = w.W; g.ldw = w.K; g.bias = w.b; g.R = R; g.ldr = Y.ld; g.Y = Y.p; g.ldy = Y.ld;
+  g.M = M; g.N = N; g.K = w.K; g.act = act;
+  if (grp) { g.gA = grp->gA; g.gW = (int64_t)N * w.K; g.gBias = N; g.gY = grp->gY; }
+  if (ns) { g.norm = ns->mode; g.gamma = ns->gamma; g.beta = ns->beta; g.add2 = ns->add2; g.ldadd2 = D; g.eps = ns->eps; }
+  return LINETR_OK;
+}
+
+int run_gemm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, const float* R = nullptr,
+             const GemmGroups* grp = nullptr, const NormSpec* fused_norm = nullptr) {
   GemmArgs g;
-  g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = K1;
-  g.W = W; g.ldw = K; g.bias = bias; g.R = R; g.ldr = ldr; g.Y = Y; g.ldy = ldy;
-  g.M = M; g.N = N; g.K = K; g.act = act;
-  g.gA = gA; g.gW = gW; g.gBias = gBias; g.gY = gY;
-  if (fused_norm) {
-    g.norm = fused_norm->mode; g.gamma = fused_norm->gamma; g.beta = fused_norm->beta;
-    g.add2 = fused_norm->add2; g.ldadd2 = D; g.eps = fused_norm->eps;
-  }
-  const double fl = 2.0 * M * (double)N * K * groups;
-  const double by = 4.0 * groups * ((double)M * K + (double)N * K + (double)M * N);
+  if (int e = gemm_args(w, M, A, Y, act, R, grp, fused_norm, g)) return e;
+  const int groups = grp ? grp->n : 1;
+  const double fl = 2.0 * M * (double)g.N * g.K * groups;
+  const double by = 4.0 * groups * ((double)M * g.K + (double)g.N * g.K + (double)M * g.N);
   if (h->precision == LINETR_PREC_F32) {
-    ProfScope ps(h, st, gemm_class_name(g, groups, "gemm_f32"), fl, by);
+    ProfScope ps(h, st, gemm_class_name(LINETR_PREC_F32, (int)f32_tile(g, groups), g, groups), fl, by);
     return gemm_launch(g, groups, st);
   }
-  auto it = h->split.find(W);
-  if (it == h->split.end()) return fail(LINETR_E_ARG, "gemm: weight has no split-bf16 copy");
   SplitGemmArgs sa;
   sa.g = g;
 #ifdef LINETR_EXPERIMENTS
   bool done = false;   // hands out the stream-K workspace; done: the row-owner GEMM took the launch
-  if (int e = x_gemm(h, st, sa, it->second, groups, fused_norm, fl, by, done); e || done) return e;
+  if (int e = x_gemm(h, st, sa, w, groups, fused_norm, fl, by, done); e || done) return e;
 #endif
-  if (h->precision == LINETR_PREC_BF16X3) {
-    sa.Wsp = h->split_arena + it->second.off2;
-    sa.gWsp = gW * 4;
-    ProfScope ps(h, st, gemm_class_name(g, groups, "gemm_bf16x3"), fl, by);
-    return gemm_split_launch<2>(sa, groups, st);
-  }
-  if (h->precision == LINETR_PREC_F16X3) {
-    sa.Wsp = h->split_arena + it->second.offh;
-    sa.gWsp = gW * 4;
-    ProfScope ps(h, st, gemm_class_name(g, groups, "gemm_f16x3"), fl, by);
-    return gemm_split_launch<2, 1>(sa, groups, st);
-  }
   // every token row of the batch through a K = 128 layer: weights stay in registers, rows stream (lt_gemm_ws.h)
-  if (groups == 1 && !A2 && !R && !fused_norm && it->second.offst && gemm_ws_fits(M, N, K, lda, ldy, act) && !LT_XENV("LINETR_NO_GEMM_WS")) {
+  if (h->precision == LINETR_PREC_BF16X6 && groups == 1 && !A.p2 && !R && !fused_norm && w.st &&
+      gemm_ws_fits(M, g.N, g.K, A.ld, Y.ld, act) && !LT_XENV("LINETR_NO_GEMM_WS")) {
     WsGemmArgs a;
-    a.A = A; a.lda = lda; a.Wst = h->split_arena + it->second.offst; a.bias = bias ? bias : h->zeros; a.Y = Y; a.ldy = ldy; a.M = M; a.act = act;
+    a.A = A.p; a.lda = A.ld; a.Wst = w.st; a.bias = w.b ? w.b : h->zeros; a.Y = Y.p; a.ldy = Y.ld; a.M = M; a.act = act;
     ProfScope ps(h, st, "gemm_bf16x6_ws64x256", fl, by);
     return gemm_ws_launch(a, st);
   }
-  sa.Wsp = h->split_arena + it->second.off3;
-  sa.gWsp = gW * 6;
-  ProfScope ps(h, st, gemm_class_name(g, groups, "gemm_bf16x6"), fl, by);
-  return gemm_split_launch<3>(sa, groups, st);
+  SplitTile tile;
+  if (int e = pick_split_tile(g, groups, h->precision == LINETR_PREC_BF16X6 ? 3 : 2, tile)) return e;
+  ProfScope ps(h, st, gemm_class_name(h->precision, (int)tile, g, groups), fl, by);
+  switch (h->precision) {
+    case LINETR_PREC_BF16X3: sa.Wsp = w.s2; sa.gWsp = g.gW * 4; return gemm_split_launch<2>(sa, groups, tile, st);
+    case LINETR_PREC_F16X3: sa.Wsp = w.h2; sa.gWsp = g.gW * 4; return gemm_split_launch<2, 1>(sa, groups, tile, st);
+    default: sa.Wsp = w.s3; sa.gWsp = g.gW * 6; return gemm_split_launch<3>(sa, groups, tile, st);
+  }
 }
 
-// Y[M,256] = norm(epi(A W^T + bias) (+ R)) (+ add2).  The split-bf16 128x256 tile owns complete rows and normalises them
-// in its epilogue (one launch and one [M,256] round trip less); every other case runs the GEMM into `tmp` and then
-// row_norm_kernel.  Same arithmetic either way.
-int run_gemm_norm(LinetrHandle* h, hipStream_t st, const float* A, int lda, const float* A2, int lda2, int K1,
-                  const float* W, const float* bias, const float* R, float* tmp, float* Y, int M, int K,
+// Y[M,256] = norm(epi(A W^T + bias) (+ R)) (+ add2), R and Y with row stride 256.  The split-bf16 128x256 tile owns complete rows
+// and normalises them in its epilogue (one launch and one [M,256] round trip less); every other case runs the GEMM into `tmp` and
+// then row_norm_kernel.  Same arithmetic either way.
+int run_gemm_norm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA& A, const float* R, float* tmp, float* Y,
                   const NormSpec& ns) {
-  const bool no_fuse = LT_XENV("LINETR_NO_FUSED_NORM") != nullptr;   // tuning / test aid (read per call)
-  bool fuse = !no_fuse && h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_GEMM_TILE");
-  if (fuse) {
-    GemmArgs g{};
-    g.M = M; g.N = D; g.K = K; g.lda = lda; g.ldy = D; g.ldr = D; g.R = R; g.A2 = A2; g.lda2 = lda2; g.K1 = K1;
-    fuse = strcmp(split_tile_name(g, 1, h->precision == LINETR_PREC_BF16X6 ? 3 : 2), "128x256") == 0;
-  }
-  if (fuse) return run_gemm(h, st, A, lda, A2, lda2, K1, W, bias, R, D, Y, D, M, D, K, ACT_NONE, 1, 0, 0, 0, 0, &ns);
-  if (int e = run_gemm(h, st, A, lda, A2, lda2, K1, W, bias, R, D, tmp, D, M, D, K, ACT_NONE)) return e;
+  if (w.rows != D) return fail(LINETR_E_ARG, "gemm_norm: the weight has %d rows, not %d", w.rows, D);
+  GemmArgs g;   // (LINETR_NO_FUSED_NORM: a tuning / test aid, read per call)
+  const bool fuse = !LT_XENV("LINETR_NO_FUSED_NORM") && h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_GEMM_TILE") &&
+                    !gemm_args(w, M, A, {Y, D}, ACT_NONE, R, nullptr, nullptr, g) &&
+                    split_tile(g, 1, h->precision == LINETR_PREC_BF16X6 ? 3 : 2) == SplitTile::t128x256;
+  if (fuse) return run_gemm(h, st, w, M, A, {Y, D}, ACT_NONE, R, nullptr, &ns);
+  if (int e = run_gemm(h, st, w, M, A, {tmp, D}, ACT_NONE, R)) return e;
   ProfScope ps(h, st, "row_norm", 0, (double)M * D * (ns.add2 ? 12 : 8));
   hipLaunchKernelGGL(row_norm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, tmp, M, ns.mode == 2 ? 1 : 0, ns.gamma, ns.beta,
                      ns.add2, ns.eps, Y);
   LT_LAUNCH_CHECK();
   return 0;
+}
+
+// Where one weight's split copies go in a buffer, from byte `off` on (advanced past them): the three split planes, then (with_st)
+// the split-tile image on a 1024-byte boundary.  The handle's arena and linetr_debug_gemm's scratch buffers are laid out this way.
+struct SplitOffsets { int64_t s2, s3, h2, st = -1; };
+SplitOffsets split_offsets(int64_t rows, int K, bool with_st, int64_t& off) {
+  SplitOffsets o;
+  o.s2 = off; off += align_up(rows * K * 4, 256);
+  o.s3 = off; off += align_up(rows * K * 6, 256);
+  o.h2 = off; off += align_up(rows * K * 4, 256);
+  if (with_st) { off = align_up(off, 1024); o.st = off; off += st_bytes(rows, K); }   // ST image (rows padded to 128)
+  return o;
+}
+
+// points w at its split copies at base + o, and (make) makes them from w.W on stream st
+void split_copies(GemmW& w, unsigned char* base, const SplitOffsets& o, bool make, hipStream_t st) {
+  w.s2 = base + o.s2; w.s3 = base + o.s3; w.h2 = base + o.h2;
+  w.st = o.st >= 0 ? base + o.st : nullptr;
+  if (!make) return;
+  const dim3 grid((unsigned)cdiv((int)((int64_t)w.rows * w.K / 4), 256));
+  hipLaunchKernelGGL(split_rows_kernel<2>, grid, dim3(256), 0, st, w.W, base + o.s2, (int64_t)w.rows, w.K);
+  hipLaunchKernelGGL(split_rows_kernel<3>, grid, dim3(256), 0, st, w.W, base + o.s3, (int64_t)w.rows, w.K);
+  hipLaunchKernelGGL((split_rows_kernel<2, 1>), grid, dim3(256), 0, st, w.W, base + o.h2, (int64_t)w.rows, w.K);
+  if (o.st >= 0) {
+    const int64_t thr = st_row_blocks(w.rows) * (w.K / 16) * 32;
+    hipLaunchKernelGGL(to_st_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st, w.W, w.K, w.rows, w.K / 16, base + o.st);
+  }
 }
 
 }  // namespace
@@ -137,34 +171,14 @@ int lt::make_split_copies(LinetrHandle* H, std::vector<GemmWSpec> weights) {
 #ifdef LINETR_EXPERIMENTS
   if (int e = x_split_weights(H, weights)) return e;
 #endif
-  size_t total = 0;
-  for (auto& w : weights) {
-    LinetrHandle::SplitW sw;
-    sw.rows = w.rows; sw.K = w.K;
-    sw.off2 = total; total += align_up(w.rows * w.K * 4, 256);
-    sw.off3 = total; total += align_up(w.rows * w.K * 6, 256);
-    sw.offh = total; total += align_up(w.rows * w.K * 4, 256);
-    // the weights that travel by LDS-DMA or stay in registers / LDS
-    if (w.st && w.rows % 16 == 0 && w.K % 32 == 0) { total = align_up(total, 1024); sw.offst = total; total += st_bytes(w.rows, w.K); }   // ST image (rows padded to 128)
-    H->split[w.W] = sw;
-  }
+  int64_t total = 0;
+  std::vector<SplitOffsets> at;
+  // the weights that travel by LDS-DMA or stay in registers / LDS get an ST image
+  for (auto& s : weights) at.push_back(split_offsets(s.w->rows, s.w->K, s.st && s.w->rows % 16 == 0 && s.w->K % 32 == 0, total));
   LT_HIP(hipMalloc((void**)&H->split_arena, total));
   LT_HIP(hipMalloc((void**)&H->zeros, 4096 * sizeof(float)));
   LT_HIP(hipMemset(H->zeros, 0, 4096 * sizeof(float)));
-  for (auto& kv : H->split) {
-    const int64_t n4 = kv.second.rows * kv.second.K / 4;
-    hipLaunchKernelGGL(split_rows_kernel<2>, dim3((unsigned)cdiv((int)n4, 256)), dim3(256), 0, 0, kv.first,
-                       H->split_arena + kv.second.off2, kv.second.rows, kv.second.K);
-    hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)cdiv((int)n4, 256)), dim3(256), 0, 0, kv.first,
-                       H->split_arena + kv.second.off3, kv.second.rows, kv.second.K);
-    hipLaunchKernelGGL((split_rows_kernel<2, 1>), dim3((unsigned)cdiv((int)n4, 256)), dim3(256), 0, 0, kv.first,
-                       H->split_arena + kv.second.offh, kv.second.rows, kv.second.K);
-    if (kv.second.offst) {
-      const int64_t thr = st_row_blocks(kv.second.rows) * (kv.second.K / 16) * 32;
-      hipLaunchKernelGGL(to_st_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, 0, kv.first, kv.second.K,
-                         (int)kv.second.rows, kv.second.K / 16, H->split_arena + kv.second.offst);
-    }
-  }
+  for (size_t i = 0; i < weights.size(); ++i) split_copies(*weights[i].w, H->split_arena, at[i], true, 0);
   LT_LAUNCH_CHECK();
   LT_HIP(hipDeviceSynchronize());
   return LINETR_OK;
@@ -412,21 +426,21 @@ int pos_encoders_bn(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, cons
                      cx, cy, scale, h->wW1, h->wb1, w.a1);
   LT_LAUNCH_CHECK();
   LT_BN(0, w.a1, rows, e0);
-  if ((e = run_gemm(h, st, w.a1, e0, nullptr, 0, 0, h->wW2, h->wb2, nullptr, 0, w.a2, e1, (int)rows, e1, e0, ACT_NONE))) return e;
+  if ((e = run_gemm(h, st, h->wW2, (int)rows, {w.a1, e0}, {w.a2, e1}, ACT_NONE))) return e;
   LT_BN(1, w.a2, rows, e1);
-  if ((e = run_gemm(h, st, w.a2, e1, nullptr, 0, 0, h->wW3, h->wb3, nullptr, 0, w.a3, e2, (int)rows, e2, e1, ACT_NONE))) return e;
+  if ((e = run_gemm(h, st, h->wW3, (int)rows, {w.a2, e1}, {w.a3, e2}, ACT_NONE))) return e;
   LT_BN(2, w.a3, rows, e2);
-  if ((e = run_gemm(h, st, w.a3, e2, nullptr, 0, 0, h->wW4, h->wb4, nullptr, 0, w.a4, e3, (int)rows, e3, e2, ACT_NONE))) return e;
+  if ((e = run_gemm(h, st, h->wW4, (int)rows, {w.a3, e2}, {w.a4, e3}, ACT_NONE))) return e;
   LT_BN(3, w.a4, rows, e3);
   hipLaunchKernelGGL(line_mlp1_kernel<false>, dim3(cdiv(N * 8, 256)), dim3(256), 0, st, sublines, resp, angle_sub, N, cx, cy, scale,
                      h->lW1, h->lb1, w.l1);
   LT_LAUNCH_CHECK();
   LT_BN(4, w.l1, N, e0);
-  if ((e = run_gemm(h, st, w.l1, e0, nullptr, 0, 0, h->lW2, h->lb2, nullptr, 0, w.l2, e1, N, e1, e0, ACT_NONE))) return e;
+  if ((e = run_gemm(h, st, h->lW2, N, {w.l1, e0}, {w.l2, e1}, ACT_NONE))) return e;
   LT_BN(5, w.l2, N, e1);
-  if ((e = run_gemm(h, st, w.l2, e1, nullptr, 0, 0, h->lW3, h->lb3, nullptr, 0, w.l3, e2, N, e2, e1, ACT_NONE))) return e;
+  if ((e = run_gemm(h, st, h->lW3, N, {w.l2, e1}, {w.l3, e2}, ACT_NONE))) return e;
   LT_BN(6, w.l3, N, e2);
-  if ((e = run_gemm(h, st, w.l3, e2, nullptr, 0, 0, h->lW4, h->lb4, nullptr, 0, w.l4, e3, N, e3, e2, ACT_NONE))) return e;
+  if ((e = run_gemm(h, st, h->lW4, N, {w.l3, e2}, {w.l4, e3}, ACT_NONE))) return e;
   LT_BN(7, w.l4, N, e3);
 #undef LT_BN
   return LINETR_OK;
@@ -447,24 +461,20 @@ int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const f
   const bool fused_mlp = fused_mlp_enabled(c);
   // layers 1-4 in one kernel (lt_tokmlp.h): the default precision and the reference's channel widths, at any size (a single pair,
   // 4 k token rows and 400 sub-lines, gains too: 42 -> 31 us for the two encoders)
-  auto st_of = [&](const float* W) -> const unsigned char* {
-    auto it = h->split.find(W);
-    return it != h->split.end() && it->second.offst ? h->split_arena + it->second.offst : nullptr;
-  };
   const bool tok_mlp_ok = fused_mlp && h->precision == LINETR_PREC_BF16X6 && e0 == 32 && e1 == 64 && e2 == 128 && e3 == 256 &&
                           !LT_XENV("LINETR_NO_TOKMLP");
-  const bool tok_mlp = tok_mlp_ok && st_of(h->wW2) && st_of(h->wW3) && st_of(h->wW4);
-  const bool line_mlp = tok_mlp_ok && st_of(h->lW2) && st_of(h->lW3) && st_of(h->lW4);
+  const bool tok_mlp = tok_mlp_ok && h->wW2.st && h->wW3.st && h->wW4.st;
+  const bool line_mlp = tok_mlp_ok && h->lW2.st && h->lW3.st && h->lW4.st;
   TokMlpArgs amw, aml;
   if (tok_mlp) {
     amw.p0 = p0; amw.p1 = p1; amw.rows = rows; amw.cx = cx; amw.cy = cy; amw.scale = scale;
-    amw.W1 = h->wW1; amw.b1 = h->wb1; amw.W2st = st_of(h->wW2); amw.b2 = h->wb2; amw.W3st = st_of(h->wW3); amw.b3 = h->wb3;
-    amw.W4st = st_of(h->wW4); amw.b4 = h->wb4; amw.Y = w.a4; amw.ldy = e3;
+    amw.W1 = h->wW1; amw.b1 = h->wb1; amw.W2st = h->wW2.st; amw.b2 = h->wW2.b; amw.W3st = h->wW3.st; amw.b3 = h->wW3.b;
+    amw.W4st = h->wW4.st; amw.b4 = h->wW4.b; amw.Y = w.a4; amw.ldy = e3;
   }
   if (line_mlp) {
     aml.p0 = sublines; aml.p1 = resp; aml.p2 = angle_sub; aml.rows = N; aml.cx = cx; aml.cy = cy; aml.scale = scale;
-    aml.W1 = h->lW1; aml.b1 = h->lb1; aml.W2st = st_of(h->lW2); aml.b2 = h->lb2; aml.W3st = st_of(h->lW3); aml.b3 = h->lb3;
-    aml.W4st = st_of(h->lW4); aml.b4 = h->lb4; aml.Y = w.l4; aml.ldy = e3;
+    aml.W1 = h->lW1; aml.b1 = h->lb1; aml.W2st = h->lW2.st; aml.b2 = h->lW2.b; aml.W3st = h->lW3.st; aml.b3 = h->lW3.b;
+    aml.W4st = h->lW4.st; aml.b4 = h->lW4.b; aml.Y = w.l4; aml.ldy = e3;
   }
   if (ts.bn) {
     if ((e = pos_encoders_bn(h, st, ts, sublines, resp, angle_sub, N, w))) return e;
@@ -483,7 +493,7 @@ int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const f
         ProfScope ps(h, st, "mlp123", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2), (double)rows * (12 + 4 * e2));
         const int rpw = mlp123_rows_per_wave(rows);
         hipLaunchKernelGGL(mlp123_kernel<true>, dim3((unsigned)cdiv((int)cdiv((int)rows, rpw), 4)), dim3(256), 0, st, p0, p1,
-                           (const float*)nullptr, rows, rpw, cx, cy, scale, h->wW1, h->wb1, h->wW2, h->wb2, h->wW3, h->wb3, w.a3);
+                           (const float*)nullptr, rows, rpw, cx, cy, scale, h->wW1, h->wb1, h->wW2.W, h->wW2.b, h->wW3.W, h->wW3.b, w.a3);
         LT_LAUNCH_CHECK();
       } else {
         {
@@ -492,10 +502,10 @@ int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const f
                              scale, h->wW1, h->wb1, w.a1);
           LT_LAUNCH_CHECK();
         }
-        if ((e = run_gemm(h, st, w.a1, e0, nullptr, 0, 0, h->wW2, h->wb2, nullptr, 0, w.a2, e1, (int)rows, e1, e0, ACT_RELU))) return e;
-        if ((e = run_gemm(h, st, w.a2, e1, nullptr, 0, 0, h->wW3, h->wb3, nullptr, 0, w.a3, e2, (int)rows, e2, e1, ACT_RELU))) return e;
+        if ((e = run_gemm(h, st, h->wW2, (int)rows, {w.a1, e0}, {w.a2, e1}, ACT_RELU))) return e;
+        if ((e = run_gemm(h, st, h->wW3, (int)rows, {w.a2, e1}, {w.a3, e2}, ACT_RELU))) return e;
       }
-      if ((e = run_gemm(h, st, w.a3, e2, nullptr, 0, 0, h->wW4, h->wb4, nullptr, 0, w.a4, e3, (int)rows, e3, e2, ACT_RELU))) return e;
+      if ((e = run_gemm(h, st, h->wW4, (int)rows, {w.a3, e2}, {w.a4, e3}, ACT_RELU))) return e;
     }
     // line encoder, as the word encoder
     if (line_mlp) {
@@ -506,7 +516,7 @@ int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const f
         ProfScope ps(h, st, "mlp123_line", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2), (double)N * (28 + 4 * e2));
         const int rpw = mlp123_rows_per_wave(N);
         hipLaunchKernelGGL(mlp123_kernel<false>, dim3((unsigned)cdiv(cdiv(N, rpw), 4)), dim3(256), 0, st, sublines, resp, angle_sub,
-                           (int64_t)N, rpw, cx, cy, scale, h->lW1, h->lb1, h->lW2, h->lb2, h->lW3, h->lb3, w.l3);
+                           (int64_t)N, rpw, cx, cy, scale, h->lW1, h->lb1, h->lW2.W, h->lW2.b, h->lW3.W, h->lW3.b, w.l3);
         LT_LAUNCH_CHECK();
       } else {
         {
@@ -515,13 +525,13 @@ int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const f
                              scale, h->lW1, h->lb1, w.l1);
           LT_LAUNCH_CHECK();
         }
-        if ((e = run_gemm(h, st, w.l1, e0, nullptr, 0, 0, h->lW2, h->lb2, nullptr, 0, w.l2, e1, N, e1, e0, ACT_RELU))) return e;
-        if ((e = run_gemm(h, st, w.l2, e1, nullptr, 0, 0, h->lW3, h->lb3, nullptr, 0, w.l3, e2, N, e2, e1, ACT_RELU))) return e;
+        if ((e = run_gemm(h, st, h->lW2, N, {w.l1, e0}, {w.l2, e1}, ACT_RELU))) return e;
+        if ((e = run_gemm(h, st, h->lW3, N, {w.l2, e1}, {w.l3, e2}, ACT_RELU))) return e;
       }
-      if ((e = run_gemm(h, st, w.l3, e2, nullptr, 0, 0, h->lW4, h->lb4, nullptr, 0, w.l4, e3, N, e3, e2, ACT_RELU))) return e;
+      if ((e = run_gemm(h, st, h->lW4, N, {w.l3, e2}, {w.l4, e3}, ACT_RELU))) return e;
     }
   }
-  return run_gemm(h, st, w.l4, e3, nullptr, 0, 0, h->lW5, h->lb5, nullptr, 0, w.lpos, D, N, D, e3, ACT_NONE);
+  return run_gemm(h, st, h->lW5, N, {w.l4, e3}, {w.lpos, D}, ACT_NONE);
 }
 
 // ---- CLS-row attention pooling + value / last-MLP projection (up to CUT_POOL)
@@ -545,8 +555,9 @@ int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_im
                        h->pool, w.pooled);
     LT_LAUNCH_CHECK();
   }
-  return run_gemm(h, st, w.pooled, HEADS * POOLW, nullptr, 0, 0, h->Watt, h->batt, nullptr, 0, w.att, D, N, DH, POOLW,
-                  ACT_NONE, HEADS, POOLW, (int64_t)DH * POOLW, DH, DH);
+  // one product per head: the head's DH rows of Watt over its pooled row
+  const GemmGroups heads{HEADS, DH, POOLW, DH};
+  return run_gemm(h, st, h->Watt, N, {w.pooled, HEADS * POOLW}, {w.att, D}, ACT_NONE, nullptr, &heads);
 }
 
 // ---- the descriptive layer's tail (up to CUT_SENTENCE): the sentence rows zA, input of the line-signature network
@@ -555,12 +566,12 @@ int sentence(LinetrHandle* h, hipStream_t& st, int N, FwdWs& w) {
   int e;
   {  // o = LN(fc(att) + cls)  (line_attention.py:36-40; the CLS residual sits in the bias)
     NormSpec ns; ns.mode = 1; ns.gamma = h->ln1g; ns.beta = h->ln1b; ns.eps = 1e-6f;
-    if ((e = run_gemm_norm(h, st, w.att, D, nullptr, 0, 0, h->Wfc, h->bfc, nullptr, w.fc, w.o, N, D, ns))) return e;
+    if ((e = run_gemm_norm(h, st, h->Wfc, N, {w.att, D}, nullptr, w.fc, w.o, ns))) return e;
   }
-  if ((e = run_gemm(h, st, w.o, D, nullptr, 0, 0, h->Wf1, h->bf1, nullptr, 0, w.f1, c.d_inner, N, c.d_inner, D, ACT_GELU))) return e;
+  if ((e = run_gemm(h, st, h->Wf1, N, {w.o, D}, {w.f1, c.d_inner}, ACT_GELU))) return e;
   // sentence = line_pos + LN(w_2(gelu(w_1 o)) + o)  (line_attention.py:79-83, line_transformer.py:128)
   NormSpec ns; ns.mode = 1; ns.gamma = h->ln2g; ns.beta = h->ln2b; ns.add2 = w.lpos; ns.eps = 1e-6f;
-  return run_gemm_norm(h, st, w.f1, c.d_inner, nullptr, 0, 0, h->Wf2, h->bf2, w.o, w.f2, w.zA, N, c.d_inner, ns);
+  return run_gemm_norm(h, st, h->Wf2, N, {w.f1, c.d_inner}, w.o, w.f2, w.zA, ns);
 }
 
 // one signature layer's attention, q/k/v rows at qkv (row stride ldq) -> msg: exact-fp32 MFMA attention in f32 mode, fp32-faithful
@@ -589,8 +600,6 @@ int sig_attention(LinetrHandle* h, hipStream_t st, const float* qkv, int ldq, co
 // q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h), z -> msg: q, k, v never reach HBM
 int sig_qkv_attention(LinetrHandle* h, hipStream_t st, const SigLayer& S, const float* z, const int* cu_dev, int n_images, int N,
                       double attn_fl, float* msg) {
-  auto it = h->split.find(S.Wqkv);
-  if (it == h->split.end() || !it->second.offst) return fail(LINETR_E_ARG, "signature layer: q/k/v weight has no split-tile image");
   static unsigned long long attr_done = 0;
   const unsigned long long dev_bit = current_device_bit();
   if (!(attr_done & dev_bit)) {
@@ -598,8 +607,8 @@ int sig_qkv_attention(LinetrHandle* h, hipStream_t st, const SigLayer& S, const 
     attr_done |= dev_bit;
   }
   ProfScope ps(h, st, "sig_qkv_attn_bf16x6", 2.0 * N * 3.0 * D * D + attn_fl, (double)N * D * 8);
-  hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, h->split_arena + it->second.offst,
-                     S.bqkv, cu_dev, msg);
+  hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, S.Wqkv.st, S.Wqkv.b,
+                     cu_dev, msg);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
@@ -629,31 +638,31 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
   int ldq = 3 * D;
   for (size_t l = 0; l < h->sig.size(); ++l) {
     const SigLayer& S = h->sig[l];
-    if (fused_qkv_attn) {
+    if (fused_qkv_attn && S.Wqkv.st) {
       if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, attn_fl, w.msgp))) return e;
     } else {
       // (with fold_next the previous layer has made them already)
       if (!fold_next || l == 0)
-        if ((e = run_gemm(h, st, z, ldz, nullptr, 0, 0, S.Wqkv, S.bqkv, nullptr, 0, w.qkv, 3 * D, N, 3 * D, D, ACT_NONE))) return e;
+        if ((e = run_gemm(h, st, S.Wqkv, N, {z, ldz}, {w.qkv, 3 * D}, ACT_NONE))) return e;
       if ((e = sig_attention(h, st, qkv, ldq, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
     }
-    if ((e = run_gemm(h, st, z, ldz, w.msgp, D, D, S.W1, S.b1, nullptr, 0, w.hid, 2 * D, N, 2 * D, 2 * D, ts.bn ? ACT_NONE : ACT_RELU))) return e;
+    if ((e = run_gemm(h, st, S.W1, N, {z, ldz, w.msgp, D, D}, {w.hid, 2 * D}, ts.bn ? ACT_NONE : ACT_RELU))) return e;
     if (ts.bn && (e = bn_train_layer(st, *ts.bn, w.hid, N, 2 * D, 2 * D, h->bn_g[8 + l], h->bn_b[8 + l], sig_bn_off + (int64_t)l * 4 * D))) return e;
     if (l + 1 == h->sig.size()) break;   // the last layer's second MLP GEMM is folded into the final projection below
     if (fold_next) {
-      if ((e = run_gemm(h, st, z, ldz, w.hid, 2 * D, D, S.Wnext, S.bnext, nullptr, 0, zq, 4 * D, N, 4 * D, 3 * D, ACT_NONE))) return e;
+      if ((e = run_gemm(h, st, S.Wnext, N, {z, ldz, w.hid, 2 * D, D}, {zq, 4 * D}, ACT_NONE))) return e;
       z = zq; ldz = 4 * D; qkv = zq + D; ldq = 4 * D;
       std::swap(zq, zq_next);
     } else {
-      if ((e = run_gemm(h, st, w.hid, 2 * D, nullptr, 0, 0, S.W2, S.b2, z, D, zn, D, N, D, 2 * D, ACT_NONE))) return e;
+      if ((e = run_gemm(h, st, S.W2, N, {w.hid, 2 * D}, {zn, D}, ACT_NONE, z))) return e;
       std::swap(z, zn);
     }
     if ((e = pipe_boundary(ts.pipe, CUT_SIG0 + (int)l, st))) return e;
   }
   NormSpec l2; l2.mode = 2;      // F.normalize(final_proj(.), dim=1)  (line_transformer.py:245-246)
-  if (h->sig.empty()) return run_gemm_norm(h, st, z, D, nullptr, 0, 0, h->Wfin, h->bfin, nullptr, zn, d_line_desc, N, D, l2);
+  if (h->sig.empty()) return run_gemm_norm(h, st, h->Wfin, N, {z, D}, nullptr, zn, d_line_desc, l2);
   // final_proj(z + W2 hid + b2) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin): one K = 768 GEMM instead of two launches
-  return run_gemm_norm(h, st, z, ldz, w.hid, 2 * D, D, h->Wfin2, h->bfin2, nullptr, zn, d_line_desc, N, 3 * D, l2);
+  return run_gemm_norm(h, st, h->Wfin2, N, {z, ldz, w.hid, 2 * D, D}, nullptr, zn, d_line_desc, l2);
 }
 }  // namespace
 
@@ -974,10 +983,10 @@ extern "C" int linetr_debug_posenc(LinetrHandle* h, int32_t which, const float* 
   const dim3 grid((unsigned)cdiv((int)cdiv((int)rows, rpw), 4));
   if (which == 0)
     hipLaunchKernelGGL(mlp123_kernel<true>, grid, dim3(256), 0, st, d_in0, d_in1, (const float*)nullptr, rows, rpw, cx, cy, scale,
-                       h->wW1, h->wb1, h->wW2, h->wb2, h->wW3, h->wb3, d_out);
+                       h->wW1, h->wb1, h->wW2.W, h->wW2.b, h->wW3.W, h->wW3.b, d_out);
   else
     hipLaunchKernelGGL(mlp123_kernel<false>, grid, dim3(256), 0, st, d_in0, d_in1, d_in2, rows, rpw, cx, cy, scale, h->lW1, h->lb1,
-                       h->lW2, h->lb2, h->lW3, h->lb3, d_out);
+                       h->lW2.W, h->lW2.b, h->lW3.W, h->lW3.b, d_out);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
@@ -990,33 +999,23 @@ extern "C" int linetr_debug_gemm(LinetrHandle* h, const float* A, int32_t lda, c
   if (K % 32 || N % 64) return fail(LINETR_E_ARG, "debug_gemm: N %% 64 == 0 and K %% 32 == 0 required");
   LT_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  if (h->precision == LINETR_PREC_F32) return run_gemm(h, st, A, lda, nullptr, 0, 0, W, bias, R, ldy, Y, ldy, M, N, K, act);
-  // caller-provided weights: split them into a scratch buffer (optionally cached by pointer)
-  auto it = h->debug_split.find(W);
-  unsigned char* buf = it != h->debug_split.end() ? it->second : nullptr;
-  const int64_t b2 = align_up((int64_t)N * K * 4, 256), b3 = align_up((int64_t)N * K * 6, 256);
-  const bool ws = N == WS_N && K == WS_K;             // the weight-stationary kernel's shape: it reads a split-tile image
-  const int64_t bst = ws ? align_up(st_bytes(N, K), 256) : 0, off_st = align_up(b2 + b3 + b2, 1024);
-  if (!buf) {
-    LT_HIP(hipMalloc((void**)&buf, off_st + bst));
-    const int64_t n4 = (int64_t)N * K / 4;
-    hipLaunchKernelGGL(split_rows_kernel<2>, dim3((unsigned)cdiv((int)n4, 256)), dim3(256), 0, st, W, buf, (int64_t)N, K);
-    hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)cdiv((int)n4, 256)), dim3(256), 0, st, W, buf + b2, (int64_t)N, K);
-    hipLaunchKernelGGL((split_rows_kernel<2, 1>), dim3((unsigned)cdiv((int)n4, 256)), dim3(256), 0, st, W, buf + b2 + b3, (int64_t)N, K);
-    if (ws) {
-      const int64_t thr = st_row_blocks(N) * (K / 16) * 32;
-      hipLaunchKernelGGL(to_st_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st, W, K, N, K / 16, buf + off_st);
-    }
+  GemmW w;
+  w.W = W; w.b = bias; w.rows = N; w.K = K;
+  unsigned char* buf = nullptr;   // this call's own scratch buffer (not cached), freed below
+  if (h->precision != LINETR_PREC_F32) {
+    // caller-provided weights: their split copies in a scratch buffer (optionally cached by pointer); the weight-stationary
+    // kernel's shape also reads a split-tile image
+    int64_t bytes = 0;
+    const SplitOffsets at = split_offsets(N, K, N == WS_N && K == WS_K, bytes);
+    auto it = h->debug_split.find(W);
+    const bool make = it == h->debug_split.end();
+    if (make) LT_HIP(hipMalloc((void**)&buf, bytes));
+    split_copies(w, make ? buf : it->second, at, make, st);
     LT_LAUNCH_CHECK();
-    if (cache_weights) h->debug_split[W] = buf;
+    if (make && cache_weights) { h->debug_split[W] = buf; buf = nullptr; }
   }
-  h->split[W] = {0, (size_t)b2, N, K, (size_t)(b2 + b3), ws ? (size_t)off_st : 0};
-  unsigned char* keep = h->split_arena;
-  h->split_arena = buf;  // the lookup inside run_gemm resolves relative to split_arena
-  int e = run_gemm(h, st, A, lda, nullptr, 0, 0, W, bias, R, ldy, Y, ldy, M, N, K, act);
-  h->split_arena = keep;
-  h->split.erase(W);
-  if (!cache_weights) {
+  const int e = run_gemm(h, st, w, M, {A, lda}, {Y, ldy}, act, R);
+  if (buf) {
     (void)hipStreamSynchronize(st);
     (void)hipFree(buf);
   }

@@ -172,18 +172,29 @@ inline int gemm_launch_t(const GemmArgs& g, int groups, hipStream_t st) {
   return 0;
 }
 
-// Picks a tile for the problem shape.  N must be a multiple of 64, K of 32.
+enum class F32Tile { t128x64, t128x128, t64x128, count };
+inline const char* tile_name(F32Tile t) {
+  static const char* const names[] = {"128x64", "128x128", "64x128"};
+  return names[(int)t];
+}
+
+// The tile gemm_launch takes for the problem shape.
+inline F32Tile f32_tile(const GemmArgs& g, int groups) {
+  if (g.N % 128 != 0) return F32Tile::t128x64;
+  // enough 128x128 tiles to fill 256 CUs twice? otherwise use 64-row tiles for more blocks
+  const int64_t big_tiles = (int64_t)cdiv(g.M, 128) * (g.N / 128) * groups;
+  return big_tiles >= 384 ? F32Tile::t128x128 : F32Tile::t64x128;
+}
+
+// N must be a multiple of 64, K of 32.
 inline int gemm_launch(const GemmArgs& g, int groups, hipStream_t st) {
   if (g.M <= 0) return 0;
   if (g.N % 64 != 0 || g.K % GEMM_BK != 0 || (g.A2 && g.K1 % GEMM_BK != 0))
     return fail(LINETR_E_ARG, "gemm: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
-  if (g.N % 128 != 0) {
-    gemm_launch_t<128, 64, 4, 1>(g, groups, st);
-  } else {
-    // enough 128x128 tiles to fill 256 CUs twice? otherwise use 64-row tiles for more blocks
-    int64_t big_tiles = (int64_t)cdiv(g.M, 128) * (g.N / 128) * groups;
-    if (big_tiles >= 384) gemm_launch_t<128, 128, 2, 2>(g, groups, st);
-    else gemm_launch_t<64, 128, 2, 2>(g, groups, st);
+  switch (f32_tile(g, groups)) {
+    case F32Tile::t128x64: gemm_launch_t<128, 64, 4, 1>(g, groups, st); break;
+    case F32Tile::t128x128: gemm_launch_t<128, 128, 2, 2>(g, groups, st); break;
+    default: gemm_launch_t<64, 128, 2, 2>(g, groups, st); break;
   }
   LT_LAUNCH_CHECK();
   return 0;

@@ -723,16 +723,22 @@ template <int PL, int FMT>
 inline void gemm_split_small_launch(const SplitGemmArgs& sa, int groups, hipStream_t st);   // lt_gemm_small.h (single-pair sizes)
 inline bool small_gemm_wins(const GemmArgs& g, int groups);
 
+enum class SplitTile { t32x32k4, t112x256, t128x64, t256x128, t128x256, t64x256, t128x128, t128x128s, t256x256, t64x64, t64x128, count };
+inline const char* tile_name(SplitTile t) {
+  static const char* const names[] = {"32x32k4", "112x256", "128x64", "256x128", "128x256", "64x256", "128x128", "128x128s", "256x256",
+                                      "64x64", "64x128"};
+  return names[(int)t];
+}
 // Tile choice, from the measured table tools/gemm_tiles_probe.py prints (bf16x6, MI355X, profiles/r02_tiles_probe.txt):
 //   * 8-wave 128x256 blocks (fixed-order pipeline, one block per CU) as soon as there are ~140 of them: 9584x512x512 runs
 //     43 us on 150 such blocks against 64 us on 300 128x128 blocks;
 //   * below that the 4-wave 64x64 tile (53 KB of LDS and 156 VGPRs: three blocks per CU) while its grid fits the
 //     768 resident slots, then 64x128 (two per CU, 512 slots), then 64x256;
 //   * single-pair sizes go to the barrier-free K-split kernel (lt_gemm_small.h).
-inline const char* split_tile_name(const GemmArgs& g, int groups, int pl = 3) {
-  if (small_gemm_wins(g, groups)) return "32x32k4";   // latency-bound sizes: barrier-free K-split kernel
-  if (g.N % 128 != 0) return "128x64";
-  if (pl == 2 && split16_wins(g, groups)) return "112x256";   // saves a round of blocks (lt_gemm_split16.h)
+inline SplitTile split_tile(const GemmArgs& g, int groups, int pl = 3) {
+  if (small_gemm_wins(g, groups)) return SplitTile::t32x32k4;   // latency-bound sizes: barrier-free K-split kernel
+  if (g.N % 128 != 0) return SplitTile::t128x64;
+  if (pl == 2 && split16_wins(g, groups)) return SplitTile::t112x256;   // saves a round of blocks (lt_gemm_split16.h)
   const int64_t r128 = cdiv(g.M, 128), r64 = cdiv(g.M, 64);
   // short K, wide N, many tiles: the single-buffered 128x128 tile (64 KB of LDS, eight waves at 102 VGPRs: two blocks =
   // 4 waves per SIMD whose prologues / epilogues overlap each other's main loops) beats the one-block-per-CU pipeline:
@@ -742,51 +748,69 @@ inline const char* split_tile_name(const GemmArgs& g, int groups, int pl = 3) {
   // r04 (profiles/r04_tiles_probe.txt): with K <= 256 and N >= 768 it already wins from ~400 tiles (9584 rows, cfg5 at 8 pairs:
   // 9584x1024x256 45.6 vs 55.4 us, 9584x768x256 30.0 vs 31.8 us)
   const int64_t t128 = r128 * (g.N / 128) * groups;
-  if (pl == 3 && ((g.K <= 256 && g.N >= 768 && t128 >= 400) || (g.K <= 128 && t128 >= 1024))) return "128x128s";
-  if (g.N % 256 == 0 && r128 * (g.N / 256) * groups >= 140) return "128x256";
+  if (pl == 3 && ((g.K <= 256 && g.N >= 768 && t128 >= 400) || (g.K <= 128 && t128 >= 1024))) return SplitTile::t128x128s;
+  if (g.N % 256 == 0 && r128 * (g.N / 256) * groups >= 140) return SplitTile::t128x256;
   // r04 probe, 9584 rows x N = 256 (75 row tiles: too few 128 x 256 blocks): two 128 x 128 s blocks per CU beat the 64 x 64 tile for
   // K <= 512 (27.7 vs 29.5 us at K = 512, 17.0 vs 18.0 at K = 256); at K = 1024 the tiles are level
-  if (pl == 3 && g.K <= 512 && t128 >= 140) return "128x128s";
-  if (g.N % 256 != 0 && (int64_t)cdiv(g.M, 256) * (g.N / 128) * groups >= 192) return "256x128";
-  if (r64 * (g.N / 64) * groups <= 768) return "64x64";
-  if (r64 * (g.N / 128) * groups <= 512) return "64x128";
-  if (g.N % 256 == 0) return r64 * (g.N / 256) * groups >= 140 ? "64x256" : "64x128";
-  return "128x128";
+  if (pl == 3 && g.K <= 512 && t128 >= 140) return SplitTile::t128x128s;
+  if (g.N % 256 != 0 && (int64_t)cdiv(g.M, 256) * (g.N / 128) * groups >= 192) return SplitTile::t256x128;
+  if (r64 * (g.N / 64) * groups <= 768) return SplitTile::t64x64;
+  if (r64 * (g.N / 128) * groups <= 512) return SplitTile::t64x128;
+  if (g.N % 256 == 0) return r64 * (g.N / 256) * groups >= 140 ? SplitTile::t64x256 : SplitTile::t64x128;
+  return SplitTile::t128x128;
 }
 
+// the tile of a split GEMM: split_tile's, or the experiments build's LINETR_GEMM_TILE override (read once: tools/gemm_tiles_probe.py
+// runs a process per tile).  Fails on a name that is no tile.
+inline int pick_split_tile(const GemmArgs& g, int groups, int pl, SplitTile& tile) {
+  static const char* forced = LT_XENV("LINETR_GEMM_TILE");
+  if (!forced) { tile = split_tile(g, groups, pl); return 0; }
+  for (int i = 0; i < (int)SplitTile::count; ++i)
+    if (!strcmp(forced, tile_name((SplitTile)i))) { tile = (SplitTile)i; return 0; }
+  return fail(LINETR_E_ARG, "LINETR_GEMM_TILE: no tile is named '%s'", forced);
+}
+
+// `tile` is pick_split_tile's choice (or a forced one: a tile the shape does not fit falls back as below)
 template <int PL, int FMT = 0>
-inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, hipStream_t st) {
+inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, SplitTile tile, hipStream_t st) {
   const GemmArgs& g = sa.g;
   if (g.M <= 0) return 0;
   if (g.N % 64 != 0 || g.K % 32 != 0 || (g.A2 && g.K1 % 32 != 0))
     return fail(LINETR_E_ARG, "gemm_split: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
-  static const char* tile_env = LT_XENV("LINETR_GEMM_TILE");  // tuning aid: force a tile
-  const char* tile = tile_env ? tile_env : split_tile_name(g, groups, PL);
   // the launcher is authoritative about the fused row normalisation: only the 128x256 tile with the LDS epilogue owns
   // complete rows of an N = 256 problem; anything else would silently skip the normalisation
   if (g.norm != 0) {
-    if (strcmp(tile, "128x256") != 0 || g.N != 256 || g.ldy % 4 != 0 || (g.R && g.ldr % 4 != 0))
-      return fail(LINETR_E_ARG, "gemm_split: fused row normalisation asked of tile %s (N=%d): dispatcher bug", tile, g.N);
+    if (tile != SplitTile::t128x256 || g.N != 256 || g.ldy % 4 != 0 || (g.R && g.ldr % 4 != 0))
+      return fail(LINETR_E_ARG, "gemm_split: fused row normalisation asked of tile %s (N=%d): dispatcher bug", tile_name(tile), g.N);
   }
-  if (!strcmp(tile, "32x32k4")) gemm_split_small_launch<PL, FMT>(sa, groups, st);
-  else if (!strcmp(tile, "112x256")) gemm_split16_launch<PL, FMT>(sa, st);
-  else if (g.N % 128 != 0 || !strcmp(tile, "128x64")) gemm_split_launch_t<128, 64, 4, 1, PL, true, FMT>(sa, groups, st);
-  else if (!strcmp(tile, "256x128")) gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT, 1, true>(sa, groups, st);
-  // (16 waves of 32 x 64 or 64 x 32 on this tile, without the software pipeline, run the cfg3 step within noise of this
-  // one: at one block per CU the extra waves meet at the same barriers)
-  else if (!strcmp(tile, "128x256") && g.N % 256 == 0) gemm_split_launch_t<128, 256, 2, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st);
-  else if (!strcmp(tile, "64x256") && g.N % 256 == 0) gemm_split_launch_t<64, 256, 1, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st);
-  else if (!strcmp(tile, "128x128")) gemm_split_launch_t<128, 128, 2, 2, PL, true, FMT>(sa, groups, st);
-  // single LDS buffer, EIGHT waves of 64 x 32 (102 VGPRs): two blocks = 4 waves per SIMD.  With four waves of 64 x 64
-  // (212 VGPRs, 2 waves per SIMD) 25472x768x256 took 76.4 us (now 73.2), 291208x256x128 206 us (now 192)
-  else if (!strcmp(tile, "128x128s")) gemm_split_launch_t<128, 128, 2, 4, PL, false, FMT>(sa, groups, st);
+  // N not a multiple of 128 takes the 128x64 tile, a 256-wide tile that N does not fit the 64x128 one, and so does 256x256 in bf16x6
+  if (g.N % 128 != 0 && tile != SplitTile::t32x32k4 && tile != SplitTile::t112x256) tile = SplitTile::t128x64;
+  if (g.N % 256 != 0 && (tile == SplitTile::t128x256 || tile == SplitTile::t64x256 || tile == SplitTile::t256x256))
+    tile = SplitTile::t64x128;
+  if (PL != 2 && tile == SplitTile::t256x256) tile = SplitTile::t64x128;
+  switch (tile) {
+    case SplitTile::t32x32k4: gemm_split_small_launch<PL, FMT>(sa, groups, st); break;
+    case SplitTile::t112x256: gemm_split16_launch<PL, FMT>(sa, st); break;
+    case SplitTile::t128x64: gemm_split_launch_t<128, 64, 4, 1, PL, true, FMT>(sa, groups, st); break;
+    case SplitTile::t256x128: gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT, 1, true>(sa, groups, st); break;
+    // (16 waves of 32 x 64 or 64 x 32 on this tile, without the software pipeline, run the cfg3 step within noise of this
+    // one: at one block per CU the extra waves meet at the same barriers)
+    case SplitTile::t128x256: gemm_split_launch_t<128, 256, 2, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st); break;
+    case SplitTile::t64x256: gemm_split_launch_t<64, 256, 1, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st); break;
+    case SplitTile::t128x128: gemm_split_launch_t<128, 128, 2, 2, PL, true, FMT>(sa, groups, st); break;
+    // single LDS buffer, EIGHT waves of 64 x 32 (102 VGPRs): two blocks = 4 waves per SIMD.  With four waves of 64 x 64
+    // (212 VGPRs, 2 waves per SIMD) 25472x768x256 took 76.4 us (now 73.2), 291208x256x128 206 us (now 192)
+    case SplitTile::t128x128s: gemm_split_launch_t<128, 128, 2, 4, PL, false, FMT>(sa, groups, st); break;
 #ifdef LINETR_EXPERIMENTS
-  else if (PL == 2 && !strcmp(tile, "256x256") && g.N % 256 == 0) gemm_split_launch_t<256, 256, 4, 2, 2, true, FMT>(sa, groups, st);
+    case SplitTile::t256x256:
+      if constexpr (PL == 2) gemm_split_launch_t<256, 256, 4, 2, 2, true, FMT>(sa, groups, st);
+      break;
 #endif
-  // 64x64: three tiles of register prefetch = 156 VGPRs = THREE blocks per CU (53 KB of LDS each); with four it was 172
-  // VGPRs = two blocks: 9584 x 256 x {256, 512, 1024} 20.9 / 33.2 / 58.8 us -> 18.6 / 29.8 / 52.8 us
-  else if (!strcmp(tile, "64x64")) gemm_split_launch_t<64, 64, 2, 2, PL, true, FMT, 3>(sa, groups, st);
-  else gemm_split_launch_t<64, 128, 2, 2, PL, true, FMT, 3>(sa, groups, st);
+    // 64x64: three tiles of register prefetch = 156 VGPRs = THREE blocks per CU (53 KB of LDS each); with four it was 172
+    // VGPRs = two blocks: 9584 x 256 x {256, 512, 1024} 20.9 / 33.2 / 58.8 us -> 18.6 / 29.8 / 52.8 us
+    case SplitTile::t64x64: gemm_split_launch_t<64, 64, 2, 2, PL, true, FMT, 3>(sa, groups, st); break;
+    default: gemm_split_launch_t<64, 128, 2, 2, PL, true, FMT, 3>(sa, groups, st); break;
+  }
   LT_LAUNCH_CHECK();
   return 0;
 }

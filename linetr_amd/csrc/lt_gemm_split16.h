@@ -227,7 +227,7 @@ inline void gemm_split16_launch(const SplitGemmArgs& sa, hipStream_t st) {
 // pipeline's shapes (M = 25 472): +6-8 % in the 3-product modes; +-0 in bf16x6, where the chip sits at its power cap and
 // the CUs a shorter round would have left idle were lending their power budget to the busy ones anyway (and this
 // kernel reads 29 % more LDS bytes per MFMA: 198 vs 214 TF on a GEMM without any quantisation effect).  So the
-// dispatcher (split_tile_name) only picks it for PL == 2.
+// dispatcher (split_tile) only picks it for PL == 2.
 inline bool split16_wins(const GemmArgs& g, int groups) {
   if (groups != 1 || g.N % 256 != 0) return false;
   const int64_t t128 = (int64_t)cdiv(g.M, 128) * (g.N / 256), t112 = (int64_t)cdiv(g.M, 112) * (g.N / 256);

@@ -14,12 +14,22 @@
 
 #include "lt_common.h"
 
+// One GEMM weight of the prepared arena, Y = A W^T + b with W [rows, K] row-major in fp32, and where its split-precision copies
+// sit in split_arena (made once by make_split_copies; nullptr = none): the 2-plane bf16 split of the bf16x3 mode, the 3-plane
+// one of bf16x6, the 2-plane fp16 split of f16x3, and the split-tile image (lt_st_image.h) of the kernels that stream it.
+struct GemmW {
+  const float* W = nullptr;
+  const float* b = nullptr;
+  int rows = 0, K = 0;
+  const unsigned char *s2 = nullptr, *s3 = nullptr, *h2 = nullptr, *st = nullptr;
+};
+
 struct SigLayer {
-  const float *Wqkv, *bqkv, *W1, *b1, *W2, *b2;  // merge conv folded into W1
-  const float* W2p = nullptr;                    // experiments build: W2 with K permuted inside 16-groups (lt_mlp_fused.h)
+  GemmW Wqkv, W1, W2;   // merge conv folded into W1
+  GemmW W2p;            // experiments build: W2 with K permuted inside 16-groups (lt_mlp_fused.h)
   // [x_out | q/k/v of the NEXT layer] = Wnext [z ; hid] + bnext: W2 + residual and the next projection as ONE contraction
   // ([4D x 3D]; all layers but the last).  Used for single-pair sizes only, where a dependent launch costs more than its flops.
-  const float *Wnext = nullptr, *bnext = nullptr;
+  GemmW Wnext;
 };
 
 struct ProfClass {
@@ -33,25 +43,25 @@ struct LinetrHandle {
   LinetrModelConfig cfg;
   int device = 0;
   float* arena = nullptr;  // all prepared weights, one allocation
-  // word / line positional encoders (BN folded)
-  const float *wW1, *wb1, *wW2, *wb2, *wW3, *wb3, *wW4, *wb4;
-  const float *lW1, *lb1, *lW2, *lb2, *lW3, *lb3, *lW4, *lb4, *lW5, *lb5;
+  // word / line positional encoders (BN folded); the first layer is no GEMM
+  const float *wW1, *wb1;
+  GemmW wW2, wW3, wW4;
+  const float *lW1, *lb1;
+  GemmW lW2, lW3, lW4, lW5;
   // line-descriptive layer (CLS-row algebra)
   lt::ClsPoolConst pool;
-  const float *Watt, *batt, *Wfc, *bfc, *ln1g, *ln1b, *Wf1, *bf1, *Wf2, *bf2, *ln2g, *ln2b;
+  GemmW Watt, Wfc, Wf1, Wf2;
+  const float *ln1g, *ln1b, *ln2g, *ln2b;
   std::vector<SigLayer> sig;
   // training-mode handle (cfg.bn_batch_stats): gamma / beta / channel count of every BatchNorm layer, in the order of the packed
   // statistics arrays of linetr_forward_train (word encoder x4, line encoder x4, one per signature layer)
   std::vector<const float*> bn_g, bn_b;
   std::vector<int> bn_c;
-  const float *Wfin, *bfin;
-  const float *Wfin2 = nullptr, *bfin2 = nullptr;   // final projection with the last signature layer's second MLP GEMM folded in
-  // split-bf16 copies of every GEMM weight (2 and 3 planes), keyed by the fp32 pointer
+  GemmW Wfin;
+  GemmW Wfin2;   // final projection with the last signature layer's second MLP GEMM folded in (no signature layers: none)
   int precision = LINETR_PREC_BF16X6;
-  unsigned char* split_arena = nullptr;
-  struct SplitW { size_t off2, off3; int64_t rows; int K; size_t offh = 0; size_t offst = 0; };  // bf16x2 planes, bf16x3 planes, fp16x2 planes, ST image (lt_st_image.h; 0 = none)
-  std::map<const float*, SplitW> split;
-  std::map<const float*, unsigned char*> debug_split;  // linetr_debug_gemm(cache_weights=1)
+  unsigned char* split_arena = nullptr;   // the split copies of every GemmW above, one allocation
+  std::map<const float*, unsigned char*> debug_split;  // linetr_debug_gemm(cache_weights=1): its split copies, by fp32 pointer
   // software pipeline of CONSECUTIVE describe calls (linetr_describe_submit / linetr_describe_join): a batch is cut into stages at
   // fixed points of the network (PipePlan), stage k of every batch runs on stream k, so stage k of batch i + 1 overlaps stage k + 1 of
   // batch i -- HBM-bound kernels under MFMA-bound ones, and the CUs a GEMM's last tile round leaves empty under another launch.
@@ -132,8 +142,9 @@ struct ProfScope {
   }
 };
 
-// one GEMM weight of the prepared arena that needs split-precision copies (made on the device by linetr_net.hip)
-struct GemmWSpec { const float* W; int64_t rows; int K; bool st; };
+// one GEMM weight of the prepared arena that needs split-precision copies (made on the device by linetr_net.hip, which points the
+// GemmW at them); st: a split-tile image as well
+struct GemmWSpec { GemmW* w; bool st; };
 int make_split_copies(LinetrHandle* H, std::vector<GemmWSpec> weights);
 
 }  // namespace lt

@@ -1,6 +1,6 @@
 """Tile table: every split-GEMM tile on a list of (M, N, K) shapes, one process per tile (LINETR_GEMM_TILE is read once).
     python tools/gemm_tiles_probe.py [bf16x6]            -> one line per (shape, tile): us and TF-equivalent
-Used to set the dispatcher's thresholds (lt_gemm_split.h: split_tile_name)."""
+Used to set the dispatcher's thresholds (lt_gemm_split.h: split_tile)."""
 import os
 import subprocess
 import sys
