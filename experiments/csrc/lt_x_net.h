@@ -148,13 +148,13 @@ int sentence_chain(LinetrHandle* h, hipStream_t st, int N, FwdWs& w) {
 int sig_network_chain(LinetrHandle* h, hipStream_t st, const int32_t* h_cu, const int* cu_dev, int n_images, int N, int max_n,
                       float* d_line_desc, FwdWs& w) {
   const double attn_fl = attn_flops(h_cu, n_images);
-  const bool small_attn = h->precision != LINETR_PREC_F32 && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
+  const int attn_kernel = sig_attn_plan(h, n_images, N, max_n).attn;
   float *z = w.zA, *zn = w.zB;
   int e;
   for (size_t l = 0;; ++l) {
     const SigLayer& S = h->sig[l];
     // (q/k/v: the previous chain has made them)
-    if ((e = sig_attention(h, st, w.qkv, 3 * D, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
+    if ((e = sig_attention(h, st, attn_kernel, w.qkv, 3 * D, cu_dev, n_images, N, max_n, attn_fl, w.msgp))) return e;
     ChainBuilder cb(h);
     const bool w1_alone = LT_XENV("LINETR_CHAIN_W1_ALONE") != nullptr;     // A/B: W1 as its own launch (all 256 CUs)
     if (w1_alone && l + 1 < h->sig.size()) {
@@ -201,7 +201,7 @@ int sig_network_fused_mlp(LinetrHandle* h, hipStream_t st, const TokenStage& ts,
   const LinetrModelConfig& c = h->cfg;
   const double attn_fl = attn_flops(h_cu, n_images);
   const int64_t sig_bn_off = 4 * (int64_t)(c.enc_channels[0] + c.enc_channels[1] + c.enc_channels[2] + c.enc_channels[3]);
-  const bool small_attn = h->precision != LINETR_PREC_F32 && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
+  const int attn_kernel = sig_attn_plan(h, n_images, N, max_n).attn;
   const bool fused_qkv_attn = !LT_XENV("LINETR_NO_FUSED_QKV_ATTN") && h->precision == LINETR_PREC_BF16X6 && max_n <= 256 &&
                               (int64_t)n_images * HEADS >= 128;
   float *z = w.zA, *zn = w.zB;
@@ -212,7 +212,7 @@ int sig_network_fused_mlp(LinetrHandle* h, hipStream_t st, const TokenStage& ts,
       if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, attn_fl, w.msgp))) return e;
     } else {
       if ((e = run_gemm(h, st, S.Wqkv, N, {z, D}, {w.qkv, 3 * D}, ACT_NONE))) return e;
-      if ((e = sig_attention(h, st, w.qkv, 3 * D, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
+      if ((e = sig_attention(h, st, attn_kernel, w.qkv, 3 * D, cu_dev, n_images, N, max_n, attn_fl, w.msgp))) return e;
     }
     if (l + 1 == h->sig.size()) break;
     if ((e = run_sig_mlp(h, st, z, w.msgp, S, zn, N))) return e;

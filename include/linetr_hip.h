@@ -17,6 +17,7 @@
  * or, for throughput:  linetr_prefilter_batch -> linetr_describe (tokenise + forward fused, var-len batch) -> linetr_match;
  * streams of batches:  linetr_describe_submit / linetr_describe_join (the same call as a software pipeline over consecutive batches).
  * ABI version 5 (r06): + linetr_describe_submit, linetr_describe_join, linetr_pipeline_max_slots.
+ * ABI version 6: + linetr_debug_sig_attention (one chosen signature-attention kernel alone, for the unit tests).
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -27,7 +28,7 @@
 extern "C" {
 #endif
 
-#define LINETR_ABI_VERSION 5
+#define LINETR_ABI_VERSION 6
 
 enum {
   LINETR_OK = 0,
@@ -397,6 +398,30 @@ int linetr_debug_posenc(LinetrHandle* h, int32_t which, const float* d_in0, cons
 int linetr_debug_gemm(LinetrHandle* h, const float* d_A, int32_t lda, const float* d_W, const float* d_bias,
                       const float* d_residual, float* d_Y, int32_t ldy, int32_t M, int32_t N, int32_t K,
                       int32_t act, int32_t cache_weights, void* stream);
+
+/* Runs ONE signature-attention kernel (models/line_transformer.py:132-154 up to, not including, the merge conv) on a
+ * var-len batch, for the unit tests (tests/test_gpu_attention.py: every kernel against a float64 reference).
+ * kernel: -1 = what the forward pass takes for this handle's precision, n_images, N = h_cu_sub[n_images] and the largest
+ *              image max_n (the choice is made by the same host function the forward pass calls), reported in *kernel_used;
+ *          0 sig_attn_kernel (exact fp32 MFMA)          -- taken in f32 mode
+ *          1 sig_attn_small_kernel (32-query blocks, the 4 waves split the KV range) -- n_images * 4 * ceil(max_n / 256) < 64
+ *          2 sig_attn_split_kernel<4>                   -- otherwise, max_n <= 128
+ *          3 sig_attn_split_kernel<8>                   -- otherwise, max_n > 128
+ *          4 sig_qkv_attn_kernel (projection + attention fused) -- bf16x6, max_n <= 256, n_images * 4 >= 128, not the
+ *                                                          folded single-pair path (small kernel and N <= 960)
+ * kernel 0-3: d_in = q/k/v rows [N][ld_in], head-major (q at column h*64 + d, k at 256 +, v at 512 +), q pre-scaled by 1/8 as
+ *             the library's projection weights make them.  ld_in = 768; 1024 is legal for kernel 1 only (q/k/v behind x_out,
+ *             the folded single-pair layout: d_in points at q, i.e. at column 256 of the [N][1024] rows).  `layer` is not read.
+ *             A forced kernel 0-3 runs whatever the handle's precision is, and each is correct for every max_n: kernels 2 and
+ *             3 walk all KV tiles of an image and spread its queries over ceil(max_n / 128) resp. ceil(max_n / 256) blocks.
+ * kernel 4:   d_in = z rows [N][256] (ld_in = 256); q/k/v are projected inside the kernel with signature layer `layer`'s weights.
+ * d_msg [N][256] head-major (c' = h*64 + d), i.e. what the kernels write BEFORE the merge conv (folded into the next GEMM).
+ * A forced kernel is launched exactly as the forward pass launches it.  Refused with LINETR_E_ARG, nothing launched: kernel 4
+ * with max_n > 256, a precision other than bf16x6, `layer` out of range or ld_in != 256; ld_in other than 768 (1024: kernel 1)
+ * for kernels 0-3; a training-mode handle; misaligned (16 bytes) or NULL tensors.  With kernel = -1 and d_in = d_msg = NULL
+ * only the choice is reported and nothing is launched.  kernel_used may be NULL.  Synchronises `stream` before returning. */
+int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32_t layer, const float* d_in, int32_t ld_in,
+                               const int32_t* h_cu_sub, int32_t n_images, float* d_msg, int32_t* kernel_used, void* stream);
 
 #ifdef LINETR_EXPERIMENTS
 /* ---- split-tile ("ST") operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h): experiments build only --------------------

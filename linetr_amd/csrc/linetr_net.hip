@@ -574,21 +574,45 @@ int sentence(LinetrHandle* h, hipStream_t& st, int N, FwdWs& w) {
   return run_gemm_norm(h, st, h->Wf2, N, {w.f1, c.d_inner}, w.o, w.f2, w.zA, ns);
 }
 
-// one signature layer's attention, q/k/v rows at qkv (row stride ldq) -> msg: exact-fp32 MFMA attention in f32 mode, fp32-faithful
-// split-bf16 (6 products) otherwise.  small: few (image, head) pairs, 32-query blocks whose 4 waves also split the KV range (a single
-// pair spreads over 56 CUs and the critical path is 2 KV chunks instead of 7); the only kernel that takes ldq != 3 D.
-int sig_attention(LinetrHandle* h, hipStream_t st, const float* qkv, int ldq, const int* cu_dev, int n_images, int N, int max_n,
-                  double fl, bool small, float* msg) {
-  if (h->precision == LINETR_PREC_F32) {
+// The signature attention's kernels (the numbers are linetr_debug_sig_attention's `kernel` argument, include/linetr_hip.h)
+enum { SIGK_F32 = 0, SIGK_SMALL = 1, SIGK_SPLIT4 = 2, SIGK_SPLIT8 = 3, SIGK_FUSED = 4 };
+// What a batch of n_images images, N sub-lines in all and max_n in the largest takes: `attn` is the kernel that reads q/k/v rows,
+// `fused` replaces it and the projection GEMM by sig_qkv_attn_kernel, `fold_next` makes the next layer's q/k/v with x_out.
+struct SigAttnPlan {
+  int attn;
+  bool fold_next, fused;
+  int kernel() const { return fused ? SIGK_FUSED : attn; }
+};
+// The ONE place where the choice is made: sig_network and linetr_debug_sig_attention(kernel = -1) both call it.
+SigAttnPlan sig_attn_plan(const LinetrHandle* h, int n_images, int N, int max_n) {
+  SigAttnPlan p;
+  // small: few (image, head) pairs, 32-query blocks whose 4 waves also split the KV range (a single pair spreads over 56 CUs and
+  // the critical path is 2 KV chunks instead of 7)
+  const bool small_attn = h->precision != LINETR_PREC_F32 && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
+  p.attn = h->precision == LINETR_PREC_F32 ? SIGK_F32 : small_attn ? SIGK_SMALL : max_n <= 128 ? SIGK_SPLIT4 : SIGK_SPLIT8;
+  // single-pair sizes (the 32-query attention is taken): x_out and the NEXT layer's q/k/v come out of ONE contraction over
+  // [z ; hid] (SigLayer::Wnext) -- one dependent launch less per layer where a launch costs more than its flops
+  p.fold_next = small_attn && N <= SIG_FOLD_MAX_ROWS && !LT_XENV("LINETR_NO_SIG_FOLD");
+  // fused q/k/v projection + attention: images of up to 256 sub-lines, and enough (image, head) blocks to fill the chip
+  p.fused = !p.fold_next && !LT_XENV("LINETR_NO_FUSED_QKV_ATTN") && h->precision == LINETR_PREC_BF16X6 && max_n <= 256 &&
+            (int64_t)n_images * HEADS >= 128;
+  return p;
+}
+
+// one signature layer's attention by kernel `kernel` (SIGK_F32 .. SIGK_SPLIT8), q/k/v rows at qkv (row stride ldq) -> msg: exact-fp32
+// MFMA attention (f32 mode), fp32-faithful split-bf16 (6 products) otherwise.  SIGK_SMALL is the only kernel that takes ldq != 3 D.
+int sig_attention(LinetrHandle* h, hipStream_t st, int kernel, const float* qkv, int ldq, const int* cu_dev, int n_images, int N,
+                  int max_n, double fl, float* msg) {
+  if (kernel == SIGK_F32) {
     ProfScope ps(h, st, "sig_attn", fl, (double)N * D * 16);
     hipLaunchKernelGGL(sig_attn_kernel, dim3(n_images, HEADS, cdiv(max_n, ATT_QT)), dim3(256), 0, st, qkv, cu_dev, msg);
   } else {
     ProfScope ps(h, st, "sig_attn_bf16x6", fl, (double)N * D * 16);
-    if (small)
+    if (kernel == SIGK_SMALL)
       // (r04: an eight-wave form -- one key chunk per wave, K fragments straight from global memory -- measured level with this
       // one, 12.6 us per launch for a cfg2 pair either way, and was not kept)
       hipLaunchKernelGGL(sig_attn_small_kernel, dim3(n_images, HEADS, cdiv(max_n, 32)), dim3(256), 0, st, qkv, cu_dev, msg, ldq);
-    else if (max_n <= 128)
+    else if (kernel == SIGK_SPLIT4)
       hipLaunchKernelGGL(sig_attn_split_kernel<4>, dim3(n_images, HEADS, cdiv(max_n, ATT_QT)), dim3(256), 0, st, qkv, cu_dev, msg);
     else
       hipLaunchKernelGGL(sig_attn_split_kernel<8>, dim3(n_images, HEADS, cdiv(max_n, 256)), dim3(512), 0, st, qkv, cu_dev, msg);
@@ -624,13 +648,8 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
   const double attn_fl = attn_flops(h_cu, n_images);
   // the signature layers' slots behind the two encoders' in the packed BatchNorm statistics
   const int64_t sig_bn_off = 4 * (int64_t)(c.enc_channels[0] + c.enc_channels[1] + c.enc_channels[2] + c.enc_channels[3]);
-  const bool small_attn = h->precision != LINETR_PREC_F32 && (int64_t)n_images * HEADS * cdiv(max_n, 256) < 64;
-  // single-pair sizes (the 32-query attention is taken): x_out and the NEXT layer's q/k/v come out of ONE contraction over
-  // [z ; hid] (SigLayer::Wnext) -- one dependent launch less per layer where a launch costs more than its flops
-  const bool fold_next = small_attn && N <= SIG_FOLD_MAX_ROWS && !LT_XENV("LINETR_NO_SIG_FOLD");
-  // fused q/k/v projection + attention: images of up to 256 sub-lines, and enough (image, head) blocks to fill the chip
-  const bool fused_qkv_attn = !fold_next && !LT_XENV("LINETR_NO_FUSED_QKV_ATTN") && h->precision == LINETR_PREC_BF16X6 &&
-                              max_n <= 256 && (int64_t)n_images * HEADS >= 128;
+  const SigAttnPlan plan = sig_attn_plan(h, n_images, N, max_n);
+  const bool fold_next = plan.fold_next, fused_qkv_attn = plan.fused;
   float *z = w.zA, *zn = w.zB;     // the layer's input rows (row stride ldz) and the next layer's
   int ldz = D;
   float *zq = w.zqA, *zq_next = w.zqB;   // fold_next: [x_out | q/k/v of the next layer] rows; z is the head of one (ldz = 4 D)
@@ -644,7 +663,7 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
       // (with fold_next the previous layer has made them already)
       if (!fold_next || l == 0)
         if ((e = run_gemm(h, st, S.Wqkv, N, {z, ldz}, {w.qkv, 3 * D}, ACT_NONE))) return e;
-      if ((e = sig_attention(h, st, qkv, ldq, cu_dev, n_images, N, max_n, attn_fl, small_attn, w.msgp))) return e;
+      if ((e = sig_attention(h, st, plan.attn, qkv, ldq, cu_dev, n_images, N, max_n, attn_fl, w.msgp))) return e;
     }
     if ((e = run_gemm(h, st, S.W1, N, {z, ldz, w.msgp, D, D}, {w.hid, 2 * D}, ts.bn ? ACT_NONE : ACT_RELU))) return e;
     if (ts.bn && (e = bn_train_layer(st, *ts.bn, w.hid, N, 2 * D, 2 * D, h->bn_g[8 + l], h->bn_b[8 + l], sig_bn_off + (int64_t)l * 4 * D))) return e;
@@ -1019,5 +1038,47 @@ extern "C" int linetr_debug_gemm(LinetrHandle* h, const float* A, int32_t lda, c
     (void)hipStreamSynchronize(st);
     (void)hipFree(buf);
   }
+  return e;
+}
+
+extern "C" int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32_t layer, const float* d_in, int32_t ld_in,
+                                          const int32_t* h_cu, int32_t n_images, float* d_msg, int32_t* kernel_used, void* stream) {
+  if (!h) return fail(LINETR_E_ARG, "debug_sig_attention: null handle");
+  if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_sig_attention: a training-mode handle (bn_batch_stats = 1) is not served");
+  if (kernel < -1 || kernel > SIGK_FUSED) return fail(LINETR_E_ARG, "debug_sig_attention: kernel must be -1 .. 4");
+  if (int e = check_cu(h_cu, n_images)) return e;
+  const int N = h_cu[n_images];
+  int max_n = 0;
+  for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
+  const bool query_only = kernel == -1 && !d_in && !d_msg;
+  if (kernel == -1) kernel = sig_attn_plan(h, n_images, N, max_n).kernel();
+  if (kernel_used) *kernel_used = kernel;
+  if (query_only) return LINETR_OK;
+  // what a kernel is not written for is refused, not launched
+  if (kernel == SIGK_FUSED) {
+    if (h->precision != LINETR_PREC_BF16X6) return fail(LINETR_E_ARG, "debug_sig_attention: the fused kernel runs in bf16x6 mode only");
+    if (max_n > 256) return fail(LINETR_E_ARG, "debug_sig_attention: the fused kernel takes images of up to 256 sub-lines");
+    if (layer < 0 || layer >= (int)h->sig.size()) return fail(LINETR_E_ARG, "debug_sig_attention: layer out of range");
+    if (!h->sig[layer].Wqkv.st) return fail(LINETR_E_ARG, "debug_sig_attention: the layer has no split-tile weight image");
+    if (ld_in != D) return fail(LINETR_E_ARG, "debug_sig_attention: the fused kernel reads z rows, ld_in must be 256");
+  } else if (ld_in != 3 * D && !(kernel == SIGK_SMALL && ld_in == 4 * D)) {
+    return fail(LINETR_E_ARG, "debug_sig_attention: ld_in must be 768 (or 1024, sig_attn_small only)");
+  }
+  if (N <= 0) return LINETR_OK;
+  if (!d_in || !d_msg) return fail(LINETR_E_ARG, "debug_sig_attention: null tensor");
+  if (((uintptr_t)d_in | (uintptr_t)d_msg) % 16) return fail(LINETR_E_ARG, "debug_sig_attention: tensors must be 16-byte aligned");
+  LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  int* cu_dev = nullptr;
+  LT_HIP(hipMalloc((void**)&cu_dev, (n_images + 1) * sizeof(int)));
+  int e = LINETR_OK;
+  if (hipMemcpyAsync(cu_dev, h_cu, (n_images + 1) * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)
+    e = fail(LINETR_E_HIP, "debug_sig_attention: cu_sub upload failed");
+  const double fl = attn_flops(h_cu, n_images);
+  if (!e)
+    e = kernel == SIGK_FUSED ? sig_qkv_attention(h, st, h->sig[layer], d_in, cu_dev, n_images, N, fl, d_msg)
+                             : sig_attention(h, st, kernel, d_in, ld_in, cu_dev, n_images, N, max_n, fl, d_msg);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(cu_dev);
   return e;
 }

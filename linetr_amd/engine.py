@@ -889,6 +889,36 @@ class Engine:
                                             int(act), int(cache_weights), self._stream()), self._L)
         return Y
 
+    SIG_KERNELS = ("sig_attn", "sig_attn_small", "sig_attn_split4", "sig_attn_split8", "sig_qkv_attn")
+
+    def sig_attention_kernel(self, cu_sub) -> int:
+        """Which signature-attention kernel (index into SIG_KERNELS) the forward pass takes for a batch with these sub-line
+        offsets at the current precision; nothing is launched."""
+        cu = np.ascontiguousarray(np.asarray(cu_sub, dtype=np.int32))
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_sig_attention(self._h, -1, 0, None, 0, cu.ctypes.data, len(cu) - 1, None,
+                                                     C.byref(used), self._stream()), self._L)
+        return used.value
+
+    def debug_sig_attention(self, kernel, x, cu_sub, layer=0, out=None):
+        """ONE signature-attention kernel alone (linetr_debug_sig_attention; diagnostics / unit tests).  kernel: -1 (the
+        forward pass's choice) or an index into SIG_KERNELS.  x: q/k/v rows [N, 768] head-major, q pre-scaled by 1/8 (kernels
+        0-3; may be the columns 256.. of [N, 1024] rows for kernel 1), or z rows [N, 256] for the fused kernel 4, which
+        projects them with signature layer `layer`.  Returns (message [N, 256] head-major, kernel used)."""
+        if x.dtype != torch.float32 or x.device != self.device or x.stride(1) != 1:
+            x = self._f32(x)
+        cu = np.ascontiguousarray(np.asarray(cu_sub, dtype=np.int32))
+        N = int(cu[-1]) if len(cu) else 0
+        if int(x.shape[0]) < N:
+            raise ValueError(f"{N} rows expected, got {int(x.shape[0])}")
+        msg = out if out is not None else torch.empty((N, D), dtype=torch.float32, device=self.device)
+        if msg.dtype != torch.float32 or msg.device != self.device or not msg.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor on the engine's device")
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_sig_attention(self._h, int(kernel), int(layer), x.data_ptr(), x.stride(0), cu.ctypes.data,
+                                                     len(cu) - 1, msg.data_ptr(), C.byref(used), self._stream()), self._L)
+        return msg, used.value
+
     # ------------------------------------------------------------------ split-tile operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h)
     def to_st(self, X):
         """fp32 [rows, K] -> ST image (uint8 tensor); K % 32 == 0."""

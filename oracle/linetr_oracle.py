@@ -236,6 +236,23 @@ def _mlp(sd: dict, prefix: str, x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def sig_attention(sd: dict, layer: int, z: torch.Tensor, dtype=None, n_heads: int = 4) -> torch.Tensor:
+    """The attention of signature layer ``layer`` BEFORE its merge conv (line_transformer.py:132-154): the three projections,
+    per-head scores / sqrt(dh), softmax over the image's own rows, message.  ``z`` is one image's rows [N,256] or a batch of
+    equally long images [B,N,256] (attention per image); the message has z's shape, channel c = d*4+h (:151).  ``dtype``
+    (e.g. torch.float64) upcasts the weights and the input first: the high-precision reference of the GPU unit tests."""
+    a = f"selfattn.layers.{layer}.attn"
+    cast = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
+    z = cast(z)
+    d = z.shape[-1]
+    dh = d // n_heads
+    qkv = [F.linear(z, cast(sd[f"{a}.proj.{j}.weight"][:, :, 0]), cast(sd[f"{a}.proj.{j}.bias"])).view(*z.shape[:-1], dh, n_heads)
+           for j in range(3)]                                                      # channel c = d*4+h (:151)
+    sc = torch.einsum("...ndh,...mdh->...hnm", qkv[0], qkv[1]) / dh ** 0.5         # :134
+    pr = F.softmax(sc, dim=-1)
+    return torch.einsum("...hnm,...mdh->...ndh", pr, qkv[2]).reshape(z.shape)
+
+
 def default_ret() -> dict:
     """line_transformer.py:284-291."""
     return {"klines": torch.empty((1, 0, 2, 2)), "sublines": torch.empty((1, 0, 2, 2)),
@@ -289,11 +306,7 @@ def forward(sd: dict, data: dict, image_shape=(480, 640), n_heads: int = 4) -> d
     l = 0
     while f"selfattn.layers.{l}.attn.merge.weight" in sd:                          # :168-183
         a = f"selfattn.layers.{l}.attn"
-        qkv = [F.linear(z, sd[f"{a}.proj.{j}.weight"][:, :, 0], sd[f"{a}.proj.{j}.bias"]).view(N, dh, n_heads)
-               for j in range(3)]                                                  # channel c = d*4+h (:151)
-        sc = torch.einsum("ndh,mdh->hnm", qkv[0], qkv[1]) / dh ** 0.5              # :134
-        pr = F.softmax(sc, dim=-1)
-        msg = torch.einsum("hnm,mdh->ndh", pr, qkv[2]).reshape(N, d)
+        msg = sig_attention(sd, l, z, n_heads=n_heads)
         msg = F.linear(msg, sd[f"{a}.merge.weight"][:, :, 0], sd[f"{a}.merge.bias"])
         z = z + _mlp(sd, f"selfattn.layers.{l}.mlp", torch.cat([z, msg], dim=1))   # :166,:181
         l += 1
@@ -380,10 +393,7 @@ def forward_train(sd: dict, data: dict, image_shape=(480, 640), n_heads: int = 4
     l = 0
     while f"selfattn.layers.{l}.attn.merge.weight" in sd:
         a = f"selfattn.layers.{l}.attn"
-        qkv = [F.linear(z, sd[f"{a}.proj.{j}.weight"][:, :, 0], sd[f"{a}.proj.{j}.bias"]).view(B, N, dh, n_heads) for j in range(3)]
-        sc = torch.einsum("bndh,bmdh->bhnm", qkv[0], qkv[1]) / dh ** 0.5           # per image (:132-136)
-        pr = F.softmax(sc, dim=-1)
-        msg = torch.einsum("bhnm,bmdh->bndh", pr, qkv[2]).reshape(M, d)
+        msg = sig_attention(sd, l, z.reshape(B, N, d), n_heads=n_heads).reshape(M, d)    # per image (:132-136)
         msg = F.linear(msg, sd[f"{a}.merge.weight"][:, :, 0], sd[f"{a}.merge.bias"])
         z = z + _mlp_train(sd, f"selfattn.layers.{l}.mlp", torch.cat([z, msg], dim=1), momentum)
         l += 1

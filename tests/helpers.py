@@ -75,3 +75,30 @@ def train_mode_batches(g, preprocess_fn, tokenizer_fn, to_dev=lambda t: t):
         batch["klines"] = batch["sublines"]           # only its length is read (models/line_transformer.py:226)
         batches.append(batch)
     return batches
+
+
+# ---- the signature attention alone (tests/test_gpu_attention.py, tools/attn_unit_report.py) ------------------------------------
+
+def to_kernel_layout(x):
+    """[N, 4, 64] (head, d) -> the library's rows [N, 256], head-major c' = h*64 + d (linetr_core.hip, signature layers)."""
+    return x.reshape(x.shape[0], 256)
+
+
+def from_reference_layout(x):
+    """Reference rows [N, 256] with channel c = d*4 + h (models/line_transformer.py:151) -> head-major c' = h*64 + d."""
+    return x.reshape(x.shape[0], 64, 4).transpose(1, 2).reshape(x.shape[0], 256)
+
+
+def attn_reference(q, k, v, cu, dtype):
+    """softmax(q k^T / 8) v per image and head over that image's rows only.  q, k, v: [N, 4, 64] with q UNSCALED (the 1/8 is
+    applied here; a power of two, so exact); cu: sub-line offsets [n_images + 1].  Returns the message [N, 256] head-major in
+    `dtype`, every operation in `dtype` on the CPU."""
+    q, k, v = (t.detach().cpu().to(dtype) for t in (q, k, v))
+    out = torch.zeros((q.shape[0], 4, 64), dtype=dtype)
+    for i in range(len(cu) - 1):
+        a, b = int(cu[i]), int(cu[i + 1])
+        if b == a:
+            continue
+        sc = torch.einsum("nhd,mhd->hnm", q[a:b] * 0.125, k[a:b])
+        out[a:b] = torch.einsum("hnm,mhd->nhd", torch.softmax(sc, dim=-1), v[a:b])
+    return to_kernel_layout(out)

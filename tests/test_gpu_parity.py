@@ -202,6 +202,51 @@ def test_batch_vs_oracle_random(engine):
         assert np.abs(ld[n0:n1].T - out["line_desc"][0].numpy()).max() < DESC_TOL
 
 
+# name -> (attention kernel the batch must take, detected lines per image, (height, width), max_tokens).  synth_lines draws lines
+# shorter than one sub-line's 168 px and the reference's max_keylines = -1 slice drops one line, so n lines are n - 1 sub-lines.
+DISPATCH_BRANCHES = {
+    "split4": (2, [41 + (88 * i) // 15 for i in range(16)], (480, 640), 21),             # 16 images of 40 .. 128 sub-lines
+    "split8": (3, [101 + (156 * i) // 19 for i in range(20)], (480, 640), 21),           # 20 images of 100 .. 256
+    "split8_cfg5": (3, [301 + (299 * i) // 5 for i in range(6)], (960, 1280), 41),       # 6 images of 300 .. 599, long tokens
+    "small_no_fold": (1, [151] * 8, (480, 640), 21),                                     # 8 x 150: N = 1200 > 960
+    "fused": (4, [3 + (254 * ((7 * i) % 40)) // 39 for i in range(40)], (480, 640), 21),  # 40 images of 2 .. 256, shuffled
+}
+
+
+@pytest.mark.parametrize("branch", list(DISPATCH_BRANCHES))
+def test_each_attention_branch_vs_oracle(branch):
+    """One ragged batch per branch of the signature attention's dispatch (linetr_net.hip: sig_attn_plan), every image against the
+    CPU oracle at DESC_TOL.  The batch is first shown to take the branch it is meant to (linetr_debug_sig_attention, kernel = -1).
+    The kernels' own unit tests are in test_gpu_attention.py; this is the same check through the whole forward pass.
+    (The oracle's share: about 0.2 .. 0.7 s per image on 16 CPU threads, under 20 s for the largest batch.)"""
+    from linetr_amd.engine import Engine
+    kernel, n_lines, hw, max_tokens = DISPATCH_BRANCHES[branch]
+    eng = Engine(synth.calibrated_state_dict(), "cuda:0", image_shape=list(hw))
+    sd = synth.to_torch_state_dict(synth.calibrated_state_dict())
+    cfg = dict(BASE_CFG, max_tokens=max_tokens)
+    rows, dds, dss = [], [], []
+    for i, n in enumerate(n_lines):
+        rows.append(synth.synth_lines(8800 + i, n, *hw))
+        dd, ds = synth.synth_dense_maps(8800 + i, *hw)
+        dds.append(dd); dss.append(ds)
+    tb, ld = run_native(eng, rows, torch.cat(dds).cuda(), torch.cat(dss).cuda(), hw, cfg)
+    assert list(np.diff(tb.cu_n)) == [n - 1 for n in n_lines]
+    if branch == "small_no_fold":
+        assert tb.cu_n[-1] > 960
+    assert eng.sig_attention_kernel(tb.cu_n) == kernel
+    ld = ld.cpu().numpy()
+    bad = []
+    for i in range(len(rows)):
+        out = oracle_image(sd, rows[i], dds[i], dss[i], hw, cfg)
+        n0, n1 = tb.cu_n[i], tb.cu_n[i + 1]
+        assert out["line_desc"].shape[2] == n1 - n0
+        err = np.abs(ld[n0:n1].T - out["line_desc"][0].numpy()).max()
+        print(f"{branch} image {i} ({n1 - n0} sub-lines): max |line_desc - oracle| = {err:.3e}")
+        if not err < DESC_TOL:
+            bad.append((i, n1 - n0, err))
+    assert not bad, bad
+
+
 def run_fused(eng, rows_list, dd, ds, hw, cfg, align_corners=False, want_tokens=False):
     recs, cu_k, cu_n = eng.prefilter(rows_list, hw[0], hw[1], remove_borders=cfg["remove_borders"],
                                      min_length=cfg["min_length"], max_keylines=cfg["max_keylines"],

@@ -58,7 +58,8 @@ def test_ragged_batch_through_the_fused_projection_attention_kernel(eng):
     """48 images with 3 .. 257 detected lines each (2 .. 256 sub-lines: one to eight 32-row wave tiles, partly filled last
     tiles, image boundaries that are not multiples of anything) described as ONE batch -- the batch runs the fused q/k/v
     projection + attention kernel (lt_attn_fused.h: >= 128 (image, head) blocks, <= 256 sub-lines per image) -- against
-    every image described alone, which runs the separate projection GEMM and the small attention kernel."""
+    every image described alone, which runs the separate projection GEMM and the small attention kernel.  (GPU against GPU;
+    the fused kernel against an independent float64 reference: test_gpu_attention.py.)"""
     counts = [3, 4, 33, 34, 65, 97, 128, 129, 160, 161, 193, 200, 224, 225, 256, 257] * 3
     lines = [synth.synth_lines(7700 + i, n, *HW) for i, n in enumerate(counts)]
     maps = [synth.synth_dense_maps(7700 + i, *HW) for i in range(len(counts))]
