@@ -360,6 +360,34 @@ int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const 
                             int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
                             float* d_dense_desc_nchw, void* stream);
 
+/* ---- SuperPoint key-point branch (models/superpoint.py:48-93, 168-187, 195-197) ---------------------- */
+
+/* Non-maximum suppression, threshold, border filter, optional top-k and (x, y) conversion for a batch of score maps, on the device:
+ * simple_nms(scores, nms_radius); nonzero(scores > keypoint_threshold); remove_borders; top_k_keypoints; flip to (x, y).
+ * d_dense_score [B,H,W].  Image b's key points lie at rows d_cu_kp[b] .. d_cu_kp[b+1] of d_keypoints [B*cap_per_image,2] (x, y) and
+ * d_scores [B*cap_per_image], in the reference's order: row-major (torch.nonzero) without a top-k or for an image with no more than
+ * max_keypoints candidates, otherwise by descending score, equal scores by ascending row-major index (a stable descending sort).
+ * Key points and scores are bit-identical to the reference's (compares, selects and copies only).  d_found[b] = the image's
+ * candidates before the top-k, never capped: an image with d_found[b] > cap_per_image has been truncated to its first
+ * cap_per_image candidates -- nothing is written past the capacity, the call still returns 0, and the caller repeats it with a
+ * larger one.  nms_radius 0..8; max_keypoints -1 (all) or 1..4096; keypoint_threshold >= 0; other values: LINETR_E_ARG.
+ * Asynchronous on `stream`; nothing inside allocates or waits.  `h` may be NULL (no weights involved; current HIP device). */
+int64_t linetr_superpoint_keypoints_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap_per_image);
+int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense_score, int32_t B, int32_t H, int32_t W, int32_t nms_radius,
+                                float keypoint_threshold, int32_t remove_borders, int32_t max_keypoints, int32_t cap_per_image,
+                                float* d_keypoints, float* d_scores, int32_t* d_cu_kp, int32_t* d_found, void* d_workspace,
+                                int64_t workspace_bytes, void* stream);
+
+/* sample_descriptors (models/superpoint.py:81-93) for the packed key points of a batch: bilinear lookup in image b's map for the
+ * rows d_cu_kp[b] .. d_cu_kp[b+1] of d_keypoints [n_total,2], L2-normalised, stored in the reference's layout: image b owns a
+ * contiguous [256, n_b] block at float offset 256 * d_cu_kp[b] of d_desc_cn.  d_dense_desc is [B,Hc,Wc,256] (dense_is_nhwc = 1,
+ * sampled in place) or [B,256,Hc,Wc] (transposed into the workspace first).  Same sampler and `align_corners` as
+ * linetr_sample_descriptors.  Asynchronous on `stream`; `h` may be NULL. */
+int64_t linetr_point_descriptors_workspace_bytes(int32_t B, int32_t Hc, int32_t Wc, int32_t dense_is_nhwc);
+int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const int32_t* d_cu_kp, int32_t B, int64_t n_total,
+                             const float* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
+                             float* d_desc_cn, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- arithmetic mode of the dense contractions ----------------------------------------------------- */
 
 /* All Linear/Conv1d(k=1) contractions run on one of three MFMA paths (fp32 in, fp32 accumulate, fp32 out):

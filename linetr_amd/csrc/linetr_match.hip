@@ -1,11 +1,12 @@
 // liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
-// multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h).
+// multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), and SuperPoint's key-point branch (lt_keypoints.h).
 #include <algorithm>
 #include <numeric>
 
 #include "lt_handle.h"
 #include "lt_match.h"
 #include "lt_producer.h"
+#include "lt_keypoints.h"
 
 using namespace lt;
 
@@ -548,6 +549,92 @@ extern "C" int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_log
   if (d_dense_score) {
     ProfScope ps(h, st, "sp_score_head", 0, (double)B * HW * (65 + 64) * 4.0);
     hipLaunchKernelGGL(sp_score_head_kernel, grid, dim3(256), 0, st, d_score_logits, d_dense_score, Hc, Wc);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// SuperPoint key-point branch (lt_keypoints.h)
+// =============================================================================================
+
+namespace {
+// workspace of linetr_superpoint_keypoints: bit mask | per-row offsets | top-k candidate keys
+struct KpLayout { int Wm; int64_t o_mask, o_rowoff, o_keys, total; };
+KpLayout kp_layout(int B, int H, int W, int cap) {
+  KpLayout L{};
+  L.Wm = cdiv(W, 32);
+  int64_t o = 0;
+  L.o_mask = o; o += align_up((int64_t)B * H * L.Wm * 4, 256);
+  L.o_rowoff = o; o += align_up((int64_t)B * H * 4, 256);
+  L.o_keys = o; o += align_up((int64_t)B * cap * 8, 256);
+  L.total = o + 256;
+  return L;
+}
+
+// sp_nms_kernel takes more than 64 KiB of dynamic LDS: raised once per device
+bool kp_lds_ok() {
+  static unsigned long long done = 0, bad = 0;
+  static std::mutex m;
+  const unsigned long long dev_bit = current_device_bit();
+  std::lock_guard<std::mutex> lk(m);
+  if (!(done & dev_bit)) {
+    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(sp_nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp_nms_lds(KP_MAX_R)) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); bad |= dev_bit; }
+    done |= dev_bit;
+  }
+  return !(bad & dev_bit);
+}
+}  // namespace
+
+extern "C" int64_t linetr_superpoint_keypoints_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap_per_image) {
+  return kp_layout(std::max(B, 0), std::max(H, 0), std::max(W, 0), std::max(cap_per_image, 0)).total;
+}
+
+extern "C" int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense_score, int32_t B, int32_t H, int32_t W, int32_t nms_radius,
+                                           float keypoint_threshold, int32_t remove_borders, int32_t max_keypoints, int32_t cap_per_image,
+                                           float* d_keypoints, float* d_scores, int32_t* d_cu_kp, int32_t* d_found, void* d_ws,
+                                           int64_t ws_bytes, void* stream) {
+  if (B < 0 || H <= 0 || W <= 0 || cap_per_image < 0 || (int64_t)H * W > INT32_MAX || (int64_t)B * H > INT32_MAX)
+    return fail(LINETR_E_ARG, "superpoint_keypoints: bad shape B=%d H=%d W=%d cap=%d", B, H, W, cap_per_image);
+  if (nms_radius < 0 || nms_radius > KP_MAX_R) return fail(LINETR_E_ARG, "superpoint_keypoints: nms_radius %d outside 0..%d", nms_radius, KP_MAX_R);
+  if (max_keypoints < -1 || max_keypoints == 0 || max_keypoints > KP_MAX_K)
+    return fail(LINETR_E_ARG, "superpoint_keypoints: max_keypoints %d (need -1 or 1..%d)", max_keypoints, KP_MAX_K);
+  // suppressed pixels hold 0 in the reference's map: with a threshold below 0 they would all be key points
+  if (!(keypoint_threshold >= 0.f)) return fail(LINETR_E_ARG, "superpoint_keypoints: keypoint_threshold must be >= 0");
+  if (remove_borders < 0) return fail(LINETR_E_ARG, "superpoint_keypoints: remove_borders must be >= 0");
+  if (!d_cu_kp || (B > 0 && (!d_dense_score || !d_found || !d_ws || (cap_per_image > 0 && (!d_keypoints || !d_scores)))))
+    return fail(LINETR_E_ARG, "superpoint_keypoints: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  if (B == 0) { LT_HIP(hipMemsetAsync(d_cu_kp, 0, 4, st)); return LINETR_OK; }
+  const KpLayout L = kp_layout(B, H, W, cap_per_image);
+  if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "superpoint_keypoints: workspace too small (need %lld)", (long long)L.total);
+  if (!kp_lds_ok()) return fail(LINETR_E_HIP, "superpoint_keypoints: the device refuses the kernels' dynamic LDS");
+  char* base = (char*)d_ws;
+  unsigned* mask = (unsigned*)(base + L.o_mask);
+  int* row_off = (int*)(base + L.o_rowoff);
+  unsigned long long* keys = max_keypoints >= 0 ? (unsigned long long*)(base + L.o_keys) : nullptr;
+  const int r = nms_radius, TH = kp_tile_h(r);
+  const double map_bytes = (double)B * H * W * 4, mask_bytes = (double)B * H * L.Wm * 4;
+  {
+    ProfScope ps(h, st, "sp_nms", 0, map_bytes + mask_bytes);
+    hipLaunchKernelGGL(sp_nms_kernel, dim3((unsigned)cdiv(W, KP_TW), (unsigned)cdiv(H, TH), (unsigned)B), dim3(256), kp_nms_lds(r), st,
+                       d_dense_score, H, W, r, TH, keypoint_threshold, remove_borders, mask, L.Wm);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "sp_kp_compact", 0, 2 * mask_bytes + 3.0 * B * H * 4);
+    hipLaunchKernelGGL(sp_kp_scan_kernel, dim3((unsigned)B), dim3(256), 0, st, (const unsigned*)mask, H, L.Wm, row_off, d_found);
+    hipLaunchKernelGGL(sp_kp_offsets_kernel, dim3(1), dim3(256), 0, st, (const int*)d_found, B, cap_per_image, max_keypoints, d_cu_kp);
+    hipLaunchKernelGGL(sp_kp_emit_kernel, dim3((unsigned)(((int64_t)B * H + 3) / 4)), dim3(256), 0, st, d_dense_score, (const unsigned*)mask,
+                       (const int*)row_off, (const int*)d_cu_kp, (int64_t)B * H, H, W, L.Wm, cap_per_image, d_keypoints, d_scores, keys);
+    LT_LAUNCH_CHECK();
+  }
+  if (keys) {
+    ProfScope ps(h, st, "sp_kp_topk", 0, (double)B * cap_per_image * 8);
+    hipLaunchKernelGGL(sp_kp_topk_kernel, dim3((unsigned)B), dim3(512), 0, st, (const unsigned long long*)keys, (const int*)d_found,
+                       (const int*)d_cu_kp, cap_per_image, max_keypoints, W, d_keypoints, d_scores);
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;

@@ -300,6 +300,46 @@ extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points,
   return LINETR_OK;
 }
 
+// sample_descriptors (models/superpoint.py:81-93) for the packed key points of a batch (the output of linetr_superpoint_keypoints)
+extern "C" int64_t linetr_point_descriptors_workspace_bytes(int32_t B, int32_t Hc, int32_t Wc, int32_t dense_is_nhwc) {
+  return dense_is_nhwc ? 0 : align_up((int64_t)std::max(B, 0) * std::max(Hc, 0) * std::max(Wc, 0) * D * 4, 256);
+}
+
+extern "C" int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const int32_t* d_cu_kp, int32_t B, int64_t n_total,
+                                        const float* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
+                                        float* d_desc_cn, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (B < 0 || n_total < 0 || Hc <= 0 || Wc <= 0 || n_total > INT32_MAX) return fail(LINETR_E_ARG, "point_descriptors: bad shape");
+  if (B == 0 || n_total == 0) return LINETR_OK;
+  if (!d_keypoints || !d_cu_kp || !d_dense_desc || !d_desc_cn) return fail(LINETR_E_ARG, "point_descriptors: null pointer");
+  if (ws_bytes < linetr_point_descriptors_workspace_bytes(B, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
+    return fail(LINETR_E_WORKSPACE, "point_descriptors: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  {   // 65 KiB of dynamic LDS: raised once per device
+    static unsigned long long done = 0;
+    static std::mutex m;
+    const unsigned long long dev_bit = current_device_bit();
+    std::lock_guard<std::mutex> lk(m);
+    if (!(done & dev_bit)) {
+      LT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sp_kp_desc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_DESC_LDS));
+      done |= dev_bit;
+    }
+  }
+  const int P = Hc * Wc;
+  const float* nhwc = d_dense_desc;
+  if (!dense_is_nhwc) {
+    ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * B * P * D * 4);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, B), dim3(256), 0, st, d_dense_desc, (float*)d_ws, D, P);
+    LT_LAUNCH_CHECK();
+    nhwc = (const float*)d_ws;
+  }
+  ProfScope ps(h, st, "sp_kp_desc", 0, (double)n_total * D * 4 * 5);
+  hipLaunchKernelGGL(sp_kp_desc_kernel, dim3((unsigned)((n_total + KP_DESC_N - 1) / KP_DESC_N + B)), dim3(256), KP_DESC_LDS, st, d_keypoints,
+                     d_cu_kp, B, nhwc, Hc, Wc, align_corners, d_desc_cn);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
 // =============================================================================================
 // forward
 // =============================================================================================

@@ -340,4 +340,40 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(
   *reinterpret_cast<f32x4*>(desc + tok * D + lane * 4) = o;
 }
 
+constexpr int KP_DESC_N = 64;     // key points per block
+constexpr int KP_DESC_LS = KP_DESC_N + 1;
+constexpr size_t KP_DESC_LDS = (size_t)D * KP_DESC_LS * 4;
+
+// sample_descriptors (models/superpoint.py:81-93) for the packed key points of a batch: one block = up to 64 consecutive key points of ONE image, one wave per
+// key point (sample_one), staged through LDS [256][65] so that the store along n is contiguous: image b owns [256][n_b] floats at
+// out + 256 cu_kp[b].  grid ceil(n_total / 64) + B (an upper bound of the chunks; the block finds its image in cu_kp), block 256,
+// dynamic LDS KP_DESC_LDS.
+__global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
+                                                         const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+                                                         float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float kp_tile[];
+  int chunk = blockIdx.x, b = 0, start = 0, n_b = 0;
+  for (; b < B; ++b) {
+    start = cu_kp[b];
+    n_b = cu_kp[b + 1] - start;
+    const int nch = (n_b + KP_DESC_N - 1) / KP_DESC_N;
+    if (chunk < nch) break;
+    chunk -= nch;
+  }
+  if (b >= B) return;
+  const int j0 = chunk * KP_DESC_N, nj = min(KP_DESC_N, n_b - j0);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float* img = nhwc + (int64_t)b * Hc * Wc * D;
+  for (int j = w; j < nj; j += 4) {
+    const int64_t g = (int64_t)start + j0 + j;
+    const f32x4 o = sample_one(kp[g * 2 + 0], kp[g * 2 + 1], img, Hc, Wc, align_corners, lane);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) kp_tile[(lane * 4 + c) * KP_DESC_LS + j] = o[c];
+  }
+  __syncthreads();
+  float* dst = out + (int64_t)D * start + j0;
+  if (lane < nj)
+    for (int ch = w * 64; ch < w * 64 + 64; ++ch) dst[(int64_t)ch * n_b + lane] = kp_tile[ch * KP_DESC_LS + lane];
+}
+
 }  // namespace lt

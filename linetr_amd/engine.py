@@ -133,8 +133,8 @@ class Engine:
 
     @classmethod
     def heads_only(cls, device="cuda:0"):
-        """An Engine without a LineTR model: only the weight-free entry points work (superpoint_heads, match_points,
-        match_distmat).  Used by FusedHeadSuperPoint when no LineTransformer engine is at hand."""
+        """An Engine without a LineTR model: only the weight-free entry points work (superpoint_heads, superpoint_keypoints,
+        match_points, match_distmat).  Used by FusedHeadSuperPoint when no LineTransformer engine is at hand."""
         self = cls.__new__(cls)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -846,6 +846,75 @@ class Engine:
             nat.check(self._L.linetr_superpoint_heads(self._h, ptr(sl), ptr(dr), B, Hc, Wc, ptr(score), ptr(o_nhwc),
                                                       ptr(o_nchw), self._stream()), self._L)
         return score, o_nhwc, o_nchw
+
+    def superpoint_keypoints(self, dense_score: torch.Tensor, dense_desc: torch.Tensor = None, *, nms_radius=4,
+                             keypoint_threshold=0.005, remove_borders=4, max_keypoints=-1, align_corners=False,
+                             dense_layout="nhwc"):
+        """SuperPoint's key-point branch for a batch (models/superpoint.py:168-187, 195-197) in native calls: simple_nms,
+        threshold, remove_borders, top_k_keypoints, (row, col) -> (x, y) and sample_descriptors.
+
+        dense_score [B,H,W]; dense_desc [B,Hc,Wc,256] ('nhwc', what superpoint_heads emits) or [B,256,Hc,Wc] ('nchw'), or None.
+        Returns three per-image lists: keypoints [n_b,2] (x, y), scores [n_b], descriptors [256,n_b] -- views into three batch
+        buffers -- or None in place of the descriptors when no map is given.  Key points and scores are the reference's bit for
+        bit, in its order (row-major; with max_keypoints and more candidates than that: descending score, equal scores by ascending
+        row-major index).  ONE host wait per call: the packed offsets come back before the descriptor buffer is sized.  (Maps with
+        exactly equal neighbouring scores can hold more key points than the default capacity: then the detector runs a second
+        time with the capacity it reported.)"""
+        ds = self._f32(dense_score)
+        if ds.dim() != 3:
+            raise ValueError(f"dense_score must be [B,H,W], got {tuple(ds.shape)}")
+        B, H, W = (int(v) for v in ds.shape)
+        r, k, border = int(nms_radius), int(max_keypoints), int(remove_borders)
+        thr = float(np.float32(keypoint_threshold))
+        if not 0 <= r <= 8:
+            raise ValueError(f"nms_radius must be 0..8, got {r}")
+        if k < -1 or k == 0 or k > 4096:
+            raise ValueError(f"max_keypoints must be -1 (all) or 1..4096, got {k}")
+        if not thr >= 0 or border < 0:
+            raise ValueError("keypoint_threshold and remove_borders must be >= 0")
+        if dense_layout not in ("nhwc", "nchw"):
+            raise ValueError("dense_layout must be 'nhwc' or 'nchw'")
+        dd = None
+        if dense_desc is not None:
+            dd = self._f32(dense_desc)
+            nhwc = dense_layout == "nhwc"
+            if dd.dim() != 4 or int(dd.shape[0]) != B or int(dd.shape[3 if nhwc else 1]) != D:
+                raise ValueError(f"dense_desc must be [B,Hc,Wc,{D}] (nhwc) or [B,{D},Hc,Wc] (nchw), got {tuple(dd.shape)}")
+            Hc, Wc = (int(dd.shape[1]), int(dd.shape[2])) if nhwc else (int(dd.shape[2]), int(dd.shape[3]))
+        if B == 0 or H == 0 or W == 0:
+            e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+            return ([e(0, 2) for _ in range(B)], [e(0) for _ in range(B)],
+                    [e(D, 0) for _ in range(B)] if dd is not None else None)
+        # kept points of a tie-free map lie at Chebyshev distance >= r + 1 from each other
+        cap = min(H * W, -(-H // (r + 1)) * -(-W // (r + 1)))
+        with torch.cuda.device(self.device):     # a heads-only engine has no handle: the current device is used
+            cu = torch.empty(B + 1, dtype=torch.int32, device=self.device)
+            found = torch.empty(B, dtype=torch.int32, device=self.device)
+            while True:
+                kp = torch.empty((B * cap, 2), dtype=torch.float32, device=self.device)
+                sc = torch.empty((B * cap,), dtype=torch.float32, device=self.device)
+                ws = self._workspace("keypoints", self._L.linetr_superpoint_keypoints_workspace_bytes(B, H, W, cap))
+                nat.check(self._L.linetr_superpoint_keypoints(self._h, ds.data_ptr(), B, H, W, r, thr, border, k, cap, kp.data_ptr(),
+                                                              sc.data_ptr(), cu.data_ptr(), found.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                              self._stream()), self._L)
+                h_cu, h_found = self.collect(self.to_host_async(cu, found))
+                if int(h_found.max()) <= cap:
+                    break
+                cap = int(h_found.max())         # exact ties only: once more with room for every candidate
+            n_total = int(h_cu[-1])
+            desc = None
+            if dd is not None:
+                desc = torch.empty((D * n_total,), dtype=torch.float32, device=self.device)
+                if n_total > 0:
+                    wd = self._workspace("sample", self._L.linetr_point_descriptors_workspace_bytes(B, Hc, Wc, int(nhwc)) + 256)
+                    nat.check(self._L.linetr_point_descriptors(self._h, kp.data_ptr(), cu.data_ptr(), B, n_total, dd.data_ptr(), Hc, Wc,
+                                                               int(bool(align_corners)), int(nhwc), desc.data_ptr(), wd.data_ptr(),
+                                                               wd.numel(), self._stream()), self._L)
+        o = h_cu.tolist()
+        kps = [kp[o[b]:o[b + 1]] for b in range(B)]
+        scs = [sc[o[b]:o[b + 1]] for b in range(B)]
+        descs = [desc[D * o[b]:D * o[b + 1]].view(D, o[b + 1] - o[b]) for b in range(B)] if desc is not None else None
+        return kps, scs, descs
 
     PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3}
 

@@ -42,10 +42,12 @@ class Matching(torch.nn.Module):
             # steps run on linetr_superpoint_heads and the descriptor map ALSO comes out channel-last: the tokeniser then
             # needs no NCHW -> NHWC pass.  Same dict as the reference's forward plus 'dense_descriptor_nhwc'.
             # An injected instance is used as given; config['fuse_superpoint_heads'] = False keeps the plain module.
+            # config['native_keypoints'] = True (default False) also moves the wrapper's key-point branch (NMS, threshold, border
+            # filter, top-k, descriptor lookup) from the module's per-image torch helpers to one native call per batch.
             if config.get("fuse_superpoint_heads", True) and all(hasattr(superpoint, a) for a in
                                                                   ("convPa", "convPb", "convDa", "convDb", "relu", "pool")):
                 from .superpoint import FusedHeadSuperPoint
-                superpoint = FusedHeadSuperPoint(superpoint)
+                superpoint = FusedHeadSuperPoint(superpoint, native_keypoints=config.get("native_keypoints", False))
         self.superpoint = superpoint
         self.lsd = lsd if lsd is not None else _frontend("line_detector", "LSD", config.get("lsd", {}))
         self.linetransformer = LineTransformer(config.get("linetransformer", {}))

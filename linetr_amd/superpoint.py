@@ -9,9 +9,11 @@ unchanged, or anything with the same conv attributes -- and returns the same dic
                                                                         + 'dense_descriptor_nhwc' [B,Hc,Wc,256]
 
 The extra NHWC key is the layout the line tokeniser samples from, so `Engine.describe_lines(...,
-dense_layout='nhwc')` skips its NCHW->NHWC pass.  The convolutions stay in PyTorch (MIOpen); key-point extraction
+dense_layout='nhwc')` skips its NCHW->NHWC pass.  The convolutions stay in PyTorch (MIOpen).  Key-point extraction
 (`simple_nms`, `remove_borders`, `top_k_keypoints`, `sample_descriptors`) is delegated to the wrapped module's own
-module-level functions -- those are the reference's and out of this path's scope.
+module-level functions, image by image, unless `native_keypoints=True`: then it is one `Engine.superpoint_keypoints`
+call for the batch (`linetr_superpoint_keypoints` + `linetr_point_descriptors`), fed the channel-last map the heads call
+has just produced -- same key points and scores bit for bit, one host wait per batch instead of one per image.
 """
 from __future__ import annotations
 
@@ -22,11 +24,15 @@ from torch import nn
 
 
 class FusedHeadSuperPoint(nn.Module):
-    def __init__(self, superpoint: nn.Module, engine=None, helpers=None, want_nchw: bool = True):
+    def __init__(self, superpoint: nn.Module, engine=None, helpers=None, want_nchw: bool = True,
+                 native_keypoints: bool = False, align_corners=None):
         super().__init__()
         self.sp = superpoint
         self.config = superpoint.config
         self.want_nchw = want_nchw
+        self.native_keypoints = bool(native_keypoints)
+        # grid_sample flag of the native descriptor lookup; None = the reference's own version switch (superpoint.py:88)
+        self.align_corners = align_corners
         self._engine = engine
         # simple_nms / remove_borders / top_k_keypoints / sample_descriptors of the wrapped implementation
         self._fn = helpers if helpers is not None else sys.modules[type(superpoint).__module__]
@@ -54,7 +60,10 @@ class FusedHeadSuperPoint(nn.Module):
         if d_nchw is None:                       # a view with the reference's shape (not contiguous)
             d_nchw = d_nhwc.permute(0, 3, 1, 2)
         hc, wc = int(score_logits.shape[2]), int(score_logits.shape[3])
-        keypoints, scores, descriptors = self._keypoints(dense_score, d_nchw, hc * 8, wc * 8)
+        if self.native_keypoints:
+            keypoints, scores, descriptors = self._keypoints_native(dense_score, d_nhwc)
+        else:
+            keypoints, scores, descriptors = self._keypoints(dense_score, d_nchw, hc * 8, wc * 8)
         return {"keypoints": keypoints, "scores": scores, "descriptors": descriptors, "dense_descriptor": d_nchw,
                 "dense_score": dense_score, "dense_descriptor_nhwc": d_nhwc}
 
@@ -74,4 +83,13 @@ class FusedHeadSuperPoint(nn.Module):
             kps.append(xy)
             scs.append(val)
             descs.append(fn.sample_descriptors(xy[None], dense_desc[b][None], 8)[0])
+        return kps, tuple(scs), descs
+
+    def _keypoints_native(self, dense_score, dense_desc_nhwc):
+        """The same branch for the whole batch on the device (Engine.superpoint_keypoints); same containers as _keypoints."""
+        cfg = self.config
+        align = self.align_corners if self.align_corners is not None else int(torch.__version__[2]) > 2
+        kps, scs, descs = self.engine().superpoint_keypoints(
+            dense_score, dense_desc_nhwc, nms_radius=cfg["nms_radius"], keypoint_threshold=cfg["keypoint_threshold"],
+            remove_borders=cfg["remove_borders"], max_keypoints=cfg["max_keypoints"], align_corners=align, dense_layout="nhwc")
         return kps, tuple(scs), descs
