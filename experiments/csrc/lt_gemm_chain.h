@@ -289,12 +289,7 @@ inline int gemm_chain_launch(const ChainArgs& c, hipStream_t st) {
       return fail(LINETR_E_ARG, "gemm_chain: unsupported stage %d (M=%d N=%d K=%d)", s, g.M, g.N, g.K);
   }
   constexpr int lds = 2 * (128 + 256) * (3 * 64 + 16);    // two tile buffers (156 KB); the epilogue image (128 KB) aliases them
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<gemm_chain_kernel>(lds));
   hipLaunchKernelGGL(gemm_chain_kernel, dim3(cdiv(M, 128)), dim3(512), lds, st, c);
   LT_LAUNCH_CHECK();
   return 0;

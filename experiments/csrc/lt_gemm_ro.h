@@ -233,12 +233,7 @@ inline int gemm_ro_launch(const RoGemmArgs& a, hipStream_t st) {
   if (a.N % RO_BN != 0 || a.nk1 < 1 || (a.A2 && a.nk2 < 1) || (!a.A2 && a.nk2 != 0) || !a.bias || !a.Wst || a.ldy % 4 || a.lda1 % 4 ||
       (a.A2 && a.lda2 % 4) || (a.R && a.ldr % 4) || (a.norm && (a.N != 256 || a.ldadd2 % 4)))
     return fail(LINETR_E_ARG, "gemm_ro: unsupported shape M=%d N=%d nk=%d+%d", a.M, a.N, a.nk1, a.nk2);
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ro_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RO_LDS);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<gemm_ro_kernel>(RO_LDS));
   hipLaunchKernelGGL(gemm_ro_kernel, dim3((a.N / RO_BN) * cdiv(a.M, RO_BM)), dim3(256), RO_LDS, st, a);
   LT_LAUNCH_CHECK();
   return 0;

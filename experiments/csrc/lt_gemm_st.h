@@ -251,12 +251,7 @@ inline int gemm_st_launch(const StGemmArgs& a, hipStream_t st) {
       (!a.Yst && (!a.Y || a.ldy % 4)))
     return fail(LINETR_E_ARG, "gemm_st: unsupported shape M=%d N=%d nk=%d+%d", a.M, a.N, a.nk1, a.nk2);
   constexpr int lds = 4 * STG_SLOT;
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_st_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<gemm_st_kernel<0>>(lds));
   const dim3 grid((a.N / STG_BN) * cdiv(a.M, STG_BM));
   hipLaunchKernelGGL(gemm_st_kernel<0>, grid, dim3(512), lds, st, a);
   LT_LAUNCH_CHECK();

@@ -258,16 +258,11 @@ inline int sig_mlp_kperm(int k) {
 }
 
 template <int PL, int FMT>
-inline void sig_mlp_fused_launch(const SigMlpArgs& a, hipStream_t st) {
+inline int sig_mlp_fused_launch(const SigMlpArgs& a, hipStream_t st) {
   constexpr size_t lds = 4 * 128 * (PL * 64 + 16) + 512 * sizeof(float);
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sig_mlp_fused_kernel<PL, FMT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done |= dev_bit;
-  }
+  LT_HIP((allow_dynamic_lds<sig_mlp_fused_kernel<PL, FMT>>((int)lds)));
   hipLaunchKernelGGL((sig_mlp_fused_kernel<PL, FMT>), dim3((unsigned)cdiv(a.M, 128)), dim3(256), lds, st, a);
+  return 0;
 }
 
 }  // namespace lt

@@ -181,15 +181,15 @@ int run_sig_mlp(LinetrHandle* h, hipStream_t st, const float* z, const float* ms
   if (h->precision == LINETR_PREC_BF16X3) {
     a.W1sp = S.W1.s2; a.W2sp = S.W2p.s2;
     ProfScope ps(h, st, "sig_mlp_bf16x3", fl, by);
-    sig_mlp_fused_launch<2, 0>(a, st);
+    if (int e = sig_mlp_fused_launch<2, 0>(a, st)) return e;
   } else if (h->precision == LINETR_PREC_F16X3) {
     a.W1sp = S.W1.h2; a.W2sp = S.W2p.h2;
     ProfScope ps(h, st, "sig_mlp_f16x3", fl, by);
-    sig_mlp_fused_launch<2, 1>(a, st);
+    if (int e = sig_mlp_fused_launch<2, 1>(a, st)) return e;
   } else {
     a.W1sp = S.W1.s3; a.W2sp = S.W2p.s3;
     ProfScope ps(h, st, "sig_mlp_bf16x6", fl, by);
-    sig_mlp_fused_launch<3, 0>(a, st);
+    if (int e = sig_mlp_fused_launch<3, 0>(a, st)) return e;
   }
   LT_LAUNCH_CHECK();
   return 0;

@@ -188,8 +188,8 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
   for (int enc = 0; enc < 2; ++enc) {
     const std::string pre = enc == 0 ? "klenc.word_position_enc.encoder." : "klenc.line_position_enc.encoder.";
     const int* ch = enc == 0 ? ch_w : ch_l;
-    GemmW* const Wdst[4] = {nullptr, enc == 0 ? &H->wW2 : &H->lW2, enc == 0 ? &H->wW3 : &H->lW3,
-                            enc == 0 ? &H->wW4 : &H->lW4};   // (layer 1 is no GEMM)
+    PosEncoder& E = H->enc[enc];
+    GemmW* const Wdst[4] = {nullptr, &E.W2, &E.W3, &E.W4};   // (layer 1 is no GEMM)
     for (int i = 0; i < 4; ++i) {
       const std::string c = pre + std::to_string(3 * i), bn = pre + std::to_string(3 * i + 1);
       const float* W = tm.get(c + ".weight", (int64_t)ch[i + 1] * ch[i], err);
@@ -209,7 +209,7 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
       fold_bn(W, b, g, be, mu, va, ch[i + 1], ch[i], Wf, bf);
       // layers 2-4 also get split-tile images: the one-kernel MLP of lt_tokmlp.h keeps layers 2 / 3 in LDS and layer 4 in registers as
       // such, and the weight-stationary GEMM of lt_gemm_ws.h reads layer 4's planes from one
-      if (i == 0) { place(enc == 0 ? &H->wW1 : &H->lW1, Wf); place(enc == 0 ? &H->wb1 : &H->lb1, bf); }
+      if (i == 0) { place(&E.W1, Wf); place(&E.b1, bf); }
       else place_w(Wdst[i], Wf, bf, ch[i + 1], ch[i], true);
     }
     const float* W = tm.get(pre + "12.weight", (int64_t)D * e3, err);

@@ -88,19 +88,12 @@ PairSlot* pair_slot(hipStream_t st) {
   return &(slots[{dev, st}] = ps);
 }
 
-// the one-launch matcher needs up to pair_fused_lds(PF_MAX_N1, PF_MAX_N1) bytes of dynamic LDS: raised once per device; a device that
-// refuses keeps the three launches
+// the one-launch matcher needs up to pair_fused_lds(PF_MAX_N1, PF_MAX_N1) bytes of dynamic LDS; a device that refuses keeps the
+// three launches
 bool fused_pair_lds_ok() {
-  static unsigned long long done = 0, bad = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(done & dev_bit)) {
-    const int want = (int)pair_fused_lds(PF_MAX_N1, PF_MAX_N1);
-    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(pair_match_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(pair_match_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); bad |= dev_bit; }
-    done |= dev_bit;
-  }
-  return !(bad & dev_bit);
+  const int want = (int)pair_fused_lds(PF_MAX_N1, PF_MAX_N1);
+  return allow_dynamic_lds<pair_match_fused_kernel<false>>(want) == hipSuccess &&
+         allow_dynamic_lds<pair_match_fused_kernel<true>>(want) == hipSuccess;
 }
 
 // does a single-pair call have the sizes of the one-launch matcher (pair_match_fused_kernel)?
@@ -573,18 +566,7 @@ KpLayout kp_layout(int B, int H, int W, int cap) {
 }
 
 // sp_nms_kernel takes more than 64 KiB of dynamic LDS: raised once per device
-bool kp_lds_ok() {
-  static unsigned long long done = 0, bad = 0;
-  static std::mutex m;
-  const unsigned long long dev_bit = current_device_bit();
-  std::lock_guard<std::mutex> lk(m);
-  if (!(done & dev_bit)) {
-    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(sp_nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp_nms_lds(KP_MAX_R)) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); bad |= dev_bit; }
-    done |= dev_bit;
-  }
-  return !(bad & dev_bit);
-}
+bool kp_lds_ok() { return allow_dynamic_lds<sp_nms_kernel>((int)kp_nms_lds(KP_MAX_R)) == hipSuccess; }
 }  // namespace
 
 extern "C" int64_t linetr_superpoint_keypoints_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap_per_image) {

@@ -209,6 +209,63 @@ int k2s_table(const LinetrTokens& out, int n_images, int K, int N, const int32_t
   }
   return 0;
 }
+
+// The channel-last form of n_images dense descriptor maps of P positions: the map itself when it is NHWC already (the repo's producer:
+// read in place), otherwise its transpose, made in `buf`
+int nhwc_map(LinetrHandle* h, hipStream_t st, const float* dense_desc, int dense_is_nhwc, int n_images, int P, float* buf,
+             const float*& nhwc) {
+  nhwc = dense_desc;
+  if (dense_is_nhwc) return LINETR_OK;
+  ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * n_images * P * D * 4);
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, n_images), dim3(256), 0, st, dense_desc, buf, D, P);
+  LT_LAUNCH_CHECK();
+  nhwc = buf;
+  return LINETR_OK;
+}
+
+// The token front end of linetr_tokenize and linetr_describe: line_fill -> tokenize -> layout pass -> (out.desc) sample_desc.
+struct TokenFront {
+  const LinetrLineRec* recs; int K, N; double td; int T;
+  const float *dense_desc, *dense_score;
+  int n_images, height, width, align_corners, dense_is_nhwc;
+  double clip_x, clip_y;               // end points are clipped to the caller's clip size (tokenize) or the map's own (describe)
+  float *sublines, *resp, *angle_sub;  // the caller's tensors, or workspace where it asked for none
+  int* s2l_g;                          // workspace: sub-line -> key-line of the batch
+  float* nhwc_buf;                     // workspace: the transposed map
+  bool map_always;                     // the layout pass runs without out.desc too (describe: the pooling kernel reads the map)
+  double tokenize_bytes;               // what the `tokenize` profile class is charged
+  // describe only: the compact list of real tokens, closed by one padding row per image (written by cdiv(n_pad_images, 64) more blocks)
+  float *cpnt = nullptr, *cscore = nullptr; int n_pad_images = 0; int64_t first_pad = 0;
+};
+int token_front(LinetrHandle* h, hipStream_t st, const TokenFront& a, const LinetrTokens& out, const K2sTable& k2s, int32_t* d_sub2line,
+                const float*& nhwc) {
+  {
+    ProfScope ps(h, st, "line_fill", 0, (double)a.K * 80 + (double)a.N * 8);
+    hipLaunchKernelGGL(line_fill_kernel, dim3(cdiv(a.K, 256)), dim3(256), 0, st, a.recs, a.K, a.clip_x, a.clip_y, out.klines, out.length,
+                       out.angles, a.s2l_g, d_sub2line);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "tokenize", 0, a.tokenize_bytes);
+    // (with out.mat: K more blocks write the rows of mat_klines2sublines in the same launch)
+    hipLaunchKernelGGL(tokenize_kernel, dim3(a.N + cdiv(a.n_pad_images, 64) + (out.mat ? a.K : 0)), dim3(64), 0, st, a.recs, a.s2l_g, a.N,
+                       a.td, a.T, a.height, a.width, a.clip_x, a.clip_y, a.dense_score, a.sublines, out.pnt, out.mask, a.resp, a.angle_sub,
+                       out.score, a.cpnt, a.cscore, a.n_pad_images, a.first_pad, out.mat, k2s);
+    LT_LAUNCH_CHECK();
+  }
+  const int Hc = a.height / 8, Wc = a.width / 8;
+  nhwc = nullptr;
+  if (a.map_always || out.desc)
+    if (int e = nhwc_map(h, st, a.dense_desc, a.dense_is_nhwc, a.n_images, Hc * Wc, a.nhwc_buf, nhwc)) return e;
+  if (out.desc) {   // the reference's dense [N, T, 256] tensor
+    const int64_t ntok = (int64_t)a.N * a.T;
+    ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
+    hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, a.s2l_g, a.recs, ntok, a.T, nhwc,
+                       Hc, Wc, a.align_corners, out.desc);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
 }  // namespace
 
 extern "C" int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t N) {
@@ -224,7 +281,6 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
   if (K <= 0 || N <= 0) return LINETR_OK;
   if (clip_height <= 0) clip_height = height;
   if (clip_width <= 0) clip_width = width;
-  const double clip_x = (double)clip_width - 0.6, clip_y = (double)clip_height - 0.6;
   if (!d_recs || !d_dense_score || !out.sublines || !out.pnt || !out.mask || !out.resp || !out.angle_sub ||
       !out.score || (out.desc && !d_dense_desc))
     return fail(LINETR_E_ARG, "tokenize: null pointer");
@@ -236,37 +292,15 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
     return fail(LINETR_E_WORKSPACE, "tokenize: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));   // no weights involved: without a handle the current device is used
-  const int Hc = height / 8, Wc = width / 8, P = Hc * Wc;
-  float* nhwc = (float*)d_ws;
-  int* s2l_g = (int*)((char*)d_ws + align_up((int64_t)n_images * P * D * 4, 256));
-  {
-    ProfScope ps(h, st, "line_fill", 0, (double)K * 80 + (double)N * 8);
-    hipLaunchKernelGGL(line_fill_kernel, dim3(cdiv(K, 256)), dim3(256), 0, st, d_recs, K, clip_x, clip_y, out.klines, out.length,
-                       out.angles, s2l_g, d_sub2line);
-    LT_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps(h, st, "tokenize", 0, (double)N * T * 16);
-    // (with out.mat: K more blocks write the rows of mat_klines2sublines in the same launch)
-    hipLaunchKernelGGL(tokenize_kernel, dim3(N + (out.mat ? K : 0)), dim3(64), 0, st, d_recs, s2l_g, N, td, T, height, width,
-                       clip_x, clip_y, d_dense_score, out.sublines, out.pnt, out.mask, out.resp, out.angle_sub, out.score, (float*)nullptr,
-                       (float*)nullptr, 0, (int64_t)0, out.mat, k2s);
-    LT_LAUNCH_CHECK();
-  }
-  if (out.desc) {
-    if (!dense_is_nhwc) {   // a channel-last map (the repo's producer) is sampled in place
-      ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * n_images * P * D * 4);
-      hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, n_images), dim3(256), 0, st, d_dense_desc,
-                         nhwc, D, P);
-      LT_LAUNCH_CHECK();
-    }
-    const int64_t ntok = (int64_t)N * T;
-    ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
-    hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, s2l_g, d_recs,
-                       ntok, T, dense_is_nhwc ? d_dense_desc : nhwc, Hc, Wc, align_corners, out.desc);
-    LT_LAUNCH_CHECK();
-  }
-  return LINETR_OK;
+  const int64_t P = (int64_t)(height / 8) * (width / 8);
+  TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, dense_is_nhwc,
+               (double)clip_width - 0.6, (double)clip_height - 0.6, out.sublines, out.resp, out.angle_sub};
+  f.nhwc_buf = (float*)d_ws;
+  f.s2l_g = (int*)((char*)d_ws + align_up(n_images * P * D * 4, 256));
+  f.map_always = false;
+  f.tokenize_bytes = (double)N * T * 16;
+  const float* nhwc;
+  return token_front(h, st, f, out, k2s, d_sub2line, nhwc);
 }
 
 // sample_descriptors (models/line_process.py:86-98) on its own: n points of ONE image
@@ -284,14 +318,8 @@ extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points,
     return fail(LINETR_E_WORKSPACE, "sample_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  const int P = Hc * Wc;
-  const float* nhwc = d_dense_desc;
-  if (!dense_is_nhwc) {
-    ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * P * D * 4);
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, 1), dim3(256), 0, st, d_dense_desc, (float*)d_ws, D, P);
-    LT_LAUNCH_CHECK();
-    nhwc = (const float*)d_ws;
-  }
+  const float* nhwc;
+  if (int e = nhwc_map(h, st, d_dense_desc, dense_is_nhwc, 1, Hc * Wc, (float*)d_ws, nhwc)) return e;
   ProfScope ps(h, st, "sample_desc", 0, (double)n * D * 4 * 2);
   // T = 1 and no records: every point is its own "sub-line" of image 0
   hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_points, (const int*)nullptr,
@@ -315,24 +343,9 @@ extern "C" int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoint
     return fail(LINETR_E_WORKSPACE, "point_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  {   // 65 KiB of dynamic LDS: raised once per device
-    static unsigned long long done = 0;
-    static std::mutex m;
-    const unsigned long long dev_bit = current_device_bit();
-    std::lock_guard<std::mutex> lk(m);
-    if (!(done & dev_bit)) {
-      LT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sp_kp_desc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_DESC_LDS));
-      done |= dev_bit;
-    }
-  }
-  const int P = Hc * Wc;
-  const float* nhwc = d_dense_desc;
-  if (!dense_is_nhwc) {
-    ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * B * P * D * 4);
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, B), dim3(256), 0, st, d_dense_desc, (float*)d_ws, D, P);
-    LT_LAUNCH_CHECK();
-    nhwc = (const float*)d_ws;
-  }
+  LT_HIP(allow_dynamic_lds<sp_kp_desc_kernel>((int)KP_DESC_LDS));   // 65 KiB
+  const float* nhwc;
+  if (int e = nhwc_map(h, st, d_dense_desc, dense_is_nhwc, B, Hc * Wc, (float*)d_ws, nhwc)) return e;
   ProfScope ps(h, st, "sp_kp_desc", 0, (double)n_total * D * 4 * 5);
   hipLaunchKernelGGL(sp_kp_desc_kernel, dim3((unsigned)((n_total + KP_DESC_N - 1) / KP_DESC_N + B)), dim3(256), KP_DESC_LDS, st, d_keypoints,
                      d_cu_kp, B, nhwc, Hc, Wc, align_corners, d_desc_cn);
@@ -349,7 +362,8 @@ namespace {
 // its N = 1024, K = 768 product still goes to the latency kernel (small_gemm_wins) -- above, 2.4x the flops cost more than a launch
 constexpr int SIG_FOLD_MAX_ROWS = 960;
 struct FwdWs {
-  float *a1, *a2, *a3, *a4, *pooled, *att, *fc, *o, *f1, *f2, *l1, *l2, *l3, *l4, *lpos, *zA, *zB, *qkv, *msgp, *msg, *hid;
+  float* act[2][4];                                // the positional encoders' activations, layers 1-4: ENC_WORD [rows, .], ENC_LINE [N, .]
+  float *pooled, *att, *fc, *o, *f1, *f2, *lpos, *zA, *zB, *qkv, *msgp, *msg, *hid;
   float *zqA, *zqB;                                // [N][4D] = [x_out | q/k/v of the next layer] (single-pair sizes: SigLayer::Wnext)
   int* cu;
   char* x = nullptr;                               // experiments build: where its own buffers start (lt_x_net.h)
@@ -360,13 +374,11 @@ FwdWs fwd_layout(const LinetrHandle* h, int N, int64_t rows, int n_images, char*
   FwdWs w;
   int64_t off = 0;
   auto take = [&](int64_t floats) { float* p = (float*)(base + off); off += align_up(floats * 4, 256); return p; };
-  w.a1 = take(rows * c.enc_channels[0]); w.a2 = take(rows * c.enc_channels[1]);
-  w.a3 = take(rows * c.enc_channels[2]); w.a4 = take(rows * c.enc_channels[3]);
+  for (int i = 0; i < 4; ++i) w.act[ENC_WORD][i] = take(rows * c.enc_channels[i]);
   w.pooled = take((int64_t)N * HEADS * POOLW);
   w.att = take((int64_t)N * D); w.fc = take((int64_t)N * D); w.o = take((int64_t)N * D);
   w.f1 = take((int64_t)N * c.d_inner); w.f2 = take((int64_t)N * D);
-  w.l1 = take((int64_t)N * c.enc_channels[0]); w.l2 = take((int64_t)N * c.enc_channels[1]);
-  w.l3 = take((int64_t)N * c.enc_channels[2]); w.l4 = take((int64_t)N * c.enc_channels[3]);
+  for (int i = 0; i < 4; ++i) w.act[ENC_LINE][i] = take((int64_t)N * c.enc_channels[i]);
   w.lpos = take((int64_t)N * D);
   w.zA = take((int64_t)N * D); w.zB = take((int64_t)N * D);
   w.qkv = take((int64_t)N * 3 * D); w.msgp = take((int64_t)N * D); w.msg = take((int64_t)N * D);
@@ -444,134 +456,142 @@ double attn_flops(const int32_t* h_cu, int n_images) {
   return fl;
 }
 
-// ---- positional encoders, training mode (train.py:127): conv -> BatchNorm(batch statistics) -> ReLU, layer by layer, on the
-// unfolded convolutions of a bn_batch_stats handle.  Statistics run over ALL rows of the batch: B*N*T token positions (padding
-// tokens included, as the reference's [B*N, 3, T] input has them) for the word encoder, B*N sub-lines for the line encoder.
-int pos_encoders_bn(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const float* sublines, const float* resp,
-                    const float* angle_sub, int N, FwdWs& w) {
-  const LinetrModelConfig& c = h->cfg;
-  const int e0 = c.enc_channels[0], e1 = c.enc_channels[1], e2 = c.enc_channels[2], e3 = c.enc_channels[3];
-  const float cx = c.norm_width / 2.f, cy = c.norm_height / 2.f;           // line_transformer.py:30-32
-  const float scale = (float)std::max(c.norm_width, c.norm_height) * 0.7f;
-  const int64_t rows = ts.rows;
-  const BnTrain& bt = *ts.bn;
-  int64_t off = 0;
-  int e;
-  auto bn = [&](int layer, float* zbuf, int64_t r, int C) {
-    const int64_t o = off; off += 2 * C;
-    return bn_train_layer(st, bt, zbuf, r, C, C, h->bn_g[layer], h->bn_b[layer], o);
-  };
-#define LT_BN(layer, zbuf, r, C) do { if ((e = bn(layer, zbuf, r, C))) return e; } while (0)
-  hipLaunchKernelGGL(word_mlp1_kernel<false>, dim3((unsigned)cdiv((int)(rows * 8), 256)), dim3(256), 0, st, ts.pnt, ts.score, rows,
-                     cx, cy, scale, h->wW1, h->wb1, w.a1);
+// ---- positional encoders (up to CUT_MLP).  The word and the line encoder are the same four layers over different inputs, through
+// distinct kernel instantiations; the host code below is written once and told which encoder it runs.
+struct EncCall {
+  int which;                   // ENC_WORD: p0 = token coordinates, p1 = scores.  ENC_LINE: p0 = sub-line end points, p1 = responses,
+  const float *p0, *p1, *p2;   // p2 = (cos, sin) of the doubled angle (TokMlpArgs has the shapes)
+  int64_t rows;
+  float* const* act;           // FwdWs::act[which]
+};
+// per encoder: first-layer inputs, bytes read per row, and the profile classes of its own launches
+constexpr struct { int in, in_bytes; const char *tok_mlp, *mlp123; } ENC_KIND[2] = {{3, 12, "tok_mlp_bf16x6", "mlp123"},
+                                                                                   {5, 28, "line_mlp_bf16x6", "mlp123_line"}};
+
+struct EncNorm { float cx, cy, scale; };   // normalize_keylines (line_transformer.py:30-32)
+EncNorm enc_norm(const LinetrModelConfig& c) {
+  return {c.norm_width / 2.f, c.norm_height / 2.f, (float)std::max(c.norm_width, c.norm_height) * 0.7f};
+}
+
+// layer 1 (no GEMM) -> out [rows, e0]; RELU = false: the pre-activations, for BatchNorm on batch statistics
+template <bool RELU>
+int enc_layer1(LinetrHandle* h, hipStream_t st, const EncCall& c, float* out) {
+  const PosEncoder& E = h->enc[c.which];
+  const EncNorm n = enc_norm(h->cfg);
+  const dim3 grid((unsigned)cdiv((int)(c.rows * 8), 256));
+  if (c.which == ENC_WORD)
+    hipLaunchKernelGGL(word_mlp1_kernel<RELU>, grid, dim3(256), 0, st, c.p0, c.p1, c.rows, n.cx, n.cy, n.scale, E.W1, E.b1, out);
+  else
+    hipLaunchKernelGGL(line_mlp1_kernel<RELU>, grid, dim3(256), 0, st, c.p0, c.p1, c.p2, (int)c.rows, n.cx, n.cy, n.scale, E.W1, E.b1, out);
   LT_LAUNCH_CHECK();
-  LT_BN(0, w.a1, rows, e0);
-  if ((e = run_gemm(h, st, h->wW2, (int)rows, {w.a1, e0}, {w.a2, e1}, ACT_NONE))) return e;
-  LT_BN(1, w.a2, rows, e1);
-  if ((e = run_gemm(h, st, h->wW3, (int)rows, {w.a2, e1}, {w.a3, e2}, ACT_NONE))) return e;
-  LT_BN(2, w.a3, rows, e2);
-  if ((e = run_gemm(h, st, h->wW4, (int)rows, {w.a3, e2}, {w.a4, e3}, ACT_NONE))) return e;
-  LT_BN(3, w.a4, rows, e3);
-  hipLaunchKernelGGL(line_mlp1_kernel<false>, dim3(cdiv(N * 8, 256)), dim3(256), 0, st, sublines, resp, angle_sub, N, cx, cy, scale,
-                     h->lW1, h->lb1, w.l1);
-  LT_LAUNCH_CHECK();
-  LT_BN(4, w.l1, N, e0);
-  if ((e = run_gemm(h, st, h->lW2, N, {w.l1, e0}, {w.l2, e1}, ACT_NONE))) return e;
-  LT_BN(5, w.l2, N, e1);
-  if ((e = run_gemm(h, st, h->lW3, N, {w.l2, e1}, {w.l3, e2}, ACT_NONE))) return e;
-  LT_BN(6, w.l3, N, e2);
-  if ((e = run_gemm(h, st, h->lW4, N, {w.l3, e2}, {w.l4, e3}, ACT_NONE))) return e;
-  LT_BN(7, w.l4, N, e3);
-#undef LT_BN
   return LINETR_OK;
 }
 
-// ---- positional encoders (up to CUT_MLP): the word encoder up to its last ReLU (a4; its final linear layer is applied after
-// pooling), the line encoder to its output (lpos)
+// layers 1-3 in one exact-fp32 MFMA kernel (lt_model.h) -> out [rows, e2]
+int enc_mlp123(LinetrHandle* h, hipStream_t st, const EncCall& c, float* out) {
+  const PosEncoder& E = h->enc[c.which];
+  const EncNorm n = enc_norm(h->cfg);
+  const int rpw = mlp123_rows_per_wave(c.rows);
+  const dim3 grid((unsigned)cdiv((int)cdiv((int)c.rows, rpw), 4));
+  if (c.which == ENC_WORD)
+    hipLaunchKernelGGL(mlp123_kernel<true>, grid, dim3(256), 0, st, c.p0, c.p1, c.p2, c.rows, rpw, n.cx, n.cy, n.scale, E.W1, E.b1,
+                       E.W2.W, E.W2.b, E.W3.W, E.W3.b, out);
+  else
+    hipLaunchKernelGGL(mlp123_kernel<false>, grid, dim3(256), 0, st, c.p0, c.p1, c.p2, c.rows, rpw, n.cx, n.cy, n.scale, E.W1, E.b1,
+                       E.W2.W, E.W2.b, E.W3.W, E.W3.b, out);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+// the operands of the one-kernel MLP (lt_tokmlp.h): layers 1-4 -> act[3]
+TokMlpArgs tok_mlp_args(const LinetrHandle* h, const EncCall& c) {
+  const PosEncoder& E = h->enc[c.which];
+  const EncNorm n = enc_norm(h->cfg);
+  TokMlpArgs a;
+  a.p0 = c.p0; a.p1 = c.p1; a.p2 = c.p2; a.rows = c.rows; a.cx = n.cx; a.cy = n.cy; a.scale = n.scale;
+  a.W1 = E.W1; a.b1 = E.b1; a.W2st = E.W2.st; a.b2 = E.W2.b; a.W3st = E.W3.st; a.b3 = E.W3.b; a.W4st = E.W4.st; a.b4 = E.W4.b;
+  a.Y = c.act[3]; a.ldy = h->cfg.enc_channels[3];
+  return a;
+}
+
+// one encoder up to its last ReLU (act[3]).  tok_mlp: layers 1-4 in one kernel; otherwise layers 1-3 in one kernel (the reference's
+// channel widths) or one by one, then layer 4's GEMM
+int pos_encoder(LinetrHandle* h, hipStream_t st, const EncCall& c, bool tok_mlp) {
+  const int *ch = h->cfg.enc_channels, e0 = ch[0], e1 = ch[1], e2 = ch[2], e3 = ch[3];
+  const PosEncoder& E = h->enc[c.which];
+  const auto& kind = ENC_KIND[c.which];
+  const int64_t rows = c.rows;
+  int e;
+  if (tok_mlp) {
+    ProfScope ps(h, st, kind.tok_mlp, 2.0 * rows * (kind.in * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)rows * (kind.in_bytes + 4 * e3));
+    return tok_mlp_launch(tok_mlp_args(h, c), c.which == ENC_WORD, st);
+  }
+  if (fused_mlp_enabled(h->cfg)) {
+    ProfScope ps(h, st, kind.mlp123, 2.0 * rows * (kind.in * e0 + e0 * e1 + e1 * e2), (double)rows * (kind.in_bytes + 4 * e2));
+    if ((e = enc_mlp123(h, st, c, c.act[2]))) return e;
+  } else {
+    {
+      ProfScope ps(h, st, "mlp_first", 2.0 * rows * kind.in * e0, (double)rows * (kind.in_bytes + 4 * e0));
+      if ((e = enc_layer1<true>(h, st, c, c.act[0]))) return e;
+    }
+    if ((e = run_gemm(h, st, E.W2, (int)rows, {c.act[0], e0}, {c.act[1], e1}, ACT_RELU))) return e;
+    if ((e = run_gemm(h, st, E.W3, (int)rows, {c.act[1], e1}, {c.act[2], e2}, ACT_RELU))) return e;
+  }
+  return run_gemm(h, st, E.W4, (int)rows, {c.act[2], e2}, {c.act[3], e3}, ACT_RELU);
+}
+
+// one encoder in training mode (train.py:127): conv -> BatchNorm(batch statistics) -> ReLU, layer by layer, on the unfolded convolutions
+// of a bn_batch_stats handle.  Statistics run over ALL rows of the batch: B*N*T token positions (padding tokens included, as the
+// reference's [B*N, 3, T] input has them) for the word encoder, B*N sub-lines for the line encoder.  The encoder's four layers are
+// BatchNorm layers 4 which .. 4 which + 3 of the handle; `off`: where the next layer's packed statistics go.
+int pos_encoder_bn(LinetrHandle* h, hipStream_t st, const EncCall& c, const BnTrain& bt, int64_t& off) {
+  const PosEncoder& E = h->enc[c.which];
+  const GemmW* const W[4] = {nullptr, &E.W2, &E.W3, &E.W4};
+  const int* ch = h->cfg.enc_channels;
+  int e;
+  for (int i = 0; i < 4; ++i) {
+    e = i == 0 ? enc_layer1<false>(h, st, c, c.act[0])
+               : run_gemm(h, st, *W[i], (int)c.rows, {c.act[i - 1], ch[i - 1]}, {c.act[i], ch[i]}, ACT_NONE);
+    if (e) return e;
+    const int layer = 4 * c.which + i;
+    if ((e = bn_train_layer(st, bt, c.act[i], c.rows, ch[i], ch[i], h->bn_g[layer], h->bn_b[layer], off))) return e;
+    off += 2 * ch[i];
+  }
+  return LINETR_OK;
+}
+
+// both encoders: the word encoder up to its last ReLU (its final linear layer is applied after pooling), the line encoder to its
+// output (lpos)
 int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const float* sublines, const float* resp,
                  const float* angle_sub, int N, FwdWs& w) {
   const LinetrModelConfig& c = h->cfg;
   const int e0 = c.enc_channels[0], e1 = c.enc_channels[1], e2 = c.enc_channels[2], e3 = c.enc_channels[3];
-  const float cx = c.norm_width / 2.f, cy = c.norm_height / 2.f;           // line_transformer.py:30-32
-  const float scale = (float)std::max(c.norm_width, c.norm_height) * 0.7f;
+  // token coordinates and scores: compact (describe) or dense (forward)
+  const EncCall word{ENC_WORD, ts.cpnt ? ts.cpnt : ts.pnt, ts.cpnt ? ts.cscore : ts.score, nullptr, ts.rows, w.act[ENC_WORD]};
+  const EncCall line{ENC_LINE, sublines, resp, angle_sub, N, w.act[ENC_LINE]};
   const int64_t rows = ts.rows;
-  const float* p0 = ts.cpnt ? ts.cpnt : ts.pnt;   // token coordinates and scores: compact (describe) or dense (forward)
-  const float* p1 = ts.cpnt ? ts.cscore : ts.score;
   int e;
-  const bool fused_mlp = fused_mlp_enabled(c);
   // layers 1-4 in one kernel (lt_tokmlp.h): the default precision and the reference's channel widths, at any size (a single pair,
-  // 4 k token rows and 400 sub-lines, gains too: 42 -> 31 us for the two encoders)
-  const bool tok_mlp_ok = fused_mlp && h->precision == LINETR_PREC_BF16X6 && e0 == 32 && e1 == 64 && e2 == 128 && e3 == 256 &&
+  // 4 k token rows and 400 sub-lines, gains too: 42 -> 31 us for the two encoders).  Each encoder takes it when its own three
+  // split-tile weight images exist; both in ONE launch only when both do and neither is empty.
+  const bool tok_mlp_ok = fused_mlp_enabled(c) && h->precision == LINETR_PREC_BF16X6 && e0 == 32 && e1 == 64 && e2 == 128 && e3 == 256 &&
                           !LT_XENV("LINETR_NO_TOKMLP");
-  const bool tok_mlp = tok_mlp_ok && h->wW2.st && h->wW3.st && h->wW4.st;
-  const bool line_mlp = tok_mlp_ok && h->lW2.st && h->lW3.st && h->lW4.st;
-  TokMlpArgs amw, aml;
-  if (tok_mlp) {
-    amw.p0 = p0; amw.p1 = p1; amw.rows = rows; amw.cx = cx; amw.cy = cy; amw.scale = scale;
-    amw.W1 = h->wW1; amw.b1 = h->wb1; amw.W2st = h->wW2.st; amw.b2 = h->wW2.b; amw.W3st = h->wW3.st; amw.b3 = h->wW3.b;
-    amw.W4st = h->wW4.st; amw.b4 = h->wW4.b; amw.Y = w.a4; amw.ldy = e3;
-  }
-  if (line_mlp) {
-    aml.p0 = sublines; aml.p1 = resp; aml.p2 = angle_sub; aml.rows = N; aml.cx = cx; aml.cy = cy; aml.scale = scale;
-    aml.W1 = h->lW1; aml.b1 = h->lb1; aml.W2st = h->lW2.st; aml.b2 = h->lW2.b; aml.W3st = h->lW3.st; aml.b3 = h->lW3.b;
-    aml.W4st = h->lW4.st; aml.b4 = h->lW4.b; aml.Y = w.l4; aml.ldy = e3;
-  }
+  auto has_images = [](const PosEncoder& E) { return E.W2.st && E.W3.st && E.W4.st; };
+  const bool tok_mlp = tok_mlp_ok && has_images(h->enc[ENC_WORD]), line_mlp = tok_mlp_ok && has_images(h->enc[ENC_LINE]);
   if (ts.bn) {
-    if ((e = pos_encoders_bn(h, st, ts, sublines, resp, angle_sub, N, w))) return e;
+    int64_t off = 0;
+    if ((e = pos_encoder_bn(h, st, word, *ts.bn, off))) return e;
+    if ((e = pos_encoder_bn(h, st, line, *ts.bn, off))) return e;
   } else if (tok_mlp && line_mlp && rows > 0 && N > 0) {
-    // both encoders in ONE launch: side by side for a small batch, one after the other inside every persistent block for a large one
+    // side by side for a small batch, one after the other inside every persistent block for a large one
     ProfScope ps(h, st, "pos_mlp_dual_bf16x6", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2 + e2 * e3) + 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2 + e2 * e3),
                  (double)rows * (12 + 4 * e3) + (double)N * (28 + 4 * e3));
-    if ((e = tok_mlp_launch_dual(amw, aml, st))) return e;
+    if ((e = tok_mlp_launch_dual(tok_mlp_args(h, word), tok_mlp_args(h, line), st))) return e;
   } else {
-    // word encoder
-    if (tok_mlp) {
-      ProfScope ps(h, st, "tok_mlp_bf16x6", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)rows * (12 + 4 * e3));
-      if ((e = tok_mlp_launch(amw, true, st))) return e;
-    } else {
-      if (fused_mlp) {   // layers 1-3 in one exact-fp32 MFMA kernel (lt_model.h)
-        ProfScope ps(h, st, "mlp123", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2), (double)rows * (12 + 4 * e2));
-        const int rpw = mlp123_rows_per_wave(rows);
-        hipLaunchKernelGGL(mlp123_kernel<true>, dim3((unsigned)cdiv((int)cdiv((int)rows, rpw), 4)), dim3(256), 0, st, p0, p1,
-                           (const float*)nullptr, rows, rpw, cx, cy, scale, h->wW1, h->wb1, h->wW2.W, h->wW2.b, h->wW3.W, h->wW3.b, w.a3);
-        LT_LAUNCH_CHECK();
-      } else {
-        {
-          ProfScope ps(h, st, "mlp_first", 2.0 * rows * 3 * e0, (double)rows * (12 + 4 * e0));
-          hipLaunchKernelGGL(word_mlp1_kernel<true>, dim3((unsigned)cdiv((int)(rows * 8), 256)), dim3(256), 0, st, p0, p1, rows, cx, cy,
-                             scale, h->wW1, h->wb1, w.a1);
-          LT_LAUNCH_CHECK();
-        }
-        if ((e = run_gemm(h, st, h->wW2, (int)rows, {w.a1, e0}, {w.a2, e1}, ACT_RELU))) return e;
-        if ((e = run_gemm(h, st, h->wW3, (int)rows, {w.a2, e1}, {w.a3, e2}, ACT_RELU))) return e;
-      }
-      if ((e = run_gemm(h, st, h->wW4, (int)rows, {w.a3, e2}, {w.a4, e3}, ACT_RELU))) return e;
-    }
-    // line encoder, as the word encoder
-    if (line_mlp) {
-      ProfScope ps(h, st, "line_mlp_bf16x6", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2 + e2 * e3), (double)N * (28 + 4 * e3));
-      if ((e = tok_mlp_launch(aml, false, st))) return e;
-    } else {
-      if (fused_mlp) {
-        ProfScope ps(h, st, "mlp123_line", 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2), (double)N * (28 + 4 * e2));
-        const int rpw = mlp123_rows_per_wave(N);
-        hipLaunchKernelGGL(mlp123_kernel<false>, dim3((unsigned)cdiv(cdiv(N, rpw), 4)), dim3(256), 0, st, sublines, resp, angle_sub,
-                           (int64_t)N, rpw, cx, cy, scale, h->lW1, h->lb1, h->lW2.W, h->lW2.b, h->lW3.W, h->lW3.b, w.l3);
-        LT_LAUNCH_CHECK();
-      } else {
-        {
-          ProfScope ps(h, st, "mlp_first", 2.0 * N * 5 * e0, (double)N * (28 + 4 * e0));
-          hipLaunchKernelGGL(line_mlp1_kernel<true>, dim3(cdiv(N * 8, 256)), dim3(256), 0, st, sublines, resp, angle_sub, N, cx, cy,
-                             scale, h->lW1, h->lb1, w.l1);
-          LT_LAUNCH_CHECK();
-        }
-        if ((e = run_gemm(h, st, h->lW2, N, {w.l1, e0}, {w.l2, e1}, ACT_RELU))) return e;
-        if ((e = run_gemm(h, st, h->lW3, N, {w.l2, e1}, {w.l3, e2}, ACT_RELU))) return e;
-      }
-      if ((e = run_gemm(h, st, h->lW4, N, {w.l3, e2}, {w.l4, e3}, ACT_RELU))) return e;
-    }
+    if ((e = pos_encoder(h, st, word, tok_mlp))) return e;
+    if ((e = pos_encoder(h, st, line, line_mlp))) return e;
   }
-  return run_gemm(h, st, h->lW5, N, {w.l4, e3}, {w.lpos, D}, ACT_NONE);
+  return run_gemm(h, st, h->lW5, N, {w.act[ENC_LINE][3], e3}, {w.lpos, D}, ACT_NONE);
 }
 
 // ---- CLS-row attention pooling + value / last-MLP projection (up to CUT_POOL)
@@ -584,14 +604,14 @@ int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_im
     // few sub-lines (a single pair): four waves per sub-line, so that the chip is covered and the token chain is a quarter as long
     if (N <= 2048)
       hipLaunchKernelGGL(cls_pool_online_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         w.a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 0);
+                         w.act[ENC_WORD][3], ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 0);
     else   // (reverse = 1: the last sub-lines first, see the kernel)
       hipLaunchKernelGGL(cls_pool_online_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         w.a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 1);
+                         w.act[ENC_WORD][3], ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 1);
     LT_LAUNCH_CHECK();
   } else {
     ProfScope ps(h, st, "cls_pool", 2.0 * rows * (2.0 * HEADS * D * 2), (double)rows * D * 8);
-    hipLaunchKernelGGL(cls_pool_kernel, dim3(N), dim3(256), HEADS * (T + 1) * sizeof(float), st, ts.desc, w.a4, T,
+    hipLaunchKernelGGL(cls_pool_kernel, dim3(N), dim3(256), HEADS * (T + 1) * sizeof(float), st, ts.desc, w.act[ENC_WORD][3], T,
                        h->pool, w.pooled);
     LT_LAUNCH_CHECK();
   }
@@ -664,12 +684,7 @@ int sig_attention(LinetrHandle* h, hipStream_t st, int kernel, const float* qkv,
 // q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h), z -> msg: q, k, v never reach HBM
 int sig_qkv_attention(LinetrHandle* h, hipStream_t st, const SigLayer& S, const float* z, const int* cu_dev, int n_images, int N,
                       double attn_fl, float* msg) {
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sig_qkv_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FQA_LDS);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<sig_qkv_attn_kernel>(FQA_LDS));
   ProfScope ps(h, st, "sig_qkv_attn_bf16x6", 2.0 * N * 3.0 * D * D + attn_fl, (double)N * D * 8);
   hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, S.Wqkv.st, S.Wqkv.b,
                      cu_dev, msg);
@@ -757,6 +772,41 @@ int check_cu(const int32_t* h_cu, int n_images) {
     if (h_cu[i + 1] < h_cu[i]) return fail(LINETR_E_ARG, "cu_sub not monotone");
   return 0;
 }
+
+// the sub-line prefix sums on the device: the caller's copy, or h_cu uploaded into the workspace
+int cu_on_device(const int32_t* h_cu, const int32_t* d_cu, int n_images, const FwdWs& w, hipStream_t st, const int*& cu_dev) {
+  cu_dev = d_cu;
+  if (cu_dev) return LINETR_OK;
+  LT_HIP(hipMemcpyAsync(w.cu, h_cu, (n_images + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  cu_dev = w.cu;
+  return LINETR_OK;
+}
+
+// linetr_forward (bt = nullptr) and linetr_forward_train (bt: running / batch statistics and momentum set by the caller; its scratch
+// sits behind linetr_forward's workspace) behind their own argument checks: the network over the reference's dense [N, T] token tensors
+int forward_dense(LinetrHandle* h, const char* who, const LinetrTokens& tok, const int32_t* h_cu, const int32_t* d_cu, int n_images,
+                  int T, float* d_line_desc, void* d_ws, int64_t ws_bytes, hipStream_t st, BnTrain* bt) {
+  if (int e = check_cu(h_cu, n_images)) return e;
+  const int N = h_cu[n_images];
+  if (N <= 0) return LINETR_OK;
+  if (!tok.sublines || !tok.pnt || !tok.resp || !tok.angle_sub || !tok.desc || !tok.score || !d_line_desc)
+    return fail(LINETR_E_ARG, "%s: null tensor", who);
+  if (ws_bytes < (bt ? linetr_forward_train_workspace_bytes(h, N, T) : linetr_forward_workspace_bytes(h, N, T)))
+    return fail(LINETR_E_WORKSPACE, "%s: workspace too small", who);
+  if ((int64_t)N * T > INT32_MAX / 8) return fail(LINETR_E_ARG, "%s: batch too large", who);
+  LT_HIP(hipSetDevice(h->device));
+  FwdWs w = fwd_layout(h, N, (int64_t)N * T, std::max(N, 1), (char*)d_ws);
+  if (bt) {
+    bt->partial = (double*)((char*)d_ws + align_up(w.total, 256));
+    bt->affine = (float*)((char*)bt->partial + (int64_t)BN_MAX_BLOCKS * 2 * BN_MAX_CHANNELS * 8);
+  }
+  const int* cu_dev;
+  if (int e = cu_on_device(h_cu, d_cu, n_images, w, st, cu_dev)) return e;
+  TokenStage ts;
+  ts.pnt = tok.pnt; ts.score = tok.score; ts.desc = tok.desc; ts.rows = (int64_t)N * T;
+  ts.bn = bt;
+  return forward_core(h, st, ts, tok.sublines, tok.resp, tok.angle_sub, h_cu, cu_dev, n_images, N, T, d_line_desc, w);
+}
 }  // namespace
 
 extern "C" int linetr_forward(LinetrHandle* h, const LinetrTokens* tok, const int32_t* h_cu, const int32_t* d_cu,
@@ -764,24 +814,7 @@ extern "C" int linetr_forward(LinetrHandle* h, const LinetrTokens* tok, const in
                               void* stream) {
   if (!h || !tok) return fail(LINETR_E_ARG, "forward: null argument");
   if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "forward: a training-mode handle (bn_batch_stats = 1) runs linetr_forward_train only");
-  if (int e = check_cu(h_cu, n_images)) return e;
-  const int N = h_cu[n_images];
-  if (N <= 0) return LINETR_OK;
-  if (!tok->sublines || !tok->pnt || !tok->resp || !tok->angle_sub || !tok->desc || !tok->score || !d_line_desc)
-    return fail(LINETR_E_ARG, "forward: null tensor");
-  if (ws_bytes < linetr_forward_workspace_bytes(h, N, T)) return fail(LINETR_E_WORKSPACE, "forward: workspace too small");
-  if ((int64_t)N * T > INT32_MAX / 8) return fail(LINETR_E_ARG, "forward: batch too large");
-  hipStream_t st = (hipStream_t)stream;
-  LT_HIP(hipSetDevice(h->device));
-  FwdWs w = fwd_layout(h, N, (int64_t)N * T, std::max(N, 1), (char*)d_ws);
-  const int* cu_dev = d_cu;
-  if (!cu_dev) {
-    LT_HIP(hipMemcpyAsync(w.cu, h_cu, (n_images + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    cu_dev = w.cu;
-  }
-  TokenStage ts;
-  ts.pnt = tok->pnt; ts.score = tok->score; ts.desc = tok->desc; ts.rows = (int64_t)N * T;
-  return forward_core(h, st, ts, tok->sublines, tok->resp, tok->angle_sub, h_cu, cu_dev, n_images, N, T, d_line_desc, w);
+  return forward_dense(h, "forward", *tok, h_cu, d_cu, n_images, T, d_line_desc, d_ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
 // Training-time forward (train.py:127,163-164): linetr_forward's dense token path with BatchNorm on batch
@@ -804,29 +837,9 @@ extern "C" int linetr_forward_train(LinetrHandle* h, const LinetrTokens* tok, co
   if (!h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "forward_train: the handle was created for inference (bn_batch_stats = 0)");
   if (!d_bn_running) return fail(LINETR_E_ARG, "forward_train: null running statistics");
   if (!(momentum >= 0.f && momentum <= 1.f)) return fail(LINETR_E_ARG, "forward_train: momentum out of [0, 1]");
-  if (int e = check_cu(h_cu, n_images)) return e;
-  const int N = h_cu[n_images];
-  if (N <= 0) return LINETR_OK;
-  if (!tok->sublines || !tok->pnt || !tok->resp || !tok->angle_sub || !tok->desc || !tok->score || !d_line_desc)
-    return fail(LINETR_E_ARG, "forward_train: null tensor");
-  if (ws_bytes < linetr_forward_train_workspace_bytes(h, N, T)) return fail(LINETR_E_WORKSPACE, "forward_train: workspace too small");
-  if ((int64_t)N * T > INT32_MAX / 8) return fail(LINETR_E_ARG, "forward_train: batch too large");
-  hipStream_t st = (hipStream_t)stream;
-  LT_HIP(hipSetDevice(h->device));
-  FwdWs w = fwd_layout(h, N, (int64_t)N * T, std::max(N, 1), (char*)d_ws);
   BnTrain bt;
   bt.running = d_bn_running; bt.batch = d_bn_batch; bt.momentum = momentum;
-  bt.partial = (double*)((char*)d_ws + align_up(w.total, 256));
-  bt.affine = (float*)((char*)bt.partial + (int64_t)BN_MAX_BLOCKS * 2 * BN_MAX_CHANNELS * 8);
-  const int* cu_dev = d_cu;
-  if (!cu_dev) {
-    LT_HIP(hipMemcpyAsync(w.cu, h_cu, (n_images + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    cu_dev = w.cu;
-  }
-  TokenStage ts;
-  ts.pnt = tok->pnt; ts.score = tok->score; ts.desc = tok->desc; ts.rows = (int64_t)N * T;
-  ts.bn = &bt;
-  return forward_core(h, st, ts, tok->sublines, tok->resp, tok->angle_sub, h_cu, cu_dev, n_images, N, T, d_line_desc, w);
+  return forward_dense(h, "forward_train", *tok, h_cu, d_cu, n_images, T, d_line_desc, d_ws, ws_bytes, (hipStream_t)stream, &bt);
 }
 
 // =============================================================================================
@@ -887,50 +900,23 @@ int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32
   LT_HIP(hipSetDevice(h->device));
   DescWs dw = desc_layout(n_images, height, width, N, rows, (char*)d_ws);
   FwdWs w = fwd_layout(h, N, rows, n_images, (char*)d_ws + dw.fwd_off);
-  const int Hc = height / 8, Wc = width / 8, P = Hc * Wc;
-  const int* cu_dev = d_cu;
-  if (!cu_dev) {
-    LT_HIP(hipMemcpyAsync(w.cu, h_cu, (n_images + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    cu_dev = w.cu;
-  }
-  float* sublines = out.sublines ? out.sublines : dw.sublines;
-  float* resp = out.resp ? out.resp : dw.resp;
-  float* angle_sub = out.angle_sub ? out.angle_sub : dw.angle_sub;
-  const float* nhwc_map = dense_is_nhwc ? d_dense_desc : dw.nhwc;
-  {
-    ProfScope ps(h, st, "line_fill", 0, (double)K * 80 + (double)N * 8);
-    hipLaunchKernelGGL(line_fill_kernel, dim3(cdiv(K, 256)), dim3(256), 0, st, d_recs, K, (double)width - 0.6,
-                       (double)height - 0.6, out.klines, out.length, out.angles, dw.s2l_g, d_sub2line);
-    LT_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps(h, st, "tokenize", 0, (double)n_real * 16);
-    // (the last cdiv(n_images, 64) blocks write the per-image padding rows of the compact token list)
-    hipLaunchKernelGGL(tokenize_kernel, dim3(N + cdiv(n_images, 64) + (out.mat ? K : 0)), dim3(64), 0, st, d_recs, dw.s2l_g, N, td, T,
-                       height, width, (double)width - 0.6, (double)height - 0.6, d_dense_score, sublines, out.pnt, out.mask, resp,
-                       angle_sub, out.score, dw.cpnt, dw.cscore,
-                       n_images, (int64_t)n_real, out.mat, k2s);
-    LT_LAUNCH_CHECK();
-  }
-  if (!dense_is_nhwc) {
-    ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * n_images * P * D * 4);
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, n_images), dim3(256), 0, st, d_dense_desc,
-                       dw.nhwc, D, P);
-    LT_LAUNCH_CHECK();
-  }
-  if (out.desc) {  // the reference's dense tensor was asked for as well
-    const int64_t ntok = (int64_t)N * T;
-    ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
-    hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, dw.s2l_g, d_recs,
-                       ntok, T, nhwc_map, Hc, Wc, align_corners, out.desc);
-    LT_LAUNCH_CHECK();
-  }
+  const int* cu_dev;
+  if (int e = cu_on_device(h_cu, d_cu, n_images, w, st, cu_dev)) return e;
+  TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, dense_is_nhwc,
+               (double)width - 0.6, (double)height - 0.6, out.sublines ? out.sublines : dw.sublines, out.resp ? out.resp : dw.resp,
+               out.angle_sub ? out.angle_sub : dw.angle_sub};
+  f.s2l_g = dw.s2l_g; f.nhwc_buf = dw.nhwc;
+  f.map_always = true;
+  f.tokenize_bytes = (double)n_real * 16;
+  f.cpnt = dw.cpnt; f.cscore = dw.cscore; f.n_pad_images = n_images; f.first_pad = n_real;
+  const float* nhwc_map;
+  if (int e = token_front(h, st, f, out, k2s, d_sub2line, nhwc_map)) return e;
   TokenStage ts;
   ts.cpnt = dw.cpnt; ts.cscore = dw.cscore; ts.nhwc = nhwc_map; ts.recs = d_recs; ts.sub2line_g = dw.s2l_g;
-  ts.rows = rows; ts.first_pad = n_real; ts.Hc = Hc; ts.Wc = Wc; ts.align_corners = align_corners;
+  ts.rows = rows; ts.first_pad = n_real; ts.Hc = height / 8; ts.Wc = width / 8; ts.align_corners = align_corners;
   ts.pipe = pipe;
   if (int e = pipe_boundary(pipe, CUT_TOKENS, st)) return e;
-  return forward_core(h, st, ts, sublines, resp, angle_sub, h_cu, cu_dev, n_images, N, T, d_line_desc, w);
+  return forward_core(h, st, ts, f.sublines, f.resp, f.angle_sub, h_cu, cu_dev, n_images, N, T, d_line_desc, w);
 }
 
 // the streams and events of the describe pipeline, made at the first submit: all or nothing
@@ -1034,20 +1020,7 @@ extern "C" int linetr_debug_posenc(LinetrHandle* h, int32_t which, const float* 
   if (!fused_mlp_enabled(h->cfg)) return fail(LINETR_E_ARG, "debug_posenc: needs keyline_encoder [32,64,128,256]");
   if (rows <= 0) return LINETR_OK;
   LT_HIP(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  const LinetrModelConfig& c = h->cfg;
-  const float cx = c.norm_width / 2.f, cy = c.norm_height / 2.f;
-  const float scale = (float)std::max(c.norm_width, c.norm_height) * 0.7f;
-  const int rpw = mlp123_rows_per_wave(rows);
-  const dim3 grid((unsigned)cdiv((int)cdiv((int)rows, rpw), 4));
-  if (which == 0)
-    hipLaunchKernelGGL(mlp123_kernel<true>, grid, dim3(256), 0, st, d_in0, d_in1, (const float*)nullptr, rows, rpw, cx, cy, scale,
-                       h->wW1, h->wb1, h->wW2.W, h->wW2.b, h->wW3.W, h->wW3.b, d_out);
-  else
-    hipLaunchKernelGGL(mlp123_kernel<false>, grid, dim3(256), 0, st, d_in0, d_in1, d_in2, rows, rpw, cx, cy, scale, h->lW1, h->lb1,
-                       h->lW2.W, h->lW2.b, h->lW3.W, h->lW3.b, d_out);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
+  return enc_mlp123(h, (hipStream_t)stream, EncCall{which, d_in0, d_in1, which == ENC_WORD ? nullptr : d_in2, rows, nullptr}, d_out);
 }
 
 extern "C" int linetr_debug_gemm(LinetrHandle* h, const float* A, int32_t lda, const float* W, const float* bias,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -65,11 +66,21 @@ inline int fail(int code, const char* fmt, ...) {
   } while (0)
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-// bit of the calling thread's current HIP device (function attributes such as the dynamic-LDS opt-in are per device)
-inline unsigned long long current_device_bit() {
+// A launch with more dynamic LDS than the default limit needs the kernel opted in first, on every device it runs on.  Makes that
+// call once per kernel and device (one flag word per kernel, one bit per device) and is safe from several host threads: a thread
+// sees a device's bit only after the attribute is set there; two first callers at most repeat the same call.  A refusal is returned,
+// cleared from HIP's last-error slot and tried again by the next call.
+template <auto Kernel>
+inline hipError_t allow_dynamic_lds(int bytes) {
+  static std::atomic<unsigned long long> done{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  return 1ull << (dev & 63);
+  const unsigned long long dev_bit = 1ull << (dev & 63);
+  if (done.load(std::memory_order_acquire) & dev_bit) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.fetch_or(dev_bit, std::memory_order_release);
+  else (void)hipGetLastError();
+  return e;
 }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

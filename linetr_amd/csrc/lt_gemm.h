@@ -160,13 +160,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 template <int BM, int BN, int WM, int WN>
 inline int gemm_launch_t(const GemmArgs& g, int groups, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * (BM + BN) * GEMM_LDS_STRIDE * sizeof(float);
-  static unsigned long long attr_done = 0;   // one bit per device: the opt-in is a per-device function attribute
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<BM, BN, WM, WN>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done |= dev_bit;
-  }
+  LT_HIP((allow_dynamic_lds<gemm_kernel<BM, BN, WM, WN>>((int)lds)));
   dim3 grid(g.N / BN, cdiv(g.M, BM), groups);
   hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN>), grid, dim3(256), lds, st, g);
   return 0;
@@ -191,11 +185,13 @@ inline int gemm_launch(const GemmArgs& g, int groups, hipStream_t st) {
   if (g.M <= 0) return 0;
   if (g.N % 64 != 0 || g.K % GEMM_BK != 0 || (g.A2 && g.K1 % GEMM_BK != 0))
     return fail(LINETR_E_ARG, "gemm: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
+  int e;
   switch (f32_tile(g, groups)) {
-    case F32Tile::t128x64: gemm_launch_t<128, 64, 4, 1>(g, groups, st); break;
-    case F32Tile::t128x128: gemm_launch_t<128, 128, 2, 2>(g, groups, st); break;
-    default: gemm_launch_t<64, 128, 2, 2>(g, groups, st); break;
+    case F32Tile::t128x64: e = gemm_launch_t<128, 64, 4, 1>(g, groups, st); break;
+    case F32Tile::t128x128: e = gemm_launch_t<128, 128, 2, 2>(g, groups, st); break;
+    default: e = gemm_launch_t<64, 128, 2, 2>(g, groups, st); break;
   }
+  if (e) return e;
   LT_LAUNCH_CHECK();
   return 0;
 }

@@ -657,7 +657,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
 }
 
 template <int BM, int BN, int WM, int WN, int PL, bool DB = true, int FMT = 0, int PFD = 1, bool PIPE = false>
-inline void gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t st) {
+inline int gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t st) {
   constexpr size_t lds_main = (size_t)(DB ? 2 : 1) * (BM + BN) * (PL * 64 + 16);
   constexpr size_t lds_epi = (size_t)BM * BN * sizeof(float);    // every wave's TM x TN accumulator tile
   constexpr bool epi_fits = lds_epi <= 160 * 1024;
@@ -666,13 +666,7 @@ inline void gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t
   // the LDS epilogue needs 16-byte aligned rows (ldy / ldr multiples of 4 floats; the entry points guarantee it for
   // their own buffers, debug_gemm checks it)
   sa2.wide_epi = sa.g.ldy % 4 == 0 && (!sa.g.R || sa.g.ldr % 4 == 0) && epi_fits;
-  static unsigned long long attr_done = 0;   // one bit per device: the opt-in is a per-device function attribute
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done |= dev_bit;
-  }
+  LT_HIP((allow_dynamic_lds<gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>>((int)lds)));
   dim3 grid((sa.g.N / BN) * cdiv(sa.g.M, BM), groups);
   sa2.sk_first = sa2.sk_blocks = 0;
 #ifdef LINETR_EXPERIMENTS
@@ -702,22 +696,18 @@ inline void gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t
       grid.x = full + n_cu;
       // the stream-K kernel is its own instantiation with one register set of prefetch (PFD = 1): with two, the segment
       // loop's extra state spilled 116 VGPRs
-      static unsigned long long attr_sk = 0;
-      if (!(attr_sk & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, 1, PIPE, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_sk |= dev_bit;
-      }
+      LT_HIP((allow_dynamic_lds<gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, 1, PIPE, true>>((int)lds)));
       hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, 1, PIPE, true>), grid, dim3(WM * WN * 64), lds, st, sa2);
-      return;
+      return 0;
     }
   }
 #endif
   hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>), grid, dim3(WM * WN * 64), lds, st, sa2);
+  return 0;
 }
 
 template <int PL, int FMT>
-inline void gemm_split16_launch(const SplitGemmArgs& sa, hipStream_t st);   // lt_gemm_split16.h (112-row tiles)
+inline int gemm_split16_launch(const SplitGemmArgs& sa, hipStream_t st);   // lt_gemm_split16.h (112-row tiles)
 inline bool split16_wins(const GemmArgs& g, int groups);
 template <int PL, int FMT>
 inline void gemm_split_small_launch(const SplitGemmArgs& sa, int groups, hipStream_t st);   // lt_gemm_small.h (single-pair sizes)
@@ -788,29 +778,31 @@ inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, SplitTile tile
   if (g.N % 256 != 0 && (tile == SplitTile::t128x256 || tile == SplitTile::t64x256 || tile == SplitTile::t256x256))
     tile = SplitTile::t64x128;
   if (PL != 2 && tile == SplitTile::t256x256) tile = SplitTile::t64x128;
+  int e = 0;
   switch (tile) {
     case SplitTile::t32x32k4: gemm_split_small_launch<PL, FMT>(sa, groups, st); break;
-    case SplitTile::t112x256: gemm_split16_launch<PL, FMT>(sa, st); break;
-    case SplitTile::t128x64: gemm_split_launch_t<128, 64, 4, 1, PL, true, FMT>(sa, groups, st); break;
-    case SplitTile::t256x128: gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT, 1, true>(sa, groups, st); break;
+    case SplitTile::t112x256: e = gemm_split16_launch<PL, FMT>(sa, st); break;
+    case SplitTile::t128x64: e = gemm_split_launch_t<128, 64, 4, 1, PL, true, FMT>(sa, groups, st); break;
+    case SplitTile::t256x128: e = gemm_split_launch_t<256, 128, 4, 2, PL, true, FMT, 1, true>(sa, groups, st); break;
     // (16 waves of 32 x 64 or 64 x 32 on this tile, without the software pipeline, run the cfg3 step within noise of this
     // one: at one block per CU the extra waves meet at the same barriers)
-    case SplitTile::t128x256: gemm_split_launch_t<128, 256, 2, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st); break;
-    case SplitTile::t64x256: gemm_split_launch_t<64, 256, 1, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st); break;
-    case SplitTile::t128x128: gemm_split_launch_t<128, 128, 2, 2, PL, true, FMT>(sa, groups, st); break;
+    case SplitTile::t128x256: e = gemm_split_launch_t<128, 256, 2, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st); break;
+    case SplitTile::t64x256: e = gemm_split_launch_t<64, 256, 1, 4, PL, true, FMT, PL == 3 ? 2 : 1, true>(sa, groups, st); break;
+    case SplitTile::t128x128: e = gemm_split_launch_t<128, 128, 2, 2, PL, true, FMT>(sa, groups, st); break;
     // single LDS buffer, EIGHT waves of 64 x 32 (102 VGPRs): two blocks = 4 waves per SIMD.  With four waves of 64 x 64
     // (212 VGPRs, 2 waves per SIMD) 25472x768x256 took 76.4 us (now 73.2), 291208x256x128 206 us (now 192)
-    case SplitTile::t128x128s: gemm_split_launch_t<128, 128, 2, 4, PL, false, FMT>(sa, groups, st); break;
+    case SplitTile::t128x128s: e = gemm_split_launch_t<128, 128, 2, 4, PL, false, FMT>(sa, groups, st); break;
 #ifdef LINETR_EXPERIMENTS
     case SplitTile::t256x256:
-      if constexpr (PL == 2) gemm_split_launch_t<256, 256, 4, 2, 2, true, FMT>(sa, groups, st);
+      if constexpr (PL == 2) e = gemm_split_launch_t<256, 256, 4, 2, 2, true, FMT>(sa, groups, st);
       break;
 #endif
     // 64x64: three tiles of register prefetch = 156 VGPRs = THREE blocks per CU (53 KB of LDS each); with four it was 172
     // VGPRs = two blocks: 9584 x 256 x {256, 512, 1024} 20.9 / 33.2 / 58.8 us -> 18.6 / 29.8 / 52.8 us
-    case SplitTile::t64x64: gemm_split_launch_t<64, 64, 2, 2, PL, true, FMT, 3>(sa, groups, st); break;
-    default: gemm_split_launch_t<64, 128, 2, 2, PL, true, FMT, 3>(sa, groups, st); break;
+    case SplitTile::t64x64: e = gemm_split_launch_t<64, 64, 2, 2, PL, true, FMT, 3>(sa, groups, st); break;
+    default: e = gemm_split_launch_t<64, 128, 2, 2, PL, true, FMT, 3>(sa, groups, st); break;
   }
+  if (e) return e;
   LT_LAUNCH_CHECK();
   return 0;
 }

@@ -210,17 +210,12 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(SplitGemmArgs sa) {
 }
 
 template <int PL, int FMT = 0>
-inline void gemm_split16_launch(const SplitGemmArgs& sa, hipStream_t st) {
+inline int gemm_split16_launch(const SplitGemmArgs& sa, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * (112 + 256) * (PL * 64 + 16);
-  static unsigned long long attr_done = 0;   // one bit per device: the opt-in is a per-device function attribute
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split16_kernel<PL, FMT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done |= dev_bit;
-  }
+  LT_HIP((allow_dynamic_lds<gemm_split16_kernel<PL, FMT>>((int)lds)));
   dim3 grid((sa.g.N / 256) * cdiv(sa.g.M, 112));
   hipLaunchKernelGGL((gemm_split16_kernel<PL, FMT>), grid, dim3(512), lds, st, sa);
+  return 0;
 }
 
 // 112-row tiles pay when they save a round of blocks: rounds x tile cost against the 128-row kernel.  Measured on the

@@ -195,12 +195,7 @@ inline int gemm_ws_launch(const WsGemmArgs& a, hipStream_t st) {
   if (a.M <= 0) return 0;
   if (!a.A || !a.Wst || !a.bias || !a.Y || a.lda % 4 || a.ldy % 4)
     return fail(LINETR_E_ARG, "gemm_ws: unsupported operands M=%d", a.M);
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<gemm_ws_kernel>(WS_LDS));
   static int n_cu = 0;
   if (!n_cu) {
     int dev = 0;

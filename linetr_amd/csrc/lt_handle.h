@@ -32,6 +32,13 @@ struct SigLayer {
   GemmW Wnext;
 };
 
+// layers 1-4 of a positional encoder: conv + BN + ReLU each; the first layer (3 or 5 inputs) is no GEMM
+struct PosEncoder {
+  const float *W1 = nullptr, *b1 = nullptr;
+  GemmW W2, W3, W4;
+};
+enum { ENC_WORD = 0, ENC_LINE = 1 };
+
 struct ProfClass {
   const char* name;
   int calls = 0;
@@ -43,11 +50,10 @@ struct LinetrHandle {
   LinetrModelConfig cfg;
   int device = 0;
   float* arena = nullptr;  // all prepared weights, one allocation
-  // word / line positional encoders (BN folded); the first layer is no GEMM
-  const float *wW1, *wb1;
-  GemmW wW2, wW3, wW4;
-  const float *lW1, *lb1;
-  GemmW lW2, lW3, lW4, lW5;
+  // the positional encoders (BN folded), ENC_WORD and ENC_LINE.  The line encoder's last (linear) layer is lW5; the word encoder's
+  // is applied after pooling and lives in pool.U2
+  PosEncoder enc[2];
+  GemmW lW5;
   // line-descriptive layer (CLS-row algebra)
   lt::ClsPoolConst pool;
   GemmW Watt, Wfc, Wf1, Wf2;

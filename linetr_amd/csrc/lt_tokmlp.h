@@ -267,13 +267,8 @@ inline int tok_mlp_launch(const TokMlpArgs& a, bool word, hipStream_t st) {
   if (a.rows <= 0) return 0;
   if (!a.p0 || !a.p1 || (!word && !a.p2) || !a.W1 || !a.W2st || !a.W3st || !a.W4st || !a.b1 || !a.b2 || !a.b3 || !a.b4 || !a.Y || a.ldy % 4)
     return fail(LINETR_E_ARG, "tok_mlp: missing operand");
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tok_mlp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TK_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tok_mlp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TK_LDS);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<tok_mlp_kernel<true>>(TK_LDS));
+  LT_HIP(allow_dynamic_lds<tok_mlp_kernel<false>>(TK_LDS));
   static int n_cu = 0;
   if (!n_cu) {
     int dev = 0;
@@ -311,13 +306,8 @@ inline int tok_mlp_launch_dual(const TokMlpArgs& aw, const TokMlpArgs& al, hipSt
   const int64_t tw = (aw.rows + TK_TM - 1) / TK_TM, tl = (al.rows + TK_TM - 1) / TK_TM;
   if (aw.rows <= 0 || al.rows <= 0) return fail(LINETR_E_ARG, "tok_mlp: empty encoder input");
   if (!aw.p0 || !aw.p1 || !al.p0 || !al.p1 || !al.p2 || !aw.Y || !al.Y || aw.ldy % 4 || al.ldy % 4) return fail(LINETR_E_ARG, "tok_mlp: missing operand");
-  static unsigned long long attr_done = 0;
-  const unsigned long long dev_bit = current_device_bit();
-  if (!(attr_done & dev_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tok_mlp_dual_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TK_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tok_mlp_seq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TK_LDS);
-    attr_done |= dev_bit;
-  }
+  LT_HIP(allow_dynamic_lds<tok_mlp_dual_kernel>(TK_LDS));
+  LT_HIP(allow_dynamic_lds<tok_mlp_seq_kernel>(TK_LDS));
   if (tok_mlp_dual_fits(aw.rows, al.rows)) {
     hipLaunchKernelGGL(tok_mlp_dual_kernel, dim3((unsigned)(tw + tl)), dim3(512), TK_LDS, st, aw, al, (int)tw);
   } else {

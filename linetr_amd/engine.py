@@ -188,6 +188,18 @@ class Engine:
             slot["event"] = None
         return slot
 
+    def _record_blob(self, n_recs, B):
+        """A pinned staging slot laid out  records | cu_k [B+1] | cu_n [B+1]  -- what _upload_recs() sends with ONE asynchronous copy.
+        Returns the three NumPy views and remembers the slot as the origin of `recs`."""
+        rec_bytes = max(n_recs, 1) * nat.REC_DTYPE.itemsize
+        slot = self._pinned_slot(rec_bytes + 8 * (B + 1) + 64)
+        host = slot["buf"].numpy()
+        recs = host[:rec_bytes].view(nat.REC_DTYPE)
+        cu_k = host[rec_bytes:rec_bytes + 4 * (B + 1)].view(np.int32)
+        cu_n = host[rec_bytes + 4 * (B + 1):rec_bytes + 8 * (B + 1)].view(np.int32)
+        self._last_host = {"slot": slot, "recs_ptr": recs.ctypes.data, "rec_bytes": rec_bytes, "B": B}
+        return recs, cu_k, cu_n
+
     def prefilter(self, lines6, height, width, *, remove_borders, min_length, max_keylines, token_distance,
                   max_tokens, valid_masks=None, offsets=None, n_threads=0, tie_order="numpy"):
         """a1-a3 for a batch.  `lines6` is a list of [K_i,6] float64 arrays, or one concatenated [sum K,6] array
@@ -212,12 +224,7 @@ class Engine:
         cat = np.ascontiguousarray(cat, dtype=np.float64)
         B = len(offsets) - 1
         cap = int(offsets[-1])
-        rec_bytes = max(cap, 1) * nat.REC_DTYPE.itemsize
-        slot = self._pinned_slot(rec_bytes + 8 * (B + 1) + 64)
-        host = slot["buf"].numpy()
-        recs = host[:rec_bytes].view(nat.REC_DTYPE)
-        cu_k = host[rec_bytes:rec_bytes + 4 * (B + 1)].view(np.int32)
-        cu_n = host[rec_bytes + 4 * (B + 1):rec_bytes + 8 * (B + 1)].view(np.int32)
+        recs, cu_k, cu_n = self._record_blob(cap, B)
         vm_ptrs = None
         keep = []
         if valid_masks is not None:
@@ -243,28 +250,21 @@ class Engine:
                 repack_like_numpy(self._L, recs, cu_k, cu_n, i, cat[offsets[i]:offsets[i + 1]], int(height), int(width),
                                   remove_borders, min_length, max_keylines, token_distance, max_tokens,
                                   valid_masks[i] if valid_masks is not None else None)
-        K = int(cu_k[-1])
-        out = recs[:K]
-        self._last_host = {"slot": slot, "recs_ptr": recs.ctypes.data, "rec_bytes": rec_bytes, "B": B}
-        return out, cu_k.copy(), cu_n.copy()
+        return recs[:int(cu_k[-1])], cu_k.copy(), cu_n.copy()
 
     def pack(self, klines, length, angles, token_distance, max_tokens, image=0, sub_base=0):
         """records for already-filtered lines (float64 arrays, reference layout).  They are written into a pinned staging
         slot together with the two prefix sums, so that tokenize() uploads them with ONE asynchronous copy."""
         K = len(klines)
-        rec_bytes = max(K, 1) * nat.REC_DTYPE.itemsize
-        slot = self._pinned_slot(rec_bytes + 16 + 64)
-        host = slot["buf"].numpy()
-        recs = host[:rec_bytes].view(nat.REC_DTYPE)
+        recs, cu_k, cu_n = self._record_blob(K, 1)
         n_out = C.c_int32()
         kl = np.ascontiguousarray(klines, dtype=np.float64)
         ln = np.ascontiguousarray(length, dtype=np.float64)
         an = np.ascontiguousarray(angles, dtype=np.float64)
         nat.check(self._L.linetr_pack_lines(nat.np_ptr(kl), nat.np_ptr(ln), nat.np_ptr(an), K, float(token_distance),
                                             int(max_tokens), int(image), int(sub_base), 0, nat.np_ptr(recs), C.byref(n_out)), self._L)
-        cu = host[rec_bytes:rec_bytes + 16].view(np.int32)
-        cu[:] = (0, K, 0, n_out.value)                     # cu_k | cu_n of the one image
-        self._last_host = {"slot": slot, "recs_ptr": recs.ctypes.data, "rec_bytes": rec_bytes, "B": 1}
+        cu_k[:] = (0, K)
+        cu_n[:] = (0, n_out.value)
         return recs[:K], n_out.value
 
     def pack_many(self, lines, token_distance, max_tokens):
@@ -273,12 +273,7 @@ class Engine:
         B = len(lines)
         ks = [len(l["klines"]) for l in lines]
         K = int(sum(ks))
-        rec_bytes = max(K, 1) * nat.REC_DTYPE.itemsize
-        slot = self._pinned_slot(rec_bytes + 8 * (B + 1) + 64)
-        host = slot["buf"].numpy()
-        recs = host[:rec_bytes].view(nat.REC_DTYPE)
-        cu_k = host[rec_bytes:rec_bytes + 4 * (B + 1)].view(np.int32)
-        cu_n = host[rec_bytes + 4 * (B + 1):rec_bytes + 8 * (B + 1)].view(np.int32)
+        recs, cu_k, cu_n = self._record_blob(K, B)
         cu_k[0] = cu_n[0] = 0
         tok = 0
         n_out = C.c_int32()
@@ -293,17 +288,12 @@ class Engine:
             cu_k[i + 1] = k0 + ks[i]
             cu_n[i + 1] = cu_n[i] + n_out.value
             tok += int(recs["n_tok"][k0:k0 + ks[i]].sum())
-        self._last_host = {"slot": slot, "recs_ptr": recs.ctypes.data, "rec_bytes": rec_bytes, "B": B}
         return recs[:K], cu_k.copy(), cu_n.copy()
 
     # ------------------------------------------------------------------ device stages
-    def tokenize(self, recs, cu_k, cu_n, dense_desc, dense_score, *, token_distance, max_tokens, align_corners=False,
-                 sample_desc=True, dense_layout="nchw", want_mat=False, clip_shape=None) -> TokenBatch:
-        """line_tokenizer on the device.  dense_desc [B,256,H/8,W/8] (dense_layout='nchw') or [B,H/8,W/8,256]
-        ('nhwc', the producer's layout: no transposition pass), dense_score [B,H,W].  clip_shape: the (height, width) the
-        reference's `image_shape` argument carries when it is not the maps' shape (it only sets the end-point clip)."""
-        B = len(cu_k) - 1
-        K, N, T = int(cu_k[-1]), int(cu_n[-1]), int(max_tokens)
+    def _dense_maps(self, dense_desc, dense_score, B, dense_layout):
+        """The dense maps of a B-image call as float32 device tensors with a batch axis, checked against each other: dense_score
+        [B,H,W] and dense_desc [B,256,H/8,W/8] ('nchw') or [B,H/8,W/8,256] ('nhwc').  Returns (dense_desc, dense_score, H, W, nhwc)."""
         dense_desc = self._f32(dense_desc)
         dense_score = self._f32(dense_score)
         if dense_score.dim() == 2:
@@ -317,40 +307,42 @@ class Engine:
         want = (B, H // 8, W // 8, D) if nhwc else (B, D, H // 8, W // 8)
         if tuple(dense_desc.shape) != want:
             raise ValueError(f"dense_descriptor shape {tuple(dense_desc.shape)} does not match {want} ({dense_layout})")
-        dev = self.device
-        f = dict(dtype=torch.float32, device=dev)
-        if want_mat and B != 1:
-            raise ValueError("want_mat needs a single-image call (the reference's matrix is per image)")
-        # the small token tensors are views of ONE allocation (a dozen torch.empty calls cost ~40 us of host time per image on
-        # the drop-in path); every view starts on a 16-byte boundary
-        shapes = [("klines", (K, 2, 2)), ("length", (K,)), ("angles", (K, 2)), ("sublines", (N, 2, 2)), ("pnt", (N, T, 2)),
-                  ("mask", (N, T + 1)), ("resp", (N,)), ("angle_sub", (N, 2)), ("score", (N, T)), ("sub2line", (N,))]
-        if want_mat:
-            shapes.append(("mat", (K, N)))                  # written by extra blocks of the tokeniser's own launch
+        return dense_desc, dense_score, H, W, nhwc
+
+    def _pooled(self, shapes):
+        """Named float32 device tensors as views of ONE allocation, each on a 16-byte boundary (a dozen torch.empty calls are ~40 us of
+        host time on the latency path of a single pair); 'sub2line' is viewed as int32.  Returns (views, the allocation)."""
         sizes = [(math.prod(sh) + 3) // 4 * 4 for _, sh in shapes]
-        pool = torch.empty((sum(sizes),), **f)
+        pool = torch.empty((sum(sizes),), dtype=torch.float32, device=self.device)
         views, o = {}, 0
         for (name, sh), sz in zip(shapes, sizes):
             views[name] = pool[o:o + math.prod(sh)].view(sh)
             o += sz
         views["sub2line"] = views["sub2line"].view(torch.int32)
+        return views, pool
+
+    def tokenize(self, recs, cu_k, cu_n, dense_desc, dense_score, *, token_distance, max_tokens, align_corners=False,
+                 sample_desc=True, dense_layout="nchw", want_mat=False, clip_shape=None) -> TokenBatch:
+        """line_tokenizer on the device.  dense_desc [B,256,H/8,W/8] (dense_layout='nchw') or [B,H/8,W/8,256]
+        ('nhwc', the producer's layout: no transposition pass), dense_score [B,H,W].  clip_shape: the (height, width) the
+        reference's `image_shape` argument carries when it is not the maps' shape (it only sets the end-point clip)."""
+        B = len(cu_k) - 1
+        K, N, T = int(cu_k[-1]), int(cu_n[-1]), int(max_tokens)
+        dense_desc, dense_score, H, W, nhwc = self._dense_maps(dense_desc, dense_score, B, dense_layout)
+        f = dict(dtype=torch.float32, device=self.device)
+        if want_mat and B != 1:
+            raise ValueError("want_mat needs a single-image call (the reference's matrix is per image)")
+        # the small token tensors are views of ONE allocation
+        shapes = [("klines", (K, 2, 2)), ("length", (K,)), ("angles", (K, 2)), ("sublines", (N, 2, 2)), ("pnt", (N, T, 2)),
+                  ("mask", (N, T + 1)), ("resp", (N,)), ("angle_sub", (N, 2)), ("score", (N, T)), ("sub2line", (N,))]
+        if want_mat:
+            shapes.append(("mat", (K, N)))                  # written by extra blocks of the tokeniser's own launch
+        views, pool = self._pooled(shapes)
         tb = TokenBatch(n_images=B, max_tokens=T, cu_k=np.asarray(cu_k, np.int32), cu_n=np.asarray(cu_n, np.int32), recs=recs,
                         desc=torch.empty((N, T, D), **f) if sample_desc else torch.empty((0,), **f), **views)
         if K == 0 or N == 0:
             return tb
-        last = getattr(self, "_last_host", None)
-        if last is not None and K > 0 and recs.ctypes.data == last["recs_ptr"] and last["B"] == B:
-            # records + prefix sums sit in one pinned blob: ONE async H2D, no host/device synchronisation
-            nb = last["rec_bytes"] + 8 * (B + 1)
-            d_blob = torch.empty(nb, dtype=torch.uint8, device=dev)
-            d_blob.copy_(last["slot"]["buf"][:nb], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            last["slot"]["event"] = ev
-            d_recs = d_blob
-            tb.extra["d_cu_n"] = d_blob[last["rec_bytes"] + 4 * (B + 1):].view(torch.int32)
-        else:
-            d_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev)
+        d_recs, _ = self._upload_recs(recs, K, B, tb)
         nbytes = self._L.linetr_tokenize_workspace_bytes(B, H, W, N)
         ws = self._workspace("tok", nbytes)
         ct = tb.c_tokens()
@@ -362,7 +354,6 @@ class Engine:
                                               int(clip_shape[0]) if clip_shape is not None else 0,
                                               int(clip_shape[1]) if clip_shape is not None else 0, int(bool(align_corners)),
                                               int(nhwc), ct, tb.sub2line.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
-        tb.extra["d_recs"] = d_recs  # keep alive until the stream has consumed it
         return tb
 
     def describe(self, recs, cu_k, cu_n, dense_desc, dense_score, *, token_distance, max_tokens, align_corners=False,
@@ -376,36 +367,16 @@ class Engine:
         (class DescribePipeline does the bookkeeping)."""
         B = len(cu_k) - 1
         K, N, T = int(cu_k[-1]), int(cu_n[-1]), int(max_tokens)
-        dense_desc = self._f32(dense_desc)
-        dense_score = self._f32(dense_score)
-        if dense_score.dim() == 2:
-            dense_score = dense_score[None]
-        if dense_desc.dim() == 3:
-            dense_desc = dense_desc[None]
-        if dense_desc.shape[0] != B or dense_score.shape[0] != B:
-            raise ValueError("dense maps must have one entry per image")
-        H, W = int(dense_score.shape[-2]), int(dense_score.shape[-1])
-        nhwc = dense_layout == "nhwc"
-        want = (B, H // 8, W // 8, D) if nhwc else (B, D, H // 8, W // 8)
-        if tuple(dense_desc.shape) != want:
-            raise ValueError(f"dense_descriptor shape {tuple(dense_desc.shape)} does not match {want} ({dense_layout})")
-        dev = self.device
-        f = dict(dtype=torch.float32, device=dev)
-        # the small outputs and line_desc are views of ONE allocation (every view on a 16-byte boundary): a dozen torch.empty
-        # calls are ~40 us of host time on the latency path of a single pair
+        dense_desc, dense_score, H, W, nhwc = self._dense_maps(dense_desc, dense_score, B, dense_layout)
+        f = dict(dtype=torch.float32, device=self.device)
+        # the small outputs and line_desc are views of ONE allocation
         shapes = [("ld", (N, D)), ("klines", (K, 2, 2)), ("length", (K,)), ("angles", (K, 2)), ("sublines", (N, 2, 2)),
                   ("resp", (N,)), ("angle_sub", (N, 2)), ("sub2line", (N,))]
         if want_tokens:
             shapes += [("pnt", (N, T, 2)), ("mask", (N, T + 1)), ("score", (N, T))]
         if want_mat:     # the per-image [K_i,N_i] blocks back to back, written by extra blocks of the tokeniser's launch (<= 8 images)
             shapes.append(("mat", (int((np.diff(np.asarray(cu_k, np.int64)) * np.diff(np.asarray(cu_n, np.int64))).sum()),)))
-        sizes = [(math.prod(sh) + 3) // 4 * 4 for _, sh in shapes]
-        pool = torch.empty((sum(sizes),), **f)
-        views, o = {}, 0
-        for (name, sh), sz in zip(shapes, sizes):
-            views[name] = pool[o:o + math.prod(sh)].view(sh)
-            o += sz
-        views["sub2line"] = views["sub2line"].view(torch.int32)
+        views, pool = self._pooled(shapes)
         ld = views.pop("ld")
         z = pool[:0]
         for name in ("pnt", "mask", "score"):
@@ -477,7 +448,8 @@ class Engine:
                              dense_layout=dense_layout, pipeline_slot=pipeline_slot)
 
     def _upload_recs(self, recs, K, B, tb):
-        """H2D of the line records (+ the sub-line prefix sums when they sit in the same pinned blob)."""
+        """H2D of the line records (+ the sub-line prefix sums when they sit in the same pinned blob: ONE asynchronous copy, no host /
+        device synchronisation).  The device copies are kept in tb.extra until the TokenBatch goes: the stream reads them later."""
         dev = self.device
         last = getattr(self, "_last_host", None)
         if last is not None and K > 0 and recs.ctypes.data == last["recs_ptr"] and last["B"] == B:
@@ -495,8 +467,9 @@ class Engine:
         tb.extra["d_recs"] = d_recs
         return d_recs, None
 
-    def forward_tensors(self, sublines, pnt, resp, angle_sub, desc, score, cu_n, out=None, d_cu_n=None) -> torch.Tensor:
-        """LineTransformer.forward on flat tensors; returns line_desc [N,256] (row-major)."""
+    def _dense_tokens(self, sublines, pnt, resp, angle_sub, desc, score, cu_n):
+        """The reference's dense [N,T] token tensors as the native Tokens struct.  Returns (N, T, struct, cu_n as int32, the float32
+        device tensors the struct points to -- to be kept alive over the call)."""
         N, T = int(pnt.shape[0]), int(pnt.shape[1])
         t = nat.Tokens()
         keep = [self._f32(x) for x in (sublines, pnt, resp, angle_sub, desc, score)]
@@ -504,6 +477,11 @@ class Engine:
         cu = np.ascontiguousarray(cu_n, dtype=np.int32)
         if int(cu[-1]) != N:
             raise ValueError("cu_n does not match the number of sub-lines")
+        return N, T, t, cu, keep
+
+    def forward_tensors(self, sublines, pnt, resp, angle_sub, desc, score, cu_n, out=None, d_cu_n=None) -> torch.Tensor:
+        """LineTransformer.forward on flat tensors; returns line_desc [N,256] (row-major)."""
+        N, T, t, cu, _keep = self._dense_tokens(sublines, pnt, resp, angle_sub, desc, score, cu_n)
         if out is None:
             out = torch.empty((N, D), dtype=torch.float32, device=self.device)
         if N == 0:
@@ -522,13 +500,7 @@ class Engine:
         the statistics of THIS batch; `bn_running` (float32 device tensor of bn_stats_floats() entries: per BatchNorm layer
         mean[C] | var[C]; word encoder's four layers, line encoder's four, then one per signature layer) is updated in place.  Returns line_desc [N,256], and with want_batch_stats the batch mean
         | biased variance packed the same way."""
-        N, T = int(pnt.shape[0]), int(pnt.shape[1])
-        t = nat.Tokens()
-        keep = [self._f32(x) for x in (sublines, pnt, resp, angle_sub, desc, score)]
-        t.sublines, t.pnt, t.resp, t.angle_sub, t.desc, t.score = [x.data_ptr() for x in keep]
-        cu = np.ascontiguousarray(cu_n, dtype=np.int32)
-        if int(cu[-1]) != N:
-            raise ValueError("cu_n does not match the number of sub-lines")
+        N, T, t, cu, _keep = self._dense_tokens(sublines, pnt, resp, angle_sub, desc, score, cu_n)
         n_stats = self.bn_stats_floats()
         if (bn_running.dtype != torch.float32 or bn_running.device != self.device or not bn_running.is_contiguous()
                 or bn_running.numel() != n_stats):
@@ -707,6 +679,18 @@ class Engine:
                                                         int(nhwc), out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
         return out
 
+    def _host_stage(self, nbytes):
+        """The next of a ring of four pinned device -> host staging buffers, at least nbytes long.  Returns (buffer, the ring's
+        generation counters, slot, the slot's generation now): a ticket handed out on the slot before is stale from here on, which
+        collect() / collect_tail() find by comparing the last two."""
+        ring = self.__dict__.setdefault("_host_ring", {"i": 0, "bufs": [None] * 4, "gen": [0] * 4})
+        i = ring["i"] = (ring["i"] + 1) % len(ring["bufs"])
+        ring["gen"][i] += 1
+        stage = ring["bufs"][i]
+        if stage is None or stage.numel() < nbytes:
+            stage = ring["bufs"][i] = torch.empty(nbytes * 2 + 4096, dtype=torch.uint8, pin_memory=True)
+        return stage, ring["gen"], i, ring["gen"][i]
+
     def to_host_async(self, *tensors):
         """Queues the device -> host copies of `tensors` into a pinned staging buffer on the current stream and returns a ticket for
         collect().  Nothing is waited for: a result that is ready early (the point matcher's, queued before the line branch) travels
@@ -715,12 +699,7 @@ class Engine:
         offs = [0]
         for b in sizes:
             offs.append(offs[-1] + (b + 255) // 256 * 256)
-        ring = self.__dict__.setdefault("_host_ring", {"i": 0, "bufs": [None] * 4, "gen": [0] * 4})
-        i = ring["i"] = (ring["i"] + 1) % len(ring["bufs"])
-        ring["gen"][i] += 1                       # a ticket on this slot that was never collected is stale from here on
-        stage = ring["bufs"][i]
-        if stage is None or stage.numel() < offs[-1]:
-            stage = ring["bufs"][i] = torch.empty(offs[-1] * 2 + 4096, dtype=torch.uint8, pin_memory=True)
+        stage, *gen = self._host_stage(offs[-1])
         views = []
         for t, o, b in zip(tensors, offs[:-1], sizes):
             v = stage[o:o + b].view(t.dtype).view(t.shape)
@@ -728,7 +707,7 @@ class Engine:
             views.append(v)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
-        return views, ev, ring["gen"], i, ring["gen"][i]
+        return (views, ev, *gen)
 
     @staticmethod
     def collect(ticket):
@@ -770,12 +749,7 @@ class Engine:
             out_bytes = int(self._L.linetr_pair_tail_output_bytes(np0, np1, int(k0), int(k1), offs))
             tab = cache[key] = (out_bytes, tuple(int(v) for v in offs), int(self._L.linetr_pair_tail_workspace_bytes(*key)))
         out_bytes, offs, ws_bytes = tab
-        ring = self.__dict__.setdefault("_host_ring", {"i": 0, "bufs": [None] * 4, "gen": [0] * 4})
-        i = ring["i"] = (ring["i"] + 1) % len(ring["bufs"])
-        ring["gen"][i] += 1
-        stage = ring["bufs"][i]
-        if stage is None or stage.numel() < out_bytes:
-            stage = ring["bufs"][i] = torch.empty(out_bytes * 2 + 4096, dtype=torch.uint8, pin_memory=True)
+        stage, *gen = self._host_stage(out_bytes)
         ws = self._workspace("tail", ws_bytes)
         s0 = s2l0 if (lns and s2l0.dtype == torch.int32 and s2l0.device == self.device and s2l0.is_contiguous()) else \
             (s2l0.to(device=self.device, dtype=torch.int32).contiguous() if lns else None)
@@ -789,7 +763,7 @@ class Engine:
                       self._L)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
-        return stage, offs, key, ev, ring["gen"], i, ring["gen"][i], (p0, p1, l0, l1, s0, s1)     # (inputs kept alive until collected)
+        return (stage, offs, key, ev, *gen, (p0, p1, l0, l1, s0, s1))     # (inputs kept alive until collected)
 
     @staticmethod
     def collect_tail(ticket):
