@@ -38,8 +38,7 @@ __global__ __launch_bounds__(512) void gemm_chain_kernel(ChainArgs c) {
   }
   const int m0 = mt * BM;
   constexpr int N_TERM = 6, N_MMA = MI * NI * N_TERM, N_FRAG = (MI + NI) * PL, E1 = 2 * A_F4 + B_PCS;
-  constexpr int TPA[6] = {2, 1, 0, 1, 0, 0};
-  constexpr int TPB[6] = {0, 1, 2, 0, 1, 0};
+  using Terms = split_terms<PL>;
 
 #pragma unroll 1
   for (int s = 0; s < c.n; ++s) {
@@ -117,7 +116,7 @@ __global__ __launch_bounds__(512) void gemm_chain_kernel(ChainArgs c) {
       bf16x8 af0[MI][PL], bf0[NI][PL], af1[MI][PL], bf1[NI][PL];
       auto step_mma = [&](int m, const bf16x8 (&af)[MI][PL], const bf16x8 (&bf)[NI][PL]) {
         const int t = m / (MI * NI), ij = m % (MI * NI), i = ij / NI, j = ij % NI;
-        acc[i][j] = mfma_split<0>(af[i][TPA[t]], bf[j][TPB[t]], acc[i][j]);
+        acc[i][j] = mfma_split<0>(af[i][Terms::pa(t)], bf[j][Terms::pb(t)], acc[i][j]);
       };
       // fragment read order = order of first use by the MFMAs (lt_gemm_split.h)
 #define LT_CH_FRAG(k) (((k) / (MI + NI)) == 0 ? (((k) % (MI + NI)) < MI ? ((k) % (MI + NI)) * PL + (PL - 1) : MI * PL + (((k) % (MI + NI)) - MI) * PL) \

@@ -39,11 +39,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ro_kernel(RoGemmArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h2 = lane >> 5, lq = lane & 31;
   const int gx = a.N / RO_BN, gy = (a.M + RO_BM - 1) / RO_BM;
-  int tile;
-  {
-    const int ntile = gx * gy, b = blockIdx.x, q = ntile / 8, r = ntile % 8, xcd = b % 8, k = b / 8;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = xcd_tile(blockIdx.x, gx * gy);
   const int m0 = (tile / gx) * RO_BM, n0 = (tile % gx) * RO_BN;
   const int nk = a.nk1 + a.nk2;
   const int64_t RBW = a.N / 16;
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ro_kernel(RoGemmArgs a) {
 
   const int lfrag = ((lane >> 4) & 1) * ST_RB + (lane >> 5) * 256 + (lane & 15) * 16;
   const int zoff = RO_W_BYTES + (wave * 32 + lq) * 64 + h2 * 32;
-  constexpr int TW[6] = {2, 1, 0, 1, 0, 0}, TA[6] = {0, 1, 2, 0, 1, 0};     // smallest cross terms first
+  using Terms = split_terms<3>;                            // the weights are the MFMA's A operand
   auto read_w = [&](int slot, int i, int p, bf16x8 (&wf)[3]) {
     wf[p] = *reinterpret_cast<const bf16x8*>(ro_smem + slot * RO_SLOT + lfrag + i * 2 * ST_RB + p * ST_CHUNK);
   };
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ro_kernel(RoGemmArgs a) {
       const int i = m / 6, t = m % 6;
       bf16x8 (&wc)[3] = (i & 1) ? wfB : wfA;
       bf16x8 (&wn)[3] = (i & 1) ? wfA : wfB;
-      acc[i] = mfma_split<0>(wc[TW[t]], zf[TA[t]], acc[i]);
+      acc[i] = mfma_split<0>(wc[Terms::pa(t)], zf[Terms::pb(t)], acc[i]);
       if (t < 3 && i < 7) read_w(slot, i + 1, t, wn);
       if (m < 8 && refill) issue_one(m, s + 1, slot ^ 1);
       __builtin_amdgcn_sched_barrier(0);
@@ -171,8 +167,8 @@ __global__ __launch_bounds__(256, 2) void gemm_ro_kernel(RoGemmArgs a) {
       float* yp = a.Y + (int64_t)row * a.ldy + n0 + i * 32 + 8 * h2;
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        sk_store16(yp + 16 * g, f32x4{acc[i][8 * g], acc[i][8 * g + 1], acc[i][8 * g + 2], acc[i][8 * g + 3]});
-        sk_store16(yp + 16 * g + 4, f32x4{acc[i][8 * g + 4], acc[i][8 * g + 5], acc[i][8 * g + 6], acc[i][8 * g + 7]});
+        store16_write_through(yp + 16 * g, f32x4{acc[i][8 * g], acc[i][8 * g + 1], acc[i][8 * g + 2], acc[i][8 * g + 3]});
+        store16_write_through(yp + 16 * g + 4, f32x4{acc[i][8 * g + 4], acc[i][8 * g + 5], acc[i][8 * g + 6], acc[i][8 * g + 7]});
       }
     }
   }
@@ -222,8 +218,8 @@ __global__ __launch_bounds__(256, 2) void gemm_ro_kernel(RoGemmArgs a) {
       }
       if (live) {
         float* yp = a.Y + (int64_t)row * a.ldy + col;
-        sk_store16(yp, o0);
-        sk_store16(yp + 4, o1);
+        store16_write_through(yp, o0);
+        store16_write_through(yp + 4, o1);
       }
     }
 }

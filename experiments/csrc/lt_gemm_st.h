@@ -45,11 +45,7 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(StGemmArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave & 3, wm = wave >> 2;
   const int gx = a.N / STG_BN, gy = (a.M + STG_BM - 1) / STG_BM;
-  int tile;
-  {
-    const int ntile = gx * gy, b = blockIdx.x, q = ntile / 8, r = ntile % 8, xcd = b % 8, k = b / 8;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = xcd_tile(blockIdx.x, gx * gy);
   const int m0 = (tile / gx) * STG_BM, n0 = (tile % gx) * STG_BN;
   const int64_t RBa = st_row_blocks(a.M), RBw = a.N / 16;
   const int nk = a.nk1 + a.nk2;
@@ -103,8 +99,7 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(StGemmArgs a) {
   const int lfrag = ((lane >> 4) & 1) * ST_RB + (lane >> 5) * 256 + (lane & 15) * 16;
   const unsigned char* wbase = st_smem + wn * 4 * ST_RB + lfrag;
   const unsigned char* abase = st_smem + STG_W_BYTES + wm * 4 * ST_RB + lfrag;
-  // term t multiplies weight plane TW[t] with activation plane TA[t]; smallest cross terms first
-  constexpr int TW[6] = {2, 1, 0, 1, 0, 0}, TA[6] = {0, 1, 2, 0, 1, 0};
+  using Terms = split_terms<3>;                // the weights are the MFMA's A operand
   auto read_one = [&](int f, int slotoff, bf16x8 (&wf)[2][3], bf16x8 (&af)[2][3]) {
     const int grp = f / 4, w = f % 4;          // group 0: planes (W 2, A 0), group 1: (1, 1), group 2: (0, 2)
     const int i = w >> 1;
@@ -120,7 +115,7 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(StGemmArgs a) {
   auto mma_one = [&](int m, const bf16x8 (&wf)[2][3], const bf16x8 (&af)[2][3]) {
     const int t = m / 4, i = (m >> 1) & 1, j = m & 1;
     if (DBG & 1) return;
-    acc[i][j] = mfma_split<0>(wf[i][TW[t]], af[j][TA[t]], acc[i][j]);
+    acc[i][j] = mfma_split<0>(wf[i][Terms::pa(t)], af[j][Terms::pb(t)], acc[i][j]);
   };
 
   // ---- prologue: K steps 0..3 into slots 0..3 (a problem with fewer steps fetches its last one again)

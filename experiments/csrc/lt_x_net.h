@@ -2,12 +2,13 @@
 // includes this file textually, behind sig_network: lt_st_image.h and lt_model.h define non-template kernels, so a second
 // translation unit would duplicate their host stubs, and the code here uses that file's local helpers (run_gemm, NormSpec,
 // FwdWs, TokenStage, sentence, sig_attention, pipe_boundary).  The hooks linetr_net.hip calls:
-//   x_gemm           run_gemm: the stream-K workspace (LINETR_STREAMK) and the row-owner GEMM (LINETR_GEMM_RO)
+//   x_gemm           run_gemm: the stream-K tail (LINETR_STREAMK) and the row-owner GEMM (LINETR_GEMM_RO) take the launch
 //   x_split_weights  make_split_copies: an ST image of every eligible weight, and each signature layer's W2p
 //   x_ws_bytes       fwd_layout: the split-tile activation images and the pairnet area, carved from FwdWs::x
 //   x_begin          forward_core, before the encoders: zeroes the pairnet counters and chooses the path (XPath)
 //   x_rest           forward_core, behind cls_pooling: the sentence rows and the signature network of the chosen path
 #pragma once
+#include "lt_gemm_sk.h"
 #include "lt_gemm_st.h"
 #include "lt_gemm_ro.h"
 #include "lt_gemm_chain.h"
@@ -19,19 +20,9 @@ namespace {
 
 int x_gemm(LinetrHandle* h, hipStream_t st, SplitGemmArgs& sa, const GemmW& w, int groups, const NormSpec* fused_norm,
            double fl, double by, bool& done) {
-  if (LT_XENV("LINETR_STREAMK")) {   // opt-in experiment (lt_gemm_split.h): the 32 MB workspace is only allocated when asked for
-    if (!h->sk_ws) {
-      constexpr size_t slots = 256, slot_bytes = 128 * 256 * sizeof(float);
-      LT_HIP(hipMalloc((void**)&h->sk_ws, slots * slot_bytes));
-      LT_HIP(hipMalloc((void**)&h->sk_flags, (slots + 1) * sizeof(unsigned)));
-      LT_HIP(hipMemset(h->sk_flags, 0, (slots + 1) * sizeof(unsigned)));
-      LT_HIP(hipDeviceSynchronize());
-    }
-    sa.sk_ws = h->sk_ws; sa.sk_flags = h->sk_flags; sa.sk_epoch = ++h->sk_epoch;
-  }
+  const GemmArgs& g = sa.g;
   // row-owner kernel (lt_gemm_ro.h): 4-wave blocks, two per CU, operands by LDS-DMA.  Measured at cfg3: 117 TF-eq against 137 for
   // the register-staged tiles (a two-slot ring leaves a DMA one K step to land, and the barrier comes every 48 MFMAs), so opt-in.
-  const GemmArgs& g = sa.g;
   if (h->precision == LINETR_PREC_BF16X6 && LT_XENV("LINETR_GEMM_RO") != nullptr && groups == 1 && g.N % 256 == 0 && g.K % 32 == 0 &&
       w.st && g.lda % 4 == 0 && g.ldy % 4 == 0 && (!g.A2 || (g.lda2 % 4 == 0 && g.K1 % 16 == 0)) && (!g.R || g.ldr % 4 == 0) &&
       g.act != ACT_DIST && cdiv(g.M, 128) * (g.N / 256) >= 140) {
@@ -43,6 +34,28 @@ int x_gemm(LinetrHandle* h, hipStream_t st, SplitGemmArgs& sa, const GemmW& w, i
     done = true;
     ProfScope ps(h, st, "gemm_bf16x6_ro128x256", fl, by);
     return gemm_ro_launch(a, st);
+  }
+  // stream-K tail (lt_gemm_sk.h), opt-in, behind the row-owner GEMM as before: takes the launches run_gemm would give to the 128x256 tile when a tail pays; a shape
+  // that tile refuses is left to gemm_split_launch to refuse.  The 32 MB workspace is only allocated when it is first needed.
+  SplitTile tile = SplitTile::count;
+  if (LT_XENV("LINETR_STREAMK") && !gemm_ws_takes(h, g, w, groups, fused_norm))
+    if (int e = pick_split_tile(g, groups, h->precision == LINETR_PREC_BF16X6 ? 3 : 2, tile)) return e;
+  if (tile == SplitTile::t128x256 && g.N % 256 == 0 && g.K % 32 == 0 && (!g.A2 || g.K1 % 32 == 0) && (g.norm == 0 || g.N == 256) &&
+      gemm_split_sk_pays(g, groups)) {
+    if (!h->sk_ws) {
+      constexpr size_t slots = 256, slot_bytes = 128 * 256 * sizeof(float);
+      LT_HIP(hipMalloc((void**)&h->sk_ws, slots * slot_bytes));
+      LT_HIP(hipMalloc((void**)&h->sk_flags, (slots + 1) * sizeof(unsigned)));
+      LT_HIP(hipMemset(h->sk_flags, 0, (slots + 1) * sizeof(unsigned)));
+      LT_HIP(hipDeviceSynchronize());
+    }
+    done = true;
+    ProfScope ps(h, st, gemm_class_name(h->precision, (int)tile, g, groups), fl, by);
+    switch (h->precision) {
+      case LINETR_PREC_BF16X3: sa.Wsp = w.s2; return gemm_split_sk_launch<2, 0>(sa, h->sk_ws, h->sk_flags, ++h->sk_epoch, st);
+      case LINETR_PREC_F16X3: sa.Wsp = w.h2; return gemm_split_sk_launch<2, 1>(sa, h->sk_ws, h->sk_flags, ++h->sk_epoch, st);
+      default: sa.Wsp = w.s3; return gemm_split_sk_launch<3, 0>(sa, h->sk_ws, h->sk_flags, ++h->sk_epoch, st);
+    }
   }
   return LINETR_OK;
 }
@@ -119,14 +132,8 @@ bool chain_wins(const LinetrHandle* h, int rows) {
   // opt-in (read per call): measured at cfg3, 2.70 vs 2.60 ms per step -- a chain keeps 199 of the 256 CUs busy for all of its
   // stages and the per-tile prologue / epilogue cost, not the launch, is what a GEMM of this size pays
   if (LT_XENV("LINETR_GEMM_CHAIN") == nullptr || h->precision != LINETR_PREC_BF16X6) return false;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
   const int gy = cdiv(rows, 128);
-  return (gy >= 140 && gy <= n_cu) || gy >= 4 * n_cu;
+  return (gy >= 140 && gy <= cu_count()) || gy >= 4 * cu_count();
 }
 
 // the descriptive layer's tail as a chain: [fc + LN] -> [w_1, GELU] -> [w_2 + residual + LN (+ line position)] -> [q/k/v of

@@ -68,14 +68,14 @@ def test_fused_signature_mlp_equals_two_gemms(eng, monkeypatch, mode):
     assert ((fused.norm(dim=1) - 1).abs() < 1e-5).all()
 
 
-# the shapes below that take the pipelined 128x256 tile, whose last round of tiles gets a stream-K tail on 256 CUs (lt_gemm_split.h)
+# the shapes below that take the pipelined 128x256 tile, whose last round of tiles gets a stream-K tail on 256 CUs (csrc/lt_gemm_sk.h)
 _STREAM_K_TAIL_SHAPES = {(25472, 512, 512), (9584, 512, 512), (25473, 512, 256)}
 
 
 @pytest.mark.parametrize("M,N,K,act", [(25472, 512, 512, 1), (25472, 768, 256, 0), (9584, 512, 512, 2), (25473, 512, 256, 0),
                                        (16500, 256, 1024, 0)])
 def test_gemm_stream_k_tail(eng, M, N, K, act, monkeypatch):
-    """(stream-K is opt-in, LINETR_STREAMK=1: measured slower than the plain launch as built, see lt_gemm_split.h.)
+    """(stream-K is opt-in, LINETR_STREAMK=1: measured slower than the plain launch as built, see csrc/lt_gemm_sk.h.)
     Shapes whose last round of 128x256 tiles would leave part of the chip idle: the tail tiles are shared by one block
     per CU in (tile, K-tile) runs, partial accumulator tiles travel through the workspace (lt_gemm_split.h).  Against
     float64 with every epilogue piece, a ragged last row tile, and twice in a row: the partition and the summation order

@@ -83,6 +83,12 @@ int gemm_args(const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, co
   return LINETR_OK;
 }
 
+// every token row of the batch through a K = 128 layer: weights stay in registers, rows stream (lt_gemm_ws.h)
+bool gemm_ws_takes(const LinetrHandle* h, const GemmArgs& g, const GemmW& w, int groups, const NormSpec* fused_norm) {
+  return h->precision == LINETR_PREC_BF16X6 && groups == 1 && !g.A2 && !g.R && !fused_norm && w.st &&
+         gemm_ws_fits(g.M, g.N, g.K, g.lda, g.ldy, g.act) && !LT_XENV("LINETR_NO_GEMM_WS");
+}
+
 int run_gemm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, const float* R = nullptr,
              const GemmGroups* grp = nullptr, const NormSpec* fused_norm = nullptr) {
   GemmArgs g;
@@ -97,12 +103,10 @@ int run_gemm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA
   SplitGemmArgs sa;
   sa.g = g;
 #ifdef LINETR_EXPERIMENTS
-  bool done = false;   // hands out the stream-K workspace; done: the row-owner GEMM took the launch
+  bool done = false;   // done: the stream-K or the row-owner GEMM took the launch
   if (int e = x_gemm(h, st, sa, w, groups, fused_norm, fl, by, done); e || done) return e;
 #endif
-  // every token row of the batch through a K = 128 layer: weights stay in registers, rows stream (lt_gemm_ws.h)
-  if (h->precision == LINETR_PREC_BF16X6 && groups == 1 && !A.p2 && !R && !fused_norm && w.st &&
-      gemm_ws_fits(M, g.N, g.K, A.ld, Y.ld, act) && !LT_XENV("LINETR_NO_GEMM_WS")) {
+  if (gemm_ws_takes(h, g, w, groups, fused_norm)) {
     WsGemmArgs a;
     a.A = A.p; a.lda = A.ld; a.Wst = w.st; a.bias = w.b ? w.b : h->zeros; a.Y = Y.p; a.ldy = Y.ld; a.M = M; a.act = act;
     ProfScope ps(h, st, "gemm_bf16x6_ws64x256", fl, by);

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
   const int zrot = (lq >> 2) & 3;
   const int zoff0 = FQA_W_BYTES + (wave * 32 + lq) * 64 + ((2 * h2 + zrot) & 3) * 16;
   const int zoff1 = FQA_W_BYTES + (wave * 32 + lq) * 64 + ((2 * h2 + 1 + zrot) & 3) * 16;
-  constexpr int TW[6] = {2, 1, 0, 1, 0, 0}, TA[6] = {0, 1, 2, 0, 1, 0};     // smallest cross terms first
+  using Terms = split_terms<3>;                            // the weights are the MFMA's A operand
   // Fixed issue order (sched_barrier after every MFMA slot, as in the GEMMs): while n-tile i of step s multiplies, the weight
   // fragments of n-tile i+1 are fetched; the activations of step s+1 are fetched at the start of step s and split into their
   // planes under its MFMAs; during the last n-tile the first weight fragments of step s+1 arrive.  Steps s and s+1 are both
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
       const int i = m / 6, t = m % 6;
       bf16x8 (&wc)[3] = (i & 1) ? wfB : wfA;
       bf16x8 (&wn)[3] = (i & 1) ? wfA : wfB;
-      acc[i] = mfma_split<0>(wc[TW[t]], zc[TA[t]], acc[i]);
+      acc[i] = mfma_split<0>(wc[Terms::pa(t)], zc[Terms::pb(t)], acc[i]);
       if (t < 3) {                                         // next weight fragments: n-tile i+1 of this step, or n-tile 0 of the next
         if (i < 5) read_w(s, i + 1, t, wn);
         else read_w(s + 1, 0, t, wn);                      // (past the last step: reads a slot that is never used; harmless)
@@ -263,8 +263,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
       const int sq = m / 6, t = m % 6;
       bf16x8 (&kc)[3] = (sq & 1) ? kaB : kaA;
       bf16x8 (&kn)[3] = (sq & 1) ? kaA : kaB;
-      constexpr int PK[6] = {2, 1, 0, 1, 0, 0}, PQ[6] = {0, 1, 2, 0, 1, 0};
-      st = mfma_split<0>(kc[PK[t]], qf[sq][PQ[t]], st);
+      st = mfma_split<0>(kc[split_terms<3>::pa(t)], qf[sq][split_terms<3>::pb(t)], st);
       if (t < 3 && sq < 3) kn[t] = *reinterpret_cast<const bf16x8*>(kp + t * 128 + (sq + 1) * 32);
       __builtin_amdgcn_sched_barrier(0);
     }

@@ -28,9 +28,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // were measured and lost.  `python -m linetr_amd.build --experiments` builds liblinetr_hip_experiments.so from the same sources
 // plus experiments/csrc: the stream-K tail, the 256x256 tile, the fused signature MLP, the split-tile / LDS-DMA path, the
 // row-owner GEMM, GEMM chains and the single-pair persistent network, and the switches that select them or that tools/ and
-// experiments/test_experiments.py read.  Apart from the two kernel-side blocks of lt_gemm_split.h, the host code of those paths
-// lives in experiments/csrc/lt_x_net.h and reaches the forward pass through a few one-line hooks in linetr_net.hip.  LT_XENV is
-// getenv there and a constant null pointer in the product, so every switch on a shipped path folds away.
+// experiments/test_experiments.py read.  Apart from the 256x256 case of gemm_split_launch (lt_gemm_split.h), those kernels and
+// their host code live in experiments/csrc and reach the forward pass through a few one-line hooks in linetr_net.hip
+// (experiments/csrc/lt_x_net.h).  LT_XENV is getenv there and a constant null pointer in the product, so every switch on a
+// shipped path folds away.
 #ifdef LINETR_EXPERIMENTS
 #define LT_XENV(name) getenv(name)
 #else
@@ -83,6 +84,16 @@ inline hipError_t allow_dynamic_lds(int bytes) {
   return e;
 }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// Compute units of the device that is current at the first call (256 if it cannot be asked), cached for the process: what
+// the persistent launchers size their grids by.
+inline int cu_count() {
+  static const int n_cu = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+  }();
+  return n_cu;
+}
 
 // ---- device helpers -------------------------------------------------------------------------
 

@@ -45,6 +45,51 @@ struct GemmArgs {
 constexpr int GEMM_BK = 32;
 constexpr int GEMM_LDS_STRIDE = GEMM_BK + 4;
 
+// ---- rules every GEMM kernel of the family shares ----------------------------------------------------------------
+__device__ __forceinline__ float apply_act(float v, int act) {
+  if (act == ACT_RELU) v = fmaxf(v, 0.f);
+  else if (act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+  else if (act == ACT_DIST) v = fmaxf(2.f - 2.f * v, 0.f);
+  return v;
+}
+
+// C/D layout of the 32x32 MFMAs: register r of lane (column lane & 31, half h = lane >> 5) is row cd_row(r, h)
+// (gemm_kernel and gemm_split_kernel spell the expression out on purpose: through this call the compiler reassociates their
+// row arithmetic and the kernels' instructions move)
+__device__ __forceinline__ constexpr int cd_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// The cross terms a PL-plane split product keeps (pa + pb <= PL - 1) in the order every kernel of the family accumulates them,
+// smallest first: pa + pb descending, then pa descending.  Term t multiplies plane pa(t) of the MFMA's A operand with plane
+// pb(t) of its B operand.
+template <int PL>
+struct split_terms {
+  static_assert(PL == 2 || PL == 3, "two or three planes");
+  static constexpr int N = PL * (PL + 1) / 2;
+  static constexpr int PA[6] = {PL == 3 ? 2 : 1, PL == 3 ? 1 : 0, 0, 1, 0, 0};
+  static constexpr int PB[6] = {0, 1, PL == 3 ? 2 : 0, 0, 1, 0};
+  static constexpr int pa(int t) { return PA[t]; }
+  static constexpr int pb(int t) { return PB[t]; }
+  static constexpr bool follows_rule() {
+    int t = 0;
+    for (int ord = PL - 1; ord >= 0; --ord)
+      for (int a = PL - 1; a >= 0; --a) {
+        if (ord - a < 0 || ord - a >= PL) continue;
+        if (PA[t] != a || PB[t] != ord - a) return false;
+        ++t;
+      }
+    return t == N;
+  }
+};
+static_assert(split_terms<2>::follows_rule(), "PL 2: (1,0) (0,1) (0,0)");
+static_assert(split_terms<3>::follows_rule(), "PL 3: (2,0) (1,1) (0,2) (1,0) (0,1) (0,0)");
+
+// XCD-aware tile order: hardware places block b on XCD b % 8 (speed assumption only).  Every XCD gets a contiguous run of
+// the ntile tiles, so with column tiles of one row tile adjacent the A row tile is fetched into ONE L2.
+__device__ __forceinline__ int xcd_tile(int block, int ntile) {
+  const int b = block, q = ntile / 8, r = ntile % 8, xcd = b % 8, k = b / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   constexpr int TM = BM / WM, TN = BN / WN;
@@ -145,10 +190,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (row < g.M) {
-          float v = acc[i][j][r] + bv;
-          if (g.act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (g.act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-          else if (g.act == ACT_DIST) v = fmaxf(2.f - 2.f * v, 0.f);
+          float v = apply_act(acc[i][j][r] + bv, g.act);
           if (g.R) v += g.R[(int64_t)row * g.ldr + col];
           Y[(int64_t)row * g.ldy + col] = v;
         }

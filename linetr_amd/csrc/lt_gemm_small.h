@@ -141,7 +141,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_split_small_kernel(SplitGemmArg
 
   // partial sums -> LDS (row stride 33: the 16 ds_write_b32 of a wave hit distinct banks)
 #pragma unroll
-  for (int r = 0; r < 16; ++r) red[wave][((r & 3) + 8 * (r >> 2) + 4 * half) * 33 + frow] = acc[r];
+  for (int r = 0; r < 16; ++r) red[wave][cd_row(r, half) * 33 + frow] = acc[r];
   __syncthreads();
   if (e_on) {
     float* Y = g.Y + grp * g.gY;

@@ -83,26 +83,27 @@ __global__ void split_rows_kernel(const float* __restrict__ W, unsigned char* __
 
 struct SplitGemmArgs {
   GemmArgs g;                 // g.W unused
-  const unsigned char* Wsp;   // split weights
-  int64_t gWsp;               // bytes between groups
+  const unsigned char* Wsp = nullptr;   // split weights
+  int64_t gWsp = 0;           // bytes between groups
   int wide_epi = 0;           // epilogue through LDS with dwordx4 row stores (set by gemm_split_launch_t)
-  // stream-K tail (128x256 pipelined kernel only; see gemm_split_kernel): tiles >= sk_first are shared by sk_blocks
-  // blocks that each take an equal run of (tile, K-tile) iterations
+  // stream-K tail (the SKT instantiations of gemm_split_kernel, launched by experiments/csrc/lt_gemm_sk.h only): tiles >= sk_first
+  // are shared by sk_blocks blocks that each take an equal run of (tile, K-tile) iterations
   int sk_first = 0, sk_blocks = 0;
   float* sk_ws = nullptr;           // [sk_blocks][BM * BN] partial accumulator tiles
   unsigned* sk_flags = nullptr;     // [sk_blocks] = epoch once the block's partial tile is published; [sk_blocks] = error flag
   unsigned sk_epoch = 0;
 };
 
-// ---- stream-K hand-off (MI355X_MICROARCH.md, "publish-large" / "Valid forms"): the partial tile is written with
-// write-through (sc1) 16-byte stores and read back with sc1 loads, the flag is a relaxed agent-scope atomic behind a
-// drained vmcnt.  No release / acquire fences: an agent release writes back the XCD's whole L2 -- which is full of the
-// output rows the data-parallel blocks of the same launch have just stored -- once per publishing block.
-__device__ __forceinline__ void sk_store16(float* p, const f32x4& v) {
+// 16-byte write-through (sc1) store: the data leaves the XCD's L2 at once instead of being written back behind the launch
+__device__ __forceinline__ void store16_write_through(float* p, const f32x4& v) {
   // the trailing s_nop: hipcc does not pad an asm store, and its next instruction may otherwise overwrite the data
   // registers before the store has read them (cdna_hip_programming.md 5.7)
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
 }
+// ---- stream-K hand-off (MI355X_MICROARCH.md, "publish-large" / "Valid forms"): the partial tile is written with
+// write-through (sc1) 16-byte stores and read back with sc1 loads, the flag is a relaxed agent-scope atomic behind a
+// drained vmcnt.  No release / acquire fences: an agent release writes back the XCD's whole L2 -- which is full of the
+// output rows the data-parallel blocks of the same launch have just stored -- once per publishing block.
 __device__ __forceinline__ f32x4 sk_load16(const float* p) {
   f32x4 v;
   asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
@@ -145,18 +146,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  // XCD-aware tile order: hardware places block b on XCD b % 8 (speed assumption only).  Give every XCD a
-  // contiguous run of tiles, column tiles of one row tile adjacent, so the A row tile is fetched into ONE L2.
   constexpr bool SK = SKT;   // the instantiation that carries a stream-K tail (its own kernel: the extra state costs registers)
   static_assert(!SKT || (PIPE && BM == 128 && BN == 256), "stream-K is built for the pipelined 128x256 tile only");
   const int gx = g.N / BN, gy = (g.M + BM - 1) / BM;
   const int ntile_all = gx * gy;
   const int ntile = (SK && sa.sk_blocks > 0) ? sa.sk_first : ntile_all;   // tiles of the data-parallel part
-  int tile;
-  {
-    const int b = blockIdx.x, q = ntile / 8, r = ntile % 8, xcd = b % 8, k = b / 8;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = xcd_tile(blockIdx.x, ntile);   // column tiles of one row tile adjacent
   int m0 = (tile / gx) * BM, n0 = (tile % gx) * BN;   // re-assigned per segment by stream-K blocks
   const int grp = blockIdx.y;
   const float* A = g.A + grp * g.gA;
@@ -238,22 +233,15 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
 #pragma unroll
       for (int p = 0; p < PL; ++p) bf[j][p] = *reinterpret_cast<const bf16x8*>(Bb + j * 32 * RS + p * 64);
   };
+  using Terms = split_terms<PL>;
   auto mma = [&](const bf16x8 (&af)[MI][PL], const bf16x8 (&bf)[NI][PL]) {
-    // smallest cross terms first
 #pragma unroll
-    for (int ord = 2 * (PL - 1); ord >= 0; --ord) {
-      if (ord > PL - 1) continue;  // keep only terms with pa + pb <= PL-1
+    for (int t = 0; t < Terms::N; ++t)
 #pragma unroll
-      for (int pa = PL - 1; pa >= 0; --pa) {
-        const int pb = ord - pa;
-        if (pb < 0 || pb >= PL) continue;
+      for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-            acc[i][j] = mfma_split<FMT>(af[i][pa], bf[j][pb], acc[i][j]);
-      }
-    }
+        for (int j = 0; j < NI; ++j)
+          acc[i][j] = mfma_split<FMT>(af[i][Terms::pa(t)], bf[j][Terms::pb(t)], acc[i][j]);
   };
   auto compute = [&](int buf) {
 #pragma unroll
@@ -292,20 +280,18 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
       //   first half  (MFMAs of K step 0): ds_reads of step 1, then split + ds_write of tile kt+1   -> barrier
       //   second half (MFMAs of K step 1): global loads of tile kt+2, then ds_reads of step 0 of tile kt+1
       bf16x8 af0[MI][PL], bf0[NI][PL], af1[MI][PL], bf1[NI][PL];
-      constexpr int N_TERM = PL * (PL + 1) / 2;
-      constexpr int N_MMA = MI * NI * N_TERM;                // MFMAs per 16-wide K step
+      constexpr int N_MMA = MI * NI * Terms::N;                // MFMAs per 16-wide K step
       constexpr int N_FRAG = (MI + NI) * PL;                 // ds_read_b128 per K step
       constexpr int E1 = 2 * A_F4 + B_PCS;                   // first-half store / refill steps
-      // fragment read order = order of first use by the MFMAs (plane PL-1 of A and plane 0 of B first)
+      // fragment read order = order of first use by the MFMAs: round q reads the planes term q of split_terms multiplies (plane
+      // PL-1 of A and plane 0 of B first).  A macro on purpose: as a constexpr function or table it moves the pipelined kernels'
+      // instructions (profiles/gemm_refactor_isa.txt)
 #define FRAG_ORDER(k) (((k) / (MI + NI)) == 0 ? (((k) % (MI + NI)) < MI ? ((k) % (MI + NI)) * PL + (PL - 1) : MI * PL + (((k) % (MI + NI)) - MI) * PL) \
                      : ((k) / (MI + NI)) == PL - 1 ? (((k) % (MI + NI)) < MI ? ((k) % (MI + NI)) * PL : MI * PL + (((k) % (MI + NI)) - MI) * PL + (PL - 1)) \
                      : (((k) % (MI + NI)) < MI ? ((k) % (MI + NI)) * PL + 1 : MI * PL + (((k) % (MI + NI)) - MI) * PL + 1))
-      // cross terms, smallest first: (pa, pb) with pa + pb descending
-      constexpr int TPA[6] = {PL == 3 ? 2 : 1, PL == 3 ? 1 : 0, 0, 1, 0, 0};
-      constexpr int TPB[6] = {0, 1, PL == 3 ? 2 : 0, 0, 1, 0};
       auto step_mma = [&](int m, const bf16x8 (&af)[MI][PL], const bf16x8 (&bf)[NI][PL]) {
         const int t = m / (MI * NI), ij = m % (MI * NI), i = ij / NI, j = ij % NI;
-        acc[i][j] = mfma_split<FMT>(af[i][TPA[t]], bf[j][TPB[t]], acc[i][j]);
+        acc[i][j] = mfma_split<FMT>(af[i][Terms::pa(t)], bf[j][Terms::pb(t)], acc[i][j]);
       };
       // Fragment k of a K step, in the order the MFMAs consume them (lowest planes last).
       auto step_read = [&](int k, int buf, int s, bf16x8 (&af)[MI][PL], bf16x8 (&bf)[NI][PL]) {
@@ -484,10 +470,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
       for (int i = 0; i < MI; ++i) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float v = acc[i][j][r] + bv;
-          if (g.act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (g.act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-          else if (g.act == ACT_DIST) v = fmaxf(2.f - 2.f * v, 0.f);
+          float v = apply_act(acc[i][j][r] + bv, g.act);
           ep[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * TN + j * 32 + (lane & 31)] = v;
         }
       }
@@ -549,7 +532,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
       }
       // write-through (sc1) stores: the fresh activations leave the XCD's L2 while the launch is still running instead of
       // being written back behind it (same-box A/B at cfg3: 9.72 -> 9.82 M descriptors/s, twice)
-      if (row < g.M) sk_store16(Y + (int64_t)row * g.ldy + gcol, v);
+      if (row < g.M) store16_write_through(Y + (int64_t)row * g.ldy + gcol, v);
     }
     return;
   }
@@ -563,10 +546,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (row < g.M) {
-          float v = acc[i][j][r] + bv;
-          if (g.act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (g.act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-          else if (g.act == ACT_DIST) v = fmaxf(2.f - 2.f * v, 0.f);
+          float v = apply_act(acc[i][j][r] + bv, g.act);
           if (g.R) v += g.R[(int64_t)row * g.ldr + col];
           Y[(int64_t)row * g.ldy + col] = v;
         }
@@ -619,7 +599,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
         for (int b = 0; b < NI; ++b)
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            sk_store16(slot + ((((a * NI + b) * 4 + q) * NT) + tid) * 4,
+            store16_write_through(slot + ((((a * NI + b) * 4 + q) * NT) + tid) * 4,
                        f32x4{acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]});
       sk_publish(sa.sk_flags + s_, sa.sk_epoch);
     } else {
@@ -656,53 +636,29 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(SplitGemmArgs 
   }
 }
 
-template <int BM, int BN, int WM, int WN, int PL, bool DB = true, int FMT = 0, int PFD = 1, bool PIPE = false>
-inline int gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t st) {
-  constexpr size_t lds_main = (size_t)(DB ? 2 : 1) * (BM + BN) * (PL * 64 + 16);
-  constexpr size_t lds_epi = (size_t)BM * BN * sizeof(float);    // every wave's TM x TN accumulator tile
-  constexpr bool epi_fits = lds_epi <= 160 * 1024;
-  constexpr size_t lds = (epi_fits && lds_epi > lds_main) ? lds_epi : lds_main;
-  SplitGemmArgs sa2 = sa;
+#undef FRAG_ORDER
+
+// LDS a BM x BN tile asks for: the operand buffers, or every wave's accumulator tile for the LDS epilogue where that fits
+template <int BM, int BN, int PL, bool DB>
+struct SplitTileLds {
+  static constexpr size_t main = (size_t)(DB ? 2 : 1) * (BM + BN) * (PL * 64 + 16);
+  static constexpr size_t epi = (size_t)BM * BN * sizeof(float);
+  static constexpr bool epi_fits = epi <= 160 * 1024;
+  static constexpr size_t bytes = (epi_fits && epi > main) ? epi : main;
   // the LDS epilogue needs 16-byte aligned rows (ldy / ldr multiples of 4 floats; the entry points guarantee it for
   // their own buffers, debug_gemm checks it)
-  sa2.wide_epi = sa.g.ldy % 4 == 0 && (!sa.g.R || sa.g.ldr % 4 == 0) && epi_fits;
-  LT_HIP((allow_dynamic_lds<gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>>((int)lds)));
-  dim3 grid((sa.g.N / BN) * cdiv(sa.g.M, BM), groups);
+  static bool wide_epi(const GemmArgs& g) { return g.ldy % 4 == 0 && (!g.R || g.ldr % 4 == 0) && epi_fits; }
+};
+
+template <int BM, int BN, int WM, int WN, int PL, bool DB = true, int FMT = 0, int PFD = 1, bool PIPE = false>
+inline int gemm_split_launch_t(const SplitGemmArgs& sa, int groups, hipStream_t st) {
+  using Lds = SplitTileLds<BM, BN, PL, DB>;
+  SplitGemmArgs sa2 = sa;
+  sa2.wide_epi = Lds::wide_epi(sa.g);
   sa2.sk_first = sa2.sk_blocks = 0;
-#ifdef LINETR_EXPERIMENTS
-  if constexpr (PIPE && BM == 128 && BN == 256) {
-    // stream-K tail: when the last round of tiles would leave a good part of the chip idle, those tiles are shared by one
-    // block per CU instead (see the kernel).  Measured quantisation: 25472 x 512 x 512 (398 tiles) took as long as
-    // 32768 x 512 x 512 (512 tiles), 104 us.
-    // OFF by default (LINETR_STREAMK=1 turns it on, read per launch so that the tests can exercise it): the stream-K
-    // kernel is correct and deterministic (tests/test_gpu_gemm.py) but as built it LOSES -- 25472x512x512 110 us vs 92 us,
-    // 25472x768x256 114 us vs 82 us -- because the segment loop's extra state spills 60 VGPRs and 70 SGPRs next to the
-    // 256-register pipelined main loop, which slows the data-parallel tiles of the same launch as well.  Kept as the
-    // starting point for a leaner version.
-    const bool no_sk = LT_XENV("LINETR_STREAMK") == nullptr;
-    static int n_cu = 0;
-    if (!n_cu) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    const int T = (int)grid.x, nkw = sa.g.K / 32;
-    const int full = T / n_cu * n_cu, rem = T - full;
-    const int idle_ok = full > 0 ? n_cu * 13 / 16 : n_cu * 11 / 16;    // only when >= 3/16 (5/16 for a single round) of the CUs would idle
-    if (!no_sk && sa.sk_ws && groups == 1 && sa2.wide_epi && rem > 0 && rem <= idle_ok && (int64_t)rem * nkw >= 2 * n_cu &&
-        n_cu <= 256 && nkw <= 4096) {
-      sa2.sk_first = full;
-      sa2.sk_blocks = n_cu;
-      grid.x = full + n_cu;
-      // the stream-K kernel is its own instantiation with one register set of prefetch (PFD = 1): with two, the segment
-      // loop's extra state spilled 116 VGPRs
-      LT_HIP((allow_dynamic_lds<gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, 1, PIPE, true>>((int)lds)));
-      hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, 1, PIPE, true>), grid, dim3(WM * WN * 64), lds, st, sa2);
-      return 0;
-    }
-  }
-#endif
-  hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>), grid, dim3(WM * WN * 64), lds, st, sa2);
+  LT_HIP((allow_dynamic_lds<gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>>((int)Lds::bytes)));
+  dim3 grid((sa.g.N / BN) * cdiv(sa.g.M, BM), groups);
+  hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, PL, DB, FMT, PFD, PIPE>), grid, dim3(WM * WN * 64), Lds::bytes, st, sa2);
   return 0;
 }
 

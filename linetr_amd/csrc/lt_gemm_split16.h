@@ -33,7 +33,7 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(SplitGemmArgs sa) {
   constexpr int RS = PL * 64 + 16;                     // LDS row stride in bytes (as in lt_gemm_split.h)
   constexpr int A_F4 = 2;                              // float4 per thread per A tile; the 2nd pass covers rows 64..111
   constexpr int B_PCS = BN * PL * 4 / NT;              // 16-byte pieces per thread per W tile (6 / 4)
-  constexpr int NTERM = PL * (PL + 1) / 2;
+  constexpr int NTERM = split_terms<PL>::N;
   constexpr int SPR = NI * NTERM;                      // MFMA slots per row tile
   constexpr int N_SLOT = MI * SPR;
   constexpr int N_ST = A_F4 + B_PCS;                   // store / refill units per tile
@@ -45,11 +45,7 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(SplitGemmArgs sa) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int gx = g.N / BN, gy = (g.M + BM - 1) / BM;
   const int ntile = gx * gy;
-  int tile;
-  {  // XCD-aware order, as in gemm_split_kernel
-    const int b = blockIdx.x, q = ntile / 8, r = ntile % 8, xcd = b % 8, k = b / 8;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = xcd_tile(blockIdx.x, ntile);
   const int m0 = (tile / gx) * BM, n0 = (tile % gx) * BN;
   const float* A = g.A;
   const float* A2 = g.A2;
@@ -108,9 +104,7 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(SplitGemmArgs sa) {
   auto read_b = [&](int buf, int j, int p) -> bf16x8 {
     return *reinterpret_cast<const bf16x8*>(Bs + (buf * BN + wave * 32 + 16 * j + frow) * RS + p * 64 + fk);
   };
-  // cross terms, smallest first: (pa, pb) with pa + pb descending
-  constexpr int TPA[6] = {PL == 3 ? 2 : 1, PL == 3 ? 1 : 0, 0, 1, 0, 0};
-  constexpr int TPB[6] = {0, 1, PL == 3 ? 2 : 0, 0, 1, 0};
+  using Terms = split_terms<PL>;
 
   // prologue: tile 0 -> LDS, tile 1 -> registers, first fragments
 #pragma unroll
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(SplitGemmArgs sa) {
       int i, t, j;
       if (m < 6 * SPR) { const int w = m % (2 * SPR), rest = w / 2; i = 2 * (m / (2 * SPR)) + (w & 1); t = rest / NI; j = rest % NI; }
       else { const int w = m - 6 * SPR; i = 6; t = w / NI; j = w % NI; }
-      acc[i][j] = mfma16_split<FMT>(af[i][TPA[t]], bcur[j][TPB[t]], acc[i][j]);
+      acc[i][j] = mfma16_split<FMT>(af[i][Terms::pa(t)], bcur[j][Terms::pb(t)], acc[i][j]);
       if (m < BAR_SLOT) {
         // A fragments of row tile r (2..6): plane p at slot SPR (r - 2) + p * (SPR / PL)
 #pragma unroll
@@ -197,10 +191,7 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(SplitGemmArgs sa) {
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + 16 * i + 4 * (lane >> 4) + r;
         if (row < g.M) {
-          float v = acc[i][j][r] + bv;
-          if (g.act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (g.act == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-          else if (g.act == ACT_DIST) v = fmaxf(2.f - 2.f * v, 0.f);
+          float v = apply_act(acc[i][j][r] + bv, g.act);
           if (g.R) v += g.R[(int64_t)row * g.ldr + col];
           Y[(int64_t)row * g.ldy + col] = v;
         }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(WsGemmArgs a) {
   int zfrag[4];                                            // lfrag with the token slot rotated by 2 (2 kt + k half): four variants
 #pragma unroll
   for (int c = 0; c < 4; ++c) zfrag[c] = ((lane >> 4) & 1) * ST_RB + (lane >> 5) * 256 + (((lane & 15) + 2 * (lane >> 5) + 4 * c) & 15) * 16;
-  constexpr int TW[6] = {2, 1, 0, 1, 0, 0}, TA[6] = {0, 1, 2, 0, 1, 0};     // smallest cross terms first
+  using Terms = split_terms<3>;                            // the weights are the MFMA's A operand
   const int step = gridDim.x;
   // One tile = 96 MFMA slots in a fixed order (sched_barrier after each): the 48 of tokens 0..31 (acc0), then the 48 of tokens
   // 32..63 (acc1).  Everything else rides in the slots: the B fragments of the next K step (3 reads at the head of each K step),
@@ -170,8 +170,8 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(WsGemmArgs a) {
     for (int m = 0; m < 96; ++m) {
       const int g = m / 6, t = m % 6, kt = g & 7;
       if (m == 48) init_acc(acc1);
-      if (g < 8) acc0 = mfma_split<0>(wreg[kt][TW[t]], z[g % 3][TA[t]], acc0);
-      else acc1 = mfma_split<0>(wreg[kt][TW[t]], z[g % 3][TA[t]], acc1);
+      if (g < 8) acc0 = mfma_split<0>(wreg[kt][Terms::pa(t)], z[g % 3][Terms::pb(t)], acc0);
+      else acc1 = mfma_split<0>(wreg[kt][Terms::pa(t)], z[g % 3][Terms::pb(t)], acc1);
       if (t < 3 && g + 2 < 16) read_z1(g + 2, t);   // into the set group g - 1 has just left
       if (m >= 2 && m < 13) epi_step(acc1, prev_tile, 1, m - 2);
       if (m >= 30 && m < 42) split_step(m - 30, (it & 1) ^ 1);
@@ -196,15 +196,9 @@ inline int gemm_ws_launch(const WsGemmArgs& a, hipStream_t st) {
   if (!a.A || !a.Wst || !a.bias || !a.Y || a.lda % 4 || a.ldy % 4)
     return fail(LINETR_E_ARG, "gemm_ws: unsupported operands M=%d", a.M);
   LT_HIP(allow_dynamic_lds<gemm_ws_kernel>(WS_LDS));
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
   const int ntiles = cdiv(a.M, WS_TM);
   // two blocks per CU in sequence: measured 4-6 % faster than one (the second block's weight prologue hides under the first one's tail)
-  hipLaunchKernelGGL(gemm_ws_kernel, dim3(std::min(ntiles, 2 * n_cu)), dim3(512), WS_LDS, st, a);
+  hipLaunchKernelGGL(gemm_ws_kernel, dim3(std::min(ntiles, 2 * cu_count())), dim3(512), WS_LDS, st, a);
   LT_LAUNCH_CHECK();
   return 0;
 }

@@ -81,7 +81,7 @@ struct LinetrHandle {
   } pipe;
   float* zeros = nullptr;   // 4096 zero floats: the "no bias" vector of the split-tile GEMM (experiments/csrc/lt_gemm_st.h)
   float* w2p_arena = nullptr;   // experiments build: every SigLayer::W2p, one allocation (experiments/csrc/lt_x_net.h)
-  // stream-K workspace of the 128x256 GEMM (partial accumulator tiles + flags, one slot per CU; lt_gemm_split.h)
+  // stream-K workspace of the 128x256 GEMM (partial accumulator tiles + flags, one slot per CU; experiments/csrc/lt_gemm_sk.h)
   float* sk_ws = nullptr;
   unsigned* sk_flags = nullptr;
   unsigned sk_epoch = 0;

@@ -83,8 +83,7 @@ __device__ __forceinline__ void line_feat(const float* __restrict__ sublines, co
   const float ex = (sl[2] - cx) / scale, ey = (sl[3] - cy) / scale;
   in[0] = (sx + ex) / 2.f; in[1] = (sy + ey) / 2.f; in[2] = resp[row]; in[3] = angle[row * 2]; in[4] = angle[row * 2 + 1];
 }
-// K index served by register r of an accumulator tile in lane half h (see above)
-__device__ __forceinline__ constexpr int cd_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// (the K index served by register r of an accumulator tile in lane half h is cd_row(r, h), lt_gemm.h; see above)
 
 template <bool WORD>
 __global__ __launch_bounds__(256) void mlp123_kernel(const float* __restrict__ p0, const float* __restrict__ p1,

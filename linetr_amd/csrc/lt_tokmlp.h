@@ -97,7 +97,7 @@ __device__ __forceinline__ void tok_mlp_body(const TokMlpArgs& a, const int bloc
   load_feat(tile);
   __syncthreads();
 
-  constexpr int TW[6] = {2, 1, 0, 1, 0, 0}, TA[6] = {0, 1, 2, 0, 1, 0};     // smallest cross terms first
+  using Terms = split_terms<3>;                            // the weights are the MFMA's A operand
   auto init_acc = [&](f32x16& acc, const float* bias32) {  // register 4 b + c of a tile is channel 8 b + 4 h2 + c of its 32
 #pragma unroll
     for (int bq = 0; bq < 4; ++bq) {
@@ -195,7 +195,7 @@ __device__ __forceinline__ void tok_mlp_body(const TokMlpArgs& a, const int bloc
           zf[p] = *reinterpret_cast<const bf16x8*>(tk_smem + TK_A1 + (kt * TK_TB + 2 * th) * ST_RB + lfrag + p * ST_CHUNK);
         }
 #pragma unroll
-        for (int t = 0; t < 6; ++t) acc0 = mfma_split<0>(wf[TW[t]], zf[TA[t]], acc0);
+        for (int t = 0; t < 6; ++t) acc0 = mfma_split<0>(wf[Terms::pa(t)], zf[Terms::pb(t)], acc0);
       }
       tile_to_image(acc0, TK_A2, 32 * cg, 32 * th + lq);
     }
@@ -220,7 +220,7 @@ __device__ __forceinline__ void tok_mlp_body(const TokMlpArgs& a, const int bloc
           }
         }
 #pragma unroll
-        for (int t = 0; t < 6; ++t) acc0 = mfma_split<0>(wf[kt & 1][TW[t]], zf[kt & 1][TA[t]], acc0);
+        for (int t = 0; t < 6; ++t) acc0 = mfma_split<0>(wf[kt & 1][Terms::pa(t)], zf[kt & 1][Terms::pb(t)], acc0);
       }
       tile_to_image(acc0, TK_A3, 32 * cg, 32 * th + lq);
     }
@@ -239,8 +239,8 @@ __device__ __forceinline__ void tok_mlp_body(const TokMlpArgs& a, const int bloc
       for (int m = 0; m < 96; ++m) {
         const int g = m / 6, t = m % 6, kt = g & 7;
         if (m == 48) init_acc(acc1, prm + 448 + 32 * wave);
-        if (g < 8) acc0 = mfma_split<0>(wreg[kt][TW[t]], z[g % 3][TA[t]], acc0);
-        else acc1 = mfma_split<0>(wreg[kt][TW[t]], z[g % 3][TA[t]], acc1);
+        if (g < 8) acc0 = mfma_split<0>(wreg[kt][Terms::pa(t)], z[g % 3][Terms::pb(t)], acc0);
+        else acc1 = mfma_split<0>(wreg[kt][Terms::pa(t)], z[g % 3][Terms::pb(t)], acc1);
         if (t < 3 && g + 2 < 16) read_z1(g + 2, t);
         if (m >= 2 && m < 12) a_step(m - 2);               // layer 1 of the NEXT tile into A1 (B of this tile has left it)
         if (m >= 50 && m < 61) epi_step(acc0, tile, 0, m - 50);
@@ -269,14 +269,8 @@ inline int tok_mlp_launch(const TokMlpArgs& a, bool word, hipStream_t st) {
     return fail(LINETR_E_ARG, "tok_mlp: missing operand");
   LT_HIP(allow_dynamic_lds<tok_mlp_kernel<true>>(TK_LDS));
   LT_HIP(allow_dynamic_lds<tok_mlp_kernel<false>>(TK_LDS));
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
   const int64_t ntiles = (a.rows + TK_TM - 1) / TK_TM;
-  const dim3 grid((unsigned)std::min<int64_t>(ntiles, n_cu));
+  const dim3 grid((unsigned)std::min<int64_t>(ntiles, cu_count()));
   if (word) hipLaunchKernelGGL(tok_mlp_kernel<true>, grid, dim3(512), TK_LDS, st, a);
   else hipLaunchKernelGGL(tok_mlp_kernel<false>, grid, dim3(512), TK_LDS, st, a);
   LT_LAUNCH_CHECK();
@@ -293,13 +287,7 @@ __global__ __launch_bounds__(512) void tok_mlp_seq_kernel(TokMlpArgs aw, TokMlpA
 
 // both encoders side by side: only when their blocks (one per 64-row tile) fit the chip together
 inline bool tok_mlp_dual_fits(int64_t rows_word, int64_t rows_line) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  return rows_word > 0 && rows_line > 0 && (rows_word + TK_TM - 1) / TK_TM + (rows_line + TK_TM - 1) / TK_TM <= n_cu;
+  return rows_word > 0 && rows_line > 0 && (rows_word + TK_TM - 1) / TK_TM + (rows_line + TK_TM - 1) / TK_TM <= cu_count();
 }
 // one launch for both encoders: side by side when the blocks fit the chip, otherwise one after the other inside every block
 inline int tok_mlp_launch_dual(const TokMlpArgs& aw, const TokMlpArgs& al, hipStream_t st) {
@@ -311,11 +299,7 @@ inline int tok_mlp_launch_dual(const TokMlpArgs& aw, const TokMlpArgs& al, hipSt
   if (tok_mlp_dual_fits(aw.rows, al.rows)) {
     hipLaunchKernelGGL(tok_mlp_dual_kernel, dim3((unsigned)(tw + tl)), dim3(512), TK_LDS, st, aw, al, (int)tw);
   } else {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    static int n_cu = 0;
-    if (!n_cu) n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    hipLaunchKernelGGL(tok_mlp_seq_kernel, dim3((unsigned)std::min<int64_t>(std::max(tw, tl), n_cu)), dim3(512), TK_LDS, st, aw, al);
+    hipLaunchKernelGGL(tok_mlp_seq_kernel, dim3((unsigned)std::min<int64_t>(std::max(tw, tl), cu_count())), dim3(512), TK_LDS, st, aw, al);
   }
   LT_LAUNCH_CHECK();
   return 0;
