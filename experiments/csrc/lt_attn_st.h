@@ -1,6 +1,6 @@
 // Signature attention (models/line_transformer.py:132-154) on split-tile operands (lt_gemm_st.h): q / k / v arrive as the
 // ST image the projection GEMM wrote ([N][768], three bf16 planes), the message leaves as an ST image ([N][256]).
-// Same mathematics and the same six-product MFMA scheme as sig_attn_split_kernel (lt_model.h); what changes is the
+// Same mathematics and the same six-product MFMA scheme as sig_attn_split_kernel (lt_attn.h); what changes is the
 // data path:
 //   * Q fragments are 12 plain 16-byte loads per lane (the planes exist already: no split VALU);
 //   * K and V tiles travel HBM/L2 -> LDS by LDS-DMA (global_load_lds_dwordx4): K as linear copies of ST chunks (the chunk
@@ -13,7 +13,7 @@
 // block are masked like the rows past the end.
 #pragma once
 #include "lt_gemm_st.h"
-#include "lt_model.h"
+#include "lt_attn_parts.h"
 
 namespace lt {
 
@@ -25,18 +25,7 @@ constexpr int ATQ_V_BYTES = 3 * ATQ_KT * 128;    // [3 planes][64 kv][8 d-pieces
 // lane's row / piece / swizzle and the d block.  out[p][0/1]: plane p, kv run KV0 + {0..3} / KV0 + 8 + {0..3} (+ 4 h2).
 template <int KV0>
 __device__ __forceinline__ void v_frags_st(unsigned base, u32x2 (&o)[3][2]) {
-  constexpr int R0 = KV0 * 128, R1 = (KV0 + 8) * 128, PB = ATQ_KT * 128;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %6 offset:%7\n\t"
-      "ds_read_b64_tr_b16 %1, %6 offset:%8\n\t"
-      "ds_read_b64_tr_b16 %2, %6 offset:%9\n\t"
-      "ds_read_b64_tr_b16 %3, %6 offset:%10\n\t"
-      "ds_read_b64_tr_b16 %4, %6 offset:%11\n\t"
-      "ds_read_b64_tr_b16 %5, %6 offset:%12\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0][0]), "=&v"(o[0][1]), "=&v"(o[1][0]), "=&v"(o[1][1]), "=&v"(o[2][0]), "=&v"(o[2][1])
-      : "v"(base), "n"(R0), "n"(R1), "n"(R0 + PB), "n"(R1 + PB), "n"(R0 + 2 * PB), "n"(R1 + 2 * PB)
-      : "memory");
+  tr_reads<KV0 * 128, (KV0 + 8) * 128, ATQ_KT * 128, true>(base, o);
 }
 
 // grid (image, head, 256-query tile), 512 threads: wave w owns 32 queries.  OCC = blocks per CU the register budget is cut
@@ -127,13 +116,7 @@ __global__ __launch_bounds__(512, OCC == 2 ? 4 : 2) void sig_attn_st_kernel(cons
         bf16x8 ka[3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) ka[p] = *reinterpret_cast<const bf16x8*>(kfrag + ((s * 4 + 2 * c) * 3 + p) * ST_CHUNK);
-        // six products, smallest first: (2,0) (1,1) (0,2) (1,0) (0,1) (0,0)
-        st = mfma_split<0>(ka[2], qf[s][0], st);
-        st = mfma_split<0>(ka[1], qf[s][1], st);
-        st = mfma_split<0>(ka[0], qf[s][2], st);
-        st = mfma_split<0>(ka[1], qf[s][0], st);
-        st = mfma_split<0>(ka[0], qf[s][1], st);
-        st = mfma_split<0>(ka[0], qf[s][0], st);
+        mma6(ka, qf[s], st);
       }
       if (kvg < n0 || kvg + 32 > n0 + Ni) {   // wave-uniform: rows of a neighbouring image / past the end
 #pragma unroll
@@ -187,13 +170,7 @@ __global__ __launch_bounds__(512, OCC == 2 ? 4 : 2) void sig_attn_st_kernel(cons
             x.u[0] = vr[p][0][0]; x.u[1] = vr[p][0][1]; x.u[2] = vr[p][1][0]; x.u[3] = vr[p][1][1];
             va[p] = x.v;
           }
-          f32x16& o = dt == 0 ? o0 : o1;
-          o = mfma_split<0>(va[2], pp[0], o);
-          o = mfma_split<0>(va[1], pp[1], o);
-          o = mfma_split<0>(va[0], pp[2], o);
-          o = mfma_split<0>(va[1], pp[0], o);
-          o = mfma_split<0>(va[0], pp[1], o);
-          o = mfma_split<0>(va[0], pp[0], o);
+          mma6(va, pp, dt == 0 ? o0 : o1);
         }
       }
     }

@@ -18,13 +18,14 @@
 // before the next call and retires this path for the handle).
 //
 // Arithmetic = the per-launch kernels': gemm_split_small_kernel<3, 0, 8> (lt_gemm_small.h: 32 x 32 tile, the 8 waves split K,
-// wave-private staging, partial sums added in wave order) and sig_attn_small_kernel (lt_model.h: 32 queries, 4 waves split the
+// wave-private staging, partial sums added in wave order) and sig_attn_small_kernel (lt_attn.h: 32 queries, 4 waves split the
 // keys, merged through LDS).  Row tiles are per IMAGE (an image's last tile is partial), so a tile never straddles two
 // softmax domains.
 #pragma once
 #include "lt_gemm_split.h"
 #include "lt_gemm_split16.h"
 #include "lt_gemm_small.h"
+#include "lt_attn_parts.h"
 
 namespace lt {
 
@@ -432,12 +433,7 @@ __device__ __noinline__ bool pn_attn_unit(const PnStage& st, int n0, int Ni, int
         u.w[0] = a[p]; u.w[1] = b[p]; u.w[2] = c[p]; u.w[3] = d[p];
         ka[p] = u.v;
       }
-      sc = mfma_split<0>(ka[2], qf[s][0], sc);
-      sc = mfma_split<0>(ka[1], qf[s][1], sc);
-      sc = mfma_split<0>(ka[0], qf[s][2], sc);
-      sc = mfma_split<0>(ka[1], qf[s][0], sc);
-      sc = mfma_split<0>(ka[0], qf[s][1], sc);
-      sc = mfma_split<0>(ka[0], qf[s][0], sc);
+      mma6(ka, qf[s], sc);
     }
     if (stamp && tid == 0) stamp[5] = wall_clock64() + (long long)(sc[0] == 12345.f);   // scores done
     const int kv_here = kv0;
@@ -464,17 +460,7 @@ __device__ __noinline__ bool pn_attn_unit(const PnStage& st, int n0, int Ni, int
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       bf16x8 pp[3];
-      {
-        unsigned w[4][3];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) split_pair<3>(sc[8 * t + 2 * e], sc[8 * t + 2 * e + 1], w[e]);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-          union { bf16x8 v; unsigned u[4]; } x;
-          x.u[0] = w[0][p]; x.u[1] = w[1][p]; x.u[2] = w[2][p]; x.u[3] = w[3][p];
-          pp[p] = x.v;
-        }
-      }
+      split_p(sc, t, pp);
       const unsigned char* vp = Vt + lq * PN_ATL_RV + (16 * t + 4 * h2) * 2;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
@@ -487,13 +473,7 @@ __device__ __noinline__ bool pn_attn_unit(const PnStage& st, int n0, int Ni, int
           x.u[0] = lo[0]; x.u[1] = lo[1]; x.u[2] = hi[0]; x.u[3] = hi[1];
           va[p] = x.v;
         }
-        f32x16& o = dt == 0 ? o0 : o1;
-        o = mfma_split<0>(va[2], pp[0], o);
-        o = mfma_split<0>(va[1], pp[1], o);
-        o = mfma_split<0>(va[0], pp[2], o);
-        o = mfma_split<0>(va[1], pp[0], o);
-        o = mfma_split<0>(va[0], pp[1], o);
-        o = mfma_split<0>(va[0], pp[0], o);
+        mma6(va, pp, dt == 0 ? o0 : o1);
       }
     }
     __builtin_amdgcn_wave_barrier();

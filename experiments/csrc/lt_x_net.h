@@ -1,5 +1,5 @@
 // Experiments build only (liblinetr_hip_experiments.so): everything the experiments add to the forward pass.  linetr_net.hip
-// includes this file textually, behind sig_network: lt_st_image.h and lt_model.h define non-template kernels, so a second
+// includes this file textually, behind sig_network: lt_st_image.h, lt_model.h and lt_attn.h define non-template kernels, so a second
 // translation unit would duplicate their host stubs, and the code here uses that file's local helpers (run_gemm, NormSpec,
 // FwdWs, TokenStage, sentence, sig_attention, pipe_boundary).  The hooks linetr_net.hip calls:
 //   x_gemm           run_gemm: the stream-K tail (LINETR_STREAMK) and the row-owner GEMM (LINETR_GEMM_RO) take the launch

@@ -13,6 +13,7 @@
 #include "lt_st_image.h"
 #include "lt_gemm_small.h"
 #include "lt_model.h"
+#include "lt_attn.h"
 #include "lt_attn_fused.h"
 #include "lt_gemm_ws.h"
 #include "lt_tokmlp.h"

@@ -14,12 +14,12 @@
 //      register pair gives 8 consecutive channels, which IS the B-operand layout of S^T = K Q^T for Q (stays in VGPRs)
 //      and a 16-byte row piece of the K / V images of sig_attn_split_kernel for K and V (written to LDS in two halves of
 //      128 keys; the weight ring is dead by then).
-//   3. attention exactly as sig_attn_split_kernel (lt_model.h): S^T by split-bf16 MFMA, in-lane softmax, P^T from the
+//   3. attention exactly as sig_attn_split_kernel (lt_attn.h): S^T by split-bf16 MFMA, in-lane softmax, P^T from the
 //      accumulator registers, V^T fragments by transposing LDS reads; the message leaves as fp32 rows.
 // q, k, v never reach HBM; one launch per layer instead of two.  Images of up to 256 sub-lines (eight waves).
 #pragma once
 #include "lt_st_image.h"
-#include "lt_model.h"
+#include "lt_attn.h"
 
 namespace lt {
 
@@ -27,26 +27,6 @@ constexpr int FQA_W_BYTES = 3 * 4 * ST_RB;              // 18 432 B: (q | k | v)
 constexpr int FQA_SLOT = FQA_W_BYTES + 256 * 64;        // + 256 rows x 16 fp32 of activations = 34 816 B
 constexpr int FQA_KEYS = 128;                           // keys per LDS half
 constexpr int FQA_LDS = 4 * FQA_SLOT;                   // 139 264 B; the K / V half images (124 928 B) alias the dead ring
-
-// The six transposing reads of v_frags_tr (lt_model.h) WITHOUT the wait: issued a (t, d block) ahead of their MFMAs.  hipcc does
-// not count an asm load, so the consumer side is fr_wait: one lgkmcnt(0) that names every destination (cdna_hip_programming.md 5.7).
-template <int KV0, int DT>
-__device__ __forceinline__ void fr_issue(unsigned base, u32x2 (&o)[3][2]) {
-  constexpr int R0 = KV0 * ATS_RV + DT * 64, R1 = (KV0 + 8) * ATS_RV + DT * 64;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %6 offset:%7\n\t"
-      "ds_read_b64_tr_b16 %1, %6 offset:%8\n\t"
-      "ds_read_b64_tr_b16 %2, %6 offset:%9\n\t"
-      "ds_read_b64_tr_b16 %3, %6 offset:%10\n\t"
-      "ds_read_b64_tr_b16 %4, %6 offset:%11\n\t"
-      "ds_read_b64_tr_b16 %5, %6 offset:%12"
-      : "=&v"(o[0][0]), "=&v"(o[0][1]), "=&v"(o[1][0]), "=&v"(o[1][1]), "=&v"(o[2][0]), "=&v"(o[2][1])
-      : "v"(base), "n"(R0), "n"(R1), "n"(R0 + 128), "n"(R1 + 128), "n"(R0 + 256), "n"(R1 + 256)
-      : "memory");
-}
-__device__ __forceinline__ void fr_wait(u32x2 (&o)[3][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o[0][0]), "+v"(o[0][1]), "+v"(o[1][0]), "+v"(o[1][1]), "+v"(o[2][0]), "+v"(o[2][1]) : : "memory");
-}
 
 __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restrict__ z /*[N][256]*/,
                                                            const unsigned char* __restrict__ Wst /*ST image of Wqkv [768][256]*/,
@@ -200,7 +180,9 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
 #pragma unroll
     for (int c = 0; c < 4; ++c) { halves_swap(v[c], v[4 + c]); halves_swap(v[8 + c], v[12 + c]); }
   };
-  auto split8 = [&](const float* x, bf16x8 (&o)[3]) {
+  // (split_z and split_run are split8 of lt_attn_parts.h, written out twice: through the free function, in either place, this
+  // kernel's instructions move -- profiles/attn_refactor_isa.txt)
+  auto split_run = [&](const float* x, bf16x8 (&o)[3]) {
     unsigned a[3], b[3], c[3], d[3];
     split_pair<3>(x[0], x[1], a); split_pair<3>(x[2], x[3], b);
     split_pair<3>(x[4], x[5], c); split_pair<3>(x[6], x[7], d);
@@ -216,8 +198,8 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
   for (int i = 0; i < 2; ++i) {
     float v[16];
     pieces(acc[i], LOG2E, v);                              // scores in log2 units: exp -> v_exp_f32 (q is pre-scaled by 1/8)
-    split8(v, qf[2 * i]);
-    split8(v + 8, qf[2 * i + 1]);
+    split_run(v, qf[2 * i]);
+    split_run(v + 8, qf[2 * i + 1]);
   }
   unsigned char* Ks = fq_smem;                             // [128][ATS_RK]
   unsigned char* Vs = fq_smem + FQA_KEYS * ATS_RK;         // [128][ATS_RV]
@@ -231,7 +213,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
         bf16x8 pl[3];
-        split8(v + 8 * g, pl);
+        split_run(v + 8 * g, pl);
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(dst + p * 128 + g * 32) = pl[p];
       }
@@ -249,7 +231,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
     const unsigned vb = v_base + KB * ATS_RV;
     // V^T fragments of (t = 0, d block 0) are on their way before the scores are even computed
     u32x2 vrA[3][2], vrB[3][2];
-    fr_issue<KL - KB, 0>(vb, vrA);
+    v_frags_tr<KL - KB, 0, false>(vb, vrA);
     f32x16 st;
 #pragma unroll
     for (int r = 0; r < 16; ++r) st[r] = 0.f;
@@ -295,7 +277,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
       float sv[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) sv[e] = st[e];
-      split8(sv, pp0);
+      split_run(sv, pp0);
     }
     auto pv = [&](u32x2 (&vr)[3][2], const bf16x8 (&pp)[3], f32x16& o) {
       bf16x8 va[3];
@@ -305,32 +287,27 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
         x.u[0] = vr[p][0][0]; x.u[1] = vr[p][0][1]; x.u[2] = vr[p][1][0]; x.u[3] = vr[p][1][1];
         va[p] = x.v;
       }
-      o = mfma_split<0>(va[2], pp[0], o);
-      o = mfma_split<0>(va[1], pp[1], o);
-      o = mfma_split<0>(va[0], pp[2], o);
-      o = mfma_split<0>(va[1], pp[0], o);
-      o = mfma_split<0>(va[0], pp[1], o);
-      o = mfma_split<0>(va[0], pp[0], o);
+      mma6(va, pp, o);
     };
-    fr_wait(vrA);
-    fr_issue<KL - KB, 1>(vb, vrB);
+    tr_wait(vrA);
+    v_frags_tr<KL - KB, 1, false>(vb, vrB);
     pv(vrA, pp0, o0);
     __builtin_amdgcn_sched_barrier(0);
     {
       float sv[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) sv[e] = st[8 + e];
-      split8(sv, pp1);
+      split_run(sv, pp1);
     }
-    fr_wait(vrB);
-    fr_issue<KL - KB + 16, 0>(vb, vrA);
+    tr_wait(vrB);
+    v_frags_tr<KL - KB + 16, 0, false>(vb, vrA);
     pv(vrB, pp0, o1);
     __builtin_amdgcn_sched_barrier(0);
-    fr_wait(vrA);
-    fr_issue<KL - KB + 16, 1>(vb, vrB);
+    tr_wait(vrA);
+    v_frags_tr<KL - KB + 16, 1, false>(vb, vrB);
     pv(vrA, pp1, o0);
     __builtin_amdgcn_sched_barrier(0);
-    fr_wait(vrB);
+    tr_wait(vrB);
     pv(vrB, pp1, o1);
   };
 #pragma unroll

@@ -9,20 +9,33 @@ import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def compile_asm(root=ROOT, experiments=False):
+    """Device assembly of every translation unit of the tree at `root`, as {stem: text}: the product (linetr_amd/csrc/linetr_*.hip),
+    or the experiments build (-DLINETR_EXPERIMENTS, experiments/csrc/linetr_*.hip as well).  tools/kernel_isa_diff.py compares two trees with it."""
+    csrc, xsrc = os.path.join(root, "linetr_amd", "csrc"), os.path.join(root, "experiments", "csrc")
+    srcs = sorted(glob.glob(os.path.join(csrc, "linetr_*.hip")) + (glob.glob(os.path.join(xsrc, "linetr_*.hip")) if experiments else []))
+    defs = ["-DLINETR_EXPERIMENTS", "-I" + xsrc, "-I" + csrc] if experiments else []
+
+    def one(src):
+        stem = os.path.splitext(os.path.basename(src))[0]
+        with tempfile.TemporaryDirectory() as tmp:
+            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Wno-unused-function",
+                            "-I" + os.path.join(root, "include"), *defs, "-save-temps", "-o", stem + ".o", src],
+                           cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            return stem, open(os.path.join(tmp, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+
+    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as ex:
+        return dict(ex.map(one, srcs))
+
+
 def main():
     filters = sys.argv[1:]
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = ""
-        for src in sorted(glob.glob(os.path.join(ROOT, "linetr_amd", "csrc", "linetr_*.hip"))):
-            stem = os.path.splitext(os.path.basename(src))[0]
-            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
-                            "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-save-temps", "-o", stem + ".o", src],
-                           cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            asm += open(os.path.join(tmp, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    asm = "".join(compile_asm().values())
     items = re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", asm, flags=re.S)
     names, rows = [], []
     for it in items:
