@@ -347,6 +347,40 @@ int linetr_pair_tail(LinetrHandle* h, const float* d_pdesc0_cn, int32_t np0, con
                      const int32_t* d_sub2line1, int32_t k1, float nn_thresh_lines, int32_t mutual, void* h_pinned_out,
                      int64_t pinned_bytes, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- validation step (section 8(f) "next" row 4: loss forward + evaluation) ------------------------- */
+
+/* What the reference's `val` epoch computes after the batched forward (train.py:198-240), on the device and forward only:
+ *   evaluations/criteria.py:59-124,173-192   descriptor_loss: D = 2 - 2 <d0, d1> (no clip); 2n anchor rows per item (the n rows of D, then
+ *       the n rows of D^T); pos = max(0, max of D over the row's entries with assign > 0.3), an anchor where pos > 0; neg = the smallest D
+ *       among the row's entries with assign <= 0 that has pos < D < pos + 0.5 (both strict, pos + 0.5 in float32; every other entry counts
+ *       as 10000); an anchor without one is dropped; loss = mean over the V anchors left of relu(pos - neg + 1), hardest_positive = max
+ *       pos, hardest_negative = min neg.  V == 0 is no error here: loss and both hardest values are NaN, the count 0.
+ *   evaluations/matcher.py:51-102            nn_matcher_batches: score = max((|d0|^2 + |d1|^2) - 2 <d0, d1>, 0) in float32 with the norms
+ *       recomputed, first-index row argmin, score < nn_thresh (strict, compared in float64), optional mutual check against the
+ *       first-index column argmin: match01 [B][n], -1 = no match.
+ *   evaluations/evaluate_pr.py:10-35         per item TP, FP, FN, TN (ground truth assign > 0) and precision, recall, f1 in float64.
+ * Both formulas read ONE set of dot products (exact-fp32 MFMA); every reduction has a fixed order.  Three launches and one copy.
+ *   d_desc0 / d_desc1  [B*n][256] row-major as linetr_forward* writes them: item b owns rows b*n .. b*n + n - 1
+ *   d_assign           [B][n+1][n+1] float32, the reference's target['mat_assign_sublines'] (dustbin row / column not read)
+ *   d_row_pos / d_row_neg  [B][2n] float32 or NULL: pos of every anchor row; neg, or -1 where the row is no anchor or was dropped.
+ *       row_pos is max(0, .): where every column of a row is a match the reference's amax can be slightly negative (n = 1 with
+ *       rounding); such a row is no anchor either way, but this array holds 0 there, never a negative value
+ *   d_match01          [B][n] int32 or NULL
+ *   h_pinned_out       PINNED host block of linetr_val_step_output_bytes(B, h_offsets) bytes, filled by one asynchronous copy:
+ *       h_offsets[0] float64 [3] loss, hardest_positive, hardest_negative   [1] int64 [1] V
+ *       h_offsets[2] int32 [B][4] TP, FP, FN, TN                            [3] float64 [B][3] precision, recall, f1
+ * Asynchronous on `stream`; `h` may be NULL.  n0 != n1 (the criterion concatenates D and D^T), B <= 0, n <= 0, a NULL required pointer,
+ * an output block or a workspace smaller than the two functions below say: LINETR_E_ARG, nothing launched. */
+int64_t linetr_val_step_workspace_bytes(int32_t B, int32_t n);
+int64_t linetr_val_step_output_bytes(int32_t B, int64_t* h_offsets);
+int linetr_val_step(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign, int32_t B,
+                    double nn_thresh, int32_t mutual, float* d_row_pos, float* d_row_neg, int32_t* d_match01, void* h_pinned_out,
+                    int64_t pinned_bytes, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* train.py:176-183: d_assign [B][n+1][n+1] float32 = 0, then 1 at (d_lmatches[b][m][0], d_lmatches[b][m][1]) for every row m of the
+ * loader's int32 [B][M][2] match list whose first entry is not -1 (an index outside 0..n is skipped).  B, n as above, M >= 0 and B * M <= 2^31 * 256, else LINETR_E_ARG.  Asynchronous; `h` may be NULL. */
+int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmatches, int32_t B, int32_t M, int32_t n, float* d_assign, void* stream);
+
 /* ---- dense-map producer (section 8(f) "next" row 2) ------------------------------------------------- */
 
 /* Post-processing of SuperPoint's two heads, fused with the layout change the tokeniser needs; replaces

@@ -1,10 +1,12 @@
 // liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
-// multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), and SuperPoint's key-point branch (lt_keypoints.h).
+// multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), SuperPoint's key-point branch (lt_keypoints.h) and the
+// validation step (lt_valstep.h).
 #include <algorithm>
 #include <numeric>
 
 #include "lt_handle.h"
 #include "lt_match.h"
+#include "lt_valstep.h"
 #include "lt_producer.h"
 #include "lt_keypoints.h"
 
@@ -617,6 +619,122 @@ extern "C" int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense
     ProfScope ps(h, st, "sp_kp_topk", 0, (double)B * cap_per_image * 8);
     hipLaunchKernelGGL(sp_kp_topk_kernel, dim3((unsigned)B), dim3(512), 0, st, (const unsigned long long*)keys, (const int*)d_found,
                        (const int*)d_cu_kp, cap_per_image, max_keypoints, W, d_keypoints, d_scores);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// validation step (lt_valstep.h)
+// =============================================================================================
+
+namespace {
+constexpr int VS_MAX_N = 32768;   // n^2 dot products per item are indexed in 64 bits; the grids stay far inside their limits
+constexpr int VS_MAX_B = 65535;   // grid.z / grid.y
+struct ValOutLayout { int64_t o_scalars, o_count, o_counts, o_scores, total; };
+ValOutLayout val_out_layout(int B) {
+  ValOutLayout L{};
+  int64_t o = 0;
+  L.o_scalars = o; o += 256;
+  L.o_count = o; o += 256;
+  L.o_counts = o; o += align_up((int64_t)B * 4 * 4, 256);
+  L.o_scores = o; o += align_up((int64_t)B * 3 * 8, 256);
+  L.total = o;
+  return L;
+}
+// workspace: device image of the result block | dots | norms | per-row results | argmins | match01
+struct ValWsLayout { int64_t o_out, o_dots, o_sq0, o_sq1, o_pos, o_neg, o_rarg, o_rmin, o_carg, o_gt, o_m01, total; };
+ValWsLayout val_ws_layout(int B, int n) {
+  ValWsLayout L{};
+  const int64_t rows = align_up((int64_t)B * n * 4, 256);
+  int64_t o = 0;
+  L.o_out = o; o += val_out_layout(B).total;
+  L.o_dots = o; o += align_up((int64_t)B * n * n * 4, 256);
+  L.o_sq0 = o; o += rows;
+  L.o_sq1 = o; o += rows;
+  L.o_pos = o; o += 2 * rows;
+  L.o_neg = o; o += 2 * rows;
+  L.o_rarg = o; o += rows;
+  L.o_rmin = o; o += rows;
+  L.o_carg = o; o += rows;
+  L.o_gt = o; o += rows;
+  L.o_m01 = o; o += rows;
+  L.total = o + 256;
+  return L;
+}
+bool val_dims_ok(int B, int n) { return B > 0 && B <= VS_MAX_B && n > 0 && n <= VS_MAX_N; }
+}  // namespace
+
+extern "C" int64_t linetr_val_step_workspace_bytes(int32_t B, int32_t n) {
+  return val_dims_ok(B, n) ? val_ws_layout(B, n).total : 0;
+}
+
+extern "C" int64_t linetr_val_step_output_bytes(int32_t B, int64_t* h_offsets) {
+  const ValOutLayout L = val_out_layout(std::min(std::max(B, 0), VS_MAX_B));
+  if (h_offsets) { h_offsets[0] = L.o_scalars; h_offsets[1] = L.o_count; h_offsets[2] = L.o_counts; h_offsets[3] = L.o_scores; }
+  return L.total;
+}
+
+extern "C" int linetr_val_step(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign,
+                               int32_t B, double nn_thresh, int32_t mutual, float* d_row_pos, float* d_row_neg, int32_t* d_match01,
+                               void* h_pinned_out, int64_t pinned_bytes, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  if (n0 != n1) return fail(LINETR_E_ARG, "val_step: %d and %d sub-lines (the criterion stacks D on D^T: one n for both sides)", n0, n1);
+  const int n = n0;
+  if (!val_dims_ok(B, n)) return fail(LINETR_E_ARG, "val_step: bad shape B=%d n=%d (B 1..%d, n 1..%d)", B, n, VS_MAX_B, VS_MAX_N);
+  if (!d_desc0 || !d_desc1 || !d_assign || !h_pinned_out || !d_ws) return fail(LINETR_E_ARG, "val_step: null pointer");
+  const ValOutLayout O = val_out_layout(B);
+  const ValWsLayout W = val_ws_layout(B, n);
+  if (pinned_bytes < O.total) return fail(LINETR_E_ARG, "val_step: output block too small (need %lld)", (long long)O.total);
+  if (ws_bytes < W.total) return fail(LINETR_E_ARG, "val_step: workspace too small (need %lld)", (long long)W.total);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  char* base = (char*)d_ws;
+  float* dots = (float*)(base + W.o_dots);
+  float* sq0 = (float*)(base + W.o_sq0);
+  float* sq1 = (float*)(base + W.o_sq1);
+  float* row_pos = d_row_pos ? d_row_pos : (float*)(base + W.o_pos);
+  float* row_neg = d_row_neg ? d_row_neg : (float*)(base + W.o_neg);
+  int* row_arg = (int*)(base + W.o_rarg);
+  float* row_min = (float*)(base + W.o_rmin);
+  int* col_arg = (int*)(base + W.o_carg);
+  int* row_gt = (int*)(base + W.o_gt);
+  int* match01 = d_match01 ? d_match01 : (int*)(base + W.o_m01);
+  char* dout = base + W.o_out;
+  const ValOut out{(double*)(dout + O.o_scalars), (long long*)(dout + O.o_count), (int*)(dout + O.o_counts), (double*)(dout + O.o_scores)};
+  const int tiles = cdiv(n, 64);
+  {
+    ProfScope ps(h, st, "val_dot", 2.0 * B * n * n * D, 4.0 * B * (2.0 * n * D + (double)n * n));
+    hipLaunchKernelGGL(val_dot_kernel, dim3(tiles, tiles, B), dim3(256), 0, st, d_desc0, d_desc1, n, dots, sq0, sq1);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "val_select", 0, 16.0 * B * n * n);
+    hipLaunchKernelGGL(val_select_kernel, dim3(cdiv(n, VS_ROWS) + cdiv(n, VS_COLS), B), dim3(256), 0, st, (const float*)dots, (const float*)sq0,
+                       (const float*)sq1, d_assign, n, row_pos, row_neg, row_arg, row_min, col_arg, row_gt);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "val_final", 0, 44.0 * B * n);
+    hipLaunchKernelGGL(val_final_kernel, dim3(B + 1), dim3(256), 0, st, (const float*)row_pos, (const float*)row_neg, (const int*)row_arg,
+                       (const float*)row_min, (const int*)col_arg, (const int*)row_gt, d_assign, B, n, nn_thresh, mutual, match01, out);
+    LT_LAUNCH_CHECK();
+  }
+  LT_HIP(hipMemcpyAsync(h_pinned_out, dout, (size_t)O.total, hipMemcpyDeviceToHost, st));
+  return LINETR_OK;
+}
+
+extern "C" int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmatches, int32_t B, int32_t M, int32_t n, float* d_assign,
+                                          void* stream) {
+  // (B * M pairs, one thread each: the grid's x extent bounds M)
+  if (!val_dims_ok(B, n) || M < 0 || ((int64_t)B * M + 255) / 256 > INT32_MAX)
+    return fail(LINETR_E_ARG, "assign_from_matches: bad shape B=%d M=%d n=%d", B, M, n);
+  if (!d_assign || (M > 0 && !d_lmatches)) return fail(LINETR_E_ARG, "assign_from_matches: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  LT_HIP(hipMemsetAsync(d_assign, 0, (size_t)B * (n + 1) * (n + 1) * 4, st));
+  if (M > 0) {
+    hipLaunchKernelGGL(val_assign_kernel, dim3((unsigned)(((int64_t)B * M + 255) / 256)), dim3(256), 0, st, d_lmatches, B, M, n, d_assign);
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;

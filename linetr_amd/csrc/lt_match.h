@@ -36,21 +36,17 @@ inline size_t pair_pool_lds(int max_k1, int seg1_global, int cache_dk) {
   return (size_t)((seg1_global ? 0 : max_k1 + 1) + PM_ROWS + 2 + (cache_dk ? PM_ROWS * max_k1 : 0)) * sizeof(int);
 }
 
-// D[a][b] = max(2 - 2 * <d0[a], d1[b]>, 0), fp32 MFMA, 64x64 tile per block, K = 256.
-// grid (tiles_b, tiles_a, pair)
-__global__ __launch_bounds__(256) void pair_dist_kernel(const PairTable pairs,
-                                                        const float* __restrict__ desc0,
-                                                        const float* __restrict__ desc1, float* __restrict__ dist) {
-  constexpr int LS = 36;
-  __shared__ __attribute__((aligned(16))) float As[64 * LS];
-  __shared__ __attribute__((aligned(16))) float Bs[64 * LS];
-  const PairDesc pd = pairs.get(blockIdx.z);
-  const int a0 = blockIdx.y * 64, b0 = blockIdx.x * 64;
-  if (a0 >= pd.n0 || b0 >= pd.n1) return;
+// One 64 x 64 tile of dot products <A[a0 + .], B[b0 + .]> over K = 256 by exact-fp32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf
+// chain, no split) for a block of 4 waves: wave (wa, wb) owns the 32 x 32 quarter at (32 wa, 32 wb).  As / Bs: [64 * DOT_LS] floats of
+// LDS each.  Rows beyond n0 / n1 are read as the last row (their results are the caller's to drop).  Element r of the result is
+// row dot_tile_row(r, lane), column lane & 31 of the quarter.
+constexpr int DOT_LS = 36;
+__device__ __forceinline__ int dot_tile_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+__device__ __forceinline__ f32x16 dot_tile_64x64(const float* __restrict__ A, int n0, int a0, const float* __restrict__ B, int n1, int b0,
+                                                 float* As, float* Bs) {
+  constexpr int LS = DOT_LS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wa = wave >> 1, wb = wave & 1;
-  const float* A = desc0 + pd.off_n0 * D;
-  const float* B = desc1 + pd.off_n1 * D;
   const int lrow = tid >> 3, lc4 = (tid & 7) * 4;
   f32x16 acc;
 #pragma unroll
@@ -59,8 +55,8 @@ __global__ __launch_bounds__(256) void pair_dist_kernel(const PairTable pairs,
   int ra[2], rb[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    ra[i] = a0 + lrow + i * 32; ra[i] = ra[i] < pd.n0 ? ra[i] : pd.n0 - 1;
-    rb[i] = b0 + lrow + i * 32; rb[i] = rb[i] < pd.n1 ? rb[i] : pd.n1 - 1;
+    ra[i] = a0 + lrow + i * 32; ra[i] = ra[i] < n0 ? ra[i] : n0 - 1;
+    rb[i] = b0 + lrow + i * 32; rb[i] = rb[i] < n1 ? rb[i] : n1 - 1;
   }
   f32x4 va[2], vb[2];
   auto fetch = [&](int k0) {
@@ -90,11 +86,27 @@ __global__ __launch_bounds__(256) void pair_dist_kernel(const PairTable pairs,
       for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s], acc, 0, 0, 0);
     }
   }
+  return acc;
+}
+
+// D[a][b] = max(2 - 2 * <d0[a], d1[b]>, 0), 64x64 tile per block.
+// grid (tiles_b, tiles_a, pair)
+__global__ __launch_bounds__(256) void pair_dist_kernel(const PairTable pairs,
+                                                        const float* __restrict__ desc0,
+                                                        const float* __restrict__ desc1, float* __restrict__ dist) {
+  __shared__ __attribute__((aligned(16))) float As[64 * DOT_LS];
+  __shared__ __attribute__((aligned(16))) float Bs[64 * DOT_LS];
+  const PairDesc pd = pairs.get(blockIdx.z);
+  const int a0 = blockIdx.y * 64, b0 = blockIdx.x * 64;
+  if (a0 >= pd.n0 || b0 >= pd.n1) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wa = wave >> 1, wb = wave & 1;
+  const f32x16 acc = dot_tile_64x64(desc0 + pd.off_n0 * D, pd.n0, a0, desc1 + pd.off_n1 * D, pd.n1, b0, As, Bs);
   float* Dp = dist + pd.off_d;
   const int col = b0 + wb * 32 + (lane & 31);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = a0 + wa * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int row = a0 + wa * 32 + dot_tile_row(r, lane);
     if (row < pd.n0 && col < pd.n1) Dp[(int64_t)row * pd.n1 + col] = fmaxf(2.f - 2.f * acc[r], 0.f);
   }
 }

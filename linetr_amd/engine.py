@@ -778,6 +778,76 @@ class Engine:
         return (f(offs[0], np0 * np1, np.float32).reshape(np0, np1), f(offs[1], np0, np.int32),
                 f(offs[2], k0 * k1, np.float32).reshape(k0, k1), f(offs[3], k0, np.int32))
 
+    def _desc_rows(self, desc: torch.Tensor):
+        """Line descriptors as linetr_val_step reads them: ([B*n, 256] contiguous float32, B or None, n).  Accepts the reference's
+        [B, 256, n] (contiguous, or the transposed view of [B*n, 256] rows that this build's forward returns: no copy then) or the
+        rows themselves."""
+        if desc.dim() == 3:
+            if int(desc.shape[1]) != D:
+                raise ValueError(f"line descriptors must be [B, {D}, n], got {tuple(desc.shape)}")
+            B, n = int(desc.shape[0]), int(desc.shape[2])
+            return self._f32(desc.transpose(1, 2)).view(B * n, D), B, n
+        if desc.dim() != 2 or int(desc.shape[1]) != D:
+            raise ValueError(f"line descriptors must be [B, {D}, n] or [B*n, {D}], got {tuple(desc.shape)}")
+        return self._f32(desc), None, None
+
+    def assign_from_matches(self, lmatches: torch.Tensor, n: int) -> torch.Tensor:
+        """train.py:176-183 on the device (linetr_assign_from_matches): the loader's lmatches [B, M, 2] (rows whose first entry is -1
+        are padding) -> mat_assign_sublines [B, n+1, n+1] float32."""
+        lm = lmatches.to(device=self.device, dtype=torch.int32).contiguous()
+        B, M = int(lm.shape[0]), int(lm.shape[1])
+        assign = torch.empty((B, n + 1, n + 1), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_assign_from_matches(self._h, lm.data_ptr(), B, M, int(n), assign.data_ptr(), self._stream()), self._L)
+        return assign
+
+    def val_step(self, desc0, desc1, assign=None, lmatches=None, nn_thresh=0.7, mutual=True):
+        """The reference's validation step after the forward, in one native call (linetr_val_step): descriptor_loss
+        (evaluations/criteria.py), nn_matcher_batches (evaluations/matcher.py) and the precision / recall / F1 of
+        evaluations/evaluate_pr.py.  desc0 / desc1: [B, 256, n] or [B*n, 256] (then `assign` / `lmatches` gives B); the ground truth is
+        either `assign` [B, n+1, n+1] (mat_assign_sublines) or the loader's `lmatches` [B, M, 2].  One host wait.  Returns a dict:
+        loss, hardest_positive, hardest_negative (float; NaN when count == 0), count, TP / FP / FN / TN (int32 [B]), precision /
+        recall / f1 (float64 [B]) and the device tensors row_pos, row_neg [B, 2n] (row_neg -1: no anchor, or no semi-hard negative)
+        and match01 [B, n]."""
+        if (assign is None) == (lmatches is None):
+            raise ValueError("val_step: give exactly one of assign / lmatches")
+        d0, B0, n0 = self._desc_rows(desc0)
+        d1, B1, n1 = self._desc_rows(desc1)
+        B = int((assign if assign is not None else lmatches).shape[0])
+        if B <= 0 or any(b is not None and b != B for b in (B0, B1)) or d0.shape[0] % B or d1.shape[0] % B:
+            raise ValueError("val_step: the descriptors and the ground truth disagree about the batch size")
+        n0, n1 = int(d0.shape[0]) // B, int(d1.shape[0]) // B
+        n = n0
+        if assign is None:
+            assign = self.assign_from_matches(lmatches, n)
+        else:
+            assign = self._f32(assign)
+            if n0 == n1 and tuple(assign.shape) != (B, n + 1, n + 1):
+                raise ValueError(f"val_step: assign must be [{B}, {n + 1}, {n + 1}], got {tuple(assign.shape)}")
+        offs = (C.c_int64 * 4)()
+        out_bytes = int(self._L.linetr_val_step_output_bytes(B, offs))
+        ws = self._workspace("val_step", max(int(self._L.linetr_val_step_workspace_bytes(B, n)), 256))
+        stage, *_gen = self._host_stage(out_bytes)
+        row_pos = torch.empty((B, 2 * n), dtype=torch.float32, device=self.device)
+        row_neg = torch.empty((B, 2 * n), dtype=torch.float32, device=self.device)
+        match01 = torch.empty((B, n), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_val_step(self._h, d0.data_ptr(), n0, d1.data_ptr(), n1, assign.data_ptr(), B, float(nn_thresh),
+                                              int(bool(mutual)), row_pos.data_ptr(), row_neg.data_ptr(), match01.data_ptr(),
+                                              stage.data_ptr(), stage.numel(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        ev.synchronize()
+        host = stage.numpy()
+        scalars = host[offs[0]:offs[0] + 24].view(np.float64)
+        counts = host[offs[2]:offs[2] + 16 * B].view(np.int32).reshape(B, 4).copy()
+        scores = host[offs[3]:offs[3] + 24 * B].view(np.float64).reshape(B, 3).copy()
+        return {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
+                "count": int(host[offs[1]:offs[1] + 8].view(np.int64)[0]),
+                "TP": counts[:, 0], "FP": counts[:, 1], "FN": counts[:, 2], "TN": counts[:, 3],
+                "precision": scores[:, 0], "recall": scores[:, 1], "f1": scores[:, 2],
+                "row_pos": row_pos, "row_neg": row_neg, "match01": match01}
+
     def match_points(self, desc0_cn: torch.Tensor, desc1_cn: torch.Tensor, thr, mutual=True):
         """nn_matcher on [256,n] descriptors; returns (dist [n0,n1] device, match01 [n0] device)."""
         d0, d1 = self._f32(desc0_cn), self._f32(desc1_cn)
