@@ -18,6 +18,8 @@
  * streams of batches:  linetr_describe_submit / linetr_describe_join (the same call as a software pipeline over consecutive batches).
  * ABI version 5 (r06): + linetr_describe_submit, linetr_describe_join, linetr_pipeline_max_slots.
  * ABI version 6: + linetr_debug_sig_attention (one chosen signature-attention kernel alone, for the unit tests).
+ *                + linetr_debug_gemm_case (one chosen GEMM tile alone on a full problem description, for the unit tests): an added
+ *                diagnostics symbol, nothing existing changes, so the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -460,6 +462,44 @@ int linetr_debug_posenc(LinetrHandle* h, int32_t which, const float* d_in0, cons
 int linetr_debug_gemm(LinetrHandle* h, const float* d_A, int32_t lda, const float* d_W, const float* d_bias,
                       const float* d_residual, float* d_Y, int32_t ldy, int32_t M, int32_t N, int32_t K,
                       int32_t act, int32_t cache_weights, void* stream);
+
+/* Runs ONE kernel of the GEMM family on everything the forward pass can ask of it, for the unit tests
+ * (tests/test_gpu_gemm_tiles.py: every tile against float64 at its tile edges):
+ *     Y_g[M,N] = norm( act([A_g | A2_g] W_g^T + bias_g) (+ R) ) (+ add2),   g = 0 .. groups - 1
+ * A [M][K1] (K1 = K without A2) and A2 [M][K - K1] with row strides lda / lda2; W [groups * N][K] and bias [groups * N] (or
+ * NULL) contiguous; R (or NULL) and Y with row stride ldy.  Group g reads A + g gA and A2 + g gA and writes Y + g gY (gA = 0: all
+ * groups share A); a grouped launch takes no R and no norm.  act as in linetr_debug_gemm.  norm: 0 none, 1 LayerNorm(x) gamma +
+ * beta with eps inside the sqrt, 2 x / max(||x||_2, 1e-12), applied after bias, activation and residual, then + add2 (row stride
+ * 256, or NULL); needs N = ldy = 256.  The normalisation runs in the tile's epilogue, or -- via_row_norm != 0, or tile = -1 where
+ * the dispatcher's tile does not own whole rows -- the product goes to a scratch buffer and row_norm_kernel writes Y.
+ * tile: -1 = what the forward pass takes for this problem at the handle's precision (the choice is made by the same host function
+ *       the forward pass calls.  Two differences: the experiments library's own launch hooks -- stream-K, the row-owner GEMM --
+ *       are not consulted here, and a 128 -> 256 weight always gets a split-tile image here, while in the forward pass only
+ *       the weights created with one can take the weight-stationary kernel); LINETR_GEMM_TILE_WS = the weight-stationary kernel; otherwise an index into the tile names,
+ *       split modes: 0 32x32k4, 1 112x256, 2 128x64, 3 256x128, 4 128x256, 5 64x256, 6 128x128, 7 128x128s, 8 256x256, 9 64x64,
+ *                    10 64x128;          f32 mode: 0 128x64, 1 128x128, 2 64x128.
+ * *tile_used (may be NULL) receives the kernel that launches, after the launchers' own fallback rules: N % 128 != 0 takes 128x64,
+ * a 256-wide tile on N % 256 != 0 takes 64x128, and so does 256x256 (built in the experiments library's two-plane modes only).
+ * Refused with LINETR_E_ARG, nothing launched: a normalisation asked of the epilogue of anything but 128x256 with N = 256; the
+ * weight-stationary kernel for anything but act(A[M,128] W[256,128]^T + bias), act none / ReLU, bf16x6, one group, no A2 / R / norm;
+ * 112x256 with groups; K1 not a multiple of 32; strides that are not multiples of 4 floats, misaligned (16 bytes) tensors.
+ * With A = W = Y = NULL only the choice (and any refusal) is reported and nothing is launched or dereferenced: A2 and R then only
+ * say whether the operand is there.  Per-call scratch (the split copies of W) is freed after synchronising `stream`. */
+#define LINETR_GEMM_TILE_WS 100
+typedef struct {
+  const float* A;   int32_t lda;
+  const float* A2;  int32_t lda2;  int32_t K1;
+  const float* W;
+  const float* bias;
+  const float* R;
+  float* Y;         int32_t ldy;
+  int32_t M, N, K, act;
+  int32_t groups;   int64_t gA, gY;
+  int32_t norm;     const float* gamma;  const float* beta;  const float* add2;  float eps;
+  int32_t via_row_norm;
+  int32_t tile;
+} LinetrGemmCase;
+int linetr_debug_gemm_case(LinetrHandle* h, const LinetrGemmCase* c, int32_t* tile_used, void* stream);
 
 /* Runs ONE signature-attention kernel (models/line_transformer.py:132-154 up to, not including, the merge conv) on a
  * var-len batch, for the unit tests (tests/test_gpu_attention.py: every kernel against a float64 reference).

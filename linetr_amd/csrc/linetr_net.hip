@@ -75,6 +75,8 @@ int gemm_args(const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, co
   const int groups = grp ? grp->n : 1, N = grp ? grp->N : w.rows;
   if (A.p2 && (A.K1 <= 0 || A.K1 >= w.K)) return fail(LINETR_E_ARG, "gemm: split point K1 = %d outside (0, K = %d)", A.K1, w.K);
   if ((int64_t)N * groups > w.rows) return fail(LINETR_E_ARG, "gemm: %d groups of %d rows exceed the weight's %d", groups, N, w.rows);
+  // the kernels step A, W, the bias and Y from group to group, nothing else
+  if (groups > 1 && (R || ns)) return fail(LINETR_E_ARG, "gemm: a grouped launch takes no residual and no row normalisation");
   g = GemmArgs{};
   g.A = A.p; g.lda = A.ld; g.A2 = A.p2; g.lda2 = A.ld2; g.K1 = A.K1;
   g.W = w.W; g.ldw = w.K; g.bias = w.b; g.R = R; g.ldr = Y.ld; g.Y = Y.p; g.ldy = Y.ld;
@@ -84,37 +86,66 @@ int gemm_args(const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, co
   return LINETR_OK;
 }
 
-// every token row of the batch through a K = 128 layer: weights stay in registers, rows stream (lt_gemm_ws.h)
-bool gemm_ws_takes(const LinetrHandle* h, const GemmArgs& g, const GemmW& w, int groups, const NormSpec* fused_norm) {
+// every token row of the batch through a K = 128 layer: weights stay in registers, rows stream (lt_gemm_ws.h).  What the kernel
+// can run (gemm_ws_able) and what the dispatcher gives it (gemm_ws_takes: token-count sizes)
+bool gemm_ws_able(const LinetrHandle* h, const GemmArgs& g, const GemmW& w, int groups, const NormSpec* fused_norm) {
   return h->precision == LINETR_PREC_BF16X6 && groups == 1 && !g.A2 && !g.R && !fused_norm && w.st &&
-         gemm_ws_fits(g.M, g.N, g.K, g.lda, g.ldy, g.act) && !LT_XENV("LINETR_NO_GEMM_WS");
+         gemm_ws_can(g.N, g.K, g.lda, g.ldy, g.act);
+}
+bool gemm_ws_takes(const LinetrHandle* h, const GemmArgs& g, const GemmW& w, int groups, const NormSpec* fused_norm) {
+  return gemm_ws_able(h, g, w, groups, fused_norm) && gemm_ws_fits(g.M, g.N, g.K, g.lda, g.ldy, g.act) && !LT_XENV("LINETR_NO_GEMM_WS");
 }
 
+// One kernel of the family chosen by hand (linetr_debug_gemm_case): `tile` -1 = the dispatcher's choice, LINETR_GEMM_TILE_WS = the
+// weight-stationary kernel, otherwise an F32Tile (f32 mode) / SplitTile index.  `used` receives what launches, after the
+// launchers' fallback rules; launch = false only reports it.
+struct GemmForce { int tile = -1; int* used = nullptr; bool launch = true; };
+
 int run_gemm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA& A, const GemmY& Y, int act, const float* R = nullptr,
-             const GemmGroups* grp = nullptr, const NormSpec* fused_norm = nullptr) {
+             const GemmGroups* grp = nullptr, const NormSpec* fused_norm = nullptr, const GemmForce* force = nullptr) {
   GemmArgs g;
   if (int e = gemm_args(w, M, A, Y, act, R, grp, fused_norm, g)) return e;
   const int groups = grp ? grp->n : 1;
+  const int forced = force ? force->tile : -1;
+  const bool launch = !force || force->launch;
+  auto report = [&](int tile) { if (force && force->used) *force->used = tile; };
   const double fl = 2.0 * M * (double)g.N * g.K * groups;
   const double by = 4.0 * groups * ((double)M * g.K + (double)g.N * g.K + (double)M * g.N);
   if (h->precision == LINETR_PREC_F32) {
-    ProfScope ps(h, st, gemm_class_name(LINETR_PREC_F32, (int)f32_tile(g, groups), g, groups), fl, by);
-    return gemm_launch(g, groups, st);
+    if (forced >= (int)F32Tile::count) return fail(LINETR_E_ARG, "gemm: the f32 mode has no tile %d", forced);
+    if (fused_norm) return fail(LINETR_E_ARG, "gemm: the f32 kernels have no fused row normalisation");
+    const F32Tile tile = f32_tile_launched(g, forced < 0 ? f32_tile(g, groups) : (F32Tile)forced);
+    report((int)tile);
+    if (!launch) return LINETR_OK;
+    ProfScope ps(h, st, gemm_class_name(LINETR_PREC_F32, (int)tile, g, groups), fl, by);
+    return gemm_launch(g, groups, tile, st);
   }
   SplitGemmArgs sa;
   sa.g = g;
 #ifdef LINETR_EXPERIMENTS
-  bool done = false;   // done: the stream-K or the row-owner GEMM took the launch
-  if (int e = x_gemm(h, st, sa, w, groups, fused_norm, fl, by, done); e || done) return e;
+  if (!force) {
+    bool done = false;   // done: the stream-K or the row-owner GEMM took the launch
+    if (int e = x_gemm(h, st, sa, w, groups, fused_norm, fl, by, done); e || done) return e;
+  }
 #endif
-  if (gemm_ws_takes(h, g, w, groups, fused_norm)) {
+  if (forced == LINETR_GEMM_TILE_WS && !gemm_ws_able(h, g, w, groups, fused_norm))
+    return fail(LINETR_E_ARG, "gemm: the weight-stationary kernel runs act(A[M,128] W[256,128]^T + b) in bf16x6 only, act none / ReLU");
+  if (forced == LINETR_GEMM_TILE_WS || (forced < 0 && gemm_ws_takes(h, g, w, groups, fused_norm))) {
+    report(LINETR_GEMM_TILE_WS);
+    if (!launch) return LINETR_OK;
     WsGemmArgs a;
     a.A = A.p; a.lda = A.ld; a.Wst = w.st; a.bias = w.b ? w.b : h->zeros; a.Y = Y.p; a.ldy = Y.ld; a.M = M; a.act = act;
     ProfScope ps(h, st, "gemm_bf16x6_ws64x256", fl, by);
     return gemm_ws_launch(a, st);
   }
+  const int pl = h->precision == LINETR_PREC_BF16X6 ? 3 : 2;
   SplitTile tile;
-  if (int e = pick_split_tile(g, groups, h->precision == LINETR_PREC_BF16X6 ? 3 : 2, tile)) return e;
+  if (forced >= (int)SplitTile::count) return fail(LINETR_E_ARG, "gemm: no split tile %d", forced);
+  if (forced >= 0) tile = (SplitTile)forced;
+  else if (int e = pick_split_tile(g, groups, pl, tile)) return e;
+  if (int e = split_tile_launched(g, groups, pl, tile)) return e;
+  report((int)tile);
+  if (!launch) return LINETR_OK;
   ProfScope ps(h, st, gemm_class_name(h->precision, (int)tile, g, groups), fl, by);
   switch (h->precision) {
     case LINETR_PREC_BF16X3: sa.Wsp = w.s2; sa.gWsp = g.gW * 4; return gemm_split_launch<2>(sa, groups, tile, st);
@@ -123,23 +154,31 @@ int run_gemm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA
   }
 }
 
+// does the dispatcher's tile for this [M,256] product normalise the rows in its epilogue?
+bool gemm_norm_fuses(const LinetrHandle* h, const GemmW& w, int M, const GemmA& A, const float* R, float* Y) {
+  GemmArgs g;   // (LINETR_NO_FUSED_NORM: a tuning / test aid, read per call)
+  return !LT_XENV("LINETR_NO_FUSED_NORM") && h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_GEMM_TILE") &&
+         !gemm_args(w, M, A, {Y, D}, ACT_NONE, R, nullptr, nullptr, g) &&
+         split_tile(g, 1, h->precision == LINETR_PREC_BF16X6 ? 3 : 2) == SplitTile::t128x256;
+}
+
+int row_norm(LinetrHandle* h, hipStream_t st, const float* x, int M, const NormSpec& ns, float* Y) {
+  ProfScope ps(h, st, "row_norm", 0, (double)M * D * (ns.add2 ? 12 : 8));
+  hipLaunchKernelGGL(row_norm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, x, M, ns.mode == 2 ? 1 : 0, ns.gamma, ns.beta,
+                     ns.add2, ns.eps, Y);
+  LT_LAUNCH_CHECK();
+  return 0;
+}
+
 // Y[M,256] = norm(epi(A W^T + bias) (+ R)) (+ add2), R and Y with row stride 256.  The split-bf16 128x256 tile owns complete rows
 // and normalises them in its epilogue (one launch and one [M,256] round trip less); every other case runs the GEMM into `tmp` and
 // then row_norm_kernel.  Same arithmetic either way.
 int run_gemm_norm(LinetrHandle* h, hipStream_t st, const GemmW& w, int M, const GemmA& A, const float* R, float* tmp, float* Y,
                   const NormSpec& ns) {
   if (w.rows != D) return fail(LINETR_E_ARG, "gemm_norm: the weight has %d rows, not %d", w.rows, D);
-  GemmArgs g;   // (LINETR_NO_FUSED_NORM: a tuning / test aid, read per call)
-  const bool fuse = !LT_XENV("LINETR_NO_FUSED_NORM") && h->precision != LINETR_PREC_F32 && !LT_XENV("LINETR_GEMM_TILE") &&
-                    !gemm_args(w, M, A, {Y, D}, ACT_NONE, R, nullptr, nullptr, g) &&
-                    split_tile(g, 1, h->precision == LINETR_PREC_BF16X6 ? 3 : 2) == SplitTile::t128x256;
-  if (fuse) return run_gemm(h, st, w, M, A, {Y, D}, ACT_NONE, R, nullptr, &ns);
+  if (gemm_norm_fuses(h, w, M, A, R, Y)) return run_gemm(h, st, w, M, A, {Y, D}, ACT_NONE, R, nullptr, &ns);
   if (int e = run_gemm(h, st, w, M, A, {tmp, D}, ACT_NONE, R)) return e;
-  ProfScope ps(h, st, "row_norm", 0, (double)M * D * (ns.add2 ? 12 : 8));
-  hipLaunchKernelGGL(row_norm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, tmp, M, ns.mode == 2 ? 1 : 0, ns.gamma, ns.beta,
-                     ns.add2, ns.eps, Y);
-  LT_LAUNCH_CHECK();
-  return 0;
+  return row_norm(h, st, tmp, M, ns, Y);
 }
 
 // Where one weight's split copies go in a buffer, from byte `off` on (advanced past them): the three split planes, then (with_st)
@@ -1056,6 +1095,76 @@ extern "C" int linetr_debug_gemm(LinetrHandle* h, const float* A, int32_t lda, c
     (void)hipStreamSynchronize(st);
     (void)hipFree(buf);
   }
+  return e;
+}
+
+extern "C" int linetr_debug_gemm_case(LinetrHandle* h, const LinetrGemmCase* c, int32_t* tile_used, void* stream) {
+  if (!h || !c) return fail(LINETR_E_ARG, "debug_gemm_case: null argument");
+  const bool query = !c->A && !c->W && !c->Y;     // nothing is dereferenced: A2 / R only say that the operand is there
+  const int M = c->M, N = c->N, K = c->K, groups = c->groups;
+  if (M < 0 || N <= 0 || K <= 0 || groups < 1) return fail(LINETR_E_ARG, "debug_gemm_case: bad shape M=%d N=%d K=%d groups=%d", M, N, K, groups);
+  if (K % 32 || N % 64) return fail(LINETR_E_ARG, "debug_gemm_case: N %% 64 == 0 and K %% 32 == 0 required");
+  if (c->lda % 4 || c->ldy % 4 || c->ldy < N || (c->A2 && (c->lda2 % 4 || c->lda2 < K - c->K1)) || c->lda < (c->A2 ? c->K1 : K))
+    return fail(LINETR_E_ARG, "debug_gemm_case: bad leading dimension");
+  if (c->A2 && (c->K1 <= 0 || c->K1 >= K || c->K1 % 32))
+    return fail(LINETR_E_ARG, "debug_gemm_case: the split point K1 = %d must be a multiple of 32 inside (0, K = %d)", c->K1, K);
+  if (c->gA % 4 || c->gY % 4 || c->gA < 0 || c->gY < 0) return fail(LINETR_E_ARG, "debug_gemm_case: group strides must be non-negative multiples of 4 floats");
+  if (c->act < ACT_NONE || c->act > ACT_DIST) return fail(LINETR_E_ARG, "debug_gemm_case: act must be 0 .. 3");
+  if (c->tile < -1 || (c->tile >= (int)SplitTile::count && c->tile != LINETR_GEMM_TILE_WS))
+    return fail(LINETR_E_ARG, "debug_gemm_case: no tile %d", c->tile);
+  NormSpec ns;
+  if (c->norm) {
+    if (c->norm != 1 && c->norm != 2) return fail(LINETR_E_ARG, "debug_gemm_case: norm must be 0, 1 (LayerNorm) or 2 (L2)");
+    if (N != D || c->ldy != D || groups != 1) return fail(LINETR_E_ARG, "debug_gemm_case: a row normalisation needs N = ldy = 256 and one group");
+    if (!query && c->norm == 1 && (!c->gamma || !c->beta)) return fail(LINETR_E_ARG, "debug_gemm_case: LayerNorm needs gamma and beta");
+    ns.mode = c->norm; ns.gamma = c->gamma; ns.beta = c->beta; ns.add2 = c->add2; ns.eps = c->eps;
+  } else if (c->via_row_norm) {
+    return fail(LINETR_E_ARG, "debug_gemm_case: via_row_norm without a norm");
+  }
+  if (!query) {
+    if (!c->A || !c->W || !c->Y) return fail(LINETR_E_ARG, "debug_gemm_case: null tensor");
+    uintptr_t al = (uintptr_t)c->A | (uintptr_t)c->A2 | (uintptr_t)c->W | (uintptr_t)c->bias | (uintptr_t)c->R | (uintptr_t)c->Y |
+                   (uintptr_t)c->gamma | (uintptr_t)c->beta | (uintptr_t)c->add2;
+    if (al % 16) return fail(LINETR_E_ARG, "debug_gemm_case: tensors must be 16-byte aligned");
+  }
+  const int64_t rows = (int64_t)N * groups;
+  const bool with_st = groups == 1 && N == WS_N && K == WS_K;
+  GemmW w;
+  w.W = c->W; w.b = c->bias; w.rows = (int)rows; w.K = K;
+  const GemmA A{c->A, c->lda, c->A2, c->lda2, c->A2 ? c->K1 : 0};
+  const GemmGroups grp{groups, N, c->gA, c->gY};
+  const GemmGroups* pg = groups > 1 ? &grp : nullptr;
+  GemmForce force;
+  force.tile = c->tile; force.used = tile_used; force.launch = false;
+  // a forced tile normalises in its epilogue or is refused; the dispatcher's choice falls back to row_norm_kernel as run_gemm_norm does
+  const bool fuse = c->norm && !c->via_row_norm && (c->tile >= 0 || gemm_norm_fuses(h, w, M, A, c->R, c->Y));
+  // first pass: the choice and every refusal, nothing launched
+  if (with_st) w.st = reinterpret_cast<const unsigned char*>(h);   // only its presence is read; split_copies makes the image below
+  if (int e = run_gemm(h, nullptr, w, M, A, {c->Y, c->ldy}, c->act, c->R, pg, fuse ? &ns : nullptr, &force)) return e;
+  if (query || M == 0) return LINETR_OK;
+  LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* buf = nullptr;   // this call's scratch: the split copies of W and, for row_norm_kernel, the un-normalised product
+  int64_t bytes = 0;
+  SplitOffsets at{};
+  if (h->precision != LINETR_PREC_F32) at = split_offsets(rows, K, with_st, bytes);
+  bytes = align_up(bytes, 256);
+  const int64_t tmp_at = bytes;
+  if (c->norm && !fuse) bytes += (int64_t)M * D * sizeof(float);
+  if (bytes > 0) LT_HIP(hipMalloc((void**)&buf, bytes));
+  if (h->precision != LINETR_PREC_F32) split_copies(w, buf, at, true, st);
+  int e = LINETR_OK;
+  if (hipGetLastError() != hipSuccess) e = fail(LINETR_E_HIP, "debug_gemm_case: splitting the weights failed");
+  force.launch = true;
+  if (!e && c->norm && !fuse) {
+    float* tmp = reinterpret_cast<float*>(buf + tmp_at);
+    e = run_gemm(h, st, w, M, A, {tmp, D}, c->act, c->R, nullptr, nullptr, &force);
+    if (!e) e = row_norm(h, st, tmp, M, ns, c->Y);
+  } else if (!e) {
+    e = run_gemm(h, st, w, M, A, {c->Y, c->ldy}, c->act, c->R, pg, fuse ? &ns : nullptr, &force);
+  }
+  (void)hipStreamSynchronize(st);
+  if (buf) (void)hipFree(buf);
   return e;
 }
 

@@ -222,13 +222,16 @@ inline F32Tile f32_tile(const GemmArgs& g, int groups) {
   return big_tiles >= 384 ? F32Tile::t128x128 : F32Tile::t64x128;
 }
 
+// The tile that launches when `tile` is asked for (f32_tile's choice or a forced one): N not a multiple of 128 takes 128x64.
+inline F32Tile f32_tile_launched(const GemmArgs& g, F32Tile tile) { return g.N % 128 != 0 ? F32Tile::t128x64 : tile; }
+
 // N must be a multiple of 64, K of 32.
-inline int gemm_launch(const GemmArgs& g, int groups, hipStream_t st) {
+inline int gemm_launch(const GemmArgs& g, int groups, F32Tile tile, hipStream_t st) {
   if (g.M <= 0) return 0;
   if (g.N % 64 != 0 || g.K % GEMM_BK != 0 || (g.A2 && g.K1 % GEMM_BK != 0))
     return fail(LINETR_E_ARG, "gemm: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
   int e;
-  switch (f32_tile(g, groups)) {
+  switch (f32_tile_launched(g, tile)) {
     case F32Tile::t128x64: e = gemm_launch_t<128, 64, 4, 1>(g, groups, st); break;
     case F32Tile::t128x128: e = gemm_launch_t<128, 128, 2, 2>(g, groups, st); break;
     default: e = gemm_launch_t<64, 128, 2, 2>(g, groups, st); break;

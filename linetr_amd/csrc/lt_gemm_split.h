@@ -716,24 +716,39 @@ inline int pick_split_tile(const GemmArgs& g, int groups, int pl, SplitTile& til
   return fail(LINETR_E_ARG, "LINETR_GEMM_TILE: no tile is named '%s'", forced);
 }
 
-// `tile` is pick_split_tile's choice (or a forced one: a tile the shape does not fit falls back as below)
-template <int PL, int FMT = 0>
-inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, SplitTile tile, hipStream_t st) {
-  const GemmArgs& g = sa.g;
-  if (g.M <= 0) return 0;
+// The tile that launches when `tile` is asked of a PL-plane GEMM (pick_split_tile's choice or a forced one), or what the family
+// refuses.  A tile the shape does not fit falls back: N not a multiple of 128 takes the 128x64 tile, a 256-wide tile that N does
+// not fit the 64x128 one, and so does 256x256 where it is not built (bf16x6, the product).
+inline int split_tile_launched(const GemmArgs& g, int groups, int pl, SplitTile& tile) {
   if (g.N % 64 != 0 || g.K % 32 != 0 || (g.A2 && g.K1 % 32 != 0))
     return fail(LINETR_E_ARG, "gemm_split: unsupported shape M=%d N=%d K=%d", g.M, g.N, g.K);
   // the launcher is authoritative about the fused row normalisation: only the 128x256 tile with the LDS epilogue owns
   // complete rows of an N = 256 problem; anything else would silently skip the normalisation
   if (g.norm != 0) {
-    if (tile != SplitTile::t128x256 || g.N != 256 || g.ldy % 4 != 0 || (g.R && g.ldr % 4 != 0))
+    if (tile != SplitTile::t128x256 || g.N != 256 || groups != 1 || g.ldy % 4 != 0 || (g.R && g.ldr % 4 != 0))
       return fail(LINETR_E_ARG, "gemm_split: fused row normalisation asked of tile %s (N=%d): dispatcher bug", tile_name(tile), g.N);
   }
-  // N not a multiple of 128 takes the 128x64 tile, a 256-wide tile that N does not fit the 64x128 one, and so does 256x256 in bf16x6
-  if (g.N % 128 != 0 && tile != SplitTile::t32x32k4 && tile != SplitTile::t112x256) tile = SplitTile::t128x64;
-  if (g.N % 256 != 0 && (tile == SplitTile::t128x256 || tile == SplitTile::t64x256 || tile == SplitTile::t256x256))
+  // the 112x256 kernel has no group dimension (split16_wins never picks it for a grouped launch)
+  if (tile == SplitTile::t112x256 && groups != 1)
+    return fail(LINETR_E_ARG, "gemm_split: tile 112x256 asked of a grouped launch (%d groups)", groups);
+  if (g.N % 128 != 0 && tile != SplitTile::t32x32k4) tile = SplitTile::t128x64;
+  if (g.N % 256 != 0 && (tile == SplitTile::t128x256 || tile == SplitTile::t64x256 || tile == SplitTile::t256x256 ||
+                         tile == SplitTile::t112x256))
     tile = SplitTile::t64x128;
-  if (PL != 2 && tile == SplitTile::t256x256) tile = SplitTile::t64x128;
+  bool has256 = pl == 2;
+#ifndef LINETR_EXPERIMENTS
+  has256 = false;
+#endif
+  if (!has256 && tile == SplitTile::t256x256) tile = SplitTile::t64x128;
+  return 0;
+}
+
+// `tile` is split_tile_launched's
+template <int PL, int FMT = 0>
+inline int gemm_split_launch(const SplitGemmArgs& sa, int groups, SplitTile tile, hipStream_t st) {
+  const GemmArgs& g = sa.g;
+  if (g.M <= 0) return 0;
+  if (int e = split_tile_launched(g, groups, PL, tile)) return e;
   int e = 0;
   switch (tile) {
     case SplitTile::t32x32k4: gemm_split_small_launch<PL, FMT>(sa, groups, st); break;

@@ -187,9 +187,12 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(WsGemmArgs a) {
   for (int e = 0; e < 11; ++e) epi_step(acc1, prev_tile, 1, e);
 }
 
-inline bool gemm_ws_fits(int M, int N, int K, int lda, int ldy, int act) {
-  return N == WS_N && K == WS_K && lda % 4 == 0 && ldy % 4 == 0 && (act == ACT_NONE || act == ACT_RELU) && M >= 16384;
+// what the kernel is written for (any M >= 1) ...
+inline bool gemm_ws_can(int N, int K, int lda, int ldy, int act) {
+  return N == WS_N && K == WS_K && lda % 4 == 0 && ldy % 4 == 0 && (act == ACT_NONE || act == ACT_RELU);
 }
+// ... and where the dispatcher gives it the launch: token-count sizes
+inline bool gemm_ws_fits(int M, int N, int K, int lda, int ldy, int act) { return gemm_ws_can(N, K, lda, ldy, act) && M >= 16384; }
 
 inline int gemm_ws_launch(const WsGemmArgs& a, hipStream_t st) {
   if (a.M <= 0) return 0;

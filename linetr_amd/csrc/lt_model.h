@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256, 3) void cls_pool_online_kernel(   // 3 = waves
 // ---------------------------------------------------------------------------------------------
 // Row kernels over [rows][256]; one wave64 per row, lane = 4 channels.
 //   mode 0: y = LayerNorm(x) * gamma + beta (+ add)      eps = 1e-6 (models/line_attention.py:40,83)
-//   mode 1: y = x / max(||x||_2, 1e-12)                  F.normalize (models/line_transformer.py:246)
+//   mode 1: y = x / max(||x||_2, 1e-12) (+ add)          F.normalize (models/line_transformer.py:246)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__ x, int rows, int mode,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -510,11 +510,6 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
     const f32x4 b = *reinterpret_cast<const f32x4*>(beta + lane * 4);
 #pragma unroll
     for (int c = 0; c < 4; ++c) o[c] = (v[c] - mean) * rstd * g[c] + b[c];
-    if (add) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(add + (int64_t)row * D + lane * 4);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] += a[c];
-    }
   } else {
     float q = 0.f;
 #pragma unroll
@@ -522,6 +517,11 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
     const float nrm = fmaxf(sqrtf(wave_sum(q)), 1e-12f);
 #pragma unroll
     for (int c = 0; c < 4; ++c) o[c] = v[c] / nrm;
+  }
+  if (add) {      // behind either normalisation, as the fused epilogue of lt_gemm_split.h does (GemmArgs::add2)
+    const f32x4 a = *reinterpret_cast<const f32x4*>(add + (int64_t)row * D + lane * 4);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] += a[c];
   }
   *reinterpret_cast<f32x4*>(y + (int64_t)row * D + lane * 4) = o;
 }

@@ -1002,6 +1002,94 @@ class Engine:
                                             int(act), int(cache_weights), self._stream()), self._L)
         return Y
 
+    # tile names of linetr_debug_gemm_case (csrc/lt_gemm_split.h: SplitTile, csrc/lt_gemm.h: F32Tile), by index
+    GEMM_SPLIT_TILES = ("32x32k4", "112x256", "128x64", "256x128", "128x256", "64x256", "128x128", "128x128s", "256x256", "64x64",
+                        "64x128")
+    GEMM_F32_TILES = ("128x64", "128x128", "64x128")
+    GEMM_WS = "ws64x256"          # LINETR_GEMM_TILE_WS
+    _GEMM_TILE_WS = 100
+
+    def _gemm_tile_code(self, tile):
+        if tile is None or tile == -1:
+            return -1
+        if tile == self.GEMM_WS:
+            return self._GEMM_TILE_WS
+        names = self.GEMM_F32_TILES if self.get_precision() == "f32" else self.GEMM_SPLIT_TILES
+        if tile not in names:
+            raise ValueError(f"no GEMM tile {tile!r} in {self.get_precision()} mode")
+        return names.index(tile)
+
+    def _gemm_tile_name(self, code):
+        if code == self._GEMM_TILE_WS:
+            return self.GEMM_WS
+        return (self.GEMM_F32_TILES if self.get_precision() == "f32" else self.GEMM_SPLIT_TILES)[code]
+
+    def gemm_tile(self, M, N, K, *, groups=1, act=0, residual=False, concat=False, norm=0, lda=None, ldy=None, tile=-1) -> str:
+        """Name of the GEMM kernel the forward pass takes for act([A | A2] W^T + b) (+ R) of this shape at the current precision
+        (`tile`: of the kernel that launches when that tile is asked for); nothing is launched."""
+        flag = C.c_void_p(16)      # never dereferenced: says that the operand is there
+        c = nat.GemmCase(A=None, lda=int(lda or K), A2=flag if concat else None, lda2=int(K), K1=32 if concat else 0, W=None, bias=None,
+                         R=flag if residual else None, Y=None, ldy=int(ldy or N), M=int(M), N=int(N), K=int(K), act=int(act),
+                         groups=int(groups), gA=0, gY=0, norm=int(norm), gamma=None, beta=None, add2=None, eps=0.0, via_row_norm=0,
+                         tile=self._gemm_tile_code(tile))
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_gemm_case(self._h, C.byref(c), C.byref(used), None), self._L)
+        return self._gemm_tile_name(used.value)
+
+    def debug_gemm_case(self, A, W, bias=None, residual=None, act=0, *, A2=None, groups=1, gA=0, gY=None, norm=0, gamma=None,
+                        beta=None, add2=None, eps=0.0, via_row_norm=False, tile=-1, out=None):
+        """ONE kernel of the GEMM family alone on a full problem description (linetr_debug_gemm_case; diagnostics / unit tests):
+        Y_g = norm(act([A_g | A2_g] @ W_g.T + bias_g) (+ residual)) (+ add2).  A [M, K1], A2 [M, K - K1], residual and out [M, N]
+        are group 0's views (row-strided: stride(0) a multiple of 4, stride(1) == 1); group g sits gA / gY floats behind them in the
+        same storage.  W [groups * N, K].  tile: -1 (the forward pass's choice), a name of GEMM_SPLIT_TILES / GEMM_F32_TILES or
+        GEMM_WS.  Returns (out -- or a new [M, N] / [groups, M, N] tensor --, name of the kernel that ran).  Every operand is
+        checked against the storage behind it before anything is launched."""
+        W = self._f32(W)
+        M, K1 = (int(v) for v in A.shape)
+        K = K1 + (int(A2.shape[1]) if A2 is not None else 0)
+        N = int(W.shape[0]) // groups
+        if W.shape != (groups * N, K) or not W.is_contiguous():
+            raise ValueError(f"W must be a contiguous [{groups} * N, {K}] tensor")
+        if out is None:
+            full = torch.empty((groups, M, N), dtype=torch.float32, device=self.device)
+            out, gY = full[0], M * N
+        else:
+            full = out
+        gY = int(gY or 0)
+
+        def extent(t, rows, cols, gstride, what):
+            """t's first `rows` x `cols` block of every group must lie inside t's storage"""
+            if t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what}: a float32 matrix on the engine's device with unit column stride expected")
+            if t.shape[0] < rows or t.shape[1] < cols:
+                raise ValueError(f"{what}: shape {tuple(t.shape)} is smaller than [{rows}, {cols}]")
+            have = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+            need = (groups - 1) * gstride + (rows - 1) * t.stride(0) + cols if rows > 0 else 0
+            if need > have:
+                raise ValueError(f"{what}: {need} floats needed behind its first element, the storage holds {have}")
+            return t
+
+        extent(A, M, K1, int(gA), "A")
+        if A2 is not None:
+            extent(A2, M, K - K1, int(gA), "A2")
+        extent(out, M, N, gY, "out")
+        if groups > 1 and gY < (M - 1) * out.stride(0) + N:
+            raise ValueError("gY: the groups' outputs overlap")
+        if residual is not None and extent(residual, M, N, 0, "residual").stride(0) != out.stride(0):
+            raise ValueError("residual must share the output's row stride")
+        vec = lambda t, n, what: None if t is None else extent(self._f32(t).reshape(1, -1), 1, n, 0, what)
+        b, ga, be = vec(bias, groups * N, "bias"), vec(gamma, N, "gamma"), vec(beta, N, "beta")
+        if add2 is not None and (extent(add2, M, N, 0, "add2").stride(0) != D or N != D):
+            raise ValueError("add2 must have row stride 256")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        c = nat.GemmCase(A=ptr(A), lda=A.stride(0), A2=ptr(A2), lda2=A2.stride(0) if A2 is not None else 0, K1=K1 if A2 is not None else 0,
+                         W=ptr(W), bias=ptr(b), R=ptr(residual), Y=ptr(out), ldy=out.stride(0), M=M, N=N, K=K, act=int(act),
+                         groups=int(groups), gA=int(gA), gY=gY, norm=int(norm), gamma=ptr(ga), beta=ptr(be), add2=ptr(add2),
+                         eps=float(eps), via_row_norm=int(bool(via_row_norm)), tile=self._gemm_tile_code(tile))
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_gemm_case(self._h, C.byref(c), C.byref(used), self._stream()), self._L)
+        return (full if groups > 1 or full is out else out), self._gemm_tile_name(used.value)
+
     SIG_KERNELS = ("sig_attn", "sig_attn_small", "sig_attn_split4", "sig_attn_split8", "sig_qkv_attn")
 
     def sig_attention_kernel(self, cu_sub) -> int:

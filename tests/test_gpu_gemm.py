@@ -79,6 +79,7 @@ def test_gemm_112_row_tiles(eng, mode, tol, M, N, K, act):
     R = torch.randn(M, N, device="cuda", generator=g)
     eng.set_precision(mode)
     try:
+        assert eng.gemm_tile(M, N, K, act=act, residual=True) == "112x256"
         Y = eng.debug_gemm(A, W, b, R, act)
     finally:
         eng.set_precision("bf16x6")
@@ -159,6 +160,8 @@ def test_gemm_small_m_kernel(eng, mode, tol, M, N, K, act):
     R = torch.randn(M, N, device="cuda", generator=g)
     eng.set_precision(mode)
     try:
+        # the dispatcher's choice for exactly this launch (debug_gemm and gemm_tile go through the same host function)
+        assert eng.gemm_tile(M, N, K, act=act, residual=True) == ("32x32k4" if mode != "f32" else "128x64" if N % 128 else "64x128")
         Y = eng.debug_gemm(A, W, b, R, act)
     finally:
         eng.set_precision("bf16x6")
