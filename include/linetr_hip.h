@@ -20,6 +20,8 @@
  * ABI version 6: + linetr_debug_sig_attention (one chosen signature-attention kernel alone, for the unit tests).
  *                + linetr_debug_gemm_case (one chosen GEMM tile alone on a full problem description, for the unit tests): an added
  *                diagnostics symbol, nothing existing changes, so the version stays.
+ *                + linetr_debug_tok_mlp, linetr_debug_cls_pool (the descriptive layer's front-end kernels alone, for the unit
+ *                tests): added diagnostics symbols again, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -524,6 +526,50 @@ int linetr_debug_gemm_case(LinetrHandle* h, const LinetrGemmCase* c, int32_t* ti
  * only the choice is reported and nothing is launched.  kernel_used may be NULL.  Synchronises `stream` before returning. */
 int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32_t layer, const float* d_in, int32_t ld_in,
                                const int32_t* h_cu_sub, int32_t n_images, float* d_msg, int32_t* kernel_used, void* stream);
+
+/* Runs ONE launch of the positional encoders' MLP up to its fourth ReLU (models/line_transformer.py:9-20, 40-73 without the last
+ * linear layer; BatchNorm folded) alone, for the unit tests (tests/test_gpu_front.py: every variant against float64 at its tile
+ * edges).  Word encoder: d_pnt [rows_word][2] token coordinates in pixels, d_score [rows_word]; line encoder: d_sublines
+ * [rows_line][2][2] end points in pixels, d_resp [rows_line], d_angle [rows_line][2]; coordinates are normalised with the
+ * handle's image_shape (normalize_keylines, :22-38).  d_out_word [rows_word][256], d_out_line [rows_line][256].
+ * variant: 0 tok_mlp_kernel<word>, 1 tok_mlp_kernel<line>, 2 tok_mlp_dual_kernel (both encoders side by side, one block per
+ *          64-row tile), 3 tok_mlp_seq_kernel (every persistent block walks the word encoder's tiles, then the line encoder's),
+ *          4 the unfused chain the forward pass falls back to (layers 1-3 in mlp123_kernel, layer 4 through the GEMM dispatcher),
+ *          for every encoder that has rows; -1 = what the forward pass takes for these row counts at the handle's precision
+ *          (the choice is made by the same host function the forward pass calls): 2 while ceil(rows_word / 64) +
+ *          ceil(rows_line / 64) <= compute units, 3 above; 0 / 1 when the other encoder has no rows; 4 outside bf16x6 mode.
+ * max_blocks: 0 = the persistent kernels (0, 1, 3) launch one block per compute unit (at most one per tile), as the forward pass
+ *          does; > 0 caps that grid, so that a block walks several tiles at a few hundred rows.  Not read by variants 2 and 4.
+ * *variant_used (may be NULL) receives what launches.  With variant = -1 and both outputs NULL only the choice is reported and
+ * nothing is launched or dereferenced.  An encoder without rows is not launched (variants 0, 1, 4).  Refused with LINETR_E_ARG,
+ * nothing launched: variant 2 whose blocks do not fit the chip, variants 2 / 3 with an empty encoder, a training-mode handle,
+ * negative sizes, NULL tensors, outputs that are not 16-byte aligned.  Synchronises `stream` before returning. */
+int linetr_debug_tok_mlp(LinetrHandle* h, int32_t variant, const float* d_pnt, const float* d_score, int64_t rows_word,
+                         const float* d_sublines, const float* d_resp, const float* d_angle, int64_t rows_line,
+                         float* d_out_word, float* d_out_line, int32_t max_blocks, int32_t* variant_used, void* stream);
+
+/* Runs ONE CLS-row pooling kernel of the descriptive layer (models/line_attention.py:6-75 restricted to query row 0) alone, for
+ * the unit tests (tests/test_gpu_front.py).  d_pooled [N][4][544] = per sub-line and head [sum_j p_j desc_j (256) | sum_j p_j
+ * a4_j (256) | p_CLS | 31 zeros], the sums over the token keys j >= 1.
+ * kernel: 0 cls_pool_kernel (the dense token stage of linetr_forward): reads d_desc_dense [N][T][256] and d_a4 [N*T][256] only;
+ *         1 cls_pool_online_kernel<1> (one wave per sub-line), sub-lines in forward order;  2 the same, last sub-lines first;
+ *         3 cls_pool_online_kernel<4> (the block's four waves share one sub-line);
+ *         -1 = what the forward pass takes: 0 for a dense token stage (d_desc_dense != NULL), otherwise 3 up to 2048
+ *         sub-lines and 2 above (the choice is made by the same host function the forward pass calls).
+ * Kernels 1-3 get the kernel's own operands, as linetr_describe prepares them: the records d_recs [K] (first_sub, n_tok, n_sub,
+ * image and first_tok are read), the sub-line -> key-line map d_sub2line [N], the compact token coordinates d_cpnt [first_pad +
+ * n_images][2] and word-encoder activations d_a4 [first_pad + n_images][256], whose row first_pad + i is image i's shared
+ * padding token, and the n_images dense descriptor maps d_map of Hc x Wc cells: NHWC, or (dense_is_nhwc = 0) NCHW, which
+ * nchw_to_nhwc_kernel first transposes into the call's own scratch.
+ * *kernel_used (may be NULL) receives what launches; with d_pooled = NULL only the choice is reported and nothing is launched or
+ * dereferenced.  Refused with LINETR_E_ARG, nothing launched: T outside 1 .. 4096, a d_sub2line entry outside [0, K), a sub-line
+ * outside its key-line's range or token count, first_tok + n_tok > first_pad, image outside [0, n_images) (records and map are
+ * copied to the host for this), NULL or misaligned tensors (16 bytes: d_a4, d_pooled, d_desc_dense, an NHWC map; 8: d_recs),
+ * a training-mode handle.  Synchronises `stream` before returning. */
+int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const LinetrLineRec* d_recs, int32_t K, const int32_t* d_sub2line,
+                          int32_t N, int32_t T, const float* d_cpnt, const float* d_a4, int64_t first_pad, int32_t n_images,
+                          const float* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
+                          const float* d_desc_dense, float* d_pooled, int32_t* kernel_used, void* stream);
 
 #ifdef LINETR_EXPERIMENTS
 /* ---- split-tile ("ST") operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h): experiments build only --------------------

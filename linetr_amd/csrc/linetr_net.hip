@@ -604,6 +604,26 @@ int pos_encoder_bn(LinetrHandle* h, hipStream_t st, const EncCall& c, const BnTr
   return LINETR_OK;
 }
 
+// The token MLP's launches (the numbers are linetr_debug_tok_mlp's `variant` argument, include/linetr_hip.h)
+enum { TOKV_WORD = 0, TOKV_LINE = 1, TOKV_DUAL = 2, TOKV_SEQ = 3, TOKV_CHAIN = 4 };
+// What rows_word token rows and rows_line sub-lines take.  Layers 1-4 in one kernel (lt_tokmlp.h): the default precision and the
+// reference's channel widths, at any size (a single pair, 4 k token rows and 400 sub-lines, gains too: 42 -> 31 us for the two
+// encoders).  Each encoder takes it when its own three split-tile weight images exist (`word`, `line`); both in ONE launch only
+// when both do and neither is empty (`both`: TOKV_DUAL / TOKV_SEQ, or -1: one launch sequence per encoder).
+// The ONE place where the choice is made: pos_encoders and linetr_debug_tok_mlp(variant = -1) both call it.
+struct TokMlpPlan { bool word, line; int both; };
+bool tok_mlp_has_images(const PosEncoder& E) { return E.W2.st && E.W3.st && E.W4.st; }
+TokMlpPlan tok_mlp_plan(const LinetrHandle* h, int64_t rows_word, int64_t rows_line) {
+  const int* ch = h->cfg.enc_channels;
+  const bool ok = fused_mlp_enabled(h->cfg) && h->precision == LINETR_PREC_BF16X6 && ch[0] == 32 && ch[1] == 64 && ch[2] == 128 && ch[3] == 256 &&
+                  !LT_XENV("LINETR_NO_TOKMLP");
+  TokMlpPlan p;
+  p.word = ok && tok_mlp_has_images(h->enc[ENC_WORD]);
+  p.line = ok && tok_mlp_has_images(h->enc[ENC_LINE]);
+  p.both = !(p.word && p.line && rows_word > 0 && rows_line > 0) ? -1 : tok_mlp_dual_fits(rows_word, rows_line) ? TOKV_DUAL : TOKV_SEQ;
+  return p;
+}
+
 // both encoders: the word encoder up to its last ReLU (its final linear layer is applied after pooling), the line encoder to its
 // output (lpos)
 int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const float* sublines, const float* resp,
@@ -615,50 +635,56 @@ int pos_encoders(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const f
   const EncCall line{ENC_LINE, sublines, resp, angle_sub, N, w.act[ENC_LINE]};
   const int64_t rows = ts.rows;
   int e;
-  // layers 1-4 in one kernel (lt_tokmlp.h): the default precision and the reference's channel widths, at any size (a single pair,
-  // 4 k token rows and 400 sub-lines, gains too: 42 -> 31 us for the two encoders).  Each encoder takes it when its own three
-  // split-tile weight images exist; both in ONE launch only when both do and neither is empty.
-  const bool tok_mlp_ok = fused_mlp_enabled(c) && h->precision == LINETR_PREC_BF16X6 && e0 == 32 && e1 == 64 && e2 == 128 && e3 == 256 &&
-                          !LT_XENV("LINETR_NO_TOKMLP");
-  auto has_images = [](const PosEncoder& E) { return E.W2.st && E.W3.st && E.W4.st; };
-  const bool tok_mlp = tok_mlp_ok && has_images(h->enc[ENC_WORD]), line_mlp = tok_mlp_ok && has_images(h->enc[ENC_LINE]);
+  const TokMlpPlan plan = tok_mlp_plan(h, rows, N);
   if (ts.bn) {
     int64_t off = 0;
     if ((e = pos_encoder_bn(h, st, word, *ts.bn, off))) return e;
     if ((e = pos_encoder_bn(h, st, line, *ts.bn, off))) return e;
-  } else if (tok_mlp && line_mlp && rows > 0 && N > 0) {
+  } else if (plan.both >= 0) {
     // side by side for a small batch, one after the other inside every persistent block for a large one
     ProfScope ps(h, st, "pos_mlp_dual_bf16x6", 2.0 * rows * (3 * e0 + e0 * e1 + e1 * e2 + e2 * e3) + 2.0 * N * (5 * e0 + e0 * e1 + e1 * e2 + e2 * e3),
                  (double)rows * (12 + 4 * e3) + (double)N * (28 + 4 * e3));
     if ((e = tok_mlp_launch_dual(tok_mlp_args(h, word), tok_mlp_args(h, line), st))) return e;
   } else {
-    if ((e = pos_encoder(h, st, word, tok_mlp))) return e;
-    if ((e = pos_encoder(h, st, line, line_mlp))) return e;
+    if ((e = pos_encoder(h, st, word, plan.word))) return e;
+    if ((e = pos_encoder(h, st, line, plan.line))) return e;
   }
   return run_gemm(h, st, h->lW5, N, {w.act[ENC_LINE][3], e3}, {w.lpos, D}, ACT_NONE);
 }
 
 // ---- CLS-row attention pooling + value / last-MLP projection (up to CUT_POOL)
-int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_images, int N, int T, FwdWs& w) {
+// The pooling kernels (the numbers are linetr_debug_cls_pool's `kernel` argument, include/linetr_hip.h)
+enum { POOLK_DENSE = 0, POOLK_ONLINE = 1, POOLK_ONLINE_REV = 2, POOLK_SPLIT4 = 3 };
+// The ONE place where the choice is made (cls_pooling and linetr_debug_cls_pool(kernel = -1) both call it): the dense token stage
+// has one kernel; of the online kernels, few sub-lines (a single pair) take four waves per sub-line, so that the chip is covered
+// and the token chain is a quarter as long, many take one wave per sub-line, the last sub-lines first (see the kernel)
+int cls_pool_plan(bool online, int N) { return !online ? POOLK_DENSE : N <= 2048 ? POOLK_SPLIT4 : POOLK_ONLINE_REV; }
+
+// kernel `kernel` over the token stage ts and the word encoder's activations a4 -> pooled [N][4][544]
+int cls_pool_launch(LinetrHandle* h, hipStream_t st, int kernel, const TokenStage& ts, int n_images, int N, int T, const float* a4,
+                    float* pooled) {
   const int64_t rows = ts.rows;
-  if (ts.cpnt) {
+  if (kernel != POOLK_DENSE) {
     // algorithmic bytes: the dense map once (or the four taps of every token, whichever is less), one a4 row per token, the pooled rows out
     const double tap_bytes = std::min((double)n_images * ts.Hc * ts.Wc * D * 4, (double)rows * D * 4 * 4);
     ProfScope ps(h, st, "cls_pool_online", 2.0 * rows * (2.0 * HEADS * D * 2), tap_bytes + (double)rows * D * 4 + (double)N * HEADS * POOLW * 4);
-    // few sub-lines (a single pair): four waves per sub-line, so that the chip is covered and the token chain is a quarter as long
-    if (N <= 2048)
+    if (kernel == POOLK_SPLIT4)
       hipLaunchKernelGGL(cls_pool_online_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         w.act[ENC_WORD][3], ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 0);
-    else   // (reverse = 1: the last sub-lines first, see the kernel)
+                         a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, pooled, 0);
+    else
       hipLaunchKernelGGL(cls_pool_online_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         w.act[ENC_WORD][3], ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, w.pooled, 1);
+                         a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, pooled, kernel == POOLK_ONLINE_REV ? 1 : 0);
     LT_LAUNCH_CHECK();
   } else {
     ProfScope ps(h, st, "cls_pool", 2.0 * rows * (2.0 * HEADS * D * 2), (double)rows * D * 8);
-    hipLaunchKernelGGL(cls_pool_kernel, dim3(N), dim3(256), HEADS * (T + 1) * sizeof(float), st, ts.desc, w.act[ENC_WORD][3], T,
-                       h->pool, w.pooled);
+    hipLaunchKernelGGL(cls_pool_kernel, dim3(N), dim3(256), HEADS * (T + 1) * sizeof(float), st, ts.desc, a4, T, h->pool, pooled);
     LT_LAUNCH_CHECK();
   }
+  return LINETR_OK;
+}
+
+int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_images, int N, int T, FwdWs& w) {
+  if (int e = cls_pool_launch(h, st, cls_pool_plan(ts.cpnt != nullptr, N), ts, n_images, N, T, w.act[ENC_WORD][3], w.pooled)) return e;
   // one product per head: the head's DH rows of Watt over its pooled row
   const GemmGroups heads{HEADS, DH, POOLW, DH};
   return run_gemm(h, st, h->Watt, N, {w.pooled, HEADS * POOLW}, {w.att, D}, ACT_NONE, nullptr, &heads);
@@ -1207,5 +1233,124 @@ extern "C" int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32
                              : sig_attention(h, st, kernel, d_in, ld_in, cu_dev, n_images, N, max_n, fl, d_msg);
   (void)hipStreamSynchronize(st);
   (void)hipFree(cu_dev);
+  return e;
+}
+
+extern "C" int linetr_debug_tok_mlp(LinetrHandle* h, int32_t variant, const float* d_pnt, const float* d_score, int64_t rows_word,
+                                    const float* d_sublines, const float* d_resp, const float* d_angle, int64_t rows_line,
+                                    float* d_out_word, float* d_out_line, int32_t max_blocks, int32_t* variant_used, void* stream) {
+  if (!h) return fail(LINETR_E_ARG, "debug_tok_mlp: null handle");
+  if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_tok_mlp: a training-mode handle (bn_batch_stats = 1) is not served");
+  if (variant < -1 || variant > TOKV_CHAIN) return fail(LINETR_E_ARG, "debug_tok_mlp: variant must be -1 .. 4");
+  if (rows_word < 0 || rows_line < 0 || rows_word > INT32_MAX / 8 || rows_line > INT32_MAX / 8)
+    return fail(LINETR_E_ARG, "debug_tok_mlp: row counts must be 0 .. %d", INT32_MAX / 8);
+  if (max_blocks < 0) return fail(LINETR_E_ARG, "debug_tok_mlp: max_blocks must be 0 (one block per compute unit) or positive");
+  if (!fused_mlp_enabled(h->cfg) || h->cfg.enc_channels[0] != 32 || h->cfg.enc_channels[3] != D)
+    return fail(LINETR_E_ARG, "debug_tok_mlp: needs keyline_encoder [32,64,128,256]");
+  const bool query_only = variant == -1 && !d_out_word && !d_out_line;
+  // which encoders run: the forced single-encoder variants their own, everything else every encoder that has rows
+  bool word = rows_word > 0 && variant != TOKV_LINE, line = rows_line > 0 && variant != TOKV_WORD;
+  if (variant == -1) {
+    const TokMlpPlan plan = tok_mlp_plan(h, rows_word, rows_line);
+    variant = plan.both >= 0 ? plan.both : (word && !plan.word) || (line && !plan.line) ? (int)TOKV_CHAIN : word ? (int)TOKV_WORD : line ? (int)TOKV_LINE : -1;
+  }
+  if (variant_used) *variant_used = variant;
+  if (query_only || variant < 0) return LINETR_OK;
+  // what a launch is not written for is refused, not launched
+  if (variant == TOKV_DUAL || variant == TOKV_SEQ) {
+    if (rows_word <= 0 || rows_line <= 0) return fail(LINETR_E_ARG, "debug_tok_mlp: the two-encoder launches need rows of both encoders");
+    if (variant == TOKV_DUAL && !tok_mlp_dual_fits(rows_word, rows_line))
+      return fail(LINETR_E_ARG, "debug_tok_mlp: %lld + %lld rows do not fit the chip side by side (one block per 64-row tile, %d compute units)",
+                  (long long)rows_word, (long long)rows_line, cu_count());
+  }
+  if (variant != TOKV_CHAIN && ((word && !tok_mlp_has_images(h->enc[ENC_WORD])) || (line && !tok_mlp_has_images(h->enc[ENC_LINE]))))
+    return fail(LINETR_E_ARG, "debug_tok_mlp: the encoder has no split-tile weight images");
+  if (!word && !line) return LINETR_OK;
+  if ((word && (!d_pnt || !d_score || !d_out_word)) || (line && (!d_sublines || !d_resp || !d_angle || !d_out_line)))
+    return fail(LINETR_E_ARG, "debug_tok_mlp: null tensor");
+  if (((uintptr_t)d_pnt | (uintptr_t)d_score | (uintptr_t)d_sublines | (uintptr_t)d_resp | (uintptr_t)d_angle) % 4 ||
+      ((uintptr_t)d_out_word | (uintptr_t)d_out_line) % 16)
+    return fail(LINETR_E_ARG, "debug_tok_mlp: outputs must be 16-byte aligned, inputs 4-byte aligned");
+  LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  float* scratch = nullptr;   // the unfused chain's [rows][128] activations, freed below
+  const int64_t off_line = align_up((word ? rows_word : 0) * h->cfg.enc_channels[2] * 4, 256);
+  if (variant == TOKV_CHAIN) LT_HIP(hipMalloc((void**)&scratch, off_line + align_up((line ? rows_line : 0) * h->cfg.enc_channels[2] * 4, 256) + 256));
+  float* act_w[4] = {nullptr, nullptr, scratch, d_out_word};
+  float* act_l[4] = {nullptr, nullptr, scratch ? (float*)((char*)scratch + off_line) : nullptr, d_out_line};
+  const EncCall cw{ENC_WORD, d_pnt, d_score, nullptr, rows_word, act_w};
+  const EncCall cl{ENC_LINE, d_sublines, d_resp, d_angle, rows_line, act_l};
+  int e = LINETR_OK;
+  switch (variant) {
+    case TOKV_WORD: e = tok_mlp_launch(tok_mlp_args(h, cw), true, st, max_blocks); break;
+    case TOKV_LINE: e = tok_mlp_launch(tok_mlp_args(h, cl), false, st, max_blocks); break;
+    case TOKV_DUAL: e = tok_mlp_launch_dual(tok_mlp_args(h, cw), tok_mlp_args(h, cl), st, max_blocks, 0); break;
+    case TOKV_SEQ: e = tok_mlp_launch_dual(tok_mlp_args(h, cw), tok_mlp_args(h, cl), st, max_blocks, 1); break;
+    default:
+      if (word) e = pos_encoder(h, st, cw, false);
+      if (!e && line) e = pos_encoder(h, st, cl, false);
+  }
+  (void)hipStreamSynchronize(st);
+  if (scratch) (void)hipFree(scratch);
+  return e;
+}
+
+extern "C" int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const LinetrLineRec* d_recs, int32_t K, const int32_t* d_sub2line,
+                                     int32_t N, int32_t T, const float* d_cpnt, const float* d_a4, int64_t first_pad, int32_t n_images,
+                                     const float* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
+                                     const float* d_desc_dense, float* d_pooled, int32_t* kernel_used, void* stream) {
+  if (!h) return fail(LINETR_E_ARG, "debug_cls_pool: null handle");
+  if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_cls_pool: a training-mode handle (bn_batch_stats = 1) is not served");
+  if (kernel < -1 || kernel > POOLK_SPLIT4) return fail(LINETR_E_ARG, "debug_cls_pool: kernel must be -1 .. 3");
+  if (N < 0) return fail(LINETR_E_ARG, "debug_cls_pool: negative sub-line count");
+  if (kernel == -1) kernel = cls_pool_plan(d_desc_dense == nullptr, N);   // d_desc_dense says that the token stage is the dense one
+  if (kernel_used) *kernel_used = kernel;
+  if (!d_pooled) return LINETR_OK;                                         // the choice only: nothing is dereferenced
+  if (T < 1 || T > 4096) return fail(LINETR_E_ARG, "debug_cls_pool: max_tokens must be 1 .. 4096");
+  if (N == 0) return LINETR_OK;
+  if (!d_a4) return fail(LINETR_E_ARG, "debug_cls_pool: null tensor");
+  if (((uintptr_t)d_a4 | (uintptr_t)d_pooled) % 16) return fail(LINETR_E_ARG, "debug_cls_pool: tensors must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  TokenStage ts;
+  if (kernel == POOLK_DENSE) {
+    if (!d_desc_dense || (uintptr_t)d_desc_dense % 16) return fail(LINETR_E_ARG, "debug_cls_pool: the dense kernel reads d_desc_dense [N][T][256], 16-byte aligned");
+    if ((int64_t)N * T > INT32_MAX / 8) return fail(LINETR_E_ARG, "debug_cls_pool: batch too large");
+    LT_HIP(hipSetDevice(h->device));
+    ts.desc = d_desc_dense; ts.rows = (int64_t)N * T;
+    const int e = cls_pool_launch(h, st, kernel, ts, 1, N, T, d_a4, d_pooled);
+    (void)hipStreamSynchronize(st);
+    return e;
+  }
+  if (!d_recs || !d_sub2line || !d_cpnt || !d_map) return fail(LINETR_E_ARG, "debug_cls_pool: null tensor");
+  if (K < 1 || n_images < 1 || Hc < 1 || Wc < 1 || first_pad < 0 || first_pad > INT32_MAX / 8 || (int64_t)n_images * Hc * Wc > INT32_MAX / D)
+    return fail(LINETR_E_ARG, "debug_cls_pool: bad shape");
+  if ((uintptr_t)d_recs % 8 || ((uintptr_t)d_sub2line | (uintptr_t)d_cpnt | (uintptr_t)d_map) % 4 || (dense_is_nhwc && (uintptr_t)d_map % 16))
+    return fail(LINETR_E_ARG, "debug_cls_pool: misaligned tensor (records 8 bytes, an NHWC map 16, the others 4)");
+  LT_HIP(hipSetDevice(h->device));
+  {  // everything the kernel indexes with comes from the caller: checked on the host first
+    std::vector<LinetrLineRec> recs(K);
+    std::vector<int32_t> s2l(N);
+    LT_HIP(hipStreamSynchronize(st));
+    LT_HIP(hipMemcpy(recs.data(), d_recs, (size_t)K * sizeof(LinetrLineRec), hipMemcpyDeviceToHost));
+    LT_HIP(hipMemcpy(s2l.data(), d_sub2line, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int n = 0; n < N; ++n) {
+      if (s2l[n] < 0 || s2l[n] >= K) return fail(LINETR_E_ARG, "debug_cls_pool: sub-line %d maps to key-line %d, outside [0, %d)", n, s2l[n], K);
+      const LinetrLineRec& r = recs[s2l[n]];
+      const int64_t j = (int64_t)n - r.first_sub;
+      if (j < 0 || j >= r.n_sub || j * T >= r.n_tok)
+        return fail(LINETR_E_ARG, "debug_cls_pool: sub-line %d is not one of key-line %d's (first_sub %d, n_sub %d, n_tok %d)", n, s2l[n], r.first_sub, r.n_sub, r.n_tok);
+      if (r.first_tok < 0 || (int64_t)r.first_tok + r.n_tok > first_pad)
+        return fail(LINETR_E_ARG, "debug_cls_pool: key-line %d's tokens [%d, %d + %d) reach past first_pad = %lld", s2l[n], r.first_tok, r.first_tok, r.n_tok, (long long)first_pad);
+      if (r.image < 0 || r.image >= n_images) return fail(LINETR_E_ARG, "debug_cls_pool: key-line %d's image %d outside [0, %d)", s2l[n], r.image, n_images);
+    }
+  }
+  float* buf = nullptr;   // the transposed map of an NCHW caller, freed below
+  if (!dense_is_nhwc) LT_HIP(hipMalloc((void**)&buf, (size_t)n_images * Hc * Wc * D * sizeof(float)));
+  ts.cpnt = d_cpnt; ts.recs = d_recs; ts.sub2line_g = d_sub2line; ts.rows = first_pad + n_images; ts.first_pad = first_pad;
+  ts.Hc = Hc; ts.Wc = Wc; ts.align_corners = align_corners;
+  int e = nhwc_map(h, st, d_map, dense_is_nhwc, n_images, Hc * Wc, buf, ts.nhwc);
+  if (!e) e = cls_pool_launch(h, st, kernel, ts, n_images, N, T, d_a4, d_pooled);
+  (void)hipStreamSynchronize(st);
+  if (buf) (void)hipFree(buf);
   return e;
 }

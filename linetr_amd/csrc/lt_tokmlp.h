@@ -263,14 +263,18 @@ __global__ __launch_bounds__(512) void tok_mlp_dual_kernel(TokMlpArgs aw, TokMlp
   else tok_mlp_body<false>(al, blockIdx.x - word_blocks, gridDim.x - word_blocks);
 }
 
-inline int tok_mlp_launch(const TokMlpArgs& a, bool word, hipStream_t st) {
+// the persistent grid: one block per CU, or at most max_blocks of them (linetr_debug_tok_mlp: a block then walks several tiles at
+// a few hundred rows)
+inline int tok_mlp_blocks(int max_blocks) { return max_blocks > 0 ? std::min(max_blocks, cu_count()) : cu_count(); }
+
+inline int tok_mlp_launch(const TokMlpArgs& a, bool word, hipStream_t st, int max_blocks = 0) {
   if (a.rows <= 0) return 0;
   if (!a.p0 || !a.p1 || (!word && !a.p2) || !a.W1 || !a.W2st || !a.W3st || !a.W4st || !a.b1 || !a.b2 || !a.b3 || !a.b4 || !a.Y || a.ldy % 4)
     return fail(LINETR_E_ARG, "tok_mlp: missing operand");
   LT_HIP(allow_dynamic_lds<tok_mlp_kernel<true>>(TK_LDS));
   LT_HIP(allow_dynamic_lds<tok_mlp_kernel<false>>(TK_LDS));
   const int64_t ntiles = (a.rows + TK_TM - 1) / TK_TM;
-  const dim3 grid((unsigned)std::min<int64_t>(ntiles, cu_count()));
+  const dim3 grid((unsigned)std::min<int64_t>(ntiles, tok_mlp_blocks(max_blocks)));
   if (word) hipLaunchKernelGGL(tok_mlp_kernel<true>, grid, dim3(512), TK_LDS, st, a);
   else hipLaunchKernelGGL(tok_mlp_kernel<false>, grid, dim3(512), TK_LDS, st, a);
   LT_LAUNCH_CHECK();
@@ -289,17 +293,19 @@ __global__ __launch_bounds__(512) void tok_mlp_seq_kernel(TokMlpArgs aw, TokMlpA
 inline bool tok_mlp_dual_fits(int64_t rows_word, int64_t rows_line) {
   return rows_word > 0 && rows_line > 0 && (rows_word + TK_TM - 1) / TK_TM + (rows_line + TK_TM - 1) / TK_TM <= cu_count();
 }
-// one launch for both encoders: side by side when the blocks fit the chip, otherwise one after the other inside every block
-inline int tok_mlp_launch_dual(const TokMlpArgs& aw, const TokMlpArgs& al, hipStream_t st) {
+// one launch for both encoders: side by side when the blocks fit the chip, otherwise one after the other inside every block.
+// force_seq (linetr_debug_tok_mlp): -1 = that rule, 0 = side by side (refused when the blocks do not fit), 1 = one after the other
+inline int tok_mlp_launch_dual(const TokMlpArgs& aw, const TokMlpArgs& al, hipStream_t st, int max_blocks = 0, int force_seq = -1) {
   const int64_t tw = (aw.rows + TK_TM - 1) / TK_TM, tl = (al.rows + TK_TM - 1) / TK_TM;
   if (aw.rows <= 0 || al.rows <= 0) return fail(LINETR_E_ARG, "tok_mlp: empty encoder input");
   if (!aw.p0 || !aw.p1 || !al.p0 || !al.p1 || !al.p2 || !aw.Y || !al.Y || aw.ldy % 4 || al.ldy % 4) return fail(LINETR_E_ARG, "tok_mlp: missing operand");
   LT_HIP(allow_dynamic_lds<tok_mlp_dual_kernel>(TK_LDS));
   LT_HIP(allow_dynamic_lds<tok_mlp_seq_kernel>(TK_LDS));
-  if (tok_mlp_dual_fits(aw.rows, al.rows)) {
+  if (force_seq == 0 && !tok_mlp_dual_fits(aw.rows, al.rows)) return fail(LINETR_E_ARG, "tok_mlp: the two encoders' blocks do not fit the chip side by side");
+  if (force_seq < 0 ? tok_mlp_dual_fits(aw.rows, al.rows) : force_seq == 0) {
     hipLaunchKernelGGL(tok_mlp_dual_kernel, dim3((unsigned)(tw + tl)), dim3(512), TK_LDS, st, aw, al, (int)tw);
   } else {
-    hipLaunchKernelGGL(tok_mlp_seq_kernel, dim3((unsigned)std::min<int64_t>(std::max(tw, tl), cu_count())), dim3(512), TK_LDS, st, aw, al);
+    hipLaunchKernelGGL(tok_mlp_seq_kernel, dim3((unsigned)std::min<int64_t>(std::max(tw, tl), tok_mlp_blocks(max_blocks))), dim3(512), TK_LDS, st, aw, al);
   }
   LT_LAUNCH_CHECK();
   return 0;

@@ -1120,6 +1120,84 @@ class Engine:
                                                      len(cu) - 1, msg.data_ptr(), C.byref(used), self._stream()), self._L)
         return msg, used.value
 
+    TOK_MLP_VARIANTS = ("tok_mlp_word", "tok_mlp_line", "tok_mlp_dual", "tok_mlp_seq", "mlp123_gemm_chain")
+
+    def tok_mlp_variant(self, rows_word, rows_line) -> int:
+        """Which launch (index into TOK_MLP_VARIANTS) the forward pass takes for the two positional encoders at these row counts
+        and the current precision; nothing is launched."""
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_tok_mlp(self._h, -1, None, None, int(rows_word), None, None, None, int(rows_line), None, None, 0,
+                                               C.byref(used), self._stream()), self._L)
+        return used.value
+
+    def debug_tok_mlp(self, variant, word=None, line=None, out_word=None, out_line=None, max_blocks=0):
+        """ONE launch of the positional encoders' MLP up to its fourth ReLU alone (linetr_debug_tok_mlp; diagnostics / unit tests).
+        variant: -1 (the forward pass's choice) or an index into TOK_MLP_VARIANTS.  word = (pnt [>= rows, 2], score [>= rows], rows),
+        line = (sublines [>= rows, 2, 2], resp [>= rows], angle [>= rows, 2], rows): contiguous float32 tensors on the engine's
+        device.  out_word / out_line: contiguous [>= rows, 256] (made here when None).  max_blocks > 0 caps the persistent grid.
+        Returns (out_word, out_line, variant used)."""
+        def f32(t, n, what):
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.numel() < n:
+                raise ValueError(f"{what}: a contiguous float32 tensor of at least {n} elements on the engine's device expected")
+            return t.data_ptr()
+        pw = [None, None]; pl = [None, None, None]
+        rw = rl = 0
+        if word is not None:
+            rw = int(word[2])
+            pw = [f32(word[0], 2 * rw, "pnt"), f32(word[1], rw, "score")]
+            if out_word is None:
+                out_word = torch.empty((rw, D), dtype=torch.float32, device=self.device)
+            f32(out_word, rw * D, "out_word")
+        if line is not None:
+            rl = int(line[3])
+            pl = [f32(line[0], 4 * rl, "sublines"), f32(line[1], rl, "resp"), f32(line[2], 2 * rl, "angle")]
+            if out_line is None:
+                out_line = torch.empty((rl, D), dtype=torch.float32, device=self.device)
+            f32(out_line, rl * D, "out_line")
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_tok_mlp(self._h, int(variant), pw[0], pw[1], rw, pl[0], pl[1], pl[2], rl,
+                                               out_word.data_ptr() if out_word is not None else None,
+                                               out_line.data_ptr() if out_line is not None else None, int(max_blocks), C.byref(used),
+                                               self._stream()), self._L)
+        return out_word, out_line, used.value
+
+    CLS_POOL_KERNELS = ("cls_pool", "cls_pool_online", "cls_pool_online_reverse", "cls_pool_online_split4")
+
+    def cls_pool_kernel(self, N, dense=False) -> int:
+        """Which pooling kernel (index into CLS_POOL_KERNELS) the forward pass takes for N sub-lines (dense: the [N, T] token
+        tensors of linetr_forward instead of linetr_describe's compact token list); nothing is launched."""
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_cls_pool(self._h, -1, None, 0, None, int(N), 1, None, None, 0, 1, None, 1, 1, 1, 0,
+                                                C.c_void_p(16) if dense else None, None, C.byref(used), self._stream()), self._L)
+        return used.value
+
+    def debug_cls_pool(self, kernel, a4, out, N, T, *, recs=None, sub2line=None, cpnt=None, first_pad=0, n_images=1, dense_map=None,
+                       nhwc=True, Hc=0, Wc=0, align_corners=False, desc_dense=None):
+        """ONE CLS-pooling kernel alone (linetr_debug_cls_pool; diagnostics / unit tests).  kernel: -1 (the forward pass's choice)
+        or an index into CLS_POOL_KERNELS.  Kernel 0 reads desc_dense [N, T, 256] and a4 [N * T, 256]; the online kernels the
+        records `recs` (a uint8 device tensor holding LineRec[K]), sub2line [N] int32, cpnt [first_pad + n_images, 2], a4
+        [first_pad + n_images, 256] and n_images maps of Hc x Wc cells (`nhwc`: channel-last, else NCHW).  out: contiguous float32
+        [>= N, 4, 544].  Returns (out, kernel used)."""
+        for t in (a4, out, cpnt, dense_map, desc_dense):
+            if t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
+                raise ValueError("contiguous float32 tensors on the engine's device expected")
+        if out.numel() < N * 4 * 544:
+            raise ValueError("out is smaller than [N, 4, 544]")
+        if desc_dense is None:
+            if recs.dtype != torch.uint8 or sub2line.dtype != torch.int32 or sub2line.numel() < N:
+                raise ValueError("recs: uint8 bytes of LineRec[K]; sub2line: int32 [N]")
+            if a4.numel() < (first_pad + n_images) * D or cpnt.numel() < (first_pad + n_images) * 2 or dense_map.numel() < n_images * Hc * Wc * D:
+                raise ValueError("a4 / cpnt / dense_map are smaller than first_pad + n_images rows / n_images maps")
+        elif a4.numel() < N * T * D or desc_dense.numel() < N * T * D:
+            raise ValueError("a4 / desc_dense are smaller than [N * T, 256]")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_cls_pool(self._h, int(kernel), ptr(recs), recs.numel() // nat.REC_DTYPE.itemsize if recs is not None else 0,
+                                                ptr(sub2line), int(N), int(T), ptr(cpnt), ptr(a4), int(first_pad), int(n_images),
+                                                ptr(dense_map), int(bool(nhwc)), int(Hc), int(Wc), int(bool(align_corners)),
+                                                ptr(desc_dense), ptr(out), C.byref(used), self._stream()), self._L)
+        return out, used.value
+
     # ------------------------------------------------------------------ split-tile operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h)
     def to_st(self, X):
         """fp32 [rows, K] -> ST image (uint8 tensor); K % 32 == 0."""
