@@ -385,6 +385,51 @@ int linetr_val_step(LinetrHandle* h, const float* d_desc0, int32_t n0, const flo
  * loader's int32 [B][M][2] match list whose first entry is not -1 (an index outside 0..n is skipped).  B, n as above, M >= 0 and B * M <= 2^31 * 256, else LINETR_E_ARG.  Asynchronous; `h` may be NULL. */
 int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmatches, int32_t B, int32_t M, int32_t n, float* d_assign, void* stream);
 
+/* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
+
+/* What the reference's dataset builder computes for one image pair with two Python double loops over every pair of sub-lines
+ * (dataloaders/build_homography_dataset.py:210-237), for a batch of B pairs, on the device:
+ *   :214-218  klns0_projected = cv2.perspectiveTransform(klns0, H), klns1_projected = cv2.perspectiveTransform(klns1, inv(H)),
+ *             restated from OpenCV's arithmetic (cv2 is not a dependency): in double w = x m6 + y m7 + m8, w = (w != 0) ? 1 / w : 0,
+ *             X = (x m0 + y m1 + m2) w, cast to the coordinate type;
+ *   :222-225  find_line_matches (dataloaders/utils/util_lines.py:67-114) in both directions -- direction 0: reference line lines0[i]
+ *             against proj(lines1[j], inv(H)); direction 1: reference line lines1[j] against proj(lines0[i], H).  A pair is skipped
+ *             when BOTH end points lie further than thres_reprojected from the reference line, or abs(angle1 - angle0) % 180 >
+ *             thres_angdiff with angle = degrees(arctan2(dx, dy)), or neither end point lies on the reference line and the largest
+ *             end-point distance exceeds len0 + len1;
+ *   :227-233  calculate_line_overlaps (util_lines.py:116-171) in both directions; assign[i][j] = both directions matched ? the larger
+ *             of the two overlaps : 0;
+ *   :234-237  lmatches = np.where(assign > min_overlap_ratio) in row-major order, -1 behind the list.
+ * coord_type selects the arithmetic: LINETR_COORD_F32 is the reference as executed (its sub-lines are float32 tensors, so NumPy
+ * computes every scalar in float32), LINETR_COORD_F64 is for float64 geometry.  No contraction, the reference's operation order,
+ * x * x for ** 2, correctly rounded divide and square root: every compare but the angle one is the reference's bit for bit, and the
+ * overlaps are its values.  (arctan2 is not correctly rounded on either side: an entry can differ only where the angle compare is
+ * within a few ulp of an angle of flipping.  The reference's scalar ** 2 is libm's powf, which may round an exact tie of x * x the
+ * other way.)  thres_reprojected and thres_angdiff are compared in the coordinate type, min_overlap_ratio in float64 against the
+ * unrounded value, as NumPy does.
+ *   d_lines0 [B][n0][2][2], d_lines1 [B][n1][2][2]   end points (x, y) in the coordinate type
+ *   d_H [B][2][9] float64                            per item H (image 0 -> image 1), then inv(H) as the caller computed it
+ *   d_count0 / d_count1 [B] int32 or NULL            valid prefix of each item (clamped to 0 .. n); rows / columns beyond it hold 0
+ *                                                    and no match.  0 is legal.
+ * Outputs, any may be NULL:
+ *   d_assign [B][n0 + pad][n1 + pad] float32         pad = 1 adds the zero dustbin row and column linetr_val_step's d_assign has
+ *   d_lmatches [B][M][2] int32, d_found [B] int32    the list, -1 behind it.  d_found is never capped: an item with d_found[b] > M
+ *                                                    has been cut to its first M pairs and nothing is written past M (the contract
+ *                                                    of linetr_superpoint_keypoints' d_found).  Deterministic: no atomics.
+ *   d_match_dir [B][2][n0][n1] uint8                 find_line_matches per direction, direction 1 stored transposed as [i][j]
+ *   d_overlap_dir [B][2][n0][n1] coordinate type     calc_overlap per direction for EVERY pair, matched or not, stored likewise
+ *   d_proj0 [B][n0][2][2], d_proj1 [B][n1][2][2]     the projected lines (all n rows, whatever the counts)
+ * Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  B, n0 or n1 <= 0 (or beyond 65535 items / 32768
+ * lines), M < 0, pad outside {0, 1}, an unknown coord_type, a NULL input or a workspace smaller than
+ * linetr_gt_assign_workspace_bytes says: LINETR_E_ARG, nothing launched. */
+enum { LINETR_COORD_F32 = 0, LINETR_COORD_F64 = 1 };
+int64_t linetr_gt_assign_workspace_bytes(int32_t B, int32_t n0, int32_t n1);
+int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void* d_lines0, int32_t n0, const void* d_lines1, int32_t n1,
+                     const double* d_H, int32_t B, const int32_t* d_count0, const int32_t* d_count1, double thres_reprojected,
+                     double thres_angdiff, double min_overlap_ratio, int32_t pad, float* d_assign, int32_t* d_lmatches, int32_t M,
+                     int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir, void* d_proj0, void* d_proj1, void* d_workspace,
+                     int64_t workspace_bytes, void* stream);
+
 /* ---- dense-map producer (section 8(f) "next" row 2) ------------------------------------------------- */
 
 /* Post-processing of SuperPoint's two heads, fused with the layout change the tokeniser needs; replaces

@@ -1,12 +1,13 @@
 // liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
-// multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), SuperPoint's key-point branch (lt_keypoints.h) and the
-// validation step (lt_valstep.h).
+// multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), SuperPoint's key-point branch (lt_keypoints.h), the
+// validation step (lt_valstep.h) and the ground-truth line assignment in front of it (lt_gtassign.h).
 #include <algorithm>
 #include <numeric>
 
 #include "lt_handle.h"
 #include "lt_match.h"
 #include "lt_valstep.h"
+#include "lt_gtassign.h"
 #include "lt_producer.h"
 #include "lt_keypoints.h"
 
@@ -738,4 +739,96 @@ extern "C" int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmat
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;
+}
+
+// =============================================================================================
+// ground-truth line assignment of a homography pair (lt_gtassign.h)
+// =============================================================================================
+
+namespace {
+// workspace (sized for the double instance): projected lines of both sides | the four angle arrays | ballot words | found
+struct GtLayout { int W64; int64_t o_proj0, o_proj1, o_ang, o_words, o_found, total; };
+GtLayout gt_layout(int B, int n0, int n1) {
+  GtLayout L{};
+  L.W64 = cdiv(n1, 64);
+  int64_t o = 0;
+  L.o_proj0 = o; o += align_up((int64_t)B * n0 * 4 * 8, 256);
+  L.o_proj1 = o; o += align_up((int64_t)B * n1 * 4 * 8, 256);
+  L.o_ang = o; o += align_up((int64_t)B * 2 * ((int64_t)n0 + n1) * 8, 256);
+  L.o_words = o; o += align_up((int64_t)B * n0 * L.W64 * 8, 256);
+  L.o_found = o; o += align_up((int64_t)B * 4, 256);
+  L.total = o + 256;
+  return L;
+}
+bool gt_dims_ok(int B, int n0, int n1) { return B > 0 && B <= VS_MAX_B && n0 > 0 && n0 <= VS_MAX_N && n1 > 0 && n1 <= VS_MAX_N; }
+
+template <typename T>
+int gt_assign_launch(LinetrHandle* h, hipStream_t st, const GtLayout& L, const void* d_lines0, int n0, const void* d_lines1, int n1,
+                     const double* d_H, int B, const int32_t* d_count0, const int32_t* d_count1, double thres_reprojected,
+                     double thres_angdiff, double min_overlap_ratio, int pad, float* d_assign, int32_t* d_lmatches, int M,
+                     int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir, void* d_proj0, void* d_proj1, char* base) {
+  const T* lines0 = (const T*)d_lines0;
+  const T* lines1 = (const T*)d_lines1;
+  T* proj0 = d_proj0 ? (T*)d_proj0 : (T*)(base + L.o_proj0);
+  T* proj1 = d_proj1 ? (T*)d_proj1 : (T*)(base + L.o_proj1);
+  T* ang0 = (T*)(base + L.o_ang);
+  T* angp0 = ang0 + (int64_t)B * n0;
+  T* ang1 = angp0 + (int64_t)B * n0;
+  T* angp1 = ang1 + (int64_t)B * n1;
+  const bool list = d_lmatches || d_found;
+  unsigned long long* words = list ? (unsigned long long*)(base + L.o_words) : nullptr;
+  const double pairs = (double)B * n0 * n1;
+  {
+    ProfScope ps(h, st, "gt_lines", 0, (double)B * ((double)n0 + n1) * (4 * 2 + 2) * sizeof(T));
+    hipLaunchKernelGGL(gt_lines_kernel<T>, dim3(cdiv(n0, 256), B), dim3(256), 0, st, lines0, n0, d_H, 0, proj0, ang0, angp0);
+    hipLaunchKernelGGL(gt_lines_kernel<T>, dim3(cdiv(n1, 256), B), dim3(256), 0, st, lines1, n1, d_H, 1, proj1, ang1, angp1);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "gt_pair", 0, (d_assign ? 4.0 * B * (n0 + pad) * (n1 + pad) : 0.0) + (d_match_dir ? 2.0 * pairs : 0.0) +
+                                          (d_overlap_dir ? 2.0 * pairs * sizeof(T) : 0.0) + (words ? (double)B * n0 * L.W64 * 8 : 0.0));
+    hipLaunchKernelGGL(gt_pair_kernel<T>, dim3(cdiv(n1 + pad, 64), cdiv(n0 + pad, GT_ROWS), B), dim3(256), 0, st, lines0, lines1,
+                       (const T*)proj0, (const T*)proj1, (const T*)ang0, (const T*)ang1, (const T*)angp0, (const T*)angp1, n0, n1,
+                       d_count0, d_count1, (T)thres_reprojected, (T)thres_angdiff, min_overlap_ratio, pad, d_assign, d_match_dir,
+                       (T*)d_overlap_dir, words);
+    LT_LAUNCH_CHECK();
+  }
+  if (list) {
+    ProfScope ps(h, st, "gt_list", 0, (double)B * n0 * L.W64 * 8 + (d_lmatches ? 8.0 * B * M : 0.0));
+    hipLaunchKernelGGL(gt_list_kernel, dim3(B), dim3(256), 0, st, (const unsigned long long*)words, n0, L.W64, M, d_lmatches,
+                       d_found ? d_found : (int32_t*)(base + L.o_found));
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int64_t linetr_gt_assign_workspace_bytes(int32_t B, int32_t n0, int32_t n1) {
+  return gt_dims_ok(B, n0, n1) ? gt_layout(B, n0, n1).total : 0;
+}
+
+extern "C" int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void* d_lines0, int32_t n0, const void* d_lines1, int32_t n1,
+                                const double* d_H, int32_t B, const int32_t* d_count0, const int32_t* d_count1,
+                                double thres_reprojected, double thres_angdiff, double min_overlap_ratio, int32_t pad, float* d_assign,
+                                int32_t* d_lmatches, int32_t M, int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir,
+                                void* d_proj0, void* d_proj1, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  if (!gt_dims_ok(B, n0, n1))
+    return fail(LINETR_E_ARG, "gt_assign: bad shape B=%d n0=%d n1=%d (B 1..%d, n 1..%d)", B, n0, n1, VS_MAX_B, VS_MAX_N);
+  if (M < 0) return fail(LINETR_E_ARG, "gt_assign: M = %d", M);
+  if (pad != 0 && pad != 1) return fail(LINETR_E_ARG, "gt_assign: pad %d (0, or 1 for the dustbin row and column)", pad);
+  if (coord_type != LINETR_COORD_F32 && coord_type != LINETR_COORD_F64)
+    return fail(LINETR_E_ARG, "gt_assign: coordinate type %d (0 float32, 1 float64)", coord_type);
+  if (!d_lines0 || !d_lines1 || !d_H || !d_ws) return fail(LINETR_E_ARG, "gt_assign: null pointer");
+  const GtLayout L = gt_layout(B, n0, n1);
+  if (ws_bytes < L.total) return fail(LINETR_E_ARG, "gt_assign: workspace too small (need %lld)", (long long)L.total);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  if (coord_type == LINETR_COORD_F32)
+    return gt_assign_launch<float>(h, st, L, d_lines0, n0, d_lines1, n1, d_H, B, d_count0, d_count1, thres_reprojected, thres_angdiff,
+                                   min_overlap_ratio, pad, d_assign, d_lmatches, M, d_found, d_match_dir, d_overlap_dir, d_proj0,
+                                   d_proj1, (char*)d_ws);
+  return gt_assign_launch<double>(h, st, L, d_lines0, n0, d_lines1, n1, d_H, B, d_count0, d_count1, thres_reprojected, thres_angdiff,
+                                  min_overlap_ratio, pad, d_assign, d_lmatches, M, d_found, d_match_dir, d_overlap_dir, d_proj0,
+                                  d_proj1, (char*)d_ws);
 }

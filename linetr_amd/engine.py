@@ -848,6 +848,67 @@ class Engine:
                 "precision": scores[:, 0], "recall": scores[:, 1], "f1": scores[:, 2],
                 "row_pos": row_pos, "row_neg": row_neg, "match01": match01}
 
+    def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
+                          counts=None, dustbin=True, directions=False, projected=False):
+        """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes
+        per pair with find_line_matches / calculate_line_overlaps in both directions (dataloaders/build_homography_dataset.py:210-237,
+        dataloaders/utils/util_lines.py:67-171).
+
+        lines0 [B, n0, 2, 2] / lines1 [B, n1, 2, 2] (or [n, 2, 2] for one pair; then H is [3, 3]): the sub-lines' end points, torch or
+        NumPy.  float32 on both sides computes as the reference does; float64 on either side selects the float64 instance.  H [B, 3, 3]
+        takes image-0 pixels to image-1 pixels; its inverse is np.linalg.inv(H), as in the builder.  `counts` = (count0 [B], count1 [B]):
+        the valid prefix of each item.  max_matches (M) defaults to the builder's int(max_sublines * 1.5) with max_sublines = n0; an item
+        with more pairs than that makes the call run once more with room for all of them (0: no list, `found` only).  Returns a dict of device tensors:
+        assign [B, n0 + 1, n1 + 1] float32 (`dustbin`; what val_step(assign=...) takes) or [B, n0, n1], lmatches [B, M, 2] int32 with -1
+        behind each list, found [B] int32; with `directions` match_dir [B, 2, n0, n1] uint8 and overlap_dir [B, 2, n0, n1] (direction 1
+        as [i][j]); with `projected` proj0 / proj1.  One host wait (the list sizes)."""
+        def arr(x):
+            return x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        l0, l1 = arr(lines0), arr(lines1)
+        Hm = np.asarray(H.detach().cpu() if isinstance(H, torch.Tensor) else H, dtype=np.float64)
+        if l0.dim() == 3 and l1.dim() == 3 and Hm.shape == (3, 3):
+            l0, l1, Hm = l0[None], l1[None], Hm[None]
+        if l0.dim() != 4 or l1.dim() != 4 or tuple(l0.shape[2:]) != (2, 2) or tuple(l1.shape[2:]) != (2, 2) or l0.shape[0] != l1.shape[0]:
+            raise ValueError(f"line_ground_truth: lines must be [B, n, 2, 2], got {tuple(l0.shape)} and {tuple(l1.shape)}")
+        B, n0, n1 = int(l0.shape[0]), int(l0.shape[1]), int(l1.shape[1])
+        if Hm.shape != (B, 3, 3):
+            raise ValueError(f"line_ground_truth: H must be [{B}, 3, 3], got {Hm.shape}")
+        dt = torch.float64 if torch.float64 in (l0.dtype, l1.dtype) else torch.float32
+        l0, l1 = (t.to(device=self.device, dtype=dt).contiguous() for t in (l0, l1))
+        Hd = torch.from_numpy(np.stack([Hm, np.linalg.inv(Hm)], axis=1).reshape(B, 2, 9)).to(self.device)
+        c0 = c1 = None
+        if counts is not None:
+            c0, c1 = (arr(c).to(device=self.device, dtype=torch.int32).contiguous() for c in counts)
+            if tuple(c0.shape) != (B,) or tuple(c1.shape) != (B,):
+                raise ValueError("line_ground_truth: counts must be two arrays of B entries")
+        M = int(n0 * 1.5) if max_matches is None else int(max_matches)
+        pad = int(bool(dustbin))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+        with torch.cuda.device(self.device):     # a heads-only engine has no handle: the current device is used
+            assign = new((B, n0 + pad, n1 + pad), torch.float32)
+            found = new((B,), torch.int32)
+            mdir = new((B, 2, n0, n1), torch.uint8) if directions else None
+            odir = new((B, 2, n0, n1), dt) if directions else None
+            p0, p1 = (new((B, n0, 2, 2), dt), new((B, n1, 2, 2), dt)) if projected else (None, None)
+            ws = self._workspace("gt_assign", int(self._L.linetr_gt_assign_workspace_bytes(B, n0, n1)))
+            while True:
+                lm = new((B, M, 2), torch.int32)
+                nat.check(self._L.linetr_gt_assign(self._h, int(dt == torch.float64), l0.data_ptr(), n0, l1.data_ptr(), n1, Hd.data_ptr(), B,
+                                                   ptr(c0), ptr(c1), float(thres_reprojected), float(thres_angdiff), float(min_overlap_ratio),
+                                                   pad, assign.data_ptr(), lm.data_ptr(), M, found.data_ptr(), ptr(mdir), ptr(odir), ptr(p0),
+                                                   ptr(p1), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+                most = int(found.max())
+                if most <= M or M == 0:          # (max_matches = 0: no list is wanted, `found` alone)
+                    break
+                M = most                         # once more with room for every pair
+        out = {"assign": assign, "lmatches": lm, "found": found}
+        if directions:
+            out["match_dir"], out["overlap_dir"] = mdir, odir
+        if projected:
+            out["proj0"], out["proj1"] = p0, p1
+        return out
+
     def match_points(self, desc0_cn: torch.Tensor, desc1_cn: torch.Tensor, thr, mutual=True):
         """nn_matcher on [256,n] descriptors; returns (dist [n0,n1] device, match01 [n0] device)."""
         d0, d1 = self._f32(desc0_cn), self._f32(desc1_cn)
