@@ -22,6 +22,8 @@
  *                diagnostics symbol, nothing existing changes, so the version stays.
  *                + linetr_debug_tok_mlp, linetr_debug_cls_pool (the descriptive layer's front-end kernels alone, for the unit
  *                tests): added diagnostics symbols again, the version stays.
+ *                + linetr_debug_match (one chosen path of the matcher alone, for the unit tests): an added diagnostics symbol, the
+ *                version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -615,6 +617,34 @@ int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const LinetrLineRec* 
                           int32_t N, int32_t T, const float* d_cpnt, const float* d_a4, int64_t first_pad, int32_t n_images,
                           const float* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
                           const float* d_desc_dense, float* d_pooled, int32_t* kernel_used, void* stream);
+
+/* Runs ONE path of the descriptor-distance matcher alone, for the unit tests (tests/test_gpu_match_kernels.py: every matcher kernel
+ * against float64 at its tile edges).  Operands as linetr_match; the extra arguments choose what launches:
+ * path:  0 the three launches (pair_dist_kernel, pair_pool_kernel, pair_final_kernel) -- batches, and single pairs beyond the
+ *          one-launch matcher;
+ *        1 pair_match_fused_kernel<false> -- one pair, k0, k1 in 1 .. 4096, n1 <= 1024;
+ *        2 pair_match_fused_kernel<true>  -- the same with one sub-line per key-line on both sides (n0 = k0, n1 = k1);
+ *       -1 what linetr_match takes for these dims (linetr_match, linetr_match_gathered and this entry point run one body).
+ * For path 0 only, each -1 (the matcher's own choice) or 0 / 1:
+ *   seg1_global   image 1's segment table in the workspace, built by pair_seg1_kernel (the matcher: more than 12000 key-lines in
+ *                 an image 1), instead of in the pooling block's LDS;
+ *   cache_dk      the pooling block keeps its 16 pooled rows in LDS (the matcher: up to 896 key-lines in every image 1);
+ *   device_table  the pair table travels through the pinned staging ring into the workspace (the matcher: more than 8 pairs)
+ *                 instead of inside the kernel arguments.
+ * *path_used (may be NULL) receives what launched.  With path = -1 and all six tensors NULL only the choice is reported: nothing
+ * is launched, queued on the stream or dereferenced but dims (the choice is made from the sizes and the device's LDS alone; the
+ * matcher itself falls back to path 0 when no scratch slot is left for the stream, after 256 streams).  A forced path is launched exactly as the matcher launches it: same grid, same
+ * LDS size, same scratch slot.  Refused with LINETR_E_ARG, nothing launched and the outputs untouched: path 1 / 2 with P != 1 or
+ * sizes beyond the one-launch matcher; path 2 with n0 != k0 or n1 != k1; cache_dk = 1 with a k1 above 896; seg1_global = 0 with a
+ * k1 above 12000; device_table = 0 with more than 8 pairs; a switch forced on a path other than 0; bad dims; NULL or misaligned
+ * tensors (descriptors and workspace 16 bytes, the others 4).  A forced path 1 / 2 on a device that refuses the kernel's dynamic
+ * LDS, or on a stream that gets no scratch slot, is LINETR_E_HIP with its own message -- never the three launches instead.
+ * Synchronises `stream` before returning. */
+int linetr_debug_match(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0, const int64_t* off_n0,
+                       const int32_t* d_s2l0, const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1, float thr,
+                       int32_t mutual, float* d_dk, const int64_t* off_dk, int32_t* d_match01, const int64_t* off_k0, void* d_ws,
+                       int64_t ws_bytes, int32_t path, int32_t seg1_global, int32_t cache_dk, int32_t device_table,
+                       int32_t* path_used, void* stream);
 
 #ifdef LINETR_EXPERIMENTS
 /* ---- split-tile ("ST") operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h): experiments build only --------------------

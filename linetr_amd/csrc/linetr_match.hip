@@ -124,18 +124,22 @@ extern "C" int64_t linetr_match_workspace_bytes(int32_t n_pairs, int64_t sum_n0n
   return align_up((int64_t)n_pairs * sizeof(PairDesc), 256) + align_up(sum_n0n1 * 4, 256) + align_up(scratch * 4, 256) + 256;
 }
 
-extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0,
-                                     const int64_t* off_n0, const int32_t* d_s2l0, const int64_t* off_s0,
-                                     const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1,
-                                     const int64_t* off_s1, float thr, int32_t mutual, float* d_dk, const int64_t* off_dk,
-                                     int32_t* d_match01, const int64_t* off_k0, void* d_ws, int64_t ws_bytes, void* stream);
+namespace {
+// What linetr_debug_match forces (-1 everywhere: nothing, the product's own choices).  path: 0 the three launches, 1 / 2
+// pair_match_fused_kernel<false> / <true>; seg1_global, cache_dk, device_table (read on the three-launch path): 0 / 1.
+struct MatchForce { int path = -1, seg1_global = -1, cache_dk = -1, device_table = -1; };
+int match_run(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0, const int64_t* off_n0, const int32_t* d_s2l0,
+              const int64_t* off_s0, const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1, const int64_t* off_s1,
+              float thr, int32_t mutual, float* d_dk, const int64_t* off_dk, int32_t* d_match01, const int64_t* off_k0, void* d_ws,
+              int64_t ws_bytes, void* stream, const MatchForce& force, int32_t* path_used);
+}  // namespace
 
 extern "C" int linetr_match(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0, const int64_t* off_n0,
                             const int32_t* d_s2l0, const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1,
                             float thr, int32_t mutual, float* d_dk, const int64_t* off_dk, int32_t* d_match01,
                             const int64_t* off_k0, void* d_ws, int64_t ws_bytes, void* stream) {
-  return linetr_match_gathered(h, P, dims, d_desc0, off_n0, d_s2l0, nullptr, d_desc1, off_n1, d_s2l1, nullptr, thr, mutual,
-                               d_dk, off_dk, d_match01, off_k0, d_ws, ws_bytes, stream);
+  return match_run(h, P, dims, d_desc0, off_n0, d_s2l0, nullptr, d_desc1, off_n1, d_s2l1, nullptr, thr, mutual, d_dk, off_dk,
+                   d_match01, off_k0, d_ws, ws_bytes, stream, MatchForce{}, nullptr);
 }
 
 extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0,
@@ -143,6 +147,20 @@ extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* 
                                      const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1,
                                      const int64_t* off_s1, float thr, int32_t mutual, float* d_dk, const int64_t* off_dk,
                                      int32_t* d_match01, const int64_t* off_k0, void* d_ws, int64_t ws_bytes, void* stream) {
+  return match_run(h, P, dims, d_desc0, off_n0, d_s2l0, off_s0, d_desc1, off_n1, d_s2l1, off_s1, thr, mutual, d_dk, off_dk,
+                   d_match01, off_k0, d_ws, ws_bytes, stream, MatchForce{}, nullptr);
+}
+
+namespace {
+// The matcher's paths (the numbers are linetr_debug_match's `path` argument, include/linetr_hip.h)
+enum { MATCH_THREE = 0, MATCH_FUSED = 1, MATCH_FUSED_IDENT = 2 };
+
+// The ONE body of the matcher: linetr_match / linetr_match_gathered pass "nothing forced", linetr_debug_match what its caller asks for
+// (already checked there: a forced path never arrives here with sizes it does not serve).
+int match_run(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0, const int64_t* off_n0, const int32_t* d_s2l0,
+              const int64_t* off_s0, const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1, const int64_t* off_s1,
+              float thr, int32_t mutual, float* d_dk, const int64_t* off_dk, int32_t* d_match01, const int64_t* off_k0, void* d_ws,
+              int64_t ws_bytes, void* stream, const MatchForce& force, int32_t* path_used) {
   if (P < 0) return fail(LINETR_E_ARG, "match: bad argument");
   if (P == 0) return LINETR_OK;
   if (!dims || !off_n0 || !off_n1 || !off_dk || !off_k0 || !d_ws) return fail(LINETR_E_ARG, "match: null argument");
@@ -151,7 +169,8 @@ extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* 
   PairTable tab{};
   int slot = -1;
   PairDesc* pd = tab.inl;
-  if (P > PT_INLINE) {
+  const bool device_table = force.device_table < 0 ? P > PT_INLINE : force.device_table != 0;
+  if (device_table) {
     pd = (PairDesc*)staging_ring().acquire((size_t)P * sizeof(PairDesc), &slot);
     if (!pd) return fail(LINETR_E_HIP, "match: pinned staging allocation failed");
   } else {
@@ -192,14 +211,18 @@ extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* 
     // A single pair of ordinary size: ONE launch (pair_match_fused_kernel, lt_match.h).  (r03 built a one-launch form that staged
     // 8 K steps through LDS with a load round trip exposed at each and lost to the three launches, 0.10 vs 0.08 ms; this one keeps
     // whole operand rows in registers -- two exposed round trips in all -- and combines the column argmin with one 64-bit atomicMin.)
-    PairSlot* ps_ = P == 1 ? fused_pair_slot(pd[0].n0, pd[0].k0, pd[0].n1, pd[0].k1, st) : nullptr;
+    PairSlot* ps_ = P == 1 && force.path != MATCH_THREE ? fused_pair_slot(pd[0].n0, pd[0].k0, pd[0].n1, pd[0].k1, st) : nullptr;
+    if (!ps_ && force.path > MATCH_THREE)      // a forced one-launch path never becomes the three launches
+      return fused_pair_lds_ok() ? fail(LINETR_E_HIP, "match: no scratch slot for the one-launch matcher on this stream")
+                                 : fail(LINETR_E_HIP, "match: the device refuses the one-launch matcher's dynamic LDS");
     if (ps_) {    // (no slot / no LDS: the three launches below)
       const PairDesc& d = pd[0];
       const size_t lds = pair_fused_lds(d.n1, d.k1);
       ProfScope ps(h, st, "pair_match_fused", flops, 4.0 * ((double)(d.n0 + d.n1) * D + (double)d.k0 * d.k1));
       // one sub-line per key-line on both sides (known from the counts alone: the maps are onto): Dk = D, columns split over two
       // blocks when a wave would otherwise multiply two tiles
-      const bool ident = d.n0 == d.k0 && d.n1 == d.k1;
+      const bool ident = force.path < 0 ? d.n0 == d.k0 && d.n1 == d.k1 : force.path == MATCH_FUSED_IDENT;
+      if (path_used) *path_used = ident ? MATCH_FUSED_IDENT : MATCH_FUSED;
       const float* a0 = d_desc0 + d.off_n0 * D; const float* a1 = d_desc1 + d.off_n1 * D;
       if (ident) {
         const int n_ct = cdiv(d.n1, 16);
@@ -221,12 +244,12 @@ extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* 
   {
     ProfScope ps(h, st, "pair_match", 0, 0);
     if (max_k1 > 0) {
-      const int seg1_global = max_k1 > PM_MAX_K1;    // the reference has no limit (max_keylines / max_keypoints = -1)
+      const int seg1_global = force.seg1_global < 0 ? max_k1 > PM_MAX_K1 : force.seg1_global;    // the reference has no limit (max_keylines / max_keypoints = -1)
       if (seg1_global) {
         hipLaunchKernelGGL(pair_seg1_kernel, dim3(cdiv(max_n1, 2048), P), dim3(256), 0, st, tab, d_s2l1, d_scr);
         LT_LAUNCH_CHECK();
       }
-      const int cache_dk = max_k1 <= PM_CACHE_K1;
+      const int cache_dk = force.cache_dk < 0 ? max_k1 <= PM_CACHE_K1 : force.cache_dk;
       hipLaunchKernelGGL(pair_pool_kernel, dim3(max_chunks, P), dim3(256), pair_pool_lds(max_k1, seg1_global, cache_dk), st, tab, d_s2l0,
                          d_s2l1, d_dist, d_dk, d_scr, seg1_global, cache_dk);
       LT_LAUNCH_CHECK();
@@ -234,7 +257,60 @@ extern "C" int linetr_match_gathered(LinetrHandle* h, int32_t P, const int32_t* 
     hipLaunchKernelGGL(pair_final_kernel, dim3(P), dim3(256), 0, st, tab, thr, mutual, d_match01, d_scr);
     LT_LAUNCH_CHECK();
   }
+  if (path_used) *path_used = MATCH_THREE;
   return LINETR_OK;   // fully asynchronous: the pair table travels in the kernel arguments or in ring-owned pinned memory
+}
+}  // namespace
+
+extern "C" int linetr_debug_match(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_desc0, const int64_t* off_n0,
+                                  const int32_t* d_s2l0, const float* d_desc1, const int64_t* off_n1, const int32_t* d_s2l1, float thr,
+                                  int32_t mutual, float* d_dk, const int64_t* off_dk, int32_t* d_match01, const int64_t* off_k0,
+                                  void* d_ws, int64_t ws_bytes, int32_t path, int32_t seg1_global, int32_t cache_dk,
+                                  int32_t device_table, int32_t* path_used, void* stream) {
+  if (P < 1 || !dims) return fail(LINETR_E_ARG, "debug_match: at least one pair and its dims expected");
+  if (path < -1 || path > MATCH_FUSED_IDENT) return fail(LINETR_E_ARG, "debug_match: path must be -1 .. 2");
+  for (const int v : {seg1_global, cache_dk, device_table})
+    if (v < -1 || v > 1) return fail(LINETR_E_ARG, "debug_match: seg1_global, cache_dk and device_table must be -1, 0 or 1");
+  if (path != MATCH_THREE && (seg1_global >= 0 || cache_dk >= 0 || device_table >= 0))
+    return fail(LINETR_E_ARG, "debug_match: seg1_global, cache_dk and device_table are forced on path 0 only");
+  int max_k1 = 0;
+  for (int p = 0; p < P; ++p) {
+    const int32_t* d = dims + 4 * p;
+    if (d[0] < 0 || d[1] < 0 || d[2] < 0 || d[3] < 0 || d[1] > d[0] || d[3] > d[2]) return fail(LINETR_E_ARG, "debug_match: bad dims for pair %d", p);
+    max_k1 = std::max(max_k1, d[3]);
+  }
+  if (path > MATCH_THREE) {
+    if (P != 1) return fail(LINETR_E_ARG, "debug_match: the one-launch matcher takes one pair, not %d", P);
+    if (!fused_pair_applies(dims[0], dims[1], dims[2], dims[3]))
+      return fail(LINETR_E_ARG, "debug_match: sizes beyond the one-launch matcher (k0, k1 in 1 .. %d, n1 <= %d)", PF_MAX_K, PF_MAX_N1);
+    if (path == MATCH_FUSED_IDENT && (dims[0] != dims[1] || dims[2] != dims[3]))
+      return fail(LINETR_E_ARG, "debug_match: the identity kernel needs one sub-line per key-line on both sides");
+  }
+  if (cache_dk == 1 && max_k1 > PM_CACHE_K1) return fail(LINETR_E_ARG, "debug_match: %d pooled columns do not fit the LDS row cache (%d)", max_k1, PM_CACHE_K1);
+  if (seg1_global == 0 && max_k1 > PM_MAX_K1) return fail(LINETR_E_ARG, "debug_match: a segment table of %d key-lines does not fit the LDS (%d)", max_k1, PM_MAX_K1);
+  if (device_table == 0 && P > PT_INLINE) return fail(LINETR_E_ARG, "debug_match: %d pairs do not fit the inline pair table (%d)", P, PT_INLINE);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  if (path < 0 && !d_desc0 && !d_desc1 && !d_s2l0 && !d_s2l1 && !d_dk && !d_match01) {
+    // the choice alone, without touching the stream (the matcher additionally needs a scratch slot for the stream: it has one
+    // unless PAIR_SLOTS_MAX streams hold them all or the allocation fails)
+    if (path_used) {
+      const bool fused = P == 1 && fused_pair_applies(dims[0], dims[1], dims[2], dims[3]) && fused_pair_lds_ok();
+      *path_used = !fused ? MATCH_THREE : dims[0] == dims[1] && dims[2] == dims[3] ? MATCH_FUSED_IDENT : MATCH_FUSED;
+    }
+    return LINETR_OK;
+  }
+  if (!d_desc0 || !d_desc1 || !d_s2l0 || !d_s2l1 || !d_dk || !d_match01 || !d_ws || !off_n0 || !off_n1 || !off_dk || !off_k0)
+    return fail(LINETR_E_ARG, "debug_match: null tensor");
+  if (((uintptr_t)d_desc0 | (uintptr_t)d_desc1 | (uintptr_t)d_ws) % 16 ||
+      ((uintptr_t)d_s2l0 | (uintptr_t)d_s2l1 | (uintptr_t)d_dk | (uintptr_t)d_match01) % 4)
+    return fail(LINETR_E_ARG, "debug_match: misaligned tensor (descriptors and workspace 16 bytes, the others 4)");
+  MatchForce force;
+  force.path = path; force.seg1_global = seg1_global; force.cache_dk = cache_dk; force.device_table = device_table;
+  if (int e = match_run(h, P, dims, d_desc0, off_n0, d_s2l0, nullptr, d_desc1, off_n1, d_s2l1, nullptr, thr, mutual, d_dk, off_dk, d_match01,
+                        off_k0, d_ws, ws_bytes, stream, force, path_used)) return e;
+  LT_HIP(hipStreamSynchronize(st));
+  return LINETR_OK;
 }
 
 extern "C" int linetr_match_points(LinetrHandle* h, const float* d0_cn, int32_t n0, const float* d1_cn, int32_t n1,

@@ -2,6 +2,8 @@
 // subline2keyline (models/line_transformer.py:277-282) and nn_matcher_distmat
 // (models/nn_matcher.py:3-31).
 #pragma once
+#include <type_traits>
+
 #include "lt_common.h"
 
 namespace lt {
@@ -366,8 +368,9 @@ __global__ __launch_bounds__(256) void dense_pool_right_kernel(const float* __re
 //   2. the distance rows of its sub-lines against ALL sub-lines of image 1, 16 rows at a time, by exact-fp32 MFMA
 //      (v_mfma_f32_16x16x4_f32) with NO staging: a lane fetches the 64 consecutive channels of its own row that the K order
 //      {64 (lane / 16) + s} assigns to it -- 16 independent dwordx4 loads, all in flight at once, operands straight in
-//      registers -- and two column tiles are multiplied interleaved (the MFMA's 40-cycle dependent latency hides behind the
-//      other accumulator).  Two exposed memory round trips in the whole kernel (the r03 attempt paid one per K step);
+//      registers -- and two column tiles are multiplied interleaved, every tile on two accumulators over alternating K steps
+//      (the MFMA's 40-cycle dependent latency hides behind the other accumulators; the same order for every tile).  Two exposed
+//      memory round trips in the whole kernel (the r03 attempt paid one per K step);
 //   3. t[r][b] = sum_a w0 D[a][b] as the rows arrive, then Dk[r][j] = sum_b t[r][b] w1 -- the summation order of pair_pool_kernel;
 //   4. row argmin per key-line; the column argmin across blocks through ONE 64-bit atomicMin per column on the packed
 //      (distance bits, row) key: distances are >= +0, so the unsigned order of the key is (distance, first row) -- np.argmin's rule;
@@ -470,28 +473,25 @@ __global__ __launch_bounds__(512) void pair_match_fused_kernel(const float* __re
           for (int q = 0; q < 16; ++q) b1[q] = p1[q];
         }
       }
+      // every tile, wherever it lands, is summed the same way: two accumulators over alternating K steps, added at the end in a fixed
+      // order -- so a distance does not depend on the launch geometry (pair_match_fused_kernel<false> on identity maps equals <true>
+      // bit for bit) and a wave with one tile does not wait the MFMA's 40-cycle dependent latency on every step
       f32x4v c0v = {0.f, 0.f, 0.f, 0.f}, c1v = {0.f, 0.f, 0.f, 0.f};
-      if (two) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            c0v = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e], b0[q][e], c0v, 0, 0, 0);
-            c1v = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e], b1[q][e], c1v, 0, 0, 0);
-          }
-      } else {
-        // one tile: two accumulators over alternating K steps (a single chain waits the MFMA's 40-cycle dependent latency on every
-        // step), added at the end in a fixed order
+      f32x4v c0w = {0.f, 0.f, 0.f, 0.f}, c1w = {0.f, 0.f, 0.f, 0.f};
+      auto multiply = [&](auto both) {                              // both: the second tile's MFMAs between the first tile's
 #pragma unroll
         for (int q = 0; q < 16; ++q)
 #pragma unroll
           for (int e = 0; e < 4; e += 2) {
             c0v = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e], b0[q][e], c0v, 0, 0, 0);
-            c1v = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e + 1], b0[q][e + 1], c1v, 0, 0, 0);
+            if constexpr (both) c1v = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e], b1[q][e], c1v, 0, 0, 0);
+            c0w = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e + 1], b0[q][e + 1], c0w, 0, 0, 0);
+            if constexpr (both) c1w = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][e + 1], b1[q][e + 1], c1w, 0, 0, 0);
           }
+      };
+      if (two) multiply(std::true_type{}); else multiply(std::false_type{});
 #pragma unroll
-        for (int i = 0; i < 4; ++i) c0v[i] += c1v[i];
-      }
+      for (int i = 0; i < 4; ++i) { c0v[i] += c0w[i]; c1v[i] += c1w[i]; }
       // C/D layout of the 16 x 16 tile: lane = column lr, registers = rows 4 lg + i
 #pragma unroll
       for (int i = 0; i < 4; ++i) {

@@ -1259,6 +1259,42 @@ class Engine:
                                                 ptr(desc_dense), ptr(out), C.byref(used), self._stream()), self._L)
         return out, used.value
 
+    MATCH_PATHS = ("pair_dist + pair_pool + pair_final", "pair_match_fused<false>", "pair_match_fused<true>")
+
+    def match_path(self, dims) -> int:
+        """Which path (index into MATCH_PATHS) linetr_match takes for pairs of these dims [P, 4] = (n0, k0, n1, k1); nothing is
+        launched."""
+        dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1, 4)
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_match(self._h, len(dims), dims.ctypes.data, None, None, None, None, None, None, 0.0, 0, None, None,
+                                             None, None, None, 0, -1, -1, -1, -1, C.byref(used), self._stream()), self._L)
+        return used.value
+
+    def debug_match(self, path, dims, desc0, off_n0, s2l0, desc1, off_n1, s2l1, thr, mutual, dk, off_dk, m01, off_k0, *,
+                    seg1_global=-1, cache_dk=-1, device_table=-1) -> int:
+        """ONE path of the matcher alone (linetr_debug_match; diagnostics / unit tests).  path: -1 (the matcher's choice) or an index
+        into MATCH_PATHS; seg1_global / cache_dk / device_table: -1 or 0 / 1, path 0 only.  Operands as linetr_match: dims [P, 4],
+        float32 descriptor rows desc0 / desc1 [>= rows, 256], int32 maps, the four host offset arrays [P], and the caller's own
+        outputs dk (float32) and m01 (int32), written at off_dk / off_k0.  Tensors go to the library as they are (a view keeps its
+        offset).  Returns the path that launched."""
+        dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1, 4)
+        P = len(dims)
+        offs = [np.ascontiguousarray(o, dtype=np.int64) for o in (off_n0, off_dk, off_n1, off_k0)]
+        if any(len(o) != P for o in offs):
+            raise ValueError("one offset per pair expected")
+        for t, dt in ((desc0, torch.float32), (desc1, torch.float32), (dk, torch.float32), (s2l0, torch.int32), (s2l1, torch.int32), (m01, torch.int32)):
+            if t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous()):
+                raise ValueError("contiguous float32 / int32 tensors on the engine's device expected")
+        d64 = dims.astype(np.int64)
+        ws = self._workspace("match", self._L.linetr_match_workspace_bytes(P, int((d64[:, 0] * d64[:, 2]).sum()), 0, int((d64[:, 1] + d64[:, 3]).sum())))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_match(self._h, P, dims.ctypes.data, ptr(desc0), offs[0].ctypes.data, ptr(s2l0), ptr(desc1),
+                                             offs[2].ctypes.data, ptr(s2l1), float(thr), int(bool(mutual)), ptr(dk), offs[1].ctypes.data,
+                                             ptr(m01), offs[3].ctypes.data, ws.data_ptr(), ws.numel(), int(path), int(seg1_global),
+                                             int(cache_dk), int(device_table), C.byref(used), self._stream()), self._L)
+        return used.value
+
     # ------------------------------------------------------------------ split-tile operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h)
     def to_st(self, X):
         """fp32 [rows, K] -> ST image (uint8 tensor); K % 32 == 0."""
