@@ -387,6 +387,29 @@ int linetr_val_step(LinetrHandle* h, const float* d_desc0, int32_t n0, const flo
  * loader's int32 [B][M][2] match list whose first entry is not -1 (an index outside 0..n is skipped).  B, n as above, M >= 0 and B * M <= 2^31 * 256, else LINETR_E_ARG.  Asynchronous; `h` may be NULL. */
 int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmatches, int32_t B, int32_t M, int32_t n, float* d_assign, void* stream);
 
+/* ---- gradient of the criterion (section 8(f) "next" row 4: the first link of the backward) ---------------- */
+
+/* descriptor_loss above, differentiated as torch autograd differentiates the reference's (evaluations/criteria.py:59-124,173-192): the
+ * loss scalars of linetr_val_step (bit-identical on the same inputs) AND d loss / d line_desc0, d loss / d line_desc1, from one selection.
+ *   w = upstream / V.  Every surviving anchor row (pos - neg + 1 > 0, which the semi-hard window guarantees) gives dD the weight
+ *   +w / ties at each of the `ties` entries with assign > 0.3 whose D equals its pos (amax's backward splits evenly) and -w at its negative,
+ *   the FIRST index of the smallest semi-hard entry (argmin, then indexing).  An entry that a row anchor and a column anchor both select
+ *   receives the sum.  With D = 2 - 2 <d0[a], d1[c]>:   grad0[a] = -2 sum_c dD[a][c] d1[c],   grad1[c] = -2 sum_a dD[a][c] d0[a].
+ * dD is gathered tile by tile on the chip and never stored; no floating-point atomics, every reduction has a fixed order: two calls give
+ * the same bits.  Four launches and one copy.
+ *   d_desc0 / d_desc1, d_assign   as linetr_val_step reads them (descriptors 16-byte aligned)
+ *   d_upstream         one float32 on the device, the gradient arriving at the loss; NULL = 1
+ *   d_grad0 / d_grad1  [B*n][256] float32, 16-byte aligned, either may be NULL.  EVERY row is written, zeros included; V == 0: all zero
+ *   h_pinned_out       PINNED host block of at least 32 bytes, filled by one asynchronous copy:
+ *       float64 [3] loss, hardest_positive, hardest_negative (NaN when V == 0) | int64 [1] V
+ * Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  n0 != n1, B <= 0, n <= 0 (or beyond 65535 items / 32768
+ * sub-lines), a NULL required pointer, an output block shorter than 32 bytes or a workspace smaller than
+ * linetr_desc_loss_grad_workspace_bytes says: LINETR_E_ARG, nothing launched. */
+int64_t linetr_desc_loss_grad_workspace_bytes(int32_t B, int32_t n);
+int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign,
+                          int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1, void* h_pinned_out, int64_t pinned_bytes,
+                          void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
 
 /* What the reference's dataset builder computes for one image pair with two Python double loops over every pair of sub-lines

@@ -1,12 +1,14 @@
 // liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
 // multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), SuperPoint's key-point branch (lt_keypoints.h), the
-// validation step (lt_valstep.h) and the ground-truth line assignment in front of it (lt_gtassign.h).
+// validation step (lt_valstep.h), the criterion's gradient (lt_lossgrad.h) and the ground-truth line assignment in front of them
+// (lt_gtassign.h).
 #include <algorithm>
 #include <numeric>
 
 #include "lt_handle.h"
 #include "lt_match.h"
 #include "lt_valstep.h"
+#include "lt_lossgrad.h"
 #include "lt_gtassign.h"
 #include "lt_producer.h"
 #include "lt_keypoints.h"
@@ -814,6 +816,85 @@ extern "C" int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmat
     hipLaunchKernelGGL(val_assign_kernel, dim3((unsigned)(((int64_t)B * M + 255) / 256)), dim3(256), 0, st, d_lmatches, B, M, n, d_assign);
     LT_LAUNCH_CHECK();
   }
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// gradient of the criterion (lt_lossgrad.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t LG_OUT_BYTES = 32;   // f64 [3] loss, hardest_positive, hardest_negative | i64 V
+// workspace: device image of the result block | dots | norms (val_dot_kernel writes them) | per-anchor records
+struct LossGradWsLayout { int64_t o_out, o_dots, o_sq0, o_sq1, o_pos, o_neg, o_ties, o_arg, total; };
+LossGradWsLayout loss_grad_ws_layout(int B, int n) {
+  LossGradWsLayout L{};
+  const int64_t rows = align_up((int64_t)B * n * 4, 256);
+  int64_t o = 0;
+  L.o_out = o; o += 256;
+  L.o_dots = o; o += align_up((int64_t)B * n * n * 4, 256);
+  L.o_sq0 = o; o += rows;
+  L.o_sq1 = o; o += rows;
+  L.o_pos = o; o += 2 * rows;
+  L.o_neg = o; o += 2 * rows;
+  L.o_ties = o; o += 2 * rows;
+  L.o_arg = o; o += 2 * rows;
+  L.total = o + 256;
+  return L;
+}
+}  // namespace
+
+extern "C" int64_t linetr_desc_loss_grad_workspace_bytes(int32_t B, int32_t n) {
+  return val_dims_ok(B, n) ? loss_grad_ws_layout(B, n).total : 0;
+}
+
+extern "C" int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign,
+                                     int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1, void* h_pinned_out,
+                                     int64_t pinned_bytes, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  if (n0 != n1) return fail(LINETR_E_ARG, "desc_loss_grad: %d and %d sub-lines (the criterion stacks D on D^T: one n for both sides)", n0, n1);
+  const int n = n0;
+  if (!val_dims_ok(B, n)) return fail(LINETR_E_ARG, "desc_loss_grad: bad shape B=%d n=%d (B 1..%d, n 1..%d)", B, n, VS_MAX_B, VS_MAX_N);
+  if (!d_desc0 || !d_desc1 || !d_assign || !h_pinned_out || !d_ws) return fail(LINETR_E_ARG, "desc_loss_grad: null pointer");
+  const LossGradWsLayout W = loss_grad_ws_layout(B, n);
+  if (pinned_bytes < LG_OUT_BYTES) return fail(LINETR_E_ARG, "desc_loss_grad: output block too small (need %lld)", (long long)LG_OUT_BYTES);
+  if (ws_bytes < W.total) return fail(LINETR_E_ARG, "desc_loss_grad: workspace too small (need %lld)", (long long)W.total);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  char* base = (char*)d_ws;
+  float* dots = (float*)(base + W.o_dots);
+  float* row_pos = (float*)(base + W.o_pos);
+  float* row_neg = (float*)(base + W.o_neg);
+  int* row_ties = (int*)(base + W.o_ties);
+  int* row_arg = (int*)(base + W.o_arg);
+  double* scalars = (double*)(base + W.o_out);
+  long long* count = (long long*)(base + W.o_out + 24);
+  const int tiles = cdiv(n, 64);
+  {
+    ProfScope ps(h, st, "val_dot", 2.0 * B * n * n * D, 4.0 * B * (2.0 * n * D + (double)n * n));
+    hipLaunchKernelGGL(val_dot_kernel, dim3(tiles, tiles, B), dim3(256), 0, st, d_desc0, d_desc1, n, dots, (float*)(base + W.o_sq0),
+                       (float*)(base + W.o_sq1));
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "lossgrad_select", 0, 16.0 * B * n * n);
+    hipLaunchKernelGGL(lg_select_kernel, dim3(cdiv(n, VS_ROWS) + cdiv(n, VS_COLS), B), dim3(256), 0, st, (const float*)dots, d_assign, n,
+                       row_pos, row_neg, row_ties, row_arg);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "lossgrad_loss", 0, 16.0 * B * n);
+    hipLaunchKernelGGL(lg_loss_kernel, dim3(1), dim3(256), 0, st, (const float*)row_pos, (const float*)row_neg, B, n, scalars, count);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_grad0 || d_grad1) {
+    const int sides = (d_grad0 ? 1 : 0) + (d_grad1 ? 1 : 0);
+    ProfScope ps(h, st, "lossgrad_grad", 0, sides * 4.0 * B * (2.0 * n * n + (double)n * D));
+    hipLaunchKernelGGL(lg_grad_kernel, dim3(tiles, 2, B), dim3(256), 0, st, d_desc0, d_desc1, (const float*)dots, d_assign, n,
+                       (const float*)row_pos, (const int*)row_ties, (const int*)row_arg, (const long long*)count, d_upstream, d_grad0, d_grad1);
+    LT_LAUNCH_CHECK();
+  }
+  LT_HIP(hipMemcpyAsync(h_pinned_out, scalars, (size_t)LG_OUT_BYTES, hipMemcpyDeviceToHost, st));
   return LINETR_OK;
 }
 

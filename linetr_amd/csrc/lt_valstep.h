@@ -186,6 +186,47 @@ __global__ __launch_bounds__(256) void val_select_kernel(const float* __restrict
 //   scores f64 [B][3] = precision, recall, f1
 struct ValOut { double* scalars; long long* count; int* counts; double* scores; };
 
+// The loss over the V anchors that kept a negative (rows: all B * 2n anchor rows), by one block of 256 threads: a float64 sum of fixed
+// shape, hardest positive / negative, V.  scalars [3] = loss, hardest_positive, hardest_negative (NaN when V == 0).
+__device__ __forceinline__ void vs_loss_block(const float* __restrict__ row_pos, const float* __restrict__ row_neg, int64_t rows,
+                                              double* __restrict__ scalars, long long* __restrict__ count) {
+  const int tid = threadIdx.x;
+  __shared__ double s_sum[256];
+  __shared__ float s_hp[256], s_hn[256];
+  __shared__ long long s_v[256];
+  double sum = 0.0;
+  float hp = -INFINITY, hn = INFINITY;
+  long long v = 0;
+  for (int64_t i = tid; i < rows; i += 256) {
+    const float neg = row_neg[i];
+    if (neg > 0.f) {
+      const float pos = row_pos[i];
+      sum += (double)fmaxf((pos - neg) + 1.f, 0.f);
+      hp = fmaxf(hp, pos); hn = fminf(hn, neg);
+      ++v;
+    }
+  }
+  s_sum[tid] = sum; s_hp[tid] = hp; s_hn[tid] = hn; s_v[tid] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {                              // a tree of fixed shape
+    if (tid < s) {
+      s_sum[tid] += s_sum[tid + s];
+      s_hp[tid] = fmaxf(s_hp[tid], s_hp[tid + s]);
+      s_hn[tid] = fminf(s_hn[tid], s_hn[tid + s]);
+      s_v[tid] += s_v[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const long long V = s_v[0];
+    const double nan = __builtin_nan("");
+    scalars[0] = V ? s_sum[0] / (double)V : nan;                   // V == 0: the reference has nothing to stack (criteria.py:117)
+    scalars[1] = V ? (double)s_hp[0] : nan;
+    scalars[2] = V ? (double)s_hn[0] : nan;
+    count[0] = V;
+  }
+}
+
 // grid (B + 1).  Blocks 0 .. B-1: match01 of an item (threshold strict, optional mutual check), its counts (evaluate_pr.py:10-22:
 // ground truth assign > 0; FP = rows without a ground truth that have a prediction) and scores (:28-30, float64, eps 1e-5, x 100).
 // Block B: the loss over the V anchors that kept a negative, summed in float64.
@@ -228,41 +269,7 @@ __global__ __launch_bounds__(256) void val_final_kernel(const float* __restrict_
     }
     return;
   }
-  __shared__ double s_sum[256];
-  __shared__ float s_hp[256], s_hn[256];
-  __shared__ long long s_v[256];
-  double sum = 0.0;
-  float hp = -INFINITY, hn = INFINITY;
-  long long v = 0;
-  const int64_t rows = (int64_t)B * 2 * n;
-  for (int64_t i = tid; i < rows; i += 256) {
-    const float neg = row_neg[i];
-    if (neg > 0.f) {
-      const float pos = row_pos[i];
-      sum += (double)fmaxf((pos - neg) + 1.f, 0.f);
-      hp = fmaxf(hp, pos); hn = fminf(hn, neg);
-      ++v;
-    }
-  }
-  s_sum[tid] = sum; s_hp[tid] = hp; s_hn[tid] = hn; s_v[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {                              // a tree of fixed shape
-    if (tid < s) {
-      s_sum[tid] += s_sum[tid + s];
-      s_hp[tid] = fmaxf(s_hp[tid], s_hp[tid + s]);
-      s_hn[tid] = fminf(s_hn[tid], s_hn[tid + s]);
-      s_v[tid] += s_v[tid + s];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const long long V = s_v[0];
-    const double nan = __builtin_nan("");
-    out.scalars[0] = V ? s_sum[0] / (double)V : nan;               // V == 0: the reference has nothing to stack (criteria.py:117)
-    out.scalars[1] = V ? (double)s_hp[0] : nan;
-    out.scalars[2] = V ? (double)s_hn[0] : nan;
-    out.count[0] = V;
-  }
+  vs_loss_block(row_pos, row_neg, (int64_t)B * 2 * n, out.scalars, out.count);
 }
 
 // train.py:176-183: assign [B][n+1][n+1] = 0, then 1 at (lmatches[b][m][0], lmatches[b][m][1]) for every row m whose first entry is

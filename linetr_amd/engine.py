@@ -848,6 +848,51 @@ class Engine:
                 "precision": scores[:, 0], "recall": scores[:, 1], "f1": scores[:, 2],
                 "row_pos": row_pos, "row_neg": row_neg, "match01": match01}
 
+    def loss_step(self, desc0, desc1, assign=None, lmatches=None, upstream=None):
+        """descriptor_loss AND its gradient with respect to both descriptor sets in one native call (linetr_desc_loss_grad): what
+        `loss.backward()` leaves in line_desc0.grad / line_desc1.grad when the reference's criterion (evaluations/criteria.py) is
+        differentiated by torch.  Inputs as val_step takes them; `upstream`: the gradient arriving at the loss, a one-element float32
+        device tensor (read on the device: no host wait for it), default 1.  One host wait.  Returns a dict: loss, hardest_positive,
+        hardest_negative (float; NaN when count == 0), count, and the device tensors grad0 / grad1 in the shape of desc0 / desc1
+        ([B, 256, n] inputs: the transposed view of the [B*n, 256] rows the kernels write); count == 0: both all zero.
+        Like val_step, every call uses the engine's one cached workspace whatever the stream: calls from two streams are safe only
+        because each ends in its host wait before it returns."""
+        if (assign is None) == (lmatches is None):
+            raise ValueError("loss_step: give exactly one of assign / lmatches")
+        d0, B0, n0 = self._desc_rows(desc0.detach())
+        d1, B1, n1 = self._desc_rows(desc1.detach())
+        B = int((assign if assign is not None else lmatches).shape[0])
+        if B <= 0 or any(b is not None and b != B for b in (B0, B1)) or d0.shape[0] % B or d1.shape[0] % B:
+            raise ValueError("loss_step: the descriptors and the ground truth disagree about the batch size")
+        n0, n1 = int(d0.shape[0]) // B, int(d1.shape[0]) // B
+        n = n0
+        if assign is None:
+            assign = self.assign_from_matches(lmatches, n)
+        else:
+            assign = self._f32(assign)
+            if n0 == n1 and tuple(assign.shape) != (B, n + 1, n + 1):
+                raise ValueError(f"loss_step: assign must be [{B}, {n + 1}, {n + 1}], got {tuple(assign.shape)}")
+        if upstream is not None:
+            upstream = self._f32(upstream.detach().reshape(-1))
+            if upstream.numel() != 1:
+                raise ValueError("loss_step: upstream must hold one element")
+        ws = self._workspace("loss_step", max(int(self._L.linetr_desc_loss_grad_workspace_bytes(B, n)), 256))
+        stage, *_gen = self._host_stage(32)
+        grad0, grad1 = torch.empty_like(d0), torch.empty_like(d1)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_desc_loss_grad(self._h, d0.data_ptr(), n0, d1.data_ptr(), n1, assign.data_ptr(), B,
+                                                    upstream.data_ptr() if upstream is not None else None, grad0.data_ptr(),
+                                                    grad1.data_ptr(), stage.data_ptr(), stage.numel(), ws.data_ptr(), ws.numel(),
+                                                    self._stream()), self._L)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        ev.synchronize()
+        host = stage.numpy()
+        scalars = host[:24].view(np.float64)
+        grad0, grad1 = (g.view(B, n, D).transpose(1, 2) if d.dim() == 3 else g for g, d in ((grad0, desc0), (grad1, desc1)))
+        return {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
+                "count": int(host[24:32].view(np.int64)[0]), "grad0": grad0, "grad1": grad1}
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes

@@ -1,6 +1,9 @@
-"""The reference's evaluation names on top of Engine.val_step (linetr_val_step, csrc/lt_valstep.h):
+"""The reference's evaluation names on top of Engine.val_step (linetr_val_step, csrc/lt_valstep.h) and Engine.loss_step
+(linetr_desc_loss_grad, csrc/lt_lossgrad.h):
 
-    descriptor_loss      evaluations/criteria.py:35-192     forward only (no gradient)
+    descriptor_loss      evaluations/criteria.py:35-192     differentiable with respect to line_desc0 / line_desc1: loss.backward()
+                                                            reaches whatever torch graph produced them (the gradient of the
+                                                            criterion is native; no gradient is taken where none is asked for)
     nn_matcher_batches   evaluations/matcher.py:51-102
     Evaluate_PR          evaluations/evaluate_pr.py:3-35
     Result, AverageMeter evaluations/metric.py:7-112        the interface train.py and its logger use; no save_matching_image
@@ -39,23 +42,54 @@ def _on_device(desc0, desc1):
     return desc0, desc1
 
 
+def _require_anchors(res):
+    if res["count"] == 0:     # the reference stacks an empty list (criteria.py:117)
+        raise RuntimeError("descriptor_loss: no anchor has a semi-hard negative (stack expects a non-empty TensorList)")
+
+
+class _DescriptorLossGrad(torch.autograd.Function):
+    """(loss, hardest_positive, hardest_negative) = criterion(desc0, desc1): forward is Engine.loss_step, which also leaves
+    d loss / d desc for an upstream of 1; backward scales them by the gradient arriving at the loss (on the device: nothing is waited
+    for).  The two hardest values are not differentiable.  The gradients live in the graph only: `owner.last` gets the scalars."""
+
+    @staticmethod
+    def forward(ctx, desc0, desc1, assign, owner):
+        res = _engine(desc0.device).loss_step(desc0, desc1, assign=assign)
+        owner.last = {k: res[k] for k in ("loss", "hardest_positive", "hardest_negative", "count")}
+        _require_anchors(res)
+        ctx.save_for_backward(res["grad0"], res["grad1"])
+        loss, hp, hn = (torch.tensor(res[k], dtype=torch.float32, device=desc0.device) for k in ("loss", "hardest_positive", "hardest_negative"))
+        ctx.mark_non_differentiable(hp, hn)
+        return loss, hp, hn
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_hp, _grad_hn):
+        grad0, grad1 = ctx.saved_tensors
+        return (grad_loss * grad0 if ctx.needs_input_grad[0] else None, grad_loss * grad1 if ctx.needs_input_grad[1] else None,
+                None, None)
+
+
 class descriptor_loss(torch.nn.Module):
-    """forward(pred, target) -> (loss, hardest_positive, hardest_negative): 0-dim float32 tensors on the descriptors' device, no grad.
-    pred: 'line_desc0', 'line_desc1' [B, 256, n]; target: 'mat_assign_sublines' [B, n+1, n+1]."""
+    """forward(pred, target) -> (loss, hardest_positive, hardest_negative): 0-dim float32 tensors on the descriptors' device.
+    pred: 'line_desc0', 'line_desc1' [B, 256, n]; target: 'mat_assign_sublines' [B, n+1, n+1].
+    With grad enabled and a descriptor set that requires grad, `loss` carries a grad_fn (Engine.loss_step: value and gradient from one
+    selection); the two hardest values never do (the reference never differentiates them).  Otherwise nothing carries one."""
 
     def __init__(self):
         super().__init__()
         self.margin = 0.5
 
-    @torch.no_grad()
     def forward(self, pred, target):
         desc0, desc1 = pred["line_desc0"], pred["line_desc1"]
-        res = _engine(desc0.device).val_step(desc0, desc1, assign=target["mat_assign_sublines"])
-        self.last = res
-        if res["count"] == 0:     # the reference stacks an empty list (criteria.py:117)
-            raise RuntimeError("descriptor_loss: no anchor has a semi-hard negative (stack expects a non-empty TensorList)")
-        return tuple(torch.tensor(res[k], dtype=torch.float32, device=desc0.device)
-                     for k in ("loss", "hardest_positive", "hardest_negative"))
+        assign = target["mat_assign_sublines"]
+        if torch.is_grad_enabled() and (desc0.requires_grad or desc1.requires_grad):
+            return _DescriptorLossGrad.apply(desc0, desc1, assign, self)
+        with torch.no_grad():
+            res = _engine(desc0.device).val_step(desc0, desc1, assign=assign)
+            self.last = res
+            _require_anchors(res)
+            return tuple(torch.tensor(res[k], dtype=torch.float32, device=desc0.device)
+                         for k in ("loss", "hardest_positive", "hardest_negative"))
 
 
 def _with_dustbins(match01: np.ndarray, n: int) -> np.ndarray:
