@@ -410,6 +410,42 @@ int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, con
                           int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1, void* h_pinned_out, int64_t pinned_bytes,
                           void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- backward of the 1x1 layers and the descriptor head (section 8(f) "next" row 4: the second link) ---------- */
+
+/* A point-wise linear layer, Conv1d(k=1) or Linear, on the UNFOLDED state_dict weight:  Y = act(X W^T + b)  and its backward, as torch
+ * autograd differentiates F.conv1d / F.linear (+ F.relu):
+ *   G' = G, zeroed where d_mask <= 0 (d_mask: the layer's own post-ReLU output, handed in by the caller; NULL: no activation)
+ *   dX [rows][K] = G' W        dW [N][K] = G'^T X        db [N] = column sums of G'
+ * rows = B n positions; activations are row-major [rows][C] with a row stride (the layout linetr_forward* writes).  Every contraction
+ * is exact-fp32 MFMA (no split).  dW / db: the rows are cut into chunks of linetr_linear_backward_chunk_rows() rows (a compile-time
+ * constant), every (chunk, tile) partial goes to the workspace and the chunks are added in ascending order: no floating-point atomics,
+ * every output element written, two calls give the same bits.  Rows beyond `rows` are neither loaded nor stored.
+ *   d_x [rows][ldx]   d_W [N][K]   d_b [N] or NULL   d_y [rows][ldy]   act: 0 none, 1 ReLU
+ *   d_g, d_mask [rows][ldg] (d_mask may be NULL)   d_dx [rows][ldx], d_dW [N][K], d_db [N]: each may be NULL (not computed then)
+ * Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  LINETR_E_ARG, nothing launched: rows < 1 (or beyond
+ * 2^30), N % 64 != 0, K % 32 != 0, N or K beyond 1024, act outside 0 .. 1, a row stride below the width or no multiple of 4 floats, a
+ * pointer that is not 16-byte aligned, a NULL required pointer (d_x, d_W, d_y; d_g, the workspace when d_dW or d_db is asked for),
+ * a workspace smaller than linetr_linear_backward_workspace_bytes says. */
+int32_t linetr_linear_backward_chunk_rows(void);
+int64_t linetr_linear_backward_workspace_bytes(int64_t rows, int32_t N, int32_t K);
+int linetr_linear_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_b, int64_t rows, int32_t N,
+                          int32_t K, int32_t act, float* d_y, int64_t ldy, void* stream);
+int linetr_linear_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg,
+                           const float* d_mask, int64_t rows, int32_t N, int32_t K, float* d_dx, float* d_dW, float* d_db,
+                           void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The descriptor head, models/line_transformer.py:245-246:  line_desc = F.normalize(final_proj(x), p=2, dim=1), on rows:
+ *   y = x W^T + b (256 -> 256)      d = y / max(|y|_2, 1e-12)
+ * and its backward as torch autograd differentiates it:  gy = (g - d (d . g)) / max(|y|, 1e-12) where |y| >= 1e-12, g / 1e-12 elsewhere
+ * (clamp_min passes no gradient to the norm there); then dx = gy W, dW = gy^T x, db = column sums of gy as above.  y is recomputed in
+ * the backward and never stored; gy [rows][256] lives at the start of the workspace.  Three kernels forward + backward of the layer.
+ *   d_x, d_g, d_desc, d_dx [rows][256] contiguous   d_W [256][256]   d_b [256]   d_dx / d_dW / d_db: each may be NULL
+ * Asynchronous; `h` may be NULL.  The refusals of the layer above (d_b is required here). */
+int64_t linetr_head_backward_workspace_bytes(int64_t rows);
+int linetr_head_forward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, int64_t rows, float* d_desc, void* stream);
+int linetr_head_backward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, const float* d_g, int64_t rows,
+                         float* d_dx, float* d_dW, float* d_db, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
 
 /* What the reference's dataset builder computes for one image pair with two Python double loops over every pair of sub-lines

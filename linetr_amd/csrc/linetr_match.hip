@@ -1,7 +1,7 @@
 // liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
 // multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), SuperPoint's key-point branch (lt_keypoints.h), the
-// validation step (lt_valstep.h), the criterion's gradient (lt_lossgrad.h) and the ground-truth line assignment in front of them
-// (lt_gtassign.h).
+// validation step (lt_valstep.h), the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head
+// (lt_linbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
 #include <algorithm>
 #include <numeric>
 
@@ -9,6 +9,7 @@
 #include "lt_match.h"
 #include "lt_valstep.h"
 #include "lt_lossgrad.h"
+#include "lt_linbwd.h"
 #include "lt_gtassign.h"
 #include "lt_producer.h"
 #include "lt_keypoints.h"
@@ -896,6 +897,156 @@ extern "C" int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int3
   }
   LT_HIP(hipMemcpyAsync(h_pinned_out, scalars, (size_t)LG_OUT_BYTES, hipMemcpyDeviceToHost, st));
   return LINETR_OK;
+}
+
+// =============================================================================================
+// backward of a point-wise linear layer and of the descriptor head (lt_linbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t LB_MAX_ROWS = (int64_t)1 << 30;
+// workspace: per-chunk tiles of dW | per-chunk column sums
+struct LinBwdWsLayout { int chunks; int64_t o_dw, o_db, total; };
+LinBwdWsLayout lin_bwd_ws_layout(int64_t rows, int N, int K) {
+  LinBwdWsLayout L{};
+  L.chunks = (int)((rows + LB_CHUNK - 1) / LB_CHUNK);
+  int64_t o = 0;
+  L.o_dw = o; o += align_up((int64_t)L.chunks * N * K * 4, 256);
+  L.o_db = o; o += align_up((int64_t)L.chunks * N * 4, 256);
+  L.total = o + 256;
+  return L;
+}
+bool lin_dims_ok(int64_t rows, int N, int K) {
+  return rows >= 1 && rows <= LB_MAX_ROWS && N > 0 && K > 0 && N % 64 == 0 && K % 32 == 0 && N <= 1024 && K <= 1024;
+}
+bool lin_stride_ok(int64_t ld, int width) { return ld >= width && ld % 4 == 0; }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }     // (NULL passes: an absent optional pointer)
+
+// the argument checks of the layer's backward, for `who`; LINETR_OK: nothing is wrong
+int lin_bwd_check(const char* who, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg, const float* d_mask,
+                  int64_t rows, int N, int K, const float* d_dx, const float* d_dW, const float* d_db, const void* d_ws, int64_t ws_bytes) {
+  if (!lin_dims_ok(rows, N, K))
+    return fail(LINETR_E_ARG, "%s: bad shape rows=%lld N=%d K=%d (rows 1..2^30, N %% 64 == 0, K %% 32 == 0, both <= 1024)", who, (long long)rows, N, K);
+  if (!lin_stride_ok(ldx, K) || !lin_stride_ok(ldg, N))
+    return fail(LINETR_E_ARG, "%s: row strides %lld / %lld (at least the width, multiples of 4 floats)", who, (long long)ldx, (long long)ldg);
+  if (!d_x || !d_W || !d_g) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if ((d_dW || d_db) && !d_ws) return fail(LINETR_E_ARG, "%s: the weight and bias gradients need the workspace", who);
+  if (!aligned16(d_x) || !aligned16(d_W) || !aligned16(d_g) || !aligned16(d_mask) || !aligned16(d_dx) || !aligned16(d_dW) ||
+      !aligned16(d_db) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  if ((d_dW || d_db) && ws_bytes < lin_bwd_ws_layout(rows, N, K).total)
+    return fail(LINETR_E_ARG, "%s: workspace too small (need %lld)", who, (long long)lin_bwd_ws_layout(rows, N, K).total);
+  return LINETR_OK;
+}
+
+// the launches of the layer's backward; the arguments have been checked
+int lin_bwd_launch(LinetrHandle* h, hipStream_t st, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg,
+                   const float* d_mask, int64_t rows, int N, int K, float* d_dx, float* d_dW, float* d_db, void* d_ws) {
+  if (d_dx) {
+    ProfScope ps(h, st, "linbwd_dx", 2.0 * rows * N * K, 4.0 * (rows * (double)(N + K) + (double)N * K));
+    hipLaunchKernelGGL(lb_dx_kernel, dim3((unsigned)((rows + 63) / 64), cdiv(K, 64)), dim3(256), 0, st, d_g, d_mask, ldg, d_W, rows, N, K,
+                       d_dx, ldx);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dW || d_db) {
+    const LinBwdWsLayout L = lin_bwd_ws_layout(rows, N, K);
+    float* dw_part = d_dW ? (float*)((char*)d_ws + L.o_dw) : nullptr;
+    float* db_part = d_db ? (float*)((char*)d_ws + L.o_db) : nullptr;
+    {
+      ProfScope ps(h, st, "linbwd_dw_partial", d_dW ? 2.0 * rows * N * K : 0.0, 4.0 * (rows * (double)(N + K) + (double)L.chunks * N * K));
+      hipLaunchKernelGGL(lb_dw_partial_kernel, dim3(L.chunks, N / 64, d_dW ? cdiv(K, 64) : 1), dim3(256), 0, st, d_g, d_mask, ldg, d_x, ldx,
+                         rows, N, K, dw_part, db_part);
+      LT_LAUNCH_CHECK();
+    }
+    {
+      const int64_t quads = (d_dW ? (int64_t)N * K / 4 : 0) + (d_db ? N / 4 : 0);
+      ProfScope ps(h, st, "linbwd_dw_reduce", 0, 4.0 * (L.chunks + 1) * (double)N * K);
+      hipLaunchKernelGGL(lb_dw_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, (const float*)dw_part,
+                         (const float*)db_part, L.chunks, N, K, d_dW, d_db);
+      LT_LAUNCH_CHECK();
+    }
+  }
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int32_t linetr_linear_backward_chunk_rows(void) { return LB_CHUNK; }
+
+extern "C" int64_t linetr_linear_backward_workspace_bytes(int64_t rows, int32_t N, int32_t K) {
+  return lin_dims_ok(rows, N, K) ? lin_bwd_ws_layout(rows, N, K).total : 0;
+}
+
+extern "C" int linetr_linear_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_b, int64_t rows,
+                                     int32_t N, int32_t K, int32_t act, float* d_y, int64_t ldy, void* stream) {
+  // every refusal comes before the first launch
+  if (!lin_dims_ok(rows, N, K))
+    return fail(LINETR_E_ARG, "linear_forward: bad shape rows=%lld N=%d K=%d (rows 1..2^30, N %% 64 == 0, K %% 32 == 0, both <= 1024)", (long long)rows, N, K);
+  if (act != 0 && act != 1) return fail(LINETR_E_ARG, "linear_forward: act %d (0 none, 1 ReLU)", act);
+  if (!lin_stride_ok(ldx, K) || !lin_stride_ok(ldy, N))
+    return fail(LINETR_E_ARG, "linear_forward: row strides %lld / %lld (at least the width, multiples of 4 floats)", (long long)ldx, (long long)ldy);
+  if (!d_x || !d_W || !d_y) return fail(LINETR_E_ARG, "linear_forward: null pointer");
+  if (!aligned16(d_x) || !aligned16(d_W) || !aligned16(d_b) || !aligned16(d_y)) return fail(LINETR_E_ARG, "linear_forward: every tensor must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "linear_fwd", 2.0 * rows * N * K, 4.0 * (rows * (double)(N + K) + (double)N * K));
+  hipLaunchKernelGGL(lb_fwd_kernel<false>, dim3((unsigned)((rows + 63) / 64), N / 64), dim3(256), 0, st, d_x, ldx, d_W, d_b, rows, N, K, act, d_y,
+                     ldy, (const float*)nullptr, (float*)nullptr);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_linear_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg,
+                                      const float* d_mask, int64_t rows, int32_t N, int32_t K, float* d_dx, float* d_dW, float* d_db,
+                                      void* d_ws, int64_t ws_bytes, void* stream) {
+  const int rc = lin_bwd_check("linear_backward", d_x, ldx, d_W, d_g, ldg, d_mask, rows, N, K, d_dx, d_dW, d_db, d_ws, ws_bytes);
+  if (rc != LINETR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  return lin_bwd_launch(h, st, d_x, ldx, d_W, d_g, ldg, d_mask, rows, N, K, d_dx, d_dW, d_db, d_ws);
+}
+
+namespace {
+int64_t head_gy_bytes(int64_t rows) { return align_up(rows * D * 4, 256); }
+int head_launch(LinetrHandle* h, hipStream_t st, const float* d_x, const float* d_W, const float* d_b, int64_t rows, float* d_desc,
+                const float* d_g, float* d_gy) {
+  ProfScope ps(h, st, d_g ? "head_fwd_bwd_norm" : "head_fwd", 2.0 * rows * D * D, 4.0 * ((d_g ? 4.0 : 2.0) * rows * D + (double)D * D));
+  hipLaunchKernelGGL(lb_fwd_kernel<true>, dim3((unsigned)((rows + LB_HEAD_ROWS - 1) / LB_HEAD_ROWS)), dim3(256), 0, st, d_x, (int64_t)D, d_W, d_b,
+                     rows, D, D, 0, d_desc, (int64_t)D, d_g, d_gy);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int64_t linetr_head_backward_workspace_bytes(int64_t rows) {
+  return lin_dims_ok(rows, D, D) ? head_gy_bytes(rows) + lin_bwd_ws_layout(rows, D, D).total : 0;
+}
+
+extern "C" int linetr_head_forward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, int64_t rows, float* d_desc,
+                                   void* stream) {
+  if (!lin_dims_ok(rows, D, D)) return fail(LINETR_E_ARG, "head_forward: bad rows=%lld (1..2^30)", (long long)rows);
+  if (!d_x || !d_W || !d_b || !d_desc) return fail(LINETR_E_ARG, "head_forward: null pointer");
+  if (!aligned16(d_x) || !aligned16(d_W) || !aligned16(d_b) || !aligned16(d_desc)) return fail(LINETR_E_ARG, "head_forward: every tensor must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  return head_launch(h, st, d_x, d_W, d_b, rows, d_desc, nullptr, nullptr);
+}
+
+extern "C" int linetr_head_backward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, const float* d_g, int64_t rows,
+                                    float* d_dx, float* d_dW, float* d_db, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!lin_dims_ok(rows, D, D)) return fail(LINETR_E_ARG, "head_backward: bad rows=%lld (1..2^30)", (long long)rows);
+  if (!d_x || !d_W || !d_b || !d_g || !d_ws) return fail(LINETR_E_ARG, "head_backward: null pointer");
+  if (!aligned16(d_b)) return fail(LINETR_E_ARG, "head_backward: every tensor must be 16-byte aligned");
+  if (ws_bytes < linetr_head_backward_workspace_bytes(rows))
+    return fail(LINETR_E_ARG, "head_backward: workspace too small (need %lld)", (long long)linetr_head_backward_workspace_bytes(rows));
+  float* gy = (float*)d_ws;
+  char* rest = (char*)d_ws + head_gy_bytes(rows);
+  const int rc = lin_bwd_check("head_backward", d_x, D, d_W, d_g, D, nullptr, rows, D, D, d_dx, d_dW, d_db, rest, ws_bytes - head_gy_bytes(rows));
+  if (rc != LINETR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  const int rl = head_launch(h, st, d_x, d_W, d_b, rows, nullptr, d_g, gy);
+  if (rl != LINETR_OK) return rl;
+  return lin_bwd_launch(h, st, d_x, D, d_W, gy, D, nullptr, rows, D, D, d_dx, d_dW, d_db, rest);
 }
 
 // =============================================================================================

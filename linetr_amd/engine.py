@@ -893,6 +893,114 @@ class Engine:
         return {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
                 "count": int(host[24:32].view(np.int64)[0]), "grad0": grad0, "grad1": grad1}
 
+    # ------------------------------------------------------------------ backward of the 1x1 layers and the descriptor head
+    def _act_rows(self, t: torch.Tensor, width: int, what: str, strided=True):
+        """Activations as the point-wise layers read them: a float32 [rows, width] tensor whose rows are `stride(0)` floats apart
+        (a multiple of 4, 16-byte aligned; anything else is copied).  Accepts [B, width, n] (contiguous, or the transposed view of
+        [B*n, width] rows: no copy then) or the rows themselves.  Returns (rows, B or None, n or None)."""
+        t = t.detach()
+        if t.dim() == 3:
+            if int(t.shape[1]) != width:
+                raise ValueError(f"{what} must be [B, {width}, n] or [rows, {width}], got {tuple(t.shape)}")
+            B, n = int(t.shape[0]), int(t.shape[2])
+            return self._f32(t.transpose(1, 2)).view(B * n, width), B, n
+        if t.dim() != 2 or int(t.shape[1]) != width:
+            raise ValueError(f"{what} must be [B, {width}, n] or [rows, {width}], got {tuple(t.shape)}")
+        ok = (strided and t.device == self.device and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) >= width
+              and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+        return (t if ok else self._f32(t)), None, None
+
+    @staticmethod
+    def _like_input(rows: torch.Tensor, B, n):
+        """[B*n, C] rows back in the shape of a [B, C, n] input (the transposed view), or the rows of a 2-D input"""
+        return rows if B is None else rows.view(B, n, rows.shape[1]).transpose(1, 2)
+
+    def _weight_2d(self, weight: torch.Tensor) -> torch.Tensor:
+        """a Conv1d(k=1) [N, K, 1] or a Linear [N, K] weight as [N, K] float32 on the device"""
+        w = weight.detach()
+        if w.dim() == 3 and int(w.shape[2]) == 1:
+            w = w[:, :, 0]
+        if w.dim() != 2:
+            raise ValueError(f"a point-wise weight must be [N, K] or [N, K, 1], got {tuple(weight.shape)}")
+        return self._f32(w)
+
+    def _stream_workspace(self, tag: str, nbytes: int) -> torch.Tensor:
+        """the cached workspace of `tag` for the current stream (these calls return without a host wait: one per stream)"""
+        return self._workspace(f"{tag}:{torch.cuda.current_stream(self.device).cuda_stream}", max(int(nbytes), 256))
+
+    def linear_forward(self, x, weight, bias=None, relu=False) -> torch.Tensor:
+        """A point-wise linear layer (Conv1d(k=1) / Linear) on the unfolded weight, by exact-fp32 MFMA (linetr_linear_forward):
+        y = act(x W^T + b).  x: [B, K, n] or [rows, K]; weight [N, K] or [N, K, 1]; y in x's layout ([B, N, n] inputs: the transposed
+        view of the [B*n, N] rows the kernel writes).  No host wait."""
+        W = self._weight_2d(weight)
+        N, K = int(W.shape[0]), int(W.shape[1])
+        xr, B, n = self._act_rows(x, K, "x")
+        b = self._f32(bias.detach().reshape(-1)) if bias is not None else None
+        if b is not None and b.numel() != N:
+            raise ValueError(f"bias must hold {N} elements")
+        y = torch.empty((xr.shape[0], N), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_linear_forward(self._h, xr.data_ptr(), xr.stride(0), W.data_ptr(), b.data_ptr() if b is not None else None,
+                                                    int(xr.shape[0]), N, K, int(bool(relu)), y.data_ptr(), N, self._stream()), self._L)
+        return self._like_input(y, B, n)
+
+    def linear_backward(self, x, weight, grad_out, mask=None, need=(True, True, True)):
+        """The layer's backward (linetr_linear_backward): (dx, dW, db) for the gradient `grad_out` arriving at y = act(x W^T + b);
+        `mask`: the layer's own post-ReLU output (the gradient passes where it is > 0), None for no activation.  dx in x's layout, dW in
+        the weight's shape, db [N]; `need` = which of the three to compute (the others are None).  Deterministic; no host wait."""
+        W = self._weight_2d(weight)
+        N, K = int(W.shape[0]), int(W.shape[1])
+        xr, B, n = self._act_rows(x, K, "x")
+        g, _, _ = self._act_rows(grad_out, N, "grad_out", strided=mask is None)
+        m = self._act_rows(mask, N, "mask", strided=False)[0] if mask is not None else None
+        rows = int(xr.shape[0])
+        if int(g.shape[0]) != rows or (m is not None and int(m.shape[0]) != rows):
+            raise ValueError("linear_backward: x, grad_out and mask disagree about the number of rows")
+        dx = torch.empty_strided((rows, K), (xr.stride(0), 1), dtype=torch.float32, device=self.device) if need[0] else None
+        dW = torch.empty((N, K), dtype=torch.float32, device=self.device) if need[1] else None
+        db = torch.empty((N,), dtype=torch.float32, device=self.device) if need[2] else None
+        ws = self._stream_workspace("linear_bwd", self._L.linetr_linear_backward_workspace_bytes(rows, N, K))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_linear_backward(self._h, xr.data_ptr(), xr.stride(0), W.data_ptr(), g.data_ptr(), g.stride(0), ptr(m), rows,
+                                                     N, K, ptr(dx), ptr(dW), ptr(db), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return (self._like_input(dx, B, n) if dx is not None else None, dW.view(weight.shape) if dW is not None else None, db)
+
+    def _head_args(self, x, weight, bias):
+        W = self._weight_2d(weight)
+        if tuple(W.shape) != (D, D) or bias is None or bias.numel() != D:
+            raise ValueError(f"the descriptor head is final_proj: a [{D}, {D}] weight and a [{D}] bias")
+        xr, B, n = self._act_rows(x, D, "x", strided=False)
+        return xr, W, self._f32(bias.detach().reshape(-1)), B, n
+
+    def head_forward(self, x, weight, bias) -> torch.Tensor:
+        """The descriptor head (models/line_transformer.py:245-246; linetr_head_forward): line_desc = F.normalize(final_proj(x), dim=1),
+        one kernel.  x: the pre-head features [B, 256, n] or [rows, 256]; line_desc in x's layout.  No host wait."""
+        xr, W, b, B, n = self._head_args(x, weight, bias)
+        desc = torch.empty_like(xr)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_head_forward(self._h, xr.data_ptr(), W.data_ptr(), b.data_ptr(), int(xr.shape[0]), desc.data_ptr(),
+                                                  self._stream()), self._L)
+        return self._like_input(desc, B, n)
+
+    def head_backward(self, x, weight, bias, grad_desc, need=(True, True, True)):
+        """The head's backward (linetr_head_backward): (dx, dW, db) for the gradient `grad_desc` arriving at line_desc, as torch autograd
+        differentiates F.normalize(final_proj(x)).  Shapes and `need` as linear_backward.  Deterministic; no host wait."""
+        xr, W, b, B, n = self._head_args(x, weight, bias)
+        g = self._act_rows(grad_desc, D, "grad_desc", strided=False)[0]
+        rows = int(xr.shape[0])
+        if int(g.shape[0]) != rows:
+            raise ValueError("head_backward: x and grad_desc disagree about the number of rows")
+        dx = torch.empty_like(xr) if need[0] else None
+        dW = torch.empty((D, D), dtype=torch.float32, device=self.device) if need[1] else None
+        db = torch.empty((D,), dtype=torch.float32, device=self.device) if need[2] else None
+        ws = self._stream_workspace("head_bwd", self._L.linetr_head_backward_workspace_bytes(rows))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_head_backward(self._h, xr.data_ptr(), W.data_ptr(), b.data_ptr(), g.data_ptr(), rows, ptr(dx), ptr(dW),
+                                                   ptr(db), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return (self._like_input(dx, B, n) if dx is not None else None, dW.view(weight.shape) if dW is not None else None, db)
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes
