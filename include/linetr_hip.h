@@ -24,6 +24,8 @@
  *                tests): added diagnostics symbols again, the version stays.
  *                + linetr_debug_match (one chosen path of the matcher alone, for the unit tests): an added diagnostics symbol, the
  *                version stays.
+ *                + linetr_debug_bn_train, linetr_debug_bn_train_workspace_bytes (the train-mode BatchNorm kernels alone, for the
+ *                unit tests): added diagnostics symbols, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -653,6 +655,32 @@ int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32_t layer, c
 int linetr_debug_tok_mlp(LinetrHandle* h, int32_t variant, const float* d_pnt, const float* d_score, int64_t rows_word,
                          const float* d_sublines, const float* d_resp, const float* d_angle, int64_t rows_line,
                          float* d_out_word, float* d_out_line, int32_t max_blocks, int32_t* variant_used, void* stream);
+
+/* Runs BatchNorm1d in TRAINING mode + ReLU (csrc/lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_relu_kernel behind
+ * their host function bn_train_layer) alone, for the unit tests (tests/test_gpu_bn_train.py: against float64 at the channel widths,
+ * row strides and row counts where the kernels' loops and chunks end).  `h` must be a training-mode handle (bn_batch_stats = 1).
+ * which = -1: ONE free-standing layer, the handle's weights are not read.  d_z [rows][ld] holds C <= ld pre-activations per row and
+ *          is transformed in place to max((z - mean) / sqrt(var + 1e-5) gamma + beta, 0), mean and the BIASED variance taken per
+ *          channel over all rows; d_gamma, d_beta [C]; d_running [2 C] = mean | var is moved in place to (1 - momentum) old +
+ *          momentum (mean | var rows / (rows - 1)) (rows = 1: the variance, 0, as it is); d_batch [2 C] (may be NULL) receives mean |
+ *          biased variance; d_affine [2 C] (may be NULL) receives alpha = gamma / sqrt(var + 1e-5) | beta' = beta - mean alpha, the
+ *          float32 constants the transform multiplies and adds.  d_in0 / d_in1 / d_in2 / d_out are not read.
+ * which = 0 / 1: the word / line positional encoder's four conv + BatchNorm(batch) + ReLU layers on the handle's unfolded weights,
+ *          as linetr_forward_train runs them.  First-layer inputs as linetr_debug_tok_mlp's: d_in0 = d_pnt [rows][2], d_in1 =
+ *          d_score [rows] (word; d_in2 not read) or d_in0 = d_sublines [rows][2][2], d_in1 = d_resp [rows], d_in2 = d_angle
+ *          [rows][2] (line).  d_out [rows][keyline_encoder[3]]; d_running / d_batch (may be NULL) hold the encoder's four layers
+ *          packed as linetr_forward_train packs them (2 (e0 + e1 + e2 + e3) floats).  d_z, C, ld, d_gamma, d_beta, d_affine are
+ *          not read.
+ * *nb_used (may be NULL) receives the number of row chunks the statistics were summed in: min(512, max(1, rows / 64)).
+ * d_ws: linetr_debug_bn_train_workspace_bytes(h, which, rows) bytes, 256-byte aligned (-1 on bad arguments).
+ * Refused with LINETR_E_ARG, nothing launched: an inference handle; C outside 4 .. 512 or no multiple of 4; ld < C or no multiple
+ * of 4; d_z / d_out not 16-byte aligned; rows < 0; momentum outside [0, 1]; NULL tensors.  A workspace that is too small is
+ * LINETR_E_WORKSPACE.  rows = 0 launches nothing.  Synchronises `stream` before returning. */
+int64_t linetr_debug_bn_train_workspace_bytes(const LinetrHandle* h, int32_t which, int64_t rows);
+int linetr_debug_bn_train(LinetrHandle* h, int32_t which, float* d_z, int64_t rows, int32_t C, int32_t ld, const float* d_gamma,
+                          const float* d_beta, const float* d_in0, const float* d_in1, const float* d_in2, float* d_out,
+                          float momentum, float* d_running, float* d_batch, float* d_affine, int32_t* nb_used, void* d_ws,
+                          int64_t ws_bytes, void* stream);
 
 /* Runs ONE CLS-row pooling kernel of the descriptive layer (models/line_attention.py:6-75 restricted to query row 0) alone, for
  * the unit tests (tests/test_gpu_front.py).  d_pooled [N][4][544] = per sub-line and head [sum_j p_j desc_j (256) | sum_j p_j

@@ -157,6 +157,9 @@ def lib(path=None):
     L.linetr_debug_gemm_case.argtypes = [vp, C.POINTER(GemmCase), vp, vp]
     L.linetr_debug_sig_attention.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]
     L.linetr_debug_tok_mlp.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, vp, vp]
+    L.linetr_debug_bn_train_workspace_bytes.argtypes = [vp, i32, i64]
+    L.linetr_debug_bn_train_workspace_bytes.restype = i64
+    L.linetr_debug_bn_train.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp]
     L.linetr_debug_cls_pool.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.linetr_debug_match.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
     if hasattr(L, "linetr_debug_gemm_st"):      # experiments build only (include/linetr_hip.h, LINETR_EXPERIMENTS)
@@ -190,7 +193,7 @@ EXPORTS = ["linetr_abi_version", "linetr_last_error", "linetr_create", "linetr_d
            "linetr_prefilter_batch", "linetr_prefilter_tied_images", "linetr_pack_lines", "linetr_tokenize_workspace_bytes", "linetr_tokenize", "linetr_forward_workspace_bytes",
            "linetr_forward", "linetr_bn_stats_floats", "linetr_forward_train_workspace_bytes", "linetr_forward_train", "linetr_describe_workspace_bytes", "linetr_describe", "linetr_describe_submit", "linetr_describe_join", "linetr_pipeline_max_slots", "linetr_match_workspace_bytes", "linetr_match", "linetr_match_gathered", "linetr_match_points",
            "linetr_match_distmat", "linetr_match_distmat_workspace_bytes", "linetr_match_distmat_f64", "linetr_match_distmat_f64_workspace_bytes", "linetr_pair_tail_workspace_bytes", "linetr_pair_tail_output_bytes", "linetr_pair_tail", "linetr_val_step_workspace_bytes", "linetr_val_step_output_bytes", "linetr_val_step", "linetr_assign_from_matches", "linetr_desc_loss_grad_workspace_bytes", "linetr_desc_loss_grad", "linetr_linear_backward_chunk_rows", "linetr_linear_backward_workspace_bytes", "linetr_linear_forward", "linetr_linear_backward", "linetr_head_backward_workspace_bytes", "linetr_head_forward", "linetr_head_backward", "linetr_gt_assign_workspace_bytes", "linetr_gt_assign", "linetr_superpoint_heads", "linetr_superpoint_keypoints_workspace_bytes", "linetr_superpoint_keypoints",
-           "linetr_point_descriptors_workspace_bytes", "linetr_point_descriptors", "linetr_set_precision", "linetr_get_precision", "linetr_debug_posenc", "linetr_debug_gemm", "linetr_debug_gemm_case", "linetr_debug_sig_attention", "linetr_debug_tok_mlp", "linetr_debug_cls_pool", "linetr_debug_match", "linetr_allgather_desc", "linetr_set_allgather_fn", "linetr_pack_slab", "linetr_sample_descriptors_workspace_bytes",
+           "linetr_point_descriptors_workspace_bytes", "linetr_point_descriptors", "linetr_set_precision", "linetr_get_precision", "linetr_debug_posenc", "linetr_debug_gemm", "linetr_debug_gemm_case", "linetr_debug_sig_attention", "linetr_debug_tok_mlp", "linetr_debug_bn_train_workspace_bytes", "linetr_debug_bn_train", "linetr_debug_cls_pool", "linetr_debug_match", "linetr_allgather_desc", "linetr_set_allgather_fn", "linetr_pack_slab", "linetr_sample_descriptors_workspace_bytes",
            "linetr_sample_descriptors", "linetr_pool_distmat_workspace_bytes", "linetr_pool_distmat", "linetr_pool_distmat_dense_workspace_bytes", "linetr_pool_distmat_dense", "linetr_set_profiling", "linetr_get_profile"]
 
 

@@ -1295,6 +1295,74 @@ extern "C" int linetr_debug_tok_mlp(LinetrHandle* h, int32_t variant, const floa
   return e;
 }
 
+namespace {
+// linetr_debug_bn_train's workspace: [the chain's act[0 .. 2] |] partial | affine
+constexpr int64_t BN_PARTIAL_BYTES = (int64_t)BN_MAX_BLOCKS * 2 * BN_MAX_CHANNELS * 8, BN_AFFINE_BYTES = 2 * BN_MAX_CHANNELS * 4;
+struct BnDebugWs { float* act[3]; double* partial; float* affine; int64_t total; };
+BnDebugWs bn_debug_layout(const LinetrHandle* h, int which, int64_t rows, char* base) {
+  BnDebugWs w;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
+  for (int i = 0; i < 3; ++i) w.act[i] = (float*)take(which < 0 ? 0 : std::max<int64_t>(rows, 0) * h->cfg.enc_channels[i] * 4);
+  w.partial = (double*)take(BN_PARTIAL_BYTES);
+  w.affine = (float*)take(BN_AFFINE_BYTES);
+  w.total = off;
+  return w;
+}
+}  // namespace
+
+extern "C" int64_t linetr_debug_bn_train_workspace_bytes(const LinetrHandle* h, int32_t which, int64_t rows) {
+  if (!h || which < -1 || which > 1 || rows < 0 || rows > INT32_MAX / 8) return -1;
+  return bn_debug_layout(h, which, rows, nullptr).total;
+}
+
+extern "C" int linetr_debug_bn_train(LinetrHandle* h, int32_t which, float* d_z, int64_t rows, int32_t C, int32_t ld,
+                                     const float* d_gamma, const float* d_beta, const float* d_in0, const float* d_in1,
+                                     const float* d_in2, float* d_out, float momentum, float* d_running, float* d_batch,
+                                     float* d_affine, int32_t* nb_used, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!h) return fail(LINETR_E_ARG, "debug_bn_train: null handle");
+  if (!h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_bn_train: the handle was created for inference (bn_batch_stats = 0)");
+  if (which < -1 || which > 1) return fail(LINETR_E_ARG, "debug_bn_train: which must be -1 (one layer), 0 (word encoder) or 1 (line encoder)");
+  if (rows < 0 || rows > INT32_MAX / 8) return fail(LINETR_E_ARG, "debug_bn_train: row count must be 0 .. %d", INT32_MAX / 8);
+  if (!(momentum >= 0.f && momentum <= 1.f)) return fail(LINETR_E_ARG, "debug_bn_train: momentum out of [0, 1]");
+  if (nb_used) *nb_used = 0;
+  if (which < 0) {
+    // (bn_train_layer has these checks too; here they come before anything else is looked at)
+    if (C > BN_MAX_CHANNELS || C < 4 || C % 4) return fail(LINETR_E_ARG, "debug_bn_train: %d channels (4 .. %d, multiples of 4)", C, BN_MAX_CHANNELS);
+    if (ld < C || ld % 4) return fail(LINETR_E_ARG, "debug_bn_train: row stride %d (at least the %d channels, a multiple of 4)", ld, C);
+    if (!d_z || !d_gamma || !d_beta || !d_running) return fail(LINETR_E_ARG, "debug_bn_train: null tensor");
+    if ((uintptr_t)d_z % 16 || ((uintptr_t)d_gamma | (uintptr_t)d_beta | (uintptr_t)d_running | (uintptr_t)d_batch | (uintptr_t)d_affine) % 4)
+      return fail(LINETR_E_ARG, "debug_bn_train: z must be 16-byte aligned, the vectors 4-byte aligned");
+  } else {
+    if (!d_in0 || !d_in1 || (which == ENC_LINE && !d_in2) || !d_out || !d_running) return fail(LINETR_E_ARG, "debug_bn_train: null tensor");
+    if (((uintptr_t)d_in0 | (uintptr_t)d_in1 | (uintptr_t)d_in2 | (uintptr_t)d_running | (uintptr_t)d_batch) % 4 || (uintptr_t)d_out % 16)
+      return fail(LINETR_E_ARG, "debug_bn_train: the output must be 16-byte aligned, the other tensors 4-byte aligned");
+  }
+  if (!d_ws || (uintptr_t)d_ws % 256) return fail(LINETR_E_ARG, "debug_bn_train: the workspace must be 256-byte aligned");
+  const BnDebugWs w = bn_debug_layout(h, which, rows, (char*)d_ws);
+  if (ws_bytes < w.total) return fail(LINETR_E_WORKSPACE, "debug_bn_train: workspace too small (%lld < %lld bytes)", (long long)ws_bytes, (long long)w.total);
+  if (rows == 0) return LINETR_OK;
+  LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  BnTrain bt;
+  bt.running = d_running; bt.batch = d_batch; bt.momentum = momentum; bt.partial = w.partial; bt.affine = w.affine;
+  int e, nb = 0;
+  if (which < 0) {
+    e = bn_train_layer(st, bt, d_z, rows, C, ld, d_gamma, d_beta, 0, &nb);
+    if (!e && d_affine && hipMemcpyAsync(d_affine, w.affine, (size_t)2 * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      e = fail(LINETR_E_HIP, "debug_bn_train: copying alpha | beta' failed");
+  } else {
+    float* act[4] = {w.act[0], w.act[1], w.act[2], d_out};
+    const EncCall c{which, d_in0, d_in1, d_in2, rows, act};
+    int64_t off = 0;
+    e = pos_encoder_bn(h, st, c, bt, off);
+    nb = bn_row_chunks(rows);
+  }
+  if (nb_used) *nb_used = nb;
+  (void)hipStreamSynchronize(st);
+  return e;
+}
+
 extern "C" int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const LinetrLineRec* d_recs, int32_t K, const int32_t* d_sub2line,
                                      int32_t N, int32_t T, const float* d_cpnt, const float* d_a4, int64_t first_pad, int32_t n_images,
                                      const float* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,

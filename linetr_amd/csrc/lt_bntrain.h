@@ -27,27 +27,33 @@ struct BnTrain {
   float* affine = nullptr;      // [2 * 512] scratch: alpha | beta'
 };
 
-// z [rows][C] (row stride ld), C in {32, 64, 128, 256, 512}; partial [gridDim.x][2 C]
+// z [rows][C] (row stride ld), any C <= BN_MAX_CHANNELS; partial [gridDim.x][2 C].  A block whose chunk lies behind the last row
+// writes zero partials.
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ z, int64_t rows, int C, int ld,
                                                          double* __restrict__ partial) {
   __shared__ double red[2][256];
   const int tid = threadIdx.x;
   const int cw = C < 256 ? C : 256;            // channels side by side in a block pass
   const int rp = 256 / cw;                     // rows in parallel
-  const int r_in = tid / cw, c_in = tid % cw;
+  const int r_in = tid / cw, c_in = tid % cw;  // (256 % cw != 0: the threads with r_in == rp own nothing)
   const int64_t chunk = (rows + gridDim.x - 1) / gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
-  for (int c = c_in; c < C; c += 256) {
+  // the trip count is the block's, not the thread's (C = 260: lanes 0-3 alone have a second channel), so that every thread reaches
+  // the barriers; loads and stores are guarded instead
+  for (int c0 = 0; c0 < C; c0 += 256) {
+    const int c = c0 + c_in;
+    const bool owns = c < C && r_in < rp;
     double s = 0.0, q = 0.0;
-    for (int64_t r = r0 + r_in; r < r1; r += rp) {
-      const double v = (double)z[r * ld + c];
-      s += v;
-      q += v * v;
-    }
+    if (owns)
+      for (int64_t r = r0 + r_in; r < r1; r += rp) {
+        const double v = (double)z[r * ld + c];
+        s += v;
+        q += v * v;
+      }
     red[0][tid] = s;
     red[1][tid] = q;
     __syncthreads();
-    if (r_in == 0) {
+    if (owns && r_in == 0) {
       for (int k = 1; k < rp; ++k) { s += red[0][k * cw + c_in]; q += red[1][k * cw + c_in]; }   // fixed order
       partial[(int64_t)blockIdx.x * 2 * C + c] = s;
       partial[(int64_t)blockIdx.x * 2 * C + C + c] = q;
@@ -99,12 +105,22 @@ __global__ __launch_bounds__(256) void bn_apply_relu_kernel(float* __restrict__ 
   *reinterpret_cast<f32x4*>(z + r * ld + c) = v;
 }
 
+// row chunks (blocks of bn_partial_kernel) for `rows` rows: one per 64 rows, at most BN_MAX_BLOCKS
+inline int bn_row_chunks(int64_t rows) { return (int)std::min<int64_t>(BN_MAX_BLOCKS, std::max<int64_t>(1, rows / 64)); }
+
 // BatchNorm(train) + ReLU of layer `layer` on z [rows][C]; `off` = float offset of the layer inside the packed statistics
+// `nb_used` (may be null) receives the number of row chunks (linetr_debug_bn_train)
 inline int bn_train_layer(hipStream_t st, const BnTrain& bt, float* z, int64_t rows, int C, int ld, const float* gamma,
-                          const float* beta, int64_t off) {
+                          const float* beta, int64_t off, int* nb_used = nullptr) {
+  if (nb_used) *nb_used = 0;
   if (rows <= 0) return 0;
-  if (C > BN_MAX_CHANNELS || C % 4) return fail(LINETR_E_ARG, "BatchNorm(train): %d channels (the statistics scratch holds %d, multiples of 4)", C, BN_MAX_CHANNELS);
-  const int nb = (int)std::min<int64_t>(BN_MAX_BLOCKS, std::max<int64_t>(1, rows / 64));
+  if (C > BN_MAX_CHANNELS || C < 4 || C % 4)
+    return fail(LINETR_E_ARG, "BatchNorm(train): %d channels (the statistics scratch holds 4 .. %d, multiples of 4)", C, BN_MAX_CHANNELS);
+  // bn_apply_relu_kernel moves four channels of a row in one 16-byte access
+  if (ld < C || ld % 4 || (uintptr_t)z % 16)
+    return fail(LINETR_E_ARG, "BatchNorm(train): rows of %d channels need a row stride >= %d that is a multiple of 4 (got %d) and a 16-byte aligned base", C, C, ld);
+  const int nb = bn_row_chunks(rows);
+  if (nb_used) *nb_used = nb;
   hipLaunchKernelGGL(bn_partial_kernel, dim3(nb), dim3(256), 0, st, (const float*)z, rows, C, ld, bt.partial);
   LT_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)bt.partial, nb, C, rows, gamma, beta,

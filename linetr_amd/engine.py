@@ -1375,6 +1375,52 @@ class Engine:
                                                self._stream()), self._L)
         return out_word, out_line, used.value
 
+    def debug_bn_train(self, which, *, z=None, rows=0, channels=0, ld=0, gamma=None, beta=None, word=None, line=None, out=None,
+                       momentum=0.1, running=None, batch=None, affine=None):
+        """BatchNorm(batch statistics) + ReLU alone (linetr_debug_bn_train; diagnostics / unit tests), on an Engine made with
+        bn_batch_stats=True.  which = -1: one free-standing layer on z (a float32 device tensor holding `rows` rows of `channels` channels
+        at row stride `ld`, transformed in place; a view keeps its offset), gamma / beta [C], running [2 C] (in place), batch and
+        affine [2 C] (optional outputs: mean | biased variance, alpha | beta').  which = 0 / 1: the word / line encoder's four
+        layers on word = (pnt, score, rows) / line = (sublines, resp, angle, rows) as debug_tok_mlp takes them; out
+        [>= rows, keyline_encoder[3]] (made here when None); running / batch hold the encoder's four layers packed.
+        Returns (out or z, number of row chunks the statistics were summed in)."""
+        def f32(t, n, what):
+            if t is None:
+                return None
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.numel() < n:
+                raise ValueError(f"{what}: a contiguous float32 tensor of at least {n} elements on the engine's device expected")
+            return t.data_ptr()
+        which = int(which)
+        e = list(self.cfg["keyline_encoder"])
+        ins = [None, None, None]
+        if which < 0:
+            rows, C_, ld = int(rows), int(channels), int(ld)
+            n_stats = 2 * C_
+            pz = f32(z, (rows - 1) * ld + C_ if rows > 0 else 0, "z")
+            res = z
+        else:
+            C_, ld, pz = 0, 0, None
+            n_stats = 2 * sum(e)
+            if which == 0:
+                rows = int(word[2])
+                ins = [f32(word[0], 2 * rows, "pnt"), f32(word[1], rows, "score"), None]
+            else:
+                rows = int(line[3])
+                ins = [f32(line[0], 4 * rows, "sublines"), f32(line[1], rows, "resp"), f32(line[2], 2 * rows, "angle")]
+            if out is None:
+                out = torch.empty((rows, e[3]), dtype=torch.float32, device=self.device)
+            res = out
+        nbytes = self._L.linetr_debug_bn_train_workspace_bytes(self._h, which, rows)
+        if nbytes < 0:
+            raise ValueError("debug_bn_train: which must be -1, 0 or 1 and rows non-negative")
+        ws = self._workspace("bn_debug", nbytes)
+        used = C.c_int32(-1)
+        nat.check(self._L.linetr_debug_bn_train(self._h, which, pz, rows, C_, ld, f32(gamma, C_, "gamma"), f32(beta, C_, "beta"), *ins,
+                                                f32(out, rows * e[3], "out") if which >= 0 else None, float(momentum),
+                                                f32(running, n_stats, "running"), f32(batch, n_stats, "batch"), f32(affine, n_stats, "affine"),
+                                                C.byref(used), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return res, used.value
+
     CLS_POOL_KERNELS = ("cls_pool", "cls_pool_online", "cls_pool_online_reverse", "cls_pool_online_split4")
 
     def cls_pool_kernel(self, N, dense=False) -> int:
