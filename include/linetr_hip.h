@@ -330,7 +330,16 @@ int linetr_pool_distmat(LinetrHandle* h, const float* d_dist, int32_t n0, int32_
  * of the form line_tokenizer writes (models/line_process.py:163-167: one non-zero per column, key-lines in order, rows of
  * float32(1 / num_sublines)) is reduced to its sub-line -> key-line map on the device and pooled like linetr_pool_distmat;
  * any other matrix is multiplied out as given, Dk = (A0 D) A1^T in fp32.  The decision is made on the device: asynchronous on
- * `stream`, no host synchronisation.  `h` may be NULL. */
+ * `stream`, no host synchronisation.  `h` may be NULL.
+ * The verdict: once the call's work on `stream` has completed, the first int32 of d_workspace holds the word the decision was
+ * taken by (0: both matrices were pooled by their maps; anything else: multiplied out as given).  Per matrix, with map[n] the
+ * LAST row that is non-zero in column n (0 for an empty column; NaN counts as non-zero, -0 as zero) and val[n] that entry, the bits are
+ *   1  a column without exactly one non-zero;
+ *   2  rows not in order (map[0] != 0, a step of map other than 0 or +1, map[N-1] != K-1: a key-line without sub-lines);
+ *   4  a val[n] that is not float32(1 / num_sublines) (a float64 quotient rounded once), num_sublines the length of the run of
+ *      equal map values that n belongs to;
+ * the bits of A0 and A1 are ORed.  The word is preset to 1 when k0 > n0 or k1 > n1 (nothing is inspected then) and is NOT written
+ * when an inner dimension is 0 (the result is a zero matrix) or an outer one is (nothing is done). */
 int64_t linetr_pool_distmat_dense_workspace_bytes(int32_t k0, int32_t n0, int32_t k1, int32_t n1);
 int linetr_pool_distmat_dense(LinetrHandle* h, const float* d_dist, int32_t n0, int32_t n1, const float* d_A0, int32_t k0,
                               const float* d_A1, int32_t k1, float* d_dk, void* d_workspace, int64_t workspace_bytes,

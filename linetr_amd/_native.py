@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "liblinetr_hip.so")
 # switches and the kernels that were measured and lost.  Lives OUTSIDE the package; only tools/ and `pytest -m experiments` load it.
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "experiments", "liblinetr_hip_experiments.so")
 
-E_ASSERT = -4
+E_ARG, E_ASSERT, E_WORKSPACE = -1, -4, -5     # LinetrStatus codes that callers tell apart (include/linetr_hip.h)
 
 
 class ModelConfig(C.Structure):

@@ -429,6 +429,7 @@ extern "C" int linetr_match_distmat(LinetrHandle* h, const float* d_dist, int32_
                                     int32_t mutual, int32_t* d_match01, void* d_ws, int64_t ws_bytes, void* stream) {
   if (n0 < 0 || n1 < 0) return fail(LINETR_E_ARG, "match_distmat: bad argument");
   if (n0 == 0) return LINETR_OK;
+  if (!d_match01 || !d_ws || (n1 > 0 && !d_dist)) return fail(LINETR_E_ARG, "match_distmat: null pointer");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
   // scratch: PairDesc | identity maps | Dk copy | argmin ints
@@ -534,7 +535,7 @@ struct DensePoolLayout { int64_t o_map0, o_map1, o_val0, o_val1, o_verdict, o_tm
 DensePoolLayout dense_pool_layout(int k0, int n0, int k1, int n1) {
   DensePoolLayout L{};
   int64_t o = 0;
-  L.o_verdict = o; o += 256;
+  L.o_verdict = o; o += 256;                         // FIRST: the header promises the verdict word at the workspace's offset 0
   L.o_map0 = o; o += align_up((int64_t)std::max(n0, 1) * 4, 256);
   L.o_map1 = o; o += align_up((int64_t)std::max(n1, 1) * 4, 256);
   L.o_val0 = o; o += align_up((int64_t)std::max(n0, 1) * 4, 256);
@@ -569,7 +570,7 @@ extern "C" int linetr_pool_distmat_dense(LinetrHandle* h, const float* d_dist, i
   // K > N cannot be a tokeniser's matrix (every key-line owns at least one sub-line): the verdict starts non-zero and the
   // segmented-mean launch is skipped
   const bool poolable = k0 <= n0 && k1 <= n1;
-  LT_HIP(hipMemsetAsync(verdict, poolable ? 0 : 0x01, 4, st));
+  LT_HIP(hipMemsetD32Async((hipDeviceptr_t)verdict, poolable ? 0 : 1, 1, st));   // the WORD 1 (a byte-wise memset left 0x01010101 for a reader of the verdict)
   if (poolable) {
     int* map0 = (int*)(base + L.o_map0); int* map1 = (int*)(base + L.o_map1);
     float* val0 = (float*)(base + L.o_val0); float* val1 = (float*)(base + L.o_val1);

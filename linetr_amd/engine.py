@@ -631,10 +631,12 @@ class Engine:
                                                   dk.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
         return dk
 
-    def pool_distmat_dense(self, dist: torch.Tensor, mat0: torch.Tensor, mat1: torch.Tensor):
+    def pool_distmat_dense(self, dist: torch.Tensor, mat0: torch.Tensor, mat1: torch.Tensor, return_verdict=False):
         """subline2keyline on the device from the two mat_klines2sublines MATRICES ([K,N] float32): a tokeniser's matrix is
         reduced to its map and pooled by the segmented-mean kernel, any other is multiplied out as given
-        (linetr_pool_distmat_dense; decided on the device, asynchronous).  Returns Dk [k0,k1]."""
+        (linetr_pool_distmat_dense; decided on the device, asynchronous).  Returns Dk [k0,k1]; with return_verdict (tests and
+        diagnosis: it waits for the device) (Dk, verdict): the word the decision was taken by (bits in include/linetr_hip.h; 0 =
+        pooled by the maps), or None where the library writes none (an inner or outer dimension of 0)."""
         d, a0, a1 = self._f32(dist), self._f32(mat0), self._f32(mat1)
         n0, n1 = int(d.shape[0]), int(d.shape[1])
         k0, k1 = int(a0.shape[0]), int(a1.shape[0])
@@ -642,11 +644,13 @@ class Engine:
             raise ValueError(f"subline2keyline: shapes {tuple(a0.shape)} @ {tuple(d.shape)} @ {tuple(a1.shape)}^T do not chain")
         dk = torch.empty((k0, k1), dtype=torch.float32, device=self.device)
         if k0 == 0 or k1 == 0:
-            return dk
+            return (dk, None) if return_verdict else dk
         ws = self._workspace("pool", self._L.linetr_pool_distmat_dense_workspace_bytes(k0, n0, k1, n1))
         with torch.cuda.device(self.device):
             nat.check(self._L.linetr_pool_distmat_dense(self._h, d.data_ptr(), n0, n1, a0.data_ptr(), k0, a1.data_ptr(), k1,
                                                         dk.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        if return_verdict:      # the first int32 of the workspace (stream-ordered read-back; not written for an empty inner dimension)
+            return dk, (int(ws[:4].view(torch.int32).item()) if n0 > 0 and n1 > 0 else None)
         return dk
 
     def match_distmat(self, dist: torch.Tensor, thr, mutual=True):

@@ -137,11 +137,12 @@ def test_strict_compares_on_exact_arithmetic(eng, mutual):
 
 # seeds chosen on the CPU so that the float64 restatement has every margin >= 1e-5 (asserted below)
 EDGE_SEEDS = {(1, 1): 0, (3, 1): 0, (1, 31): 0, (3, 31): 0, (1, 33): 0, (3, 33): 0, (1, 64): 0, (3, 64): 0, (1, 65): 0, (3, 65): 0,
-              (1, 250): 1, (3, 250): 1}
+              (1, 250): 1, (3, 250): 1,
+              # beyond 256: val_final_kernel's `a += 256` loop runs a second time and val_select_kernel gets a fifth column block
+              (1, 256): 0, (2, 256): 0, (1, 257): 0, (2, 257): 0, (1, 300): 0, (2, 300): 0}
 
 
-@pytest.mark.parametrize("n", [1, 31, 33, 64, 65, 250])
-@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("B,n", [(B, n) for n in (1, 31, 33, 64, 65, 250) for B in (1, 3)] + [(B, n) for n in (256, 257, 300) for B in (1, 2)])
 def test_tile_edges(eng, fix, B, n):
     d0, d1, assign = R.clustered_case(EDGE_SEEDS[(B, n)], B, n)
     thr = 0.7
