@@ -457,6 +457,38 @@ int linetr_head_forward(LinetrHandle* h, const float* d_x, const float* d_W, con
 int linetr_head_backward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, const float* d_g, int64_t rows,
                          float* d_dx, float* d_dW, float* d_db, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- neighbour-line attention for training (section 8(f) "next" row 4: the third link) ---------- */
+
+/* The attention of the signature network, models/line_transformer.py:132-136 of the reference, per image and head on the library's
+ * head-major rows (column c = h*64 + d), forward with the softmax statistics and backward as torch autograd differentiates it:
+ *   S = (q / 8) k^T      m = row max of S      l = row sum of exp(S - m)      msg = exp(S - m) v / l      lse = m + logf(l)
+ *   delta[r][h] = sum_d dO[r][h][d] msg[r][h][d]        P = exp(S - lse)        dV = P^T dO        dP = dO V^T
+ *   dS = P * (dP - delta)        dK = dS^T (q / 8)        dQ = (dS K) / 8
+ * q is UNSCALED at this interface: the kernels multiply by 1/8 on load (a power of two, exact), and the forward's message has the bits of
+ * linetr_debug_sig_attention's kernel 0 on pre-scaled q.  Every contraction is exact-fp32 MFMA (no split), natural-log scores and expf.
+ * Flash-style: P is recomputed from q, k and lse and nothing n x n reaches memory; delta [N][4] lives at the start of the workspace.
+ *   d_q, d_k, d_v, d_msg, d_g (= dO), d_dq, d_dk, d_dv   [N][256 of ld*] float32, each with a row stride of its own: q | k | v may be three
+ *                      column blocks of one [N][768] buffer (ldq = ldk = ldv = 768), the layout the forward pass writes
+ *   d_lse              [N][4] float32, contiguous
+ *   d_cu_sub           [n_images + 1] int32 ON THE DEVICE, ascending, d_cu_sub[0] = 0 and d_cu_sub[n_images] = N: one image is one softmax
+ *                      domain.  Images of 0 sub-lines are legal and cost nothing; image sizes are unbounded; n_images <= 4096 (every
+ *                      block finds its image by walking d_cu_sub, so that no size has to be known on the host)
+ *   d_dq, d_dk, d_dv   each may be NULL and is then not computed (what is computed has the same bits either way)
+ * Deterministic: no floating-point atomics; every output row is written exactly once, by the block that owns it, and every sum has a
+ * fixed order (ascending chunks of 32 rows of the other side, each an MFMA chain of its own): two calls give the same bits.  Rows and
+ * columns beyond an image are neither loaded into a sum nor stored.  Forward: one launch; backward: three (delta, dK / dV, dQ).
+ * Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  LINETR_E_ARG, nothing launched: a NULL required pointer
+ * (forward: all of them; backward: d_q, d_k, d_v, d_msg, d_lse, d_g, d_cu_sub, the workspace), a row stride below 256 or no multiple of 4
+ * floats (the stride of a NULL output is not read), a pointer that is not 16-byte aligned, n_images < 1 (or beyond 4096), N < 0 (or beyond 2^31 - 1), a
+ * workspace smaller than linetr_sig_attention_backward_workspace_bytes(N) says. */
+int64_t linetr_sig_attention_backward_workspace_bytes(int64_t N);
+int linetr_sig_attention_forward(LinetrHandle* h, const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, const float* d_v, int64_t ldv,
+                                 const int32_t* d_cu_sub, int32_t n_images, int64_t N, float* d_msg, int64_t ldo, float* d_lse, void* stream);
+int linetr_sig_attention_backward(LinetrHandle* h, const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, const float* d_v, int64_t ldv,
+                                  const float* d_msg, int64_t ldo, const float* d_lse, const float* d_g, int64_t ldg, const int32_t* d_cu_sub,
+                                  int32_t n_images, int64_t N, float* d_dq, int64_t lddq, float* d_dk, int64_t lddk, float* d_dv,
+                                  int64_t lddv, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
 
 /* What the reference's dataset builder computes for one image pair with two Python double loops over every pair of sub-lines

@@ -139,6 +139,11 @@ def lib(path=None):
     L.linetr_head_backward_workspace_bytes.restype = i64
     L.linetr_head_forward.argtypes = [vp, vp, vp, vp, i64, vp, vp]
     L.linetr_head_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.linetr_sig_attention_backward_workspace_bytes.argtypes = [i64]
+    L.linetr_sig_attention_backward_workspace_bytes.restype = i64
+    L.linetr_sig_attention_forward.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, i64, vp, vp]
+    L.linetr_sig_attention_backward.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i64, vp, i64, vp, i64, vp, i64,
+                                                vp, i64, vp]
     L.linetr_gt_assign_workspace_bytes.argtypes = [i32, i32, i32]
     L.linetr_gt_assign_workspace_bytes.restype = i64
     L.linetr_gt_assign.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp,
@@ -192,7 +197,7 @@ def lib(path=None):
 EXPORTS = ["linetr_abi_version", "linetr_last_error", "linetr_create", "linetr_destroy", "linetr_prefilter",
            "linetr_prefilter_batch", "linetr_prefilter_tied_images", "linetr_pack_lines", "linetr_tokenize_workspace_bytes", "linetr_tokenize", "linetr_forward_workspace_bytes",
            "linetr_forward", "linetr_bn_stats_floats", "linetr_forward_train_workspace_bytes", "linetr_forward_train", "linetr_describe_workspace_bytes", "linetr_describe", "linetr_describe_submit", "linetr_describe_join", "linetr_pipeline_max_slots", "linetr_match_workspace_bytes", "linetr_match", "linetr_match_gathered", "linetr_match_points",
-           "linetr_match_distmat", "linetr_match_distmat_workspace_bytes", "linetr_match_distmat_f64", "linetr_match_distmat_f64_workspace_bytes", "linetr_pair_tail_workspace_bytes", "linetr_pair_tail_output_bytes", "linetr_pair_tail", "linetr_val_step_workspace_bytes", "linetr_val_step_output_bytes", "linetr_val_step", "linetr_assign_from_matches", "linetr_desc_loss_grad_workspace_bytes", "linetr_desc_loss_grad", "linetr_linear_backward_chunk_rows", "linetr_linear_backward_workspace_bytes", "linetr_linear_forward", "linetr_linear_backward", "linetr_head_backward_workspace_bytes", "linetr_head_forward", "linetr_head_backward", "linetr_gt_assign_workspace_bytes", "linetr_gt_assign", "linetr_superpoint_heads", "linetr_superpoint_keypoints_workspace_bytes", "linetr_superpoint_keypoints",
+           "linetr_match_distmat", "linetr_match_distmat_workspace_bytes", "linetr_match_distmat_f64", "linetr_match_distmat_f64_workspace_bytes", "linetr_pair_tail_workspace_bytes", "linetr_pair_tail_output_bytes", "linetr_pair_tail", "linetr_val_step_workspace_bytes", "linetr_val_step_output_bytes", "linetr_val_step", "linetr_assign_from_matches", "linetr_desc_loss_grad_workspace_bytes", "linetr_desc_loss_grad", "linetr_linear_backward_chunk_rows", "linetr_linear_backward_workspace_bytes", "linetr_linear_forward", "linetr_linear_backward", "linetr_head_backward_workspace_bytes", "linetr_head_forward", "linetr_head_backward", "linetr_sig_attention_backward_workspace_bytes", "linetr_sig_attention_forward", "linetr_sig_attention_backward", "linetr_gt_assign_workspace_bytes", "linetr_gt_assign", "linetr_superpoint_heads", "linetr_superpoint_keypoints_workspace_bytes", "linetr_superpoint_keypoints",
            "linetr_point_descriptors_workspace_bytes", "linetr_point_descriptors", "linetr_set_precision", "linetr_get_precision", "linetr_debug_posenc", "linetr_debug_gemm", "linetr_debug_gemm_case", "linetr_debug_sig_attention", "linetr_debug_tok_mlp", "linetr_debug_bn_train_workspace_bytes", "linetr_debug_bn_train", "linetr_debug_cls_pool", "linetr_debug_match", "linetr_allgather_desc", "linetr_set_allgather_fn", "linetr_pack_slab", "linetr_sample_descriptors_workspace_bytes",
            "linetr_sample_descriptors", "linetr_pool_distmat_workspace_bytes", "linetr_pool_distmat", "linetr_pool_distmat_dense_workspace_bytes", "linetr_pool_distmat_dense", "linetr_set_profiling", "linetr_get_profile"]
 

@@ -1,7 +1,8 @@
 // liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
 // multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h), SuperPoint's key-point branch (lt_keypoints.h), the
 // validation step (lt_valstep.h), the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head
-// (lt_linbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
+// (lt_linbwd.h), the neighbour-line attention's forward with statistics and backward (lt_attnbwd.h) and the ground-truth line assignment
+// in front of them (lt_gtassign.h).
 #include <algorithm>
 #include <numeric>
 
@@ -10,6 +11,7 @@
 #include "lt_valstep.h"
 #include "lt_lossgrad.h"
 #include "lt_linbwd.h"
+#include "lt_attnbwd.h"
 #include "lt_gtassign.h"
 #include "lt_producer.h"
 #include "lt_keypoints.h"
@@ -1048,6 +1050,85 @@ extern "C" int linetr_head_backward(LinetrHandle* h, const float* d_x, const flo
   const int rl = head_launch(h, st, d_x, d_W, d_b, rows, nullptr, d_g, gy);
   if (rl != LINETR_OK) return rl;
   return lin_bwd_launch(h, st, d_x, D, d_W, gy, D, nullptr, rows, D, D, d_dx, d_dW, d_db, rest);
+}
+
+// =============================================================================================
+// neighbour-line attention for training: forward with statistics, backward (lt_attnbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t AB_MAX_ROWS = 0x7fffffff;      // cu_sub is int32
+constexpr int AB_MAX_IMAGES = 4096;              // every block walks cu_sub (ab_find_tile): the walk, and the grid of N / 128 + n_images, stay small
+int64_t attn_delta_bytes(int64_t N) { return align_up(N * HEADS * 4, 256); }
+bool attn_stride_ok(int64_t ld) { return ld >= D && ld % 4 == 0; }
+// tiles of 128 rows of any split of N rows into n_images images, at most
+unsigned attn_tiles(int64_t N, int n_images) { return (unsigned)(N / AB_T + n_images); }
+}  // namespace
+
+extern "C" int64_t linetr_sig_attention_backward_workspace_bytes(int64_t N) {
+  return N >= 0 && N <= AB_MAX_ROWS ? attn_delta_bytes(N) + 256 : 0;
+}
+
+extern "C" int linetr_sig_attention_forward(LinetrHandle* h, const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, const float* d_v,
+                                            int64_t ldv, const int32_t* d_cu_sub, int32_t n_images, int64_t N, float* d_msg, int64_t ldo,
+                                            float* d_lse, void* stream) {
+  // every refusal comes before the first launch
+  if (n_images < 1 || n_images > AB_MAX_IMAGES || N < 0 || N > AB_MAX_ROWS)
+    return fail(LINETR_E_ARG, "sig_attention_forward: n_images=%d N=%lld (1 <= n_images <= %d, 0 <= N < 2^31)", n_images, (long long)N, AB_MAX_IMAGES);
+  if (!d_q || !d_k || !d_v || !d_cu_sub || !d_msg || !d_lse) return fail(LINETR_E_ARG, "sig_attention_forward: null pointer");
+  if (!attn_stride_ok(ldq) || !attn_stride_ok(ldk) || !attn_stride_ok(ldv) || !attn_stride_ok(ldo))
+    return fail(LINETR_E_ARG, "sig_attention_forward: row strides %lld / %lld / %lld / %lld (at least 256, multiples of 4 floats)", (long long)ldq,
+                (long long)ldk, (long long)ldv, (long long)ldo);
+  if (!aligned16(d_q) || !aligned16(d_k) || !aligned16(d_v) || !aligned16(d_msg) || !aligned16(d_lse))
+    return fail(LINETR_E_ARG, "sig_attention_forward: every tensor must be 16-byte aligned");
+  if (N == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "sig_attn_fwd_lse", 0, 4.0 * N * (4.0 * D + HEADS));
+  hipLaunchKernelGGL(ab_fwd_kernel, dim3(attn_tiles(N, n_images), HEADS), dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, (const int*)d_cu_sub,
+                     n_images, d_msg, ldo, d_lse);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_sig_attention_backward(LinetrHandle* h, const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, const float* d_v,
+                                             int64_t ldv, const float* d_msg, int64_t ldo, const float* d_lse, const float* d_g, int64_t ldg,
+                                             const int32_t* d_cu_sub, int32_t n_images, int64_t N, float* d_dq, int64_t lddq, float* d_dk,
+                                             int64_t lddk, float* d_dv, int64_t lddv, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (n_images < 1 || n_images > AB_MAX_IMAGES || N < 0 || N > AB_MAX_ROWS)
+    return fail(LINETR_E_ARG, "sig_attention_backward: n_images=%d N=%lld (1 <= n_images <= %d, 0 <= N < 2^31)", n_images, (long long)N, AB_MAX_IMAGES);
+  if (!d_q || !d_k || !d_v || !d_msg || !d_lse || !d_g || !d_cu_sub || !d_ws) return fail(LINETR_E_ARG, "sig_attention_backward: null pointer");
+  if (!attn_stride_ok(ldq) || !attn_stride_ok(ldk) || !attn_stride_ok(ldv) || !attn_stride_ok(ldo) || !attn_stride_ok(ldg) ||
+      (d_dq && !attn_stride_ok(lddq)) || (d_dk && !attn_stride_ok(lddk)) || (d_dv && !attn_stride_ok(lddv)))
+    return fail(LINETR_E_ARG, "sig_attention_backward: every row stride must be at least 256 and a multiple of 4 floats");
+  if (!aligned16(d_q) || !aligned16(d_k) || !aligned16(d_v) || !aligned16(d_msg) || !aligned16(d_lse) || !aligned16(d_g) || !aligned16(d_dq) ||
+      !aligned16(d_dk) || !aligned16(d_dv) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "sig_attention_backward: every tensor must be 16-byte aligned");
+  if (ws_bytes < linetr_sig_attention_backward_workspace_bytes(N))
+    return fail(LINETR_E_ARG, "sig_attention_backward: workspace too small (need %lld)", (long long)linetr_sig_attention_backward_workspace_bytes(N));
+  if (N == 0 || (!d_dq && !d_dk && !d_dv)) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  float* delta = (float*)d_ws;
+  const dim3 grid(attn_tiles(N, n_images), HEADS);
+  if (d_dq || d_dk) {       // dV reads P alone
+    ProfScope ps(h, st, "sig_attn_bwd_delta", 0, 4.0 * N * (2.0 * D + HEADS));
+    hipLaunchKernelGGL(ab_delta_kernel, dim3((unsigned)((N + 31) / 32), HEADS), dim3(64), 0, st, d_g, ldg, d_msg, ldo, N, delta);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dk || d_dv) {
+    ProfScope ps(h, st, "sig_attn_bwd_dkv", 0, 4.0 * N * (6.0 * D + 2.0 * HEADS));
+    hipLaunchKernelGGL(ab_dkv_kernel, grid, dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, d_g, ldg, d_lse, (const float*)delta,
+                       (const int*)d_cu_sub, n_images, d_dk, lddk, d_dv, lddv);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dq) {
+    ProfScope ps(h, st, "sig_attn_bwd_dq", 0, 4.0 * N * (5.0 * D + 2.0 * HEADS));
+    hipLaunchKernelGGL(ab_dq_kernel, grid, dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, d_g, ldg, d_lse, (const float*)delta,
+                       (const int*)d_cu_sub, n_images, d_dq, lddq);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
 }
 
 // =============================================================================================

@@ -1005,6 +1005,64 @@ class Engine:
                                                    ptr(db), ws.data_ptr(), ws.numel(), self._stream()), self._L)
         return (self._like_input(dx, B, n) if dx is not None else None, dW.view(weight.shape) if dW is not None else None, db)
 
+    # ------------------------------------------------------------------ neighbour-line attention for training
+    def _cu_sub_dev(self, cu_sub) -> torch.Tensor:
+        """sub-line offsets [n_images + 1] as an int32 tensor on the device (a device tensor is taken as it is: no host wait)"""
+        cu = cu_sub if isinstance(cu_sub, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cu_sub, dtype=np.int32)))
+        cu = cu.detach().reshape(-1)
+        if cu.numel() < 2:
+            raise ValueError("cu_sub must hold n_images + 1 >= 2 offsets")
+        if cu.device != self.device or cu.dtype != torch.int32 or not cu.is_contiguous():
+            cu = cu.to(device=self.device, dtype=torch.int32).contiguous()
+        return cu
+
+    def _attn_rows(self, named, N=None):
+        """head-major [N, 256] rows as the attention kernels read them: strided row views pass as they are, anything else is copied"""
+        rows = [self._act_rows(t, D, name)[0] for name, t in named]
+        N = int(rows[0].shape[0]) if N is None else N
+        for (name, _), r in zip(named, rows):
+            if r.dim() != 2 or int(r.shape[0]) != N:
+                raise ValueError(f"{name} must be [{N}, {D}] head-major rows, got {tuple(r.shape)}")
+        return rows, N
+
+    def sig_attention_forward(self, q, k, v, cu_sub):
+        """The neighbour-line attention softmax(q^T k / 8) v of models/line_transformer.py:132-136 with its softmax statistics
+        (linetr_sig_attention_forward; exact-fp32 MFMA).  q, k, v: head-major rows [N, 256] (column h*64 + d), q UNSCALED; each may be a
+        strided row view, e.g. a column block of one [N, 768] buffer.  cu_sub [n_images + 1]: one image is one softmax domain (a device
+        int32 tensor is read in place).  Returns (message [N, 256] head-major, lse [N, 4] = m + log l).  No host wait."""
+        (qr, kr, vr), N = self._attn_rows((("q", q), ("k", k), ("v", v)))
+        cu = self._cu_sub_dev(cu_sub)
+        msg = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        lse = torch.empty((N, 4), dtype=torch.float32, device=self.device)
+        if N == 0:                                   # (an empty tensor has no address to hand over)
+            return msg, lse
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_sig_attention_forward(self._h, qr.data_ptr(), qr.stride(0), kr.data_ptr(), kr.stride(0), vr.data_ptr(),
+                                                           vr.stride(0), cu.data_ptr(), cu.numel() - 1, N, msg.data_ptr(), D, lse.data_ptr(),
+                                                           self._stream()), self._L)
+        return msg, lse
+
+    def sig_attention_backward(self, q, k, v, o, lse, grad_out, cu_sub, need=(True, True, True)):
+        """The attention's backward (linetr_sig_attention_backward): (dq, dk, dv) [N, 256] head-major for the gradient `grad_out` arriving at
+        the message `o`; q, k, v, o, lse as sig_attention_forward took and returned them.  P is recomputed from q, k and lse; nothing n x n
+        is stored.  `need` = which of the three to compute (the others are None).  Deterministic; no host wait."""
+        (qr, kr, vr, orow, g), N = self._attn_rows((("q", q), ("k", k), ("v", v), ("o", o), ("grad_out", grad_out)))
+        ls = self._f32(lse.detach())
+        if tuple(ls.shape) != (N, 4):
+            raise ValueError(f"lse must be [{N}, 4], got {tuple(ls.shape)}")
+        cu = self._cu_sub_dev(cu_sub)
+        dq, dk, dv = (torch.empty((N, D), dtype=torch.float32, device=self.device) if n else None for n in need)
+        if N == 0:
+            return dq, dk, dv
+        ws = self._stream_workspace("sig_attn_bwd", self._L.linetr_sig_attention_backward_workspace_bytes(N))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_sig_attention_backward(self._h, qr.data_ptr(), qr.stride(0), kr.data_ptr(), kr.stride(0), vr.data_ptr(),
+                                                            vr.stride(0), orow.data_ptr(), orow.stride(0), ls.data_ptr(), g.data_ptr(), g.stride(0),
+                                                            cu.data_ptr(), cu.numel() - 1, N, ptr(dq), D, ptr(dk), D, ptr(dv), D, ws.data_ptr(),
+                                                            ws.numel(), self._stream()), self._L)
+        return dq, dk, dv
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes
