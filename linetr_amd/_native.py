@@ -54,6 +54,102 @@ class ProfileEntry(C.Structure):
                 ("bytes", C.c_double)]
 
 
+vp, i32, i64, f64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float
+_P = C.POINTER
+
+# The C ABI of include/linetr_hip.h, in the header's order: name -> (restype, argtypes).  lib() applies it; EXPORTS is its name set.
+# (i32: a LinetrStatus unless the name says otherwise.)
+ABI = {
+    "linetr_abi_version": (i32, []),
+    "linetr_last_error": (C.c_char_p, []),
+    "linetr_create": (i32, [_P(ModelConfig), i32, _P(C.c_char_p), _P(vp), _P(i64), i32, _P(vp)]),
+    "linetr_destroy": (None, [vp]),
+    "linetr_prefilter": (i32, [vp, i32, i32, i32, i32, f64, i32, vp, f64, i32, i32, i32, i32, vp, i32, _P(i32), _P(i32)]),
+    "linetr_prefilter_batch": (i32, [vp, vp, i32, i32, i32, i32, f64, i32, vp, f64, i32, i32, vp, i32, vp, vp]),
+    "linetr_prefilter_tied_images": (i32, [vp, i32]),
+    "linetr_pack_lines": (i32, [vp, vp, vp, i32, f64, i32, i32, i32, i32, vp, _P(i32)]),
+    "linetr_tokenize_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_tokenize": (i32, [vp, vp, i32, i32, f64, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, Tokens, vp, vp, i64, vp]),
+    "linetr_sample_descriptors_workspace_bytes": (i64, [i32, i32, i32]),
+    "linetr_sample_descriptors": (i32, [vp, vp, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "linetr_forward_workspace_bytes": (i64, [vp, i32, i32]),
+    "linetr_forward": (i32, [vp, _P(Tokens), vp, vp, i32, i32, vp, vp, i64, vp]),
+    "linetr_bn_stats_floats": (i64, [vp]),
+    "linetr_forward_train_workspace_bytes": (i64, [vp, i32, i32]),
+    "linetr_forward_train": (i32, [vp, _P(Tokens), vp, vp, i32, i32, f32, vp, vp, vp, vp, i64, vp]),
+    "linetr_describe_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i64]),
+    "linetr_describe": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, i32, i32, i32, i32, Tokens, vp, vp, vp, i64, vp]),
+    "linetr_describe_submit": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, i32, i32, i32, i32, Tokens, vp, vp, vp, i64, i32,
+                                     i32, vp]),
+    "linetr_pipeline_max_slots": (i32, []),
+    "linetr_describe_join": (i32, [vp, i32, vp]),
+    "linetr_match_workspace_bytes": (i64, [i32, i64, i64, i64]),
+    "linetr_match": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_match_gathered": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_match_distmat_workspace_bytes": (i64, [i32, i32]),
+    "linetr_match_distmat": (i32, [vp, vp, i32, i32, f32, i32, vp, vp, i64, vp]),
+    "linetr_match_distmat_f64_workspace_bytes": (i64, [i32, i32]),
+    "linetr_match_distmat_f64": (i32, [vp, vp, i32, i32, f64, i32, vp, vp, i64, vp]),
+    "linetr_pool_distmat_workspace_bytes": (i64, [i32, i32]),
+    "linetr_pool_distmat": (i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]),
+    "linetr_pool_distmat_dense_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_pool_distmat_dense": (i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]),
+    "linetr_match_points": (i32, [vp, vp, i32, vp, i32, f32, i32, vp, vp, vp, i64, vp]),
+    "linetr_pair_tail_workspace_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
+    "linetr_pair_tail_output_bytes": (i64, [i32, i32, i32, i32, vp]),
+    "linetr_pair_tail": (i32, [vp, vp, i32, vp, i32, f32, vp, i32, vp, i32, vp, i32, vp, i32, f32, i32, vp, i64, vp, i64, vp]),
+    "linetr_val_step_workspace_bytes": (i64, [i32, i32]),
+    "linetr_val_step_output_bytes": (i64, [i32, vp]),
+    "linetr_val_step": (i32, [vp, vp, i32, vp, i32, vp, i32, f64, i32, vp, vp, vp, vp, i64, vp, i64, vp]),
+    "linetr_assign_from_matches": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "linetr_desc_loss_grad_workspace_bytes": (i64, [i32, i32]),
+    "linetr_desc_loss_grad": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, i64, vp]),
+    "linetr_linear_backward_chunk_rows": (i32, []),
+    "linetr_linear_backward_workspace_bytes": (i64, [i64, i32, i32]),
+    "linetr_linear_forward": (i32, [vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, i64, vp]),
+    "linetr_linear_backward": (i32, [vp, vp, i64, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp]),
+    "linetr_head_backward_workspace_bytes": (i64, [i64]),
+    "linetr_head_forward": (i32, [vp, vp, vp, vp, i64, vp, vp]),
+    "linetr_head_backward": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "linetr_sig_attention_backward_workspace_bytes": (i64, [i64]),
+    "linetr_sig_attention_forward": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, i64, vp, vp]),
+    "linetr_sig_attention_backward": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                            vp]),
+    "linetr_gt_assign_workspace_bytes": (i64, [i32, i32, i32]),
+    "linetr_gt_assign": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_superpoint_heads": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "linetr_superpoint_keypoints_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_superpoint_keypoints": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_point_descriptors_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_point_descriptors": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "linetr_set_precision": (i32, [vp, i32]),
+    "linetr_get_precision": (i32, [vp]),
+    "linetr_debug_posenc": (i32, [vp, i32, vp, vp, vp, i64, vp, vp]),
+    "linetr_debug_gemm": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "linetr_debug_gemm_case": (i32, [vp, _P(GemmCase), vp, vp]),
+    "linetr_debug_sig_attention": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
+    "linetr_debug_tok_mlp": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, vp, vp]),
+    "linetr_debug_bn_train_workspace_bytes": (i64, [vp, i32, i64]),
+    "linetr_debug_bn_train": (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_debug_cls_pool": (i32, [vp, i32, vp, i32, vp, i32, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "linetr_debug_match": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
+    "linetr_allgather_desc": (i32, [vp, vp, vp, i64, vp]),
+    "linetr_set_allgather_fn": (i32, [vp]),
+    "linetr_pack_slab": (i32, [vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp]),
+    "linetr_set_profiling": (i32, [vp, i32]),
+    "linetr_get_profile": (i32, [vp, _P(ProfileEntry), i32, _P(i32)]),
+}
+# the experiments build only (include/linetr_hip.h, LINETR_EXPERIMENTS)
+EXPERIMENT_ABI = {
+    "linetr_st_bytes": (i64, [i64, i32]),
+    "linetr_debug_to_st": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "linetr_debug_from_st": (i32, [vp, vp, i32, i32, vp, i32, vp]),
+    "linetr_debug_gemm_st": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "linetr_debug_pairnet_stamps": (i32, [vp, vp]),
+}
+EXPORTS = list(ABI)
+EXPERIMENT_EXPORTS = list(EXPERIMENT_ABI)
+
 _libs = {}
 
 
@@ -72,137 +168,14 @@ def lib(path=None):
             f"{path} is missing: the HIP extension has not been built (run `python -m linetr_amd.build`). "
             "linetr_amd has no CPU fallback.")
     L = C.CDLL(path)
-    vp, i32, i64, f64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float
-    L.linetr_abi_version.restype = i32
-    L.linetr_last_error.restype = C.c_char_p
-    L.linetr_create.argtypes = [C.POINTER(ModelConfig), i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(i64), i32,
-                                C.POINTER(vp)]
-    L.linetr_destroy.argtypes = [vp]
-    L.linetr_destroy.restype = None
-    L.linetr_prefilter.argtypes = [vp, i32, i32, i32, i32, f64, i32, vp, f64, i32, i32, i32, i32, vp, i32, C.POINTER(i32),
-                                   C.POINTER(i32)]
-    L.linetr_prefilter_batch.argtypes = [vp, vp, i32, i32, i32, i32, f64, i32, vp, f64, i32, i32, vp, i32, vp, vp]
-    L.linetr_prefilter_tied_images.argtypes = [vp, i32]
-    L.linetr_prefilter_tied_images.restype = i32
-    L.linetr_pack_lines.argtypes = [vp, vp, vp, i32, f64, i32, i32, i32, i32, vp, C.POINTER(i32)]
-    L.linetr_describe_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i64]
-    L.linetr_describe_workspace_bytes.restype = i64
-    L.linetr_describe.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, i32, i32, i32, i32, Tokens, vp, vp,
-                                  vp, i64, vp]
-    L.linetr_describe_submit.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, i32, i32, i32, i32, Tokens, vp, vp,
-                                         vp, i64, i32, i32, vp]
-    L.linetr_describe_join.argtypes = [vp, i32, vp]
-    L.linetr_pipeline_max_slots.argtypes = []
-    L.linetr_tokenize_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.linetr_tokenize_workspace_bytes.restype = i64
-    L.linetr_tokenize.argtypes = [vp, vp, i32, i32, f64, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, Tokens, vp, vp, i64, vp]
-    L.linetr_forward_workspace_bytes.argtypes = [vp, i32, i32]
-    L.linetr_forward_workspace_bytes.restype = i64
-    L.linetr_forward.argtypes = [vp, C.POINTER(Tokens), vp, vp, i32, i32, vp, vp, i64, vp]
-    L.linetr_bn_stats_floats.argtypes = [vp]
-    L.linetr_bn_stats_floats.restype = i64
-    L.linetr_forward_train_workspace_bytes.argtypes = [vp, i32, i32]
-    L.linetr_forward_train_workspace_bytes.restype = i64
-    L.linetr_forward_train.argtypes = [vp, C.POINTER(Tokens), vp, vp, i32, i32, f32, vp, vp, vp, vp, i64, vp]
-    L.linetr_match_workspace_bytes.argtypes = [i32, i64, i64, i64]
-    L.linetr_match_workspace_bytes.restype = i64
-    L.linetr_match.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, vp]
-    L.linetr_match_gathered.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, vp]
-    L.linetr_match_points.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp, vp, i64, vp]
-    L.linetr_match_distmat.argtypes = [vp, vp, i32, i32, f32, i32, vp, vp, i64, vp]
-    L.linetr_match_distmat_workspace_bytes.argtypes = [i32, i32]
-    L.linetr_match_distmat_workspace_bytes.restype = i64
-    L.linetr_match_distmat_f64.argtypes = [vp, vp, i32, i32, f64, i32, vp, vp, i64, vp]
-    L.linetr_match_distmat_f64_workspace_bytes.argtypes = [i32, i32]
-    L.linetr_match_distmat_f64_workspace_bytes.restype = i64
-    L.linetr_pair_tail_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
-    L.linetr_pair_tail_workspace_bytes.restype = i64
-    L.linetr_pair_tail_output_bytes.argtypes = [i32, i32, i32, i32, vp]
-    L.linetr_pair_tail_output_bytes.restype = i64
-    L.linetr_pair_tail.argtypes = [vp, vp, i32, vp, i32, f32, vp, i32, vp, i32, vp, i32, vp, i32, f32, i32, vp, i64, vp, i64, vp]
-    L.linetr_val_step_workspace_bytes.argtypes = [i32, i32]
-    L.linetr_val_step_workspace_bytes.restype = i64
-    L.linetr_val_step_output_bytes.argtypes = [i32, vp]
-    L.linetr_val_step_output_bytes.restype = i64
-    L.linetr_val_step.argtypes = [vp, vp, i32, vp, i32, vp, i32, f64, i32, vp, vp, vp, vp, i64, vp, i64, vp]
-    L.linetr_assign_from_matches.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.linetr_desc_loss_grad_workspace_bytes.argtypes = [i32, i32]
-    L.linetr_desc_loss_grad_workspace_bytes.restype = i64
-    L.linetr_desc_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, i64, vp]
-    L.linetr_linear_backward_chunk_rows.argtypes = []
-    L.linetr_linear_backward_chunk_rows.restype = i32
-    L.linetr_linear_backward_workspace_bytes.argtypes = [i64, i32, i32]
-    L.linetr_linear_backward_workspace_bytes.restype = i64
-    L.linetr_linear_forward.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, i64, vp]
-    L.linetr_linear_backward.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp]
-    L.linetr_head_backward_workspace_bytes.argtypes = [i64]
-    L.linetr_head_backward_workspace_bytes.restype = i64
-    L.linetr_head_forward.argtypes = [vp, vp, vp, vp, i64, vp, vp]
-    L.linetr_head_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.linetr_sig_attention_backward_workspace_bytes.argtypes = [i64]
-    L.linetr_sig_attention_backward_workspace_bytes.restype = i64
-    L.linetr_sig_attention_forward.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, i64, vp, vp]
-    L.linetr_sig_attention_backward.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i64, vp, i64, vp, i64, vp, i64,
-                                                vp, i64, vp]
-    L.linetr_gt_assign_workspace_bytes.argtypes = [i32, i32, i32]
-    L.linetr_gt_assign_workspace_bytes.restype = i64
-    L.linetr_gt_assign.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp,
-                                   i64, vp]
-    L.linetr_superpoint_heads.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
-    L.linetr_superpoint_keypoints_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.linetr_superpoint_keypoints_workspace_bytes.restype = i64
-    L.linetr_superpoint_keypoints.argtypes = [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]
-    L.linetr_point_descriptors_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.linetr_point_descriptors_workspace_bytes.restype = i64
-    L.linetr_point_descriptors.argtypes = [vp, vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]
-    L.linetr_set_precision.argtypes = [vp, i32]
-    L.linetr_get_precision.argtypes = [vp]
-    L.linetr_debug_posenc.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp]
-    L.linetr_debug_gemm.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    L.linetr_debug_gemm_case.argtypes = [vp, C.POINTER(GemmCase), vp, vp]
-    L.linetr_debug_sig_attention.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]
-    L.linetr_debug_tok_mlp.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, vp, vp]
-    L.linetr_debug_bn_train_workspace_bytes.argtypes = [vp, i32, i64]
-    L.linetr_debug_bn_train_workspace_bytes.restype = i64
-    L.linetr_debug_bn_train.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp]
-    L.linetr_debug_cls_pool.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.linetr_debug_match.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
-    if hasattr(L, "linetr_debug_gemm_st"):      # experiments build only (include/linetr_hip.h, LINETR_EXPERIMENTS)
-        L.linetr_st_bytes.argtypes = [i64, i32]
-        L.linetr_st_bytes.restype = i64
-        L.linetr_debug_to_st.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-        L.linetr_debug_from_st.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-        L.linetr_debug_gemm_st.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        L.linetr_debug_pairnet_stamps.argtypes = [vp, vp]
-    L.linetr_allgather_desc.argtypes = [vp, vp, vp, i64, vp]
-    L.linetr_set_allgather_fn.argtypes = [vp]
-    L.linetr_pack_slab.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp]
-    L.linetr_sample_descriptors_workspace_bytes.argtypes = [i32, i32, i32]
-    L.linetr_sample_descriptors_workspace_bytes.restype = i64
-    L.linetr_sample_descriptors.argtypes = [vp, vp, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]
-    L.linetr_pool_distmat_workspace_bytes.argtypes = [i32, i32]
-    L.linetr_pool_distmat_workspace_bytes.restype = i64
-    L.linetr_pool_distmat.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]
-    L.linetr_pool_distmat_dense_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.linetr_pool_distmat_dense_workspace_bytes.restype = i64
-    L.linetr_pool_distmat_dense.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]
-    L.linetr_set_profiling.argtypes = [vp, i32]
-    L.linetr_get_profile.argtypes = [vp, C.POINTER(ProfileEntry), i32, C.POINTER(i32)]
+    table = {**ABI, **EXPERIMENT_ABI} if hasattr(L, "linetr_debug_gemm_st") else ABI
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.linetr_abi_version() != 6:
         raise RuntimeError("liblinetr_hip.so ABI version mismatch")
     _libs[path] = L
     return L
-
-
-EXPORTS = ["linetr_abi_version", "linetr_last_error", "linetr_create", "linetr_destroy", "linetr_prefilter",
-           "linetr_prefilter_batch", "linetr_prefilter_tied_images", "linetr_pack_lines", "linetr_tokenize_workspace_bytes", "linetr_tokenize", "linetr_forward_workspace_bytes",
-           "linetr_forward", "linetr_bn_stats_floats", "linetr_forward_train_workspace_bytes", "linetr_forward_train", "linetr_describe_workspace_bytes", "linetr_describe", "linetr_describe_submit", "linetr_describe_join", "linetr_pipeline_max_slots", "linetr_match_workspace_bytes", "linetr_match", "linetr_match_gathered", "linetr_match_points",
-           "linetr_match_distmat", "linetr_match_distmat_workspace_bytes", "linetr_match_distmat_f64", "linetr_match_distmat_f64_workspace_bytes", "linetr_pair_tail_workspace_bytes", "linetr_pair_tail_output_bytes", "linetr_pair_tail", "linetr_val_step_workspace_bytes", "linetr_val_step_output_bytes", "linetr_val_step", "linetr_assign_from_matches", "linetr_desc_loss_grad_workspace_bytes", "linetr_desc_loss_grad", "linetr_linear_backward_chunk_rows", "linetr_linear_backward_workspace_bytes", "linetr_linear_forward", "linetr_linear_backward", "linetr_head_backward_workspace_bytes", "linetr_head_forward", "linetr_head_backward", "linetr_sig_attention_backward_workspace_bytes", "linetr_sig_attention_forward", "linetr_sig_attention_backward", "linetr_gt_assign_workspace_bytes", "linetr_gt_assign", "linetr_superpoint_heads", "linetr_superpoint_keypoints_workspace_bytes", "linetr_superpoint_keypoints",
-           "linetr_point_descriptors_workspace_bytes", "linetr_point_descriptors", "linetr_set_precision", "linetr_get_precision", "linetr_debug_posenc", "linetr_debug_gemm", "linetr_debug_gemm_case", "linetr_debug_sig_attention", "linetr_debug_tok_mlp", "linetr_debug_bn_train_workspace_bytes", "linetr_debug_bn_train", "linetr_debug_cls_pool", "linetr_debug_match", "linetr_allgather_desc", "linetr_set_allgather_fn", "linetr_pack_slab", "linetr_sample_descriptors_workspace_bytes",
-           "linetr_sample_descriptors", "linetr_pool_distmat_workspace_bytes", "linetr_pool_distmat", "linetr_pool_distmat_dense_workspace_bytes", "linetr_pool_distmat_dense", "linetr_set_profiling", "linetr_get_profile"]
-
-
-EXPERIMENT_EXPORTS = ["linetr_st_bytes", "linetr_debug_to_st", "linetr_debug_from_st", "linetr_debug_gemm_st", "linetr_debug_pairnet_stamps"]
 
 
 class NativeError(RuntimeError):

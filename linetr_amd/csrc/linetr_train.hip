@@ -1,0 +1,530 @@
+// liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h): the validation step (lt_valstep.h),
+// the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
+// attention's forward with statistics and backward (lt_attnbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
+#include <algorithm>
+
+#include "lt_handle.h"
+#include "lt_valstep.h"
+#include "lt_lossgrad.h"
+#include "lt_linbwd.h"
+#include "lt_attnbwd.h"
+#include "lt_gtassign.h"
+
+using namespace lt;
+
+// =============================================================================================
+// validation step (lt_valstep.h)
+// =============================================================================================
+
+namespace {
+constexpr int VS_MAX_N = 32768;   // n^2 dot products per item are indexed in 64 bits; the grids stay far inside their limits
+constexpr int VS_MAX_B = 65535;   // grid.z / grid.y
+struct ValOutLayout { int64_t o_scalars, o_count, o_counts, o_scores, total; };
+ValOutLayout val_out_layout(int B) {
+  ValOutLayout L{};
+  Carve c;
+  L.o_scalars = c.take(3 * 8);
+  L.o_count = c.take(8);
+  L.o_counts = c.take((int64_t)B * 4 * 4);
+  L.o_scores = c.take((int64_t)B * 3 * 8);
+  L.total = c.o;
+  return L;
+}
+// workspace: device image of the result block | dots | norms | per-row results | argmins | match01
+struct ValWsLayout { int64_t o_out, o_dots, o_sq0, o_sq1, o_pos, o_neg, o_rarg, o_rmin, o_carg, o_gt, o_m01, total; };
+ValWsLayout val_ws_layout(int B, int n) {
+  ValWsLayout L{};
+  const int64_t rows = align_up((int64_t)B * n * 4, 256);
+  Carve c;
+  L.o_out = c.take(val_out_layout(B).total);
+  L.o_dots = c.take((int64_t)B * n * n * 4);
+  L.o_sq0 = c.take(rows);
+  L.o_sq1 = c.take(rows);
+  L.o_pos = c.take(2 * rows);
+  L.o_neg = c.take(2 * rows);
+  L.o_rarg = c.take(rows);
+  L.o_rmin = c.take(rows);
+  L.o_carg = c.take(rows);
+  L.o_gt = c.take(rows);
+  L.o_m01 = c.take(rows);
+  L.total = c.o + 256;
+  return L;
+}
+bool val_dims_ok(int B, int n) { return B > 0 && B <= VS_MAX_B && n > 0 && n <= VS_MAX_N; }
+
+// The prologue of the two criterion entry points (linetr_val_step, linetr_desc_loss_grad), for `who`.  First their refusals, every one
+// before the first launch (out_need / ws_need: what the entry point's own _output_bytes / _workspace_bytes answer, safe for any shape) ...
+int criterion_check(const char* who, int n0, int n1, int B, const float* d_desc0, const float* d_desc1, const float* d_assign,
+                    const void* h_pinned_out, int64_t pinned_bytes, int64_t out_need, const void* d_ws, int64_t ws_bytes, int64_t ws_need) {
+  if (n0 != n1) return fail(LINETR_E_ARG, "%s: %d and %d sub-lines (the criterion stacks D on D^T: one n for both sides)", who, n0, n1);
+  if (!val_dims_ok(B, n0)) return fail(LINETR_E_ARG, "%s: bad shape B=%d n=%d (B 1..%d, n 1..%d)", who, B, n0, VS_MAX_B, VS_MAX_N);
+  if (!d_desc0 || !d_desc1 || !d_assign || !h_pinned_out || !d_ws) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if (pinned_bytes < out_need) return fail(LINETR_E_ARG, "%s: output block too small (need %lld)", who, (long long)out_need);
+  if (ws_bytes < ws_need) return fail(LINETR_E_ARG, "%s: workspace too small (need %lld)", who, (long long)ws_need);
+  return LINETR_OK;
+}
+// ... then the dot products and squared norms both read
+int criterion_dots(LinetrHandle* h, hipStream_t st, const float* d_desc0, const float* d_desc1, int B, int n, float* dots, float* sq0, float* sq1) {
+  const int tiles = cdiv(n, 64);
+  ProfScope ps(h, st, "val_dot", 2.0 * B * n * n * D, 4.0 * B * (2.0 * n * D + (double)n * n));
+  hipLaunchKernelGGL(val_dot_kernel, dim3(tiles, tiles, B), dim3(256), 0, st, d_desc0, d_desc1, n, dots, sq0, sq1);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int64_t linetr_val_step_workspace_bytes(int32_t B, int32_t n) {
+  return val_dims_ok(B, n) ? val_ws_layout(B, n).total : 0;
+}
+
+extern "C" int64_t linetr_val_step_output_bytes(int32_t B, int64_t* h_offsets) {
+  const ValOutLayout L = val_out_layout(std::min(std::max(B, 0), VS_MAX_B));
+  if (h_offsets) { h_offsets[0] = L.o_scalars; h_offsets[1] = L.o_count; h_offsets[2] = L.o_counts; h_offsets[3] = L.o_scores; }
+  return L.total;
+}
+
+extern "C" int linetr_val_step(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign,
+                               int32_t B, double nn_thresh, int32_t mutual, float* d_row_pos, float* d_row_neg, int32_t* d_match01,
+                               void* h_pinned_out, int64_t pinned_bytes, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (int e = criterion_check("val_step", n0, n1, B, d_desc0, d_desc1, d_assign, h_pinned_out, pinned_bytes, linetr_val_step_output_bytes(B, nullptr),
+                              d_ws, ws_bytes, linetr_val_step_workspace_bytes(B, n0))) return e;
+  const int n = n0;
+  const ValOutLayout O = val_out_layout(B);
+  const ValWsLayout W = val_ws_layout(B, n);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  char* base = (char*)d_ws;
+  float* dots = (float*)(base + W.o_dots);
+  float* sq0 = (float*)(base + W.o_sq0);
+  float* sq1 = (float*)(base + W.o_sq1);
+  float* row_pos = d_row_pos ? d_row_pos : (float*)(base + W.o_pos);
+  float* row_neg = d_row_neg ? d_row_neg : (float*)(base + W.o_neg);
+  int* row_arg = (int*)(base + W.o_rarg);
+  float* row_min = (float*)(base + W.o_rmin);
+  int* col_arg = (int*)(base + W.o_carg);
+  int* row_gt = (int*)(base + W.o_gt);
+  int* match01 = d_match01 ? d_match01 : (int*)(base + W.o_m01);
+  char* dout = base + W.o_out;
+  const ValOut out{(double*)(dout + O.o_scalars), (long long*)(dout + O.o_count), (int*)(dout + O.o_counts), (double*)(dout + O.o_scores)};
+  if (int e = criterion_dots(h, st, d_desc0, d_desc1, B, n, dots, sq0, sq1)) return e;
+  {
+    ProfScope ps(h, st, "val_select", 0, 16.0 * B * n * n);
+    hipLaunchKernelGGL(val_select_kernel, dim3(cdiv(n, VS_ROWS) + cdiv(n, VS_COLS), B), dim3(256), 0, st, (const float*)dots, (const float*)sq0,
+                       (const float*)sq1, d_assign, n, row_pos, row_neg, row_arg, row_min, col_arg, row_gt);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "val_final", 0, 44.0 * B * n);
+    hipLaunchKernelGGL(val_final_kernel, dim3(B + 1), dim3(256), 0, st, (const float*)row_pos, (const float*)row_neg, (const int*)row_arg,
+                       (const float*)row_min, (const int*)col_arg, (const int*)row_gt, d_assign, B, n, nn_thresh, mutual, match01, out);
+    LT_LAUNCH_CHECK();
+  }
+  LT_HIP(hipMemcpyAsync(h_pinned_out, dout, (size_t)O.total, hipMemcpyDeviceToHost, st));
+  return LINETR_OK;
+}
+
+extern "C" int linetr_assign_from_matches(LinetrHandle* h, const int32_t* d_lmatches, int32_t B, int32_t M, int32_t n, float* d_assign,
+                                          void* stream) {
+  // (B * M pairs, one thread each: the grid's x extent bounds M)
+  if (!val_dims_ok(B, n) || M < 0 || ((int64_t)B * M + 255) / 256 > INT32_MAX)
+    return fail(LINETR_E_ARG, "assign_from_matches: bad shape B=%d M=%d n=%d", B, M, n);
+  if (!d_assign || (M > 0 && !d_lmatches)) return fail(LINETR_E_ARG, "assign_from_matches: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  LT_HIP(hipMemsetAsync(d_assign, 0, (size_t)B * (n + 1) * (n + 1) * 4, st));
+  if (M > 0) {
+    hipLaunchKernelGGL(val_assign_kernel, dim3((unsigned)(((int64_t)B * M + 255) / 256)), dim3(256), 0, st, d_lmatches, B, M, n, d_assign);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// gradient of the criterion (lt_lossgrad.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t LG_OUT_BYTES = 32;   // f64 [3] loss, hardest_positive, hardest_negative | i64 V
+// workspace: device image of the result block | dots | norms (val_dot_kernel writes them) | per-anchor records
+struct LossGradWsLayout { int64_t o_out, o_dots, o_sq0, o_sq1, o_pos, o_neg, o_ties, o_arg, total; };
+LossGradWsLayout loss_grad_ws_layout(int B, int n) {
+  LossGradWsLayout L{};
+  const int64_t rows = align_up((int64_t)B * n * 4, 256);
+  Carve c;
+  L.o_out = c.take(LG_OUT_BYTES);
+  L.o_dots = c.take((int64_t)B * n * n * 4);
+  L.o_sq0 = c.take(rows);
+  L.o_sq1 = c.take(rows);
+  L.o_pos = c.take(2 * rows);
+  L.o_neg = c.take(2 * rows);
+  L.o_ties = c.take(2 * rows);
+  L.o_arg = c.take(2 * rows);
+  L.total = c.o + 256;
+  return L;
+}
+}  // namespace
+
+extern "C" int64_t linetr_desc_loss_grad_workspace_bytes(int32_t B, int32_t n) {
+  return val_dims_ok(B, n) ? loss_grad_ws_layout(B, n).total : 0;
+}
+
+extern "C" int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign,
+                                     int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1, void* h_pinned_out,
+                                     int64_t pinned_bytes, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (int e = criterion_check("desc_loss_grad", n0, n1, B, d_desc0, d_desc1, d_assign, h_pinned_out, pinned_bytes, LG_OUT_BYTES, d_ws, ws_bytes,
+                              linetr_desc_loss_grad_workspace_bytes(B, n0))) return e;
+  const int n = n0;
+  const LossGradWsLayout W = loss_grad_ws_layout(B, n);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  char* base = (char*)d_ws;
+  float* dots = (float*)(base + W.o_dots);
+  float* row_pos = (float*)(base + W.o_pos);
+  float* row_neg = (float*)(base + W.o_neg);
+  int* row_ties = (int*)(base + W.o_ties);
+  int* row_arg = (int*)(base + W.o_arg);
+  double* scalars = (double*)(base + W.o_out);
+  long long* count = (long long*)(base + W.o_out + 24);
+  if (int e = criterion_dots(h, st, d_desc0, d_desc1, B, n, dots, (float*)(base + W.o_sq0), (float*)(base + W.o_sq1))) return e;
+  {
+    ProfScope ps(h, st, "lossgrad_select", 0, 16.0 * B * n * n);
+    hipLaunchKernelGGL(lg_select_kernel, dim3(cdiv(n, VS_ROWS) + cdiv(n, VS_COLS), B), dim3(256), 0, st, (const float*)dots, d_assign, n,
+                       row_pos, row_neg, row_ties, row_arg);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "lossgrad_loss", 0, 16.0 * B * n);
+    hipLaunchKernelGGL(lg_loss_kernel, dim3(1), dim3(256), 0, st, (const float*)row_pos, (const float*)row_neg, B, n, scalars, count);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_grad0 || d_grad1) {
+    const int sides = (d_grad0 ? 1 : 0) + (d_grad1 ? 1 : 0);
+    ProfScope ps(h, st, "lossgrad_grad", 0, sides * 4.0 * B * (2.0 * n * n + (double)n * D));
+    hipLaunchKernelGGL(lg_grad_kernel, dim3(cdiv(n, 64), 2, B), dim3(256), 0, st, d_desc0, d_desc1, (const float*)dots, d_assign, n,
+                       (const float*)row_pos, (const int*)row_ties, (const int*)row_arg, (const long long*)count, d_upstream, d_grad0, d_grad1);
+    LT_LAUNCH_CHECK();
+  }
+  LT_HIP(hipMemcpyAsync(h_pinned_out, scalars, (size_t)LG_OUT_BYTES, hipMemcpyDeviceToHost, st));
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// backward of a point-wise linear layer and of the descriptor head (lt_linbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t LB_MAX_ROWS = (int64_t)1 << 30;
+// workspace: per-chunk tiles of dW | per-chunk column sums
+struct LinBwdWsLayout { int chunks; int64_t o_dw, o_db, total; };
+LinBwdWsLayout lin_bwd_ws_layout(int64_t rows, int N, int K) {
+  LinBwdWsLayout L{};
+  L.chunks = (int)((rows + LB_CHUNK - 1) / LB_CHUNK);
+  Carve c;
+  L.o_dw = c.take((int64_t)L.chunks * N * K * 4);
+  L.o_db = c.take((int64_t)L.chunks * N * 4);
+  L.total = c.o + 256;
+  return L;
+}
+bool lin_dims_ok(int64_t rows, int N, int K) {
+  return rows >= 1 && rows <= LB_MAX_ROWS && N > 0 && K > 0 && N % 64 == 0 && K % 32 == 0 && N <= 1024 && K <= 1024;
+}
+bool lin_stride_ok(int64_t ld, int width) { return ld >= width && ld % 4 == 0; }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }     // (NULL passes: an absent optional pointer)
+
+// the argument checks of the layer's backward, for `who`; LINETR_OK: nothing is wrong
+int lin_bwd_check(const char* who, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg, const float* d_mask,
+                  int64_t rows, int N, int K, const float* d_dx, const float* d_dW, const float* d_db, const void* d_ws, int64_t ws_bytes) {
+  if (!lin_dims_ok(rows, N, K))
+    return fail(LINETR_E_ARG, "%s: bad shape rows=%lld N=%d K=%d (rows 1..2^30, N %% 64 == 0, K %% 32 == 0, both <= 1024)", who, (long long)rows, N, K);
+  if (!lin_stride_ok(ldx, K) || !lin_stride_ok(ldg, N))
+    return fail(LINETR_E_ARG, "%s: row strides %lld / %lld (at least the width, multiples of 4 floats)", who, (long long)ldx, (long long)ldg);
+  if (!d_x || !d_W || !d_g) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if ((d_dW || d_db) && !d_ws) return fail(LINETR_E_ARG, "%s: the weight and bias gradients need the workspace", who);
+  if (!aligned16(d_x) || !aligned16(d_W) || !aligned16(d_g) || !aligned16(d_mask) || !aligned16(d_dx) || !aligned16(d_dW) ||
+      !aligned16(d_db) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  if ((d_dW || d_db) && ws_bytes < lin_bwd_ws_layout(rows, N, K).total)
+    return fail(LINETR_E_ARG, "%s: workspace too small (need %lld)", who, (long long)lin_bwd_ws_layout(rows, N, K).total);
+  return LINETR_OK;
+}
+
+// the launches of the layer's backward; the arguments have been checked
+int lin_bwd_launch(LinetrHandle* h, hipStream_t st, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg,
+                   const float* d_mask, int64_t rows, int N, int K, float* d_dx, float* d_dW, float* d_db, void* d_ws) {
+  if (d_dx) {
+    ProfScope ps(h, st, "linbwd_dx", 2.0 * rows * N * K, 4.0 * (rows * (double)(N + K) + (double)N * K));
+    hipLaunchKernelGGL(lb_dx_kernel, dim3((unsigned)((rows + 63) / 64), cdiv(K, 64)), dim3(256), 0, st, d_g, d_mask, ldg, d_W, rows, N, K,
+                       d_dx, ldx);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dW || d_db) {
+    const LinBwdWsLayout L = lin_bwd_ws_layout(rows, N, K);
+    float* dw_part = d_dW ? (float*)((char*)d_ws + L.o_dw) : nullptr;
+    float* db_part = d_db ? (float*)((char*)d_ws + L.o_db) : nullptr;
+    {
+      ProfScope ps(h, st, "linbwd_dw_partial", d_dW ? 2.0 * rows * N * K : 0.0, 4.0 * (rows * (double)(N + K) + (double)L.chunks * N * K));
+      hipLaunchKernelGGL(lb_dw_partial_kernel, dim3(L.chunks, N / 64, d_dW ? cdiv(K, 64) : 1), dim3(256), 0, st, d_g, d_mask, ldg, d_x, ldx,
+                         rows, N, K, dw_part, db_part);
+      LT_LAUNCH_CHECK();
+    }
+    {
+      const int64_t quads = (d_dW ? (int64_t)N * K / 4 : 0) + (d_db ? N / 4 : 0);
+      ProfScope ps(h, st, "linbwd_dw_reduce", 0, 4.0 * (L.chunks + 1) * (double)N * K);
+      hipLaunchKernelGGL(lb_dw_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, (const float*)dw_part,
+                         (const float*)db_part, L.chunks, N, K, d_dW, d_db);
+      LT_LAUNCH_CHECK();
+    }
+  }
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int32_t linetr_linear_backward_chunk_rows(void) { return LB_CHUNK; }
+
+extern "C" int64_t linetr_linear_backward_workspace_bytes(int64_t rows, int32_t N, int32_t K) {
+  return lin_dims_ok(rows, N, K) ? lin_bwd_ws_layout(rows, N, K).total : 0;
+}
+
+extern "C" int linetr_linear_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_b, int64_t rows,
+                                     int32_t N, int32_t K, int32_t act, float* d_y, int64_t ldy, void* stream) {
+  // every refusal comes before the first launch
+  if (!lin_dims_ok(rows, N, K))
+    return fail(LINETR_E_ARG, "linear_forward: bad shape rows=%lld N=%d K=%d (rows 1..2^30, N %% 64 == 0, K %% 32 == 0, both <= 1024)", (long long)rows, N, K);
+  if (act != 0 && act != 1) return fail(LINETR_E_ARG, "linear_forward: act %d (0 none, 1 ReLU)", act);
+  if (!lin_stride_ok(ldx, K) || !lin_stride_ok(ldy, N))
+    return fail(LINETR_E_ARG, "linear_forward: row strides %lld / %lld (at least the width, multiples of 4 floats)", (long long)ldx, (long long)ldy);
+  if (!d_x || !d_W || !d_y) return fail(LINETR_E_ARG, "linear_forward: null pointer");
+  if (!aligned16(d_x) || !aligned16(d_W) || !aligned16(d_b) || !aligned16(d_y)) return fail(LINETR_E_ARG, "linear_forward: every tensor must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "linear_fwd", 2.0 * rows * N * K, 4.0 * (rows * (double)(N + K) + (double)N * K));
+  hipLaunchKernelGGL(lb_fwd_kernel<false>, dim3((unsigned)((rows + 63) / 64), N / 64), dim3(256), 0, st, d_x, ldx, d_W, d_b, rows, N, K, act, d_y,
+                     ldy, (const float*)nullptr, (float*)nullptr);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_linear_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg,
+                                      const float* d_mask, int64_t rows, int32_t N, int32_t K, float* d_dx, float* d_dW, float* d_db,
+                                      void* d_ws, int64_t ws_bytes, void* stream) {
+  const int rc = lin_bwd_check("linear_backward", d_x, ldx, d_W, d_g, ldg, d_mask, rows, N, K, d_dx, d_dW, d_db, d_ws, ws_bytes);
+  if (rc != LINETR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  return lin_bwd_launch(h, st, d_x, ldx, d_W, d_g, ldg, d_mask, rows, N, K, d_dx, d_dW, d_db, d_ws);
+}
+
+namespace {
+int64_t head_gy_bytes(int64_t rows) { return align_up(rows * D * 4, 256); }
+int head_launch(LinetrHandle* h, hipStream_t st, const float* d_x, const float* d_W, const float* d_b, int64_t rows, float* d_desc,
+                const float* d_g, float* d_gy) {
+  ProfScope ps(h, st, d_g ? "head_fwd_bwd_norm" : "head_fwd", 2.0 * rows * D * D, 4.0 * ((d_g ? 4.0 : 2.0) * rows * D + (double)D * D));
+  hipLaunchKernelGGL(lb_fwd_kernel<true>, dim3((unsigned)((rows + LB_HEAD_ROWS - 1) / LB_HEAD_ROWS)), dim3(256), 0, st, d_x, (int64_t)D, d_W, d_b,
+                     rows, D, D, 0, d_desc, (int64_t)D, d_g, d_gy);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int64_t linetr_head_backward_workspace_bytes(int64_t rows) {
+  return lin_dims_ok(rows, D, D) ? head_gy_bytes(rows) + lin_bwd_ws_layout(rows, D, D).total : 0;
+}
+
+extern "C" int linetr_head_forward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, int64_t rows, float* d_desc,
+                                   void* stream) {
+  if (!lin_dims_ok(rows, D, D)) return fail(LINETR_E_ARG, "head_forward: bad rows=%lld (1..2^30)", (long long)rows);
+  if (!d_x || !d_W || !d_b || !d_desc) return fail(LINETR_E_ARG, "head_forward: null pointer");
+  if (!aligned16(d_x) || !aligned16(d_W) || !aligned16(d_b) || !aligned16(d_desc)) return fail(LINETR_E_ARG, "head_forward: every tensor must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  return head_launch(h, st, d_x, d_W, d_b, rows, d_desc, nullptr, nullptr);
+}
+
+extern "C" int linetr_head_backward(LinetrHandle* h, const float* d_x, const float* d_W, const float* d_b, const float* d_g, int64_t rows,
+                                    float* d_dx, float* d_dW, float* d_db, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!lin_dims_ok(rows, D, D)) return fail(LINETR_E_ARG, "head_backward: bad rows=%lld (1..2^30)", (long long)rows);
+  if (!d_x || !d_W || !d_b || !d_g || !d_ws) return fail(LINETR_E_ARG, "head_backward: null pointer");
+  if (!aligned16(d_b)) return fail(LINETR_E_ARG, "head_backward: every tensor must be 16-byte aligned");
+  if (ws_bytes < linetr_head_backward_workspace_bytes(rows))
+    return fail(LINETR_E_ARG, "head_backward: workspace too small (need %lld)", (long long)linetr_head_backward_workspace_bytes(rows));
+  float* gy = (float*)d_ws;
+  char* rest = (char*)d_ws + head_gy_bytes(rows);
+  const int rc = lin_bwd_check("head_backward", d_x, D, d_W, d_g, D, nullptr, rows, D, D, d_dx, d_dW, d_db, rest, ws_bytes - head_gy_bytes(rows));
+  if (rc != LINETR_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  const int rl = head_launch(h, st, d_x, d_W, d_b, rows, nullptr, d_g, gy);
+  if (rl != LINETR_OK) return rl;
+  return lin_bwd_launch(h, st, d_x, D, d_W, gy, D, nullptr, rows, D, D, d_dx, d_dW, d_db, rest);
+}
+
+// =============================================================================================
+// neighbour-line attention for training: forward with statistics, backward (lt_attnbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t AB_MAX_ROWS = 0x7fffffff;      // cu_sub is int32
+constexpr int AB_MAX_IMAGES = 4096;              // every block walks cu_sub (ab_find_tile): the walk, and the grid of N / 128 + n_images, stay small
+int64_t attn_delta_bytes(int64_t N) { return align_up(N * HEADS * 4, 256); }
+bool attn_stride_ok(int64_t ld) { return ld >= D && ld % 4 == 0; }
+// tiles of 128 rows of any split of N rows into n_images images, at most
+unsigned attn_tiles(int64_t N, int n_images) { return (unsigned)(N / AB_T + n_images); }
+}  // namespace
+
+extern "C" int64_t linetr_sig_attention_backward_workspace_bytes(int64_t N) {
+  return N >= 0 && N <= AB_MAX_ROWS ? attn_delta_bytes(N) + 256 : 0;
+}
+
+extern "C" int linetr_sig_attention_forward(LinetrHandle* h, const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, const float* d_v,
+                                            int64_t ldv, const int32_t* d_cu_sub, int32_t n_images, int64_t N, float* d_msg, int64_t ldo,
+                                            float* d_lse, void* stream) {
+  // every refusal comes before the first launch
+  if (n_images < 1 || n_images > AB_MAX_IMAGES || N < 0 || N > AB_MAX_ROWS)
+    return fail(LINETR_E_ARG, "sig_attention_forward: n_images=%d N=%lld (1 <= n_images <= %d, 0 <= N < 2^31)", n_images, (long long)N, AB_MAX_IMAGES);
+  if (!d_q || !d_k || !d_v || !d_cu_sub || !d_msg || !d_lse) return fail(LINETR_E_ARG, "sig_attention_forward: null pointer");
+  if (!attn_stride_ok(ldq) || !attn_stride_ok(ldk) || !attn_stride_ok(ldv) || !attn_stride_ok(ldo))
+    return fail(LINETR_E_ARG, "sig_attention_forward: row strides %lld / %lld / %lld / %lld (at least 256, multiples of 4 floats)", (long long)ldq,
+                (long long)ldk, (long long)ldv, (long long)ldo);
+  if (!aligned16(d_q) || !aligned16(d_k) || !aligned16(d_v) || !aligned16(d_msg) || !aligned16(d_lse))
+    return fail(LINETR_E_ARG, "sig_attention_forward: every tensor must be 16-byte aligned");
+  if (N == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "sig_attn_fwd_lse", 0, 4.0 * N * (4.0 * D + HEADS));
+  hipLaunchKernelGGL(ab_fwd_kernel, dim3(attn_tiles(N, n_images), HEADS), dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, (const int*)d_cu_sub,
+                     n_images, d_msg, ldo, d_lse);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_sig_attention_backward(LinetrHandle* h, const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, const float* d_v,
+                                             int64_t ldv, const float* d_msg, int64_t ldo, const float* d_lse, const float* d_g, int64_t ldg,
+                                             const int32_t* d_cu_sub, int32_t n_images, int64_t N, float* d_dq, int64_t lddq, float* d_dk,
+                                             int64_t lddk, float* d_dv, int64_t lddv, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (n_images < 1 || n_images > AB_MAX_IMAGES || N < 0 || N > AB_MAX_ROWS)
+    return fail(LINETR_E_ARG, "sig_attention_backward: n_images=%d N=%lld (1 <= n_images <= %d, 0 <= N < 2^31)", n_images, (long long)N, AB_MAX_IMAGES);
+  if (!d_q || !d_k || !d_v || !d_msg || !d_lse || !d_g || !d_cu_sub || !d_ws) return fail(LINETR_E_ARG, "sig_attention_backward: null pointer");
+  if (!attn_stride_ok(ldq) || !attn_stride_ok(ldk) || !attn_stride_ok(ldv) || !attn_stride_ok(ldo) || !attn_stride_ok(ldg) ||
+      (d_dq && !attn_stride_ok(lddq)) || (d_dk && !attn_stride_ok(lddk)) || (d_dv && !attn_stride_ok(lddv)))
+    return fail(LINETR_E_ARG, "sig_attention_backward: every row stride must be at least 256 and a multiple of 4 floats");
+  if (!aligned16(d_q) || !aligned16(d_k) || !aligned16(d_v) || !aligned16(d_msg) || !aligned16(d_lse) || !aligned16(d_g) || !aligned16(d_dq) ||
+      !aligned16(d_dk) || !aligned16(d_dv) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "sig_attention_backward: every tensor must be 16-byte aligned");
+  if (ws_bytes < linetr_sig_attention_backward_workspace_bytes(N))
+    return fail(LINETR_E_ARG, "sig_attention_backward: workspace too small (need %lld)", (long long)linetr_sig_attention_backward_workspace_bytes(N));
+  if (N == 0 || (!d_dq && !d_dk && !d_dv)) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  float* delta = (float*)d_ws;
+  const dim3 grid(attn_tiles(N, n_images), HEADS);
+  if (d_dq || d_dk) {       // dV reads P alone
+    ProfScope ps(h, st, "sig_attn_bwd_delta", 0, 4.0 * N * (2.0 * D + HEADS));
+    hipLaunchKernelGGL(ab_delta_kernel, dim3((unsigned)((N + 31) / 32), HEADS), dim3(64), 0, st, d_g, ldg, d_msg, ldo, N, delta);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dk || d_dv) {
+    ProfScope ps(h, st, "sig_attn_bwd_dkv", 0, 4.0 * N * (6.0 * D + 2.0 * HEADS));
+    hipLaunchKernelGGL(ab_dkv_kernel, grid, dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, d_g, ldg, d_lse, (const float*)delta,
+                       (const int*)d_cu_sub, n_images, d_dk, lddk, d_dv, lddv);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dq) {
+    ProfScope ps(h, st, "sig_attn_bwd_dq", 0, 4.0 * N * (5.0 * D + 2.0 * HEADS));
+    hipLaunchKernelGGL(ab_dq_kernel, grid, dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, d_g, ldg, d_lse, (const float*)delta,
+                       (const int*)d_cu_sub, n_images, d_dq, lddq);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// ground-truth line assignment of a homography pair (lt_gtassign.h)
+// =============================================================================================
+
+namespace {
+// workspace (sized for the double instance): projected lines of both sides | the four angle arrays | ballot words | found
+struct GtLayout { int W64; int64_t o_proj0, o_proj1, o_ang, o_words, o_found, total; };
+GtLayout gt_layout(int B, int n0, int n1) {
+  GtLayout L{};
+  L.W64 = cdiv(n1, 64);
+  Carve c;
+  L.o_proj0 = c.take((int64_t)B * n0 * 4 * 8);
+  L.o_proj1 = c.take((int64_t)B * n1 * 4 * 8);
+  L.o_ang = c.take((int64_t)B * 2 * ((int64_t)n0 + n1) * 8);
+  L.o_words = c.take((int64_t)B * n0 * L.W64 * 8);
+  L.o_found = c.take((int64_t)B * 4);
+  L.total = c.o + 256;
+  return L;
+}
+bool gt_dims_ok(int B, int n0, int n1) { return B > 0 && B <= VS_MAX_B && n0 > 0 && n0 <= VS_MAX_N && n1 > 0 && n1 <= VS_MAX_N; }
+
+template <typename T>
+int gt_assign_launch(LinetrHandle* h, hipStream_t st, const GtLayout& L, const void* d_lines0, int n0, const void* d_lines1, int n1,
+                     const double* d_H, int B, const int32_t* d_count0, const int32_t* d_count1, double thres_reprojected,
+                     double thres_angdiff, double min_overlap_ratio, int pad, float* d_assign, int32_t* d_lmatches, int M,
+                     int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir, void* d_proj0, void* d_proj1, char* base) {
+  const T* lines0 = (const T*)d_lines0;
+  const T* lines1 = (const T*)d_lines1;
+  T* proj0 = d_proj0 ? (T*)d_proj0 : (T*)(base + L.o_proj0);
+  T* proj1 = d_proj1 ? (T*)d_proj1 : (T*)(base + L.o_proj1);
+  T* ang0 = (T*)(base + L.o_ang);
+  T* angp0 = ang0 + (int64_t)B * n0;
+  T* ang1 = angp0 + (int64_t)B * n0;
+  T* angp1 = ang1 + (int64_t)B * n1;
+  const bool list = d_lmatches || d_found;
+  unsigned long long* words = list ? (unsigned long long*)(base + L.o_words) : nullptr;
+  const double pairs = (double)B * n0 * n1;
+  {
+    ProfScope ps(h, st, "gt_lines", 0, (double)B * ((double)n0 + n1) * (4 * 2 + 2) * sizeof(T));
+    hipLaunchKernelGGL(gt_lines_kernel<T>, dim3(cdiv(n0, 256), B), dim3(256), 0, st, lines0, n0, d_H, 0, proj0, ang0, angp0);
+    hipLaunchKernelGGL(gt_lines_kernel<T>, dim3(cdiv(n1, 256), B), dim3(256), 0, st, lines1, n1, d_H, 1, proj1, ang1, angp1);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "gt_pair", 0, (d_assign ? 4.0 * B * (n0 + pad) * (n1 + pad) : 0.0) + (d_match_dir ? 2.0 * pairs : 0.0) +
+                                          (d_overlap_dir ? 2.0 * pairs * sizeof(T) : 0.0) + (words ? (double)B * n0 * L.W64 * 8 : 0.0));
+    hipLaunchKernelGGL(gt_pair_kernel<T>, dim3(cdiv(n1 + pad, 64), cdiv(n0 + pad, GT_ROWS), B), dim3(256), 0, st, lines0, lines1,
+                       (const T*)proj0, (const T*)proj1, (const T*)ang0, (const T*)ang1, (const T*)angp0, (const T*)angp1, n0, n1,
+                       d_count0, d_count1, (T)thres_reprojected, (T)thres_angdiff, min_overlap_ratio, pad, d_assign, d_match_dir,
+                       (T*)d_overlap_dir, words);
+    LT_LAUNCH_CHECK();
+  }
+  if (list) {
+    ProfScope ps(h, st, "gt_list", 0, (double)B * n0 * L.W64 * 8 + (d_lmatches ? 8.0 * B * M : 0.0));
+    hipLaunchKernelGGL(gt_list_kernel, dim3(B), dim3(256), 0, st, (const unsigned long long*)words, n0, L.W64, M, d_lmatches,
+                       d_found ? d_found : (int32_t*)(base + L.o_found));
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int64_t linetr_gt_assign_workspace_bytes(int32_t B, int32_t n0, int32_t n1) {
+  return gt_dims_ok(B, n0, n1) ? gt_layout(B, n0, n1).total : 0;
+}
+
+extern "C" int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void* d_lines0, int32_t n0, const void* d_lines1, int32_t n1,
+                                const double* d_H, int32_t B, const int32_t* d_count0, const int32_t* d_count1,
+                                double thres_reprojected, double thres_angdiff, double min_overlap_ratio, int32_t pad, float* d_assign,
+                                int32_t* d_lmatches, int32_t M, int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir,
+                                void* d_proj0, void* d_proj1, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  if (!gt_dims_ok(B, n0, n1))
+    return fail(LINETR_E_ARG, "gt_assign: bad shape B=%d n0=%d n1=%d (B 1..%d, n 1..%d)", B, n0, n1, VS_MAX_B, VS_MAX_N);
+  if (M < 0) return fail(LINETR_E_ARG, "gt_assign: M = %d", M);
+  if (pad != 0 && pad != 1) return fail(LINETR_E_ARG, "gt_assign: pad %d (0, or 1 for the dustbin row and column)", pad);
+  if (coord_type != LINETR_COORD_F32 && coord_type != LINETR_COORD_F64)
+    return fail(LINETR_E_ARG, "gt_assign: coordinate type %d (0 float32, 1 float64)", coord_type);
+  if (!d_lines0 || !d_lines1 || !d_H || !d_ws) return fail(LINETR_E_ARG, "gt_assign: null pointer");
+  const GtLayout L = gt_layout(B, n0, n1);
+  if (ws_bytes < L.total) return fail(LINETR_E_ARG, "gt_assign: workspace too small (need %lld)", (long long)L.total);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  if (coord_type == LINETR_COORD_F32)
+    return gt_assign_launch<float>(h, st, L, d_lines0, n0, d_lines1, n1, d_H, B, d_count0, d_count1, thres_reprojected, thres_angdiff,
+                                   min_overlap_ratio, pad, d_assign, d_lmatches, M, d_found, d_match_dir, d_overlap_dir, d_proj0,
+                                   d_proj1, (char*)d_ws);
+  return gt_assign_launch<double>(h, st, L, d_lines0, n0, d_lines1, n1, d_H, B, d_count0, d_count1, thres_reprojected, thres_angdiff,
+                                  min_overlap_ratio, pad, d_assign, d_lmatches, M, d_found, d_match_dir, d_overlap_dir, d_proj0,
+                                  d_proj1, (char*)d_ws);
+}

@@ -67,6 +67,11 @@ inline int fail(int code, const char* fmt, ...) {
   } while (0)
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// A workspace carved into 256-byte aligned segments: take(bytes) is the next segment's offset, `o` what has been handed out so far.
+struct Carve {
+  int64_t o = 0;
+  int64_t take(int64_t bytes) { const int64_t at = o; o += align_up(bytes, 256); return at; }
+};
 // A launch with more dynamic LDS than the default limit needs the kernel opted in first, on every device it runs on.  Makes that
 // call once per kernel and device (one flag word per kernel, one bit per device) and is safe from several host threads: a thread
 // sees a device's bit only after the attribute is set there; two first callers at most repeat the same call.  A refusal is returned,

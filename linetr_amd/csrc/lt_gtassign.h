@@ -19,7 +19,7 @@
 // both sides: an entry can differ from the reference's only where |angle difference % 180 - thres_angdiff| (or the distance of the
 // difference from the wrap at 180 / 360) is within a few ulp of the angles.
 #pragma once
-#include "lt_keypoints.h"
+#include "lt_parts.h"
 
 namespace lt {
 

@@ -3,7 +3,9 @@
 //   linetr_core.hip   lifetime (float64 weight preparation), host pre-filter, collective, profiling entry points
 //   linetr_net.hip    tokenise / forward / describe + the GEMM dispatcher and every model kernel (the experiments build includes
 //                     experiments/csrc/lt_x_net.h into it: the host code of its alternative paths and the hooks that select them)
-//   linetr_match.hip  matcher, dense-map producer, slab packing
+//   linetr_match.hip  matcher, dense-map producer, slab packing, SuperPoint's key-point branch
+//   linetr_train.hip  training and evaluation: validation step, criterion gradient, backward of the 1x1 layers, the descriptor head and
+//                     the neighbour-line attention, ground-truth line assignment
 //   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once
 #include <map>

@@ -9,7 +9,7 @@
 // (the descriptor lookup of the branch, sp_kp_desc_kernel, sits next to the sampler it shares: lt_token.h)
 // Every step of the detector is a compare, a select or a copy: its key points and scores equal torch's bit for bit.
 #pragma once
-#include "lt_common.h"
+#include "lt_parts.h"
 
 namespace lt {
 
@@ -96,23 +96,6 @@ __global__ __launch_bounds__(256) void sp_nms_kernel(const float* __restrict__ s
       if (wi + 1 < Wm) row[wi + 1] = (unsigned)(bal >> 32);
     }
   }
-}
-
-// exclusive scan over up to 256 values per pass, one per thread; returns the thread's exclusive prefix and the total in `sum`
-__device__ __forceinline__ int kp_block_scan(int c, int* part, int& sum) {
-  const int t = threadIdx.x;
-  part[t] = c;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    const int v = t >= off ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  const int inc = part[t];
-  sum = part[255];
-  __syncthreads();
-  return inc - c;
 }
 
 // one block per image: row_off[b][y] = number of set bits in rows < y, found[b] = the image's count (uncapped)

@@ -4,7 +4,7 @@
 //   Evaluate_PR          evaluations/evaluate_pr.py:10-35         TP / FP / FN / TN, precision / recall / F1 per item
 // and the ground-truth matrix train.py:176-183 scatters from the loader's match list.
 // Three launches for a batch of B items with n sub-lines on both sides:
-//   val_dot_kernel     grid (tiles, tiles, B): <d0[a], d1[c]> ONCE, by the matcher's exact-fp32 MFMA tile (dot_tile_64x64, lt_match.h:
+//   val_dot_kernel     grid (tiles, tiles, B): <d0[a], d1[c]> ONCE, by the matcher's exact-fp32 MFMA tile (dot_tile_64x64, lt_parts.h:
 //                      a selection must not inherit a split's error), and the squared norms of both sides;
 //   val_select_kernel  grid (row blocks + column blocks, B): per anchor row (n rows of D, then n rows of D^T) the hardest positive
 //                      and its semi-hard negative; per row / column the first-index argmin of the matcher's score;
@@ -13,7 +13,7 @@
 // Deterministic: every reduction has a fixed order (max / min / integer sums are order-independent, the loss sum is a float64 tree
 // of fixed shape); no floating-point atomics.
 #pragma once
-#include "lt_match.h"
+#include "lt_parts.h"
 
 namespace lt {
 

@@ -1,0 +1,304 @@
+"""The training and evaluation surface of Engine (a mixin: engine.py declares `class Engine(_TrainSurface, _DebugSurface)` and holds
+the helpers used here -- _call, _f32, _workspace, _host_stage, _event, _await_stage): ground truth, the validation step, the criterion with
+its gradient, and forward / backward of the layers that have a native backward (csrc/linetr_train.hip)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._shapes import D, as_rows_weight, check_pointwise_shapes, ptr
+
+
+class _TrainSurface:
+    def assign_from_matches(self, lmatches: torch.Tensor, n: int) -> torch.Tensor:
+        """train.py:176-183 on the device (linetr_assign_from_matches): the loader's lmatches [B, M, 2] (rows whose first entry is -1
+        are padding) -> mat_assign_sublines [B, n+1, n+1] float32."""
+        lm = lmatches.to(device=self.device, dtype=torch.int32).contiguous()
+        B, M = int(lm.shape[0]), int(lm.shape[1])
+        assign = torch.empty((B, n + 1, n + 1), dtype=torch.float32, device=self.device)
+        self._call("linetr_assign_from_matches", lm.data_ptr(), B, M, int(n), assign.data_ptr())
+        return assign
+
+    def _criterion_args(self, who, desc0, desc1, assign, lmatches):
+        """What val_step and loss_step (`who`) take, checked and brought to what the criterion kernels read: the two descriptor sets as
+        [B*n, 256] rows, B, n0, n1 and mat_assign_sublines [B, n+1, n+1] (made from `lmatches` where that is what was given)."""
+        if (assign is None) == (lmatches is None):
+            raise ValueError(f"{who}: give exactly one of assign / lmatches")
+        d0, B0, _ = self._act_rows(desc0, D, "line descriptors", strided=False)
+        d1, B1, _ = self._act_rows(desc1, D, "line descriptors", strided=False)
+        B = int((assign if assign is not None else lmatches).shape[0])
+        if B <= 0 or any(b is not None and b != B for b in (B0, B1)) or d0.shape[0] % B or d1.shape[0] % B:
+            raise ValueError(f"{who}: the descriptors and the ground truth disagree about the batch size")
+        n0, n1 = int(d0.shape[0]) // B, int(d1.shape[0]) // B
+        if assign is None:
+            assign = self.assign_from_matches(lmatches, n0)
+        else:
+            assign = self._f32(assign)
+            if n0 == n1 and tuple(assign.shape) != (B, n0 + 1, n0 + 1):
+                raise ValueError(f"{who}: assign must be [{B}, {n0 + 1}, {n0 + 1}], got {tuple(assign.shape)}")
+        return d0, d1, B, n0, n1, assign
+
+    def val_step(self, desc0, desc1, assign=None, lmatches=None, nn_thresh=0.7, mutual=True):
+        """The reference's validation step after the forward, in one native call (linetr_val_step): descriptor_loss
+        (evaluations/criteria.py), nn_matcher_batches (evaluations/matcher.py) and the precision / recall / F1 of
+        evaluations/evaluate_pr.py.  desc0 / desc1: [B, 256, n] or [B*n, 256] (then `assign` / `lmatches` gives B); the ground truth is
+        either `assign` [B, n+1, n+1] (mat_assign_sublines) or the loader's `lmatches` [B, M, 2].  One host wait.  Returns a dict:
+        loss, hardest_positive, hardest_negative (float; NaN when count == 0), count, TP / FP / FN / TN (int32 [B]), precision /
+        recall / f1 (float64 [B]) and the device tensors row_pos, row_neg [B, 2n] (row_neg -1: no anchor, or no semi-hard negative)
+        and match01 [B, n]."""
+        d0, d1, B, n0, n1, assign = self._criterion_args("val_step", desc0, desc1, assign, lmatches)
+        n = n0
+        offs = (C.c_int64 * 4)()
+        out_bytes = int(self._L.linetr_val_step_output_bytes(B, offs))
+        ws = self._workspace("val_step", max(int(self._L.linetr_val_step_workspace_bytes(B, n)), 256))
+        stage, *gen = self._host_stage(out_bytes)
+        row_pos = torch.empty((B, 2 * n), dtype=torch.float32, device=self.device)
+        row_neg = torch.empty((B, 2 * n), dtype=torch.float32, device=self.device)
+        match01 = torch.empty((B, n), dtype=torch.int32, device=self.device)
+        self._call("linetr_val_step", d0.data_ptr(), n0, d1.data_ptr(), n1, assign.data_ptr(), B, float(nn_thresh), int(bool(mutual)),
+                   row_pos.data_ptr(), row_neg.data_ptr(), match01.data_ptr(), stage.data_ptr(), stage.numel(), ws.data_ptr(), ws.numel())
+        self._await_stage("val_step", self._event(), *gen)
+        host = stage.numpy()
+        scalars = host[offs[0]:offs[0] + 24].view(np.float64)
+        counts = host[offs[2]:offs[2] + 16 * B].view(np.int32).reshape(B, 4).copy()
+        scores = host[offs[3]:offs[3] + 24 * B].view(np.float64).reshape(B, 3).copy()
+        return {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
+                "count": int(host[offs[1]:offs[1] + 8].view(np.int64)[0]),
+                "TP": counts[:, 0], "FP": counts[:, 1], "FN": counts[:, 2], "TN": counts[:, 3],
+                "precision": scores[:, 0], "recall": scores[:, 1], "f1": scores[:, 2],
+                "row_pos": row_pos, "row_neg": row_neg, "match01": match01}
+
+    def loss_step(self, desc0, desc1, assign=None, lmatches=None, upstream=None):
+        """descriptor_loss AND its gradient with respect to both descriptor sets in one native call (linetr_desc_loss_grad): what
+        `loss.backward()` leaves in line_desc0.grad / line_desc1.grad when the reference's criterion (evaluations/criteria.py) is
+        differentiated by torch.  Inputs as val_step takes them; `upstream`: the gradient arriving at the loss, a one-element float32
+        device tensor (read on the device: no host wait for it), default 1.  One host wait.  Returns a dict: loss, hardest_positive,
+        hardest_negative (float; NaN when count == 0), count, and the device tensors grad0 / grad1 in the shape of desc0 / desc1
+        ([B, 256, n] inputs: the transposed view of the [B*n, 256] rows the kernels write); count == 0: both all zero.
+        Like val_step, every call uses the engine's one cached workspace whatever the stream: calls from two streams are safe only
+        because each ends in its host wait before it returns."""
+        d0, d1, B, n0, n1, assign = self._criterion_args("loss_step", desc0, desc1, assign, lmatches)
+        n = n0
+        if upstream is not None:
+            upstream = self._f32(upstream.detach().reshape(-1))
+            if upstream.numel() != 1:
+                raise ValueError("loss_step: upstream must hold one element")
+        ws = self._workspace("loss_step", max(int(self._L.linetr_desc_loss_grad_workspace_bytes(B, n)), 256))
+        stage, *gen = self._host_stage(32)
+        grad0, grad1 = torch.empty_like(d0), torch.empty_like(d1)
+        self._call("linetr_desc_loss_grad", d0.data_ptr(), n0, d1.data_ptr(), n1, assign.data_ptr(), B, ptr(upstream), grad0.data_ptr(),
+                   grad1.data_ptr(), stage.data_ptr(), stage.numel(), ws.data_ptr(), ws.numel())
+        self._await_stage("loss_step", self._event(), *gen)
+        host = stage.numpy()
+        scalars = host[:24].view(np.float64)
+        grad0, grad1 = (g.view(B, n, D).transpose(1, 2) if d.dim() == 3 else g for g, d in ((grad0, desc0), (grad1, desc1)))
+        return {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
+                "count": int(host[24:32].view(np.int64)[0]), "grad0": grad0, "grad1": grad1}
+
+    # ------------------------------------------------------------------ backward of the 1x1 layers and the descriptor head
+    def _act_rows(self, t: torch.Tensor, width: int, what: str, strided=True):
+        """Activations as the point-wise layers read them: a float32 [rows, width] tensor whose rows are `stride(0)` floats apart
+        (a multiple of 4, 16-byte aligned; anything else is copied).  Accepts [B, width, n] (contiguous, or the transposed view of
+        [B*n, width] rows: no copy then) or the rows themselves.  Returns (rows, B or None, n or None)."""
+        t = t.detach()
+        if t.dim() == 3:
+            if int(t.shape[1]) != width:
+                raise ValueError(f"{what} must be [B, {width}, n] or [rows, {width}], got {tuple(t.shape)}")
+            B, n = int(t.shape[0]), int(t.shape[2])
+            return self._f32(t.transpose(1, 2)).view(B * n, width), B, n
+        if t.dim() != 2 or int(t.shape[1]) != width:
+            raise ValueError(f"{what} must be [B, {width}, n] or [rows, {width}], got {tuple(t.shape)}")
+        ok = (strided and t.device == self.device and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) >= width
+              and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+        return (t if ok else self._f32(t)), None, None
+
+    @staticmethod
+    def _like_input(rows: torch.Tensor, B, n):
+        """[B*n, C] rows back in the shape of a [B, C, n] input (the transposed view), or the rows of a 2-D input"""
+        return rows if B is None else rows.view(B, n, rows.shape[1]).transpose(1, 2)
+
+    def _weight_2d(self, weight: torch.Tensor) -> torch.Tensor:
+        """a Conv1d(k=1) [N, K, 1] or a Linear [N, K] weight as [N, K] float32 on the device"""
+        return self._f32(as_rows_weight(weight.detach()))
+
+    def _stream_workspace(self, tag: str, nbytes: int) -> torch.Tensor:
+        """the cached workspace of `tag` for the current stream (these calls return without a host wait: one per stream)"""
+        return self._workspace(f"{tag}:{torch.cuda.current_stream(self.device).cuda_stream}", max(int(nbytes), 256))
+
+    def linear_forward(self, x, weight, bias=None, relu=False) -> torch.Tensor:
+        """A point-wise linear layer (Conv1d(k=1) / Linear) on the unfolded weight, by exact-fp32 MFMA (linetr_linear_forward):
+        y = act(x W^T + b).  x: [B, K, n] or [rows, K]; weight [N, K] or [N, K, 1]; y in x's layout ([B, N, n] inputs: the transposed
+        view of the [B*n, N] rows the kernel writes).  No host wait."""
+        N, K = check_pointwise_shapes(x, weight, bias)
+        W = self._weight_2d(weight)
+        xr, B, n = self._act_rows(x, K, "x")
+        b = self._f32(bias.detach().reshape(-1)) if bias is not None else None
+        y = torch.empty((xr.shape[0], N), dtype=torch.float32, device=self.device)
+        self._call("linetr_linear_forward", xr.data_ptr(), xr.stride(0), W.data_ptr(), ptr(b), int(xr.shape[0]), N, K, int(bool(relu)),
+                   y.data_ptr(), N)
+        return self._like_input(y, B, n)
+
+    def linear_backward(self, x, weight, grad_out, mask=None, need=(True, True, True)):
+        """The layer's backward (linetr_linear_backward): (dx, dW, db) for the gradient `grad_out` arriving at y = act(x W^T + b);
+        `mask`: the layer's own post-ReLU output (the gradient passes where it is > 0), None for no activation.  dx in x's layout, dW in
+        the weight's shape, db [N]; `need` = which of the three to compute (the others are None).  Deterministic; no host wait."""
+        W = self._weight_2d(weight)
+        N, K = int(W.shape[0]), int(W.shape[1])
+        xr, B, n = self._act_rows(x, K, "x")
+        g, _, _ = self._act_rows(grad_out, N, "grad_out", strided=mask is None)
+        m = self._act_rows(mask, N, "mask", strided=False)[0] if mask is not None else None
+        rows = int(xr.shape[0])
+        if int(g.shape[0]) != rows or (m is not None and int(m.shape[0]) != rows):
+            raise ValueError("linear_backward: x, grad_out and mask disagree about the number of rows")
+        dx = torch.empty_strided((rows, K), (xr.stride(0), 1), dtype=torch.float32, device=self.device) if need[0] else None
+        dW = torch.empty((N, K), dtype=torch.float32, device=self.device) if need[1] else None
+        db = torch.empty((N,), dtype=torch.float32, device=self.device) if need[2] else None
+        ws = self._stream_workspace("linear_bwd", self._L.linetr_linear_backward_workspace_bytes(rows, N, K))
+        self._call("linetr_linear_backward", xr.data_ptr(), xr.stride(0), W.data_ptr(), g.data_ptr(), g.stride(0), ptr(m), rows, N, K, ptr(dx),
+                   ptr(dW), ptr(db), ws.data_ptr(), ws.numel())
+        return (self._like_input(dx, B, n) if dx is not None else None, dW.view(weight.shape) if dW is not None else None, db)
+
+    def _head_args(self, x, weight, bias):
+        W = self._weight_2d(weight)
+        if tuple(W.shape) != (D, D) or bias is None or bias.numel() != D:
+            raise ValueError(f"the descriptor head is final_proj: a [{D}, {D}] weight and a [{D}] bias")
+        xr, B, n = self._act_rows(x, D, "x", strided=False)
+        return xr, W, self._f32(bias.detach().reshape(-1)), B, n
+
+    def head_forward(self, x, weight, bias) -> torch.Tensor:
+        """The descriptor head (models/line_transformer.py:245-246; linetr_head_forward): line_desc = F.normalize(final_proj(x), dim=1),
+        one kernel.  x: the pre-head features [B, 256, n] or [rows, 256]; line_desc in x's layout.  No host wait."""
+        xr, W, b, B, n = self._head_args(x, weight, bias)
+        desc = torch.empty_like(xr)
+        self._call("linetr_head_forward", xr.data_ptr(), W.data_ptr(), b.data_ptr(), int(xr.shape[0]), desc.data_ptr())
+        return self._like_input(desc, B, n)
+
+    def head_backward(self, x, weight, bias, grad_desc, need=(True, True, True)):
+        """The head's backward (linetr_head_backward): (dx, dW, db) for the gradient `grad_desc` arriving at line_desc, as torch autograd
+        differentiates F.normalize(final_proj(x)).  Shapes and `need` as linear_backward.  Deterministic; no host wait."""
+        xr, W, b, B, n = self._head_args(x, weight, bias)
+        g = self._act_rows(grad_desc, D, "grad_desc", strided=False)[0]
+        rows = int(xr.shape[0])
+        if int(g.shape[0]) != rows:
+            raise ValueError("head_backward: x and grad_desc disagree about the number of rows")
+        dx = torch.empty_like(xr) if need[0] else None
+        dW = torch.empty((D, D), dtype=torch.float32, device=self.device) if need[1] else None
+        db = torch.empty((D,), dtype=torch.float32, device=self.device) if need[2] else None
+        ws = self._stream_workspace("head_bwd", self._L.linetr_head_backward_workspace_bytes(rows))
+        self._call("linetr_head_backward", xr.data_ptr(), W.data_ptr(), b.data_ptr(), g.data_ptr(), rows, ptr(dx), ptr(dW), ptr(db),
+                   ws.data_ptr(), ws.numel())
+        return (self._like_input(dx, B, n) if dx is not None else None, dW.view(weight.shape) if dW is not None else None, db)
+
+    # ------------------------------------------------------------------ neighbour-line attention for training
+    def _cu_sub_dev(self, cu_sub) -> torch.Tensor:
+        """sub-line offsets [n_images + 1] as an int32 tensor on the device (a device tensor is taken as it is: no host wait)"""
+        cu = cu_sub if isinstance(cu_sub, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cu_sub, dtype=np.int32)))
+        cu = cu.detach().reshape(-1)
+        if cu.numel() < 2:
+            raise ValueError("cu_sub must hold n_images + 1 >= 2 offsets")
+        if cu.device != self.device or cu.dtype != torch.int32 or not cu.is_contiguous():
+            cu = cu.to(device=self.device, dtype=torch.int32).contiguous()
+        return cu
+
+    def _attn_rows(self, named, N=None):
+        """head-major [N, 256] rows as the attention kernels read them: strided row views pass as they are, anything else is copied"""
+        rows = [self._act_rows(t, D, name)[0] for name, t in named]
+        N = int(rows[0].shape[0]) if N is None else N
+        for (name, _), r in zip(named, rows):
+            if r.dim() != 2 or int(r.shape[0]) != N:
+                raise ValueError(f"{name} must be [{N}, {D}] head-major rows, got {tuple(r.shape)}")
+        return rows, N
+
+    def sig_attention_forward(self, q, k, v, cu_sub):
+        """The neighbour-line attention softmax(q^T k / 8) v of models/line_transformer.py:132-136 with its softmax statistics
+        (linetr_sig_attention_forward; exact-fp32 MFMA).  q, k, v: head-major rows [N, 256] (column h*64 + d), q UNSCALED; each may be a
+        strided row view, e.g. a column block of one [N, 768] buffer.  cu_sub [n_images + 1]: one image is one softmax domain (a device
+        int32 tensor is read in place).  Returns (message [N, 256] head-major, lse [N, 4] = m + log l).  No host wait."""
+        (qr, kr, vr), N = self._attn_rows((("q", q), ("k", k), ("v", v)))
+        cu = self._cu_sub_dev(cu_sub)
+        msg = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        lse = torch.empty((N, 4), dtype=torch.float32, device=self.device)
+        if N == 0:                                   # (an empty tensor has no address to hand over)
+            return msg, lse
+        self._call("linetr_sig_attention_forward", qr.data_ptr(), qr.stride(0), kr.data_ptr(), kr.stride(0), vr.data_ptr(), vr.stride(0),
+                   cu.data_ptr(), cu.numel() - 1, N, msg.data_ptr(), D, lse.data_ptr())
+        return msg, lse
+
+    def sig_attention_backward(self, q, k, v, o, lse, grad_out, cu_sub, need=(True, True, True)):
+        """The attention's backward (linetr_sig_attention_backward): (dq, dk, dv) [N, 256] head-major for the gradient `grad_out` arriving at
+        the message `o`; q, k, v, o, lse as sig_attention_forward took and returned them.  P is recomputed from q, k and lse; nothing n x n
+        is stored.  `need` = which of the three to compute (the others are None).  Deterministic; no host wait."""
+        (qr, kr, vr, orow, g), N = self._attn_rows((("q", q), ("k", k), ("v", v), ("o", o), ("grad_out", grad_out)))
+        ls = self._f32(lse.detach())
+        if tuple(ls.shape) != (N, 4):
+            raise ValueError(f"lse must be [{N}, 4], got {tuple(ls.shape)}")
+        cu = self._cu_sub_dev(cu_sub)
+        dq, dk, dv = (torch.empty((N, D), dtype=torch.float32, device=self.device) if n else None for n in need)
+        if N == 0:
+            return dq, dk, dv
+        ws = self._stream_workspace("sig_attn_bwd", self._L.linetr_sig_attention_backward_workspace_bytes(N))
+        self._call("linetr_sig_attention_backward", qr.data_ptr(), qr.stride(0), kr.data_ptr(), kr.stride(0), vr.data_ptr(), vr.stride(0),
+                   orow.data_ptr(), orow.stride(0), ls.data_ptr(), g.data_ptr(), g.stride(0), cu.data_ptr(), cu.numel() - 1, N, ptr(dq), D,
+                   ptr(dk), D, ptr(dv), D, ws.data_ptr(), ws.numel())
+        return dq, dk, dv
+
+    def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
+                          counts=None, dustbin=True, directions=False, projected=False):
+        """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes
+        per pair with find_line_matches / calculate_line_overlaps in both directions (dataloaders/build_homography_dataset.py:210-237,
+        dataloaders/utils/util_lines.py:67-171).
+
+        lines0 [B, n0, 2, 2] / lines1 [B, n1, 2, 2] (or [n, 2, 2] for one pair; then H is [3, 3]): the sub-lines' end points, torch or
+        NumPy.  float32 on both sides computes as the reference does; float64 on either side selects the float64 instance.  H [B, 3, 3]
+        takes image-0 pixels to image-1 pixels; its inverse is np.linalg.inv(H), as in the builder.  `counts` = (count0 [B], count1 [B]):
+        the valid prefix of each item.  max_matches (M) defaults to the builder's int(max_sublines * 1.5) with max_sublines = n0; an item
+        with more pairs than that makes the call run once more with room for all of them (0: no list, `found` only).  Returns a dict of device tensors:
+        assign [B, n0 + 1, n1 + 1] float32 (`dustbin`; what val_step(assign=...) takes) or [B, n0, n1], lmatches [B, M, 2] int32 with -1
+        behind each list, found [B] int32; with `directions` match_dir [B, 2, n0, n1] uint8 and overlap_dir [B, 2, n0, n1] (direction 1
+        as [i][j]); with `projected` proj0 / proj1.  One host wait (the list sizes)."""
+        def arr(x):
+            return x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        l0, l1 = arr(lines0), arr(lines1)
+        Hm = np.asarray(H.detach().cpu() if isinstance(H, torch.Tensor) else H, dtype=np.float64)
+        if l0.dim() == 3 and l1.dim() == 3 and Hm.shape == (3, 3):
+            l0, l1, Hm = l0[None], l1[None], Hm[None]
+        if l0.dim() != 4 or l1.dim() != 4 or tuple(l0.shape[2:]) != (2, 2) or tuple(l1.shape[2:]) != (2, 2) or l0.shape[0] != l1.shape[0]:
+            raise ValueError(f"line_ground_truth: lines must be [B, n, 2, 2], got {tuple(l0.shape)} and {tuple(l1.shape)}")
+        B, n0, n1 = int(l0.shape[0]), int(l0.shape[1]), int(l1.shape[1])
+        if Hm.shape != (B, 3, 3):
+            raise ValueError(f"line_ground_truth: H must be [{B}, 3, 3], got {Hm.shape}")
+        dt = torch.float64 if torch.float64 in (l0.dtype, l1.dtype) else torch.float32
+        l0, l1 = (t.to(device=self.device, dtype=dt).contiguous() for t in (l0, l1))
+        Hd = torch.from_numpy(np.stack([Hm, np.linalg.inv(Hm)], axis=1).reshape(B, 2, 9)).to(self.device)
+        c0 = c1 = None
+        if counts is not None:
+            c0, c1 = (arr(c).to(device=self.device, dtype=torch.int32).contiguous() for c in counts)
+            if tuple(c0.shape) != (B,) or tuple(c1.shape) != (B,):
+                raise ValueError("line_ground_truth: counts must be two arrays of B entries")
+        M = int(n0 * 1.5) if max_matches is None else int(max_matches)
+        pad = int(bool(dustbin))
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+        with torch.cuda.device(self.device):     # a heads-only engine has no handle: the current device is used
+            assign = new((B, n0 + pad, n1 + pad), torch.float32)
+            found = new((B,), torch.int32)
+            mdir = new((B, 2, n0, n1), torch.uint8) if directions else None
+            odir = new((B, 2, n0, n1), dt) if directions else None
+            p0, p1 = (new((B, n0, 2, 2), dt), new((B, n1, 2, 2), dt)) if projected else (None, None)
+            ws = self._workspace("gt_assign", int(self._L.linetr_gt_assign_workspace_bytes(B, n0, n1)))
+            while True:
+                lm = new((B, M, 2), torch.int32)
+                self._call("linetr_gt_assign", int(dt == torch.float64), l0.data_ptr(), n0, l1.data_ptr(), n1, Hd.data_ptr(), B, ptr(c0), ptr(c1),
+                           float(thres_reprojected), float(thres_angdiff), float(min_overlap_ratio), pad, assign.data_ptr(), lm.data_ptr(), M,
+                           found.data_ptr(), ptr(mdir), ptr(odir), ptr(p0), ptr(p1), ws.data_ptr(), ws.numel())
+                most = int(found.max())
+                if most <= M or M == 0:          # (max_matches = 0: no list is wanted, `found` alone)
+                    break
+                M = most                         # once more with room for every pair
+        out = {"assign": assign, "lmatches": lm, "found": found}
+        if directions:
+            out["match_dir"], out["overlap_dir"] = mdir, odir
+        if projected:
+            out["proj0"], out["proj1"] = p0, p1
+        return out

@@ -22,28 +22,10 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from ._shapes import as_rows_weight, check_pointwise_shapes  # noqa: F401  (the layer's shape rules; Engine.linear_forward applies them too)
 from .evaluations import _engine
 
 HEADS, DH, D = 4, 64, 256
-
-
-def as_rows_weight(weight: torch.Tensor) -> torch.Tensor:
-    """a Conv1d(k=1) [N, K, 1] or a Linear [N, K] weight as its [N, K] matrix (a view)"""
-    if weight.dim() == 3 and weight.shape[2] == 1:
-        return weight[:, :, 0]
-    if weight.dim() != 2:
-        raise ValueError(f"a point-wise weight must be [N, K] or [N, K, 1], got {tuple(weight.shape)}")
-    return weight
-
-
-def check_pointwise_shapes(x, weight, bias=None):
-    """(N, K) of the layer; raises ValueError where x / bias do not fit the weight: x is [B, K, n] or [rows, K]"""
-    N, K = (int(v) for v in as_rows_weight(weight).shape)
-    if x.dim() not in (2, 3) or int(x.shape[1]) != K:
-        raise ValueError(f"x must be [B, {K}, n] or [rows, {K}] for a [{N}, {K}] weight, got {tuple(x.shape)}")
-    if bias is not None and bias.numel() != N:
-        raise ValueError(f"bias must hold {N} elements, got {tuple(bias.shape)}")
-    return N, K
 
 
 class _PointwiseLinear(torch.autograd.Function):
@@ -51,7 +33,7 @@ class _PointwiseLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
-        check_pointwise_shapes(x, weight, bias)
+        check_pointwise_shapes(x, weight, bias)       # (before an engine is looked up: a bad shape is a ValueError on any device)
         y = _engine(x.device).linear_forward(x, weight, bias, relu)
         ctx.relu = bool(relu)
         ctx.has_bias = bias is not None

@@ -34,6 +34,14 @@ def test_library_exports_every_declared_symbol():
         LX = nat.lib(nat.EXPERIMENTS_LIB_PATH)
         for name in declared | declared_x:
             assert hasattr(LX, name), name
+    # every prototype of the header has as many parameters as its entry of the binding's table has argtypes
+    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    protos = dict(re.findall(r"\b(linetr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code))
+    assert set(protos) == declared | declared_x, set(protos) ^ (declared | declared_x)
+    table = {**nat.ABI, **nat.EXPERIMENT_ABI}
+    for name, params in protos.items():
+        n_params = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert n_params == len(table[name][1]), (name, n_params, len(table[name][1]))
     assert L.linetr_abi_version() == 6
     assert C.sizeof(nat.LineRec) == 80
 

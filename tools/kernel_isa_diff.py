@@ -4,7 +4,8 @@ Both trees are compiled with tools/resource_table.py's compile step, once as the
 the experiments build (-DLINETR_EXPERIMENTS, experiments/csrc/linetr_*.hip included).  Per kernel symbol it compares the text from the
 kernel's label to .end_amdhsa_kernel and the kernel's metadata entry, and per device function that was not inlined its text, with
 comments, the numbers of local labels (renumbered in order of appearance) and the per-compile __hip_cuid symbol masked.  Prints one line per build and the symbols that differ or exist on one side
-only (-v: a unified diff of each differing kernel); exit status 1 if there are any.  profiles/*_refactor_isa.txt record its results."""
+only (-v: a unified diff of each differing kernel); exit status 1 if there are any.  A symbol that changed translation unit is compared all
+the same and listed as moved.  profiles/*_refactor_isa.txt record its results."""
 import difflib
 import re
 import sys
@@ -38,11 +39,17 @@ def kernels(asm):
 
 
 def tree_kernels(root, experiments):
-    out = {}
-    for stem, asm in compile_asm(root, experiments).items():
-        for sym, text in kernels(asm).items():
-            out[stem + ":" + sym] = text
-    return out
+    """({key: masked text}, {symbol: its unit(s)}) of a tree.  A symbol with ONE text in the tree -- it exists in one translation unit,
+    or several units instantiate the same template alike -- is keyed by the symbol alone and listed in the second map, so that a
+    kernel which moves between units is still compared; one whose copies differ keeps "unit:" in front."""
+    units = {stem: kernels(asm) for stem, asm in compile_asm(root, experiments).items()}
+    holders = {}
+    for stem, syms in sorted(units.items()):
+        for sym in syms:
+            holders.setdefault(sym, []).append(stem)
+    one_text = {sym for sym, stems in holders.items() if len({units[stem][sym] for stem in stems}) == 1}
+    out = {(sym if sym in one_text else stem + ":" + sym): text for stem, syms in units.items() for sym, text in syms.items()}
+    return out, {sym: " + ".join(holders[sym]) for sym in one_text}
 
 
 def compare(a, b):
@@ -56,9 +63,9 @@ def main():
     parent, head = [a for a in sys.argv[1:] if a != "-v"]
     bad = 0
     for name, experiments in (("product", False), ("experiments", True)):
-        a, b = tree_kernels(parent, experiments), tree_kernels(head, experiments)
+        (a, unit_a), (b, unit_b) = tree_kernels(parent, experiments), tree_kernels(head, experiments)
         both, differing, single = compare(a, b)
-        nk = lambda syms: sum(":fn:" not in s for s in syms)
+        nk = lambda syms: sum("fn:" not in s for s in syms)
         print(f"{name:12s} kernels parent {nk(a):<4d} head {nk(b):<4d} compared {nk(both):<4d} differing {nk(differing):<4d} "
               f"only in one build {nk(single)}")
         print(f"{'':12s} device functions that are not inlined: parent {len(a) - nk(a)} head {len(b) - nk(b)} compared {len(both) - nk(both)} "
@@ -69,6 +76,9 @@ def main():
                 sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(a[s].split("\n"), b[s].split("\n"), "parent", "head", lineterm="", n=2))
         for s in single:
             print("  one side: " + s)
+        for s in both:
+            if unit_a.get(s, unit_b.get(s)) != unit_b.get(s):
+                print(f"  moved:    {s}  {unit_a[s]} -> {unit_b[s]}")
         bad += len(differing) + len(single)
     return 1 if bad else 0
 
