@@ -26,6 +26,8 @@
  *                version stays.
  *                + linetr_debug_bn_train, linetr_debug_bn_train_workspace_bytes (the train-mode BatchNorm kernels alone, for the
  *                unit tests): added diagnostics symbols, the version stays.
+ *                + linetr_bn_forward, linetr_bn_backward and their _workspace_bytes (BatchNorm on batch statistics with a backward): added
+ *                symbols, nothing existing changes, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -488,6 +490,42 @@ int linetr_sig_attention_backward(LinetrHandle* h, const float* d_q, int64_t ldq
                                   const float* d_msg, int64_t ldo, const float* d_lse, const float* d_g, int64_t ldg, const int32_t* d_cu_sub,
                                   int32_t n_images, int64_t N, float* d_dq, int64_t lddq, float* d_dk, int64_t lddk, float* d_dv,
                                   int64_t lddv, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- BatchNorm1d (+ ReLU) for training, forward and backward (section 8(f) "next" row 4: the fourth link) ---------- */
+
+/* torch.nn.BatchNorm1d (+ F.relu) on rows z [rows][C] (rows = B n positions, row stride ldz), as the MLP of the signature layer applies
+ * it (models/line_transformer.py:9-20, :161), OUT OF PLACE -- z is kept, the backward reads it -- and its backward as torch autograd
+ * differentiates it.  4 <= C <= 512, C % 4 == 0; every row stride at least C and a multiple of 4 floats; 16-byte aligned pointers.
+ *   forward, mode LINETR_BN_TRAIN:  mean, var = the batch mean and BIASED variance over all rows, float64 sums in row chunks added in
+ *     ascending order (the kernels and the chunking of linetr_forward_train);  invstd = 1 / sqrt(var + eps);  alpha = gamma invstd;
+ *     beta' = beta - mean alpha (both rounded to float32);  y = max(z alpha + beta', 0), or without the max (relu = 0): the bits of
+ *     linetr_forward_train's layer on the same z.  d_running [mean[C] | var[C]] (may be NULL) <- (1 - momentum) running + momentum
+ *     (mean | var n / (n - 1)), in place, the same bits too.  rows = 1: var = 0 and the unbiased factor is taken as 1.
+ *   forward, mode LINETR_BN_EVAL:  mean | var = d_running (required, only read); nothing is updated.
+ *   d_save [2 C] float64 <- mean[C] | invstd[C] (the batch's, or the running ones): what the backward takes.
+ *   backward:  g' = g where y > 0, else 0 (d_y: the layer's own output as the forward wrote it, NULL for relu = 0; nothing is recomputed to
+ *     decide a sign);  xhat = (z - mean) invstd, z - mean formed in float64;
+ *       dbeta[c] = sum_r g'      dgamma[c] = sum_r g' xhat      (float64 sums, the forward's chunks, ascending; rounded to float32)
+ *       LINETR_BN_TRAIN:  dz = gamma invstd (g' - dbeta / n - xhat dgamma / n)        LINETR_BN_EVAL:  dz = gamma invstd g'
+ *     evaluated as k1 g' - k2 - k3 fl(z - mean) in float32 with per-channel float32 coefficients.  d_dz [rows][lddz], d_dgamma [C],
+ *     d_dbeta [C]: each may be NULL and is then not computed.
+ * Three launches each way (eval forward: two).  Deterministic: no atomics, fixed summation order, two calls give the same bits.  Columns
+ * behind C and rows behind `rows` are neither read nor written.  The caller owns the workspace (linetr_bn_*_workspace_bytes(rows, C); 0
+ * for a shape that is refused).  Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL (it names the device and
+ * collects the profile; no training-mode handle is needed).  rows <= 0: nothing is launched.  LINETR_E_ARG, nothing launched: C outside
+ * the above, rows beyond 2^30, a mode or relu outside 0 .. 1, eps <= 0, momentum outside 0 .. 1, a bad row stride (that of a NULL tensor
+ * is not read), a pointer that is not 16-byte aligned, a NULL required pointer (forward: d_z, d_gamma, d_beta, d_y, d_save, the
+ * workspace, d_running in eval mode; backward: d_z, d_g, d_save, d_gamma, the workspace), a workspace smaller than
+ * linetr_bn_*_workspace_bytes says. */
+enum { LINETR_BN_TRAIN = 0, LINETR_BN_EVAL = 1 };
+int64_t linetr_bn_forward_workspace_bytes(int64_t rows, int32_t C);
+int linetr_bn_forward(LinetrHandle* h, const float* d_z, int64_t ldz, int64_t rows, int32_t C, const float* d_gamma, const float* d_beta,
+                      float eps, float momentum, float* d_running, int32_t mode, int32_t relu, float* d_y, int64_t ldy, double* d_save,
+                      void* d_workspace, int64_t workspace_bytes, void* stream);
+int64_t linetr_bn_backward_workspace_bytes(int64_t rows, int32_t C);
+int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_y, int64_t ldy, const float* d_g, int64_t ldg,
+                       const double* d_save, const float* d_gamma, int64_t rows, int32_t C, int32_t mode, float* d_dz, int64_t lddz,
+                       float* d_dgamma, float* d_dbeta, void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
 

@@ -115,6 +115,10 @@ ABI = {
     "linetr_sig_attention_forward": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, i64, vp, vp]),
     "linetr_sig_attention_backward": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                             vp]),
+    "linetr_bn_forward_workspace_bytes": (i64, [i64, i32]),
+    "linetr_bn_forward": (i32, [vp, vp, i64, i64, i32, vp, vp, f32, f32, vp, i32, i32, vp, i64, vp, vp, i64, vp]),
+    "linetr_bn_backward_workspace_bytes": (i64, [i64, i32]),
+    "linetr_bn_backward": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, vp]),
     "linetr_gt_assign_workspace_bytes": (i64, [i32, i32, i32]),
     "linetr_gt_assign": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_superpoint_heads": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),

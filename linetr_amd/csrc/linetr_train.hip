@@ -1,6 +1,7 @@
 // liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h): the validation step (lt_valstep.h),
 // the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
-// attention's forward with statistics and backward (lt_attnbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
+// attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h) and the
+// ground-truth line assignment in front of them (lt_gtassign.h).
 #include <algorithm>
 
 #include "lt_handle.h"
@@ -8,6 +9,7 @@
 #include "lt_lossgrad.h"
 #include "lt_linbwd.h"
 #include "lt_attnbwd.h"
+#include "lt_bnbwd.h"
 #include "lt_gtassign.h"
 
 using namespace lt;
@@ -432,6 +434,119 @@ extern "C" int linetr_sig_attention_backward(LinetrHandle* h, const float* d_q, 
     ProfScope ps(h, st, "sig_attn_bwd_dq", 0, 4.0 * N * (5.0 * D + 2.0 * HEADS));
     hipLaunchKernelGGL(ab_dq_kernel, grid, dim3(256), 0, st, d_q, ldq, d_k, ldk, d_v, ldv, d_g, ldg, d_lse, (const float*)delta,
                        (const int*)d_cu_sub, n_images, d_dq, lddq);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// BatchNorm1d (+ ReLU) for training: forward that keeps z and the statistics, backward (lt_bnbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t BN_MAX_ROWS = (int64_t)1 << 30;
+// workspace: per-chunk partial sums [chunks][2 C] float64 | per-channel coefficients (forward: alpha | beta'; backward: k1 | k2 | k3)
+struct BnWsLayout { int chunks; int64_t o_partial, o_coef, total; };
+BnWsLayout bn_ws_layout(int64_t rows, int C) {
+  BnWsLayout L{};
+  L.chunks = bn_row_chunks(rows);
+  Carve c;
+  L.o_partial = c.take((int64_t)L.chunks * 2 * C * 8);
+  L.o_coef = c.take((int64_t)3 * C * 4);
+  L.total = c.o + 256;
+  return L;
+}
+bool bn_dims_ok(int64_t rows, int C) { return rows <= BN_MAX_ROWS && C >= 4 && C <= BN_MAX_CHANNELS && C % 4 == 0; }
+bool bn_stride_ok(int64_t ld, int C) { return ld >= C && ld % 4 == 0 && ld <= INT32_MAX; }
+}  // namespace
+
+extern "C" int64_t linetr_bn_forward_workspace_bytes(int64_t rows, int32_t C) { return bn_dims_ok(rows, C) ? bn_ws_layout(rows, C).total : 0; }
+extern "C" int64_t linetr_bn_backward_workspace_bytes(int64_t rows, int32_t C) { return bn_dims_ok(rows, C) ? bn_ws_layout(rows, C).total : 0; }
+
+extern "C" int linetr_bn_forward(LinetrHandle* h, const float* d_z, int64_t ldz, int64_t rows, int32_t C, const float* d_gamma,
+                                 const float* d_beta, float eps, float momentum, float* d_running, int32_t mode, int32_t relu, float* d_y,
+                                 int64_t ldy, double* d_save, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  if (!bn_dims_ok(rows, C))
+    return fail(LINETR_E_ARG, "bn_forward: bad shape rows=%lld C=%d (rows <= 2^30, 4 <= C <= %d, C %% 4 == 0)", (long long)rows, C, BN_MAX_CHANNELS);
+  if (mode != LINETR_BN_TRAIN && mode != LINETR_BN_EVAL) return fail(LINETR_E_ARG, "bn_forward: mode %d (0 batch statistics, 1 running statistics)", mode);
+  if (relu != 0 && relu != 1) return fail(LINETR_E_ARG, "bn_forward: relu %d (0 none, 1 ReLU)", relu);
+  if (!(eps > 0.f) || !(momentum >= 0.f && momentum <= 1.f)) return fail(LINETR_E_ARG, "bn_forward: eps %g (> 0), momentum %g (0 .. 1)", eps, momentum);
+  if (!bn_stride_ok(ldz, C) || !bn_stride_ok(ldy, C))
+    return fail(LINETR_E_ARG, "bn_forward: row strides %lld / %lld (at least C = %d, multiples of 4 floats)", (long long)ldz, (long long)ldy, C);
+  if (!d_z || !d_gamma || !d_beta || !d_y || !d_save || !d_ws) return fail(LINETR_E_ARG, "bn_forward: null pointer");
+  if (mode == LINETR_BN_EVAL && !d_running) return fail(LINETR_E_ARG, "bn_forward: eval mode reads the running statistics");
+  if (!aligned16(d_z) || !aligned16(d_gamma) || !aligned16(d_beta) || !aligned16(d_running) || !aligned16(d_y) || !aligned16(d_save) ||
+      !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "bn_forward: every tensor must be 16-byte aligned");
+  if (ws_bytes < linetr_bn_forward_workspace_bytes(rows, C))
+    return fail(LINETR_E_ARG, "bn_forward: workspace too small (need %lld)", (long long)linetr_bn_forward_workspace_bytes(rows, C));
+  if (rows <= 0) return LINETR_OK;
+  const BnWsLayout L = bn_ws_layout(rows, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  double* partial = (double*)((char*)d_ws + L.o_partial);
+  float* affine = (float*)((char*)d_ws + L.o_coef);
+  const bool eval = mode == LINETR_BN_EVAL;
+  if (!eval) {
+    ProfScope ps(h, st, "bn_fwd_partial", 0, 4.0 * rows * C);
+    hipLaunchKernelGGL(bn_partial_kernel, dim3(L.chunks), dim3(256), 0, st, d_z, rows, (int)C, (int)ldz, partial);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "bn_fwd_finalize", 0, 16.0 * L.chunks * C);
+    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)partial, L.chunks, (int)C, rows, d_gamma,
+                       d_beta, eps, momentum, d_running, (int)eval, affine, d_save);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "bn_fwd_apply", 0, 8.0 * rows * C);
+    hipLaunchKernelGGL(bn_fwd_apply_kernel, dim3((unsigned)((rows * (C / 4) + 255) / 256)), dim3(256), 0, st, d_z, rows, (int)C, ldz,
+                       (const float*)affine, (int)relu, d_y, ldy);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+extern "C" int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_y, int64_t ldy, const float* d_g, int64_t ldg,
+                                  const double* d_save, const float* d_gamma, int64_t rows, int32_t C, int32_t mode, float* d_dz,
+                                  int64_t lddz, float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!bn_dims_ok(rows, C))
+    return fail(LINETR_E_ARG, "bn_backward: bad shape rows=%lld C=%d (rows <= 2^30, 4 <= C <= %d, C %% 4 == 0)", (long long)rows, C, BN_MAX_CHANNELS);
+  if (mode != LINETR_BN_TRAIN && mode != LINETR_BN_EVAL) return fail(LINETR_E_ARG, "bn_backward: mode %d (0 batch statistics, 1 running statistics)", mode);
+  if (!bn_stride_ok(ldz, C) || !bn_stride_ok(ldg, C) || (d_y && !bn_stride_ok(ldy, C)) || (d_dz && !bn_stride_ok(lddz, C)))
+    return fail(LINETR_E_ARG, "bn_backward: every row stride must be at least C = %d and a multiple of 4 floats", C);
+  if (!d_z || !d_g || !d_save || !d_gamma || !d_ws) return fail(LINETR_E_ARG, "bn_backward: null pointer");
+  if (!aligned16(d_z) || !aligned16(d_y) || !aligned16(d_g) || !aligned16(d_save) || !aligned16(d_gamma) || !aligned16(d_dz) ||
+      !aligned16(d_dgamma) || !aligned16(d_dbeta) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "bn_backward: every tensor must be 16-byte aligned");
+  if (ws_bytes < linetr_bn_backward_workspace_bytes(rows, C))
+    return fail(LINETR_E_ARG, "bn_backward: workspace too small (need %lld)", (long long)linetr_bn_backward_workspace_bytes(rows, C));
+  if (rows <= 0 || (!d_dz && !d_dgamma && !d_dbeta)) return LINETR_OK;
+  const BnWsLayout L = bn_ws_layout(rows, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  double* partial = (double*)((char*)d_ws + L.o_partial);
+  float* coef = (float*)((char*)d_ws + L.o_coef);
+  const bool eval = mode == LINETR_BN_EVAL;
+  const bool sums = !eval || d_dgamma || d_dbeta;      // eval mode: dz needs no sum
+  const double tensors = d_y ? 3.0 : 2.0;
+  if (sums) {
+    ProfScope ps(h, st, "bn_bwd_partial", 0, 4.0 * tensors * rows * C);
+    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(L.chunks, cdiv(C / 4, BNB_QUADS)), dim3(256), 0, st, d_g, ldg, d_y, ldy, d_z, ldz, d_save, rows,
+                       (int)C, partial);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "bn_bwd_finalize", 0, 16.0 * L.chunks * C);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)partial, sums ? L.chunks : 0, (int)C, rows,
+                       d_gamma, d_save, (int)eval, d_dgamma, d_dbeta, coef);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dz) {
+    ProfScope ps(h, st, "bn_bwd_apply", 0, 4.0 * (tensors + (eval ? 0.0 : 1.0)) * rows * C);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((rows * (C / 4) + 255) / 256)), dim3(256), 0, st, d_g, ldg, d_y, ldy, d_z, ldz, d_save,
+                       (const float*)coef, rows, (int)C, (int)eval, d_dz, lddz);
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;

@@ -10,6 +10,8 @@
 //                        (the affine form torch's batch_norm_cpu_transform_input applies), running statistics updated in place
 //   bn_apply_relu_kernel z <- max(z alpha + beta', 0)
 // HBM-bound elementwise work (one read for the statistics, one read + write for the transform); coalesced along the channel axis.
+// The kernels have internal linkage: two translation units include this header (linetr_net.hip for linetr_forward_train, linetr_train.hip
+// through lt_bnbwd.h for the forward that keeps z for a backward), each with its own copy.
 #pragma once
 #include "lt_common.h"
 
@@ -29,7 +31,7 @@ struct BnTrain {
 
 // z [rows][C] (row stride ld), any C <= BN_MAX_CHANNELS; partial [gridDim.x][2 C].  A block whose chunk lies behind the last row
 // writes zero partials.
-__global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ z, int64_t rows, int C, int ld,
+static __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ z, int64_t rows, int C, int ld,
                                                          double* __restrict__ partial) {
   __shared__ double red[2][256];
   const int tid = threadIdx.x;
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
 }
 
 // one thread per channel
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ partial, int n_blocks, int C, int64_t rows,
+static __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ partial, int n_blocks, int C, int64_t rows,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                           float momentum, float* __restrict__ running /*mean[C] | var[C]*/,
                                                           float* __restrict__ batch /*mean[C] | biased var[C], or null*/,
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
 }
 
 // in place, four channels per thread (C % 4 == 0, ld % 4 == 0)
-__global__ __launch_bounds__(256) void bn_apply_relu_kernel(float* __restrict__ z, int64_t rows, int C, int ld,
+static __global__ __launch_bounds__(256) void bn_apply_relu_kernel(float* __restrict__ z, int64_t rows, int C, int ld,
                                                             const float* __restrict__ affine) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int c4 = C / 4;

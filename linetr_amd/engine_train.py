@@ -244,6 +244,62 @@ class _TrainSurface:
                    ptr(dk), D, ptr(dv), D, ws.data_ptr(), ws.numel())
         return dq, dk, dv
 
+    # ------------------------------------------------------------------ BatchNorm (+ ReLU) for training
+    def bn_forward(self, z, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, training=True, relu=True):
+        """torch.nn.BatchNorm1d (+ ReLU) out of place (linetr_bn_forward): y = relu?((z - mean) invstd gamma + beta) with the batch's mean
+        and biased variance (`training`) or the running ones.  z: [B, C, n] (the transposed view of [B*n, C] rows: no copy) or
+        [rows, C], rows may be strided; gamma, beta [C].  running_mean / running_var [C]: float32 device tensors, updated IN PLACE in
+        training mode (both or neither), required and only read otherwise.  Returns (y in z's layout, save: float64 [2 C] mean | invstd,
+        what bn_backward takes).  No host wait."""
+        C_ = int(gamma.numel())
+        zr, B, n = self._act_rows(z, C_, "z")
+        rows = int(zr.shape[0])
+        if (running_mean is None) != (running_var is None) or (not training and running_mean is None):
+            raise ValueError("bn_forward: running_mean and running_var come together, and eval mode needs them")
+        run = None
+        if running_mean is not None:
+            for t in (running_mean, running_var):
+                if t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (C_,):
+                    raise ValueError(f"bn_forward: the running statistics must be float32 [{C_}] tensors on {self.device}")
+            run = torch.cat([running_mean.detach(), running_var.detach()])
+        y = torch.empty((rows, C_), dtype=torch.float32, device=self.device)
+        save = torch.empty((2 * C_,), dtype=torch.float64, device=self.device)
+        if rows == 0:
+            return self._like_input(y, B, n), save.zero_()
+        ws = self._stream_workspace("bn_fwd", self._L.linetr_bn_forward_workspace_bytes(rows, C_))
+        self._call("linetr_bn_forward", zr.data_ptr(), zr.stride(0), rows, C_, self._f32(gamma.detach().reshape(-1)).data_ptr(),
+                   self._f32(beta.detach().reshape(-1)).data_ptr(), float(eps), float(momentum), ptr(run), int(not training), int(bool(relu)),
+                   y.data_ptr(), C_, save.data_ptr(), ws.data_ptr(), ws.numel())
+        if training and run is not None:
+            with torch.no_grad():
+                running_mean.copy_(run[:C_])
+                running_var.copy_(run[C_:])
+        return self._like_input(y, B, n), save
+
+    def bn_backward(self, z, y, grad_out, save, gamma, training=True, need=(True, True, True)):
+        """The layer's backward (linetr_bn_backward): (dz, dgamma, dbeta) for the gradient `grad_out` arriving at y; z and save as
+        bn_forward took and returned them, y: the layer's own post-ReLU output (the mask y > 0), None for no activation.  dz in z's
+        layout; `need` = which of the three to compute (the others are None).  Deterministic; no host wait."""
+        C_ = int(gamma.numel())
+        zr, B, n = self._act_rows(z, C_, "z")
+        g = self._act_rows(grad_out, C_, "grad_out")[0]
+        m = self._act_rows(y, C_, "y")[0] if y is not None else None
+        rows = int(zr.shape[0])
+        if int(g.shape[0]) != rows or (m is not None and int(m.shape[0]) != rows):
+            raise ValueError("bn_backward: z, grad_out and y disagree about the number of rows")
+        if save.device != self.device or save.dtype != torch.float64 or tuple(save.shape) != (2 * C_,) or not save.is_contiguous():
+            raise ValueError(f"bn_backward: save must be the float64 [{2 * C_}] tensor bn_forward returned")
+        dz = torch.empty((rows, C_), dtype=torch.float32, device=self.device) if need[0] else None
+        dgamma, dbeta = (torch.empty((C_,), dtype=torch.float32, device=self.device) if k else None for k in need[1:3])
+        if rows == 0:
+            return (self._like_input(dz, B, n) if dz is not None else None, dgamma.zero_() if dgamma is not None else None,
+                    dbeta.zero_() if dbeta is not None else None)
+        ws = self._stream_workspace("bn_bwd", self._L.linetr_bn_backward_workspace_bytes(rows, C_))
+        self._call("linetr_bn_backward", zr.data_ptr(), zr.stride(0), ptr(m), m.stride(0) if m is not None else 0, g.data_ptr(), g.stride(0),
+                   save.data_ptr(), self._f32(gamma.detach().reshape(-1)).data_ptr(), rows, C_, int(not training), ptr(dz), C_, ptr(dgamma),
+                   ptr(dbeta), ws.data_ptr(), ws.numel())
+        return self._like_input(dz, B, n) if dz is not None else None, dgamma, dbeta
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes

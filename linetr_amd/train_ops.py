@@ -1,4 +1,5 @@
-"""Differentiable native layers: torch.autograd.Functions on top of the exact-fp32 kernels of csrc/lt_linbwd.h and csrc/lt_attnbwd.h.
+"""Differentiable native layers: torch.autograd.Functions on top of the exact-fp32 kernels of csrc/lt_linbwd.h and csrc/lt_attnbwd.h and
+the BatchNorm kernels of csrc/lt_bnbwd.h, and the signature network composed of them.
 
     pointwise_linear(x, weight, bias=None, relu=False)   y = act(x W^T + b): Conv1d(k=1) ([N, K, 1] weight, x [B, K, n]) or Linear
                                                          ([N, K] weight, x [rows, K]) on the UNFOLDED state_dict weight, with the
@@ -11,12 +12,21 @@
                                                          (Engine.sig_attention_forward / _backward)
     MultiHeadedAttention                                 the reference's module (:139-154): three projections, attention, merge, with its
                                                          state_dict; every gradient native
+    batch_norm_relu(z, bn, relu=True)                    relu?(bn(z)) for an nn.BatchNorm1d `bn`, on batch statistics in .train() (the running
+                                                         statistics and num_batches_tracked move as torch moves them) and on the running
+                                                         ones in .eval(); dz, dgamma and dbeta native (Engine.bn_forward / bn_backward)
+    AttentionalPropagation                               the reference's signature layer (:157-166): attn(x, source, source), cat, Conv1d(512,
+                                                         512), BatchNorm1d(512), ReLU, Conv1d(512, 256), with its state_dict
+    SelfAttentionalLayer                                 the reference's stack (:168-183): kline_desc + delta, layer after layer
 
-With linetr_amd.evaluations.descriptor_loss on top of a DescriptorHead, `loss.backward()` fills head.final_proj.weight.grad, .bias.grad
-and the pre-head features' .grad on the device, with no torch arithmetic between the criterion's gradient and them; a
-MultiHeadedAttention's `message.backward(g)` fills its eight parameters' and its inputs' .grad the same way.  The tensors must live on a
-HIP device (there is no CPU path).  Of the signature layer the BatchNorm backward, the concatenated MLP and the residual are not here, nor
-is the descriptive layer."""
+With linetr_amd.evaluations.descriptor_loss on top of a DescriptorHead on top of a SelfAttentionalLayer, `loss.backward()` fills every
+gradient of the signature network -- the eight attention parameters, the two convolutions and the BatchNorm weight and bias of every layer,
+the head, and the input features' .grad -- on the device.  Every contraction, softmax, normalisation and reduction in it, forward and
+backward, is a native kernel.  What torch still does: data movement (cat, permute / transpose, views, the gather of the attention's
+parameters into head-major order and its scatter back, copies of the running statistics into and out of their packed pair), the residual
+add kline_desc + delta, the increment of num_batches_tracked, and autograd's own sums where one tensor feeds several consumers (x feeds the
+attention's three projections, the concatenation and the residual) -- single float32 adds, as in the reference.  The tensors must live on
+a HIP device (there is no CPU path).  The descriptive layer and the two positional encoders have no native backward yet and are not here."""
 from __future__ import annotations
 
 import torch
@@ -168,3 +178,118 @@ class MultiHeadedAttention(nn.Module):
         o, _ = _SigAttnRows.apply(head_major_rows(self.proj[0], query), head_major_rows(self.proj[1], key), head_major_rows(self.proj[2], value),
                                   _item_offsets(B, n, query.device))
         return pointwise_linear(o.view(B, n, D).transpose(1, 2), self.merge.weight[:, hm], self.merge.bias), None
+
+
+class _BatchNormRelu(torch.autograd.Function):
+    """y = relu?(batch_norm(z)).  Saved for the backward: z, the statistics float64 [mean | invstd], gamma and, with ReLU, the output
+    itself -- the mask (nothing is recomputed)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, training, relu):
+        y, save = _engine(z.device).bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, training, relu)
+        ctx.training, ctx.relu = bool(training), bool(relu)
+        ctx.save_for_backward(z, y if relu else None, save, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        z, y, save, gamma = ctx.saved_tensors
+        dz, dgamma, dbeta = _engine(z.device).bn_backward(z, y, grad_out, save, gamma, ctx.training, need=tuple(ctx.needs_input_grad[:3]))
+        return dz, dgamma, dbeta, None, None, None, None, None, None
+
+
+def batch_norm_relu(z, bn: nn.BatchNorm1d, relu: bool = True):
+    """relu?(bn(z)) as torch computes it for z [B, C, n] or [rows, C], differentiable with respect to z, bn.weight and bn.bias; y in z's
+    layout.  bn.training: batch statistics (mean and biased variance over all B n positions), bn.running_mean / running_var moved in
+    place with bn.momentum and the unbiased variance, num_batches_tracked incremented; a single value per channel raises torch's
+    ValueError.  bn.eval(): the running statistics, nothing moves.  Refused: momentum=None (the cumulative average) and affine=False."""
+    if not isinstance(bn, nn.BatchNorm1d):
+        raise TypeError(f"batch_norm_relu takes an nn.BatchNorm1d, got {type(bn).__name__}")
+    if not bn.affine or bn.momentum is None:
+        raise ValueError("batch_norm_relu: affine=False and momentum=None (a cumulative moving average) have no native kernel")
+    C_ = int(bn.num_features)
+    if z.dim() not in (2, 3) or int(z.shape[1]) != C_:
+        raise ValueError(f"z must be [B, {C_}, n] or [rows, {C_}], got {tuple(z.shape)}")
+    training = bn.training or bn.running_mean is None          # (track_running_stats=False: batch statistics in either mode, as torch)
+    if training and z.numel() // C_ <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    tracked = bn.training and bn.running_mean is not None
+    if tracked and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _BatchNormRelu.apply(z, bn.weight, bn.bias, bn.running_mean if tracked or not training else None,
+                                bn.running_var if tracked or not training else None, float(bn.momentum), float(bn.eps), training, relu)
+
+
+def _sub_state_dict(model, prefix):
+    """the entries of a model's (or a state_dict's) state dict under `prefix`, the prefix cut off, as tensors"""
+    sd = model if isinstance(model, dict) else model.state_dict()
+    return {k[len(prefix):]: torch.as_tensor(v) for k, v in sd.items() if k.startswith(prefix)}
+
+
+def _device_of(sub):
+    ref = next(iter(sub.values()))
+    return ref.device
+
+
+class AttentionalPropagation(nn.Module):
+    """The reference's AttentionalPropagation (models/line_transformer.py:157-166): delta = mlp(cat([x, attn(x, source, source)])) with
+    mlp = Conv1d(512, 512) -> BatchNorm1d(512) -> ReLU -> Conv1d(512, 256).  Its state_dict has the reference's names and shapes: attn.*
+    (MultiHeadedAttention), mlp.0.weight / .bias, mlp.1.weight / .bias / .running_mean / .running_var / .num_batches_tracked, mlp.3.weight /
+    .bias.  `mlp` is the reference's nn.Sequential and holds the parameters; it is never called: the two convolutions are
+    pointwise_linear and the normalisation with its activation is batch_norm_relu, which follows .train() / .eval() through mlp[1].
+    The concatenation is made of rows ([B, n, 512], x beside the message), so that every layer reads and writes [B n, C] rows behind
+    the [B, C, n] view and no activation is copied between the kernels."""
+
+    def __init__(self, feature_dim: int = D, num_heads: int = HEADS):
+        super().__init__()
+        if feature_dim != D:
+            raise ValueError(f"the native signature layer is {D} channels wide, got {feature_dim}")
+        self.attn = MultiHeadedAttention(num_heads, feature_dim)
+        self.mlp = nn.Sequential(nn.Conv1d(2 * D, 2 * D, kernel_size=1), nn.BatchNorm1d(2 * D), nn.ReLU(), nn.Conv1d(2 * D, D, kernel_size=1))
+        nn.init.constant_(self.mlp[-1].bias, 0.0)
+
+    @classmethod
+    def from_line_transformer(cls, model, layer: int = 0) -> "AttentionalPropagation":
+        """signature layer `layer` of a LineTransformer (this package's or the reference's), or of its state_dict: a copy"""
+        sub = _sub_state_dict(model, f"selfattn.layers.{int(layer)}.")
+        own = cls()
+        own.load_state_dict(sub, strict=True)
+        return own.to(_device_of(sub))
+
+    def forward(self, x, source):
+        """x, source [B, 256, n] -> (delta [B, 256, n], None): the reference returns the n x n prob second, which is never formed here."""
+        message, _ = self.attn(x, source, source)
+        rows = torch.cat([x.transpose(1, 2), message.transpose(1, 2)], dim=2)         # [B, n, 512]: data movement only
+        z = pointwise_linear(rows.transpose(1, 2), self.mlp[0].weight, self.mlp[0].bias)
+        y = batch_norm_relu(z, self.mlp[1], relu=True)
+        return pointwise_linear(y, self.mlp[3].weight, self.mlp[3].bias), None
+
+
+class SelfAttentionalLayer(nn.Module):
+    """The reference's SelfAttentionalLayer (models/line_transformer.py:168-183): kline_desc <- kline_desc + layer(kline_desc, kline_desc)
+    for every layer; state_dict layers.<i>.* as AttentionalPropagation names them.  The input is brought to rows once (a copy: data
+    movement), after which the residual adds keep the [B n, 256] rows behind the [B, 256, n] view from layer to layer."""
+
+    def __init__(self, feature_dim: int = D, layer_names=("self",) * 7):
+        super().__init__()
+        self.layers = nn.ModuleList(AttentionalPropagation(feature_dim, HEADS) for _ in range(len(layer_names)))
+        self.names = list(layer_names)
+
+    @classmethod
+    def from_line_transformer(cls, model) -> "SelfAttentionalLayer":
+        """the signature network of a LineTransformer (this package's or the reference's), or of its state_dict: a copy"""
+        sub = _sub_state_dict(model, "selfattn.")
+        n_layers = 1 + max(int(k.split(".")[1]) for k in sub)
+        own = cls(D, ["self"] * n_layers)
+        own.load_state_dict(sub, strict=True)
+        return own.to(_device_of(sub))
+
+    def forward(self, kline_desc):
+        """kline_desc [B, 256, n] -> [B, 256, n] (the transposed view of [B n, 256] rows)"""
+        if kline_desc.dim() != 3 or int(kline_desc.shape[1]) != D:
+            raise ValueError(f"kline_desc must be [B, {D}, n], got {tuple(kline_desc.shape)}")
+        kline_desc = kline_desc.transpose(1, 2).contiguous().transpose(1, 2)
+        for layer in self.layers:
+            delta, _ = layer(kline_desc, kline_desc)
+            kline_desc = kline_desc + delta
+        return kline_desc
