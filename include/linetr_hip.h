@@ -735,7 +735,7 @@ int linetr_debug_tok_mlp(LinetrHandle* h, int32_t variant, const float* d_pnt, c
                          const float* d_sublines, const float* d_resp, const float* d_angle, int64_t rows_line,
                          float* d_out_word, float* d_out_line, int32_t max_blocks, int32_t* variant_used, void* stream);
 
-/* Runs BatchNorm1d in TRAINING mode + ReLU (csrc/lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_relu_kernel behind
+/* Runs BatchNorm1d in TRAINING mode + ReLU (csrc/lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel behind
  * their host function bn_train_layer) alone, for the unit tests (tests/test_gpu_bn_train.py: against float64 at the channel widths,
  * row strides and row counts where the kernels' loops and chunks end).  `h` must be a training-mode handle (bn_batch_stats = 1).
  * which = -1: ONE free-standing layer, the handle's weights are not read.  d_z [rows][ld] holds C <= ld pre-activations per row and

@@ -1328,11 +1328,12 @@ extern "C" int linetr_debug_bn_train(LinetrHandle* h, int32_t which, float* d_z,
   if (nb_used) *nb_used = 0;
   if (which < 0) {
     // (bn_train_layer has these checks too; here they come before anything else is looked at)
-    if (C > BN_MAX_CHANNELS || C < 4 || C % 4) return fail(LINETR_E_ARG, "debug_bn_train: %d channels (4 .. %d, multiples of 4)", C, BN_MAX_CHANNELS);
-    if (ld < C || ld % 4) return fail(LINETR_E_ARG, "debug_bn_train: row stride %d (at least the %d channels, a multiple of 4)", ld, C);
+    if (!bn_channels_ok(C)) return fail(LINETR_E_ARG, "debug_bn_train: %d channels (4 .. %d, multiples of 4)", C, BN_MAX_CHANNELS);
+    if (!bn_rows_ok(d_z, ld, C))
+      return fail(LINETR_E_ARG, "debug_bn_train: row stride %d (at least the %d channels, a multiple of 4) on a 16-byte aligned z", ld, C);
     if (!d_z || !d_gamma || !d_beta || !d_running) return fail(LINETR_E_ARG, "debug_bn_train: null tensor");
-    if ((uintptr_t)d_z % 16 || ((uintptr_t)d_gamma | (uintptr_t)d_beta | (uintptr_t)d_running | (uintptr_t)d_batch | (uintptr_t)d_affine) % 4)
-      return fail(LINETR_E_ARG, "debug_bn_train: z must be 16-byte aligned, the vectors 4-byte aligned");
+    if (((uintptr_t)d_gamma | (uintptr_t)d_beta | (uintptr_t)d_running | (uintptr_t)d_batch | (uintptr_t)d_affine) % 4)
+      return fail(LINETR_E_ARG, "debug_bn_train: the vectors must be 4-byte aligned");
   } else {
     if (!d_in0 || !d_in1 || (which == ENC_LINE && !d_in2) || !d_out || !d_running) return fail(LINETR_E_ARG, "debug_bn_train: null tensor");
     if (((uintptr_t)d_in0 | (uintptr_t)d_in1 | (uintptr_t)d_in2 | (uintptr_t)d_running | (uintptr_t)d_batch) % 4 || (uintptr_t)d_out % 16)

@@ -370,7 +370,7 @@ constexpr int AB_MAX_IMAGES = 4096;              // every block walks cu_sub (ab
 int64_t attn_delta_bytes(int64_t N) { return align_up(N * HEADS * 4, 256); }
 bool attn_stride_ok(int64_t ld) { return ld >= D && ld % 4 == 0; }
 // tiles of 128 rows of any split of N rows into n_images images, at most
-unsigned attn_tiles(int64_t N, int n_images) { return (unsigned)(N / AB_T + n_images); }
+unsigned attn_tiles(int64_t N, int n_images) { return (unsigned)(N / ATT_QT + n_images); }
 }  // namespace
 
 extern "C" int64_t linetr_sig_attention_backward_workspace_bytes(int64_t N) {
@@ -440,7 +440,7 @@ extern "C" int linetr_sig_attention_backward(LinetrHandle* h, const float* d_q, 
 }
 
 // =============================================================================================
-// BatchNorm1d (+ ReLU) for training: forward that keeps z and the statistics, backward (lt_bnbwd.h)
+// BatchNorm1d (+ ReLU) for training: forward that keeps z and the statistics (lt_bntrain.h), backward (lt_bnbwd.h)
 // =============================================================================================
 
 namespace {
@@ -456,8 +456,7 @@ BnWsLayout bn_ws_layout(int64_t rows, int C) {
   L.total = c.o + 256;
   return L;
 }
-bool bn_dims_ok(int64_t rows, int C) { return rows <= BN_MAX_ROWS && C >= 4 && C <= BN_MAX_CHANNELS && C % 4 == 0; }
-bool bn_stride_ok(int64_t ld, int C) { return ld >= C && ld % 4 == 0 && ld <= INT32_MAX; }
+bool bn_dims_ok(int64_t rows, int C) { return rows <= BN_MAX_ROWS && bn_channels_ok(C); }
 }  // namespace
 
 extern "C" int64_t linetr_bn_forward_workspace_bytes(int64_t rows, int32_t C) { return bn_dims_ok(rows, C) ? bn_ws_layout(rows, C).total : 0; }
@@ -472,12 +471,12 @@ extern "C" int linetr_bn_forward(LinetrHandle* h, const float* d_z, int64_t ldz,
   if (mode != LINETR_BN_TRAIN && mode != LINETR_BN_EVAL) return fail(LINETR_E_ARG, "bn_forward: mode %d (0 batch statistics, 1 running statistics)", mode);
   if (relu != 0 && relu != 1) return fail(LINETR_E_ARG, "bn_forward: relu %d (0 none, 1 ReLU)", relu);
   if (!(eps > 0.f) || !(momentum >= 0.f && momentum <= 1.f)) return fail(LINETR_E_ARG, "bn_forward: eps %g (> 0), momentum %g (0 .. 1)", eps, momentum);
-  if (!bn_stride_ok(ldz, C) || !bn_stride_ok(ldy, C))
-    return fail(LINETR_E_ARG, "bn_forward: row strides %lld / %lld (at least C = %d, multiples of 4 floats)", (long long)ldz, (long long)ldy, C);
+  if (!bn_rows_ok(d_z, ldz, C) || !bn_rows_ok(d_y, ldy, C))
+    return fail(LINETR_E_ARG, "bn_forward: row strides %lld / %lld (at least C = %d, multiples of 4 floats) on 16-byte aligned bases", (long long)ldz,
+                (long long)ldy, C);
   if (!d_z || !d_gamma || !d_beta || !d_y || !d_save || !d_ws) return fail(LINETR_E_ARG, "bn_forward: null pointer");
   if (mode == LINETR_BN_EVAL && !d_running) return fail(LINETR_E_ARG, "bn_forward: eval mode reads the running statistics");
-  if (!aligned16(d_z) || !aligned16(d_gamma) || !aligned16(d_beta) || !aligned16(d_running) || !aligned16(d_y) || !aligned16(d_save) ||
-      !aligned16(d_ws))
+  if (!aligned16(d_gamma) || !aligned16(d_beta) || !aligned16(d_running) || !aligned16(d_save) || !aligned16(d_ws))
     return fail(LINETR_E_ARG, "bn_forward: every tensor must be 16-byte aligned");
   if (ws_bytes < linetr_bn_forward_workspace_bytes(rows, C))
     return fail(LINETR_E_ARG, "bn_forward: workspace too small (need %lld)", (long long)linetr_bn_forward_workspace_bytes(rows, C));
@@ -485,27 +484,8 @@ extern "C" int linetr_bn_forward(LinetrHandle* h, const float* d_z, int64_t ldz,
   const BnWsLayout L = bn_ws_layout(rows, C);
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  double* partial = (double*)((char*)d_ws + L.o_partial);
-  float* affine = (float*)((char*)d_ws + L.o_coef);
-  const bool eval = mode == LINETR_BN_EVAL;
-  if (!eval) {
-    ProfScope ps(h, st, "bn_fwd_partial", 0, 4.0 * rows * C);
-    hipLaunchKernelGGL(bn_partial_kernel, dim3(L.chunks), dim3(256), 0, st, d_z, rows, (int)C, (int)ldz, partial);
-    LT_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps(h, st, "bn_fwd_finalize", 0, 16.0 * L.chunks * C);
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)partial, L.chunks, (int)C, rows, d_gamma,
-                       d_beta, eps, momentum, d_running, (int)eval, affine, d_save);
-    LT_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps(h, st, "bn_fwd_apply", 0, 8.0 * rows * C);
-    hipLaunchKernelGGL(bn_fwd_apply_kernel, dim3((unsigned)((rows * (C / 4) + 255) / 256)), dim3(256), 0, st, d_z, rows, (int)C, ldz,
-                       (const float*)affine, (int)relu, d_y, ldy);
-    LT_LAUNCH_CHECK();
-  }
-  return LINETR_OK;
+  return bn_forward_launch(st, h, (double*)((char*)d_ws + L.o_partial), (float*)((char*)d_ws + L.o_coef), d_z, ldz, rows, C, d_gamma, d_beta, eps,
+                           momentum, d_running, mode == LINETR_BN_EVAL, nullptr, d_save, relu != 0, d_y, ldy);
 }
 
 extern "C" int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_y, int64_t ldy, const float* d_g, int64_t ldg,
@@ -514,11 +494,10 @@ extern "C" int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz
   if (!bn_dims_ok(rows, C))
     return fail(LINETR_E_ARG, "bn_backward: bad shape rows=%lld C=%d (rows <= 2^30, 4 <= C <= %d, C %% 4 == 0)", (long long)rows, C, BN_MAX_CHANNELS);
   if (mode != LINETR_BN_TRAIN && mode != LINETR_BN_EVAL) return fail(LINETR_E_ARG, "bn_backward: mode %d (0 batch statistics, 1 running statistics)", mode);
-  if (!bn_stride_ok(ldz, C) || !bn_stride_ok(ldg, C) || (d_y && !bn_stride_ok(ldy, C)) || (d_dz && !bn_stride_ok(lddz, C)))
-    return fail(LINETR_E_ARG, "bn_backward: every row stride must be at least C = %d and a multiple of 4 floats", C);
+  if (!bn_rows_ok(d_z, ldz, C) || !bn_rows_ok(d_g, ldg, C) || (d_y && !bn_rows_ok(d_y, ldy, C)) || (d_dz && !bn_rows_ok(d_dz, lddz, C)))
+    return fail(LINETR_E_ARG, "bn_backward: every row stride must be at least C = %d and a multiple of 4 floats, every base 16-byte aligned", C);
   if (!d_z || !d_g || !d_save || !d_gamma || !d_ws) return fail(LINETR_E_ARG, "bn_backward: null pointer");
-  if (!aligned16(d_z) || !aligned16(d_y) || !aligned16(d_g) || !aligned16(d_save) || !aligned16(d_gamma) || !aligned16(d_dz) ||
-      !aligned16(d_dgamma) || !aligned16(d_dbeta) || !aligned16(d_ws))
+  if (!aligned16(d_save) || !aligned16(d_gamma) || !aligned16(d_dgamma) || !aligned16(d_dbeta) || !aligned16(d_ws))
     return fail(LINETR_E_ARG, "bn_backward: every tensor must be 16-byte aligned");
   if (ws_bytes < linetr_bn_backward_workspace_bytes(rows, C))
     return fail(LINETR_E_ARG, "bn_backward: workspace too small (need %lld)", (long long)linetr_bn_backward_workspace_bytes(rows, C));

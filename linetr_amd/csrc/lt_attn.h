@@ -9,125 +9,19 @@ namespace lt {
 
 // ---------------------------------------------------------------------------------------------
 // Neighbour-line ("signature") multi-head attention, one image = one softmax domain
-// (models/line_transformer.py:132-154).  Flash-style, fp32 MFMA, no N x N matrix in memory.
+// (models/line_transformer.py:132-154), exact fp32 MFMA: sig_attn_tile<false> (lt_attn_parts.h) on one buffer.
 //
-// grid (image, head, q-tile of 128), block 256 = 4 wave64, wave w owns 32 query rows.
+// grid (image, head, q-tile of ATT_QT = 128), block 256.
 // qkv [N,768] = [q | k | v], each head-major (c = h*64+d; the reference's interleaved c = d*4+h is
 // undone by permuting weight rows at load time) and q pre-scaled by 1/8 (exact, power of two).
-//
-// Per 32-row kv chunk and wave:
-//   S^T[kv][q] = K_h[kv,:] . Q_h[q,:]      (A = K tile from LDS, B = Q fragment held in VGPRs)
-//   in the 32x32 C/D layout a lane owns ONE query column (q = lane&31) and 16 kv rows, so the online
-//   softmax max/sum are in-lane + one exchange with lane^32;
-//   the exponentiated S^T registers ARE the B operand of  O^T[d][q] += V^T[d][kv] . P^T[kv][q]
-//   under the k-permutation k = 8kk + 4*(lane>>5) + s  <->  register 4kk+s, so P never leaves VGPRs.
 // ---------------------------------------------------------------------------------------------
-constexpr int ATT_QT = 128;   // query rows per block
-constexpr int ATT_KT = 64;    // kv rows staged per iteration
-constexpr int ATT_KS = DH + 4;
-
 __global__ __launch_bounds__(256) void sig_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ cu_sub,
                                                        float* __restrict__ out /*[N][256] head-major*/) {
-  __shared__ __attribute__((aligned(16))) float Ks[ATT_KT * ATT_KS];
-  __shared__ __attribute__((aligned(16))) float Vs[ATT_KT * DH];
   const int img = blockIdx.x, head = blockIdx.y;
   const int n0 = cu_sub[img], Ni = cu_sub[img + 1] - n0;
   const int q0 = blockIdx.z * ATT_QT;
   if (q0 >= Ni) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h2 = lane >> 5, lq = lane & 31;
-  const int q = q0 + wave * 32 + lq;
-  const bool wave_active = q0 + wave * 32 < Ni;  // wave-uniform
-  const float* base = qkv + (int64_t)n0 * 768;
-
-  f32x4 qf[8];
-  {
-    const int qr = q < Ni ? q : Ni - 1;
-    const float* qp = base + (int64_t)qr * 768 + head * DH + h2 * 4;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) qf[kk] = *reinterpret_cast<const f32x4*>(qp + kk * 8);
-  }
-  f32x16 o0, o1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-  float m = -INFINITY, l = 0.f;
-
-  const int srow = tid >> 4, sc4 = (tid & 15) * 4;  // staging: 16 rows x 16 float4 per pass
-  for (int t0 = 0; t0 < Ni; t0 += ATT_KT) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + i * 16;
-      const int kv = t0 + r;
-      f32x4 kx = {0.f, 0.f, 0.f, 0.f}, vx = {0.f, 0.f, 0.f, 0.f};
-      if (kv < Ni) {
-        const float* p = base + (int64_t)kv * 768 + head * DH + sc4;
-        kx = *reinterpret_cast<const f32x4*>(p + 256);
-        vx = *reinterpret_cast<const f32x4*>(p + 512);
-      }
-      *reinterpret_cast<f32x4*>(&Ks[r * ATT_KS + sc4]) = kx;
-      *reinterpret_cast<f32x4*>(&Vs[r * DH + sc4]) = vx;
-    }
-    __syncthreads();
-    if (!wave_active) continue;
-#pragma unroll
-    for (int c = 0; c < ATT_KT / 32; ++c) {
-      const int kv0 = t0 + c * 32;
-      if (kv0 >= Ni) break;
-      f32x16 st;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) st[r] = 0.f;
-      const float* kp = &Ks[(c * 32 + lq) * ATT_KS + h2 * 4];
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(kp + kk * 8);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], qf[kk][s], st, 0, 0, 0);
-      }
-      // online softmax over this lane's 16 kv rows (+ the other half-wave's 16)
-      if (kv0 + 32 > Ni) {   // wave-uniform: only the image's last chunk has keys past the end
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kv0 + (r & 3) + 8 * (r >> 2) + 4 * h2 >= Ni) st[r] = -INFINITY;
-      }
-      float mx = st[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
-      mx = xor32_max(mx);
-      const float m_new = fmaxf(m, mx);
-      const float alpha = expf(m - m_new);  // m = -inf on the first chunk -> 0  (natural-log scores and expf: the exact-fp32 reference path)
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { st[r] = expf(st[r] - m_new); ps += st[r]; }
-      ps = xor32_sum(ps);
-      l = l * alpha + ps;
-      m = m_new;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-      // O^T += V^T . P^T
-      const float* vp = &Vs[(c * 32 + h2 * 4) * DH + lq];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const float v0 = vp[(kk * 8 + s) * DH];
-          const float v1 = vp[(kk * 8 + s) * DH + 32];
-          o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, st[kk * 4 + s], o0, 0, 0, 0);
-          o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, st[kk * 4 + s], o1, 0, 0, 0);
-        }
-      }
-    }
-  }
-  if (wave_active && q < Ni) {
-    const float inv = 1.f / l;
-    float* op = out + (int64_t)(n0 + q) * D + head * DH;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = (r & 3) + 8 * (r >> 2) + 4 * h2;
-      op[d] = o0[r] * inv;
-      op[d + 32] = o1[r] * inv;
-    }
-  }
+  sig_attn_tile<false>(qkv, 768, qkv + 256, 768, qkv + 512, 768, n0, Ni, q0, head, out, D, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
-// The pieces the signature-attention kernels share (lt_attn.h, lt_attn_fused.h, experiments/csrc): device helpers only, no
-// __global__ function, so that every translation unit may include it.  A piece is used wherever the kernel's instructions stay
-// exactly as they were with the text written out (tools/kernel_isa_diff.py; profiles/attn_refactor_isa.txt lists the sites).
+// The pieces the signature-attention kernels share (lt_attn.h, lt_attn_fused.h, lt_attnbwd.h, experiments/csrc): device helpers
+// only, no __global__ function, so that every translation unit may include it.  The split-bf16 pieces are used wherever the kernel's
+// instructions stay exactly as they were with the text written out (tools/kernel_isa_diff.py; profiles/attn_refactor_isa.txt lists
+// the sites); sig_attn_tile, the whole body of the two exact-fp32 forward kernels, moved a few of their instructions and was gated on
+// output bits instead (tools/entry_point_digest.py; profiles/train_fwd_once_isa.txt, train_fwd_once_digest.txt).
 #pragma once
 #include "lt_gemm_split.h"
 
@@ -72,5 +74,137 @@ __device__ __forceinline__ void tr_reads(unsigned base, u32x2 (&o)[3][2]) {
   else LT_TR_READS6("");
 }
 #undef LT_TR_READS6
+
+// ---------------------------------------------------------------------------------------------
+// The exact-fp32 attention tile: 128 queries of one head of one image against all of the image's keys.  Flash-style, fp32 MFMA
+// (v_mfma_f32_32x32x2_f32), natural-log scores and expf, no n x n matrix in memory.  The body of sig_attn_kernel (lt_attn.h,
+// TRAIN = false: q arrives pre-scaled by 1/8, lse is not touched) and of ab_fwd_kernel (lt_attnbwd.h, TRAIN = true: q is multiplied
+// by 1/8 on load -- a power of two, exact -- and lse = m + logf(l) is stored per (row, head)).  The summation order of the message
+// lives here and nowhere else, so the two kernels' messages have the same bits.
+//
+// block 256 = 4 wave64, wave w owns 32 query rows.  Q, K, V, out: row 0 of the BATCH, column 0 of head 0, a row stride each (they
+// may be column blocks of one buffer; all are only read).  n0, Ni: the image's first row and row count; q0 < Ni: the tile's first
+// query within the image.  Per 32-row kv chunk and wave:
+//   S^T[kv][q] = K_h[kv,:] . Q_h[q,:]      (A = K tile from LDS, B = Q fragment held in VGPRs)
+//   in the 32x32 C/D layout a lane owns ONE query column (q = lane&31) and 16 kv rows, so the online
+//   softmax max/sum are in-lane + one exchange with lane^32;
+//   the exponentiated S^T registers ARE the B operand of  O^T[d][q] += V^T[d][kv] . P^T[kv][q]
+//   under the k-permutation k = 8kk + 4*(lane>>5) + s  <->  register 4kk+s, so P never leaves VGPRs.
+// Keys beyond the image are staged as zeros and score -inf; nothing beyond the image is loaded or stored.
+// ---------------------------------------------------------------------------------------------
+constexpr int ATT_QT = 128;      // rows a block owns (4 waves x 32): queries here and in ab_dq, keys in ab_dkv
+constexpr int ATT_KT = 64;       // rows of the other side staged per iteration
+constexpr int ATT_KS = DH + 4;   // padded LDS row stride
+
+template <bool TRAIN>
+__device__ __forceinline__ void sig_attn_tile(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ K, int64_t ldk,
+                                              const float* __restrict__ V, int64_t ldv, int n0, int Ni, int q0, int head,
+                                              float* __restrict__ out, int64_t ldo, float* __restrict__ lse /*[N][4], TRAIN only*/) {
+  __shared__ __attribute__((aligned(16))) float Ks[ATT_KT * ATT_KS];
+  __shared__ __attribute__((aligned(16))) float Vs[ATT_KT * DH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h2 = lane >> 5, lq = lane & 31;
+  const int q = q0 + wave * 32 + lq;
+  const bool wave_active = q0 + wave * 32 < Ni;  // wave-uniform
+  const float* kbase = K + (int64_t)n0 * ldk + head * DH;
+  const float* vbase = V + (int64_t)n0 * ldv + head * DH;
+
+  f32x4 qf[8];
+  {
+    const int qr = q < Ni ? q : Ni - 1;   // a lane behind the image repeats its last query; it stores nothing
+    const float* qp = Q + (int64_t)(n0 + qr) * ldq + head * DH + h2 * 4;
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      qf[kk] = *reinterpret_cast<const f32x4*>(qp + kk * 8);
+      if constexpr (TRAIN) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) qf[kk][e] *= 0.125f;
+      }
+    }
+  }
+  f32x16 o0, o1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+  float m = -INFINITY, l = 0.f;
+
+  const int srow = tid >> 4, sc4 = (tid & 15) * 4;  // staging: 16 rows x 16 float4 per pass
+  for (int t0 = 0; t0 < Ni; t0 += ATT_KT) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = srow + i * 16;
+      const int kv = t0 + r;
+      f32x4 kx = {0.f, 0.f, 0.f, 0.f}, vx = {0.f, 0.f, 0.f, 0.f};
+      if (kv < Ni) {
+        kx = *reinterpret_cast<const f32x4*>(kbase + (int64_t)kv * ldk + sc4);
+        vx = *reinterpret_cast<const f32x4*>(vbase + (int64_t)kv * ldv + sc4);
+      }
+      *reinterpret_cast<f32x4*>(&Ks[r * ATT_KS + sc4]) = kx;
+      *reinterpret_cast<f32x4*>(&Vs[r * DH + sc4]) = vx;
+    }
+    __syncthreads();
+    if (!wave_active) continue;
+#pragma unroll
+    for (int c = 0; c < ATT_KT / 32; ++c) {
+      const int kv0 = t0 + c * 32;
+      if (kv0 >= Ni) break;
+      f32x16 st;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[r] = 0.f;
+      const float* kp = &Ks[(c * 32 + lq) * ATT_KS + h2 * 4];
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(kp + kk * 8);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], qf[kk][s], st, 0, 0, 0);
+      }
+      // online softmax over this lane's 16 kv rows (+ the other half-wave's 16)
+      if (kv0 + 32 > Ni) {   // wave-uniform: only the image's last chunk has keys past the end
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kv0 + (r & 3) + 8 * (r >> 2) + 4 * h2 >= Ni) st[r] = -INFINITY;
+      }
+      float mx = st[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
+      mx = xor32_max(mx);
+      const float m_new = fmaxf(m, mx);
+      const float alpha = expf(m - m_new);  // m = -inf on the first chunk -> 0  (natural-log scores and expf: the exact-fp32 reference path)
+      float ps = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { st[r] = expf(st[r] - m_new); ps += st[r]; }
+      ps = xor32_sum(ps);
+      l = l * alpha + ps;
+      m = m_new;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+      // O^T += V^T . P^T
+      const float* vp = &Vs[(c * 32 + h2 * 4) * DH + lq];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float v0 = vp[(kk * 8 + s) * DH];
+          const float v1 = vp[(kk * 8 + s) * DH + 32];
+          o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, st[kk * 4 + s], o0, 0, 0, 0);
+          o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, st[kk * 4 + s], o1, 0, 0, 0);
+        }
+      }
+    }
+  }
+  if (wave_active && q < Ni) {
+    const float inv = 1.f / l;
+    float* op = out + (int64_t)(n0 + q) * ldo + head * DH;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * h2;
+      op[d] = o0[r] * inv;
+      op[d + 32] = o1[r] * inv;
+    }
+    if constexpr (TRAIN) {
+      if (h2 == 0) lse[(int64_t)(n0 + q) * HEADS + head] = m + logf(l);   // (both halves hold the same m and l)
+    }
+  }
+}
 
 }  // namespace lt

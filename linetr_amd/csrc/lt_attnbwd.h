@@ -2,8 +2,8 @@
 // image = one softmax domain), forward with the softmax statistics and backward.  Head-major rows (column c = h*64 + d); q, k, v, o, dO,
 // dq, dk, dv are [N][*] with a row stride of their own (q | k | v may be three column blocks of one [N][768] buffer).  q is UNSCALED here:
 // the kernels multiply by 1/8 on load (a power of two, exact), so the scores have the bits sig_attn_kernel (lt_attn.h) computes on
-// pre-scaled q.
-//   ab_fwd_kernel     sig_attn_kernel's arithmetic, statement by statement, + lse [N][4] = m + logf(l) per (row, head)
+// pre-scaled q.  Tile sizes are the forward's: ATT_QT rows per block, ATT_KT staged rows, ATT_KS LDS row stride (lt_attn_parts.h).
+//   ab_fwd_kernel     sig_attn_kernel's body (sig_attn_tile, lt_attn_parts.h) + lse [N][4] = m + logf(l) per (row, head)
 //   ab_delta_kernel   delta [N][4] = sum_d dO[r][h][d] o[r][h][d]  (by the MFMA chain that contracts dP)
 //   ab_dq_kernel      per (image, head, 128 queries), walking the image's keys:   dQ = (dS K) / 8
 //   ab_dkv_kernel     per (image, head, 128 keys), walking the image's queries:   dV = P^T dO,  dK = dS^T (q / 8)
@@ -24,18 +24,14 @@
 
 namespace lt {
 
-constexpr int AB_T = 128;        // rows a block owns (4 waves x 32): queries in ab_fwd / ab_dq, keys in ab_dkv
-constexpr int AB_S = 64;         // rows of the other side staged per iteration
-constexpr int AB_LS = DH + 4;    // padded LDS row stride, the forward's
-
 // block b of a head -> its image (first row n0, Ni rows) and the first row t0 of its tile within the image; false: no such tile
 __device__ __forceinline__ bool ab_find_tile(const int* __restrict__ cu_sub, int n_images, int b, int& n0, int& Ni, int& t0) {
   int first = 0;
   for (int i = 0; i < n_images; ++i) {
     const int a = cu_sub[i], n = cu_sub[i + 1] - a;
-    const int nt = n > 0 ? (n + AB_T - 1) / AB_T : 0;
+    const int nt = n > 0 ? (n + ATT_QT - 1) / ATT_QT : 0;
     if (b < first + nt) {
-      n0 = a; Ni = n; t0 = (b - first) * AB_T;
+      n0 = a; Ni = n; t0 = (b - first) * ATT_QT;
       return true;
     }
     first += nt;
@@ -51,13 +47,13 @@ __device__ __forceinline__ void ab_zero(f32x16& a) {
   for (int r = 0; r < 16; ++r) a[r] = 0.f;
 }
 
-// acc[row][col] = sum_d T[row0 + row][d] * f[col][d]: T a staged tile (row stride AB_LS), f the lane's own 64-channel fragment.
+// acc[row][col] = sum_d T[row0 + row][d] * f[col][d]: T a staged tile (row stride ATT_KS), f the lane's own 64-channel fragment.
 // PARTS = 1: one MFMA chain over the 64 channels, the forward's scores bit for bit.  PARTS = 4 (dP and delta): four chains of 16
 // channels, each started at zero, added in channel order -- the difference dP - delta cancels most of either term, and a chain's
 // rounding grows with its length (measured on the peaky family's two-row image: 1.2 x the bar with one chain, inside it with four).
 template <int PARTS>
 __device__ __forceinline__ void ab_rows_dot(const float* __restrict__ T, int row0, int lq, int h2, const f32x4 (&f)[8], f32x16& acc) {
-  const float* tp = &T[(row0 + lq) * AB_LS + h2 * 4];
+  const float* tp = &T[(row0 + lq) * ATT_KS + h2 * 4];
 #pragma unroll
   for (int p = 0; p < PARTS; ++p) {
     f32x16 part;
@@ -79,13 +75,13 @@ __device__ __forceinline__ void ab_cols_acc(const float* __restrict__ T, int row
   f32x16 p0, p1;
   ab_zero(p0);
   ab_zero(p1);
-  const float* tp = &T[(row0 + h2 * 4) * AB_LS + lq];
+  const float* tp = &T[(row0 + h2 * 4) * ATT_KS + lq];
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const float a0 = tp[(kk * 8 + s) * AB_LS];
-      const float a1 = tp[(kk * 8 + s) * AB_LS + 32];
+      const float a0 = tp[(kk * 8 + s) * ATT_KS];
+      const float a1 = tp[(kk * 8 + s) * ATT_KS + 32];
       p0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, w[kk * 4 + s], p0, 0, 0, 0);
       p1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, w[kk * 4 + s], p1, 0, 0, 0);
     }
@@ -94,12 +90,12 @@ __device__ __forceinline__ void ab_cols_acc(const float* __restrict__ T, int row
   o1 += p1;
 }
 
-// rows r0 .. r0 + AB_S - 1 of one head of an image (base: its row 0, column 0 of the head) into a tile, times `scale`; rows at or
+// rows r0 .. r0 + ATT_KT - 1 of one head of an image (base: its row 0, column 0 of the head) into a tile, times `scale`; rows at or
 // beyond Ni are zeros and are not loaded
 __device__ __forceinline__ void ab_stage(float* __restrict__ T, const float* __restrict__ base, int64_t ld, int r0, int Ni, float scale) {
   const int srow = threadIdx.x >> 4, sc4 = (threadIdx.x & 15) * 4;
 #pragma unroll
-  for (int i = 0; i < AB_S / 16; ++i) {
+  for (int i = 0; i < ATT_KT / 16; ++i) {
     const int r = srow + i * 16;
     f32x4 x = {0.f, 0.f, 0.f, 0.f};
     if (r0 + r < Ni) {
@@ -107,7 +103,7 @@ __device__ __forceinline__ void ab_stage(float* __restrict__ T, const float* __r
 #pragma unroll
       for (int e = 0; e < 4; ++e) x[e] *= scale;
     }
-    *reinterpret_cast<f32x4*>(&T[r * AB_LS + sc4]) = x;
+    *reinterpret_cast<f32x4*>(&T[r * ATT_KS + sc4]) = x;
   }
 }
 
@@ -122,110 +118,15 @@ __device__ __forceinline__ void ab_frag(const float* __restrict__ p, float scale
 }
 
 // ---------------------------------------------------------------------------------------------
-// Forward with statistics: grid (floor(N / 128) + n_images, head), block 256.  The body is sig_attn_kernel's.
-// It is kept as that kernel's text, line for line, and not rewritten on ab_stage / ab_rows_dot / ab_cols_acc above: a diff of the two bodies
-// then shows only the pointers, the strides and lse, which is what keeps the message's bits those of the inference kernel.
+// Forward with statistics: grid (floor(N / 128) + n_images, head), block 256.  sig_attn_tile<true> (lt_attn_parts.h), the body
+// sig_attn_kernel runs as well: the message has the inference kernel's bits because both execute the same statements.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ab_fwd_kernel(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ K, int64_t ldk,
                                                      const float* __restrict__ V, int64_t ldv, const int* __restrict__ cu_sub, int n_images,
                                                      float* __restrict__ out, int64_t ldo, float* __restrict__ lse /*[N][4]*/) {
-  __shared__ __attribute__((aligned(16))) float Ks[AB_S * AB_LS];
-  __shared__ __attribute__((aligned(16))) float Vs[AB_S * DH];
-  const int head = blockIdx.y;
   int n0, Ni, q0;
   if (!ab_find_tile(cu_sub, n_images, blockIdx.x, n0, Ni, q0)) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h2 = lane >> 5, lq = lane & 31;
-  const int q = q0 + wave * 32 + lq;
-  const bool wave_active = q0 + wave * 32 < Ni;  // wave-uniform
-  const float* kbase = K + (int64_t)n0 * ldk + head * DH;
-  const float* vbase = V + (int64_t)n0 * ldv + head * DH;
-
-  f32x4 qf[8];
-  {
-    const int qr = q < Ni ? q : Ni - 1;
-    ab_frag(Q + (int64_t)(n0 + qr) * ldq + head * DH + h2 * 4, 0.125f, qf);
-  }
-  f32x16 o0, o1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-  float m = -INFINITY, l = 0.f;
-
-  const int srow = tid >> 4, sc4 = (tid & 15) * 4;  // staging: 16 rows x 16 float4 per pass
-  for (int t0 = 0; t0 < Ni; t0 += AB_S) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = srow + i * 16;
-      const int kv = t0 + r;
-      f32x4 kx = {0.f, 0.f, 0.f, 0.f}, vx = {0.f, 0.f, 0.f, 0.f};
-      if (kv < Ni) {
-        kx = *reinterpret_cast<const f32x4*>(kbase + (int64_t)kv * ldk + sc4);
-        vx = *reinterpret_cast<const f32x4*>(vbase + (int64_t)kv * ldv + sc4);
-      }
-      *reinterpret_cast<f32x4*>(&Ks[r * AB_LS + sc4]) = kx;
-      *reinterpret_cast<f32x4*>(&Vs[r * DH + sc4]) = vx;
-    }
-    __syncthreads();
-    if (!wave_active) continue;
-#pragma unroll
-    for (int c = 0; c < AB_S / 32; ++c) {
-      const int kv0 = t0 + c * 32;
-      if (kv0 >= Ni) break;
-      f32x16 st;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) st[r] = 0.f;
-      const float* kp = &Ks[(c * 32 + lq) * AB_LS + h2 * 4];
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(kp + kk * 8);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], qf[kk][s], st, 0, 0, 0);
-      }
-      if (kv0 + 32 > Ni) {   // wave-uniform: only the image's last chunk has keys past the end
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kv0 + (r & 3) + 8 * (r >> 2) + 4 * h2 >= Ni) st[r] = -INFINITY;
-      }
-      float mx = st[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
-      mx = xor32_max(mx);
-      const float m_new = fmaxf(m, mx);
-      const float alpha = expf(m - m_new);  // m = -inf on the first chunk -> 0
-      float ps = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { st[r] = expf(st[r] - m_new); ps += st[r]; }
-      ps = xor32_sum(ps);
-      l = l * alpha + ps;
-      m = m_new;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-      // O^T += V^T . P^T
-      const float* vp = &Vs[(c * 32 + h2 * 4) * DH + lq];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const float v0 = vp[(kk * 8 + s) * DH];
-          const float v1 = vp[(kk * 8 + s) * DH + 32];
-          o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, st[kk * 4 + s], o0, 0, 0, 0);
-          o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, st[kk * 4 + s], o1, 0, 0, 0);
-        }
-      }
-    }
-  }
-  if (wave_active && q < Ni) {
-    const float inv = 1.f / l;
-    float* op = out + (int64_t)(n0 + q) * ldo + head * DH;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = (r & 3) + 8 * (r >> 2) + 4 * h2;
-      op[d] = o0[r] * inv;
-      op[d + 32] = o1[r] * inv;
-    }
-    if (h2 == 0) lse[(int64_t)(n0 + q) * HEADS + head] = m + logf(l);   // (both halves hold the same m and l)
-  }
+  sig_attn_tile<true>(Q, ldq, K, ldk, V, ldv, n0, Ni, q0, blockIdx.y, out, ldo, lse);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -235,7 +136,7 @@ __global__ __launch_bounds__(256) void ab_fwd_kernel(const float* __restrict__ Q
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void ab_delta_kernel(const float* __restrict__ dO, int64_t ldg, const float* __restrict__ O, int64_t ldo,
                                                       int64_t N, float* __restrict__ delta) {
-  __shared__ __attribute__((aligned(16))) float Os[32 * AB_LS];
+  __shared__ __attribute__((aligned(16))) float Os[32 * ATT_KS];
   const int head = blockIdx.y, lane = threadIdx.x, h2 = lane >> 5, lq = lane & 31;
   const int64_t r0 = (int64_t)blockIdx.x * 32;
   const int srow = lane >> 4, sc4 = (lane & 15) * 4;
@@ -244,7 +145,7 @@ __global__ __launch_bounds__(64) void ab_delta_kernel(const float* __restrict__ 
     const int r = srow + i * 4;
     f32x4 x = {0.f, 0.f, 0.f, 0.f};
     if (r0 + r < N) x = *reinterpret_cast<const f32x4*>(O + (r0 + r) * ldo + head * DH + sc4);
-    *reinterpret_cast<f32x4*>(&Os[r * AB_LS + sc4]) = x;
+    *reinterpret_cast<f32x4*>(&Os[r * ATT_KS + sc4]) = x;
   }
   const int64_t row = r0 + lq < N ? r0 + lq : N - 1;
   f32x4 gf[8];
@@ -269,8 +170,8 @@ __global__ __launch_bounds__(256) void ab_dq_kernel(const float* __restrict__ Q,
                                                     const float* __restrict__ V, int64_t ldv, const float* __restrict__ dO, int64_t ldg,
                                                     const float* __restrict__ lse, const float* __restrict__ delta,
                                                     const int* __restrict__ cu_sub, int n_images, float* __restrict__ dQ, int64_t lddq) {
-  __shared__ __attribute__((aligned(16))) float Ks[AB_S * AB_LS];
-  __shared__ __attribute__((aligned(16))) float Vs[AB_S * AB_LS];
+  __shared__ __attribute__((aligned(16))) float Ks[ATT_KT * ATT_KS];
+  __shared__ __attribute__((aligned(16))) float Vs[ATT_KT * ATT_KS];
   const int head = blockIdx.y;
   int n0, Ni, q0;
   if (!ab_find_tile(cu_sub, n_images, blockIdx.x, n0, Ni, q0)) return;
@@ -290,14 +191,14 @@ __global__ __launch_bounds__(256) void ab_dq_kernel(const float* __restrict__ Q,
 
   const float* kbase = K + (int64_t)n0 * ldk + head * DH;
   const float* vbase = V + (int64_t)n0 * ldv + head * DH;
-  for (int t0 = 0; t0 < Ni; t0 += AB_S) {
+  for (int t0 = 0; t0 < Ni; t0 += ATT_KT) {
     __syncthreads();
     ab_stage(Ks, kbase, ldk, t0, Ni, 1.f);
     ab_stage(Vs, vbase, ldv, t0, Ni, 1.f);
     __syncthreads();
     if (!wave_active) continue;
 #pragma unroll
-    for (int c = 0; c < AB_S / 32; ++c) {
+    for (int c = 0; c < ATT_KT / 32; ++c) {
       const int kv0 = t0 + c * 32;
       if (kv0 >= Ni) break;
       f32x16 st, dp;
@@ -332,9 +233,9 @@ __global__ __launch_bounds__(256) void ab_dkv_kernel(const float* __restrict__ Q
                                                      const float* __restrict__ lse, const float* __restrict__ delta,
                                                      const int* __restrict__ cu_sub, int n_images, float* __restrict__ dK, int64_t lddk,
                                                      float* __restrict__ dV, int64_t lddv) {
-  __shared__ __attribute__((aligned(16))) float Qs[AB_S * AB_LS];
-  __shared__ __attribute__((aligned(16))) float Gs[AB_S * AB_LS];
-  __shared__ float Ls[AB_S], Ds[AB_S];
+  __shared__ __attribute__((aligned(16))) float Qs[ATT_KT * ATT_KS];
+  __shared__ __attribute__((aligned(16))) float Gs[ATT_KT * ATT_KS];
+  __shared__ float Ls[ATT_KT], Ds[ATT_KT];
   const int head = blockIdx.y;
   int n0, Ni, k0;
   if (!ab_find_tile(cu_sub, n_images, blockIdx.x, n0, Ni, k0)) return;
@@ -357,11 +258,11 @@ __global__ __launch_bounds__(256) void ab_dkv_kernel(const float* __restrict__ Q
 
   const float* qbase = Q + (int64_t)n0 * ldq + head * DH;
   const float* gbase = dO + (int64_t)n0 * ldg + head * DH;
-  for (int t0 = 0; t0 < Ni; t0 += AB_S) {
+  for (int t0 = 0; t0 < Ni; t0 += ATT_KT) {
     __syncthreads();
     ab_stage(Qs, qbase, ldq, t0, Ni, 0.125f);
     ab_stage(Gs, gbase, ldg, t0, Ni, 1.f);
-    if (tid < AB_S) {
+    if (tid < ATT_KT) {
       const bool in = t0 + tid < Ni;
       Ls[tid] = in ? lse[(int64_t)(n0 + t0 + tid) * HEADS + head] : 0.f;
       Ds[tid] = in ? delta[(int64_t)(n0 + t0 + tid) * HEADS + head] : 0.f;
@@ -369,7 +270,7 @@ __global__ __launch_bounds__(256) void ab_dkv_kernel(const float* __restrict__ Q
     __syncthreads();
     if (!wave_active) continue;
 #pragma unroll
-    for (int c = 0; c < AB_S / 32; ++c) {
+    for (int c = 0; c < ATT_KT / 32; ++c) {
       const int q0 = t0 + c * 32;
       if (q0 >= Ni) break;
       f32x16 st;

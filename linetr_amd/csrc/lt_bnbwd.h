@@ -2,14 +2,9 @@
 // (Conv1d(512, 512) -> BatchNorm1d(512) -> ReLU -> Conv1d(512, 256), models/line_transformer.py:157-166) that lt_linbwd.h and
 // lt_attnbwd.h leave open.  z [rows][C] with a row stride, the widths and strides of bn_train_layer (lt_bntrain.h).
 //
-// Forward, out of place (z is kept: the backward reads it):
-//   bn_partial_kernel       (lt_bntrain.h, as it is) per-channel sum / sum of squares of a row chunk in float64, bn_row_chunks chunks
-//   bn_fwd_finalize_kernel  bn_finalize_kernel's arithmetic, statement by statement (the same alpha, beta' and running statistics bit for
-//                           bit), plus the saved statistics float64 [mean[C] | invstd[C]]; eval mode: mean and variance are the running
-//                           ones, nothing is updated and no partials are read
-//   bn_fwd_apply_kernel     y = max(z alpha + beta', 0), or without the max, into y [rows][ldy]: bn_apply_relu_kernel's two roundings
-// Backward, as torch autograd differentiates relu(batch_norm(z)):  g' = g where y > 0 else 0 (y: the layer's own output, nothing is
-// recomputed to decide a sign; no y: g' = g),  xhat = (z - mean) invstd,
+// The forward is lt_bntrain.h's (bn_forward_launch), out of place -- z is kept: the backward reads it -- and with the saved statistics
+// float64 [mean[C] | invstd[C]].  Here is the backward, as torch autograd differentiates relu(batch_norm(z)):  g' = g where y > 0
+// else 0 (y: the layer's own output, nothing is recomputed to decide a sign; no y: g' = g),  xhat = (z - mean) invstd,
 //   dbeta = sum_r g'      dgamma = sum_r g' xhat      dz = gamma invstd (g' - dbeta / n - xhat dgamma / n)       (eval: dz = gamma invstd g')
 //   bn_bwd_partial_kernel   per row chunk (the forward's chunking) and channel: sum g' and sum g' (z - mean), float64, z - mean formed
 //                           against the float64 mean; one partial row per block, no atomics
@@ -25,63 +20,6 @@ namespace lt {
 
 constexpr int BNB_QUADS = 32;      // channel quads side by side in a block of bn_bwd_partial_kernel (128 channels, 512 bytes of a row)
 constexpr int BNB_RP = 8;          // rows in parallel
-
-// one thread per channel.  mode 0 (train): bn_finalize_kernel and the saved statistics; running may be null (no update).
-// mode 1 (eval): mean | var = running, which is only read; partial is not read.
-__global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(const double* __restrict__ partial, int n_blocks, int C, int64_t rows,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                              float momentum, float* __restrict__ running /*mean[C] | var[C]*/, int eval,
-                                                              float* __restrict__ affine /*alpha[C] | beta'[C]*/,
-                                                              double* __restrict__ save /*mean[C] | invstd[C]*/) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  if (eval) {
-    const double mean = (double)running[c];
-    const double invstd = 1.0 / sqrt((double)running[C + c] + (double)eps);
-    const double alpha = (double)gamma[c] * invstd;
-    affine[c] = (float)alpha;
-    affine[C + c] = (float)((double)beta[c] - mean * alpha);
-    save[c] = mean;
-    save[C + c] = invstd;
-    return;
-  }
-  double s = 0.0, q = 0.0;
-  for (int b = 0; b < n_blocks; ++b) { s += partial[(int64_t)b * 2 * C + c]; q += partial[(int64_t)b * 2 * C + C + c]; }
-  const double n = (double)rows;
-  const double mean = s / n;
-  double var = q / n - mean * mean;            // biased (what the normalisation uses)
-  if (var < 0.0) var = 0.0;
-  const double invstd = 1.0 / sqrt(var + (double)eps);
-  const double alpha = (double)gamma[c] * invstd;
-  affine[c] = (float)alpha;
-  affine[C + c] = (float)((double)beta[c] - mean * alpha);
-  save[c] = mean;
-  save[C + c] = invstd;
-  if (running) {
-    const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
-    running[c] = (float)((1.0 - (double)momentum) * (double)running[c] + (double)momentum * mean);
-    running[C + c] = (float)((1.0 - (double)momentum) * (double)running[C + c] + (double)momentum * unbiased);
-  }
-}
-
-// out of place, four channels per thread (C % 4 == 0, ldz % 4 == 0, ldy % 4 == 0)
-__global__ __launch_bounds__(256) void bn_fwd_apply_kernel(const float* __restrict__ z, int64_t rows, int C, int64_t ldz,
-                                                           const float* __restrict__ affine, int relu, float* __restrict__ y, int64_t ldy) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int c4 = C / 4;
-  if (i >= rows * c4) return;
-  const int64_t r = i / c4;
-  const int c = (int)(i - r * c4) * 4;
-  f32x4 v = *reinterpret_cast<const f32x4*>(z + r * ldz + c);
-  const f32x4 a = *reinterpret_cast<const f32x4*>(affine + c), b = *reinterpret_cast<const f32x4*>(affine + C + c);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma clang fp contract(off)
-    const float t = v[k] * a[k] + b[k];
-    v[k] = relu ? fmaxf(t, 0.f) : t;
-  }
-  *reinterpret_cast<f32x4*>(y + r * ldy + c) = v;
-}
 
 // grid (row chunks, ceil(C / 4 / BNB_QUADS)); partial [gridDim.x][2 C]: sum g' | sum g' (z - mean).  A block whose chunk lies behind
 // the last row writes zero partials.  y may be null (no mask).

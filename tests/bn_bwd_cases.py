@@ -1,7 +1,7 @@
 """Case generator, references and error measure of the BatchNorm forward-for-training / backward unit tests (tests/test_gpu_bn_bwd.py,
 tests/test_bn_bwd_cases_cpu.py; reused by tools/sig_layer_report.py, which writes profiles/bn_bwd_errors.txt).  Test infrastructure only.
 
-The kernels (csrc/lt_bnbwd.h behind linetr_bn_forward / linetr_bn_backward) compute, per channel over ALL rows of z [rows][C],
+The kernels (csrc/lt_bntrain.h behind linetr_bn_forward, csrc/lt_bnbwd.h behind linetr_bn_backward) compute, per channel over ALL rows of z [rows][C],
 
     forward    mean, var = the mean and the BIASED variance;  invstd = 1 / sqrt(var + eps);  y = relu?((z - mean) invstd gamma + beta)
     backward   g' = g where y > 0 else 0 (y is an INPUT: the layer's own output; without ReLU g' = g);  xhat = (z - mean) invstd

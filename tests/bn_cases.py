@@ -1,7 +1,7 @@
 """Case generator, references and error measure of the train-mode BatchNorm unit tests (tests/test_gpu_bn_train.py,
 tests/test_bn_cases_cpu.py; reused by tools/bn_unit_report.py, which writes profiles/bn_unit_errors.txt).  Test infrastructure only.
 
-The kernels (lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_relu_kernel behind bn_train_layer) compute, per channel
+The kernels (lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel behind bn_train_layer) compute, per channel
 over ALL rows of z [rows][C],
 
     mean, var = the mean and the BIASED variance        y = relu((z - mean) / sqrt(var + 1e-5) * gamma + beta)

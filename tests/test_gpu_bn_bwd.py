@@ -1,4 +1,4 @@
-"""GPU: BatchNorm (+ ReLU) for training -- the forward that keeps z and the statistics, and the backward (csrc/lt_bnbwd.h;
+"""GPU: BatchNorm (+ ReLU) for training -- the forward that keeps z and the statistics, and the backward (csrc/lt_bntrain.h, lt_bnbwd.h;
 linetr_bn_forward / linetr_bn_backward; Engine.bn_forward / bn_backward; linetr_amd.train_ops.batch_norm_relu) -- against the float64
 formulae that tests/test_bn_bwd_cases_cpu.py pins to torch's float64 autograd.
 

@@ -1,4 +1,4 @@
-"""GPU: the train-mode BatchNorm kernels ALONE (lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_relu_kernel behind
+"""GPU: the train-mode BatchNorm kernels ALONE (lt_bntrain.h: bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel behind
 bn_train_layer; the train-only first layers word_mlp1_kernel<false> / line_mlp1_kernel<false> and pos_encoder_bn around them),
 through linetr_debug_bn_train, against float64 references written from the formula, at the channel widths, row strides and row
 counts where their loops and chunks end.
@@ -12,7 +12,7 @@ What ran here for the first time: every width but 32, 64, 128, 256 and 512 (C = 
 without a row; 256 < C < 512: a second channel pass for part of the block -- its barrier sat in a loop whose trip count differed
 between the threads of a block, and for C = 260 between the lanes of a wave; the loop now runs to the block's bound with the loads
 and stores guarded, same summation order), every row stride but ld = C (bn_train_layer now refuses a stride or a base that
-bn_apply_relu_kernel's 16-byte accesses cannot take), the chunking's edges and its empty trailing blocks.
+bn_apply_kernel's 16-byte accesses cannot take), the chunking's edges and its empty trailing blocks.
 
 The 'constant' family: a constant channel's variance q / n - mean^2 comes out as a rounding residue of either sign in float64; the
 clamp makes it >= 0 and the test asks for 0 <= var inside the bar (all-zero channels: exactly 0), no NaN anywhere, y inside the bar.
