@@ -28,6 +28,8 @@
  *                unit tests): added diagnostics symbols, the version stays.
  *                + linetr_bn_forward, linetr_bn_backward and their _workspace_bytes (BatchNorm on batch statistics with a backward): added
  *                symbols, nothing existing changes, the version stays.
+ *                + linetr_cls_pool_train_forward / _backward, linetr_layer_norm_forward / _backward / _backward_workspace_bytes,
+ *                linetr_gelu_forward / _backward (the descriptive layer's training kernels): added symbols, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -526,6 +528,59 @@ int64_t linetr_bn_backward_workspace_bytes(int64_t rows, int32_t C);
 int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_y, int64_t ldy, const float* d_g, int64_t ldg,
                        const double* d_save, const float* d_gamma, int64_t rows, int32_t C, int32_t mode, float* d_dz, int64_t lddz,
                        float* d_dgamma, float* d_dbeta, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- the line descriptive layer for training (section 8(f) "next" row 4: the fifth link) ---------- */
+
+/* LineDescriptiveEncoder (models/line_transformer.py:75-91 = MultiHeadAttention + FeedForward, models/line_attention.py:23-94) is
+ * trained in the folded form of DESIGN 3.1-3.3: KeylineEncoder reads only the CLS row of its output (:128), the CLS query row is never
+ * masked, so per segment (sub-line) l of S token rows and head h, with u_lh = Wk_h^T (q_lh / 8) made by the linear layers above,
+ *   s_t = u_h . x_t      lse_h = m + logf(l) of the scores      p_t = exp(s_t - lse_h)      pooled_h = sum_t p_t x_t
+ * and the value projection is applied to pooled_h afterwards.  The key bias adds one constant per (l, h), which the softmax cancels.
+ * Backward, as torch autograd differentiates the above:
+ *   delta_h = dpooled_h . pooled_h      dp_t = dpooled_h . x_t      ds_t = p_t (dp_t - delta_h)      (p recomputed from x, u and lse)
+ *   dx_t = sum_h (p_t dpooled_h + ds_t u_h)      du_h = sum_t ds_t x_t  (token order)
+ *   d_x, d_dx     [L S][256 of ldx / lddx] float32 token rows, segment l = rows l S .. l S + S - 1;  1 <= S <= 256, 0 <= L <= 2^24
+ *   d_u, d_du     [L][1024 of ldu / lddu], head h in columns h*256 ..
+ *   d_pooled, d_dpooled [L][1024] contiguous      d_lse [L][4] contiguous
+ *   d_dx, d_du    each may be NULL and is then not computed (what is computed has the same bits either way)
+ * One launch each way, one wave per segment, x read once per direction (the backward writes dx as well): bound by bytes.
+ * Deterministic: no atomics, every sum in a fixed order.  Rows behind L S and columns behind the widths are neither read nor written.
+ * Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  L = 0: nothing is launched.  LINETR_E_ARG, nothing
+ * launched: S or L outside the above, a row stride below the width or no multiple of 4 floats (that of a NULL output is not read), a
+ * pointer that is not 16-byte aligned, a NULL required pointer (every one but d_dx / d_du). */
+int linetr_cls_pool_train_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
+                                  float* d_pooled, float* d_lse, void* stream);
+int linetr_cls_pool_train_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                                   const float* d_lse, const float* d_dpooled, int64_t L, int32_t S, float* d_dx, int64_t lddx,
+                                   float* d_du, int64_t lddu, void* stream);
+
+/* torch.nn.LayerNorm(256) on rows with an optional residual, as the reference's `q += residual; q = self.layer_norm(q)`
+ * (models/line_attention.py:72-73, :91-92), and its backward:
+ *   v = a + r (one float32 add; d_r NULL: v = a)      mean, var (biased) two-pass on the row      rstd = 1 / sqrt(var + eps)
+ *   y = (v - mean) rstd gamma + beta      d_stats [rows][2] float32 <- mean | rstd: what the backward takes
+ *   backward:  xhat = (v - mean) rstd      gg = g gamma      dx = rstd (gg - mean_c gg - xhat mean_c (gg xhat)): the gradient of a AND of r
+ *     dgamma = sum_r g xhat      dbeta = sum_r g      (float32 partial sums per chunk of rows, the chunks added in ascending order in
+ *     float64 through the workspace)      d_dx, d_dgamma, d_dbeta: each may be NULL and is then not computed
+ * C must be 256; 0 <= rows <= 2^30; every row stride at least 256 and a multiple of 4 floats; 16-byte aligned pointers.  Forward one
+ * launch, backward two.  Deterministic.  Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  rows = 0: no row
+ * is touched (dgamma / dbeta, where asked for, are zeros).  LINETR_E_ARG, nothing launched: C != 256, rows outside the above, eps <= 0, a
+ * bad row stride (that of a NULL tensor is not read), a pointer that is not 16-byte aligned, a NULL required pointer (forward: d_a,
+ * d_gamma, d_beta, d_y, d_stats; backward: d_a, d_stats, d_gamma, d_g, and the workspace when d_dgamma or d_dbeta is asked for), a
+ * workspace smaller than linetr_layer_norm_backward_workspace_bytes says (0 for a shape that is refused). */
+int64_t linetr_layer_norm_backward_workspace_bytes(int64_t rows, int32_t C);
+int linetr_layer_norm_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                              const float* d_beta, float eps, int64_t rows, int32_t C, float* d_y, int64_t ldy, float* d_stats, void* stream);
+int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                               const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dx, int64_t lddx,
+                               float* d_dgamma, float* d_dbeta, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* F.gelu, erf form (models/line_attention.py:89), on rows [rows][C of ld*]:  y = z Phi(z)      dz = g (Phi(z) + z phi(z)) from the saved
+ * pre-activation z;  Phi(z) = erfc(-z / sqrt 2) / 2, phi(z) = exp(-z^2 / 2) / sqrt(2 pi).  4 <= C <= 4096, C % 4 == 0, 0 <= rows <= 2^30
+ * (rows C / 4 below 2^39).  One launch.  Asynchronous; `h` may be NULL.  LINETR_E_ARG, nothing launched: a shape outside the above, a row
+ * stride below C or no multiple of 4 floats, a NULL or misaligned pointer. */
+int linetr_gelu_forward(LinetrHandle* h, const float* d_z, int64_t ldz, int64_t rows, int32_t C, float* d_y, int64_t ldy, void* stream);
+int linetr_gelu_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dz,
+                         int64_t lddz, void* stream);
 
 /* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
 

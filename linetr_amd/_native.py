@@ -119,6 +119,13 @@ ABI = {
     "linetr_bn_forward": (i32, [vp, vp, i64, i64, i32, vp, vp, f32, f32, vp, i32, i32, vp, i64, vp, vp, i64, vp]),
     "linetr_bn_backward_workspace_bytes": (i64, [i64, i32]),
     "linetr_bn_backward": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, vp]),
+    "linetr_cls_pool_train_forward": (i32, [vp, vp, i64, vp, i64, i64, i32, vp, vp, vp]),
+    "linetr_cls_pool_train_backward": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, vp, i64, vp, i64, vp]),
+    "linetr_layer_norm_backward_workspace_bytes": (i64, [i64, i32]),
+    "linetr_layer_norm_forward": (i32, [vp, vp, i64, vp, i64, vp, vp, f32, i64, i32, vp, i64, vp, vp]),
+    "linetr_layer_norm_backward": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, i64, vp]),
+    "linetr_gelu_forward": (i32, [vp, vp, i64, i64, i32, vp, i64, vp]),
+    "linetr_gelu_backward": (i32, [vp, vp, i64, vp, i64, i64, i32, vp, i64, vp]),
     "linetr_gt_assign_workspace_bytes": (i64, [i32, i32, i32]),
     "linetr_gt_assign": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_superpoint_heads": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -1,7 +1,8 @@
 // liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h): the validation step (lt_valstep.h),
 // the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
-// attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h) and the
-// ground-truth line assignment in front of them (lt_gtassign.h).
+// attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h), the
+// descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h) and the ground-truth line assignment in
+// front of them (lt_gtassign.h).
 #include <algorithm>
 
 #include "lt_handle.h"
@@ -10,6 +11,7 @@
 #include "lt_linbwd.h"
 #include "lt_attnbwd.h"
 #include "lt_bnbwd.h"
+#include "lt_descbwd.h"
 #include "lt_gtassign.h"
 
 using namespace lt;
@@ -529,6 +531,142 @@ extern "C" int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;
+}
+
+// =============================================================================================
+// the line descriptive layer for training: CLS token pooling, LayerNorm, GELU, each forward and backward (lt_descbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t CP_MAX_L = (int64_t)1 << 24;      // L S <= 2^32 rows are indexed in 64 bits; the grid of L / 4 blocks stays small
+constexpr int64_t LN_MAX_ROWS = (int64_t)1 << 30;
+bool cp_dims_ok(int64_t L, int S) { return L >= 0 && L <= CP_MAX_L && S >= 1 && S <= CP_MAX_S; }
+int64_t ln_chunks(int64_t rows) { return (rows + LN_CHUNK - 1) / LN_CHUNK; }
+}  // namespace
+
+extern "C" int linetr_cls_pool_train_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
+                                             float* d_pooled, float* d_lse, void* stream) {
+  // every refusal comes before the first launch
+  if (!cp_dims_ok(L, S)) return fail(LINETR_E_ARG, "cls_pool_train_forward: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", (long long)L, S, CP_MAX_S);
+  if (!lin_stride_ok(ldx, D) || !lin_stride_ok(ldu, HEADS * D))
+    return fail(LINETR_E_ARG, "cls_pool_train_forward: row strides %lld / %lld (at least 256 / 1024, multiples of 4 floats)", (long long)ldx, (long long)ldu);
+  if (!d_x || !d_u || !d_pooled || !d_lse) return fail(LINETR_E_ARG, "cls_pool_train_forward: null pointer");
+  if (!aligned16(d_x) || !aligned16(d_u) || !aligned16(d_pooled) || !aligned16(d_lse))
+    return fail(LINETR_E_ARG, "cls_pool_train_forward: every tensor must be 16-byte aligned");
+  if (L == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "cls_pool_train_fwd", 2.0 * HEADS * 2.0 * L * S * D, 4.0 * L * ((double)S * D + 2.0 * HEADS * D + HEADS));
+  hipLaunchKernelGGL(cp_fwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, L, (int)S, d_pooled, d_lse);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_cls_pool_train_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                                              const float* d_lse, const float* d_dpooled, int64_t L, int32_t S, float* d_dx, int64_t lddx,
+                                              float* d_du, int64_t lddu, void* stream) {
+  if (!cp_dims_ok(L, S)) return fail(LINETR_E_ARG, "cls_pool_train_backward: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", (long long)L, S, CP_MAX_S);
+  if (!lin_stride_ok(ldx, D) || !lin_stride_ok(ldu, HEADS * D) || (d_dx && !lin_stride_ok(lddx, D)) || (d_du && !lin_stride_ok(lddu, HEADS * D)))
+    return fail(LINETR_E_ARG, "cls_pool_train_backward: every row stride must be at least the width (256 tokens, 1024 u) and a multiple of 4 floats");
+  if (!d_x || !d_u || !d_pooled || !d_lse || !d_dpooled) return fail(LINETR_E_ARG, "cls_pool_train_backward: null pointer");
+  if (!aligned16(d_x) || !aligned16(d_u) || !aligned16(d_pooled) || !aligned16(d_lse) || !aligned16(d_dpooled) || !aligned16(d_dx) || !aligned16(d_du))
+    return fail(LINETR_E_ARG, "cls_pool_train_backward: every tensor must be 16-byte aligned");
+  if (L == 0 || (!d_dx && !d_du)) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "cls_pool_train_bwd", 2.0 * HEADS * 4.0 * L * S * D, 4.0 * L * ((d_dx ? 2.0 : 1.0) * S * D + 4.0 * HEADS * D + HEADS));
+  hipLaunchKernelGGL(cp_bwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L,
+                     (int)S, d_dx, lddx, d_du, lddu);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int64_t linetr_layer_norm_backward_workspace_bytes(int64_t rows, int32_t C) {
+  return C == D && rows >= 0 && rows <= LN_MAX_ROWS ? align_up(ln_chunks(rows) * 2 * D * 4, 256) + 256 : 0;
+}
+
+extern "C" int linetr_layer_norm_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                                         const float* d_beta, float eps, int64_t rows, int32_t C, float* d_y, int64_t ldy, float* d_stats,
+                                         void* stream) {
+  if (C != D || rows < 0 || rows > LN_MAX_ROWS)
+    return fail(LINETR_E_ARG, "layer_norm_forward: bad shape rows=%lld C=%d (0 <= rows <= 2^30, C = 256)", (long long)rows, C);
+  if (!(eps > 0.f)) return fail(LINETR_E_ARG, "layer_norm_forward: eps %g (> 0)", eps);
+  if (!lin_stride_ok(lda, D) || (d_r && !lin_stride_ok(ldr, D)) || !lin_stride_ok(ldy, D))
+    return fail(LINETR_E_ARG, "layer_norm_forward: every row stride must be at least 256 and a multiple of 4 floats");
+  if (!d_a || !d_gamma || !d_beta || !d_y || !d_stats) return fail(LINETR_E_ARG, "layer_norm_forward: null pointer");
+  if (!aligned16(d_a) || !aligned16(d_r) || !aligned16(d_gamma) || !aligned16(d_beta) || !aligned16(d_y) || !aligned16(d_stats))
+    return fail(LINETR_E_ARG, "layer_norm_forward: every tensor must be 16-byte aligned");
+  if (rows == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "layer_norm_fwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2));
+  hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(256), 0, st, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows,
+                     d_y, ldy, d_stats);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                                          const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dx,
+                                          int64_t lddx, float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (C != D || rows < 0 || rows > LN_MAX_ROWS)
+    return fail(LINETR_E_ARG, "layer_norm_backward: bad shape rows=%lld C=%d (0 <= rows <= 2^30, C = 256)", (long long)rows, C);
+  if (!lin_stride_ok(lda, D) || (d_r && !lin_stride_ok(ldr, D)) || !lin_stride_ok(ldg, D) || (d_dx && !lin_stride_ok(lddx, D)))
+    return fail(LINETR_E_ARG, "layer_norm_backward: every row stride must be at least 256 and a multiple of 4 floats");
+  if (!d_a || !d_stats || !d_gamma || !d_g) return fail(LINETR_E_ARG, "layer_norm_backward: null pointer");
+  const bool sums = d_dgamma || d_dbeta;
+  if (sums && !d_ws) return fail(LINETR_E_ARG, "layer_norm_backward: the gamma and beta gradients need the workspace");
+  if (!aligned16(d_a) || !aligned16(d_r) || !aligned16(d_stats) || !aligned16(d_gamma) || !aligned16(d_g) || !aligned16(d_dx) || !aligned16(d_dgamma) ||
+      !aligned16(d_dbeta) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "layer_norm_backward: every tensor must be 16-byte aligned");
+  if (sums && ws_bytes < linetr_layer_norm_backward_workspace_bytes(rows, C))
+    return fail(LINETR_E_ARG, "layer_norm_backward: workspace too small (need %lld)", (long long)linetr_layer_norm_backward_workspace_bytes(rows, C));
+  if (!d_dx && !sums) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  const int chunks = (int)ln_chunks(rows);
+  float* partial = sums ? (float*)d_ws : nullptr;
+  if (rows > 0) {
+    ProfScope ps(h, st, "layer_norm_bwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2 + (d_dx ? D : 0)));
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, d_dx, lddx, partial);
+    LT_LAUNCH_CHECK();
+  }
+  if (sums) {      // (no rows: zeros)
+    ProfScope ps(h, st, "layer_norm_bwd_reduce", 0, 4.0 * (chunks + 1) * 2.0 * D);
+    hipLaunchKernelGGL(ln_reduce_kernel, dim3(2), dim3(256), 0, st, (const float*)partial, chunks, d_dgamma, d_dbeta);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+namespace {
+// forward (d_g null) and backward of GELU share one check and one kernel
+int gelu_call(const char* who, LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_g, int64_t ldg, bool backward, int64_t rows, int C,
+              float* d_out, int64_t ldo, void* stream) {
+  if (rows < 0 || rows > LN_MAX_ROWS || C < 4 || C > 4096 || C % 4 || (rows * (C / 4) + 255) / 256 > INT32_MAX)
+    return fail(LINETR_E_ARG, "%s: bad shape rows=%lld C=%d (0 <= rows <= 2^30, 4 <= C <= 4096, C %% 4 == 0)", who, (long long)rows, C);
+  if (!lin_stride_ok(ldz, C) || (backward && !lin_stride_ok(ldg, C)) || !lin_stride_ok(ldo, C))
+    return fail(LINETR_E_ARG, "%s: every row stride must be at least C = %d and a multiple of 4 floats", who, C);
+  if (!d_z || !d_out || (backward && !d_g)) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if (!aligned16(d_z) || !aligned16(d_g) || !aligned16(d_out)) return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  if (rows == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, backward ? "gelu_bwd" : "gelu_fwd", 0, 4.0 * rows * C * (backward ? 3.0 : 2.0));
+  hipLaunchKernelGGL(gelu_kernel, dim3((unsigned)((rows * (C / 4) + 255) / 256)), dim3(256), 0, st, d_z, ldz, backward ? d_g : nullptr, ldg, rows, C, d_out,
+                     ldo);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int linetr_gelu_forward(LinetrHandle* h, const float* d_z, int64_t ldz, int64_t rows, int32_t C, float* d_y, int64_t ldy, void* stream) {
+  return gelu_call("gelu_forward", h, d_z, ldz, nullptr, 0, false, rows, C, d_y, ldy, stream);
+}
+
+extern "C" int linetr_gelu_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_g, int64_t ldg, int64_t rows, int32_t C,
+                                    float* d_dz, int64_t lddz, void* stream) {
+  return gelu_call("gelu_backward", h, d_z, ldz, d_g, ldg, true, rows, C, d_dz, lddz, stream);
 }
 
 // =============================================================================================

@@ -300,6 +300,108 @@ class _TrainSurface:
                    ptr(dbeta), ws.data_ptr(), ws.numel())
         return self._like_input(dz, B, n) if dz is not None else None, dgamma, dbeta
 
+    # ------------------------------------------------------------------ the descriptive layer for training: CLS pooling, LayerNorm, GELU
+    def _rows_of(self, t, shape, what, strided=True):
+        """a float32 2-D device tensor of exactly `shape` as the kernels read it (strided rows pass as they are, anything else is copied)"""
+        if t.dim() != 2 or tuple(int(v) for v in t.shape) != tuple(shape):
+            raise ValueError(f"{what} must be {list(shape)}, got {tuple(t.shape)}")
+        return self._act_rows(t, int(shape[1]), what, strided=strided)[0]
+
+    def _pool_args(self, x, u):
+        if x.dim() != 3 or int(x.shape[2]) != D or not 1 <= int(x.shape[1]) <= 256:
+            raise ValueError(f"x must be [L, S, {D}] token rows with 1 <= S <= 256, got {tuple(x.shape)}")
+        L, S = int(x.shape[0]), int(x.shape[1])
+        if tuple(u.shape) != (L, 4, D):
+            raise ValueError(f"u must be [{L}, 4, {D}], got {tuple(u.shape)}")
+        return self._f32(x.detach()).view(L * S, D), self._f32(u.detach()).view(L, 4 * D), L, S
+
+    def cls_pool_forward(self, x, u):
+        """The CLS row's attention pooling of the descriptive layer in its folded form (linetr_cls_pool_train_forward): per segment l and
+        head h, p = softmax_t(u[l, h] . x[l, t]) and pooled[l, h] = sum_t p_t x[l, t].  x [L, S, 256] token rows (slot 0: the CLS token),
+        u [L, 4, 256] = Wk_h^T (q_h / 8).  Returns (pooled [L, 4, 256], lse [L, 4]).  No host wait."""
+        xr, ur, L, S = self._pool_args(x, u)
+        pooled = torch.empty((L, 4, D), dtype=torch.float32, device=self.device)
+        lse = torch.empty((L, 4), dtype=torch.float32, device=self.device)
+        if L == 0:                                   # (an empty tensor has no address to hand over)
+            return pooled, lse
+        self._call("linetr_cls_pool_train_forward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, L, S, pooled.data_ptr(), lse.data_ptr())
+        return pooled, lse
+
+    def cls_pool_backward(self, x, u, pooled, lse, grad_pooled, need=(True, True)):
+        """The pooling's backward (linetr_cls_pool_train_backward): (dx [L, S, 256], du [L, 4, 256]) for the gradient `grad_pooled`
+        arriving at pooled; x, u, pooled, lse as cls_pool_forward took and returned them.  p is recomputed from x, u and lse.  `need` =
+        which of the two to compute (the other is None).  Deterministic; no host wait."""
+        xr, ur, L, S = self._pool_args(x, u)
+        pr = self._rows_of(pooled.detach().reshape(L, 4 * D), (L, 4 * D), "pooled", strided=False)
+        gr = self._rows_of(grad_pooled.detach().reshape(L, 4 * D), (L, 4 * D), "grad_pooled", strided=False)
+        ls = self._rows_of(lse.detach(), (L, 4), "lse", strided=False)
+        dx = torch.empty((L, S, D), dtype=torch.float32, device=self.device) if need[0] else None
+        du = torch.empty((L, 4, D), dtype=torch.float32, device=self.device) if need[1] else None
+        if L == 0:
+            return dx, du
+        self._call("linetr_cls_pool_train_backward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, pr.data_ptr(), ls.data_ptr(), gr.data_ptr(), L, S,
+                   ptr(dx), D, ptr(du), 4 * D)
+        return dx, du
+
+    def _ln_args(self, who, a, residual, gamma):
+        if a.dim() != 2 or int(a.shape[1]) != D or int(gamma.numel()) != D:
+            raise ValueError(f"{who}: the native LayerNorm is over rows of {D}, got {tuple(a.shape)} and {int(gamma.numel())} weights")
+        ar = self._act_rows(a, D, "a")[0]
+        rr = self._rows_of(residual.detach(), a.shape, "residual") if residual is not None else None
+        return ar, rr, self._f32(gamma.detach().reshape(-1)), int(ar.shape[0])
+
+    def layer_norm_forward(self, a, residual, gamma, beta, eps=1e-6):
+        """y = LayerNorm(a + residual) gamma + beta over rows of 256 (linetr_layer_norm_forward); a, residual [rows, 256] (rows may be
+        strided; residual may be None), the add one float32 add.  Returns (y [rows, 256], stats [rows, 2] float32: mean | rstd, what
+        layer_norm_backward takes).  No host wait."""
+        ar, rr, gm, rows = self._ln_args("layer_norm_forward", a, residual, gamma)
+        y = torch.empty((rows, D), dtype=torch.float32, device=self.device)
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=self.device)
+        if rows == 0:
+            return y, stats
+        self._call("linetr_layer_norm_forward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, gm.data_ptr(),
+                   self._f32(beta.detach().reshape(-1)).data_ptr(), float(eps), rows, D, y.data_ptr(), D, stats.data_ptr())
+        return y, stats
+
+    def layer_norm_backward(self, a, residual, stats, gamma, grad_out, need=(True, True, True)):
+        """The layer's backward (linetr_layer_norm_backward): (dx, dgamma, dbeta) for the gradient `grad_out` arriving at y; dx [rows, 256]
+        is the gradient of a and of the residual alike.  `need` = which of the three to compute (the others are None).  Deterministic;
+        no host wait."""
+        ar, rr, gm, rows = self._ln_args("layer_norm_backward", a, residual, gamma)
+        g = self._rows_of(grad_out.detach(), (rows, D), "grad_out")
+        st = self._rows_of(stats.detach(), (rows, 2), "stats", strided=False)
+        dx = torch.empty((rows, D), dtype=torch.float32, device=self.device) if need[0] else None
+        dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=self.device) if k else None for k in need[1:3])
+        if rows == 0:
+            return dx, dgamma.zero_() if dgamma is not None else None, dbeta.zero_() if dbeta is not None else None
+        ws = self._stream_workspace("layer_norm_bwd", self._L.linetr_layer_norm_backward_workspace_bytes(rows, D))
+        self._call("linetr_layer_norm_backward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, st.data_ptr(),
+                   gm.data_ptr(), g.data_ptr(), g.stride(0), rows, D, ptr(dx), D, ptr(dgamma), ptr(dbeta), ws.data_ptr(), ws.numel())
+        return dx, dgamma, dbeta
+
+    def _gelu_rows(self, z, what):
+        if z.dim() != 2 or int(z.shape[1]) % 4 or not 4 <= int(z.shape[1]) <= 4096:
+            raise ValueError(f"{what} must be [rows, C] with C a multiple of 4 up to 4096, got {tuple(z.shape)}")
+        return self._act_rows(z, int(z.shape[1]), what)[0]
+
+    def gelu_forward(self, z) -> torch.Tensor:
+        """F.gelu(z), erf form, on rows [rows, C] (linetr_gelu_forward).  No host wait."""
+        zr = self._gelu_rows(z, "z")
+        y = torch.empty(tuple(zr.shape), dtype=torch.float32, device=self.device)
+        if zr.numel():
+            self._call("linetr_gelu_forward", zr.data_ptr(), zr.stride(0), int(zr.shape[0]), int(zr.shape[1]), y.data_ptr(), int(zr.shape[1]))
+        return y
+
+    def gelu_backward(self, z, grad_out) -> torch.Tensor:
+        """dz = grad_out (Phi(z) + z phi(z)) from the pre-activation z (linetr_gelu_backward).  No host wait."""
+        zr = self._gelu_rows(z, "z")
+        g = self._rows_of(grad_out.detach(), zr.shape, "grad_out")
+        dz = torch.empty(tuple(zr.shape), dtype=torch.float32, device=self.device)
+        if zr.numel():
+            self._call("linetr_gelu_backward", zr.data_ptr(), zr.stride(0), g.data_ptr(), g.stride(0), int(zr.shape[0]), int(zr.shape[1]),
+                       dz.data_ptr(), int(zr.shape[1]))
+        return dz
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes

@@ -1,5 +1,6 @@
-"""Differentiable native layers: torch.autograd.Functions on top of the exact-fp32 kernels of csrc/lt_linbwd.h and csrc/lt_attnbwd.h and
-the BatchNorm kernels of csrc/lt_bnbwd.h, and the signature network composed of them.
+"""Differentiable native layers: torch.autograd.Functions on top of the exact-fp32 kernels of csrc/lt_linbwd.h and csrc/lt_attnbwd.h, the
+BatchNorm kernels of csrc/lt_bnbwd.h and the pooling / LayerNorm / GELU kernels of csrc/lt_descbwd.h, and the signature network and the
+descriptive layer composed of them.
 
     pointwise_linear(x, weight, bias=None, relu=False)   y = act(x W^T + b): Conv1d(k=1) ([N, K, 1] weight, x [B, K, n]) or Linear
                                                          ([N, K] weight, x [rows, K]) on the UNFOLDED state_dict weight, with the
@@ -18,6 +19,13 @@ the BatchNorm kernels of csrc/lt_bnbwd.h, and the signature network composed of 
     AttentionalPropagation                               the reference's signature layer (:157-166): attn(x, source, source), cat, Conv1d(512,
                                                          512), BatchNorm1d(512), ReLU, Conv1d(512, 256), with its state_dict
     SelfAttentionalLayer                                 the reference's stack (:168-183): kline_desc + delta, layer after layer
+    gelu(x)                                              F.gelu in its erf form, from the saved pre-activation (Engine.gelu_forward / _backward)
+    residual_layer_norm(a, residual, ln)                 ln(a + residual) for an nn.LayerNorm(256) `ln`; the data gradient (of a and of the
+                                                         residual), dgamma and dbeta native (Engine.layer_norm_forward / _backward)
+    cls_token_pool(x, u)                                 the CLS query row's softmax-weighted mean of the S tokens of every segment and head,
+                                                         x [L, S, 256], u [L, 4, 256]; dx and du native (Engine.cls_pool_forward / _backward)
+    LineDescriptiveEncoder                               the reference's descriptive layer (:75-91) with its state_dict, in the folded form:
+                                                         only the CLS row KeylineEncoder reads is computed; every gradient native
 
 With linetr_amd.evaluations.descriptor_loss on top of a DescriptorHead on top of a SelfAttentionalLayer, `loss.backward()` fills every
 gradient of the signature network -- the eight attention parameters, the two convolutions and the BatchNorm weight and bias of every layer,
@@ -26,7 +34,10 @@ backward, is a native kernel.  What torch still does: data movement (cat, permut
 parameters into head-major order and its scatter back, copies of the running statistics into and out of their packed pair), the residual
 add kline_desc + delta, the increment of num_batches_tracked, and autograd's own sums where one tensor feeds several consumers (x feeds the
 attention's three projections, the concatenation and the residual) -- single float32 adds, as in the reference.  The tensors must live on
-a HIP device (there is no CPU path).  The descriptive layer and the two positional encoders have no native backward yet and are not here."""
+a HIP device (there is no CPU path).  The descriptive layer underneath trains the same way: in LineDescriptiveEncoder torch gathers the
+per-head slices of the key and value weights, stacks and concatenates the heads, scales q by the exact 1/8 and adds the gradients of the
+CLS rows (which feed the query, the tokens and the residual); the rest is native.  The two positional encoders have no native backward
+yet and are not here."""
 from __future__ import annotations
 
 import torch
@@ -293,3 +304,169 @@ class SelfAttentionalLayer(nn.Module):
             delta, _ = layer(kline_desc, kline_desc)
             kline_desc = kline_desc + delta
         return kline_desc
+
+
+# ---- the line descriptive layer ----------------------------------------------------------------------------------------------------
+
+class _Gelu(torch.autograd.Function):
+    """y = gelu(z), erf form.  Saved for the backward: the pre-activation z."""
+
+    @staticmethod
+    def forward(ctx, z):
+        ctx.save_for_backward(z)
+        return _engine(z.device).gelu_forward(z.reshape(-1, z.shape[-1])).view(z.shape)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        z, = ctx.saved_tensors
+        return _engine(z.device).gelu_backward(z.reshape(-1, z.shape[-1]), grad_out.reshape(-1, z.shape[-1])).view(z.shape)
+
+
+def gelu(x):
+    """F.gelu(x) in its erf form, 0.5 x (1 + erf(x / sqrt 2)), differentiable; x [..., C] with C a multiple of 4 up to 4096"""
+    if x.dim() < 1 or int(x.shape[-1]) % 4 or not 4 <= int(x.shape[-1]) <= 4096:
+        raise ValueError(f"x must be [..., C] with C a multiple of 4 up to 4096, got {tuple(x.shape)}")
+    return _Gelu.apply(x)
+
+
+class _ResidualLayerNorm(torch.autograd.Function):
+    """y = LayerNorm(a + residual).  Saved for the backward: a, the residual, the rows' float32 mean | rstd and gamma."""
+
+    @staticmethod
+    def forward(ctx, a, residual, gamma, beta, eps):
+        y, stats = _engine(a.device).layer_norm_forward(a, residual, gamma, beta, eps)
+        ctx.save_for_backward(a, residual, stats, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, residual, stats, gamma = ctx.saved_tensors
+        need_dx = ctx.needs_input_grad[0] or (residual is not None and ctx.needs_input_grad[1])
+        dx, dgamma, dbeta = _engine(a.device).layer_norm_backward(a, residual, stats, gamma, grad_out,
+                                                                  need=(need_dx, ctx.needs_input_grad[2], ctx.needs_input_grad[3]))
+        return (dx if ctx.needs_input_grad[0] else None, dx if residual is not None and ctx.needs_input_grad[1] else None, dgamma, dbeta,
+                None)
+
+
+def residual_layer_norm(a, residual, ln: nn.LayerNorm):
+    """ln(a + residual) for an nn.LayerNorm(256) `ln`, as the reference's `q += residual; q = self.layer_norm(q)`; a, residual
+    [rows, 256] (residual may be None).  Differentiable with respect to a, residual, ln.weight and ln.bias.  Refused: an `ln` without
+    affine parameters or of another width."""
+    if not isinstance(ln, nn.LayerNorm):
+        raise TypeError(f"residual_layer_norm takes an nn.LayerNorm, got {type(ln).__name__}")
+    if tuple(ln.normalized_shape) != (D,) or ln.weight is None or ln.bias is None:
+        raise ValueError(f"residual_layer_norm: the native kernel is an affine LayerNorm({D}), got normalized_shape {tuple(ln.normalized_shape)}"
+                         f"{'' if ln.weight is not None and ln.bias is not None else ' without weight and bias'}")
+    if a.dim() != 2 or int(a.shape[1]) != D or (residual is not None and residual.shape != a.shape):
+        raise ValueError(f"a and residual must be [rows, {D}], got {tuple(a.shape)} and {None if residual is None else tuple(residual.shape)}")
+    return _ResidualLayerNorm.apply(a, residual, ln.weight, ln.bias, float(ln.eps))
+
+
+class _ClsTokenPool(torch.autograd.Function):
+    """pooled[l, h] = sum_t softmax_t(u[l, h] . x[l, t]) x[l, t].  Saved for the backward: x, u, pooled and lse [L, 4]; the softmax is
+    recomputed from them."""
+
+    @staticmethod
+    def forward(ctx, x, u):
+        pooled, lse = _engine(x.device).cls_pool_forward(x, u)
+        ctx.save_for_backward(x, u, pooled, lse)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, grad_pooled):
+        x, u, pooled, lse = ctx.saved_tensors
+        return _engine(x.device).cls_pool_backward(x, u, pooled, lse, grad_pooled, need=tuple(ctx.needs_input_grad[:2]))
+
+
+def cls_token_pool(x, u):
+    """The CLS query row's attention over the S tokens of each segment, in the folded form: x [L, S, 256] token rows (slot 0: the CLS
+    token), u [L, 4, 256] with u[l, h] = Wk_h^T (q_lh / 8); returns pooled [L, 4, 256], the softmax-weighted mean of the tokens per
+    head.  Differentiable with respect to x and u."""
+    if x.dim() != 3 or int(x.shape[2]) != D or not 1 <= int(x.shape[1]) <= 256 or tuple(u.shape) != (int(x.shape[0]), HEADS, D):
+        raise ValueError(f"x must be [L, S, {D}] with 1 <= S <= 256 and u [L, {HEADS}, {D}], got {tuple(x.shape)} and {tuple(u.shape)}")
+    return _ClsTokenPool.apply(x, u)
+
+
+class _CancelledBias(torch.autograd.Function):
+    """Ties a parameter that cancels out of the forward into the graph: the output is `y` itself, and the parameter's gradient is a
+    tensor of exact zeros."""
+
+    @staticmethod
+    def forward(ctx, y, bias):
+        ctx.save_for_backward(bias)
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        bias, = ctx.saved_tensors
+        return grad_y, torch.zeros_like(bias) if ctx.needs_input_grad[1] else None
+
+
+class _Linears(nn.Module):
+    """a holder of nn.Linear / nn.LayerNorm parameters under the reference's names; never called"""
+
+
+class LineDescriptiveEncoder(nn.Module):
+    """The reference's LineDescriptiveEncoder (models/line_transformer.py:75-91) = MultiHeadAttention + FeedForward
+    (models/line_attention.py:23-94), with its state_dict names and shapes: slf_attn.w_qs / w_ks / w_vs / fc (.weight [256, 256],
+    .bias [256]), slf_attn.layer_norm, pos_ffn.w_1 ([1024, 256]), pos_ffn.w_2 ([256, 1024]), pos_ffn.layer_norm (both eps 1e-6).
+
+    KeylineEncoder reads only the CLS row enc_output[:, :, 0, :] of the layer's output (:128), so only the CLS query row is computed,
+    in the folded form: q = w_qs(x_0);  u_h = Wk_h^T (q_h / 8);  pooled = cls_token_pool(x, u);  o_h = Wv_h pooled_h +
+    bv_h (the weights sum to 1);  y = LN1(fc(o) + x_0);  out = LN2(w_2(gelu(w_1(y))) + y).  The output and every gradient -- of the
+    parameters and of desc, slot 0 included -- are those of the reference's row 0; token rows 1 .. S-1 of its output are not made.
+    The key bias adds one constant per (segment, head) to the scores, which the softmax cancels: slf_attn.w_ks.bias.grad is a tensor of
+    exact zeros, the exact value of what float32 autograd through the reference leaves as noise of about 1e-6."""
+
+    def __init__(self, d_feature: int = D, n_heads: int = HEADS, n_att_layers: int = 1, d_inner: int = 1024, dropout: float = 0.0):
+        super().__init__()
+        if d_feature != D or n_heads != HEADS or d_inner % 64 or not 64 <= d_inner <= 1024:
+            raise ValueError(f"the native descriptive layer is {D} wide with {HEADS} heads and d_inner a multiple of 64 up to 1024, got "
+                             f"{d_feature}, {n_heads}, {d_inner}")
+        self.dropout = float(dropout)
+        self.slf_attn, self.pos_ffn = _Linears(), _Linears()
+        for name in ("w_qs", "w_ks", "w_vs", "fc"):
+            setattr(self.slf_attn, name, nn.Linear(D, D, bias=True))
+        self.slf_attn.layer_norm = nn.LayerNorm(D, eps=1e-6)
+        self.pos_ffn.w_1 = nn.Linear(D, d_inner)
+        self.pos_ffn.w_2 = nn.Linear(d_inner, D)
+        self.pos_ffn.layer_norm = nn.LayerNorm(D, eps=1e-6)
+
+    @classmethod
+    def from_line_transformer(cls, model, layer: int = -1) -> "LineDescriptiveEncoder":
+        """descriptive layer `layer` (default: the last, the only one whose output KeylineEncoder reads) of a LineTransformer (this
+        package's or the reference's), or of its state_dict: a copy"""
+        sd = model if isinstance(model, dict) else model.state_dict()
+        n_layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("klenc.desc_layers."))
+        sub = _sub_state_dict(sd, f"klenc.desc_layers.{int(layer) % n_layers}.")
+        own = cls(d_inner=int(sub["pos_ffn.w_1.weight"].shape[0]))
+        own.load_state_dict(sub, strict=True)
+        return own.to(_device_of(sub))
+
+    def forward(self, desc, slf_attn_mask=None):
+        """desc [B, L, S, 256] (slot 0 of every segment: the CLS token) -> (cls_out [B, L, 256], None).  cls_out is row 0 of the
+        reference's output, enc_output[:, :, 0, :], the only row KeylineEncoder reads; the reference's second result, the S x S attention
+        map, is never formed.  `slf_attn_mask` is accepted and ignored: the reference's mask acts on QUERY rows, and the CLS row is never
+        masked, so row 0 attends to all S keys whatever the mask holds."""
+        if self.training and self.dropout != 0.0:
+            raise RuntimeError(
+                "linetr_amd.train_ops.LineDescriptiveEncoder in train mode: the training-time forward of this build has no dropout (the "
+                "reference applies nn.Dropout(0.1) in its attention blocks, models/line_attention.py:11,39,84).  Set `dropout = 0.0` to "
+                "run the deterministic train-mode forward, or call .eval()")
+        if desc.dim() != 4 or int(desc.shape[3]) != D or not 1 <= int(desc.shape[2]) <= 256:
+            raise ValueError(f"desc must be [B, L, S, {D}] with 1 <= S <= 256, got {tuple(desc.shape)}")
+        B, L, S = (int(v) for v in desc.shape[:3])
+        att, ffn = self.slf_attn, self.pos_ffn
+        x = desc.reshape(B * L, S, D)
+        x0 = x[:, 0].contiguous()                                                            # the CLS rows: the query and the residual
+        q = pointwise_linear(x0, att.w_qs.weight, att.w_qs.bias) * 0.125                     # (a power of two: exact)
+        head = lambda h: slice(h * DH, (h + 1) * DH)
+        u = torch.stack([pointwise_linear(q[:, head(h)], att.w_ks.weight[head(h)].t()) for h in range(HEADS)], dim=1)
+        pooled = cls_token_pool(x, u)
+        o = torch.cat([pointwise_linear(pooled[:, h], att.w_vs.weight[head(h)], att.w_vs.bias[head(h)]) for h in range(HEADS)], dim=1)
+        y = residual_layer_norm(pointwise_linear(o, att.fc.weight, att.fc.bias), x0, att.layer_norm)
+        hidden = gelu(pointwise_linear(y, ffn.w_1.weight, ffn.w_1.bias))
+        out = residual_layer_norm(pointwise_linear(hidden, ffn.w_2.weight, ffn.w_2.bias), y, ffn.layer_norm)
+        if att.w_ks.bias.requires_grad and torch.is_grad_enabled():
+            out = _CancelledBias.apply(out, att.w_ks.bias)
+        return out.view(B, L, D), None
