@@ -30,6 +30,9 @@
  *                symbols, nothing existing changes, the version stays.
  *                + linetr_cls_pool_train_forward / _backward, linetr_layer_norm_forward / _backward / _backward_workspace_bytes,
  *                linetr_gelu_forward / _backward (the descriptive layer's training kernels): added symbols, the version stays.
+ *                + linetr_input_layer_forward / _backward / _backward_workspace_bytes / _chunk_rows, linetr_token_assemble_forward /
+ *                _backward / _backward_workspace_bytes (the positional encoders' first layer and the token assembly): added symbols,
+ *                the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -581,6 +584,49 @@ int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, c
 int linetr_gelu_forward(LinetrHandle* h, const float* d_z, int64_t ldz, int64_t rows, int32_t C, float* d_y, int64_t ldy, void* stream);
 int linetr_gelu_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dz,
                          int64_t lddz, void* stream);
+
+/* ---- the positional encoders and the token assembly for training (section 8(f) "next" row 4: the sixth link) ---------- */
+
+/* The first layer of LinePositionalEncoder / WordPositionalEncoder (models/line_transformer.py:40-73), Conv1d(Kin -> N, k = 1) with
+ * Kin = 5 / 3 and N = 32, which is no GEMM (every later layer is the linear layer above), and its backward:
+ *   z [rows][N of ldz] = x [rows][Kin of ldx] W^T + b      W [N][Kin], d_b [N] or NULL (no bias); per channel one fmaf chain in
+ *     ascending k that starts at the bias
+ *   dW [N][Kin] = g^T x      db [N] = sum_r g      g [rows][N of ldg]: the gradient arriving at z (no activation, so no mask)
+ *   dx is not computed: the coordinates, scores and angles the encoders read never require a gradient.
+ * 0 <= rows <= 2^30, 1 <= Kin <= 8, N % 4 == 0, 4 <= N <= 64.  x is the narrow tensor: ldx >= Kin floats and any (4-byte) alignment, as W,
+ * b, dW and db; z and g are the wide ones: 16-byte aligned, ldz / ldg at least N and multiples of 4 floats.  dW / db: the rows are cut
+ * into chunks of linetr_input_layer_chunk_rows() rows (a compile-time constant), each chunk is summed in float32 in a fixed order and the
+ * chunks are added in ascending order in float64 through the workspace.  d_dW, d_db: each may be NULL and is then not computed (both
+ * NULL: nothing is launched and the workspace is not needed).  Forward one launch, backward two.  Deterministic: no atomics.  Rows
+ * behind `rows` and columns behind the widths are neither read nor written.  Asynchronous on `stream`; nothing inside allocates or
+ * waits; `h` may be NULL.  rows = 0: no row is touched (dW / db, where asked for, are zeros).  LINETR_E_ARG, nothing launched: a shape
+ * outside the above, a bad row stride, a misaligned pointer, a NULL required pointer (forward: d_x, d_W, d_z; backward: d_x, d_g, and
+ * the workspace when a gradient is asked for), a workspace smaller than linetr_input_layer_backward_workspace_bytes says (0 for a
+ * shape that is refused). */
+int32_t linetr_input_layer_chunk_rows(void);
+int64_t linetr_input_layer_backward_workspace_bytes(int64_t rows, int32_t N, int32_t Kin);
+int linetr_input_layer_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_b, int64_t rows, int32_t N,
+                               int32_t Kin, float* d_z, int64_t ldz, void* stream);
+int linetr_input_layer_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_g, int64_t ldg, int64_t rows, int32_t N,
+                                int32_t Kin, float* d_dW, float* d_db, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The token rows the descriptive layer reads (KeylineEncoder, models/line_transformer.py:116-121): per segment (sub-line) l of S tokens
+ *   x [L][S + 1][256]      x[l][0] = cls      x[l][1 + t] = desc[l][t] + pos[l][t]  (one float32 add)
+ *   d_desc, d_pos [L S][256] contiguous rows, d_cls [256]
+ * and its backward from d_dx [L][S + 1][256], in one pass over it:
+ *   d_dtok [L S][256] = dx[:, 1:] as contiguous rows: the gradient of desc and of pos alike      d_dcls [256] = sum_l dx[l][0]
+ *     (float32 partial sums per block of segments in segment order, the blocks added in ascending order in float64 through the workspace)
+ *   d_dtok, d_dcls: each may be NULL and is then not computed
+ * 1 <= S <= 255 (with the CLS slot: the 256 rows the pooling takes), 0 <= L <= 2^24; 16-byte aligned pointers.  Forward one launch,
+ * backward two.  Deterministic.  Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  L = 0: no row is
+ * touched (dcls, where asked for, is zeros).  LINETR_E_ARG, nothing launched: S or L outside the above, a pointer that is not 16-byte
+ * aligned, a NULL required pointer (forward: all four; backward: d_dx, and the workspace when d_dcls is asked for), a workspace smaller
+ * than linetr_token_assemble_backward_workspace_bytes says (0 for an L that is refused). */
+int64_t linetr_token_assemble_backward_workspace_bytes(int64_t L);
+int linetr_token_assemble_forward(LinetrHandle* h, const float* d_desc, const float* d_pos, const float* d_cls, int64_t L, int32_t S,
+                                  float* d_x, void* stream);
+int linetr_token_assemble_backward(LinetrHandle* h, const float* d_dx, int64_t L, int32_t S, float* d_dtok, float* d_dcls,
+                                   void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- ground-truth line assignment of a homography pair (the producer of d_assign / d_lmatches above) ---------- */
 

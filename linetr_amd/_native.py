@@ -126,6 +126,13 @@ ABI = {
     "linetr_layer_norm_backward": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, i64, vp]),
     "linetr_gelu_forward": (i32, [vp, vp, i64, i64, i32, vp, i64, vp]),
     "linetr_gelu_backward": (i32, [vp, vp, i64, vp, i64, i64, i32, vp, i64, vp]),
+    "linetr_input_layer_chunk_rows": (i32, []),
+    "linetr_input_layer_backward_workspace_bytes": (i64, [i64, i32, i32]),
+    "linetr_input_layer_forward": (i32, [vp, vp, i64, vp, vp, i64, i32, i32, vp, i64, vp]),
+    "linetr_input_layer_backward": (i32, [vp, vp, i64, vp, i64, i64, i32, i32, vp, vp, vp, i64, vp]),
+    "linetr_token_assemble_backward_workspace_bytes": (i64, [i64]),
+    "linetr_token_assemble_forward": (i32, [vp, vp, vp, vp, i64, i32, vp, vp]),
+    "linetr_token_assemble_backward": (i32, [vp, vp, i64, i32, vp, vp, vp, i64, vp]),
     "linetr_gt_assign_workspace_bytes": (i64, [i32, i32, i32]),
     "linetr_gt_assign": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_superpoint_heads": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),

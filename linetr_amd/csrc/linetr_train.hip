@@ -1,8 +1,8 @@
 // liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h): the validation step (lt_valstep.h),
 // the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
 // attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h), the
-// descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h) and the ground-truth line assignment in
-// front of them (lt_gtassign.h).
+// descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h), the positional encoders' input layer and
+// the token assembly with their backwards (lt_posbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
 #include <algorithm>
 
 #include "lt_handle.h"
@@ -12,6 +12,7 @@
 #include "lt_attnbwd.h"
 #include "lt_bnbwd.h"
 #include "lt_descbwd.h"
+#include "lt_posbwd.h"
 #include "lt_gtassign.h"
 
 using namespace lt;
@@ -667,6 +668,132 @@ extern "C" int linetr_gelu_forward(LinetrHandle* h, const float* d_z, int64_t ld
 extern "C" int linetr_gelu_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_g, int64_t ldg, int64_t rows, int32_t C,
                                     float* d_dz, int64_t lddz, void* stream) {
   return gelu_call("gelu_backward", h, d_z, ldz, d_g, ldg, true, rows, C, d_dz, lddz, stream);
+}
+
+// =============================================================================================
+// the positional encoders' input layer and the token assembly, each forward and backward (lt_posbwd.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t IL_MAX_ROWS = (int64_t)1 << 30;
+constexpr int64_t TA_MAX_L = (int64_t)1 << 24;      // L (S + 1) <= 2^32 rows are indexed in 64 bits; the grid of L (S + 1) / 4 blocks stays below 2^31
+bool il_dims_ok(int64_t rows, int N, int Kin) {
+  return rows >= 0 && rows <= IL_MAX_ROWS && Kin >= 1 && Kin <= IL_MAX_K && N >= 4 && N <= IL_MAX_N && N % 4 == 0;
+}
+int64_t il_chunks(int64_t rows) { return (rows + IL_CHUNK - 1) / IL_CHUNK; }
+bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+bool ta_dims_ok(int64_t L, int S) { return L >= 0 && L <= TA_MAX_L && S >= 1 && S <= TA_MAX_S; }
+int64_t ta_blocks(int64_t L) { return (L + TA_SEGS - 1) / TA_SEGS; }
+}  // namespace
+
+extern "C" int32_t linetr_input_layer_chunk_rows(void) { return IL_CHUNK; }
+
+extern "C" int64_t linetr_input_layer_backward_workspace_bytes(int64_t rows, int32_t N, int32_t Kin) {
+  return il_dims_ok(rows, N, Kin) ? align_up(il_chunks(rows) * (Kin + 1) * N * 4, 256) + 256 : 0;
+}
+
+extern "C" int linetr_input_layer_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_W, const float* d_b, int64_t rows,
+                                          int32_t N, int32_t Kin, float* d_z, int64_t ldz, void* stream) {
+  // every refusal comes before the first launch
+  if (!il_dims_ok(rows, N, Kin))
+    return fail(LINETR_E_ARG, "input_layer_forward: bad shape rows=%lld N=%d Kin=%d (0 <= rows <= 2^30, 1 <= Kin <= 8, N %% 4 == 0, 4 <= N <= 64)",
+                (long long)rows, N, Kin);
+  if (ldx < Kin || !lin_stride_ok(ldz, N))
+    return fail(LINETR_E_ARG, "input_layer_forward: row strides %lld / %lld (x: at least Kin = %d floats; z: at least N = %d, a multiple of 4 floats)",
+                (long long)ldx, (long long)ldz, Kin, N);
+  if (!d_x || !d_W || !d_z) return fail(LINETR_E_ARG, "input_layer_forward: null pointer");
+  if (!aligned4(d_x) || !aligned4(d_W) || !aligned4(d_b) || !aligned16(d_z))
+    return fail(LINETR_E_ARG, "input_layer_forward: z must be 16-byte aligned (x, W and b: 4-byte aligned)");
+  if (rows == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "input_layer_fwd", 2.0 * rows * N * Kin, 4.0 * rows * ((double)N + Kin));
+  hipLaunchKernelGGL(il_fwd_kernel, dim3((unsigned)((rows * (N / 4) + 255) / 256)), dim3(256), 0, st, d_x, ldx, d_W, d_b, rows, (int)N, (int)Kin, d_z,
+                     ldz);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_input_layer_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_g, int64_t ldg, int64_t rows, int32_t N,
+                                           int32_t Kin, float* d_dW, float* d_db, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!il_dims_ok(rows, N, Kin))
+    return fail(LINETR_E_ARG, "input_layer_backward: bad shape rows=%lld N=%d Kin=%d (0 <= rows <= 2^30, 1 <= Kin <= 8, N %% 4 == 0, 4 <= N <= 64)",
+                (long long)rows, N, Kin);
+  if (ldx < Kin || !lin_stride_ok(ldg, N))
+    return fail(LINETR_E_ARG, "input_layer_backward: row strides %lld / %lld (x: at least Kin = %d floats; g: at least N = %d, a multiple of 4 floats)",
+                (long long)ldx, (long long)ldg, Kin, N);
+  if (!d_x || !d_g) return fail(LINETR_E_ARG, "input_layer_backward: null pointer");
+  if ((d_dW || d_db) && !d_ws) return fail(LINETR_E_ARG, "input_layer_backward: the weight and bias gradients need the workspace");
+  if (!aligned4(d_x) || !aligned16(d_g) || !aligned4(d_dW) || !aligned4(d_db) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "input_layer_backward: g and the workspace must be 16-byte aligned (x, dW and db: 4-byte aligned)");
+  if ((d_dW || d_db) && ws_bytes < linetr_input_layer_backward_workspace_bytes(rows, N, Kin))
+    return fail(LINETR_E_ARG, "input_layer_backward: workspace too small (need %lld)", (long long)linetr_input_layer_backward_workspace_bytes(rows, N, Kin));
+  if (!d_dW && !d_db) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  const int chunks = (int)il_chunks(rows);
+  float* partial = (float*)d_ws;
+  if (rows > 0) {
+    ProfScope ps(h, st, "input_layer_bwd_partial", 2.0 * rows * N * Kin, 4.0 * (rows * ((double)N + Kin) + (double)chunks * (Kin + 1) * N));
+    hipLaunchKernelGGL(il_bwd_partial_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_x, ldx, d_g, ldg, rows, (int)N, (int)Kin, partial);
+    LT_LAUNCH_CHECK();
+  }
+  {      // (no rows: zeros)
+    ProfScope ps(h, st, "input_layer_bwd_reduce", 0, 4.0 * (chunks + 1) * (double)(Kin + 1) * N);
+    hipLaunchKernelGGL(il_bwd_reduce_kernel, dim3(cdiv((Kin + 1) * N, 64)), dim3(1024), 0, st, (const float*)partial, chunks, (int)N, (int)Kin, d_dW,
+                       d_db);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+extern "C" int64_t linetr_token_assemble_backward_workspace_bytes(int64_t L) {
+  return L >= 0 && L <= TA_MAX_L ? align_up(ta_blocks(L) * D * 4, 256) + 256 : 0;
+}
+
+extern "C" int linetr_token_assemble_forward(LinetrHandle* h, const float* d_desc, const float* d_pos, const float* d_cls, int64_t L, int32_t S,
+                                             float* d_x, void* stream) {
+  // every refusal comes before the first launch
+  if (!ta_dims_ok(L, S))
+    return fail(LINETR_E_ARG, "token_assemble_forward: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", (long long)L, S, TA_MAX_S);
+  if (!d_desc || !d_pos || !d_cls || !d_x) return fail(LINETR_E_ARG, "token_assemble_forward: null pointer");
+  if (!aligned16(d_desc) || !aligned16(d_pos) || !aligned16(d_cls) || !aligned16(d_x))
+    return fail(LINETR_E_ARG, "token_assemble_forward: every tensor must be 16-byte aligned");
+  if (L == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "token_assemble_fwd", 0, 4.0 * L * D * (3.0 * S + 1));
+  hipLaunchKernelGGL(ta_fwd_kernel, dim3((unsigned)((L * (S + 1) + 3) / 4)), dim3(256), 0, st, d_desc, d_pos, d_cls, L, (int)S, d_x);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_token_assemble_backward(LinetrHandle* h, const float* d_dx, int64_t L, int32_t S, float* d_dtok, float* d_dcls, void* d_ws,
+                                              int64_t ws_bytes, void* stream) {
+  if (!ta_dims_ok(L, S))
+    return fail(LINETR_E_ARG, "token_assemble_backward: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", (long long)L, S, TA_MAX_S);
+  if (!d_dx) return fail(LINETR_E_ARG, "token_assemble_backward: null pointer");
+  if (d_dcls && !d_ws) return fail(LINETR_E_ARG, "token_assemble_backward: the cls gradient needs the workspace");
+  if (!aligned16(d_dx) || !aligned16(d_dtok) || !aligned16(d_dcls) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "token_assemble_backward: every tensor must be 16-byte aligned");
+  if (d_dcls && ws_bytes < linetr_token_assemble_backward_workspace_bytes(L))
+    return fail(LINETR_E_ARG, "token_assemble_backward: workspace too small (need %lld)", (long long)linetr_token_assemble_backward_workspace_bytes(L));
+  if (!d_dtok && !d_dcls) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  const int blocks = (int)ta_blocks(L);
+  float* partial = d_dcls ? (float*)d_ws : nullptr;
+  if (L > 0) {
+    ProfScope ps(h, st, "token_assemble_bwd", 0, 4.0 * L * D * ((d_dtok ? 2.0 * S : 0.0) + (d_dcls ? 1.0 : 0.0)));
+    hipLaunchKernelGGL(ta_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_dx, L, (int)S, d_dtok, partial);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_dcls) {      // (no segments: zeros)
+    ProfScope ps(h, st, "token_assemble_bwd_reduce", 0, 4.0 * (blocks + 1) * (double)D);
+    hipLaunchKernelGGL(ta_reduce_kernel, dim3(D / 64), dim3(1024), 0, st, (const float*)partial, blocks, d_dcls);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
 }
 
 // =============================================================================================

@@ -402,6 +402,90 @@ class _TrainSurface:
                        dz.data_ptr(), int(zr.shape[1]))
         return dz
 
+    # ------------------------------------------------------------------ the positional encoders' input layer and the token assembly
+    def _narrow_rows(self, x, Kin, what):
+        """the encoders' input [rows, Kin] as the input-layer kernels read it: float32 on the device, unit column stride, any row
+        stride and alignment (anything else is copied)"""
+        x = x.detach()
+        if x.dim() != 2 or int(x.shape[1]) != Kin:
+            raise ValueError(f"{what} must be [rows, {Kin}], got {tuple(x.shape)}")
+        ok = x.device == self.device and x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) >= Kin
+        return x if ok else self._f32(x)
+
+    @staticmethod
+    def _input_layer_shape(weight):
+        W = as_rows_weight(weight.detach())
+        N, Kin = int(W.shape[0]), int(W.shape[1])
+        if not 1 <= Kin <= 8 or N % 4 or not 4 <= N <= 64:
+            raise ValueError(f"the native input layer takes 1 <= Kin <= 8 inputs and N % 4 == 0, 4 <= N <= 64 outputs, got a weight {tuple(weight.shape)}")
+        return W, N, Kin
+
+    def input_layer_forward(self, x, weight, bias=None) -> torch.Tensor:
+        """The first layer of a positional encoder, Conv1d(Kin -> N, k = 1) with 1 <= Kin <= 8 and N % 4 == 0, 4 <= N <= 64, which is no
+        GEMM (linetr_input_layer_forward): z = x W^T + b.  x [rows, Kin] (rows may be strided, any alignment); weight [N, Kin] or
+        [N, Kin, 1]; returns z [rows, N].  No host wait."""
+        W, N, Kin = self._input_layer_shape(weight)
+        W = self._f32(W)
+        xr = self._narrow_rows(x, Kin, "x")
+        b = self._f32(bias.detach().reshape(-1)) if bias is not None else None
+        if b is not None and b.numel() != N:
+            raise ValueError(f"bias must hold {N} values, got {tuple(bias.shape)}")
+        rows = int(xr.shape[0])
+        z = torch.empty((rows, N), dtype=torch.float32, device=self.device)
+        if rows:
+            self._call("linetr_input_layer_forward", xr.data_ptr(), xr.stride(0), W.data_ptr(), ptr(b), rows, N, Kin, z.data_ptr(), N)
+        return z
+
+    def input_layer_backward(self, x, weight, grad_out, need=(True, True)):
+        """The layer's backward (linetr_input_layer_backward): (dW in the weight's shape, db [N]) for the gradient `grad_out` [rows, N]
+        arriving at z; there is no dx (the encoders' inputs never require a gradient).  `need` = which of the two to compute (the other
+        is None).  Deterministic; no host wait."""
+        _, N, Kin = self._input_layer_shape(weight)
+        xr = self._narrow_rows(x, Kin, "x")
+        rows = int(xr.shape[0])
+        g = self._rows_of(grad_out.detach(), (rows, N), "grad_out")
+        dW = torch.empty((N, Kin), dtype=torch.float32, device=self.device) if need[0] else None
+        db = torch.empty((N,), dtype=torch.float32, device=self.device) if need[1] else None
+        if rows == 0:
+            return dW.zero_().view(weight.shape) if dW is not None else None, db.zero_() if db is not None else None
+        ws = self._stream_workspace("input_layer_bwd", self._L.linetr_input_layer_backward_workspace_bytes(rows, N, Kin))
+        self._call("linetr_input_layer_backward", xr.data_ptr(), xr.stride(0), g.data_ptr(), g.stride(0), rows, N, Kin, ptr(dW), ptr(db),
+                   ws.data_ptr(), ws.numel())
+        return dW.view(weight.shape) if dW is not None else None, db
+
+    def _token_args(self, who, desc, pos):
+        if desc.dim() != 3 or int(desc.shape[2]) != D or not 1 <= int(desc.shape[1]) <= 255 or pos.shape != desc.shape:
+            raise ValueError(f"{who}: desc and pos must share the shape [L, S, {D}] with 1 <= S <= 255, got {tuple(desc.shape)} and {tuple(pos.shape)}")
+        return self._f32(desc.detach()), self._f32(pos.detach()), int(desc.shape[0]), int(desc.shape[1])
+
+    def assemble_tokens_forward(self, desc, pos, cls_token) -> torch.Tensor:
+        """The token rows of the descriptive layer (linetr_token_assemble_forward): x [L, S + 1, 256] with x[:, 0] = cls_token and
+        x[:, 1:] = desc + pos (one float32 add).  desc, pos [L, S, 256], 1 <= S <= 255; cls_token: 256 values.  No host wait."""
+        d, p, L, S = self._token_args("assemble_tokens_forward", desc, pos)
+        cls = self._f32(cls_token.detach().reshape(-1))
+        if cls.numel() != D:
+            raise ValueError(f"cls_token must hold {D} values, got {tuple(cls_token.shape)}")
+        x = torch.empty((L, S + 1, D), dtype=torch.float32, device=self.device)
+        if L:                                        # (an empty tensor has no address to hand over)
+            self._call("linetr_token_assemble_forward", d.data_ptr(), p.data_ptr(), cls.data_ptr(), L, S, x.data_ptr())
+        return x
+
+    def assemble_tokens_backward(self, grad_x, need=(True, True)):
+        """The assembly's backward (linetr_token_assemble_backward), one pass over grad_x [L, S + 1, 256]: (dtok [L, S, 256] = grad_x[:, 1:]
+        as contiguous rows -- the gradient of desc and of pos alike --, dcls [256] = the sum of grad_x[:, 0]).  `need` = which of the two
+        to compute (the other is None).  Deterministic; no host wait."""
+        if grad_x.dim() != 3 or int(grad_x.shape[2]) != D or not 2 <= int(grad_x.shape[1]) <= 256:
+            raise ValueError(f"grad_x must be [L, S + 1, {D}] with 1 <= S <= 255, got {tuple(grad_x.shape)}")
+        g = self._f32(grad_x.detach())
+        L, S = int(g.shape[0]), int(g.shape[1]) - 1
+        dtok = torch.empty((L, S, D), dtype=torch.float32, device=self.device) if need[0] else None
+        dcls = torch.empty((D,), dtype=torch.float32, device=self.device) if need[1] else None
+        if L == 0:
+            return dtok, dcls.zero_() if dcls is not None else None
+        ws = self._stream_workspace("token_assemble_bwd", self._L.linetr_token_assemble_backward_workspace_bytes(L))
+        self._call("linetr_token_assemble_backward", g.data_ptr(), L, S, ptr(dtok), ptr(dcls), ws.data_ptr(), ws.numel())
+        return dtok, dcls
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes

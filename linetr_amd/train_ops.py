@@ -1,6 +1,7 @@
 """Differentiable native layers: torch.autograd.Functions on top of the exact-fp32 kernels of csrc/lt_linbwd.h and csrc/lt_attnbwd.h, the
-BatchNorm kernels of csrc/lt_bnbwd.h and the pooling / LayerNorm / GELU kernels of csrc/lt_descbwd.h, and the signature network and the
-descriptive layer composed of them.
+BatchNorm kernels of csrc/lt_bnbwd.h, the pooling / LayerNorm / GELU kernels of csrc/lt_descbwd.h and the input-layer / token-assembly
+kernels of csrc/lt_posbwd.h, and the signature network, the descriptive layer, the positional encoders and the whole network composed
+of them.
 
     pointwise_linear(x, weight, bias=None, relu=False)   y = act(x W^T + b): Conv1d(k=1) ([N, K, 1] weight, x [B, K, n]) or Linear
                                                          ([N, K] weight, x [rows, K]) on the UNFOLDED state_dict weight, with the
@@ -36,8 +37,23 @@ add kline_desc + delta, the increment of num_batches_tracked, and autograd's own
 attention's three projections, the concatenation and the residual) -- single float32 adds, as in the reference.  The tensors must live on
 a HIP device (there is no CPU path).  The descriptive layer underneath trains the same way: in LineDescriptiveEncoder torch gathers the
 per-head slices of the key and value weights, stacks and concatenates the heads, scales q by the exact 1/8 and adds the gradients of the
-CLS rows (which feed the query, the tokens and the residual); the rest is native.  The two positional encoders have no native backward
-yet and are not here."""
+CLS rows (which feed the query, the tokens and the residual); the rest is native.
+
+    input_linear(x, weight, bias)                        z = x W^T + b for the narrow first layer of a positional encoder (1 <= Kin <= 8 inputs,
+                                                         N % 4 == 0, 4 <= N <= 64 outputs): dW and db native, no gradient for x
+                                                         (Engine.input_layer_forward / _backward)
+    assemble_tokens(desc, pos, cls_token)                the token rows of the descriptive layer, x[:, 0] = cls_token, x[:, 1:] = desc + pos; the
+                                                         gradient of desc and pos (one tensor) and of cls_token native
+                                                         (Engine.assemble_tokens_forward / _backward)
+    LinePositionalEncoder, WordPositionalEncoder         the reference's encoders (:40-73) with their state_dict: input_linear, then
+                                                         batch_norm_relu / pointwise_linear per layer, on [rows, C] rows
+    KeylineEncoder                                       the reference's module (:93-130): both encoders, assemble_tokens, the last descriptive layer
+    TrainableLineTransformer                             the reference's LineTransformer (:185-249) under its full key set, on its input dict:
+                                                         klenc, selfattn, final_proj + normalize; `loss.backward()` fills all 153 gradients
+
+With these the training surface is complete: every layer of the model the reference's train.py trains has a native backward.  In the
+encoders and their glue torch makes the key-line normalisation, the mid-point, the concatenation of the 3 / 5 input columns, the reshapes
+(no gradient flows there) and the final add klines_pos + cls_out^T."""
 from __future__ import annotations
 
 import torch
@@ -470,3 +486,247 @@ class LineDescriptiveEncoder(nn.Module):
         if att.w_ks.bias.requires_grad and torch.is_grad_enabled():
             out = _CancelledBias.apply(out, att.w_ks.bias)
         return out.view(B, L, D), None
+
+
+# ---- the positional encoders, KeylineEncoder and the whole network ------------------------------------------------------------------
+
+class _InputLinear(torch.autograd.Function):
+    """z = x W^T + b for the narrow first layer of an encoder.  Saved for the backward: x and the weight (for its shape)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("linetr_amd.train_ops.input_linear has no gradient with respect to x: the coordinates, scores and angles the "
+                               "positional encoders read are inputs of the network, not functions of a parameter (detach them)")
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight)
+        return _engine(x.device).input_layer_forward(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        dW, db = _engine(x.device).input_layer_backward(x, weight, grad_out, need=(ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]))
+        return None, dW, db
+
+
+def input_linear(x, weight, bias=None):
+    """z = x W^T + b for x [rows, Kin] with 1 <= Kin <= 8 and a weight [N, Kin] or [N, Kin, 1] with N % 4 == 0, 4 <= N <= 64: the first
+    layer of a positional encoder, too narrow for the GEMM of pointwise_linear.  Differentiable with respect to weight and bias; an x
+    that requires a gradient raises."""
+    check_pointwise_shapes(x, weight, bias)
+    if x.dim() != 2:
+        raise ValueError(f"x must be [rows, Kin], got {tuple(x.shape)}")
+    return _InputLinear.apply(x, weight, bias)
+
+
+class _AssembleTokens(torch.autograd.Function):
+    """x[:, 0] = cls, x[:, 1:] = desc + pos.  Nothing is saved but the shape of the cls token."""
+
+    @staticmethod
+    def forward(ctx, desc, pos, cls_token):
+        ctx.cls_shape = tuple(cls_token.shape)
+        return _engine(desc.device).assemble_tokens_forward(desc, pos, cls_token)
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        need = ctx.needs_input_grad
+        dtok, dcls = _engine(grad_x.device).assemble_tokens_backward(grad_x, need=(need[0] or need[1], need[2]))
+        return dtok if need[0] else None, dtok if need[1] else None, dcls.view(ctx.cls_shape) if dcls is not None else None
+
+
+def assemble_tokens(desc, pos, cls_token):
+    """The token rows the descriptive layer reads (models/line_transformer.py:116-121 of the reference): desc, pos [L, S, 256] with
+    1 <= S <= 255 and cls_token (256 values, any shape) -> x [L, S + 1, 256], x[:, 0] = cls_token and x[:, 1:] = desc + pos.
+    Differentiable with respect to all three (the gradient of desc and of pos is one tensor)."""
+    if desc.dim() != 3 or int(desc.shape[2]) != D or not 1 <= int(desc.shape[1]) <= 255 or pos.shape != desc.shape or cls_token.numel() != D:
+        raise ValueError(f"desc and pos must share the shape [L, S, {D}] with 1 <= S <= 255 and cls_token hold {D} values, got "
+                         f"{tuple(desc.shape)}, {tuple(pos.shape)} and {tuple(cls_token.shape)}")
+    return _AssembleTokens.apply(desc, pos, cls_token)
+
+
+def _mlp_holder(channels):
+    """the reference's MLP(channels) (models/line_transformer.py:9-20): Conv1d(k=1) [-> BatchNorm1d -> ReLU] per layer, none behind the last"""
+    layers = []
+    for i in range(1, len(channels)):
+        layers.append(nn.Conv1d(channels[i - 1], channels[i], kernel_size=1, bias=True))
+        if i < len(channels) - 1:
+            layers += [nn.BatchNorm1d(channels[i]), nn.ReLU()]
+    return nn.Sequential(*layers)
+
+
+class _PositionalEncoder(nn.Module):
+    """What the two encoders share: `encoder`, the reference's nn.Sequential, holds the parameters and the BatchNorm buffers under the
+    reference's names and is never called; rows [rows, n_in] go through input_linear, batch_norm_relu and then pointwise_linear /
+    batch_norm_relu per further layer, all on [rows, C] rows."""
+    N_IN = 0
+
+    def __init__(self, feature_dim: int, layers):
+        super().__init__()
+        widths = [int(v) for v in layers] + [int(feature_dim)]
+        ok = len(widths) >= 2 and widths[0] % 4 == 0 and 4 <= widths[0] <= 64
+        ok = ok and all(n % 64 == 0 and k % 32 == 0 and n <= 1024 for k, n in zip(widths[:-1], widths[1:]))
+        if not ok:
+            raise ValueError(f"the native encoder takes a first width that is a multiple of 4 in 4 .. 64 and then widths that are multiples of "
+                             f"64 up to 1024 (each one's input a multiple of 32), got layers {list(layers)} and feature_dim {feature_dim}")
+        self.feature_dim = int(feature_dim)
+        self.encoder = _mlp_holder([self.N_IN] + widths)
+        nn.init.constant_(self.encoder[-1].bias, 0.0)
+
+    @classmethod
+    def _from(cls, model, prefix):
+        sub = _sub_state_dict(model, prefix)
+        convs = sorted((int(k.split(".")[1]), int(v.shape[0])) for k, v in sub.items() if k.endswith(".weight") and v.dim() == 3)
+        own = cls(convs[-1][1], [n for _, n in convs[:-1]])
+        own.load_state_dict(sub, strict=True)
+        return own.to(_device_of(sub))
+
+    def _rows(self, x):
+        enc = self.encoder
+        y = batch_norm_relu(input_linear(x, enc[0].weight, enc[0].bias), enc[1], relu=True)
+        for i in range(3, len(enc) - 1, 3):
+            y = batch_norm_relu(pointwise_linear(y, enc[i].weight, enc[i].bias), enc[i + 1], relu=True)
+        return pointwise_linear(y, enc[-1].weight, enc[-1].bias)
+
+
+class LinePositionalEncoder(_PositionalEncoder):
+    """The reference's LinePositionalEncoder (models/line_transformer.py:40-50) with its state_dict (encoder.{0,1,3,4,..}.*): the
+    mid-point, response and angle of every sub-line -> [B, feature_dim, n].  Torch makes the mid-point and the concatenation of the five
+    input columns (no gradient flows there); every layer, forward and backward, is native."""
+    N_IN = 5
+
+    @classmethod
+    def from_line_transformer(cls, model) -> "LinePositionalEncoder":
+        """the line encoder of a LineTransformer (this package's or the reference's), or of its state_dict: a copy"""
+        return cls._from(model, "klenc.line_position_enc.")
+
+    def forward(self, klines, responses, angles):
+        """klines [B, n, 2, 2], responses [B, n, 1], angles [B, n, 2] -> [B, feature_dim, n] (the transposed view of [B n, C] rows)"""
+        B, n = int(klines.shape[0]), int(klines.shape[1])
+        mid_points = (klines[:, :, 0] + klines[:, :, 1]) / 2.
+        rows = torch.cat([mid_points, responses, angles], dim=2).reshape(B * n, self.N_IN)
+        return self._rows(rows).view(B, n, self.feature_dim).transpose(1, 2)
+
+
+class WordPositionalEncoder(_PositionalEncoder):
+    """The reference's WordPositionalEncoder (models/line_transformer.py:52-73) with its state_dict: the position and score of every
+    token -> [B, n, S, feature_dim].  One row per token, B n S of them: BatchNorm's statistics run over all of them, as the reference's
+    do over its [B n, C, S] tensor."""
+    N_IN = 3
+
+    @classmethod
+    def from_line_transformer(cls, model) -> "WordPositionalEncoder":
+        """the word encoder of a LineTransformer (this package's or the reference's), or of its state_dict: a copy"""
+        return cls._from(model, "klenc.word_position_enc.")
+
+    def forward(self, words_in_line, scores_in_line):
+        """words_in_line [B, n, S, 2], scores_in_line [B, n, S, 1] -> [B, n, S, feature_dim]"""
+        B, n, S = (int(v) for v in words_in_line.shape[:3])
+        rows = torch.cat([words_in_line, scores_in_line], dim=-1).reshape(B * n * S, self.N_IN)
+        return self._rows(rows).view(B, n, S, self.feature_dim)
+
+
+class KeylineEncoder(nn.Module):
+    """The reference's KeylineEncoder (models/line_transformer.py:93-130) with its state_dict: line_position_enc.*, word_position_enc.*,
+    desc_layers.<i>.* and cls_token [1, 1, 1, 256].  sentence = line_position_enc(..) + desc_layer(cat(cls, desc + word_position_enc(..)))
+    [:, :, 0]^T.  The reference feeds every descriptive layer the same `desc` and reads only the last one's output, so only the last is
+    computed (the others get no gradient there either).  The sum desc + pos and the CLS slot are assemble_tokens; the final sum is a
+    torch add, like the signature network's residual."""
+
+    def __init__(self, feature_dim: int = D, mlp_layers=(32, 64, 128, 256), n_heads: int = HEADS, n_att_layers: int = 1, d_inner: int = 1024,
+                 dropout: float = 0.0):
+        super().__init__()
+        if feature_dim != D or int(n_att_layers) < 1:
+            raise ValueError(f"the native KeylineEncoder is {D} wide with at least one descriptive layer, got {feature_dim}, {n_att_layers}")
+        self.feature_dim = D
+        self.line_position_enc = LinePositionalEncoder(D, list(mlp_layers))
+        self.word_position_enc = WordPositionalEncoder(D, list(mlp_layers))
+        self.desc_layers = nn.ModuleList(LineDescriptiveEncoder(D, n_heads, n_att_layers, d_inner, dropout=dropout) for _ in range(int(n_att_layers)))
+        self.cls_token = nn.Parameter(torch.randn(1, 1, 1, D))
+
+    @classmethod
+    def from_line_transformer(cls, model) -> "KeylineEncoder":
+        """the klenc of a LineTransformer (this package's or the reference's), or of its state_dict: a copy"""
+        sub = _sub_state_dict(model, "klenc.")
+        widths = sorted((int(k.split(".")[2]), int(v.shape[0])) for k, v in sub.items()
+                        if k.startswith("line_position_enc.") and k.endswith(".weight") and v.dim() == 3)
+        n_layers = 1 + max(int(k.split(".")[1]) for k in sub if k.startswith("desc_layers."))
+        own = cls(D, [n for _, n in widths[:-1]], HEADS, n_layers, int(sub["desc_layers.0.pos_ffn.w_1.weight"].shape[0]))
+        own.load_state_dict(sub, strict=True)
+        return own.to(_device_of(sub))
+
+    def forward(self, klines, resp, angle, pnt, desc, score, mask=None):
+        """klines [B, n, 2, 2], resp [B, n, 1], angle [B, n, 2], pnt [B, n, S, 2], desc [B, n, S, 256], score [B, n, S, 1] -> sentence
+        [B, 256, n].  `mask` is accepted and ignored, as in LineDescriptiveEncoder."""
+        if desc.dim() != 4 or int(desc.shape[3]) != D or not 1 <= int(desc.shape[2]) <= 255:
+            raise ValueError(f"desc must be [B, n, S, {D}] with 1 <= S <= 255, got {tuple(desc.shape)}")
+        B, n, S = (int(v) for v in desc.shape[:3])
+        klines_pos = self.line_position_enc(klines, resp, angle)
+        pos = self.word_position_enc(pnt, score)
+        tokens = assemble_tokens(desc.reshape(B * n, S, D), pos.reshape(B * n, S, D), self.cls_token)
+        cls_out, _ = self.desc_layers[-1](tokens.view(B, n, S + 1, D), mask)
+        return klines_pos + cls_out.transpose(1, 2)
+
+
+class TrainableLineTransformer(nn.Module):
+    """The network the reference's train.py trains (LineTransformer, models/line_transformer.py:185-249) with a native backward: klenc
+    (KeylineEncoder), selfattn (SelfAttentionalLayer) and final_proj, under the reference's full key set -- load_state_dict(strict=True)
+    works in both directions with the reference's model.  forward(data) takes the reference's dict and returns it with `line_desc`
+    [B, 256, n] carrying the autograd graph; with linetr_amd.evaluations.descriptor_loss on top, `loss.backward()` fills every
+    parameter's .grad and desc_sublines.grad.  The key-line normalisation is torch without a gradient; the coordinates, responses,
+    angles and scores are inputs only (one that requires a gradient raises).  `config` is merged over default_config; `dropout` must be
+    0 in train mode (this build has no training-time dropout: LineDescriptiveEncoder).  linetr_amd.LineTransformer, the inference model, is
+    another class and stays as it is."""
+    default_config = {"image_shape": [480, 640], "descriptor_dim": D, "keyline_encoder": [32, 64, 128, 256], "n_heads": HEADS,
+                      "n_line_descriptive_layers": 1, "d_inner": 1024, "n_signature_layers": 7, "dropout": 0.0}
+    _INPUTS = ("sublines", "resp_sublines", "angle_sublines", "pnt_sublines", "score_sublines")
+
+    def __init__(self, config=None):
+        super().__init__()
+        self.config = c = {**self.default_config, **(config or {})}
+        self.image_shape = c["image_shape"]
+        if c["descriptor_dim"] != D:
+            raise ValueError(f"the native network is {D} wide, got descriptor_dim {c['descriptor_dim']}")
+        self.klenc = KeylineEncoder(D, c["keyline_encoder"], c["n_heads"], c["n_line_descriptive_layers"], c["d_inner"], dropout=c["dropout"])
+        self.selfattn = SelfAttentionalLayer(D, ["self"] * int(c["n_signature_layers"]))
+        self.final_proj = nn.Conv1d(D, D, kernel_size=1, bias=True)
+
+    @classmethod
+    def from_line_transformer(cls, model, **config) -> "TrainableLineTransformer":
+        """a copy of a LineTransformer (this package's or the reference's), or of its state_dict"""
+        sd = {k: torch.as_tensor(v) for k, v in (model if isinstance(model, dict) else model.state_dict()).items()}
+        enc = sorted((int(k.split(".")[3]), int(v.shape[0])) for k, v in sd.items()
+                     if k.startswith("klenc.line_position_enc.encoder.") and k.endswith(".weight") and v.dim() == 3)
+        own = cls({"keyline_encoder": [n for _, n in enc[:-1]],
+                   "n_line_descriptive_layers": 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("klenc.desc_layers.")),
+                   "d_inner": int(sd["klenc.desc_layers.0.pos_ffn.w_1.weight"].shape[0]),
+                   "n_signature_layers": 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("selfattn.layers.")), **config})
+        own.load_state_dict(sd, strict=True)
+        return own.to(sd["final_proj.weight"].device)
+
+    def _normalize(self, klines, pnt):
+        """normalize_keylines of the reference (:22-38): (x - centre) / (0.7 max(width, height)) on both end points and on the tokens"""
+        height, width = self.image_shape[-2:]
+        size = klines.new_tensor([float(width), float(height)])
+        center, scaling = size / 2, size.max() * 0.7
+        return (klines - center) / scaling, (pnt - center) / scaling
+
+    @staticmethod
+    def default_ret():
+        """the reference's return for an input without lines (:284-291)"""
+        return {"klines": torch.empty((1, 0, 2, 2)), "sublines": torch.empty((1, 0, 2, 2)), "line_desc": torch.empty((1, 256, 0)),
+                "mat_klines2sublines": torch.empty((1, 0, 0))}
+
+    def forward(self, data):
+        if len(data["klines"]) == 0:
+            return self.default_ret()
+        if torch.is_grad_enabled():
+            asked = [k for k in self._INPUTS if data[k].requires_grad]
+            if asked:
+                raise RuntimeError(f"linetr_amd.train_ops.TrainableLineTransformer has no gradient with respect to {', '.join(asked)}: of the "
+                                   "network's inputs only desc_sublines is differentiated")
+        with torch.no_grad():
+            klines, pnt = self._normalize(data["sublines"], data["pnt_sublines"])
+        sentence = self.klenc(klines, data["resp_sublines"], data["angle_sublines"], pnt, data["desc_sublines"], data["score_sublines"],
+                              data["mask_sublines"])
+        data.update({"line_desc": _Head.apply(self.selfattn(sentence), self.final_proj.weight, self.final_proj.bias)})
+        return data
