@@ -33,6 +33,9 @@
  *                + linetr_input_layer_forward / _backward / _backward_workspace_bytes / _chunk_rows, linetr_token_assemble_forward /
  *                _backward / _backward_workspace_bytes (the positional encoders' first layer and the token assembly): added symbols,
  *                the version stays.
+ *                + LinetrDropout, linetr_cls_pool_dropout_forward / _backward, linetr_layer_norm_dropout_forward / _backward,
+ *                linetr_dropout_factors (training-time dropout of the descriptive layer, masks generated in the kernels): added
+ *                symbols, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -584,6 +587,59 @@ int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, c
 int linetr_gelu_forward(LinetrHandle* h, const float* d_z, int64_t ldz, int64_t rows, int32_t C, float* d_y, int64_t ldy, void* stream);
 int linetr_gelu_backward(LinetrHandle* h, const float* d_z, int64_t ldz, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dz,
                          int64_t lddz, void* stream);
+
+/* ---- training-time dropout of the line descriptive layer ---------- */
+
+/* The reference trains with nn.Dropout(0.1) at three places of every descriptive layer (models/line_attention.py:18 on the attention
+ * weights, :70 behind fc, :90 behind w_2).  Here a mask is never stored: it is a pure function of (seed, call, site, row, element) that
+ * the forward AND the backward kernels generate, the same bits on every launch geometry.  Generator: Philox4x32-10, multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; key = (seed & 0xffffffff, seed >> 32), counter = (inner, row, call,
+ * site).  A word w keeps its element iff w >= threshold (= floor(p 2^32), made by the caller in double); the factor r is `scale`
+ * (= float(1 / (1 - p))) for a kept element and 0 for a dropped one.  threshold = 0, scale = 1 is p = 0 and gives the bits of the entry
+ * points without dropout.
+ *   site 0   the CLS query row's attention weights: row = segment l, inner = token t, word h belongs to head h
+ *   site 1/2 the [rows][256] tensor in front of the first / second residual LayerNorm: inner = column / 4, word k = column 4 inner + k
+ * `call` is the caller's count of training forwards; a backward passes the value its forward used. */
+typedef struct {
+  uint64_t seed;
+  uint32_t call;
+  uint32_t threshold;
+  float scale;
+} LinetrDropout;
+
+/* linetr_cls_pool_train_forward / _backward with site 0 (every argument they share means what it means there):
+ *   a_t = p_t r_t      pooled_h = sum_t a_t x_t      kept_h = sum_t a_t      d_kept [L][4] contiguous; d_lse is that of the full softmax
+ *   (the value projection behind it is then Wv_h pooled_h + kept_h bv_h: without dropout kept = 1)
+ *   da_t = dpooled_h . x_t + dkept_h      delta_h = dpooled_h . pooled_h + dkept_h kept_h      ds_t = p_t (r_t da_t - delta_h)
+ *   dx_t = sum_h (a_t dpooled_h + ds_t u_h)      du_h = sum_t ds_t x_t      d_dkept [L][4] may be NULL: no gradient arrives at kept
+ * A (segment, head) all of whose tokens are dropped gives pooled = 0 and kept = 0 exactly and adds nothing to dx and du; no NaN.
+ * `drop` is read before the call returns.  LINETR_E_ARG, nothing launched: what the plain entry points refuse, a NULL `drop`, d_kept or
+ * (backward) a misaligned d_dkept, a scale that is not finite or below 1. */
+int linetr_cls_pool_dropout_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
+                                    const LinetrDropout* drop, float* d_pooled, float* d_kept, float* d_lse, void* stream);
+int linetr_cls_pool_dropout_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                                     const float* d_lse, const float* d_kept, const float* d_dpooled, const float* d_dkept, int64_t L,
+                                     int32_t S, const LinetrDropout* drop, float* d_dx, int64_t lddx, float* d_du, int64_t lddu, void* stream);
+
+/* linetr_layer_norm_forward / _backward with dropout on `a` at `site` (1 or 2; 0 is accepted and draws site 0's words in the layout of
+ * sites 1 / 2):  v = fl(r a) + residual -- the product is rounded on its own, so that every output has the bits of the plain entry
+ * points on a pre-masked a --, y = LN(v).  The backward returns two tensors: d_dr <- dv (the gradient of the residual, what the plain
+ * backward calls dx) and d_da <- r dv; each may be NULL.  The workspace is that of linetr_layer_norm_backward.  LINETR_E_ARG, nothing
+ * launched: what the plain entry points refuse, a site outside 0..2, a NULL `drop`, a scale that is not finite or below 1. */
+int linetr_layer_norm_dropout_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                                      const float* d_beta, float eps, int64_t rows, int32_t C, const LinetrDropout* drop, int32_t site,
+                                      float* d_y, int64_t ldy, float* d_stats, void* stream);
+int linetr_layer_norm_dropout_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                                       const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C,
+                                       const LinetrDropout* drop, int32_t site, float* d_da, int64_t ldda, float* d_dr, int64_t lddr,
+                                       float* d_dgamma, float* d_dbeta, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The factors themselves: d_out [rows][inner][4] float32 <- `scale` or 0 for the words of counter (inner, row, call, site).  What the
+ * kernels above apply at site 0 to segment `row`, token `inner`, heads 0..3, and at sites 1 / 2 to row `row`, columns 4 inner .. + 3.
+ * Stateless; for tests and for looking at a mask.  0 <= rows < 2^31, 1 <= inner < 2^31, rows * inner <= 2^38.  rows = 0: nothing is
+ * launched.  LINETR_E_ARG, nothing launched: a shape outside the above, a site outside 0..2, a NULL or misaligned d_out, a NULL
+ * `drop`, a scale that is not finite or below 1. */
+int linetr_dropout_factors(LinetrHandle* h, const LinetrDropout* drop, int32_t site, int64_t rows, int64_t inner, float* d_out, void* stream);
 
 /* ---- the positional encoders and the token assembly for training (section 8(f) "next" row 4: the sixth link) ---------- */
 

@@ -49,6 +49,20 @@ class GemmCase(C.Structure):
                 ("add2", C.c_void_p), ("eps", C.c_float), ("via_row_norm", C.c_int32), ("tile", C.c_int32)]
 
 
+class Dropout(C.Structure):
+    """LinetrDropout: what a dropout kernel draws its masks from.  `make` is the one place a probability becomes a threshold."""
+    _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("threshold", C.c_uint32), ("scale", C.c_float)]
+
+    @classmethod
+    def make(cls, seed: int, call: int, p: float) -> "Dropout":
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"dropout probability {p}: 0 <= p < 1")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(call) < 1 << 32:
+            raise ValueError(f"dropout seed {seed} / call {call}: a 64-bit seed and a 32-bit call index")
+        return cls(int(seed), int(call), int(p * 4294967296.0), 1.0 / (1.0 - p))       # floor(p 2^32) in double; float32(1 / (1 - p))
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("calls", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -124,6 +138,12 @@ ABI = {
     "linetr_layer_norm_backward_workspace_bytes": (i64, [i64, i32]),
     "linetr_layer_norm_forward": (i32, [vp, vp, i64, vp, i64, vp, vp, f32, i64, i32, vp, i64, vp, vp]),
     "linetr_layer_norm_backward": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, i64, vp]),
+    "linetr_cls_pool_dropout_forward": (i32, [vp, vp, i64, vp, i64, i64, i32, _P(Dropout), vp, vp, vp, vp]),
+    "linetr_cls_pool_dropout_backward": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, _P(Dropout), vp, i64, vp, i64, vp]),
+    "linetr_layer_norm_dropout_forward": (i32, [vp, vp, i64, vp, i64, vp, vp, f32, i64, i32, _P(Dropout), i32, vp, i64, vp, vp]),
+    "linetr_layer_norm_dropout_backward": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, _P(Dropout), i32, vp, i64, vp, i64, vp, vp, vp,
+                                                 i64, vp]),
+    "linetr_dropout_factors": (i32, [vp, _P(Dropout), i32, i64, i64, vp, vp]),
     "linetr_gelu_forward": (i32, [vp, vp, i64, i64, i32, vp, i64, vp]),
     "linetr_gelu_backward": (i32, [vp, vp, i64, vp, i64, i64, i32, vp, i64, vp]),
     "linetr_input_layer_chunk_rows": (i32, []),

@@ -1,7 +1,7 @@
 // liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h): the validation step (lt_valstep.h),
 // the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
 // attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h), the
-// descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h), the positional encoders' input layer and
+// descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h) and their dropout siblings (lt_dropout.h), the positional encoders' input layer and
 // the token assembly with their backwards (lt_posbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
 #include <algorithm>
 
@@ -12,6 +12,7 @@
 #include "lt_attnbwd.h"
 #include "lt_bnbwd.h"
 #include "lt_descbwd.h"
+#include "lt_dropout.h"
 #include "lt_posbwd.h"
 #include "lt_gtassign.h"
 
@@ -541,19 +542,84 @@ extern "C" int linetr_bn_backward(LinetrHandle* h, const float* d_z, int64_t ldz
 namespace {
 constexpr int64_t CP_MAX_L = (int64_t)1 << 24;      // L S <= 2^32 rows are indexed in 64 bits; the grid of L / 4 blocks stays small
 constexpr int64_t LN_MAX_ROWS = (int64_t)1 << 30;
+constexpr int64_t DROP_MAX_ROWS = ((int64_t)1 << 31) - 1;     // a row is one 32-bit word of the Philox counter
 bool cp_dims_ok(int64_t L, int S) { return L >= 0 && L <= CP_MAX_L && S >= 1 && S <= CP_MAX_S; }
 int64_t ln_chunks(int64_t rows) { return (rows + LN_CHUNK - 1) / LN_CHUNK; }
+
+// The refusals of the pooling and LayerNorm entry points, with and without dropout, for `who`: every one before the first launch.
+int cp_fwd_check(const char* who, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int S, const float* d_pooled,
+                 const float* d_lse) {
+  if (!cp_dims_ok(L, S)) return fail(LINETR_E_ARG, "%s: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", who, (long long)L, S, CP_MAX_S);
+  if (!lin_stride_ok(ldx, D) || !lin_stride_ok(ldu, HEADS * D))
+    return fail(LINETR_E_ARG, "%s: row strides %lld / %lld (at least 256 / 1024, multiples of 4 floats)", who, (long long)ldx, (long long)ldu);
+  if (!d_x || !d_u || !d_pooled || !d_lse) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if (!aligned16(d_x) || !aligned16(d_u) || !aligned16(d_pooled) || !aligned16(d_lse))
+    return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  return LINETR_OK;
+}
+int cp_bwd_check(const char* who, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled, const float* d_lse,
+                 const float* d_dpooled, int64_t L, int S, const float* d_dx, int64_t lddx, const float* d_du, int64_t lddu) {
+  if (!cp_dims_ok(L, S)) return fail(LINETR_E_ARG, "%s: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", who, (long long)L, S, CP_MAX_S);
+  if (!lin_stride_ok(ldx, D) || !lin_stride_ok(ldu, HEADS * D) || (d_dx && !lin_stride_ok(lddx, D)) || (d_du && !lin_stride_ok(lddu, HEADS * D)))
+    return fail(LINETR_E_ARG, "%s: every row stride must be at least the width (256 tokens, 1024 u) and a multiple of 4 floats", who);
+  if (!d_x || !d_u || !d_pooled || !d_lse || !d_dpooled) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if (!aligned16(d_x) || !aligned16(d_u) || !aligned16(d_pooled) || !aligned16(d_lse) || !aligned16(d_dpooled) || !aligned16(d_dx) || !aligned16(d_du))
+    return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  return LINETR_OK;
+}
+int ln_fwd_check(const char* who, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma, const float* d_beta, float eps,
+                 int64_t rows, int C, const float* d_y, int64_t ldy, const float* d_stats) {
+  if (C != D || rows < 0 || rows > LN_MAX_ROWS) return fail(LINETR_E_ARG, "%s: bad shape rows=%lld C=%d (0 <= rows <= 2^30, C = 256)", who, (long long)rows, C);
+  if (!(eps > 0.f)) return fail(LINETR_E_ARG, "%s: eps %g (> 0)", who, eps);
+  if (!lin_stride_ok(lda, D) || (d_r && !lin_stride_ok(ldr, D)) || !lin_stride_ok(ldy, D))
+    return fail(LINETR_E_ARG, "%s: every row stride must be at least 256 and a multiple of 4 floats", who);
+  if (!d_a || !d_gamma || !d_beta || !d_y || !d_stats) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  if (!aligned16(d_a) || !aligned16(d_r) || !aligned16(d_gamma) || !aligned16(d_beta) || !aligned16(d_y) || !aligned16(d_stats))
+    return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  return LINETR_OK;
+}
+// (d_dx / d_dx2: the one data gradient of the plain backward, the two of the dropout one)
+int ln_bwd_check(const char* who, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats, const float* d_gamma,
+                 const float* d_g, int64_t ldg, int64_t rows, int C, const float* d_dx, int64_t lddx, const float* d_dx2, int64_t lddx2,
+                 const float* d_dgamma, const float* d_dbeta, const void* d_ws, int64_t ws_bytes) {
+  if (C != D || rows < 0 || rows > LN_MAX_ROWS) return fail(LINETR_E_ARG, "%s: bad shape rows=%lld C=%d (0 <= rows <= 2^30, C = 256)", who, (long long)rows, C);
+  if (!lin_stride_ok(lda, D) || (d_r && !lin_stride_ok(ldr, D)) || !lin_stride_ok(ldg, D) || (d_dx && !lin_stride_ok(lddx, D)) ||
+      (d_dx2 && !lin_stride_ok(lddx2, D)))
+    return fail(LINETR_E_ARG, "%s: every row stride must be at least 256 and a multiple of 4 floats", who);
+  if (!d_a || !d_stats || !d_gamma || !d_g) return fail(LINETR_E_ARG, "%s: null pointer", who);
+  const bool sums = d_dgamma || d_dbeta;
+  if (sums && !d_ws) return fail(LINETR_E_ARG, "%s: the gamma and beta gradients need the workspace", who);
+  if (!aligned16(d_a) || !aligned16(d_r) || !aligned16(d_stats) || !aligned16(d_gamma) || !aligned16(d_g) || !aligned16(d_dx) || !aligned16(d_dx2) ||
+      !aligned16(d_dgamma) || !aligned16(d_dbeta) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "%s: every tensor must be 16-byte aligned", who);
+  if (sums && ws_bytes < linetr_layer_norm_backward_workspace_bytes(rows, C))
+    return fail(LINETR_E_ARG, "%s: workspace too small (need %lld)", who, (long long)linetr_layer_norm_backward_workspace_bytes(rows, C));
+  return LINETR_OK;
+}
+// the second launch of both LayerNorm backwards: the chunks' partial rows added in ascending order (no rows: zeros)
+int ln_reduce(LinetrHandle* h, hipStream_t st, const float* partial, int chunks, float* d_dgamma, float* d_dbeta) {
+  ProfScope ps(h, st, "layer_norm_bwd_reduce", 0, 4.0 * (chunks + 1) * 2.0 * D);
+  hipLaunchKernelGGL(ln_reduce_kernel, dim3(2), dim3(256), 0, st, partial, chunks, d_dgamma, d_dbeta);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+// LinetrDropout as the kernels take it, or a refusal
+int drop_args(const char* who, const LinetrDropout* drop, int site, DropArgs* out) {
+  if (!drop) return fail(LINETR_E_ARG, "%s: null dropout state", who);
+  if (site < 0 || site > 2) return fail(LINETR_E_ARG, "%s: site %d (0: attention weights, 1 / 2: in front of the first / second LayerNorm)", who, site);
+  if (!std::isfinite(drop->scale) || drop->scale < 1.f) return fail(LINETR_E_ARG, "%s: scale %g (1 / (1 - p) with 0 <= p < 1)", who, drop->scale);
+  *out = DropArgs{(uint32_t)(drop->seed & 0xffffffffu), (uint32_t)(drop->seed >> 32), drop->call, drop->threshold, drop->scale};
+  return LINETR_OK;
+}
 }  // namespace
+
+extern "C" int64_t linetr_layer_norm_backward_workspace_bytes(int64_t rows, int32_t C) {
+  return C == D && rows >= 0 && rows <= LN_MAX_ROWS ? align_up(ln_chunks(rows) * 2 * D * 4, 256) + 256 : 0;
+}
 
 extern "C" int linetr_cls_pool_train_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
                                              float* d_pooled, float* d_lse, void* stream) {
-  // every refusal comes before the first launch
-  if (!cp_dims_ok(L, S)) return fail(LINETR_E_ARG, "cls_pool_train_forward: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", (long long)L, S, CP_MAX_S);
-  if (!lin_stride_ok(ldx, D) || !lin_stride_ok(ldu, HEADS * D))
-    return fail(LINETR_E_ARG, "cls_pool_train_forward: row strides %lld / %lld (at least 256 / 1024, multiples of 4 floats)", (long long)ldx, (long long)ldu);
-  if (!d_x || !d_u || !d_pooled || !d_lse) return fail(LINETR_E_ARG, "cls_pool_train_forward: null pointer");
-  if (!aligned16(d_x) || !aligned16(d_u) || !aligned16(d_pooled) || !aligned16(d_lse))
-    return fail(LINETR_E_ARG, "cls_pool_train_forward: every tensor must be 16-byte aligned");
+  if (int e = cp_fwd_check("cls_pool_train_forward", d_x, ldx, d_u, ldu, L, S, d_pooled, d_lse)) return e;
   if (L == 0) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
@@ -566,12 +632,7 @@ extern "C" int linetr_cls_pool_train_forward(LinetrHandle* h, const float* d_x, 
 extern "C" int linetr_cls_pool_train_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
                                               const float* d_lse, const float* d_dpooled, int64_t L, int32_t S, float* d_dx, int64_t lddx,
                                               float* d_du, int64_t lddu, void* stream) {
-  if (!cp_dims_ok(L, S)) return fail(LINETR_E_ARG, "cls_pool_train_backward: bad shape L=%lld S=%d (0 <= L <= 2^24, 1 <= S <= %d)", (long long)L, S, CP_MAX_S);
-  if (!lin_stride_ok(ldx, D) || !lin_stride_ok(ldu, HEADS * D) || (d_dx && !lin_stride_ok(lddx, D)) || (d_du && !lin_stride_ok(lddu, HEADS * D)))
-    return fail(LINETR_E_ARG, "cls_pool_train_backward: every row stride must be at least the width (256 tokens, 1024 u) and a multiple of 4 floats");
-  if (!d_x || !d_u || !d_pooled || !d_lse || !d_dpooled) return fail(LINETR_E_ARG, "cls_pool_train_backward: null pointer");
-  if (!aligned16(d_x) || !aligned16(d_u) || !aligned16(d_pooled) || !aligned16(d_lse) || !aligned16(d_dpooled) || !aligned16(d_dx) || !aligned16(d_du))
-    return fail(LINETR_E_ARG, "cls_pool_train_backward: every tensor must be 16-byte aligned");
+  if (int e = cp_bwd_check("cls_pool_train_backward", d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L, S, d_dx, lddx, d_du, lddu)) return e;
   if (L == 0 || (!d_dx && !d_du)) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
@@ -582,21 +643,10 @@ extern "C" int linetr_cls_pool_train_backward(LinetrHandle* h, const float* d_x,
   return LINETR_OK;
 }
 
-extern "C" int64_t linetr_layer_norm_backward_workspace_bytes(int64_t rows, int32_t C) {
-  return C == D && rows >= 0 && rows <= LN_MAX_ROWS ? align_up(ln_chunks(rows) * 2 * D * 4, 256) + 256 : 0;
-}
-
 extern "C" int linetr_layer_norm_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
                                          const float* d_beta, float eps, int64_t rows, int32_t C, float* d_y, int64_t ldy, float* d_stats,
                                          void* stream) {
-  if (C != D || rows < 0 || rows > LN_MAX_ROWS)
-    return fail(LINETR_E_ARG, "layer_norm_forward: bad shape rows=%lld C=%d (0 <= rows <= 2^30, C = 256)", (long long)rows, C);
-  if (!(eps > 0.f)) return fail(LINETR_E_ARG, "layer_norm_forward: eps %g (> 0)", eps);
-  if (!lin_stride_ok(lda, D) || (d_r && !lin_stride_ok(ldr, D)) || !lin_stride_ok(ldy, D))
-    return fail(LINETR_E_ARG, "layer_norm_forward: every row stride must be at least 256 and a multiple of 4 floats");
-  if (!d_a || !d_gamma || !d_beta || !d_y || !d_stats) return fail(LINETR_E_ARG, "layer_norm_forward: null pointer");
-  if (!aligned16(d_a) || !aligned16(d_r) || !aligned16(d_gamma) || !aligned16(d_beta) || !aligned16(d_y) || !aligned16(d_stats))
-    return fail(LINETR_E_ARG, "layer_norm_forward: every tensor must be 16-byte aligned");
+  if (int e = ln_fwd_check("layer_norm_forward", d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, C, d_y, ldy, d_stats)) return e;
   if (rows == 0) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
@@ -610,18 +660,9 @@ extern "C" int linetr_layer_norm_forward(LinetrHandle* h, const float* d_a, int6
 extern "C" int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
                                           const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dx,
                                           int64_t lddx, float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
-  if (C != D || rows < 0 || rows > LN_MAX_ROWS)
-    return fail(LINETR_E_ARG, "layer_norm_backward: bad shape rows=%lld C=%d (0 <= rows <= 2^30, C = 256)", (long long)rows, C);
-  if (!lin_stride_ok(lda, D) || (d_r && !lin_stride_ok(ldr, D)) || !lin_stride_ok(ldg, D) || (d_dx && !lin_stride_ok(lddx, D)))
-    return fail(LINETR_E_ARG, "layer_norm_backward: every row stride must be at least 256 and a multiple of 4 floats");
-  if (!d_a || !d_stats || !d_gamma || !d_g) return fail(LINETR_E_ARG, "layer_norm_backward: null pointer");
+  if (int e = ln_bwd_check("layer_norm_backward", d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, C, d_dx, lddx, nullptr, 0, d_dgamma, d_dbeta,
+                           d_ws, ws_bytes)) return e;
   const bool sums = d_dgamma || d_dbeta;
-  if (sums && !d_ws) return fail(LINETR_E_ARG, "layer_norm_backward: the gamma and beta gradients need the workspace");
-  if (!aligned16(d_a) || !aligned16(d_r) || !aligned16(d_stats) || !aligned16(d_gamma) || !aligned16(d_g) || !aligned16(d_dx) || !aligned16(d_dgamma) ||
-      !aligned16(d_dbeta) || !aligned16(d_ws))
-    return fail(LINETR_E_ARG, "layer_norm_backward: every tensor must be 16-byte aligned");
-  if (sums && ws_bytes < linetr_layer_norm_backward_workspace_bytes(rows, C))
-    return fail(LINETR_E_ARG, "layer_norm_backward: workspace too small (need %lld)", (long long)linetr_layer_norm_backward_workspace_bytes(rows, C));
   if (!d_dx && !sums) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
@@ -632,11 +673,102 @@ extern "C" int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int
     hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, d_dx, lddx, partial);
     LT_LAUNCH_CHECK();
   }
-  if (sums) {      // (no rows: zeros)
-    ProfScope ps(h, st, "layer_norm_bwd_reduce", 0, 4.0 * (chunks + 1) * 2.0 * D);
-    hipLaunchKernelGGL(ln_reduce_kernel, dim3(2), dim3(256), 0, st, (const float*)partial, chunks, d_dgamma, d_dbeta);
+  return sums ? ln_reduce(h, st, partial, chunks, d_dgamma, d_dbeta) : LINETR_OK;
+}
+
+// ---- the same four with training-time dropout (lt_dropout.h) ----
+
+extern "C" int linetr_cls_pool_dropout_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
+                                               const LinetrDropout* drop, float* d_pooled, float* d_kept, float* d_lse, void* stream) {
+  const char* who = "cls_pool_dropout_forward";
+  if (int e = cp_fwd_check(who, d_x, ldx, d_u, ldu, L, S, d_pooled, d_lse)) return e;
+  if (!d_kept || !aligned16(d_kept)) return fail(LINETR_E_ARG, "%s: kept must be a 16-byte aligned [L][4] tensor", who);
+  DropArgs dr;
+  if (int e = drop_args(who, drop, 0, &dr)) return e;
+  if (L == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "cls_pool_dropout_fwd", 2.0 * HEADS * 2.0 * L * S * D, 4.0 * L * ((double)S * D + 2.0 * HEADS * D + 2 * HEADS));
+  hipLaunchKernelGGL(cp_drop_fwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, L, (int)S, dr, d_pooled,
+                     d_kept, d_lse);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_cls_pool_dropout_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                                                const float* d_lse, const float* d_kept, const float* d_dpooled, const float* d_dkept, int64_t L,
+                                                int32_t S, const LinetrDropout* drop, float* d_dx, int64_t lddx, float* d_du, int64_t lddu,
+                                                void* stream) {
+  const char* who = "cls_pool_dropout_backward";
+  if (int e = cp_bwd_check(who, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L, S, d_dx, lddx, d_du, lddu)) return e;
+  if (!d_kept || !aligned16(d_kept) || !aligned16(d_dkept)) return fail(LINETR_E_ARG, "%s: kept and dkept must be 16-byte aligned [L][4] tensors (dkept may be null)", who);
+  DropArgs dr;
+  if (int e = drop_args(who, drop, 0, &dr)) return e;
+  if (L == 0 || (!d_dx && !d_du)) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "cls_pool_dropout_bwd", 2.0 * HEADS * 4.0 * L * S * D, 4.0 * L * ((d_dx ? 2.0 : 1.0) * S * D + 4.0 * HEADS * D + 3 * HEADS));
+  hipLaunchKernelGGL(cp_drop_bwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_kept,
+                     d_dpooled, d_dkept, L, (int)S, dr, d_dx, lddx, d_du, lddu);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_layer_norm_dropout_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                                                 const float* d_beta, float eps, int64_t rows, int32_t C, const LinetrDropout* drop, int32_t site,
+                                                 float* d_y, int64_t ldy, float* d_stats, void* stream) {
+  const char* who = "layer_norm_dropout_forward";
+  if (int e = ln_fwd_check(who, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, C, d_y, ldy, d_stats)) return e;
+  DropArgs dr;
+  if (int e = drop_args(who, drop, site, &dr)) return e;
+  if (rows == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "layer_norm_dropout_fwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2));
+  hipLaunchKernelGGL(ln_drop_fwd_kernel, dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(256), 0, st, d_a, lda, d_r, ldr, d_gamma, d_beta, eps,
+                     rows, dr, (uint32_t)site, d_y, ldy, d_stats);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_layer_norm_dropout_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                                                  const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C,
+                                                  const LinetrDropout* drop, int32_t site, float* d_da, int64_t ldda, float* d_dr, int64_t lddr,
+                                                  float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
+  const char* who = "layer_norm_dropout_backward";
+  if (int e = ln_bwd_check(who, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, C, d_da, ldda, d_dr, lddr, d_dgamma, d_dbeta, d_ws, ws_bytes))
+    return e;
+  DropArgs dr;
+  if (int e = drop_args(who, drop, site, &dr)) return e;
+  const bool sums = d_dgamma || d_dbeta;
+  if (!d_da && !d_dr && !sums) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  const int chunks = (int)ln_chunks(rows);
+  float* partial = sums ? (float*)d_ws : nullptr;
+  if (rows > 0) {
+    ProfScope ps(h, st, "layer_norm_dropout_bwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2 + (d_da ? D : 0) + (d_dr ? D : 0)));
+    hipLaunchKernelGGL(ln_drop_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, dr,
+                       (uint32_t)site, d_da, ldda, d_dr, lddr, partial);
     LT_LAUNCH_CHECK();
   }
+  return sums ? ln_reduce(h, st, partial, chunks, d_dgamma, d_dbeta) : LINETR_OK;
+}
+
+extern "C" int linetr_dropout_factors(LinetrHandle* h, const LinetrDropout* drop, int32_t site, int64_t rows, int64_t inner, float* d_out, void* stream) {
+  const char* who = "dropout_factors";
+  if (rows < 0 || rows > DROP_MAX_ROWS || inner < 1 || inner > DROP_MAX_ROWS || rows * inner > ((int64_t)1 << 38))
+    return fail(LINETR_E_ARG, "%s: bad shape rows=%lld inner=%lld (0 <= rows < 2^31, 1 <= inner < 2^31, rows inner <= 2^38)", who, (long long)rows,
+                (long long)inner);
+  DropArgs dr;
+  if (int e = drop_args(who, drop, site, &dr)) return e;
+  if (!d_out || !aligned16(d_out)) return fail(LINETR_E_ARG, "%s: the output must be a 16-byte aligned tensor", who);
+  if (rows == 0) return LINETR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  ProfScope ps(h, st, "dropout_factors", 0, 16.0 * rows * inner);
+  hipLaunchKernelGGL(drop_factors_kernel, dim3((unsigned)((rows * inner + 255) / 256)), dim3(256), 0, st, dr, (uint32_t)site, rows, inner, d_out);
+  LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
 

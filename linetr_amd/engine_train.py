@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _native as nat
 from ._shapes import D, as_rows_weight, check_pointwise_shapes, ptr
 
 
@@ -378,6 +379,78 @@ class _TrainSurface:
         self._call("linetr_layer_norm_backward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, st.data_ptr(),
                    gm.data_ptr(), g.data_ptr(), g.stride(0), rows, D, ptr(dx), D, ptr(dgamma), ptr(dbeta), ws.data_ptr(), ws.numel())
         return dx, dgamma, dbeta
+
+    # ------------------------------------------------------------------ the same with training-time dropout (csrc/lt_dropout.h)
+    @staticmethod
+    def dropout(seed: int, call: int, p: float) -> nat.Dropout:
+        """The LinetrDropout of (seed, call, p): threshold = floor(p 2^32), scale = float32(1 / (1 - p)); 0 <= p < 1, else ValueError.  The
+        masks are a pure function of it, the site and the element: a backward takes the one its forward took."""
+        return nat.Dropout.make(seed, call, p)
+
+    def dropout_factors(self, drop: nat.Dropout, site: int, rows: int, inner: int) -> torch.Tensor:
+        """The factors a dropout kernel applies (linetr_dropout_factors): [rows, inner, 4] float32, `scale` or 0.  Site 0: [segment, token,
+        head]; sites 1 / 2: [row, column / 4, column % 4].  Stateless.  No host wait."""
+        out = torch.empty((int(rows), int(inner), 4), dtype=torch.float32, device=self.device)
+        if out.numel():
+            self._call("linetr_dropout_factors", C.byref(drop), int(site), int(rows), int(inner), out.data_ptr())
+        return out
+
+    def cls_pool_dropout_forward(self, x, u, drop: nat.Dropout):
+        """cls_pool_forward with dropout on the softmax weights (site 0; linetr_cls_pool_dropout_forward): a = p r, pooled = sum_t a_t x_t,
+        kept = sum_t a_t.  Returns (pooled [L, 4, 256], kept [L, 4], lse [L, 4]).  No host wait."""
+        xr, ur, L, S = self._pool_args(x, u)
+        pooled = torch.empty((L, 4, D), dtype=torch.float32, device=self.device)
+        kept, lse = (torch.empty((L, 4), dtype=torch.float32, device=self.device) for _ in range(2))
+        if L:
+            self._call("linetr_cls_pool_dropout_forward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, L, S, C.byref(drop), pooled.data_ptr(),
+                       kept.data_ptr(), lse.data_ptr())
+        return pooled, kept, lse
+
+    def cls_pool_dropout_backward(self, x, u, pooled, lse, kept, grad_pooled, grad_kept, drop: nat.Dropout, need=(True, True)):
+        """The backward of cls_pool_dropout_forward (linetr_cls_pool_dropout_backward): (dx, du) for the gradients arriving at pooled and
+        at kept (`grad_kept` None: none arrives); `drop`: what the forward took -- the masks are generated again.  Deterministic; no
+        host wait."""
+        xr, ur, L, S = self._pool_args(x, u)
+        pr = self._rows_of(pooled.detach().reshape(L, 4 * D), (L, 4 * D), "pooled", strided=False)
+        gr = self._rows_of(grad_pooled.detach().reshape(L, 4 * D), (L, 4 * D), "grad_pooled", strided=False)
+        ls = self._rows_of(lse.detach(), (L, 4), "lse", strided=False)
+        kp = self._rows_of(kept.detach(), (L, 4), "kept", strided=False)
+        gk = self._rows_of(grad_kept.detach(), (L, 4), "grad_kept", strided=False) if grad_kept is not None else None
+        dx = torch.empty((L, S, D), dtype=torch.float32, device=self.device) if need[0] else None
+        du = torch.empty((L, 4, D), dtype=torch.float32, device=self.device) if need[1] else None
+        if L:
+            self._call("linetr_cls_pool_dropout_backward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, pr.data_ptr(), ls.data_ptr(), kp.data_ptr(),
+                       gr.data_ptr(), ptr(gk), L, S, C.byref(drop), ptr(dx), D, ptr(du), 4 * D)
+        return dx, du
+
+    def layer_norm_dropout_forward(self, a, residual, gamma, beta, drop: nat.Dropout, site: int, eps=1e-6):
+        """y = LayerNorm(r a + residual) with r the factors of `site` (1 or 2; linetr_layer_norm_dropout_forward).  Returns (y, stats) as
+        layer_norm_forward.  No host wait."""
+        ar, rr, gm, rows = self._ln_args("layer_norm_dropout_forward", a, residual, gamma)
+        y = torch.empty((rows, D), dtype=torch.float32, device=self.device)
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=self.device)
+        if rows:
+            self._call("linetr_layer_norm_dropout_forward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0,
+                       gm.data_ptr(), self._f32(beta.detach().reshape(-1)).data_ptr(), float(eps), rows, D, C.byref(drop), int(site), y.data_ptr(), D,
+                       stats.data_ptr())
+        return y, stats
+
+    def layer_norm_dropout_backward(self, a, residual, stats, gamma, grad_out, drop: nat.Dropout, site: int, need=(True, True, True, True)):
+        """The backward of layer_norm_dropout_forward (linetr_layer_norm_dropout_backward): (da, dresidual, dgamma, dbeta) with dresidual =
+        dv and da = r dv, the masks generated again from `drop` and `site`.  `need` = which of the four to compute (the others are
+        None).  Deterministic; no host wait."""
+        ar, rr, gm, rows = self._ln_args("layer_norm_dropout_backward", a, residual, gamma)
+        g = self._rows_of(grad_out.detach(), (rows, D), "grad_out")
+        st = self._rows_of(stats.detach(), (rows, 2), "stats", strided=False)
+        da, dr = (torch.empty((rows, D), dtype=torch.float32, device=self.device) if k else None for k in need[:2])
+        dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=self.device) if k else None for k in need[2:4])
+        if rows == 0:
+            return da, dr, dgamma.zero_() if dgamma is not None else None, dbeta.zero_() if dbeta is not None else None
+        ws = self._stream_workspace("layer_norm_bwd", self._L.linetr_layer_norm_backward_workspace_bytes(rows, D))
+        self._call("linetr_layer_norm_dropout_backward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, st.data_ptr(),
+                   gm.data_ptr(), g.data_ptr(), g.stride(0), rows, D, C.byref(drop), int(site), ptr(da), D, ptr(dr), D, ptr(dgamma), ptr(dbeta),
+                   ws.data_ptr(), ws.numel())
+        return da, dr, dgamma, dbeta
 
     def _gelu_rows(self, z, what):
         if z.dim() != 2 or int(z.shape[1]) % 4 or not 4 <= int(z.shape[1]) <= 4096:

@@ -27,6 +27,10 @@ of them.
                                                          x [L, S, 256], u [L, 4, 256]; dx and du native (Engine.cls_pool_forward / _backward)
     LineDescriptiveEncoder                               the reference's descriptive layer (:75-91) with its state_dict, in the folded form:
                                                          only the CLS row KeylineEncoder reads is computed; every gradient native
+    cls_token_pool(x, u, dropout), residual_layer_norm(a, residual, ln, dropout, site), seed_dropout(seed)
+                                                         training-time dropout at the reference's three places, the masks a pure function
+                                                         of (seed, call, site, element) that the kernels of csrc/lt_dropout.h generate in the
+                                                         forward and again in the backward (Engine.cls_pool_dropout_* / layer_norm_dropout_*)
 
 With linetr_amd.evaluations.descriptor_loss on top of a DescriptorHead on top of a SelfAttentionalLayer, `loss.backward()` fills every
 gradient of the signature network -- the eight attention parameters, the two convolutions and the BatchNorm weight and bias of every layer,
@@ -55,6 +59,8 @@ With these the training surface is complete: every layer of the model the refere
 encoders and their glue torch makes the key-line normalisation, the mid-point, the concatenation of the 3 / 5 input columns, the reshapes
 (no gradient flows there) and the final add klines_pos + cls_out^T."""
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -364,10 +370,46 @@ class _ResidualLayerNorm(torch.autograd.Function):
                 None)
 
 
-def residual_layer_norm(a, residual, ln: nn.LayerNorm):
+class DropoutState(NamedTuple):
+    """What the masks of one training forward are a pure function of: a 64-bit seed, the 32-bit index of the forward, the probability.
+    (The generator and its counter layout: include/linetr_hip.h, LinetrDropout.)"""
+    seed: int
+    call: int
+    p: float
+
+
+def _native_dropout(dropout):
+    """a DropoutState (or any (seed, call, p)) as the engine's LinetrDropout; 0 <= p < 1, else ValueError"""
+    from ._native import Dropout
+    seed, call, p = dropout
+    return Dropout.make(seed, call, p)
+
+
+class _ResidualLayerNormDropout(torch.autograd.Function):
+    """y = LayerNorm(r a + residual), r the factors of `site`.  Saved for the backward: a, the residual, the rows' mean | rstd, gamma and the
+    dropout state itself -- the mask is generated again, not stored."""
+
+    @staticmethod
+    def forward(ctx, a, residual, gamma, beta, eps, drop, site):
+        y, stats = _engine(a.device).layer_norm_dropout_forward(a, residual, gamma, beta, drop, site, eps)
+        ctx.drop, ctx.site = drop, site
+        ctx.save_for_backward(a, residual, stats, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, residual, stats, gamma = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        da, dr, dgamma, dbeta = _engine(a.device).layer_norm_dropout_backward(
+            a, residual, stats, gamma, grad_out, ctx.drop, ctx.site, need=(need[0], residual is not None and need[1], need[2], need[3]))
+        return da, dr, dgamma, dbeta, None, None, None
+
+
+def residual_layer_norm(a, residual, ln: nn.LayerNorm, dropout=None, site=None):
     """ln(a + residual) for an nn.LayerNorm(256) `ln`, as the reference's `q += residual; q = self.layer_norm(q)`; a, residual
-    [rows, 256] (residual may be None).  Differentiable with respect to a, residual, ln.weight and ln.bias.  Refused: an `ln` without
-    affine parameters or of another width."""
+    [rows, 256] (residual may be None).  Differentiable with respect to a, residual, ln.weight and ln.bias.  With `dropout` (a
+    DropoutState) and `site` (1: behind fc, 2: behind w_2) it is ln(dropout(a) + residual) as the reference's train mode computes it, the
+    mask generated in the kernels, forward and backward.  Refused: an `ln` without affine parameters or of another width."""
     if not isinstance(ln, nn.LayerNorm):
         raise TypeError(f"residual_layer_norm takes an nn.LayerNorm, got {type(ln).__name__}")
     if tuple(ln.normalized_shape) != (D,) or ln.weight is None or ln.bias is None:
@@ -375,7 +417,11 @@ def residual_layer_norm(a, residual, ln: nn.LayerNorm):
                          f"{'' if ln.weight is not None and ln.bias is not None else ' without weight and bias'}")
     if a.dim() != 2 or int(a.shape[1]) != D or (residual is not None and residual.shape != a.shape):
         raise ValueError(f"a and residual must be [rows, {D}], got {tuple(a.shape)} and {None if residual is None else tuple(residual.shape)}")
-    return _ResidualLayerNorm.apply(a, residual, ln.weight, ln.bias, float(ln.eps))
+    if dropout is None:
+        return _ResidualLayerNorm.apply(a, residual, ln.weight, ln.bias, float(ln.eps))
+    if site not in (1, 2):
+        raise ValueError(f"residual_layer_norm: dropout needs its site, 1 (behind fc) or 2 (behind w_2), got {site!r}")
+    return _ResidualLayerNormDropout.apply(a, residual, ln.weight, ln.bias, float(ln.eps), _native_dropout(dropout), int(site))
 
 
 class _ClsTokenPool(torch.autograd.Function):
@@ -394,13 +440,35 @@ class _ClsTokenPool(torch.autograd.Function):
         return _engine(x.device).cls_pool_backward(x, u, pooled, lse, grad_pooled, need=tuple(ctx.needs_input_grad[:2]))
 
 
-def cls_token_pool(x, u):
+class _ClsTokenPoolDropout(torch.autograd.Function):
+    """a = softmax_t(u[l, h] . x[l, t]) r[l, h, t];  pooled[l, h] = sum_t a_t x[l, t];  kept[l, h] = sum_t a_t.  Saved for the backward: x, u,
+    pooled, kept, lse and the dropout state itself -- softmax and mask are made again, not stored."""
+
+    @staticmethod
+    def forward(ctx, x, u, drop):
+        pooled, kept, lse = _engine(x.device).cls_pool_dropout_forward(x, u, drop)
+        ctx.drop = drop
+        ctx.save_for_backward(x, u, pooled, kept, lse)
+        return pooled, kept
+
+    @staticmethod
+    def backward(ctx, grad_pooled, grad_kept):
+        x, u, pooled, kept, lse = ctx.saved_tensors
+        return (*_engine(x.device).cls_pool_dropout_backward(x, u, pooled, lse, kept, grad_pooled, grad_kept, ctx.drop,
+                                                              need=tuple(ctx.needs_input_grad[:2])), None)
+
+
+def cls_token_pool(x, u, dropout=None):
     """The CLS query row's attention over the S tokens of each segment, in the folded form: x [L, S, 256] token rows (slot 0: the CLS
     token), u [L, 4, 256] with u[l, h] = Wk_h^T (q_lh / 8); returns pooled [L, 4, 256], the softmax-weighted mean of the tokens per
-    head.  Differentiable with respect to x and u."""
+    head.  Differentiable with respect to x and u.  With `dropout` (a DropoutState) the softmax weights go through the reference's
+    attention dropout (site 0) and the result is (pooled, kept): kept [L, 4] is what is left of the weights' sum, the factor of the
+    value bias behind the pooling; both are differentiable."""
     if x.dim() != 3 or int(x.shape[2]) != D or not 1 <= int(x.shape[1]) <= 256 or tuple(u.shape) != (int(x.shape[0]), HEADS, D):
         raise ValueError(f"x must be [L, S, {D}] with 1 <= S <= 256 and u [L, {HEADS}, {D}], got {tuple(x.shape)} and {tuple(u.shape)}")
-    return _ClsTokenPool.apply(x, u)
+    if dropout is None:
+        return _ClsTokenPool.apply(x, u)
+    return _ClsTokenPoolDropout.apply(x, u, _native_dropout(dropout))
 
 
 class _CancelledBias(torch.autograd.Function):
@@ -440,6 +508,7 @@ class LineDescriptiveEncoder(nn.Module):
             raise ValueError(f"the native descriptive layer is {D} wide with {HEADS} heads and d_inner a multiple of 64 up to 1024, got "
                              f"{d_feature}, {n_heads}, {d_inner}")
         self.dropout = float(dropout)
+        self._dropout_state = None               # (seed, call) once seed_dropout() was called: plain Python, not in the state_dict
         self.slf_attn, self.pos_ffn = _Linears(), _Linears()
         for name in ("w_qs", "w_ks", "w_vs", "fc"):
             setattr(self.slf_attn, name, nn.Linear(D, D, bias=True))
@@ -459,18 +528,50 @@ class LineDescriptiveEncoder(nn.Module):
         own.load_state_dict(sub, strict=True)
         return own.to(_device_of(sub))
 
+    def seed_dropout(self, seed: int, call: int = 0):
+        """Switches training-time dropout on: from now on a train-mode forward with `dropout != 0` draws its masks from (seed, call) and
+        then increments `call`, so that consecutive forwards -- the two views of one step -- draw different masks.  A 64-bit seed, a
+        32-bit call index (it wraps)."""
+        self.set_dropout_state((seed, call))
+        return self
+
+    def dropout_state(self):
+        """(seed, call) of the next training forward, or None for a module that was never seeded: what a checkpoint keeps beside the
+        state_dict (it is no tensor and not part of it)"""
+        return self._dropout_state
+
+    def set_dropout_state(self, state):
+        """dropout_state()'s inverse: (seed, call), or None to go back to refusing"""
+        if state is not None:
+            seed, call = (int(v) for v in state)
+            if not 0 <= seed < 1 << 64 or not 0 <= call < 1 << 32:
+                raise ValueError(f"dropout state {state!r}: a 64-bit seed and a 32-bit call index")
+            state = (seed, call)
+        self._dropout_state = state
+
+    def _next_dropout(self):
+        """the DropoutState of this training forward (None: no dropout); advances the call index"""
+        if not self.training or self.dropout == 0.0:
+            return None
+        if self._dropout_state is None:
+            raise RuntimeError(
+                "linetr_amd.train_ops.LineDescriptiveEncoder in train mode with dropout "
+                f"{self.dropout}: the masks of training-time dropout (the reference's nn.Dropout(0.1), models/line_attention.py:18,70,90) "
+                "are a function of a seed, and randomness is never drawn implicitly.  Call `seed_dropout(seed)` first, set `dropout = 0.0` "
+                "to run the deterministic train-mode forward, or call .eval()")
+        seed, call = self._dropout_state
+        self._dropout_state = (seed, (call + 1) & 0xffffffff)
+        return DropoutState(seed, call, self.dropout)
+
     def forward(self, desc, slf_attn_mask=None):
         """desc [B, L, S, 256] (slot 0 of every segment: the CLS token) -> (cls_out [B, L, 256], None).  cls_out is row 0 of the
         reference's output, enc_output[:, :, 0, :], the only row KeylineEncoder reads; the reference's second result, the S x S attention
         map, is never formed.  `slf_attn_mask` is accepted and ignored: the reference's mask acts on QUERY rows, and the CLS row is never
-        masked, so row 0 attends to all S keys whatever the mask holds."""
-        if self.training and self.dropout != 0.0:
-            raise RuntimeError(
-                "linetr_amd.train_ops.LineDescriptiveEncoder in train mode: the training-time forward of this build has no dropout (the "
-                "reference applies nn.Dropout(0.1) in its attention blocks, models/line_attention.py:11,39,84).  Set `dropout = 0.0` to "
-                "run the deterministic train-mode forward, or call .eval()")
+        masked, so row 0 attends to all S keys whatever the mask holds.  In train mode with `dropout != 0` the three
+        dropouts of the reference act on row 0 (training-time dropout): the value bias is then scaled by what the attention dropout kept."""
         if desc.dim() != 4 or int(desc.shape[3]) != D or not 1 <= int(desc.shape[2]) <= 256:
             raise ValueError(f"desc must be [B, L, S, {D}] with 1 <= S <= 256, got {tuple(desc.shape)}")
+        drop = self._next_dropout()
         B, L, S = (int(v) for v in desc.shape[:3])
         att, ffn = self.slf_attn, self.pos_ffn
         x = desc.reshape(B * L, S, D)
@@ -478,11 +579,16 @@ class LineDescriptiveEncoder(nn.Module):
         q = pointwise_linear(x0, att.w_qs.weight, att.w_qs.bias) * 0.125                     # (a power of two: exact)
         head = lambda h: slice(h * DH, (h + 1) * DH)
         u = torch.stack([pointwise_linear(q[:, head(h)], att.w_ks.weight[head(h)].t()) for h in range(HEADS)], dim=1)
-        pooled = cls_token_pool(x, u)
-        o = torch.cat([pointwise_linear(pooled[:, h], att.w_vs.weight[head(h)], att.w_vs.bias[head(h)]) for h in range(HEADS)], dim=1)
-        y = residual_layer_norm(pointwise_linear(o, att.fc.weight, att.fc.bias), x0, att.layer_norm)
+        if drop is None:
+            pooled = cls_token_pool(x, u)
+            o = torch.cat([pointwise_linear(pooled[:, h], att.w_vs.weight[head(h)], att.w_vs.bias[head(h)]) for h in range(HEADS)], dim=1)
+        else:
+            pooled, kept = cls_token_pool(x, u, drop)
+            o = torch.cat([pointwise_linear(pooled[:, h], att.w_vs.weight[head(h)]) + kept[:, h:h + 1] * att.w_vs.bias[head(h)]
+                           for h in range(HEADS)], dim=1)
+        y = residual_layer_norm(pointwise_linear(o, att.fc.weight, att.fc.bias), x0, att.layer_norm, drop, 1 if drop is not None else None)
         hidden = gelu(pointwise_linear(y, ffn.w_1.weight, ffn.w_1.bias))
-        out = residual_layer_norm(pointwise_linear(hidden, ffn.w_2.weight, ffn.w_2.bias), y, ffn.layer_norm)
+        out = residual_layer_norm(pointwise_linear(hidden, ffn.w_2.weight, ffn.w_2.bias), y, ffn.layer_norm, drop, 2 if drop is not None else None)
         if att.w_ks.bias.requires_grad and torch.is_grad_enabled():
             out = _CancelledBias.apply(out, att.w_ks.bias)
         return out.view(B, L, D), None
@@ -654,6 +760,17 @@ class KeylineEncoder(nn.Module):
         own.load_state_dict(sub, strict=True)
         return own.to(_device_of(sub))
 
+    def seed_dropout(self, seed: int, call: int = 0):
+        """LineDescriptiveEncoder.seed_dropout of the layer that is computed, the last one"""
+        self.desc_layers[-1].seed_dropout(seed, call)
+        return self
+
+    def dropout_state(self):
+        return self.desc_layers[-1].dropout_state()
+
+    def set_dropout_state(self, state):
+        self.desc_layers[-1].set_dropout_state(state)
+
     def forward(self, klines, resp, angle, pnt, desc, score, mask=None):
         """klines [B, n, 2, 2], resp [B, n, 1], angle [B, n, 2], pnt [B, n, S, 2], desc [B, n, S, 256], score [B, n, S, 1] -> sentence
         [B, 256, n].  `mask` is accepted and ignored, as in LineDescriptiveEncoder."""
@@ -673,9 +790,9 @@ class TrainableLineTransformer(nn.Module):
     works in both directions with the reference's model.  forward(data) takes the reference's dict and returns it with `line_desc`
     [B, 256, n] carrying the autograd graph; with linetr_amd.evaluations.descriptor_loss on top, `loss.backward()` fills every
     parameter's .grad and desc_sublines.grad.  The key-line normalisation is torch without a gradient; the coordinates, responses,
-    angles and scores are inputs only (one that requires a gradient raises).  `config` is merged over default_config; `dropout` must be
-    0 in train mode (this build has no training-time dropout: LineDescriptiveEncoder).  linetr_amd.LineTransformer, the inference model, is
-    another class and stays as it is."""
+    angles and scores are inputs only (one that requires a gradient raises).  `config` is merged over default_config; a `dropout` other
+    than 0 runs in train mode once seed_dropout(seed) was called and raises before (LineDescriptiveEncoder: randomness is never drawn
+    implicitly).  linetr_amd.LineTransformer, the inference model, is another class and stays as it is."""
     default_config = {"image_shape": [480, 640], "descriptor_dim": D, "keyline_encoder": [32, 64, 128, 256], "n_heads": HEADS,
                       "n_line_descriptive_layers": 1, "d_inner": 1024, "n_signature_layers": 7, "dropout": 0.0}
     _INPUTS = ("sublines", "resp_sublines", "angle_sublines", "pnt_sublines", "score_sublines")
@@ -702,6 +819,19 @@ class TrainableLineTransformer(nn.Module):
                    "n_signature_layers": 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("selfattn.layers.")), **config})
         own.load_state_dict(sd, strict=True)
         return own.to(sd["final_proj.weight"].device)
+
+    def seed_dropout(self, seed: int, call: int = 0):
+        """Switches training-time dropout on (LineDescriptiveEncoder.seed_dropout of klenc's last descriptive layer): with `dropout` 0.1
+        in the config and a seed, .train() runs the reference's recipe; every forward draws its own masks.  Checkpoint
+        dropout_state() beside the state_dict and hand it to set_dropout_state() to resume."""
+        self.klenc.seed_dropout(seed, call)
+        return self
+
+    def dropout_state(self):
+        return self.klenc.dropout_state()
+
+    def set_dropout_state(self, state):
+        self.klenc.set_dropout_state(state)
 
     def _normalize(self, klines, pnt):
         """normalize_keylines of the reference (:22-38): (x - centre) / (0.7 max(width, height)) on both end points and on the tokens"""
