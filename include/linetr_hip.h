@@ -36,6 +36,8 @@
  *                + LinetrDropout, linetr_cls_pool_dropout_forward / _backward, linetr_layer_norm_dropout_forward / _backward,
  *                linetr_dropout_factors (training-time dropout of the descriptive layer, masks generated in the kernels): added
  *                symbols, the version stays.
+ *                + LinetrAdamTensor, LinetrAdamHyper, linetr_adam_step, linetr_grad_norm and their _workspace_bytes (the optimizer
+ *                step over a table of tensors and the gradient norm that can feed it): added symbols, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -728,6 +730,70 @@ int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void* d_lines0, 
                      double thres_angdiff, double min_overlap_ratio, int32_t pad, float* d_assign, int32_t* d_lmatches, int32_t M,
                      int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir, void* d_proj0, void* d_proj1, void* d_workspace,
                      int64_t workspace_bytes, void* stream);
+
+/* ---- the optimizer step (section 8(f) "next" row 4: the line that changes the weights) ---------- */
+
+/* torch.optim.Adam as the reference builds it (train.py:82) and steps it (:195), over a table of tensors in ONE launch, and the global
+ * gradient norm of the same table, whose clipping coefficient the step can read on the device.
+ *
+ * h_table: a HOST array of n_tensors entries; p / g / m / v are DEVICE pointers to n float32 each (parameter, gradient, exp_avg,
+ * exp_avg_sq).  The library cuts every tensor into chunks of 4 096 elements, one block each, and puts the table with its chunk prefix
+ * into the caller's workspace through the arguments of small launches of 64 entries each in front of the update: h_table is read
+ * before the call returns, nothing on the host is kept, and the call never waits for the stream.  A block finds its tensor by a
+ * binary search of the prefix.
+ *
+ * The update, per element, float32, one rounding per written operation: the order of torch's non-capturable single-tensor path
+ * (torch/optim/adam.py, _single_tensor_adam, torch 2.10).  Every float(.) is formed in double first.
+ *   g  <- fl(scale g)                         only when d_grad_scale != NULL (one float32 read on the device); rounded on its own
+ *   coupled   (decoupled == 0, weight_decay != 0):  g <- fmaf(wd, p, g)
+ *   decoupled (decoupled == 1, weight_decay != 0):  p <- p float(1 - lr wd)
+ *   m' = fmaf(float(1 - beta1), g - m, m)
+ *   v' = fmaf(float(1 - beta2) g, g, float(beta2) v)
+ *   d  = sqrtf(v') / bc2_sqrt + float(eps)     IEEE square root and division
+ *   p' = fmaf(-step_size, m' / d, p)
+ * p, m and v are updated in place; g is only read (a scale never rewrites it).  step_size = lr / (1 - beta1^step) and bc2_sqrt =
+ * sqrt(1 - beta2^step) are made by the caller in double, per tensor, as torch makes them: a parameter that got no gradient on some
+ * steps has its own step count.  `lr` of the hyper-parameters is read by the decoupled decay alone.
+ * 16 bytes per lane where p, g, m and v of a tensor are all 16-byte aligned, 4 bytes per lane otherwise (views carved out of a flat
+ * buffer); nothing outside [0, n) of a tensor is touched.  Deterministic; no atomics.  Asynchronous on `stream`; nothing inside
+ * allocates or waits; `h` may be NULL.  A table of no elements at all: LINETR_OK, nothing launched.
+ * LINETR_E_ARG, nothing launched, no output changed: a NULL table or hyper; n_tensors outside 1 .. 65 536; n < 0; more than 2^30
+ * chunks; for a tensor with n > 0 a NULL or not 4-byte aligned p / g / m / v, two of the four equal, a step_size that is not finite, a
+ * bc2_sqrt not in (0, 1]; a beta outside [0, 1); eps or weight_decay negative or not finite; decoupled not 0 / 1, or 1 with an lr that
+ * is not finite; a misaligned d_grad_scale; a NULL, not 256-byte aligned or short workspace (linetr_adam_workspace_bytes of the table's
+ * n_tensors and total element count; 0 for a shape that is refused). */
+typedef struct {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  float step_size;
+  float bc2_sqrt;
+} LinetrAdamTensor; /* 48 bytes */
+typedef struct {
+  double beta1, beta2, eps, weight_decay, lr;
+  int32_t decoupled;
+} LinetrAdamHyper;
+
+int64_t linetr_adam_workspace_bytes(int32_t n_tensors, int64_t n_total);
+int linetr_adam_step(LinetrHandle* h, const LinetrAdamTensor* h_table, int32_t n_tensors, const LinetrAdamHyper* hyper,
+                     const float* d_grad_scale, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The L2 norm of every g of the table together (only g and n of an entry are read), deterministic, and the coefficient of
+ * torch.nn.utils.clip_grad_norm_:
+ *   d_norm[0]  <- sqrt(sum g^2)                                float64
+ *   d_scale[0] <- float(min(1, max_norm / (norm + 1e-6)))      max_norm = +inf: the norm alone, the scale is then 1; a NaN norm gives NaN
+ * Same chunks as the step.  Each chunk's squares are summed in float64 in a fixed order into the workspace (lane t of 256 adds elements
+ * t, t + 256, ... in ascending order; the lanes by a fixed tree); a second, one-block launch adds the chunks' sums: 256 contiguous runs,
+ * each in ascending order, then the runs in ascending order.  The bits depend on the table's sizes alone, not on alignment.  No host
+ * wait: linetr_adam_step reads d_scale on the device.  A table of no elements: norm 0, scale 1 (one launch).
+ * LINETR_E_ARG, nothing launched, no output changed: what the step refuses of the table (g alone of the pointers), a max_norm that is
+ * negative or NaN, a NULL d_norm (8-byte aligned) or d_scale (4-byte aligned), a NULL, not 256-byte aligned or short workspace
+ * (linetr_grad_norm_workspace_bytes). */
+int64_t linetr_grad_norm_workspace_bytes(int32_t n_tensors, int64_t n_total);
+int linetr_grad_norm(LinetrHandle* h, const LinetrAdamTensor* h_table, int32_t n_tensors, double max_norm, double* d_norm,
+                     float* d_scale, void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- dense-map producer (section 8(f) "next" row 2) ------------------------------------------------- */
 

@@ -63,6 +63,24 @@ class Dropout(C.Structure):
         return cls(int(seed), int(call), int(p * 4294967296.0), 1.0 / (1.0 - p))       # floor(p 2^32) in double; float32(1 / (1 - p))
 
 
+# LinetrAdamTensor: one row of the HOST table linetr_adam_step / linetr_grad_norm take (p, g, m, v: device pointers; 0 = NULL)
+ADAM_TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"), ("bc2_sqrt", "<f4")])
+assert ADAM_TENSOR_DTYPE.itemsize == 48
+
+
+def adam_bias_corrections(lr: float, beta1: float, beta2: float, step: float):
+    """(step_size, bc2_sqrt) of one parameter as torch's _single_tensor_adam makes them, in double: lr / (1 - beta1^step) and
+    sqrt(1 - beta2^step).  The one place a step count becomes what the kernel reads (each is then rounded to float32 once)."""
+    step = float(step)
+    return float(lr) / (1.0 - float(beta1) ** step), (1.0 - float(beta2) ** step) ** 0.5
+
+
+class AdamHyper(C.Structure):
+    """LinetrAdamHyper"""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("lr", C.c_double),
+                ("decoupled", C.c_int32)]
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("calls", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -155,6 +173,10 @@ ABI = {
     "linetr_token_assemble_backward": (i32, [vp, vp, i64, i32, vp, vp, vp, i64, vp]),
     "linetr_gt_assign_workspace_bytes": (i64, [i32, i32, i32]),
     "linetr_gt_assign": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_adam_workspace_bytes": (i64, [i32, i64]),
+    "linetr_adam_step": (i32, [vp, vp, i32, _P(AdamHyper), vp, vp, i64, vp]),
+    "linetr_grad_norm_workspace_bytes": (i64, [i32, i64]),
+    "linetr_grad_norm": (i32, [vp, vp, i32, f64, vp, vp, vp, i64, vp]),
     "linetr_superpoint_heads": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "linetr_superpoint_keypoints_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "linetr_superpoint_keypoints": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),

@@ -2,7 +2,8 @@
 // the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
 // attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h), the
 // descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h) and their dropout siblings (lt_dropout.h), the positional encoders' input layer and
-// the token assembly with their backwards (lt_posbwd.h) and the ground-truth line assignment in front of them (lt_gtassign.h).
+// the token assembly with their backwards (lt_posbwd.h), the ground-truth line assignment in front of them (lt_gtassign.h) and the
+// optimizer step behind them, with the gradient norm that can feed it (lt_adam.h).
 #include <algorithm>
 
 #include "lt_handle.h"
@@ -15,6 +16,7 @@
 #include "lt_dropout.h"
 #include "lt_posbwd.h"
 #include "lt_gtassign.h"
+#include "lt_adam.h"
 
 using namespace lt;
 
@@ -1018,4 +1020,147 @@ extern "C" int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void*
   return gt_assign_launch<double>(h, st, L, d_lines0, n0, d_lines1, n1, d_H, B, d_count0, d_count1, thres_reprojected, thres_angdiff,
                                   min_overlap_ratio, pad, d_assign, d_lmatches, M, d_found, d_match_dir, d_overlap_dir, d_proj0,
                                   d_proj1, (char*)d_ws);
+}
+
+// =============================================================================================
+// the Adam step and the gradient norm over a table of tensors (lt_adam.h)
+// =============================================================================================
+
+namespace {
+constexpr int AD_MAX_TENSORS = 65536;
+constexpr int64_t AD_MAX_CHUNKS = (int64_t)1 << 30;      // one block a chunk: the grid, and gn_final_kernel's int run bounds
+// chunks of any table of n_tensors tensors with n_total elements in all, at most
+int64_t ad_chunk_bound(int n_tensors, int64_t n_total) { return n_total / AD_CHUNK + n_tensors; }
+bool ad_dims_ok(int n_tensors, int64_t n_total) {
+  return n_tensors >= 1 && n_tensors <= AD_MAX_TENSORS && n_total >= 0 && n_total / AD_CHUNK <= AD_MAX_CHUNKS - AD_MAX_TENSORS;
+}
+// workspace: the table | the chunk prefix [n_tensors + 1] | (the norm alone) one float64 a chunk
+struct AdamWsLayout { int64_t o_table, o_prefix, o_partial, total; };
+AdamWsLayout adam_ws_layout(int n_tensors, int64_t partials) {
+  AdamWsLayout L{};
+  Carve c;
+  L.o_table = c.take((int64_t)n_tensors * (int64_t)sizeof(LinetrAdamTensor));
+  L.o_prefix = c.take(((int64_t)n_tensors + 1) * 4);
+  L.o_partial = c.take(partials * 8);
+  L.total = c.o + 256;
+  return L;
+}
+
+// The refusals both entry points share, for `who`, every one before the first launch; `all`: the step reads p, g, m and v, the norm g
+// alone.  Leaves the table's chunk count in *chunks.
+int adam_table_check(const char* who, const LinetrAdamTensor* tab, int n_tensors, bool all, int64_t* chunks) {
+  if (!tab) return fail(LINETR_E_ARG, "%s: null table", who);
+  if (n_tensors < 1 || n_tensors > AD_MAX_TENSORS) return fail(LINETR_E_ARG, "%s: %d tensors (1 .. %d)", who, n_tensors, AD_MAX_TENSORS);
+  int64_t total = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    const LinetrAdamTensor& e = tab[t];
+    if (e.n < 0) return fail(LINETR_E_ARG, "%s: tensor %d has n = %lld", who, t, (long long)e.n);
+    if (e.n == 0) continue;
+    const void* ptrs[4] = {e.g, e.p, e.m, e.v};
+    const int used = all ? 4 : 1;
+    for (int i = 0; i < used; ++i) {
+      if (!ptrs[i] || !aligned4(ptrs[i])) return fail(LINETR_E_ARG, "%s: tensor %d has a NULL or misaligned pointer (4-byte alignment)", who, t);
+      for (int j = 0; j < i; ++j)
+        if (ptrs[i] == ptrs[j]) return fail(LINETR_E_ARG, "%s: two of tensor %d's pointers are equal", who, t);
+    }
+    if (all && !std::isfinite(e.step_size)) return fail(LINETR_E_ARG, "%s: tensor %d has step_size %g (finite)", who, t, e.step_size);
+    if (all && !(e.bc2_sqrt > 0.f && e.bc2_sqrt <= 1.f)) return fail(LINETR_E_ARG, "%s: tensor %d has bc2_sqrt %g (0 < . <= 1)", who, t, e.bc2_sqrt);
+    total += (e.n + AD_CHUNK - 1) / AD_CHUNK;
+    if (total > AD_MAX_CHUNKS) return fail(LINETR_E_ARG, "%s: more than 2^30 chunks of %d elements", who, AD_CHUNK);
+  }
+  *chunks = total;
+  return LINETR_OK;
+}
+int adam_ws_check(const char* who, const void* d_ws, int64_t ws_bytes, int64_t need) {
+  if (!d_ws || ((uintptr_t)d_ws & 255)) return fail(LINETR_E_ARG, "%s: the workspace is NULL or not 256-byte aligned", who);
+  if (ws_bytes < need) return fail(LINETR_E_ARG, "%s: workspace too small (need %lld)", who, (long long)need);
+  return LINETR_OK;
+}
+// the table and its chunk prefix into the workspace, AD_PIECE entries a launch, through the kernel arguments (lt_adam.h)
+int adam_table_upload(hipStream_t st, const LinetrAdamTensor* tab, int n_tensors, LinetrAdamTensor* d_table, int32_t* d_prefix) {
+  AdamTablePiece piece;
+  int32_t at = 0;
+  for (int first = 0; first < n_tensors; first += AD_PIECE) {
+    const int count = std::min(AD_PIECE, n_tensors - first);
+    for (int i = 0; i < count; ++i) {
+      piece.entry[i] = tab[first + i];
+      piece.prefix[i] = at;
+      at += (int32_t)((tab[first + i].n + AD_CHUNK - 1) / AD_CHUNK);
+    }
+    piece.prefix[count] = at;
+    hipLaunchKernelGGL(ad_table_kernel, dim3(1), dim3(AD_PIECE), 0, st, piece, first, count, (int)(first + count == n_tensors), d_table, d_prefix);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int64_t linetr_adam_workspace_bytes(int32_t n_tensors, int64_t n_total) {
+  return ad_dims_ok(n_tensors, n_total) ? adam_ws_layout(n_tensors, 0).total : 0;
+}
+
+extern "C" int64_t linetr_grad_norm_workspace_bytes(int32_t n_tensors, int64_t n_total) {
+  return ad_dims_ok(n_tensors, n_total) ? adam_ws_layout(n_tensors, ad_chunk_bound(n_tensors, n_total)).total : 0;
+}
+
+extern "C" int linetr_adam_step(LinetrHandle* h, const LinetrAdamTensor* h_table, int32_t n_tensors, const LinetrAdamHyper* hyper,
+                                const float* d_grad_scale, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  int64_t chunks = 0;
+  if (int e = adam_table_check("adam_step", h_table, n_tensors, true, &chunks)) return e;
+  if (!hyper) return fail(LINETR_E_ARG, "adam_step: null hyper-parameters");
+  if (!(hyper->beta1 >= 0.0 && hyper->beta1 < 1.0) || !(hyper->beta2 >= 0.0 && hyper->beta2 < 1.0))
+    return fail(LINETR_E_ARG, "adam_step: betas %g / %g (0 <= beta < 1)", hyper->beta1, hyper->beta2);
+  if (!(hyper->eps >= 0.0) || !std::isfinite(hyper->eps) || !(hyper->weight_decay >= 0.0) || !std::isfinite(hyper->weight_decay))
+    return fail(LINETR_E_ARG, "adam_step: eps %g, weight_decay %g (finite, not negative)", hyper->eps, hyper->weight_decay);
+  if (hyper->decoupled != 0 && hyper->decoupled != 1) return fail(LINETR_E_ARG, "adam_step: decoupled %d (0 or 1)", hyper->decoupled);
+  if (hyper->decoupled && !std::isfinite(hyper->lr)) return fail(LINETR_E_ARG, "adam_step: lr %g (decoupled weight decay multiplies by 1 - lr wd)", hyper->lr);
+  if (!aligned4(d_grad_scale)) return fail(LINETR_E_ARG, "adam_step: misaligned grad scale");
+  if (int e = adam_ws_check("adam_step", d_ws, ws_bytes, adam_ws_layout(n_tensors, 0).total)) return e;
+  if (chunks == 0) return LINETR_OK;
+  AdamK k{};
+  k.b1c = (float)(1.0 - hyper->beta1);
+  k.b2c = (float)(1.0 - hyper->beta2);
+  k.b2 = (float)hyper->beta2;
+  k.eps = (float)hyper->eps;
+  k.wd = (float)hyper->weight_decay;
+  k.decay = (float)(1.0 - hyper->lr * hyper->weight_decay);
+  k.mode = hyper->weight_decay != 0.0 ? (hyper->decoupled ? 2 : 1) : 0;
+  const AdamWsLayout W = adam_ws_layout(n_tensors, 0);
+  LinetrAdamTensor* d_table = (LinetrAdamTensor*)((char*)d_ws + W.o_table);
+  int32_t* d_prefix = (int32_t*)((char*)d_ws + W.o_prefix);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  if (int e = adam_table_upload(st, h_table, n_tensors, d_table, d_prefix)) return e;
+  ProfScope ps(h, st, "adam_step", 0, 28.0 * AD_CHUNK * (double)chunks);
+  hipLaunchKernelGGL(ad_step_kernel, dim3((unsigned)chunks), dim3(AD_THREADS), 0, st, (const LinetrAdamTensor*)d_table, (const int32_t*)d_prefix,
+                     (int)n_tensors, k, d_grad_scale);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_grad_norm(LinetrHandle* h, const LinetrAdamTensor* h_table, int32_t n_tensors, double max_norm, double* d_norm,
+                                float* d_scale, void* d_ws, int64_t ws_bytes, void* stream) {
+  int64_t chunks = 0;
+  if (int e = adam_table_check("grad_norm", h_table, n_tensors, false, &chunks)) return e;
+  if (!(max_norm >= 0.0)) return fail(LINETR_E_ARG, "grad_norm: max_norm %g (not negative; +inf for the norm alone)", max_norm);
+  if (!d_norm || !d_scale || ((uintptr_t)d_norm & 7) || !aligned4(d_scale)) return fail(LINETR_E_ARG, "grad_norm: NULL or misaligned d_norm / d_scale");
+  if (int e = adam_ws_check("grad_norm", d_ws, ws_bytes, adam_ws_layout(n_tensors, chunks).total)) return e;
+  const AdamWsLayout W = adam_ws_layout(n_tensors, chunks);
+  LinetrAdamTensor* d_table = (LinetrAdamTensor*)((char*)d_ws + W.o_table);
+  int32_t* d_prefix = (int32_t*)((char*)d_ws + W.o_prefix);
+  double* partial = (double*)((char*)d_ws + W.o_partial);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  if (chunks > 0) {
+    if (int e = adam_table_upload(st, h_table, n_tensors, d_table, d_prefix)) return e;
+    ProfScope ps(h, st, "grad_norm_partial", 0, 4.0 * AD_CHUNK * (double)chunks);
+    hipLaunchKernelGGL(gn_partial_kernel, dim3((unsigned)chunks), dim3(AD_THREADS), 0, st, (const LinetrAdamTensor*)d_table,
+                       (const int32_t*)d_prefix, (int)n_tensors, partial);
+    LT_LAUNCH_CHECK();
+  }
+  ProfScope ps(h, st, "grad_norm_final", 0, 8.0 * (double)chunks);      // (no element at all: norm 0, scale 1)
+  hipLaunchKernelGGL(gn_final_kernel, dim3(1), dim3(AD_THREADS), 0, st, (const double*)partial, (int)chunks, max_norm, d_norm, d_scale);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
 }

@@ -559,6 +559,61 @@ class _TrainSurface:
         self._call("linetr_token_assemble_backward", g.data_ptr(), L, S, ptr(dtok), ptr(dcls), ws.data_ptr(), ws.numel())
         return dtok, dcls
 
+    # ------------------------------------------------------------------ the optimizer step and the gradient norm (csrc/lt_adam.h)
+    def _adam_table(self, who, grads, rest=None):
+        """The host table (nat.ADAM_TENSOR_DTYPE records) of `grads` and, for the step, of `rest` = (params, exp_avgs, exp_avg_sqs):
+        contiguous float32 tensors on the engine's device, every one of a row the size of its gradient.  Returns (table, n_total)."""
+        lists = [list(grads)] + ([list(r) for r in rest] if rest is not None else [])
+        if not lists[0] or any(len(l) != len(lists[0]) for l in lists):
+            raise ValueError(f"{who}: the tensor lists must be non-empty and equally long")
+        table = np.zeros(len(lists[0]), dtype=nat.ADAM_TENSOR_DTYPE)
+        sizes = [t.numel() for t in lists[0]]
+        dev, f32, strided = self.device, torch.float32, torch.strided
+        for name, column in zip(("g", "p", "m", "v"), lists):
+            for t in column:                                 # (the host cost of a step is this loop: 4 x 153 tensors for the model)
+                if t.dtype is not f32 or t.device != dev or t.layout is not strided or not t.is_contiguous():
+                    raise ValueError(f"{who}: every tensor must be a contiguous float32 tensor on {self.device}")
+            table[name] = [t.data_ptr() for t in column]
+            if name != "g" and [t.numel() for t in column] != sizes:
+                raise ValueError(f"{who}: a parameter, its gradient and its two moments must hold equally many elements")
+        table["n"] = sizes
+        return table, sum(sizes)
+
+    def adam_step(self, params, grads, exp_avgs, exp_avg_sqs, steps, *, lr, betas, eps, weight_decay, decoupled=False, grad_scale=None):
+        """One Adam step over every tensor of the lists in ONE native call (linetr_adam_step), the functional form, like
+        torch.optim._functional.adam: params, exp_avgs and exp_avg_sqs are updated in place in the arithmetic of torch's single-tensor path
+        (include/linetr_hip.h); grads are only read.  `steps`: the step count of each parameter AFTER this step (Python numbers; the bias
+        corrections are made here in double, per tensor).  `grad_scale`: a one-element float32 device tensor every gradient is multiplied
+        by on the way in (grad_norm's scale), read on the device.  The tensors are written through raw pointers: their autograd version
+        counters do not move (linetr_amd.optim.Adam moves them).  No host wait."""
+        table, n_total = self._adam_table("adam_step", grads, (params, exp_avgs, exp_avg_sqs))
+        steps = list(steps)
+        if len(steps) != len(table):
+            raise ValueError("adam_step: one step count per parameter")
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("adam_step: a tensor lr is not supported")
+        corr = [nat.adam_bias_corrections(lr, betas[0], betas[1], s) for s in steps]
+        table["step_size"] = [c[0] for c in corr]
+        table["bc2_sqrt"] = [c[1] for c in corr]
+        hyper = nat.AdamHyper(float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(lr), int(bool(decoupled)))
+        if grad_scale is not None:
+            if grad_scale.device != self.device or grad_scale.dtype != torch.float32 or grad_scale.numel() != 1:
+                raise ValueError(f"adam_step: grad_scale must be a one-element float32 tensor on {self.device}")
+        ws = self._stream_workspace("adam_step", self._L.linetr_adam_workspace_bytes(len(table), n_total))
+        self._call("linetr_adam_step", table.ctypes.data, len(table), C.byref(hyper), ptr(grad_scale), ws.data_ptr(), ws.numel())
+
+    def grad_norm(self, grads, max_norm=float("inf")):
+        """The L2 norm of all `grads` together and the coefficient of torch.nn.utils.clip_grad_norm_ (linetr_grad_norm): (norm: a float64
+        scalar tensor, scale: a float32 one-element tensor = min(1, max_norm / (norm + 1e-6))), both on the device.  Deterministic: float64
+        sums in a fixed order.  No host wait."""
+        table, n_total = self._adam_table("grad_norm", grads)
+        with torch.cuda.device(self.device):
+            norm = torch.empty((), dtype=torch.float64, device=self.device)
+            scale = torch.empty((1,), dtype=torch.float32, device=self.device)
+        ws = self._stream_workspace("grad_norm", self._L.linetr_grad_norm_workspace_bytes(len(table), n_total))
+        self._call("linetr_grad_norm", table.ctypes.data, len(table), float(max_norm), norm.data_ptr(), scale.data_ptr(), ws.data_ptr(), ws.numel())
+        return norm, scale
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes

@@ -57,7 +57,12 @@ CLS rows (which feed the query, the tokens and the residual); the rest is native
 
 With these the training surface is complete: every layer of the model the reference's train.py trains has a native backward.  In the
 encoders and their glue torch makes the key-line normalisation, the mid-point, the concatenation of the 3 / 5 input columns, the reshapes
-(no gradient flows there) and the final add klines_pos + cls_out^T."""
+(no gradient flows there) and the final add klines_pos + cls_out^T.
+
+The line behind loss.backward() is native too: linetr_amd.optim.Adam (optim.py; csrc/lt_adam.h) steps all 153 parameters in one launch, in
+the arithmetic of torch.optim.Adam's single-tensor path.  What torch still does in optimizer.step(): it keeps the 153 step counters (0-d
+float32 CPU tensors, as in torch's state_dict) and adds 1 to each, makes a non-contiguous .grad contiguous, allocates the two moments of
+a parameter at its first step, and bumps the parameters' version counters; zero_grad() is torch's."""
 from __future__ import annotations
 
 from typing import NamedTuple
