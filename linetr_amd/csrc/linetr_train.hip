@@ -1,9 +1,14 @@
-// liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h): the validation step (lt_valstep.h),
-// the criterion's gradient (lt_lossgrad.h), the backward of the 1x1 layers and the descriptor head (lt_linbwd.h), the neighbour-line
-// attention's forward with statistics and backward (lt_attnbwd.h), BatchNorm on batch statistics with its backward (lt_bnbwd.h), the
-// descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards (lt_descbwd.h) and their dropout siblings (lt_dropout.h), the positional encoders' input layer and
-// the token assembly with their backwards (lt_posbwd.h), the ground-truth line assignment in front of them (lt_gtassign.h) and the
-// optimizer step behind them, with the gradient norm that can feed it (lt_adam.h).
+// liblinetr_hip.so, translation unit 4 of 4: training and evaluation (C ABI in include/linetr_hip.h).
+//   lt_valstep.h    the validation step
+//   lt_lossgrad.h   the criterion's gradient
+//   lt_linbwd.h     the backward of the 1x1 layers and the descriptor head
+//   lt_attnbwd.h    the neighbour-line attention's forward with statistics and its backward
+//   lt_bnbwd.h      BatchNorm on batch statistics with its backward
+//   lt_descbwd.h    the descriptive layer's CLS token pooling, LayerNorm and GELU with their backwards
+//   lt_dropout.h    the dropout instances of that pooling and LayerNorm
+//   lt_posbwd.h     the positional encoders' input layer and the token assembly with their backwards
+//   lt_gtassign.h   the ground-truth line assignment in front of them
+//   lt_adam.h       the optimizer step behind them, with the gradient norm that can feed it
 #include <algorithm>
 
 #include "lt_handle.h"
@@ -619,129 +624,82 @@ extern "C" int64_t linetr_layer_norm_backward_workspace_bytes(int64_t rows, int3
   return C == D && rows >= 0 && rows <= LN_MAX_ROWS ? align_up(ln_chunks(rows) * 2 * D * 4, 256) + 256 : 0;
 }
 
-extern "C" int linetr_cls_pool_train_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
-                                             float* d_pooled, float* d_lse, void* stream) {
-  if (int e = cp_fwd_check("cls_pool_train_forward", d_x, ldx, d_u, ldu, L, S, d_pooled, d_lse)) return e;
-  if (L == 0) return LINETR_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (h) LT_HIP(hipSetDevice(h->device));
-  ProfScope ps(h, st, "cls_pool_train_fwd", 2.0 * HEADS * 2.0 * L * S * D, 4.0 * L * ((double)S * D + 2.0 * HEADS * D + HEADS));
-  hipLaunchKernelGGL(cp_fwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, L, (int)S, d_pooled, d_lse);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
-}
-
-extern "C" int linetr_cls_pool_train_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
-                                              const float* d_lse, const float* d_dpooled, int64_t L, int32_t S, float* d_dx, int64_t lddx,
-                                              float* d_du, int64_t lddu, void* stream) {
-  if (int e = cp_bwd_check("cls_pool_train_backward", d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L, S, d_dx, lddx, d_du, lddu)) return e;
-  if (L == 0 || (!d_dx && !d_du)) return LINETR_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (h) LT_HIP(hipSetDevice(h->device));
-  ProfScope ps(h, st, "cls_pool_train_bwd", 2.0 * HEADS * 4.0 * L * S * D, 4.0 * L * ((d_dx ? 2.0 : 1.0) * S * D + 4.0 * HEADS * D + HEADS));
-  hipLaunchKernelGGL(cp_bwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L,
-                     (int)S, d_dx, lddx, d_du, lddu);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
-}
-
-extern "C" int linetr_layer_norm_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
-                                         const float* d_beta, float eps, int64_t rows, int32_t C, float* d_y, int64_t ldy, float* d_stats,
-                                         void* stream) {
-  if (int e = ln_fwd_check("layer_norm_forward", d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, C, d_y, ldy, d_stats)) return e;
-  if (rows == 0) return LINETR_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (h) LT_HIP(hipSetDevice(h->device));
-  ProfScope ps(h, st, "layer_norm_fwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2));
-  hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(256), 0, st, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows,
-                     d_y, ldy, d_stats);
-  LT_LAUNCH_CHECK();
-  return LINETR_OK;
-}
-
-extern "C" int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
-                                          const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dx,
-                                          int64_t lddx, float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
-  if (int e = ln_bwd_check("layer_norm_backward", d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, C, d_dx, lddx, nullptr, 0, d_dgamma, d_dbeta,
-                           d_ws, ws_bytes)) return e;
-  const bool sums = d_dgamma || d_dbeta;
-  if (!d_dx && !sums) return LINETR_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (h) LT_HIP(hipSetDevice(h->device));
-  const int chunks = (int)ln_chunks(rows);
-  float* partial = sums ? (float*)d_ws : nullptr;
-  if (rows > 0) {
-    ProfScope ps(h, st, "layer_norm_bwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2 + (d_dx ? D : 0)));
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, d_dx, lddx, partial);
-    LT_LAUNCH_CHECK();
-  }
-  return sums ? ln_reduce(h, st, partial, chunks, d_dgamma, d_dbeta) : LINETR_OK;
-}
-
-// ---- the same four with training-time dropout (lt_dropout.h) ----
-
-extern "C" int linetr_cls_pool_dropout_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
-                                               const LinetrDropout* drop, float* d_pooled, float* d_kept, float* d_lse, void* stream) {
-  const char* who = "cls_pool_dropout_forward";
+namespace {
+// The pooling and the LayerNorm, forward and backward: one call each behind its plain entry point (`dropout` false: drop, site, d_kept,
+// d_dkept and the second data gradient are not looked at) and its dropout one (lt_dropout.h).
+int cp_fwd_call(const char* who, LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int S, bool dropout,
+                const LinetrDropout* drop, float* d_pooled, float* d_kept, float* d_lse, void* stream) {
   if (int e = cp_fwd_check(who, d_x, ldx, d_u, ldu, L, S, d_pooled, d_lse)) return e;
-  if (!d_kept || !aligned16(d_kept)) return fail(LINETR_E_ARG, "%s: kept must be a 16-byte aligned [L][4] tensor", who);
-  DropArgs dr;
-  if (int e = drop_args(who, drop, 0, &dr)) return e;
+  DropArgs dr{};
+  if (dropout) {
+    if (!d_kept || !aligned16(d_kept)) return fail(LINETR_E_ARG, "%s: kept must be a 16-byte aligned [L][4] tensor", who);
+    if (int e = drop_args(who, drop, 0, &dr)) return e;
+  }
   if (L == 0) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  ProfScope ps(h, st, "cls_pool_dropout_fwd", 2.0 * HEADS * 2.0 * L * S * D, 4.0 * L * ((double)S * D + 2.0 * HEADS * D + 2 * HEADS));
-  hipLaunchKernelGGL(cp_drop_fwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, L, (int)S, dr, d_pooled,
-                     d_kept, d_lse);
+  ProfScope ps(h, st, dropout ? "cls_pool_dropout_fwd" : "cls_pool_train_fwd", 2.0 * HEADS * 2.0 * L * S * D,
+               4.0 * L * ((double)S * D + 2.0 * HEADS * D + (dropout ? 2 : 1) * HEADS));
+  const dim3 grid((unsigned)((L + CP_SEGS - 1) / CP_SEGS));
+  if (dropout) hipLaunchKernelGGL(cp_drop_fwd_kernel, grid, dim3(256), 0, st, d_x, ldx, d_u, ldu, L, S, dr, d_pooled, d_kept, d_lse);
+  else hipLaunchKernelGGL(cp_fwd_kernel, grid, dim3(256), 0, st, d_x, ldx, d_u, ldu, L, S, d_pooled, d_lse);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
 
-extern "C" int linetr_cls_pool_dropout_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
-                                                const float* d_lse, const float* d_kept, const float* d_dpooled, const float* d_dkept, int64_t L,
-                                                int32_t S, const LinetrDropout* drop, float* d_dx, int64_t lddx, float* d_du, int64_t lddu,
-                                                void* stream) {
-  const char* who = "cls_pool_dropout_backward";
+int cp_bwd_call(const char* who, LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                const float* d_lse, const float* d_kept, const float* d_dpooled, const float* d_dkept, int64_t L, int S, bool dropout,
+                const LinetrDropout* drop, float* d_dx, int64_t lddx, float* d_du, int64_t lddu, void* stream) {
   if (int e = cp_bwd_check(who, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L, S, d_dx, lddx, d_du, lddu)) return e;
-  if (!d_kept || !aligned16(d_kept) || !aligned16(d_dkept)) return fail(LINETR_E_ARG, "%s: kept and dkept must be 16-byte aligned [L][4] tensors (dkept may be null)", who);
-  DropArgs dr;
-  if (int e = drop_args(who, drop, 0, &dr)) return e;
+  DropArgs dr{};
+  if (dropout) {
+    if (!d_kept || !aligned16(d_kept) || !aligned16(d_dkept))
+      return fail(LINETR_E_ARG, "%s: kept and dkept must be 16-byte aligned [L][4] tensors (dkept may be null)", who);
+    if (int e = drop_args(who, drop, 0, &dr)) return e;
+  }
   if (L == 0 || (!d_dx && !d_du)) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  ProfScope ps(h, st, "cls_pool_dropout_bwd", 2.0 * HEADS * 4.0 * L * S * D, 4.0 * L * ((d_dx ? 2.0 : 1.0) * S * D + 4.0 * HEADS * D + 3 * HEADS));
-  hipLaunchKernelGGL(cp_drop_bwd_kernel, dim3((unsigned)((L + CP_SEGS - 1) / CP_SEGS)), dim3(256), 0, st, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_kept,
-                     d_dpooled, d_dkept, L, (int)S, dr, d_dx, lddx, d_du, lddu);
+  ProfScope ps(h, st, dropout ? "cls_pool_dropout_bwd" : "cls_pool_train_bwd", 2.0 * HEADS * 4.0 * L * S * D,
+               4.0 * L * ((d_dx ? 2.0 : 1.0) * S * D + 4.0 * HEADS * D + (dropout ? 3 : 1) * HEADS));
+  const dim3 grid((unsigned)((L + CP_SEGS - 1) / CP_SEGS));
+  if (dropout)
+    hipLaunchKernelGGL(cp_drop_bwd_kernel, grid, dim3(256), 0, st, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_kept, d_dpooled, d_dkept, L, S, dr, d_dx,
+                       lddx, d_du, lddu);
+  else hipLaunchKernelGGL(cp_bwd_kernel, grid, dim3(256), 0, st, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_dpooled, L, S, d_dx, lddx, d_du, lddu);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
 
-extern "C" int linetr_layer_norm_dropout_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
-                                                 const float* d_beta, float eps, int64_t rows, int32_t C, const LinetrDropout* drop, int32_t site,
-                                                 float* d_y, int64_t ldy, float* d_stats, void* stream) {
-  const char* who = "layer_norm_dropout_forward";
+int ln_fwd_call(const char* who, LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                const float* d_beta, float eps, int64_t rows, int C, bool dropout, const LinetrDropout* drop, int site, float* d_y, int64_t ldy,
+                float* d_stats, void* stream) {
   if (int e = ln_fwd_check(who, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, C, d_y, ldy, d_stats)) return e;
-  DropArgs dr;
-  if (int e = drop_args(who, drop, site, &dr)) return e;
+  DropArgs dr{};
+  if (dropout)
+    if (int e = drop_args(who, drop, site, &dr)) return e;
   if (rows == 0) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  ProfScope ps(h, st, "layer_norm_dropout_fwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2));
-  hipLaunchKernelGGL(ln_drop_fwd_kernel, dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(256), 0, st, d_a, lda, d_r, ldr, d_gamma, d_beta, eps,
-                     rows, dr, (uint32_t)site, d_y, ldy, d_stats);
+  ProfScope ps(h, st, dropout ? "layer_norm_dropout_fwd" : "layer_norm_fwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2));
+  const dim3 grid((unsigned)((rows + LN_ROWS - 1) / LN_ROWS));
+  if (dropout)
+    hipLaunchKernelGGL(ln_drop_fwd_kernel, grid, dim3(256), 0, st, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, dr, (uint32_t)site, d_y, ldy,
+                       d_stats);
+  else hipLaunchKernelGGL(ln_fwd_kernel, grid, dim3(256), 0, st, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, d_y, ldy, d_stats);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
 
-extern "C" int linetr_layer_norm_dropout_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
-                                                  const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C,
-                                                  const LinetrDropout* drop, int32_t site, float* d_da, int64_t ldda, float* d_dr, int64_t lddr,
-                                                  float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
-  const char* who = "layer_norm_dropout_backward";
+// (d_dr: the gradient of v = a + residual, the plain backward's one data gradient; d_da: that of a under dropout, r dv)
+int ln_bwd_call(const char* who, LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int C, bool dropout, const LinetrDropout* drop, int site,
+                float* d_da, int64_t ldda, float* d_dr, int64_t lddr, float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
   if (int e = ln_bwd_check(who, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, C, d_da, ldda, d_dr, lddr, d_dgamma, d_dbeta, d_ws, ws_bytes))
     return e;
-  DropArgs dr;
-  if (int e = drop_args(who, drop, site, &dr)) return e;
+  DropArgs dr{};
+  if (dropout)
+    if (int e = drop_args(who, drop, site, &dr)) return e;
   const bool sums = d_dgamma || d_dbeta;
   if (!d_da && !d_dr && !sums) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -749,12 +707,70 @@ extern "C" int linetr_layer_norm_dropout_backward(LinetrHandle* h, const float* 
   const int chunks = (int)ln_chunks(rows);
   float* partial = sums ? (float*)d_ws : nullptr;
   if (rows > 0) {
-    ProfScope ps(h, st, "layer_norm_dropout_bwd", 0, 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2 + (d_da ? D : 0) + (d_dr ? D : 0)));
-    hipLaunchKernelGGL(ln_drop_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, dr,
-                       (uint32_t)site, d_da, ldda, d_dr, lddr, partial);
+    ProfScope ps(h, st, dropout ? "layer_norm_dropout_bwd" : "layer_norm_bwd", 0,
+                 4.0 * rows * ((d_r ? 3.0 : 2.0) * D + 2 + (d_da ? D : 0) + (d_dr ? D : 0)));
+    if (dropout)
+      hipLaunchKernelGGL(ln_drop_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, dr,
+                         (uint32_t)site, d_da, ldda, d_dr, lddr, partial);
+    else
+      hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, d_dr, lddr,
+                         partial);
     LT_LAUNCH_CHECK();
   }
   return sums ? ln_reduce(h, st, partial, chunks, d_dgamma, d_dbeta) : LINETR_OK;
+}
+}  // namespace
+
+extern "C" int linetr_cls_pool_train_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
+                                             float* d_pooled, float* d_lse, void* stream) {
+  return cp_fwd_call("cls_pool_train_forward", h, d_x, ldx, d_u, ldu, L, S, false, nullptr, d_pooled, nullptr, d_lse, stream);
+}
+
+extern "C" int linetr_cls_pool_train_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                                              const float* d_lse, const float* d_dpooled, int64_t L, int32_t S, float* d_dx, int64_t lddx,
+                                              float* d_du, int64_t lddu, void* stream) {
+  return cp_bwd_call("cls_pool_train_backward", h, d_x, ldx, d_u, ldu, d_pooled, d_lse, nullptr, d_dpooled, nullptr, L, S, false, nullptr, d_dx,
+                     lddx, d_du, lddu, stream);
+}
+
+extern "C" int linetr_layer_norm_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                                         const float* d_beta, float eps, int64_t rows, int32_t C, float* d_y, int64_t ldy, float* d_stats,
+                                         void* stream) {
+  return ln_fwd_call("layer_norm_forward", h, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, C, false, nullptr, 0, d_y, ldy, d_stats, stream);
+}
+
+extern "C" int linetr_layer_norm_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                                          const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C, float* d_dx,
+                                          int64_t lddx, float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
+  return ln_bwd_call("layer_norm_backward", h, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, C, false, nullptr, 0, nullptr, 0, d_dx, lddx,
+                     d_dgamma, d_dbeta, d_ws, ws_bytes, stream);
+}
+
+extern "C" int linetr_cls_pool_dropout_forward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, int64_t L, int32_t S,
+                                               const LinetrDropout* drop, float* d_pooled, float* d_kept, float* d_lse, void* stream) {
+  return cp_fwd_call("cls_pool_dropout_forward", h, d_x, ldx, d_u, ldu, L, S, true, drop, d_pooled, d_kept, d_lse, stream);
+}
+
+extern "C" int linetr_cls_pool_dropout_backward(LinetrHandle* h, const float* d_x, int64_t ldx, const float* d_u, int64_t ldu, const float* d_pooled,
+                                                const float* d_lse, const float* d_kept, const float* d_dpooled, const float* d_dkept, int64_t L,
+                                                int32_t S, const LinetrDropout* drop, float* d_dx, int64_t lddx, float* d_du, int64_t lddu,
+                                                void* stream) {
+  return cp_bwd_call("cls_pool_dropout_backward", h, d_x, ldx, d_u, ldu, d_pooled, d_lse, d_kept, d_dpooled, d_dkept, L, S, true, drop, d_dx, lddx,
+                     d_du, lddu, stream);
+}
+
+extern "C" int linetr_layer_norm_dropout_forward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_gamma,
+                                                 const float* d_beta, float eps, int64_t rows, int32_t C, const LinetrDropout* drop, int32_t site,
+                                                 float* d_y, int64_t ldy, float* d_stats, void* stream) {
+  return ln_fwd_call("layer_norm_dropout_forward", h, d_a, lda, d_r, ldr, d_gamma, d_beta, eps, rows, C, true, drop, site, d_y, ldy, d_stats, stream);
+}
+
+extern "C" int linetr_layer_norm_dropout_backward(LinetrHandle* h, const float* d_a, int64_t lda, const float* d_r, int64_t ldr, const float* d_stats,
+                                                  const float* d_gamma, const float* d_g, int64_t ldg, int64_t rows, int32_t C,
+                                                  const LinetrDropout* drop, int32_t site, float* d_da, int64_t ldda, float* d_dr, int64_t lddr,
+                                                  float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
+  return ln_bwd_call("layer_norm_dropout_backward", h, d_a, lda, d_r, ldr, d_stats, d_gamma, d_g, ldg, rows, C, true, drop, site, d_da, ldda, d_dr,
+                     lddr, d_dgamma, d_dbeta, d_ws, ws_bytes, stream);
 }
 
 extern "C" int linetr_dropout_factors(LinetrHandle* h, const LinetrDropout* drop, int32_t site, int64_t rows, int64_t inner, float* d_out, void* stream) {

@@ -316,34 +316,54 @@ class _TrainSurface:
             raise ValueError(f"u must be [{L}, 4, {D}], got {tuple(u.shape)}")
         return self._f32(x.detach()).view(L * S, D), self._f32(u.detach()).view(L, 4 * D), L, S
 
+    def _cls_pool_fwd(self, x, u, drop=None):
+        """cls_pool_forward (`drop` None: kept is None) and cls_pool_dropout_forward: (pooled, kept, lse)"""
+        xr, ur, L, S = self._pool_args(x, u)
+        pooled = torch.empty((L, 4, D), dtype=torch.float32, device=self.device)
+        lse = torch.empty((L, 4), dtype=torch.float32, device=self.device)
+        kept = torch.empty_like(lse) if drop is not None else None
+        if L == 0:                                   # (an empty tensor has no address to hand over)
+            return pooled, kept, lse
+        if drop is None:
+            self._call("linetr_cls_pool_train_forward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, L, S, pooled.data_ptr(), lse.data_ptr())
+        else:
+            self._call("linetr_cls_pool_dropout_forward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, L, S, C.byref(drop), pooled.data_ptr(),
+                       kept.data_ptr(), lse.data_ptr())
+        return pooled, kept, lse
+
+    def _cls_pool_bwd(self, x, u, pooled, lse, grad_pooled, need, drop=None, kept=None, grad_kept=None):
+        """cls_pool_backward (`drop` None) and cls_pool_dropout_backward: (dx, du)"""
+        xr, ur, L, S = self._pool_args(x, u)
+        pr = self._rows_of(pooled.detach().reshape(L, 4 * D), (L, 4 * D), "pooled", strided=False)
+        gr = self._rows_of(grad_pooled.detach().reshape(L, 4 * D), (L, 4 * D), "grad_pooled", strided=False)
+        ls = self._rows_of(lse.detach(), (L, 4), "lse", strided=False)
+        if drop is not None:
+            kp = self._rows_of(kept.detach(), (L, 4), "kept", strided=False)
+            gk = self._rows_of(grad_kept.detach(), (L, 4), "grad_kept", strided=False) if grad_kept is not None else None
+        dx = torch.empty((L, S, D), dtype=torch.float32, device=self.device) if need[0] else None
+        du = torch.empty((L, 4, D), dtype=torch.float32, device=self.device) if need[1] else None
+        if L == 0:
+            return dx, du
+        if drop is None:
+            self._call("linetr_cls_pool_train_backward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, pr.data_ptr(), ls.data_ptr(), gr.data_ptr(), L, S,
+                       ptr(dx), D, ptr(du), 4 * D)
+        else:
+            self._call("linetr_cls_pool_dropout_backward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, pr.data_ptr(), ls.data_ptr(), kp.data_ptr(),
+                       gr.data_ptr(), ptr(gk), L, S, C.byref(drop), ptr(dx), D, ptr(du), 4 * D)
+        return dx, du
+
     def cls_pool_forward(self, x, u):
         """The CLS row's attention pooling of the descriptive layer in its folded form (linetr_cls_pool_train_forward): per segment l and
         head h, p = softmax_t(u[l, h] . x[l, t]) and pooled[l, h] = sum_t p_t x[l, t].  x [L, S, 256] token rows (slot 0: the CLS token),
         u [L, 4, 256] = Wk_h^T (q_h / 8).  Returns (pooled [L, 4, 256], lse [L, 4]).  No host wait."""
-        xr, ur, L, S = self._pool_args(x, u)
-        pooled = torch.empty((L, 4, D), dtype=torch.float32, device=self.device)
-        lse = torch.empty((L, 4), dtype=torch.float32, device=self.device)
-        if L == 0:                                   # (an empty tensor has no address to hand over)
-            return pooled, lse
-        self._call("linetr_cls_pool_train_forward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, L, S, pooled.data_ptr(), lse.data_ptr())
+        pooled, _, lse = self._cls_pool_fwd(x, u)
         return pooled, lse
 
     def cls_pool_backward(self, x, u, pooled, lse, grad_pooled, need=(True, True)):
         """The pooling's backward (linetr_cls_pool_train_backward): (dx [L, S, 256], du [L, 4, 256]) for the gradient `grad_pooled`
         arriving at pooled; x, u, pooled, lse as cls_pool_forward took and returned them.  p is recomputed from x, u and lse.  `need` =
         which of the two to compute (the other is None).  Deterministic; no host wait."""
-        xr, ur, L, S = self._pool_args(x, u)
-        pr = self._rows_of(pooled.detach().reshape(L, 4 * D), (L, 4 * D), "pooled", strided=False)
-        gr = self._rows_of(grad_pooled.detach().reshape(L, 4 * D), (L, 4 * D), "grad_pooled", strided=False)
-        ls = self._rows_of(lse.detach(), (L, 4), "lse", strided=False)
-        dx = torch.empty((L, S, D), dtype=torch.float32, device=self.device) if need[0] else None
-        du = torch.empty((L, 4, D), dtype=torch.float32, device=self.device) if need[1] else None
-        if L == 0:
-            return dx, du
-        self._call("linetr_cls_pool_train_backward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, pr.data_ptr(), ls.data_ptr(), gr.data_ptr(), L, S,
-                   ptr(dx), D, ptr(du), 4 * D)
-        return dx, du
-
+        return self._cls_pool_bwd(x, u, pooled, lse, grad_pooled, need)
     def _ln_args(self, who, a, residual, gamma):
         if a.dim() != 2 or int(a.shape[1]) != D or int(gamma.numel()) != D:
             raise ValueError(f"{who}: the native LayerNorm is over rows of {D}, got {tuple(a.shape)} and {int(gamma.numel())} weights")
@@ -351,34 +371,45 @@ class _TrainSurface:
         rr = self._rows_of(residual.detach(), a.shape, "residual") if residual is not None else None
         return ar, rr, self._f32(gamma.detach().reshape(-1)), int(ar.shape[0])
 
-    def layer_norm_forward(self, a, residual, gamma, beta, eps=1e-6):
-        """y = LayerNorm(a + residual) gamma + beta over rows of 256 (linetr_layer_norm_forward); a, residual [rows, 256] (rows may be
-        strided; residual may be None), the add one float32 add.  Returns (y [rows, 256], stats [rows, 2] float32: mean | rstd, what
-        layer_norm_backward takes).  No host wait."""
-        ar, rr, gm, rows = self._ln_args("layer_norm_forward", a, residual, gamma)
+    def _ln_fwd(self, who, a, residual, gamma, beta, eps, drop=None, site=None):
+        """layer_norm_forward (`drop` None) and layer_norm_dropout_forward: (y, stats)"""
+        ar, rr, gm, rows = self._ln_args(who, a, residual, gamma)
         y = torch.empty((rows, D), dtype=torch.float32, device=self.device)
         stats = torch.empty((rows, 2), dtype=torch.float32, device=self.device)
         if rows == 0:
             return y, stats
-        self._call("linetr_layer_norm_forward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, gm.data_ptr(),
-                   self._f32(beta.detach().reshape(-1)).data_ptr(), float(eps), rows, D, y.data_ptr(), D, stats.data_ptr())
+        dropout = () if drop is None else (C.byref(drop), int(site))
+        self._call("linetr_" + who, ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, gm.data_ptr(),
+                   self._f32(beta.detach().reshape(-1)).data_ptr(), float(eps), rows, D, *dropout, y.data_ptr(), D, stats.data_ptr())
         return y, stats
+
+    def _ln_bwd(self, who, a, residual, stats, gamma, grad_out, need, drop=None, site=None):
+        """layer_norm_backward (`drop` None: da is None and dresidual is its dx) and layer_norm_dropout_backward:
+        (da, dresidual, dgamma, dbeta); `need` = which of the four"""
+        ar, rr, gm, rows = self._ln_args(who, a, residual, gamma)
+        g = self._rows_of(grad_out.detach(), (rows, D), "grad_out")
+        st = self._rows_of(stats.detach(), (rows, 2), "stats", strided=False)
+        da, dr = (torch.empty((rows, D), dtype=torch.float32, device=self.device) if k else None for k in need[:2])
+        dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=self.device) if k else None for k in need[2:4])
+        if rows == 0:
+            return da, dr, dgamma.zero_() if dgamma is not None else None, dbeta.zero_() if dbeta is not None else None
+        ws = self._stream_workspace("layer_norm_bwd", self._L.linetr_layer_norm_backward_workspace_bytes(rows, D))
+        grads = (ptr(dr), D) if drop is None else (C.byref(drop), int(site), ptr(da), D, ptr(dr), D)
+        self._call("linetr_" + who, ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, st.data_ptr(), gm.data_ptr(),
+                   g.data_ptr(), g.stride(0), rows, D, *grads, ptr(dgamma), ptr(dbeta), ws.data_ptr(), ws.numel())
+        return da, dr, dgamma, dbeta
+
+    def layer_norm_forward(self, a, residual, gamma, beta, eps=1e-6):
+        """y = LayerNorm(a + residual) gamma + beta over rows of 256 (linetr_layer_norm_forward); a, residual [rows, 256] (rows may be
+        strided; residual may be None), the add one float32 add.  Returns (y [rows, 256], stats [rows, 2] float32: mean | rstd, what
+        layer_norm_backward takes).  No host wait."""
+        return self._ln_fwd("layer_norm_forward", a, residual, gamma, beta, eps)
 
     def layer_norm_backward(self, a, residual, stats, gamma, grad_out, need=(True, True, True)):
         """The layer's backward (linetr_layer_norm_backward): (dx, dgamma, dbeta) for the gradient `grad_out` arriving at y; dx [rows, 256]
         is the gradient of a and of the residual alike.  `need` = which of the three to compute (the others are None).  Deterministic;
         no host wait."""
-        ar, rr, gm, rows = self._ln_args("layer_norm_backward", a, residual, gamma)
-        g = self._rows_of(grad_out.detach(), (rows, D), "grad_out")
-        st = self._rows_of(stats.detach(), (rows, 2), "stats", strided=False)
-        dx = torch.empty((rows, D), dtype=torch.float32, device=self.device) if need[0] else None
-        dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=self.device) if k else None for k in need[1:3])
-        if rows == 0:
-            return dx, dgamma.zero_() if dgamma is not None else None, dbeta.zero_() if dbeta is not None else None
-        ws = self._stream_workspace("layer_norm_bwd", self._L.linetr_layer_norm_backward_workspace_bytes(rows, D))
-        self._call("linetr_layer_norm_backward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, st.data_ptr(),
-                   gm.data_ptr(), g.data_ptr(), g.stride(0), rows, D, ptr(dx), D, ptr(dgamma), ptr(dbeta), ws.data_ptr(), ws.numel())
-        return dx, dgamma, dbeta
+        return self._ln_bwd("layer_norm_backward", a, residual, stats, gamma, grad_out, (False, *need))[1:]
 
     # ------------------------------------------------------------------ the same with training-time dropout (csrc/lt_dropout.h)
     @staticmethod
@@ -398,59 +429,24 @@ class _TrainSurface:
     def cls_pool_dropout_forward(self, x, u, drop: nat.Dropout):
         """cls_pool_forward with dropout on the softmax weights (site 0; linetr_cls_pool_dropout_forward): a = p r, pooled = sum_t a_t x_t,
         kept = sum_t a_t.  Returns (pooled [L, 4, 256], kept [L, 4], lse [L, 4]).  No host wait."""
-        xr, ur, L, S = self._pool_args(x, u)
-        pooled = torch.empty((L, 4, D), dtype=torch.float32, device=self.device)
-        kept, lse = (torch.empty((L, 4), dtype=torch.float32, device=self.device) for _ in range(2))
-        if L:
-            self._call("linetr_cls_pool_dropout_forward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, L, S, C.byref(drop), pooled.data_ptr(),
-                       kept.data_ptr(), lse.data_ptr())
-        return pooled, kept, lse
+        return self._cls_pool_fwd(x, u, drop)
 
     def cls_pool_dropout_backward(self, x, u, pooled, lse, kept, grad_pooled, grad_kept, drop: nat.Dropout, need=(True, True)):
         """The backward of cls_pool_dropout_forward (linetr_cls_pool_dropout_backward): (dx, du) for the gradients arriving at pooled and
         at kept (`grad_kept` None: none arrives); `drop`: what the forward took -- the masks are generated again.  Deterministic; no
         host wait."""
-        xr, ur, L, S = self._pool_args(x, u)
-        pr = self._rows_of(pooled.detach().reshape(L, 4 * D), (L, 4 * D), "pooled", strided=False)
-        gr = self._rows_of(grad_pooled.detach().reshape(L, 4 * D), (L, 4 * D), "grad_pooled", strided=False)
-        ls = self._rows_of(lse.detach(), (L, 4), "lse", strided=False)
-        kp = self._rows_of(kept.detach(), (L, 4), "kept", strided=False)
-        gk = self._rows_of(grad_kept.detach(), (L, 4), "grad_kept", strided=False) if grad_kept is not None else None
-        dx = torch.empty((L, S, D), dtype=torch.float32, device=self.device) if need[0] else None
-        du = torch.empty((L, 4, D), dtype=torch.float32, device=self.device) if need[1] else None
-        if L:
-            self._call("linetr_cls_pool_dropout_backward", xr.data_ptr(), D, ur.data_ptr(), 4 * D, pr.data_ptr(), ls.data_ptr(), kp.data_ptr(),
-                       gr.data_ptr(), ptr(gk), L, S, C.byref(drop), ptr(dx), D, ptr(du), 4 * D)
-        return dx, du
+        return self._cls_pool_bwd(x, u, pooled, lse, grad_pooled, need, drop, kept, grad_kept)
 
     def layer_norm_dropout_forward(self, a, residual, gamma, beta, drop: nat.Dropout, site: int, eps=1e-6):
         """y = LayerNorm(r a + residual) with r the factors of `site` (1 or 2; linetr_layer_norm_dropout_forward).  Returns (y, stats) as
         layer_norm_forward.  No host wait."""
-        ar, rr, gm, rows = self._ln_args("layer_norm_dropout_forward", a, residual, gamma)
-        y = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        stats = torch.empty((rows, 2), dtype=torch.float32, device=self.device)
-        if rows:
-            self._call("linetr_layer_norm_dropout_forward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0,
-                       gm.data_ptr(), self._f32(beta.detach().reshape(-1)).data_ptr(), float(eps), rows, D, C.byref(drop), int(site), y.data_ptr(), D,
-                       stats.data_ptr())
-        return y, stats
+        return self._ln_fwd("layer_norm_dropout_forward", a, residual, gamma, beta, eps, drop, site)
 
     def layer_norm_dropout_backward(self, a, residual, stats, gamma, grad_out, drop: nat.Dropout, site: int, need=(True, True, True, True)):
         """The backward of layer_norm_dropout_forward (linetr_layer_norm_dropout_backward): (da, dresidual, dgamma, dbeta) with dresidual =
         dv and da = r dv, the masks generated again from `drop` and `site`.  `need` = which of the four to compute (the others are
         None).  Deterministic; no host wait."""
-        ar, rr, gm, rows = self._ln_args("layer_norm_dropout_backward", a, residual, gamma)
-        g = self._rows_of(grad_out.detach(), (rows, D), "grad_out")
-        st = self._rows_of(stats.detach(), (rows, 2), "stats", strided=False)
-        da, dr = (torch.empty((rows, D), dtype=torch.float32, device=self.device) if k else None for k in need[:2])
-        dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=self.device) if k else None for k in need[2:4])
-        if rows == 0:
-            return da, dr, dgamma.zero_() if dgamma is not None else None, dbeta.zero_() if dbeta is not None else None
-        ws = self._stream_workspace("layer_norm_bwd", self._L.linetr_layer_norm_backward_workspace_bytes(rows, D))
-        self._call("linetr_layer_norm_dropout_backward", ar.data_ptr(), ar.stride(0), ptr(rr), rr.stride(0) if rr is not None else 0, st.data_ptr(),
-                   gm.data_ptr(), g.data_ptr(), g.stride(0), rows, D, C.byref(drop), int(site), ptr(da), D, ptr(dr), D, ptr(dgamma), ptr(dbeta),
-                   ws.data_ptr(), ws.numel())
-        return da, dr, dgamma, dbeta
+        return self._ln_bwd("layer_norm_dropout_backward", a, residual, stats, gamma, grad_out, need, drop, site)
 
     def _gelu_rows(self, z, what):
         if z.dim() != 2 or int(z.shape[1]) % 4 or not 4 <= int(z.shape[1]) <= 4096:

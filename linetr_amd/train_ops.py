@@ -356,25 +356,6 @@ def gelu(x):
     return _Gelu.apply(x)
 
 
-class _ResidualLayerNorm(torch.autograd.Function):
-    """y = LayerNorm(a + residual).  Saved for the backward: a, the residual, the rows' float32 mean | rstd and gamma."""
-
-    @staticmethod
-    def forward(ctx, a, residual, gamma, beta, eps):
-        y, stats = _engine(a.device).layer_norm_forward(a, residual, gamma, beta, eps)
-        ctx.save_for_backward(a, residual, stats, gamma)
-        return y
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        a, residual, stats, gamma = ctx.saved_tensors
-        need_dx = ctx.needs_input_grad[0] or (residual is not None and ctx.needs_input_grad[1])
-        dx, dgamma, dbeta = _engine(a.device).layer_norm_backward(a, residual, stats, gamma, grad_out,
-                                                                  need=(need_dx, ctx.needs_input_grad[2], ctx.needs_input_grad[3]))
-        return (dx if ctx.needs_input_grad[0] else None, dx if residual is not None and ctx.needs_input_grad[1] else None, dgamma, dbeta,
-                None)
-
-
 class DropoutState(NamedTuple):
     """What the masks of one training forward are a pure function of: a 64-bit seed, the 32-bit index of the forward, the probability.
     (The generator and its counter layout: include/linetr_hip.h, LinetrDropout.)"""
@@ -390,13 +371,16 @@ def _native_dropout(dropout):
     return Dropout.make(seed, call, p)
 
 
-class _ResidualLayerNormDropout(torch.autograd.Function):
-    """y = LayerNorm(r a + residual), r the factors of `site`.  Saved for the backward: a, the residual, the rows' mean | rstd, gamma and the
-    dropout state itself -- the mask is generated again, not stored."""
+class _ResidualLayerNorm(torch.autograd.Function):
+    """y = LayerNorm(a + residual), or with `drop` (a native Dropout, else None) y = LayerNorm(r a + residual), r the factors of `site`.
+    Saved for the backward: a, the residual, the rows' float32 mean | rstd, gamma and the dropout state itself -- the mask is generated
+    again, not stored."""
 
     @staticmethod
     def forward(ctx, a, residual, gamma, beta, eps, drop, site):
-        y, stats = _engine(a.device).layer_norm_dropout_forward(a, residual, gamma, beta, drop, site, eps)
+        eng = _engine(a.device)
+        y, stats = (eng.layer_norm_forward(a, residual, gamma, beta, eps) if drop is None else
+                    eng.layer_norm_dropout_forward(a, residual, gamma, beta, drop, site, eps))
         ctx.drop, ctx.site = drop, site
         ctx.save_for_backward(a, residual, stats, gamma)
         return y
@@ -404,9 +388,14 @@ class _ResidualLayerNormDropout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         a, residual, stats, gamma = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        da, dr, dgamma, dbeta = _engine(a.device).layer_norm_dropout_backward(
-            a, residual, stats, gamma, grad_out, ctx.drop, ctx.site, need=(need[0], residual is not None and need[1], need[2], need[3]))
+        eng, need = _engine(a.device), ctx.needs_input_grad
+        need_a, need_r = need[0], residual is not None and need[1]
+        if ctx.drop is None:                         # one data gradient, of a and of the residual alike
+            dx, dgamma, dbeta = eng.layer_norm_backward(a, residual, stats, gamma, grad_out, need=(need_a or need_r, need[2], need[3]))
+            da, dr = dx if need_a else None, dx if need_r else None
+        else:
+            da, dr, dgamma, dbeta = eng.layer_norm_dropout_backward(a, residual, stats, gamma, grad_out, ctx.drop, ctx.site,
+                                                                    need=(need_a, need_r, need[2], need[3]))
         return da, dr, dgamma, dbeta, None, None, None
 
 
@@ -423,10 +412,10 @@ def residual_layer_norm(a, residual, ln: nn.LayerNorm, dropout=None, site=None):
     if a.dim() != 2 or int(a.shape[1]) != D or (residual is not None and residual.shape != a.shape):
         raise ValueError(f"a and residual must be [rows, {D}], got {tuple(a.shape)} and {None if residual is None else tuple(residual.shape)}")
     if dropout is None:
-        return _ResidualLayerNorm.apply(a, residual, ln.weight, ln.bias, float(ln.eps))
+        return _ResidualLayerNorm.apply(a, residual, ln.weight, ln.bias, float(ln.eps), None, None)
     if site not in (1, 2):
         raise ValueError(f"residual_layer_norm: dropout needs its site, 1 (behind fc) or 2 (behind w_2), got {site!r}")
-    return _ResidualLayerNormDropout.apply(a, residual, ln.weight, ln.bias, float(ln.eps), _native_dropout(dropout), int(site))
+    return _ResidualLayerNorm.apply(a, residual, ln.weight, ln.bias, float(ln.eps), _native_dropout(dropout), int(site))
 
 
 class _ClsTokenPool(torch.autograd.Function):
