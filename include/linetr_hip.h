@@ -836,6 +836,64 @@ int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const in
                              const float* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
                              float* d_desc_cn, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* linetr_superpoint_heads for channel-last raw head outputs: d_score_rows [B*Hc*Wc][ld_score >= 65] and d_desc_rows
+ * [B*Hc*Wc][ld_desc >= 256] (row strides in floats), cell (b, h, w) at row (b Hc + h) Wc + w -- what linetr_sp_encoder_forward writes.
+ * Same three outputs, same rules; the softmax / normalisation body is the same code, so given the same values the two entry
+ * points give the same bits.  A row stride below the row's length: LINETR_E_ARG. */
+int linetr_superpoint_heads_rows(LinetrHandle* h, const float* d_score_rows, int64_t ld_score, const float* d_desc_rows, int64_t ld_desc,
+                                 int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
+                                 float* d_dense_desc_nchw, void* stream);
+
+/* ---- native SuperPoint encoder (models/superpoint.py:113-134, 148-160, 188-189) ---------------------- */
+
+/* Inference only, float32 in and out, channel-last inside, deterministic (a fixed summation order; no atomics).  OFF by default at every
+ * level above this header (Engine.superpoint_encode, FusedHeadSuperPoint(native_encoder=True), Matching's config['native_encoder']).
+ *
+ * One 3x3 layer alone, on channel-last tensors: y = [maxpool2x2](relu(conv3x3(x, stride 1, zero padding 1) + bias)).
+ *   d_x [B,H,W,Cin] -> d_y [B,H,W,Cout], or [B,H/2,W/2,Cout] with pool = 1 (floors like nn.MaxPool2d(2, 2): an odd last row or column is
+ *   computed and dropped; H or W = 1 gives an empty output and launches nothing).  Exact-fp32 MFMA, fp32 accumulation.
+ *   (Cin, Cout): (64,64) (64,128) (128,128) (128,256) and (128,512) = convPa | convDa as one layer.
+ *   d_packed_w: the state_dict weight [Cout,Cin,3,3] re-ordered ONCE by linetr_sp_conv3x3_pack into the K order the kernel walks
+ *   (linetr_sp_conv3x3_pack_bytes bytes; 0 for an unsupported pair):
+ *       packed[(((c / 32) * 9 + 3 ky + kx) * 4 + (c % 32) / 8) * Cout + n][c % 8] = w[n][c][ky][kx]
+ *   linetr_sp_conv3x3_tile: the kernel's spatial tile in pixels (the unit tests walk its edges).
+ * linetr_sp_conv1a: the first layer (Cin = 1, no GEMM): gray image d_image [B,1,H,W] -> d_y [B,H,W,64], d_w [64,1,3,3] and d_bias [64] in
+ * state_dict layout, bias + ReLU.
+ * All asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  LINETR_E_ARG, nothing launched, no output changed:
+ * B < 1 (or above 65 535), H or W below 1 (or above 32 768), a (Cin, Cout) outside the set, pool outside 0 .. 1, a pointer that is NULL
+ * or not 16-byte aligned. */
+int linetr_sp_conv3x3_tile(int32_t* tile_h, int32_t* tile_w);
+int64_t linetr_sp_conv3x3_pack_bytes(int32_t Cin, int32_t Cout);
+int linetr_sp_conv3x3_pack(const float* d_w, int32_t Cin, int32_t Cout, float* d_packed, void* stream);
+int linetr_sp_conv3x3(LinetrHandle* h, const float* d_x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* d_packed_w,
+                      const float* d_bias, int32_t Cout, int32_t pool, float* d_y, void* stream);
+int linetr_sp_conv1a(LinetrHandle* h, const float* d_image, int32_t B, int32_t H, int32_t W, const float* d_w, const float* d_bias,
+                     float* d_y, void* stream);
+
+/* The whole encoder: conv1a .. conv4b with the three poolings, convPa | convDa as one launch, then the two 1x1 heads convPb / convDb
+ * (the same implicit-GEMM kernel with one tap; convPb's 65 outputs are padded with zero weights to its 128-channel tile and the
+ * padding is never stored).  11 launches for a batch.
+ *   linetr_sp_encoder_create        allocates the packed-weight arena on `device` (the only allocation of the encoder's life)
+ *   linetr_sp_encoder_set_weights   d_weights[12] / d_biases[12]: HOST arrays of device pointers in state_dict layout and order --
+ *                                   conv1a conv1b conv2a conv2b conv3a conv3b conv4a conv4b convPa convPb convDa convDb; packs them
+ *                                   asynchronously on `stream` (a forward on the same stream sees them); may be called again
+ *   linetr_sp_encoder_forward       d_image [B,1,H,W] -> d_score_rows [B*Hc*Wc][LINETR_SP_SCORE_LD] (convPb, raw logits in columns 0..64;
+ *                                   the row stride of 68 floats keeps every row, and so every image's block, 16-byte aligned; columns
+ *                                   65..67 are never written) and d_desc_rows [B*Hc*Wc][256] (convDb, raw): the rows
+ *                                   linetr_superpoint_heads_rows takes, Hc = H / 8, Wc = W / 8 (floor at every pooling); d_feat (or NULL) [B,Hc,Wc,128] = conv4b's output, for the tests.  Asynchronous on `stream`;
+ *                                   nothing inside allocates or waits.
+ * LINETR_E_ARG, nothing launched, no output changed: a NULL encoder or one without weights, B < 1 (or above 65 535), H or W below 8 (or
+ * above 32 768), a required pointer that is NULL or not 16-byte aligned (d_feat: misaligned), a workspace smaller than
+ * linetr_sp_encoder_workspace_bytes says. */
+#define LINETR_SP_SCORE_LD 68
+typedef struct LinetrSpEncoder LinetrSpEncoder;
+int linetr_sp_encoder_create(int32_t device, LinetrSpEncoder** out);
+void linetr_sp_encoder_destroy(LinetrSpEncoder* enc);
+int linetr_sp_encoder_set_weights(LinetrSpEncoder* enc, const float* const* d_weights, const float* const* d_biases, void* stream);
+int64_t linetr_sp_encoder_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int linetr_sp_encoder_forward(LinetrSpEncoder* enc, const float* d_image, int32_t B, int32_t H, int32_t W, float* d_score_rows,
+                              float* d_desc_rows, float* d_feat, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- arithmetic mode of the dense contractions ----------------------------------------------------- */
 
 /* All Linear/Conv1d(k=1) contractions run on one of three MFMA paths (fp32 in, fp32 accumulate, fp32 out):

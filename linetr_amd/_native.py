@@ -182,6 +182,17 @@ ABI = {
     "linetr_superpoint_keypoints": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_point_descriptors_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "linetr_point_descriptors": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "linetr_superpoint_heads_rows": (i32, [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+    "linetr_sp_conv3x3_tile": (i32, [_P(i32), _P(i32)]),
+    "linetr_sp_conv3x3_pack_bytes": (i64, [i32, i32]),
+    "linetr_sp_conv3x3_pack": (i32, [vp, i32, i32, vp, vp]),
+    "linetr_sp_conv3x3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
+    "linetr_sp_conv1a": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "linetr_sp_encoder_create": (i32, [i32, _P(vp)]),
+    "linetr_sp_encoder_destroy": (None, [vp]),
+    "linetr_sp_encoder_set_weights": (i32, [vp, _P(vp), _P(vp), vp]),
+    "linetr_sp_encoder_workspace_bytes": (i64, [i32, i32, i32]),
+    "linetr_sp_encoder_forward": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
     "linetr_set_precision": (i32, [vp, i32]),
     "linetr_get_precision": (i32, [vp]),
     "linetr_debug_posenc": (i32, [vp, i32, vp, vp, vp, i64, vp, vp]),

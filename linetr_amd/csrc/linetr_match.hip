@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 3 of 4: the descriptor-distance matcher, the dense-map producer and the slab packing of the
+// liblinetr_hip.so, translation unit 3 of 5: the descriptor-distance matcher, the dense-map producer and the slab packing of the
 // multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h) and SuperPoint's key-point branch
 // (lt_keypoints.h).  Training and evaluation are linetr_train.hip.
 #include <algorithm>
@@ -588,13 +588,16 @@ extern "C" int linetr_pack_slab(const float* d_line_desc, int32_t N, const int32
   return LINETR_OK;
 }
 
-extern "C" int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const float* d_desc_raw, int32_t B,
-                                       int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
-                                       float* d_dense_desc_nchw, void* stream) {
-  if (B < 0 || Hc <= 0 || Wc <= 0) return fail(LINETR_E_ARG, "superpoint_heads: bad shape B=%d Hc=%d Wc=%d", B, Hc, Wc);
-  if (d_dense_score && !d_score_logits) return fail(LINETR_E_ARG, "superpoint_heads: score output without score logits");
-  if ((d_dense_desc_nhwc || d_dense_desc_nchw) && !d_desc_raw)
-    return fail(LINETR_E_ARG, "superpoint_heads: descriptor output without the raw descriptor head");
+namespace {
+// Both layouts of the raw head outputs: NCHW (rows = false; the strides are unused) or channel-last rows of ld_score / ld_desc floats.
+template <bool ROWS>
+int superpoint_heads_any(LinetrHandle* h, const char* who, const float* d_score, int64_t ld_score, const float* d_desc, int64_t ld_desc,
+                         int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc, float* d_dense_desc_nchw,
+                         void* stream) {
+  if (B < 0 || Hc <= 0 || Wc <= 0) return fail(LINETR_E_ARG, "%s: bad shape B=%d Hc=%d Wc=%d", who, B, Hc, Wc);
+  if (d_dense_score && !d_score) return fail(LINETR_E_ARG, "%s: score output without score logits", who);
+  if ((d_dense_desc_nhwc || d_dense_desc_nchw) && !d_desc) return fail(LINETR_E_ARG, "%s: descriptor output without the raw descriptor head", who);
+  if (ROWS && ((d_score && ld_score < 65) || (d_desc && ld_desc < D))) return fail(LINETR_E_ARG, "%s: row stride below the row's length", who);
   if (B == 0) return LINETR_OK;
   if (h) LT_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
@@ -603,15 +606,31 @@ extern "C" int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_log
   if (d_dense_desc_nhwc || d_dense_desc_nchw) {
     const double by = (double)B * HW * D * 4.0 * (1 + (d_dense_desc_nhwc ? 1 : 0) + (d_dense_desc_nchw ? 1 : 0));
     ProfScope ps(h, st, "sp_desc_head", 3.0 * B * HW * D, by);
-    hipLaunchKernelGGL(sp_desc_head_kernel<32>, dim3((unsigned)cdiv(HW, 32), (unsigned)B), dim3(256), 0, st, d_desc_raw, d_dense_desc_nhwc, d_dense_desc_nchw, HW);
+    hipLaunchKernelGGL((sp_desc_head_kernel<32, ROWS>), dim3((unsigned)cdiv(HW, 32), (unsigned)B), dim3(256), 0, st, d_desc, d_dense_desc_nhwc,
+                       d_dense_desc_nchw, HW, ld_desc);
     LT_LAUNCH_CHECK();
   }
   if (d_dense_score) {
     ProfScope ps(h, st, "sp_score_head", 0, (double)B * HW * (65 + 64) * 4.0);
-    hipLaunchKernelGGL(sp_score_head_kernel, grid, dim3(256), 0, st, d_score_logits, d_dense_score, Hc, Wc);
+    hipLaunchKernelGGL(sp_score_head_kernel<ROWS>, grid, dim3(256), 0, st, d_score, d_dense_score, Hc, Wc, ld_score);
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const float* d_desc_raw, int32_t B,
+                                       int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
+                                       float* d_dense_desc_nchw, void* stream) {
+  return superpoint_heads_any<false>(h, "superpoint_heads", d_score_logits, 0, d_desc_raw, 0, B, Hc, Wc, d_dense_score, d_dense_desc_nhwc,
+                                     d_dense_desc_nchw, stream);
+}
+
+extern "C" int linetr_superpoint_heads_rows(LinetrHandle* h, const float* d_score_rows, int64_t ld_score, const float* d_desc_rows,
+                                            int64_t ld_desc, int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score,
+                                            float* d_dense_desc_nhwc, float* d_dense_desc_nchw, void* stream) {
+  return superpoint_heads_any<true>(h, "superpoint_heads_rows", d_score_rows, ld_score, d_desc_rows, ld_desc, B, Hc, Wc, d_dense_score,
+                                    d_dense_desc_nhwc, d_dense_desc_nchw, stream);
 }
 
 // =============================================================================================

@@ -6,6 +6,7 @@
 //   linetr_match.hip  matcher, dense-map producer, slab packing, SuperPoint's key-point branch
 //   linetr_train.hip  training and evaluation: validation step, criterion gradient, backward of the 1x1 layers, the descriptor head and
 //                     the neighbour-line attention, ground-truth line assignment
+//   linetr_sp.hip     the native SuperPoint encoder (its own LinetrSpEncoder object; no LinetrHandle state)
 //   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once
 #include <map>

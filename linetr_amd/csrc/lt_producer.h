@@ -13,9 +13,11 @@ namespace lt {
 // stride makes the NCHW-side accesses (lanes along cells) and the NHWC-side accesses (lanes along channels) both
 // bank-conflict-free.  CELLS = 32 (33 KiB of LDS, 4 blocks per CU) keeps more loads in flight than 64 (2 blocks per
 // CU): 5.4 vs 4.3 TB/s on a cfg3-sized batch (tools/producer_bench.py).
-template <int CELLS>
+// ROWS: the raw head output is channel-last rows [B * HW][ld >= 256] (linetr_superpoint_heads_rows: what the native encoder's convDb
+// writes) instead of NCHW; only phase 1 differs, so given the same values both layouts give the same bits.
+template <int CELLS, bool ROWS>
 __global__ __launch_bounds__(256) void sp_desc_head_kernel(const float* __restrict__ raw, float* __restrict__ nhwc,
-                                                           float* __restrict__ nchw, int HW) {
+                                                           float* __restrict__ nchw, int HW, int64_t ld) {
   constexpr int LS = CELLS + 1;
   constexpr int LPC = CELLS / 4;          // lanes per channel row (one float4 each)
   constexpr int CPP = 256 / LPC;          // channels per pass
@@ -26,7 +28,16 @@ __global__ __launch_bounds__(256) void sp_desc_head_kernel(const float* __restri
   const float* src = raw + (int64_t)b * D * HW;
   const bool vec = (HW % 4) == 0;
   const int cl = t / LPC, p4 = (t % LPC) * 4;
-  // phase 1: CPP channels per pass, LPC lanes x 4 cells per channel
+  // phase 1: CPP channels per pass, LPC lanes x 4 cells per channel (rows: one wave per cell, 256 B per instruction)
+  if constexpr (ROWS) {
+    const int lane = t & 63, w = t >> 6;
+    for (int p = w; p < CELLS; p += 4) {
+      const bool in = p0 + p < HW;
+      const float* s = raw + ((int64_t)b * HW + p0 + p) * ld;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) tile[(lane + 64 * i) * LS + p] = in ? s[lane + 64 * i] : 0.f;
+    }
+  } else
 #pragma unroll 4
   for (int pass = 0; pass < D / CPP; ++pass) {
     const int c = pass * CPP + cl;
@@ -90,15 +101,22 @@ __global__ __launch_bounds__(256) void sp_desc_head_kernel(const float* __restri
 // One block = 64 consecutive cells of one image x 65 logits.  Thread (cell p, quarter g) owns the 16 channels of
 // sub-pixel rows dy = 2g, 2g+1 of its cell's 8x8 patch (quarter 3 also the dustbin): one expf per output, the
 // max and the sum are combined across the four quarters through LDS.
+// ROWS: logits are channel-last rows [B * HW][ld >= 65] instead of NCHW (as for sp_desc_head_kernel: the load alone differs).
+template <bool ROWS>
 __global__ __launch_bounds__(256) void sp_score_head_kernel(const float* __restrict__ logits, float* __restrict__ score,
-                                                            int Hc, int Wc) {
+                                                            int Hc, int Wc, int64_t ld) {
   constexpr int LS = 65;
   __shared__ float tile[65 * LS];
   __shared__ float red[2][4 * 64];
   const int t = threadIdx.x, b = blockIdx.y, p0 = blockIdx.x * 64, HW = Hc * Wc;
   const float* src = logits + (int64_t)b * 65 * HW;
   const bool vec = (HW % 4) == 0;
-  {  // 16 lanes x 4 cells per channel row, 16 channels per pass (+ the dustbin row)
+  if constexpr (ROWS) {
+    for (int i = t; i < 64 * 65; i += 256) {
+      const int p = i / 65, c = i % 65;
+      tile[c * LS + p] = p0 + p < HW ? logits[((int64_t)b * HW + p0 + p) * ld + c] : 0.f;
+    }
+  } else {  // 16 lanes x 4 cells per channel row, 16 channels per pass (+ the dustbin row)
     const int cl = t >> 4, p4 = (t & 15) * 4;
 #pragma unroll
     for (int pass = 0; pass < 5; ++pass) {

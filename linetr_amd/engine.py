@@ -153,6 +153,9 @@ class Engine(_TrainSurface, _DebugSurface):
         if getattr(self, "_h", None):
             self._L.linetr_destroy(self._h)
             self._h = None
+        sp = self.__dict__.pop("_sp", None)
+        if sp and sp["enc"] is not None:
+            self._L.linetr_sp_encoder_destroy(sp["enc"])
 
     def __del__(self):
         try:
@@ -835,6 +838,126 @@ class Engine(_TrainSurface, _DebugSurface):
             nat.check(self._L.linetr_superpoint_heads(self._h, ptr(sl), ptr(dr), B, Hc, Wc, ptr(score), ptr(o_nhwc),
                                                       ptr(o_nchw), self._stream()), self._L)
         return score, o_nhwc, o_nchw
+
+    def superpoint_heads_rows(self, score_rows: torch.Tensor = None, desc_rows: torch.Tensor = None, shape=None, *, nhwc=True,
+                              nchw=False):
+        """superpoint_heads for channel-last raw head outputs (linetr_superpoint_heads_rows): score_rows [B*Hc*Wc, 65] and desc_rows
+        [B*Hc*Wc, 256], float32 on the device with contiguous columns (a row stride is taken as it is), `shape` = (B, Hc, Wc) -- what
+        superpoint_encode returns.  Same outputs as superpoint_heads, bit for bit given the same values."""
+        if score_rows is None and desc_rows is None:
+            raise ValueError("superpoint_heads_rows needs at least one head")
+        B, Hc, Wc = (int(v) for v in shape)
+
+        def rows(t, width, what):
+            if t is None:
+                return None
+            if t.device != self.device or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+                t = t.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != (B * Hc * Wc, width):
+                raise ValueError(f"{what} must be [{B * Hc * Wc},{width}], got {tuple(t.shape)}")
+            return t
+        sl, dr = rows(score_rows, 65, "score_rows"), rows(desc_rows, D, "desc_rows")
+        score = torch.empty((B, Hc * 8, Wc * 8), dtype=torch.float32, device=self.device) if sl is not None else None
+        o_nhwc = torch.empty((B, Hc, Wc, D), dtype=torch.float32, device=self.device) if (dr is not None and nhwc) else None
+        o_nchw = torch.empty((B, D, Hc, Wc), dtype=torch.float32, device=self.device) if (dr is not None and nchw) else None
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_superpoint_heads_rows(self._h, ptr(sl), sl.stride(0) if sl is not None else 0, ptr(dr),
+                                                           dr.stride(0) if dr is not None else 0, B, Hc, Wc, ptr(score), ptr(o_nhwc),
+                                                           ptr(o_nchw), self._stream()), self._L)
+        return score, o_nhwc, o_nchw
+
+    # ------------------------------------------------------------------ native SuperPoint encoder (off by default everywhere)
+    SP_CONV_NAMES = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
+
+    def sp_conv_tile(self):
+        """(TH, TW): the spatial tile of the 3x3 kernel in pixels"""
+        th, tw = C.c_int32(), C.c_int32()
+        nat.check(self._L.linetr_sp_conv3x3_tile(C.byref(th), C.byref(tw)), self._L)
+        return th.value, tw.value
+
+    def sp_conv3x3_pack(self, weight: torch.Tensor) -> torch.Tensor:
+        """a state_dict weight [Cout,Cin,3,3] in the K order linetr_sp_conv3x3 walks"""
+        w = self._f32(weight)
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        nbytes = self._L.linetr_sp_conv3x3_pack_bytes(cin, cout)
+        if tuple(w.shape[2:]) != (3, 3) or nbytes == 0:
+            raise ValueError(f"no native 3x3 layer for a weight of shape {tuple(w.shape)}")
+        packed = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_sp_conv3x3_pack(w.data_ptr(), cin, cout, packed.data_ptr(), self._stream()), self._L)
+        return packed
+
+    def sp_conv3x3(self, x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, pool=False, out: torch.Tensor = None):
+        """One encoder layer alone (linetr_sp_conv3x3): x [B,H,W,Cin] channel-last -> relu(conv3x3 + bias) [B,H,W,Cout], or its 2x2
+        maximum [B,H//2,W//2,Cout] with `pool`.  `out`: write there instead of into a new tensor (the unit tests' guarded buffers)."""
+        B, H, W, cin = (int(v) for v in x.shape)
+        cout = int(bias.numel())
+        if out is None:
+            out = torch.empty((B, H // 2, W // 2, cout) if pool else (B, H, W, cout), dtype=torch.float32, device=self.device)
+        self._call("linetr_sp_conv3x3", x.data_ptr(), B, H, W, cin, packed.data_ptr(), bias.data_ptr(), cout, int(pool), out.data_ptr())
+        return out
+
+    def sp_conv1a(self, image: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, out: torch.Tensor = None):
+        """The first layer alone (linetr_sp_conv1a): image [B,1,H,W] -> relu(conv1a) [B,H,W,64], weight [64,1,3,3]."""
+        B, _, H, W = (int(v) for v in image.shape)
+        if out is None:
+            out = torch.empty((B, H, W, 64), dtype=torch.float32, device=self.device)
+        self._call("linetr_sp_conv1a", image.data_ptr(), B, H, W, weight.data_ptr(), bias.data_ptr(), out.data_ptr())
+        return out
+
+    def _sp_encoder(self, weights):
+        """The native encoder with `weights` packed: a mapping name -> tensor holding '<conv>.weight' / '<conv>.bias' of SP_CONV_NAMES
+        (a SuperPoint state_dict, or dict(module.named_parameters())).  Packed again when any of the 24 tensors has another address
+        or version than at the last call."""
+        ts = [weights[n + s] for s in (".weight", ".bias") for n in self.SP_CONV_NAMES]
+        key = tuple((t.data_ptr(), t._version, t.device, t.dtype) for t in ts)
+        st = self.__dict__.setdefault("_sp", {"enc": None, "key": None})
+        if st["enc"] is None:
+            enc = C.c_void_p()
+            nat.check(self._L.linetr_sp_encoder_create(self.device.index, C.byref(enc)), self._L)
+            st["enc"] = enc
+        if st["key"] != key:
+            ts32 = [self._f32(t.detach()) for t in ts]
+            arr = lambda part: (C.c_void_p * 12)(*[t.data_ptr() for t in part])
+            with torch.cuda.device(self.device):
+                nat.check(self._L.linetr_sp_encoder_set_weights(st["enc"], arr(ts32[:12]), arr(ts32[12:]), self._stream()), self._L)
+            for t in ts32:       # a converted copy is read by the packing kernels queued above: keep it until they have run
+                t.record_stream(torch.cuda.current_stream(self.device))
+            st["key"] = key
+        return st["enc"]
+
+    def superpoint_encode(self, image: torch.Tensor, weights, *, max_workspace_bytes=2 << 30, return_feat=False):
+        """SuperPoint's shared encoder and the two head convolutions natively (linetr_sp_encoder_forward; the torch counterpart is
+        FusedHeadSuperPoint.encode): image [B,1,H,W] float32 -> (score_rows [B*Hc*Wc,65], desc_rows [B*Hc*Wc,256], (B, Hc, Wc)), the
+        raw head outputs as channel-last rows for superpoint_heads_rows (score_rows is a view with a row stride of 68 floats).  `weights`: see _sp_encoder.  The batch is cut into chunks
+        of as many images as keep the workspace under max_workspace_bytes (at least one); every image's result is independent of the
+        chunking.  No host wait.  return_feat: conv4b's output [B,Hc,Wc,128] as a fourth element (tests)."""
+        img = self._f32(image)
+        if img.dim() != 4 or int(img.shape[1]) != 1:
+            raise ValueError(f"image must be [B,1,H,W], got {tuple(img.shape)}")
+        B, _, H, W = (int(v) for v in img.shape)
+        if H < 8 or W < 8:
+            raise ValueError(f"the encoder needs at least 8 x 8 pixels, got {H} x {W}")
+        Hc, Wc = H // 8, W // 8
+        cells = Hc * Wc
+        score = torch.empty((B * cells, 68), dtype=torch.float32, device=self.device)[:, :65]     # LINETR_SP_SCORE_LD: 16-byte aligned rows
+        desc = torch.empty((B * cells, D), dtype=torch.float32, device=self.device)
+        feat = torch.empty((B, Hc, Wc, 128), dtype=torch.float32, device=self.device) if return_feat else None
+        if B > 0:
+            enc = self._sp_encoder(weights)
+            per_image = self._L.linetr_sp_encoder_workspace_bytes(1, H, W)
+            n = max(1, min(B, int(max_workspace_bytes) // max(per_image, 1)))
+            ws = self._workspace("sp_encoder", self._L.linetr_sp_encoder_workspace_bytes(n, H, W))
+            with torch.cuda.device(self.device):
+                for b0 in range(0, B, n):
+                    nb = min(n, B - b0)
+                    src = img[b0:b0 + nb]
+                    if src.data_ptr() % 16:          # an odd H * W: a later chunk's first image is not 16-byte aligned inside the batch
+                        src = src.clone()
+                    nat.check(self._L.linetr_sp_encoder_forward(enc, src.data_ptr(), nb, H, W, score[b0 * cells:].data_ptr(),
+                                                                desc[b0 * cells:].data_ptr(), ptr(feat[b0:]) if return_feat else None,
+                                                                ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return (score, desc, (B, Hc, Wc), feat) if return_feat else (score, desc, (B, Hc, Wc))
 
     def superpoint_keypoints(self, dense_score: torch.Tensor, dense_desc: torch.Tensor = None, *, nms_radius=4,
                              keypoint_threshold=0.005, remove_borders=4, max_keypoints=-1, align_corners=False,

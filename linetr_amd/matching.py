@@ -44,10 +44,12 @@ class Matching(torch.nn.Module):
             # An injected instance is used as given; config['fuse_superpoint_heads'] = False keeps the plain module.
             # config['native_keypoints'] = True (default False) also moves the wrapper's key-point branch (NMS, threshold, border
             # filter, top-k, descriptor lookup) from the module's per-image torch helpers to one native call per batch.
+            # config['native_encoder'] = True (default False) runs the twelve convolutions natively as well (inference only).
             if config.get("fuse_superpoint_heads", True) and all(hasattr(superpoint, a) for a in
                                                                   ("convPa", "convPb", "convDa", "convDb", "relu", "pool")):
                 from .superpoint import FusedHeadSuperPoint
-                superpoint = FusedHeadSuperPoint(superpoint, native_keypoints=config.get("native_keypoints", False))
+                superpoint = FusedHeadSuperPoint(superpoint, native_keypoints=config.get("native_keypoints", False),
+                                                 native_encoder=config.get("native_encoder", False))
         self.superpoint = superpoint
         self.lsd = lsd if lsd is not None else _frontend("line_detector", "LSD", config.get("lsd", {}))
         self.linetransformer = LineTransformer(config.get("linetransformer", {}))

@@ -25,12 +25,13 @@ from torch import nn
 
 class FusedHeadSuperPoint(nn.Module):
     def __init__(self, superpoint: nn.Module, engine=None, helpers=None, want_nchw: bool = True,
-                 native_keypoints: bool = False, align_corners=None):
+                 native_keypoints: bool = False, align_corners=None, native_encoder: bool = False):
         super().__init__()
         self.sp = superpoint
         self.config = superpoint.config
         self.want_nchw = want_nchw
         self.native_keypoints = bool(native_keypoints)
+        self.native_encoder = bool(native_encoder)
         # grid_sample flag of the native descriptor lookup; None = the reference's own version switch (superpoint.py:88)
         self.align_corners = align_corners
         self._engine = engine
@@ -53,13 +54,27 @@ class FusedHeadSuperPoint(nn.Module):
         x = relu(sp.conv4a(x)); x = relu(sp.conv4b(x))
         return sp.convPb(relu(sp.convPa(x))), sp.convDb(relu(sp.convDa(x)))
 
+    def _dense_maps_native(self, image):
+        """The dense maps through the native encoder: no autograd graph, so a trainable encoder under enabled grad is refused."""
+        params = dict(self.sp.named_parameters())
+        eng = self.engine()
+        if torch.is_grad_enabled() and any(params[n + s].requires_grad for n in eng.SP_CONV_NAMES for s in (".weight", ".bias")):
+            raise RuntimeError("FusedHeadSuperPoint(native_encoder=True) is inference only: an encoder parameter requires grad. Call it "
+                               "under torch.no_grad(), freeze the encoder, or use native_encoder=False.")
+        with torch.no_grad():
+            score_rows, desc_rows, shape = eng.superpoint_encode(image, params)
+            return eng.superpoint_heads_rows(score_rows, desc_rows, shape, nhwc=True, nchw=self.want_nchw) + (shape[1], shape[2])
+
     def forward(self, data):
-        score_logits, desc_raw = self.encode(data["image"])
-        dense_score, d_nhwc, d_nchw = self.engine().superpoint_heads(score_logits, desc_raw, nhwc=True,
-                                                                     nchw=self.want_nchw)
+        if self.native_encoder:
+            dense_score, d_nhwc, d_nchw, hc, wc = self._dense_maps_native(data["image"])
+        else:
+            score_logits, desc_raw = self.encode(data["image"])
+            dense_score, d_nhwc, d_nchw = self.engine().superpoint_heads(score_logits, desc_raw, nhwc=True,
+                                                                         nchw=self.want_nchw)
+            hc, wc = int(score_logits.shape[2]), int(score_logits.shape[3])
         if d_nchw is None:                       # a view with the reference's shape (not contiguous)
             d_nchw = d_nhwc.permute(0, 3, 1, 2)
-        hc, wc = int(score_logits.shape[2]), int(score_logits.shape[3])
         if self.native_keypoints:
             keypoints, scores, descriptors = self._keypoints_native(dense_score, d_nhwc)
         else:
