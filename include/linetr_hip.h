@@ -189,7 +189,9 @@ int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t height, int32_
  * is written for linetr_match.  `out.desc` may be NULL to skip descriptor sampling.  `h` may be NULL (no weights are
  * involved; the current HIP device is used).  clip_height / clip_width: the `image_shape` ARGUMENT of line_tokenizer
  * (models/line_process.py:101), which only sets the end-point clip (:115-116) and need not be the maps' shape -- the dataset
- * builder passes (640, 480) for 480 x 640 images (dataloaders/utils/util_lines.py:682,703); <= 0 = height / width. */
+ * builder passes (640, 480) for 480 x 640 images (dataloaders/utils/util_lines.py:682,703); <= 0 = height / width.
+ * A channel-last d_dense_desc, out.desc and d_workspace are accessed with 16-byte vectors: one that is not 16-byte aligned is refused
+ * with LINETR_E_ARG before anything is launched (linetr_describe / linetr_describe_submit: the same three). */
 int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N,
                     double token_distance, int32_t max_tokens, const float* d_dense_desc,
                     const float* d_dense_score, int32_t n_images, int32_t height, int32_t width,
@@ -198,7 +200,8 @@ int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int
 
 /* sample_descriptors (models/line_process.py:86-98) on its own, for the module-level function of the shim: n points
  * d_points [n,2] (x,y in pixels) of ONE image sampled bilinearly (zero padding) from its dense descriptor map
- * ([256,Hc,Wc], or [Hc,Wc,256] with dense_is_nhwc) and L2-normalised; d_out [n,256] row-major.  `h` may be NULL. */
+ * ([256,Hc,Wc], or [Hc,Wc,256] with dense_is_nhwc) and L2-normalised; d_out [n,256] row-major.  `h` may be NULL.
+ * A channel-last map, d_out and d_workspace must be 16-byte aligned (LINETR_E_ARG otherwise; an NCHW map and d_points may lie anywhere). */
 int64_t linetr_sample_descriptors_workspace_bytes(int32_t Hc, int32_t Wc, int32_t dense_is_nhwc);
 int linetr_sample_descriptors(LinetrHandle* h, const float* d_points, int64_t n, const float* d_dense_desc, int32_t Hc,
                               int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc, float* d_out, void* d_workspace,
@@ -803,7 +806,9 @@ int linetr_grad_norm(LinetrHandle* h, const LinetrAdamTensor* h_table, int32_t n
  * d_score_logits [B,65,Hc,Wc] and d_desc_raw [B,256,Hc,Wc] are the raw convPb / convDb outputs (float32, NCHW,
  * contiguous).  Outputs (any may be NULL): d_dense_score [B,8Hc,8Wc]; d_dense_desc_nhwc [B,Hc,Wc,256] -- pass it
  * to linetr_describe with dense_is_nhwc = 1 and the NCHW->NHWC pass disappears; d_dense_desc_nchw [B,256,Hc,Wc],
- * the reference's 'dense_descriptor' layout.  `h` may be NULL (no weights involved; current HIP device). */
+ * the reference's 'dense_descriptor' layout.  `h` may be NULL (no weights involved; current HIP device).
+ * Every output must be 16-byte aligned, and so must both inputs when Hc * Wc is a multiple of 4 (their planes are then loaded as
+ * 16-byte vectors): LINETR_E_ARG otherwise, before anything is launched. */
 int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const float* d_desc_raw, int32_t B,
                             int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
                             float* d_dense_desc_nchw, void* stream);
@@ -830,7 +835,8 @@ int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense_score, int
  * rows d_cu_kp[b] .. d_cu_kp[b+1] of d_keypoints [n_total,2], L2-normalised, stored in the reference's layout: image b owns a
  * contiguous [256, n_b] block at float offset 256 * d_cu_kp[b] of d_desc_cn.  d_dense_desc is [B,Hc,Wc,256] (dense_is_nhwc = 1,
  * sampled in place) or [B,256,Hc,Wc] (transposed into the workspace first).  Same sampler and `align_corners` as
- * linetr_sample_descriptors.  Asynchronous on `stream`; `h` may be NULL. */
+ * linetr_sample_descriptors.  Asynchronous on `stream`; `h` may be NULL.  A channel-last map and d_workspace must be 16-byte aligned
+ * (LINETR_E_ARG otherwise); d_keypoints, d_desc_cn and an NCHW map may lie anywhere. */
 int64_t linetr_point_descriptors_workspace_bytes(int32_t B, int32_t Hc, int32_t Wc, int32_t dense_is_nhwc);
 int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const int32_t* d_cu_kp, int32_t B, int64_t n_total,
                              const float* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
@@ -839,7 +845,8 @@ int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const in
 /* linetr_superpoint_heads for channel-last raw head outputs: d_score_rows [B*Hc*Wc][ld_score >= 65] and d_desc_rows
  * [B*Hc*Wc][ld_desc >= 256] (row strides in floats), cell (b, h, w) at row (b Hc + h) Wc + w -- what linetr_sp_encoder_forward writes.
  * Same three outputs, same rules; the softmax / normalisation body is the same code, so given the same values the two entry
- * points give the same bits.  A row stride below the row's length: LINETR_E_ARG. */
+ * points give the same bits.  A row stride below the row's length: LINETR_E_ARG.  The rows are read float by float and may lie anywhere;
+ * the outputs must be 16-byte aligned as for linetr_superpoint_heads. */
 int linetr_superpoint_heads_rows(LinetrHandle* h, const float* d_score_rows, int64_t ld_score, const float* d_desc_rows, int64_t ld_desc,
                                  int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
                                  float* d_dense_desc_nchw, void* stream);

@@ -598,6 +598,12 @@ int superpoint_heads_any(LinetrHandle* h, const char* who, const float* d_score,
   if (d_dense_score && !d_score) return fail(LINETR_E_ARG, "%s: score output without score logits", who);
   if ((d_dense_desc_nhwc || d_dense_desc_nchw) && !d_desc) return fail(LINETR_E_ARG, "%s: descriptor output without the raw descriptor head", who);
   if (ROWS && ((d_score && ld_score < 65) || (d_desc && ld_desc < D))) return fail(LINETR_E_ARG, "%s: row stride below the row's length", who);
+  // 16-byte vectors: every output (the score map and the NCHW map are stored so, the channel-last map is what the samplers load so) and
+  // the NCHW head outputs when a channel's plane is a multiple of 4 floats; rows are read scalar-wise
+  const bool vec_in = !ROWS && ((int64_t)Hc * Wc) % 4 == 0;
+  if (!aligned16(d_dense_score) || !aligned16(d_dense_desc_nhwc) || !aligned16(d_dense_desc_nchw) ||
+      (vec_in && (!aligned16(d_score) || !aligned16(d_desc))))
+    return fail(LINETR_E_ARG, "%s: the dense maps%s must be 16-byte aligned", who, vec_in ? " and the raw head outputs" : "");
   if (B == 0) return LINETR_OK;
   if (h) LT_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;

@@ -329,6 +329,8 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
       !out.score || (out.desc && !d_dense_desc))
     return fail(LINETR_E_ARG, "tokenize: null pointer");
   if (T < 1 || T > 4096 || height % 8 || width % 8) return fail(LINETR_E_ARG, "tokenize: bad max_tokens / image size");
+  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(out.desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "tokenize: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned");
   if (out.mat && n_images != 1) return fail(LINETR_E_ARG, "tokenize: mat_klines2sublines of several images: use linetr_describe (it has the sub-line prefix sums)");
   K2sTable k2s;
   if (int e = k2s_table(out, n_images, K, N, nullptr, k2s, "tokenize")) return e;
@@ -358,6 +360,8 @@ extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points,
   if (n < 0 || Hc <= 0 || Wc <= 0) return fail(LINETR_E_ARG, "sample_descriptors: bad shape");
   if (n == 0) return LINETR_OK;
   if (!d_points || !d_dense_desc || !d_out) return fail(LINETR_E_ARG, "sample_descriptors: null pointer");
+  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(d_out) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "sample_descriptors: a channel-last descriptor map, the output and the workspace must be 16-byte aligned");
   if (ws_bytes < linetr_sample_descriptors_workspace_bytes(Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
     return fail(LINETR_E_WORKSPACE, "sample_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -383,6 +387,8 @@ extern "C" int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoint
   if (B < 0 || n_total < 0 || Hc <= 0 || Wc <= 0 || n_total > INT32_MAX) return fail(LINETR_E_ARG, "point_descriptors: bad shape");
   if (B == 0 || n_total == 0) return LINETR_OK;
   if (!d_keypoints || !d_cu_kp || !d_dense_desc || !d_desc_cn) return fail(LINETR_E_ARG, "point_descriptors: null pointer");
+  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "point_descriptors: a channel-last descriptor map and the workspace must be 16-byte aligned");
   if (ws_bytes < linetr_point_descriptors_workspace_bytes(B, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
     return fail(LINETR_E_WORKSPACE, "point_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -961,6 +967,8 @@ int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32
   if (T < 1 || T > 4096 || height % 8 || width % 8) return fail(LINETR_E_ARG, "describe: bad max_tokens / image size");
   if (n_real < N || n_real > (int64_t)N * T) return fail(LINETR_E_ARG, "describe: implausible real-token count");
   if (out.desc && !out.pnt) return fail(LINETR_E_ARG, "describe: out.desc requires out.pnt");
+  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(out.desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "describe: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned");
   K2sTable k2s;
   if (int e = k2s_table(out, n_images, K, N, h_cu, k2s, "describe")) return e;
   if (ws_bytes < linetr_describe_workspace_bytes(h, n_images, height, width, N, n_real))

@@ -10,7 +10,7 @@ using namespace lt;
 
 namespace {
 
-bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool there16(const void* p) { return p && aligned16(p); }   // a required tensor: present and 16-byte aligned
 constexpr int SP_MAX_DIM = 32768, SP_MAX_B = 65535;    // grid.z; tiles and pixel counts of one image stay far inside 2^31
 
 // the (Cin, Cout) pairs of the encoder's 3x3 layers; 128 -> 512 is convPa | convDa as one launch
@@ -94,7 +94,7 @@ extern "C" int64_t linetr_sp_conv3x3_pack_bytes(int32_t Cin, int32_t Cout) { ret
 
 extern "C" int linetr_sp_conv3x3_pack(const float* d_w, int32_t Cin, int32_t Cout, float* d_packed, void* stream) {
   if (!sp_pair_ok(Cin, Cout)) return fail(LINETR_E_ARG, "sp_conv3x3_pack: unsupported layer %d -> %d", Cin, Cout);
-  if (!aligned16(d_w) || !aligned16(d_packed)) return fail(LINETR_E_ARG, "sp_conv3x3_pack: a NULL or misaligned pointer");
+  if (!there16(d_w) || !there16(d_packed)) return fail(LINETR_E_ARG, "sp_conv3x3_pack: a NULL or misaligned pointer");
   return sp_pack_launch(d_w, Cout, Cin, 9, d_packed, Cout, 0, (hipStream_t)stream);
 }
 
@@ -103,7 +103,7 @@ extern "C" int linetr_sp_conv3x3(LinetrHandle* h, const float* d_x, int32_t B, i
   if (B < 1 || B > SP_MAX_B || H < 1 || W < 1 || H > SP_MAX_DIM || W > SP_MAX_DIM) return fail(LINETR_E_ARG, "sp_conv3x3: bad shape B=%d H=%d W=%d", B, H, W);
   if (!sp_pair_ok(Cin, Cout)) return fail(LINETR_E_ARG, "sp_conv3x3: unsupported layer %d -> %d", Cin, Cout);
   if (pool < 0 || pool > 1) return fail(LINETR_E_ARG, "sp_conv3x3: pool %d outside 0..1", pool);
-  if (!aligned16(d_x) || !aligned16(d_packed_w) || !aligned16(d_bias) || !aligned16(d_y)) return fail(LINETR_E_ARG, "sp_conv3x3: a NULL or misaligned pointer");
+  if (!there16(d_x) || !there16(d_packed_w) || !there16(d_bias) || !there16(d_y)) return fail(LINETR_E_ARG, "sp_conv3x3: a NULL or misaligned pointer");
   if (h) LT_HIP(hipSetDevice(h->device));
   SpConvArgs a{d_x, Cin, d_packed_w, d_bias, d_y, Cout, H, W, Cout, Cout, 1};
   return sp_conv_launch(h, "sp_conv3x3", a, B, Cin, 3, pool, (hipStream_t)stream);
@@ -112,7 +112,7 @@ extern "C" int linetr_sp_conv3x3(LinetrHandle* h, const float* d_x, int32_t B, i
 extern "C" int linetr_sp_conv1a(LinetrHandle* h, const float* d_image, int32_t B, int32_t H, int32_t W, const float* d_w, const float* d_bias,
                                 float* d_y, void* stream) {
   if (B < 1 || B > SP_MAX_B || H < 1 || W < 1 || H > SP_MAX_DIM || W > SP_MAX_DIM) return fail(LINETR_E_ARG, "sp_conv1a: bad shape B=%d H=%d W=%d", B, H, W);
-  if (!aligned16(d_image) || !aligned16(d_w) || !aligned16(d_bias) || !aligned16(d_y)) return fail(LINETR_E_ARG, "sp_conv1a: a NULL or misaligned pointer");
+  if (!there16(d_image) || !there16(d_w) || !there16(d_bias) || !there16(d_y)) return fail(LINETR_E_ARG, "sp_conv1a: a NULL or misaligned pointer");
   if (h) LT_HIP(hipSetDevice(h->device));
   return sp_conv1a_launch(h, d_image, B, H, W, d_w, d_bias, d_y, (hipStream_t)stream);
 }
@@ -149,7 +149,7 @@ extern "C" void linetr_sp_encoder_destroy(LinetrSpEncoder* enc) {
 extern "C" int linetr_sp_encoder_set_weights(LinetrSpEncoder* enc, const float* const* d_weights, const float* const* d_biases, void* stream) {
   if (!enc || !d_weights || !d_biases) return fail(LINETR_E_ARG, "sp_encoder_set_weights: null pointer");
   for (int i = 0; i < 12; ++i)
-    if (!aligned16(d_weights[i]) || !aligned16(d_biases[i])) return fail(LINETR_E_ARG, "sp_encoder_set_weights: tensor %d is NULL or misaligned", i);
+    if (!there16(d_weights[i]) || !there16(d_biases[i])) return fail(LINETR_E_ARG, "sp_encoder_set_weights: tensor %d is NULL or misaligned", i);
   LT_HIP(hipSetDevice(enc->device));
   hipStream_t st = (hipStream_t)stream;
   auto copy = [&](float* dst, const float* src, int n) { return hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, st); };
@@ -183,7 +183,7 @@ extern "C" int linetr_sp_encoder_forward(LinetrSpEncoder* enc, const float* d_im
                                          float* d_desc_rows, float* d_feat, void* d_workspace, int64_t workspace_bytes, void* stream) {
   if (!enc || !enc->has_weights) return fail(LINETR_E_ARG, "sp_encoder_forward: an encoder without weights");
   if (B < 1 || B > SP_MAX_B || H < 8 || W < 8 || H > SP_MAX_DIM || W > SP_MAX_DIM) return fail(LINETR_E_ARG, "sp_encoder_forward: bad shape B=%d H=%d W=%d", B, H, W);
-  if (!aligned16(d_image) || !aligned16(d_score_rows) || !aligned16(d_desc_rows) || !aligned16(d_workspace) || (d_feat && !aligned16(d_feat)))
+  if (!there16(d_image) || !there16(d_score_rows) || !there16(d_desc_rows) || !there16(d_workspace) || (d_feat && !there16(d_feat)))
     return fail(LINETR_E_ARG, "sp_encoder_forward: a NULL or misaligned pointer");
   const SpLayout L = sp_layout(B, H, W);
   if (workspace_bytes < L.total) return fail(LINETR_E_ARG, "sp_encoder_forward: workspace too small (need %lld)", (long long)L.total);

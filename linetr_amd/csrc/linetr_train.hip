@@ -242,7 +242,6 @@ bool lin_dims_ok(int64_t rows, int N, int K) {
   return rows >= 1 && rows <= LB_MAX_ROWS && N > 0 && K > 0 && N % 64 == 0 && K % 32 == 0 && N <= 1024 && K <= 1024;
 }
 bool lin_stride_ok(int64_t ld, int width) { return ld >= width && ld % 4 == 0; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }     // (NULL passes: an absent optional pointer)
 
 // the argument checks of the layer's backward, for `who`; LINETR_OK: nothing is wrong
 int lin_bwd_check(const char* who, const float* d_x, int64_t ldx, const float* d_W, const float* d_g, int64_t ldg, const float* d_mask,

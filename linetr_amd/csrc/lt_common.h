@@ -67,6 +67,8 @@ inline int fail(int code, const char* fmt, ...) {
   } while (0)
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// What every entry point asks of a pointer its kernels access with 16-byte vectors (NULL passes: an absent optional pointer).
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // A workspace carved into 256-byte aligned segments: take(bytes) is the next segment's offset, `o` what has been handed out so far.
 struct Carve {
   int64_t o = 0;

@@ -197,6 +197,8 @@ class Engine(_TrainSurface, _DebugSurface):
     def _f32(self, t: torch.Tensor) -> torch.Tensor:
         if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
             t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.data_ptr() % 16:       # a contiguous view at an odd storage offset: the kernels load and store 16-byte vectors
+            t = t.clone()
         return t
 
     # ------------------------------------------------------------------ host pre-filter
