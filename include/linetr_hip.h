@@ -734,6 +734,67 @@ int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void* d_lines0, 
                      int32_t* d_found, uint8_t* d_match_dir, void* d_overlap_dir, void* d_proj0, void* d_proj1, void* d_workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* ---- fixed-size training samples (the producer of the batches linetr_forward_train, linetr_gt_assign and the criterion consume) ---------- */
+
+/* The pseudo lines conv_fixed_size pads a sample with (dataloaders/utils/util_lines.py:559-617, make_pseudo_lines), host, float64:
+ * n lines h_lines [n][2][2] for image `image_index` of a batch.  Per line: start point (shape0 - min_length - 15, shape1 - min_length
+ * - 15) * U^2, angle 2 pi U, length (160 - min_length) U + min_length, end point = start + length (cos, sin), both coordinates
+ * clipped to [15, shape_i - 15]; the first draw stands unless it came out shorter than min_length, a redraw must be longer (the
+ * reference's two compares).  The reference draws from NumPy's reseeded global generator; here every U is 53 bits of
+ * Philox4x32-10 (the generator of the dropout masks), key = (seed, image_index), counter = (line, attempt, draw, 0): draw 0 gives
+ * the start point (words 0,1 -> x; 2,3 -> y), draw 1 the angle and the length; U = ((hi >> 5) 2^26 + (lo >> 6)) / 2^53.  At most 64
+ * attempts, then the fixed line (15, 15) -> (15 + 2 min_length, 15).  The same (seed, image_index, line) gives the same bits on
+ * every call, whatever n.  LINETR_E_ARG: n < 0, a seed beyond 32 bits, min_length outside (0, 160), a shape without room
+ * (shape_i < 30 + 2 min_length). */
+int linetr_make_pseudo_lines(uint64_t seed, int32_t image_index, int32_t n, double shape0, double shape1, double min_length,
+                             double* h_lines);
+
+/* find_line_attributes (util_lines.py:634-668), host, float64: end points swapped unless sp_x < ep_x, length = sqrt(dx dx + dy dy),
+ * lines shorter than min_length dropped, sorted by descending length under linetr_prefilter's tie rule (equal lengths by descending
+ * original index), cut to [:max_sublines], angles as get_angles (the pre-filter's).  Writes *n_out rows of h_klines [n][2][2],
+ * h_length [n], h_angles [n][2] (each sized for all n lines). */
+int linetr_find_line_attributes(const double* h_lines, int32_t n, double min_length, int32_t max_sublines, double* h_klines,
+                                double* h_length, double* h_angles, int32_t* n_out);
+
+/* The 'klines' branch of conv_fixed_size (dataloaders/utils/util_lines.py:695-766, called at build_homography_dataset.py:205-206) for a
+ * batch of B images, on the device, straight from line records: what linetr_tokenize would emit for image b, padded to M =
+ * max_sublines sub-lines with tokenised pseudo lines or cut to M, in [B, M, ...] tensors.
+ *   d_recs, h_cu_k, h_cu_n     the batch's records (device; image-major, as linetr_prefilter_batch writes them) and the HOST prefix
+ *                              sums [B + 1] of key-lines (num_klns) and sub-lines (num_slns) per image; an image may have none
+ *   d_pseudo, h_pseudo, h_cu_p the pseudo records on the device and the same array on the host, with their HOST prefix sums [B + 1].
+ *                              Image b must bring exactly max(M - num_slns, 0) of them, `image` = b, `line_local` = 0, 1, .. and
+ *                              n_sub = 1 each (linetr_pack_lines with image_index b; first_sub / first_tok are not read)
+ *   clip_height / clip_width   the end-point clip of the real lines (linetr_tokenize's; <= 0: height / width);
+ *   pseudo_clip_height / _width  the one of the pseudo lines: the builder hands conf['data']['resize'] = (640, 480) to line_tokenizer
+ *                              as (height, width), i.e. x <= 479.4 and y <= 639.4 for a 480 x 640 image (util_lines.py:701,713)
+ *   d_dense_desc / d_dense_score, dense_is_nhwc, align_corners   as linetr_tokenize
+ * Outputs, all required, every byte written exactly once by this call (nothing has to be cleared), float32 unless noted:
+ *   out.klines [B,M,2,2], out.length [B,M], out.angles [B,M,2]   real key-lines at [:num_klns], the pseudo key-lines (the tokeniser's
+ *                              float32 copies, clipped end points included) behind them, zeros behind those
+ *   out.sublines [B,M,2,2], out.pnt [B,M,T,2], out.mask [B,M,T+1], out.resp [B,M], out.angle_sub [B,M,2], out.desc [B,M,T,256],
+ *   out.score [B,M,T]          the image's first min(num_slns, M) sub-line rows, then the pseudo rows.  The cut may fall inside a split
+ *                              key-line.  Every row has the bits linetr_tokenize gives it (one device body each)
+ *   out.mat [B,M,M]            eye(M) with the block [:num_klns, :min(num_slns, M)] replaced by the image's mat_klines2sublines: a pseudo
+ *                              sub-line j has its 1 at [j][j], and rows num_klns .. num_slns - 1 keep a diagonal 1 (the reference's)
+ *   d_num_klns, d_num_slns [B] int32   the counts before padding / truncation
+ * Superset of the reference: an image without a surviving line is M pseudo lines with num_klns = num_slns = 0 (the reference raises).
+ * Three launches (+ the layout pass of an NCHW map, + one small launch per 32 images that carries the prefix sums): nothing var-len is
+ * materialised, tokens, scores and descriptors go straight to their final rows.  Asynchronous on `stream`; nothing inside allocates or
+ * waits; the host arrays are read before the call returns; `h` may be NULL.  LINETR_E_ARG, nothing launched, no output changed: B < 1
+ * (or above 65 535), height / width no multiple of 8, M outside 1 .. 32 768, T outside 1 .. 4096, token_distance <= 0, B M T beyond
+ * 2^33, a NULL pointer, prefix sums that do not start at 0 or ascend, an image with more key-lines than M (the reference raises
+ * there), a pseudo count other than max(M - num_slns, 0), a pseudo line that does not make exactly one sub-line, a channel-last map,
+ * out.desc or workspace that is not 16-byte aligned.  LINETR_E_WORKSPACE, nothing launched: a workspace smaller than
+ * linetr_fixed_size_workspace_bytes says. */
+int64_t linetr_fixed_size_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t dense_is_nhwc);
+int linetr_fixed_size(LinetrHandle* h, const LinetrLineRec* d_recs, const int32_t* h_cu_k, const int32_t* h_cu_n,
+                      const LinetrLineRec* d_pseudo, const LinetrLineRec* h_pseudo, const int32_t* h_cu_p, int32_t n_images,
+                      int32_t max_sublines, int32_t max_tokens, double token_distance, const float* d_dense_desc,
+                      const float* d_dense_score, int32_t height, int32_t width, int32_t clip_height, int32_t clip_width,
+                      int32_t pseudo_clip_height, int32_t pseudo_clip_width, int32_t align_corners, int32_t dense_is_nhwc,
+                      LinetrTokens out, int32_t* d_num_klns, int32_t* d_num_slns, void* d_workspace, int64_t workspace_bytes,
+                      void* stream);
+
 /* ---- the optimizer step (section 8(f) "next" row 4: the line that changes the weights) ---------- */
 
 /* torch.optim.Adam as the reference builds it (train.py:82) and steps it (:195), over a table of tensors in ONE launch, and the global

@@ -173,6 +173,11 @@ ABI = {
     "linetr_token_assemble_backward": (i32, [vp, vp, i64, i32, vp, vp, vp, i64, vp]),
     "linetr_gt_assign_workspace_bytes": (i64, [i32, i32, i32]),
     "linetr_gt_assign": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, f64, f64, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_make_pseudo_lines": (i32, [C.c_uint64, i32, i32, f64, f64, f64, vp]),
+    "linetr_find_line_attributes": (i32, [vp, i32, f64, i32, vp, vp, vp, _P(i32)]),
+    "linetr_fixed_size_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_fixed_size": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, Tokens, vp, vp,
+                                vp, i64, vp]),
     "linetr_adam_workspace_bytes": (i64, [i32, i64]),
     "linetr_adam_step": (i32, [vp, vp, i32, _P(AdamHyper), vp, vp, i64, vp]),
     "linetr_grad_norm_workspace_bytes": (i64, [i32, i64]),

@@ -521,6 +521,84 @@ extern "C" int linetr_pack_lines(const double* h_klines, const double* h_length,
   return LINETR_OK;
 }
 
+// ---- pseudo lines of the fixed-size training samples (dataloaders/utils/util_lines.py:559-668), float64 on the host ----------------
+
+struct KeptLineAttr { double sp[2], ep[2], length; };
+// one uniform double in [0, 1) from two Philox words: 53 bits, (hi >> 5) 2^26 + (lo >> 6) over 2^53
+static double philox_u01(uint32_t hi, uint32_t lo) { return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) / 9007199254740992.0; }
+
+extern "C" int linetr_make_pseudo_lines(uint64_t seed, int32_t image_index, int32_t n, double shape0, double shape1, double min_length,
+                                        double* h_lines) {
+#pragma clang fp contract(off)
+  constexpr double MASK = 15.0, MAX_RAND = 160.0;
+  constexpr int MAX_ATTEMPTS = 64;
+  if (n < 0 || (n > 0 && !h_lines) || image_index < 0 || seed >> 32) return fail(LINETR_E_ARG, "make_pseudo_lines: bad argument (a 32-bit seed, n >= 0)");
+  if (!(min_length > 0) || !(min_length < MAX_RAND) || !(shape0 - MASK >= MASK + 2 * min_length) || !(shape1 - MASK >= MASK + 2 * min_length))
+    return fail(LINETR_E_ARG, "make_pseudo_lines: image_shape (%g, %g) has no room for lines of min_length %g", shape0, shape1, min_length);
+  const double area0 = shape0 - min_length - MASK, area1 = shape1 - min_length - MASK;     // util_lines.py:563
+  for (int i = 0; i < n; ++i) {
+    double* l = h_lines + (size_t)i * 4;
+    int attempt = 0;
+    for (; attempt < MAX_ATTEMPTS; ++attempt) {
+      uint32_t a[4], b[4];
+      philox4x32_10((uint32_t)i, (uint32_t)attempt, 0u, 0u, (uint32_t)seed, (uint32_t)image_index, a);
+      philox4x32_10((uint32_t)i, (uint32_t)attempt, 1u, 0u, (uint32_t)seed, (uint32_t)image_index, b);
+      const double sx = area0 * philox_u01(a[0], a[1]), sy = area1 * philox_u01(a[2], a[3]);        // :568
+      const double ang = 2 * M_PI * philox_u01(b[0], b[1]);                                          // :571
+      const double len = (MAX_RAND - min_length) * philox_u01(b[2], b[3]) + min_length;              // :573
+      const double ex = sx + len * std::cos(ang), ey = sy + len * std::sin(ang);                     // :574-575
+      l[0] = std::min(std::max(sx, MASK), shape0 - MASK);                                            // :576-577
+      l[1] = std::min(std::max(sy, MASK), shape1 - MASK);
+      l[2] = std::min(std::max(ex, MASK), shape0 - MASK);
+      l[3] = std::min(std::max(ey, MASK), shape1 - MASK);
+      const double dx = l[2] - l[0], dy = l[3] - l[1];
+      const double length = std::sqrt(dx * dx + dy * dy);
+      // the first draw stands unless it is shorter than min_length (:588); a redraw has to be longer (:610)
+      if (attempt == 0 ? !(length < min_length) : length > min_length) break;
+    }
+    if (attempt == MAX_ATTEMPTS) {   // the reference would loop on: a fixed valid line instead
+      l[0] = MASK; l[1] = MASK; l[2] = MASK + 2 * min_length; l[3] = MASK;
+    }
+  }
+  return LINETR_OK;
+}
+
+extern "C" int linetr_find_line_attributes(const double* h_lines, int32_t n, double min_length, int32_t max_sublines, double* h_klines,
+                                           double* h_length, double* h_angles, int32_t* n_out) {
+#pragma clang fp contract(off)
+  if (n < 0 || (n > 0 && (!h_lines || !h_klines || !h_length || !h_angles)) || !n_out) return fail(LINETR_E_ARG, "find_line_attributes: null argument");
+  std::vector<KeptLineAttr> keep;
+  keep.reserve(n);
+  for (int i = 0; i < n; ++i) {
+    const double* l = h_lines + (size_t)i * 4;
+    KeptLineAttr r;
+    if (l[0] < l[2]) { r.sp[0] = l[0]; r.sp[1] = l[1]; r.ep[0] = l[2]; r.ep[1] = l[3]; }      // :641-646
+    else { r.sp[0] = l[2]; r.sp[1] = l[3]; r.ep[0] = l[0]; r.ep[1] = l[1]; }
+    const double dx = r.ep[0] - r.sp[0], dy = r.ep[1] - r.sp[1];
+    r.length = std::sqrt(dx * dx + dy * dy);                                                    // :648
+    if (r.length < min_length) continue;                                                        // :649
+    keep.push_back(r);
+  }
+  // np.argsort, reversed (:662-663), under linetr_prefilter's tie rule: a stable ascending order read backwards
+  std::vector<std::pair<double, int>> order(keep.size());
+  for (size_t i = 0; i < keep.size(); ++i) order[i] = {keep[i].length, (int)i};
+  std::stable_sort(order.begin(), order.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
+  int64_t n_keep = (int64_t)order.size();
+  if (max_sublines < 0) n_keep = std::max<int64_t>(0, n_keep + max_sublines);                   // python slice [:m]
+  else n_keep = std::min<int64_t>(n_keep, max_sublines);
+  for (int64_t i = 0; i < n_keep; ++i) {
+    const KeptLineAttr& kl = keep[order[order.size() - 1 - i].second];
+    LinetrLineRec r{};
+    r.sp[0] = kl.sp[0]; r.sp[1] = kl.sp[1]; r.ep[0] = kl.ep[0]; r.ep[1] = kl.ep[1];
+    angle_of(r);                                                                                // get_angles, :619-632
+    h_klines[i * 4 + 0] = kl.sp[0]; h_klines[i * 4 + 1] = kl.sp[1]; h_klines[i * 4 + 2] = kl.ep[0]; h_klines[i * 4 + 3] = kl.ep[1];
+    h_length[i] = kl.length;
+    h_angles[i * 2 + 0] = r.angle[0]; h_angles[i * 2 + 1] = r.angle[1];
+  }
+  *n_out = (int32_t)n_keep;
+  return LINETR_OK;
+}
+
 // filter + sort of one image (records carry geometry/length/angle only).  `emit(n)` is called once with the number of surviving
 // lines and returns where to write them: straight into the caller's record array on the single-thread path (a record is 80 bytes;
 // the earlier form copied every survivor three times).

@@ -8,6 +8,7 @@
 //   lt_dropout.h    the dropout instances of that pooling and LayerNorm
 //   lt_posbwd.h     the positional encoders' input layer and the token assembly with their backwards
 //   lt_gtassign.h   the ground-truth line assignment in front of them
+//   lt_fixedsize.h  the fixed-size samples (pseudo-line padding / truncation) in front of that
 //   lt_adam.h       the optimizer step behind them, with the gradient norm that can feed it
 #include <algorithm>
 
@@ -21,6 +22,7 @@
 #include "lt_dropout.h"
 #include "lt_posbwd.h"
 #include "lt_gtassign.h"
+#include "lt_fixedsize.h"
 #include "lt_adam.h"
 
 using namespace lt;
@@ -1035,6 +1037,109 @@ extern "C" int linetr_gt_assign(LinetrHandle* h, int32_t coord_type, const void*
   return gt_assign_launch<double>(h, st, L, d_lines0, n0, d_lines1, n1, d_H, B, d_count0, d_count1, thres_reprojected, thres_angdiff,
                                   min_overlap_ratio, pad, d_assign, d_lmatches, M, d_found, d_match_dir, d_overlap_dir, d_proj0,
                                   d_proj1, (char*)d_ws);
+}
+
+// =============================================================================================
+// fixed-size training samples: pseudo-line padding / truncation of the tokeniser's tensors (lt_fixedsize.h)
+// =============================================================================================
+
+namespace {
+constexpr int FS_MAX_B = 65535, FS_MAX_M = 32768;
+struct FsLayout { int64_t o_table, o_nhwc, total; };
+FsLayout fs_layout(int B, int height, int width, int dense_is_nhwc) {
+  FsLayout L{};
+  Carve c;
+  L.o_table = c.take((int64_t)B * sizeof(FsImage));
+  L.o_nhwc = c.take(dense_is_nhwc ? 0 : (int64_t)B * (height / 8) * (width / 8) * D * 4);
+  L.total = c.o;
+  return L;
+}
+bool fs_dims_ok(int B, int height, int width) {
+  return B > 0 && B <= FS_MAX_B && height >= 8 && width >= 8 && height % 8 == 0 && width % 8 == 0 && height <= 32768 && width <= 32768;
+}
+}  // namespace
+
+extern "C" int64_t linetr_fixed_size_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t dense_is_nhwc) {
+  return fs_dims_ok(n_images, height, width) ? fs_layout(n_images, height, width, dense_is_nhwc).total : 0;
+}
+
+extern "C" int linetr_fixed_size(LinetrHandle* h, const LinetrLineRec* d_recs, const int32_t* h_cu_k, const int32_t* h_cu_n,
+                                 const LinetrLineRec* d_pseudo, const LinetrLineRec* h_pseudo, const int32_t* h_cu_p, int32_t B,
+                                 int32_t M, int32_t T, double td, const float* d_dense_desc, const float* d_dense_score, int32_t height,
+                                 int32_t width, int32_t clip_height, int32_t clip_width, int32_t pseudo_clip_height,
+                                 int32_t pseudo_clip_width, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
+                                 int32_t* d_num_klns, int32_t* d_num_slns, void* d_ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch
+  if (!fs_dims_ok(B, height, width)) return fail(LINETR_E_ARG, "fixed_size: bad shape B=%d height=%d width=%d", B, height, width);
+  if (M < 1 || M > FS_MAX_M || T < 1 || T > 4096 || !(td > 0)) return fail(LINETR_E_ARG, "fixed_size: bad max_sublines / max_tokens / token_distance");
+  if (((int64_t)B * M * T + 3) / 4 > INT32_MAX) return fail(LINETR_E_ARG, "fixed_size: B * max_sublines * max_tokens beyond 2^33 tokens");
+  if (!h_cu_k || !h_cu_n || !h_cu_p || !d_dense_desc || !d_dense_score || !out.klines || !out.length || !out.angles || !out.sublines ||
+      !out.pnt || !out.mask || !out.resp || !out.angle_sub || !out.desc || !out.score || !out.mat || !d_num_klns || !d_num_slns || !d_ws)
+    return fail(LINETR_E_ARG, "fixed_size: null pointer");
+  if (clip_height <= 0) clip_height = height;
+  if (clip_width <= 0) clip_width = width;
+  if (pseudo_clip_height <= 0) pseudo_clip_height = height;
+  if (pseudo_clip_width <= 0) pseudo_clip_width = width;
+  if (h_cu_k[0] != 0 || h_cu_n[0] != 0 || h_cu_p[0] != 0) return fail(LINETR_E_ARG, "fixed_size: prefix sums must start at 0");
+  for (int b = 0; b < B; ++b) {
+    const int64_t nk = (int64_t)h_cu_k[b + 1] - h_cu_k[b], ns = (int64_t)h_cu_n[b + 1] - h_cu_n[b], np = (int64_t)h_cu_p[b + 1] - h_cu_p[b];
+    if (nk < 0 || ns < nk || np < 0) return fail(LINETR_E_ARG, "fixed_size: image %d: prefix sums must ascend, with at least one sub-line per key-line", b);
+    if (nk > M)
+      return fail(LINETR_E_ARG, "fixed_size: image %d has %lld key-lines, more than max_sublines = %d (the reference raises there)", b, (long long)nk, M);
+    const int64_t n_add = std::max<int64_t>(M - ns, 0);
+    if (np != n_add) return fail(LINETR_E_ARG, "fixed_size: image %d needs %lld pseudo lines, got %lld", b, (long long)n_add, (long long)np);
+    if (np > 0 && !h_pseudo) return fail(LINETR_E_ARG, "fixed_size: null pointer");
+    for (int64_t p = h_cu_p[b]; p < h_cu_p[b + 1]; ++p) {
+      const LinetrLineRec& r = h_pseudo[p];
+      if (r.n_sub != 1 || r.n_tok < 1 || r.n_tok > T)
+        return fail(LINETR_E_ARG, "fixed_size: pseudo line %lld of image %d makes %d sub-lines (%d tokens), every one must make exactly one",
+                    (long long)(p - h_cu_p[b]), b, r.n_sub, r.n_tok);
+      if (r.image != b || r.line_local != p - h_cu_p[b]) return fail(LINETR_E_ARG, "fixed_size: pseudo record %lld is not line %lld of image %d", (long long)p, (long long)(p - h_cu_p[b]), b);
+    }
+  }
+  if ((h_cu_k[B] > 0 && !d_recs) || (h_cu_p[B] > 0 && !d_pseudo)) return fail(LINETR_E_ARG, "fixed_size: null pointer");
+  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(out.desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "fixed_size: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned");
+  const FsLayout L = fs_layout(B, height, width, dense_is_nhwc);
+  if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "fixed_size: workspace too small (need %lld)", (long long)L.total);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  FsImage* table = (FsImage*)((char*)d_ws + L.o_table);
+  for (int first = 0; first < B; first += FS_TABLE_CHUNK) {
+    FsChunk c{};
+    const int count = std::min(FS_TABLE_CHUNK, B - first);
+    for (int i = 0; i < count; ++i) {
+      const int b = first + i;
+      c.img[i] = FsImage{h_cu_k[b], h_cu_k[b + 1] - h_cu_k[b], h_cu_n[b], h_cu_n[b + 1] - h_cu_n[b], h_cu_p[b], h_cu_p[b + 1] - h_cu_p[b]};
+    }
+    hipLaunchKernelGGL(fs_table_kernel, dim3(1), dim3(64), 0, st, c, first, count, table);
+    LT_LAUNCH_CHECK();
+  }
+  const int Hc = height / 8, Wc = width / 8;
+  const int64_t rows = (int64_t)B * M, ntok = rows * T;
+  {
+    ProfScope ps(h, st, "fixed_size_rows", 0, (double)rows * (T * 16.0 + M * 4.0 + 64.0));
+    hipLaunchKernelGGL(fs_rows_kernel, dim3((unsigned)rows), dim3(64), 0, st, d_recs, d_pseudo, table, M, td, T, height, width,
+                       (double)clip_width - 0.6, (double)clip_height - 0.6, (double)pseudo_clip_width - 0.6, (double)pseudo_clip_height - 0.6,
+                       d_dense_score, out.klines, out.length, out.angles, out.sublines, out.pnt, out.mask, out.resp, out.angle_sub, out.score,
+                       out.mat, d_num_klns, d_num_slns);
+    LT_LAUNCH_CHECK();
+  }
+  const float* nhwc = d_dense_desc;
+  if (!dense_is_nhwc) {
+    float* buf = (float*)((char*)d_ws + L.o_nhwc);
+    ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * B * Hc * Wc * D * 4);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(Hc * Wc, 64), D / 64, B), dim3(256), 0, st, d_dense_desc, buf, D, Hc * Wc);
+    LT_LAUNCH_CHECK();
+    nhwc = buf;
+  }
+  {
+    ProfScope ps(h, st, "fixed_size_desc", 0, (double)ntok * D * 4 * 2);
+    hipLaunchKernelGGL(fs_sample_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, ntok, (int64_t)M * T, nhwc, Hc, Wc,
+                       align_corners, out.desc);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
 }
 
 // =============================================================================================

@@ -102,6 +102,30 @@ inline int cu_count() {
   return n_cu;
 }
 
+// Philox4x32-10 (Salmon et al., SC'11), the standard multipliers and key increments.  Host and device: the dropout masks of
+// lt_dropout.h draw from it in their kernels, the pseudo lines of linetr_make_pseudo_lines on the host.
+__host__ __device__ __forceinline__ uint32_t philox_mulhi(uint32_t a, uint32_t b) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __umulhi(a, b);
+#else
+  return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32);
+#endif
+}
+__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&w)[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = philox_mulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = philox_mulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
 // ---- device helpers -------------------------------------------------------------------------
 
 // constants of the CLS-row attention pooling (lt_model.h: the cls_pool kernels; prepared in float64 by linetr_create)

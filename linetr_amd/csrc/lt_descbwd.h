@@ -49,22 +49,6 @@ struct DropArgs {          // LinetrDropout as the kernels take it; a plain inst
   float scale;
 };
 
-// Philox4x32-10 (Salmon et al., SC'11), the standard multipliers and key increments
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&w)[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
 // the four factors of (inner, row) at `site`
 __device__ __forceinline__ void drop_factors(const DropArgs& dr, uint32_t site, uint32_t row, uint32_t inner, float (&f)[4]) {
   uint32_t w[4];

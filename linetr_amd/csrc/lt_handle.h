@@ -5,7 +5,8 @@
 //                     experiments/csrc/lt_x_net.h into it: the host code of its alternative paths and the hooks that select them)
 //   linetr_match.hip  matcher, dense-map producer, slab packing, SuperPoint's key-point branch
 //   linetr_train.hip  training and evaluation: validation step, criterion gradient, backward of the 1x1 layers, the descriptor head and
-//                     the neighbour-line attention, ground-truth line assignment
+//                     the neighbour-line attention, ground-truth line assignment, fixed-size samples (lt_fixedsize.h over lt_token.h,
+//                     whose kernels are static: the header is compiled into this unit and into linetr_net.hip)
 //   linetr_sp.hip     the native SuperPoint encoder (its own LinetrSpEncoder object; no LinetrHandle state)
 //   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once

@@ -11,7 +11,7 @@ namespace lt {
 // row (SuperPoint emits [1,256,H/8,W/8], models/superpoint.py:193).  32x32 LDS-tiled transpose.
 // grid (P/64 ceil, C/64, B), block 256
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out,
+static __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                            int C, int P) {
   // 64 channels x 64 positions per block, dwordx4 on both sides: reads 16 B along p (NCHW rows), writes 16 B along c
   // (NHWC rows).  LDS tile [64 c][64 p + 1]: the odd stride keeps the 4-way column gather conflict-free.
@@ -57,22 +57,26 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
 // per key-line: float32 copies of klines/length/angles (models/line_process.py:182-184, with the
 // end-point clip of :114-116 already applied) and the sub-line -> key-line maps.
 // ---------------------------------------------------------------------------------------------
-__global__ void line_fill_kernel(const LinetrLineRec* __restrict__ recs, int K, double wclip, double hclip,
+// one key-line's row of the three arrays (also the rows of lt_fixedsize.h)
+__device__ __forceinline__ void kline_row(const LinetrLineRec& r, double wclip, double hclip, float* __restrict__ kline,
+                                          float* __restrict__ length, float* __restrict__ angle) {
+  kline[0] = (float)r.sp[0];
+  kline[1] = (float)r.sp[1];
+  kline[2] = (float)fmin(r.ep[0], wclip);
+  kline[3] = (float)fmin(r.ep[1], hclip);
+  *length = (float)r.length;
+  angle[0] = (float)r.angle[0];
+  angle[1] = (float)r.angle[1];
+}
+
+static __global__ void line_fill_kernel(const LinetrLineRec* __restrict__ recs, int K, double wclip, double hclip,
                                  float* __restrict__ klines, float* __restrict__ length,
                                  float* __restrict__ angles, int* __restrict__ sub2line_g,
                                  int* __restrict__ sub2line_l) {
   int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
   const LinetrLineRec r = recs[k];
-  if (klines) {
-    klines[k * 4 + 0] = (float)r.sp[0];
-    klines[k * 4 + 1] = (float)r.sp[1];
-    klines[k * 4 + 2] = (float)fmin(r.ep[0], wclip);
-    klines[k * 4 + 3] = (float)fmin(r.ep[1], hclip);
-    length[k] = (float)r.length;
-    angles[k * 2 + 0] = (float)r.angle[0];
-    angles[k * 2 + 1] = (float)r.angle[1];
-  }
+  if (klines) kline_row(r, wclip, hclip, klines + k * 4, length + k, angles + k * 2);
   for (int s = 0; s < r.n_sub; ++s) {
     sub2line_g[r.first_sub + s] = k;
     if (sub2line_l) sub2line_l[r.first_sub + s] = r.line_local;
@@ -84,6 +88,9 @@ __global__ void line_fill_kernel(const LinetrLineRec* __restrict__ recs, int K, 
 constexpr int K2S_MAX_IMAGES = 8;
 struct K2sImage { int64_t off; int n_sub; int sub_base; };
 struct K2sTable { K2sImage img[K2S_MAX_IMAGES]; };
+
+// a key-line's entry of mat_klines2sublines over its own sub-lines: Python's 1 / num is a float64 quotient stored as float32
+__device__ __forceinline__ float k2s_weight(const LinetrLineRec& r) { return (float)(1.0 / (double)r.n_sub); }
 
 // point at arclength `d` from sp along sp->ep in the reference's slope form, float64, no FMA
 // contraction (models/line_process.py:43-57).
@@ -103,44 +110,14 @@ __device__ __forceinline__ void walk_along(const double sp[2], const double ep[2
   y = dy + sp[1];
 }
 
-// ---------------------------------------------------------------------------------------------
-// One 64-thread block per sub-line; thread t < T produces token t.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void tokenize_kernel(
-    const LinetrLineRec* __restrict__ recs, const int* __restrict__ sub2line_g, int N, double td, int T,
-    int height, int width, double clip_x, double clip_y, const float* __restrict__ dense_score, float* __restrict__ sublines,
-    float* __restrict__ pnt, float* __restrict__ mask, float* __restrict__ resp,
-    float* __restrict__ angle_sub, float* __restrict__ score, float* __restrict__ cpnt,
-    float* __restrict__ cscore, int n_pad_images, int64_t first_pad, float* __restrict__ mat_k2s, const K2sTable k2s) {
+// One sub-line's rows of the tokeniser's tensors: sub-line `j` of key-line `r`, written at row `n` of every output (the tokeniser: the
+// batch-wide sub-line index; lt_fixedsize.h: row b * max_sublines + j' of the fixed-size sample).  One 64-thread block.
+__device__ __forceinline__ void tokenize_subline(
+    const LinetrLineRec& r, int j, int n, double td, int T, int height, int width, double clip_x, double clip_y,
+    const float* __restrict__ dense_score, float* __restrict__ sublines, float* __restrict__ pnt, float* __restrict__ mask,
+    float* __restrict__ resp, float* __restrict__ angle_sub, float* __restrict__ score, float* __restrict__ cpnt,
+    float* __restrict__ cscore) {
 #pragma clang fp contract(off)
-  const int n = blockIdx.x;
-  if (n >= N) {
-    const int pad_blocks = (n_pad_images + 63) / 64;
-    if (n - N < pad_blocks) {
-      // blocks past the sub-lines: one shared padding token per image for the compact token list -- coordinate (0, 0), score
-      // dense_score[img][0][0] (the reference pads with zeros and gathers the score at the rounded coordinate, line_process.py:174-179)
-      const int i = (n - N) * 64 + threadIdx.x;
-      if (i < n_pad_images) {
-        cpnt[(first_pad + i) * 2 + 0] = 0.f;
-        cpnt[(first_pad + i) * 2 + 1] = 0.f;
-        cscore[first_pad + i] = dense_score[(int64_t)i * height * width];
-      }
-      return;
-    }
-    // one more block per key-line (calls of up to K2S_MAX_IMAGES images): its row of the image's mat_klines2sublines [K_i][N_i],
-    // 1 / num_sublines over the key-line's own sub-lines and 0 elsewhere (line_process.py:160-165; Python's 1/num is a float64
-    // quotient stored as float32)
-    const int k = n - N - pad_blocks;
-    const LinetrLineRec r = recs[k];
-    const K2sImage im = k2s.img[r.image & (K2S_MAX_IMAGES - 1)];
-    float* row = mat_k2s + im.off + (int64_t)r.line_local * im.n_sub;
-    const float w = (float)(1.0 / (double)r.n_sub);
-    const int j0 = r.first_sub - im.sub_base;
-    for (int j = threadIdx.x; j < im.n_sub; j += 64) row[j] = (j >= j0 && j < j0 + r.n_sub) ? w : 0.f;
-    return;
-  }
-  const LinetrLineRec r = recs[sub2line_g[n]];
-  const int j = n - r.first_sub;  // sub-line index inside its key-line
   // end-point clip of line_process.py:115-116: the limits come from the `image_shape` ARGUMENT of line_tokenizer (width - 0.6,
   // height - 0.6), which need not be the score map's shape (the dataset builder passes (640, 480) for a 480 x 640 image)
   const double epc[2] = {fmin(r.ep[0], clip_x), fmin(r.ep[1], clip_y)};
@@ -192,6 +169,47 @@ __global__ __launch_bounds__(64) void tokenize_kernel(
     angle_sub[(int64_t)n * 2 + 0] = (float)r.angle[0];                        // :151
     angle_sub[(int64_t)n * 2 + 1] = (float)r.angle[1];
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// One 64-thread block per sub-line; thread t < T produces token t.
+// ---------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(64) void tokenize_kernel(
+    const LinetrLineRec* __restrict__ recs, const int* __restrict__ sub2line_g, int N, double td, int T,
+    int height, int width, double clip_x, double clip_y, const float* __restrict__ dense_score, float* __restrict__ sublines,
+    float* __restrict__ pnt, float* __restrict__ mask, float* __restrict__ resp,
+    float* __restrict__ angle_sub, float* __restrict__ score, float* __restrict__ cpnt,
+    float* __restrict__ cscore, int n_pad_images, int64_t first_pad, float* __restrict__ mat_k2s, const K2sTable k2s) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x;
+  if (n >= N) {
+    const int pad_blocks = (n_pad_images + 63) / 64;
+    if (n - N < pad_blocks) {
+      // blocks past the sub-lines: one shared padding token per image for the compact token list -- coordinate (0, 0), score
+      // dense_score[img][0][0] (the reference pads with zeros and gathers the score at the rounded coordinate, line_process.py:174-179)
+      const int i = (n - N) * 64 + threadIdx.x;
+      if (i < n_pad_images) {
+        cpnt[(first_pad + i) * 2 + 0] = 0.f;
+        cpnt[(first_pad + i) * 2 + 1] = 0.f;
+        cscore[first_pad + i] = dense_score[(int64_t)i * height * width];
+      }
+      return;
+    }
+    // one more block per key-line (calls of up to K2S_MAX_IMAGES images): its row of the image's mat_klines2sublines [K_i][N_i],
+    // 1 / num_sublines over the key-line's own sub-lines and 0 elsewhere (line_process.py:160-165; Python's 1/num is a float64
+    // quotient stored as float32)
+    const int k = n - N - pad_blocks;
+    const LinetrLineRec r = recs[k];
+    const K2sImage im = k2s.img[r.image & (K2S_MAX_IMAGES - 1)];
+    float* row = mat_k2s + im.off + (int64_t)r.line_local * im.n_sub;
+    const float w = k2s_weight(r);
+    const int j0 = r.first_sub - im.sub_base;
+    for (int j = threadIdx.x; j < im.n_sub; j += 64) row[j] = (j >= j0 && j < j0 + r.n_sub) ? w : 0.f;
+    return;
+  }
+  const LinetrLineRec r = recs[sub2line_g[n]];
+  tokenize_subline(r, n - r.first_sub, n, td, T, height, width, clip_x, clip_y, dense_score, sublines, pnt, mask, resp, angle_sub, score,
+                   cpnt, cscore);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -326,7 +344,7 @@ __device__ __forceinline__ f32x4 sample_one(float px, float py, const float* __r
   return o;
 }
 
-__global__ __launch_bounds__(256) void sample_desc_kernel(
+static __global__ __launch_bounds__(256) void sample_desc_kernel(
     const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs,
     int64_t n_tokens, int T, const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
     float* __restrict__ desc) {
@@ -348,7 +366,7 @@ constexpr size_t KP_DESC_LDS = (size_t)D * KP_DESC_LS * 4;
 // key point (sample_one), staged through LDS [256][65] so that the store along n is contiguous: image b owns [256][n_b] floats at
 // out + 256 cu_kp[b].  grid ceil(n_total / 64) + B (an upper bound of the chunks; the block finds its image in cu_kp), block 256,
 // dynamic LDS KP_DESC_LDS.
-__global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
+static __global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
                                                          const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
                                                          float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float kp_tile[];

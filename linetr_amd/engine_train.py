@@ -610,6 +610,87 @@ class _TrainSurface:
         self._call("linetr_grad_norm", table.ctypes.data, len(table), float(max_norm), norm.data_ptr(), scale.data_ptr(), ws.data_ptr(), ws.numel())
         return norm, scale
 
+    # ------------------------------------------------------------------ fixed-size training samples (csrc/lt_fixedsize.h)
+    FIXED_SIZE_SHAPES = (("klines", ("M", 2, 2)), ("length_klines", ("M",)), ("angles", ("M", 2)), ("sublines", ("M", 2, 2)),
+                         ("pnt_sublines", ("M", "T", 2)), ("mask_sublines", ("M", "S", 1)), ("resp_sublines", ("M", 1)),
+                         ("angle_sublines", ("M", 2)), ("desc_sublines", ("M", "T", D)), ("score_sublines", ("M", "T", 1)),
+                         ("mat_klines2sublines", ("M", "M")))
+    _FIXED_SIZE_FIELDS = ("klines", "length", "angles", "sublines", "pnt", "mask", "resp", "angle_sub", "desc", "score", "mat")
+
+    @classmethod
+    def fixed_size_shapes(cls, B, max_sublines, max_tokens):
+        """{key: shape} of the float32 tensors fixed_size_batch returns"""
+        dims = {"M": int(max_sublines), "T": int(max_tokens), "S": int(max_tokens) + 1}
+        return {k: (int(B), *(dims.get(d, d) for d in sh)) for k, sh in cls.FIXED_SIZE_SHAPES}
+
+    def fixed_size_batch(self, recs, cu_k, cu_n, dense_desc, dense_score, *, max_sublines, token_distance, max_tokens, min_length=16,
+                         resize=(640, 480), seed=None, pseudo_lines=None, dense_layout="nchw", align_corners=False, clip_shape=None,
+                         out=None):
+        """Fixed-size training samples of a batch in one native call (linetr_fixed_size): the 'klines' branch of the reference's
+        conv_fixed_size (dataloaders/utils/util_lines.py:695-766) applied to what `preprocess` returns for each image, without the
+        per-image tensors ever existing.  recs, cu_k, cu_n: the pre-filter's (prefilter / pack_many); dense maps as tokenize takes
+        them; clip_shape: tokenize's, for the real lines.
+
+        Image b with num_slns < max_sublines is padded with max_sublines - num_slns tokenised pseudo lines, clipped as the dataset
+        builder clips them: `resize` = conf['data']['resize'] reaches line_tokenizer as (height, width).  The lines are
+        `pseudo_lines[b]` = {'klines', 'length_klines', 'angles'} (float64, as find_line_attributes returns them; None or absent
+        where none is needed), or, with pseudo_lines=None, util_lines.make_pseudo_lines + find_line_attributes with the Philox stream
+        of (seed, b) -- seed None is 0.  Every pseudo line must make exactly one sub-line.  An image with num_slns >= max_sublines
+        is cut to its first max_sublines sub-lines; more key-lines than max_sublines is refused, as the reference raises.  An image
+        with no line at all is all pseudo lines (the reference raises there).
+
+        Returns a dict of device tensors under the reference's key names with leading axis B (fixed_size_shapes), num_klns /
+        num_slns (int64 [B], the counts before padding or truncation) and 'pseudo_lines': the host float64 dicts used, one per
+        image (None where none was needed).  `out`: float32 device tensors to write into instead of new ones.  No host wait."""
+        from . import util_lines
+        cu_k32, cu_n32 = (np.ascontiguousarray(c, dtype=np.int32) for c in (cu_k, cu_n))
+        B = len(cu_k32) - 1
+        M, T = int(max_sublines), int(max_tokens)
+        if B < 1 or len(cu_n32) != B + 1:
+            raise ValueError("fixed_size_batch: cu_k and cu_n must hold B + 1 >= 2 prefix sums")
+        dense_desc, dense_score, H, W, nhwc = self._dense_maps(dense_desc, dense_score, B, dense_layout)
+        n_add = np.maximum(M - np.diff(cu_n32).astype(np.int64), 0)
+        if pseudo_lines is None:
+            pseudo_lines = [util_lines.find_line_attributes(util_lines.make_pseudo_lines(int(n), resize, seed=seed or 0, image=b), min_length, M)
+                            if n else None for b, n in enumerate(n_add)]
+        pseudo_lines = list(pseudo_lines) + [None] * (B - len(pseudo_lines))
+        if len(pseudo_lines) != B:
+            raise ValueError(f"fixed_size_batch: {len(pseudo_lines)} pseudo-line sets for {B} images")
+        counts = [0 if p is None else len(p["klines"]) for p in pseudo_lines]
+        cu_p = np.zeros(B + 1, dtype=np.int32)
+        np.cumsum(counts, out=cu_p[1:])
+        precs = np.zeros(max(int(cu_p[-1]), 1), dtype=nat.REC_DTYPE)
+        n_out = C.c_int32()
+        for b, p in enumerate(pseudo_lines):
+            if counts[b]:
+                kl, ln, an = (np.ascontiguousarray(p[k], dtype=np.float64) for k in ("klines", "length_klines", "angles"))
+                nat.check(self._L.linetr_pack_lines(nat.np_ptr(kl), nat.np_ptr(ln), nat.np_ptr(an), counts[b], float(token_distance), T, b, 0, 0,
+                                                    nat.np_ptr(precs[cu_p[b]:cu_p[b + 1]]), C.byref(n_out)), self._L)
+        shapes = self.fixed_size_shapes(B, M, T)
+        f = dict(dtype=torch.float32, device=self.device)
+        if out is None:
+            out = {k: torch.empty(sh, **f) for k, sh in shapes.items()}
+        for k, sh in shapes.items():
+            t = out[k]
+            if tuple(t.shape) != sh or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"fixed_size_batch: out['{k}'] must be a contiguous float32 {sh} tensor on {self.device}")
+        counts_dev = torch.empty((2, B), dtype=torch.int32, device=self.device)
+        K = int(cu_k32[-1])
+        d_recs = torch.from_numpy(np.ascontiguousarray(recs[:K]).view(np.uint8).reshape(-1).copy()).to(self.device) if K else None
+        d_precs = torch.from_numpy(precs.view(np.uint8).reshape(-1)).to(self.device) if int(cu_p[-1]) else None
+        ct = nat.Tokens()
+        for field, key in zip(self._FIXED_SIZE_FIELDS, shapes):
+            setattr(ct, field, out[key].data_ptr())
+        ws = self._stream_workspace("fixed_size", self._L.linetr_fixed_size_workspace_bytes(B, H, W, int(nhwc)))
+        clip = (int(clip_shape[0]), int(clip_shape[1])) if clip_shape is not None else (0, 0)
+        self._call("linetr_fixed_size", ptr(d_recs), nat.np_ptr(cu_k32), nat.np_ptr(cu_n32), ptr(d_precs), nat.np_ptr(precs), nat.np_ptr(cu_p), B, M, T,
+                   float(token_distance), dense_desc.data_ptr(), dense_score.data_ptr(), H, W, clip[0], clip[1], int(resize[0]), int(resize[1]),
+                   int(bool(align_corners)), int(nhwc), ct, counts_dev[0].data_ptr(), counts_dev[1].data_ptr(), ws.data_ptr(), ws.numel())
+        res = {k: out[k] for k in shapes}
+        res["num_klns"], res["num_slns"] = counts_dev[0].to(torch.int64), counts_dev[1].to(torch.int64)
+        res["pseudo_lines"] = pseudo_lines
+        return res
+
     def line_ground_truth(self, lines0, lines1, H, *, thres_reprojected=3, thres_angdiff=2, min_overlap_ratio=0.3, max_matches=None,
                           counts=None, dustbin=True, directions=False, projected=False):
         """The ground truth of homography pairs in one native call (linetr_gt_assign): what the reference's dataset builder computes
