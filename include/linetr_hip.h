@@ -912,6 +912,35 @@ int linetr_superpoint_heads_rows(LinetrHandle* h, const float* d_score_rows, int
                                  int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
                                  float* d_dense_desc_nchw, void* stream);
 
+/* ---- homography views (dataloaders/build_homography_dataset.py:164-167, 179-184; dataloaders/utils/utils.py:317-351, 677-704) ------- */
+
+/* d_dst[b, c, y, x] = d_src[b, c] sampled at the source position of destination pixel (x, y), for contiguous float32 [B,C,H,W] tensors
+ * (C >= 1).  h_mat: B row-major 3x3 float64 matrices on the HOST, read before the call returns; matrix b maps the destination pixel
+ * (x, y, 1) to (x', y', w') and the source position is (x' / w', y' / w'), in PIXEL coordinates (pixel centres at the integers).
+ *   mode 0  bilinear with zero padding: F.grid_sample(mode='bilinear', padding_mode='zeros', align_corners=True) read in pixel units.
+ *           Taps at floor(x), floor(x) + 1 and the same in y; a tap outside the image contributes 0.
+ *   mode 1  nearest: the pixel at nearbyint (half to even) of the position, 0 where that lies outside the image.
+ * The position is computed per pixel in float64 (one reciprocal of w'), the four weights in float64 and rounded once, products and sums
+ * in float32.  A non-finite position (w' == 0, overflow) gives 0; a finite one with negative w' is sampled like any other.  The
+ * position is clamped to [-2, extent + 1] before it becomes an integer, which changes no result.
+ * d_valid: NULL or uint8 [B,H,W], written by the same launch whatever the mode: 1 where the nearest source pixel lies inside the image,
+ * else 0 (compute_valid_mask at erosion_radius = 0).
+ * One launch per 32 images (their matrices travel in the kernel's arguments); no atomics, the same call gives the same bits; nothing is
+ * read or written outside the tensors.  Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.
+ * linetr_warp_tile: the spatial tiles of the two kernels in pixels (the unit tests walk their edges).
+ * LINETR_E_ARG, nothing launched, no output changed: a NULL d_src / d_dst / h_mat, B, C, H or W below 1, H or W above 32 768, H W C at or
+ * beyond 2^31, a mode other than 0 or 1, a non-finite matrix entry, d_dst == d_src, a float pointer that is not 4-byte aligned. */
+int linetr_warp_images(LinetrHandle* h, const float* d_src, int32_t B, int32_t C, int32_t H, int32_t W, const double* h_mat, int32_t mode,
+                       float* d_dst, uint8_t* d_valid, void* stream);
+int linetr_warp_tile(int32_t* tile_h, int32_t* tile_w, int32_t* erode_tile_h, int32_t* erode_tile_w);
+
+/* Binary erosion of a uint8 [B,H,W] mask (non-zero = set; the output holds 0 / 1) by the (2 radius + 1)^2 square of ones.  Pixels outside
+ * the image count as set: cv2.erode's default border, scipy.ndimage.binary_erosion(border_value=1).  radius 2 is the dataset builder's
+ * cv2.erode(mask, np.ones((5, 5))) (build_homography_dataset.py:183-184); radius 0 copies.  One launch, a separable AND over a tile plus
+ * halo in LDS.  LINETR_E_ARG, nothing launched: a NULL pointer, B (above 65 535), H or W (above 32 768) below 1, H W at or beyond 2^31,
+ * radius outside 0 .. 8, d_out overlapping d_mask. */
+int linetr_mask_erode(LinetrHandle* h, const uint8_t* d_mask, int32_t B, int32_t H, int32_t W, int32_t radius, uint8_t* d_out, void* stream);
+
 /* ---- native SuperPoint encoder (models/superpoint.py:113-134, 148-160, 188-189) ---------------------- */
 
 /* Inference only, float32 in and out, channel-last inside, deterministic (a fixed summation order; no atomics).  OFF by default at every

@@ -188,6 +188,9 @@ ABI = {
     "linetr_point_descriptors_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "linetr_point_descriptors": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
     "linetr_superpoint_heads_rows": (i32, [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+    "linetr_warp_images": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "linetr_warp_tile": (i32, [_P(i32), _P(i32), _P(i32), _P(i32)]),
+    "linetr_mask_erode": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "linetr_sp_conv3x3_tile": (i32, [_P(i32), _P(i32)]),
     "linetr_sp_conv3x3_pack_bytes": (i64, [i32, i32]),
     "linetr_sp_conv3x3_pack": (i32, [vp, i32, i32, vp, vp]),

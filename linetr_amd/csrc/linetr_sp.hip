@@ -1,10 +1,12 @@
-// liblinetr_hip.so, translation unit 5 of 5: the native SuperPoint encoder (C ABI in include/linetr_hip.h; kernels in lt_spconv.h).
-// Inference only, float32 in and out, channel-last inside, deterministic.  The two dense-map entry points that consume its rows
-// (linetr_superpoint_heads_rows) live next to linetr_superpoint_heads in linetr_match.hip.
+// liblinetr_hip.so, translation unit 5 of 5: the image front end.  The native SuperPoint encoder (C ABI in include/linetr_hip.h; kernels
+// in lt_spconv.h): inference only, float32 in and out, channel-last inside, deterministic.  The two dense-map entry points that consume
+// its rows (linetr_superpoint_heads_rows) live next to linetr_superpoint_heads in linetr_match.hip.  In front of it the homography views
+// of the dataset builder (lt_warp.h): linetr_warp_images and linetr_mask_erode.
 #include <algorithm>
 
 #include "lt_handle.h"
 #include "lt_spconv.h"
+#include "lt_warp.h"
 
 using namespace lt;
 
@@ -207,4 +209,72 @@ extern "C" int linetr_sp_encoder_forward(LinetrSpEncoder* enc, const float* d_im
   if (int e = sp_conv_launch(nullptr, "sp_convPb", pb, B, 256, 1, 0, st)) return e;
   SpConvArgs db{rows + 256, 512, enc->wDb, enc->bDb, d_desc_rows, 256, h, w, 256, 256, 0};
   return sp_conv_launch(nullptr, "sp_convDb", db, B, 256, 1, 0, st);
+}
+
+// =============================================================================================
+// homography views: warped image batches with their valid masks, and the erosion of a mask (lt_warp.h)
+// =============================================================================================
+
+namespace {
+// B, H, W, C positive, one image below 2^31 elements (plane offsets are ints), extents inside the grid limits
+int view_dims_ok(const char* who, int64_t B, int64_t C, int64_t H, int64_t W) {
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(LINETR_E_ARG, "%s: bad shape B=%lld C=%lld H=%lld W=%lld", who, (long long)B, (long long)C, (long long)H, (long long)W);
+  if (H > SP_MAX_DIM || W > SP_MAX_DIM || H * W * C >= ((int64_t)1 << 31))
+    return fail(LINETR_E_ARG, "%s: H * W * C = %lld x %lld x %lld at or beyond 2^31 elements (or an extent above %d)", who, (long long)H, (long long)W, (long long)C, SP_MAX_DIM);
+  return LINETR_OK;
+}
+}  // namespace
+
+extern "C" int linetr_warp_images(LinetrHandle* h, const float* d_src, int32_t B, int32_t C, int32_t H, int32_t W, const double* h_mat,
+                                  int32_t mode, float* d_dst, uint8_t* d_valid, void* stream) {
+  // every refusal comes before the first launch
+  if (int e = view_dims_ok("warp_images", B, C, H, W)) return e;
+  if (!d_src || !d_dst || !h_mat) return fail(LINETR_E_ARG, "warp_images: null pointer");
+  if (mode != 0 && mode != 1) return fail(LINETR_E_ARG, "warp_images: mode %d is neither 0 (bilinear) nor 1 (nearest)", mode);
+  if (((uintptr_t)d_src | (uintptr_t)d_dst) & 3) return fail(LINETR_E_ARG, "warp_images: a float tensor that is not 4-byte aligned");
+  if (d_src == d_dst) return fail(LINETR_E_ARG, "warp_images: in-place operation (d_dst == d_src)");
+  for (int64_t i = 0; i < (int64_t)B * 9; ++i)
+    if (!std::isfinite(h_mat[i])) return fail(LINETR_E_ARG, "warp_images: matrix %lld has a non-finite entry", (long long)(i / 9));
+  if (h) LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = W % 4 == 0 && aligned16(d_dst) && (!d_valid || ((uintptr_t)d_valid & 3) == 0);
+  const double px = (double)B * H * W;
+  ProfScope ps(h, st, "warp_images", 0, px * (8.0 * C + (d_valid ? 1 : 0)));
+  for (int first = 0; first < B; first += WARP_CHUNK) {
+    const int count = std::min(WARP_CHUNK, B - first);
+    WarpMats mats{};
+    memcpy(mats.m, h_mat + (int64_t)first * 9, (size_t)count * 9 * sizeof(double));
+    const dim3 grid((unsigned)cdiv(W, WARP_TW), (unsigned)cdiv(H, WARP_TH), (unsigned)count);
+    if (mode == 0) hipLaunchKernelGGL(warp_kernel<0>, grid, dim3(256), 0, st, d_src, mats, first, C, H, W, vec, d_dst, d_valid);
+    else hipLaunchKernelGGL(warp_kernel<1>, grid, dim3(256), 0, st, d_src, mats, first, C, H, W, vec, d_dst, d_valid);
+    LT_LAUNCH_CHECK();
+  }
+  return LINETR_OK;
+}
+
+extern "C" int linetr_warp_tile(int32_t* tile_h, int32_t* tile_w, int32_t* erode_tile_h, int32_t* erode_tile_w) {
+  if (!tile_h || !tile_w || !erode_tile_h || !erode_tile_w) return fail(LINETR_E_ARG, "warp_tile: null pointer");
+  *tile_h = WARP_TH;
+  *tile_w = WARP_TW;
+  *erode_tile_h = ERODE_TH;
+  *erode_tile_w = ERODE_TW;
+  return LINETR_OK;
+}
+
+extern "C" int linetr_mask_erode(LinetrHandle* h, const uint8_t* d_mask, int32_t B, int32_t H, int32_t W, int32_t radius, uint8_t* d_out,
+                                 void* stream) {
+  if (int e = view_dims_ok("mask_erode", B, 1, H, W)) return e;
+  if (B > SP_MAX_B) return fail(LINETR_E_ARG, "mask_erode: B=%d above %d", B, SP_MAX_B);
+  if (!d_mask || !d_out) return fail(LINETR_E_ARG, "mask_erode: null pointer");
+  if (radius < 0 || radius > ERODE_MAX_R) return fail(LINETR_E_ARG, "mask_erode: radius %d outside 0..%d", radius, ERODE_MAX_R);
+  const int64_t bytes = (int64_t)B * H * W;
+  if (d_out < d_mask + bytes && d_mask < d_out + bytes) return fail(LINETR_E_ARG, "mask_erode: in-place operation (d_out overlaps d_mask)");
+  if (h) LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = W % 4 == 0 && ((uintptr_t)d_out & 3) == 0;
+  ProfScope ps(h, st, "mask_erode", 0, 2.0 * bytes);
+  hipLaunchKernelGGL(erode_kernel, dim3((unsigned)cdiv(W, ERODE_TW), (unsigned)cdiv(H, ERODE_TH), (unsigned)B), dim3(256), 0, st, d_mask, H, W,
+                     radius, vec, d_out);
+  LT_LAUNCH_CHECK();
+  return LINETR_OK;
 }

@@ -7,7 +7,8 @@
 //   linetr_train.hip  training and evaluation: validation step, criterion gradient, backward of the 1x1 layers, the descriptor head and
 //                     the neighbour-line attention, ground-truth line assignment, fixed-size samples (lt_fixedsize.h over lt_token.h,
 //                     whose kernels are static: the header is compiled into this unit and into linetr_net.hip)
-//   linetr_sp.hip     the native SuperPoint encoder (its own LinetrSpEncoder object; no LinetrHandle state)
+//   linetr_sp.hip     the image front end: the native SuperPoint encoder (its own LinetrSpEncoder object; no LinetrHandle state) and the
+//                     homography views in front of it (lt_warp.h: warped image batches, valid masks, mask erosion)
 //   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once
 #include <map>

@@ -868,6 +868,64 @@ class Engine(_TrainSurface, _DebugSurface):
                                                            ptr(o_nchw), self._stream()), self._L)
         return score, o_nhwc, o_nchw
 
+    # ------------------------------------------------------------------ homography views (csrc/lt_warp.h; linetr_amd/homography.py)
+    WARP_MODES = {"bilinear": 0, "nearest": 1}
+
+    def warp_tiles(self):
+        """((TH, TW) of the warp kernel, (TH, TW) of the erosion kernel) in pixels"""
+        v = [C.c_int32() for _ in range(4)]
+        nat.check(self._L.linetr_warp_tile(*(C.byref(x) for x in v)), self._L)
+        return (v[0].value, v[1].value), (v[2].value, v[3].value)
+
+    def _on_device(self, t, what):
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise RuntimeError(f"{what} must be a tensor on the HIP device {self.device}; there is no CPU path")
+        return t
+
+    def warp_images(self, images: torch.Tensor, mat_dst_to_src, mode="bilinear", return_valid=False, out=None, out_valid=None):
+        """Every image of a float32 [B,C,H,W] batch seen through its own homography, in one native call (linetr_warp_images):
+        out[b, c, y, x] = images[b, c] at M_b (x, y, 1), in pixel coordinates.  mat_dst_to_src: [B,3,3] or one [3,3] for the whole
+        batch, read on the host in float64 (a device tensor is copied, which waits for it; nothing else waits).  mode 'bilinear'
+        (zero padding, F.grid_sample's align_corners=True in pixel units) or 'nearest'.  return_valid: also the uint8 [B,H,W] mask of
+        the pixels whose nearest source pixel lies inside the image.  `out` / `out_valid`: write there instead of into new tensors."""
+        if mode not in self.WARP_MODES:
+            raise ValueError(f"mode must be one of {sorted(self.WARP_MODES)}, got {mode!r}")
+        img = self._on_device(images, "images")
+        if img.dim() != 4 or img.dtype != torch.float32:
+            raise ValueError(f"images must be float32 [B,C,H,W], got {img.dtype} {tuple(img.shape)}")
+        img = img.contiguous()
+        B, Cn, H, W = (int(v) for v in img.shape)
+        m = mat_dst_to_src.detach().cpu().numpy() if isinstance(mat_dst_to_src, torch.Tensor) else np.asarray(mat_dst_to_src)
+        m = m.astype(np.float64).reshape(-1, 3, 3)
+        m = np.ascontiguousarray(np.broadcast_to(m, (B, 3, 3)) if len(m) == 1 else m)
+        if m.shape != (B, 3, 3):
+            raise ValueError(f"{m.shape[0]} matrices for {B} images")
+        if out is None:
+            out = torch.empty_like(img)
+        valid = out_valid
+        if valid is None and return_valid:
+            valid = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        for t, shape, dtype, what in ((out, (B, Cn, H, W), torch.float32, "out"), (valid, (B, H, W), torch.uint8, "out_valid")):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dtype} {shape} tensor on {self.device}")
+        self._call("linetr_warp_images", img.data_ptr(), B, Cn, H, W, nat.np_ptr(m), self.WARP_MODES[mode], out.data_ptr(), ptr(valid))
+        return (out, valid) if return_valid else out
+
+    def erode_mask(self, mask: torch.Tensor, radius: int, out=None):
+        """Binary erosion of a uint8 [B,H,W] (or [H,W]) device mask by the (2 radius + 1)^2 square of ones, outside the image counting as
+        set (linetr_mask_erode): radius 2 is the dataset builder's cv2.erode(mask, np.ones((5, 5))).  Returns a new 0 / 1 mask."""
+        mk = self._on_device(mask, "mask")
+        if mk.dtype != torch.uint8 or mk.dim() not in (2, 3):
+            raise ValueError(f"mask must be uint8 [B,H,W] or [H,W], got {mk.dtype} {tuple(mk.shape)}")
+        mk = mk.contiguous()
+        B, H, W = (1, *mk.shape) if mk.dim() == 2 else mk.shape
+        if out is None:
+            out = torch.empty_like(mk)
+        if tuple(out.shape) != tuple(mk.shape) or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 {tuple(mk.shape)} tensor on {self.device}")
+        self._call("linetr_mask_erode", mk.data_ptr(), int(B), int(H), int(W), int(radius), out.data_ptr())
+        return out
+
     # ------------------------------------------------------------------ native SuperPoint encoder (off by default everywhere)
     SP_CONV_NAMES = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
 
