@@ -941,6 +941,55 @@ int linetr_warp_tile(int32_t* tile_h, int32_t* tile_w, int32_t* erode_tile_h, in
  * radius outside 0 .. 8, d_out overlapping d_mask. */
 int linetr_mask_erode(LinetrHandle* h, const uint8_t* d_mask, int32_t B, int32_t H, int32_t W, int32_t radius, uint8_t* d_out, void* stream);
 
+/* ---- line segment detector (the surface of models/line_detector.py:11-28; NOT OpenCV's LSD) ------------------------------------------ */
+
+/* A detector of the LSD / Burns family whose every step is independent of any processing order (DESIGN.md 4.18 has the algorithm down to
+ * its integer arithmetic; tests/line_detector_reference.py restates it in NumPy).  Pixel centres sit at the integers.  Per octave: the
+ * image is smoothed by [1 2 1] x [1 2 1] (reflect-101, kept times 16), the gradient (gx, gy) is taken on every 2 x 2 cell, a cell is used
+ * iff gx^2 + gy^2 >= grad_threshold, its orientation is put into one of eight buckets twice (partition A: boundaries at multiples of 45
+ * degrees; partition B: at 22.5 degrees + multiples of 45), regions are the 8-connected components of used cells with the same bucket, every
+ * cell votes for the partition in which its region is larger (A on a tie), a region with size >= min_region_size and 2 * votes > size is
+ * fitted through its gradient-weighted integer moments (float64), and kept if its rectangle is filled to at least `density`.
+ * Octave o + 1 is octave o under the separable [1 4 6 4 1] kernel, (sum + 128) >> 8, even rows and columns. */
+typedef struct LinetrDetectConfig {
+  int32_t n_octaves;        /* 1 .. 12; an octave below 2 x 2 pixels yields no lines */
+  int32_t scale;            /* 2, nothing else */
+  int32_t grad_threshold;   /* >= 1; 28160 = LSD's rho = 2 / sin 22.5 deg on the 2 x 2 norm, at this scale */
+  int32_t min_region_size;  /* >= 4 (the candidate tables hold Nc / 4 regions per partition); 16 */
+  double density;           /* 0 .. 1; 0.6 */
+} LinetrDetectConfig;
+
+/* d_images: [B][H][W] on the device, uint8 (images_are_float = 0) or float32 in [0,1] (1; quantised as uint8(v * 255): float32 multiply,
+ * truncation, clamped to 0..255).  d_rows: float64 [B][capacity][6] rows (startX, startY, endX, endY, lineLength, octave) as
+ * linetr_prefilter_batch takes them: end points in pixels of the input image, lineLength in pixels of the line's octave.  Per image the rows
+ * are ordered by octave, then partition A before B, then by the region's smallest cell index.  h_counts: int32 [B][n_octaves] in PINNED host
+ * memory, the true number of lines per image and octave, copied there by the stream; rows beyond `capacity` are not written (call again with
+ * more).  d_debug_regions: NULL or int64 [B][capacity][10], for row r: octave, partition, label, n, sum w, sum wx, sum wy, sum wxx, sum wxy,
+ * sum wyy.  Integer atomics and min / max only: two calls give the same bytes.  Asynchronous on `stream`; nothing inside allocates or waits;
+ * `h` may be NULL.  linetr_detect_tile: the tile of the gradient and labelling kernels in cells (the unit tests walk its edges).
+ * LINETR_E_ARG, nothing launched: B outside 1 .. 32 767, H or W outside 1 .. 2048, a config outside the ranges above, a NULL d_images /
+ * cfg / d_rows / h_counts / d_workspace, capacity below 0, a workspace shorter than linetr_detect_lines_workspace_bytes (0 for extents that
+ * would be refused), misaligned rows (float32 images 4, d_rows and d_debug_regions 8, h_counts 4, the workspace 256 bytes). */
+int64_t linetr_detect_lines_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t n_octaves);
+int linetr_detect_lines(LinetrHandle* h, const void* d_images, int32_t images_are_float, int32_t B, int32_t H, int32_t W,
+                        const LinetrDetectConfig* cfg, int32_t capacity, double* d_rows, int32_t* h_counts, int64_t* d_debug_regions,
+                        void* d_workspace, int64_t workspace_bytes, void* stream);
+int linetr_detect_tile(int32_t* tile_h, int32_t* tile_w);
+
+/* Parts of the detector alone, for the unit tests.
+ * linetr_detect_debug_labels: the three labelling kernels on caller-provided bucket maps, int8 [B][H][W] with -1 = unused (H x W counts
+ * cells here, 1 .. 2048 each; B up to 65 534): d_labels int32 [B][H][W] = the smallest linear index y * W + x of the cell's region, -1 for an
+ * unused cell.  Workspace: linetr_detect_debug_labels_workspace_bytes.
+ * linetr_detect_debug_gradient: quantisation, pyramid and gradient kernel up to `octave`: d_m2 int32 and both bucket maps int8 (-1 =
+ * unused), each [B][Ho - 1][Wo - 1] for the octave's Ho x Wo pixels; nothing is written for an octave below 2 x 2.  Workspace as for
+ * linetr_detect_lines.  Refusals as above. */
+int64_t linetr_detect_debug_labels_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int linetr_detect_debug_labels(LinetrHandle* h, const int8_t* d_buckets, int32_t B, int32_t H, int32_t W, int32_t* d_labels, void* d_workspace,
+                               int64_t workspace_bytes, void* stream);
+int linetr_detect_debug_gradient(LinetrHandle* h, const void* d_images, int32_t images_are_float, int32_t B, int32_t H, int32_t W,
+                                 const LinetrDetectConfig* cfg, int32_t octave, int32_t* d_m2, int8_t* d_bucket_a, int8_t* d_bucket_b,
+                                 void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- native SuperPoint encoder (models/superpoint.py:113-134, 148-160, 188-189) ---------------------- */
 
 /* Inference only, float32 in and out, channel-last inside, deterministic (a fixed summation order; no atomics).  OFF by default at every

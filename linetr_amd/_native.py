@@ -81,6 +81,12 @@ class AdamHyper(C.Structure):
                 ("decoupled", C.c_int32)]
 
 
+class DetectConfig(C.Structure):
+    """LinetrDetectConfig"""
+    _fields_ = [("n_octaves", C.c_int32), ("scale", C.c_int32), ("grad_threshold", C.c_int32), ("min_region_size", C.c_int32),
+                ("density", C.c_double)]
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("calls", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -191,6 +197,12 @@ ABI = {
     "linetr_warp_images": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "linetr_warp_tile": (i32, [_P(i32), _P(i32), _P(i32), _P(i32)]),
     "linetr_mask_erode": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "linetr_detect_lines_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_detect_lines": (i32, [vp, vp, i32, i32, i32, i32, _P(DetectConfig), i32, vp, vp, vp, vp, i64, vp]),
+    "linetr_detect_tile": (i32, [_P(i32), _P(i32)]),
+    "linetr_detect_debug_labels_workspace_bytes": (i64, [i32, i32, i32]),
+    "linetr_detect_debug_labels": (i32, [vp, vp, i32, i32, i32, vp, vp, i64, vp]),
+    "linetr_detect_debug_gradient": (i32, [vp, vp, i32, i32, i32, i32, _P(DetectConfig), i32, vp, vp, vp, vp, i64, vp]),
     "linetr_sp_conv3x3_tile": (i32, [_P(i32), _P(i32)]),
     "linetr_sp_conv3x3_pack_bytes": (i64, [i32, i32]),
     "linetr_sp_conv3x3_pack": (i32, [vp, i32, i32, vp, vp]),

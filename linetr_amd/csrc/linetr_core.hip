@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 1 of 5: lifetime (float64 weight preparation), host pre-filter, the collective entry point
+// liblinetr_hip.so, translation unit 1 of 6: lifetime (float64 weight preparation), host pre-filter, the collective entry point
 // and the profiling entry points of the C ABI declared in include/linetr_hip.h.  No device code lives here.
 #include <dlfcn.h>
 

@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 3 of 5: the descriptor-distance matcher, the dense-map producer and the slab packing of the
+// liblinetr_hip.so, translation unit 3 of 6: the descriptor-distance matcher, the dense-map producer and the slab packing of the
 // multi-GPU path (C ABI in include/linetr_hip.h; kernels in lt_match.h, lt_producer.h) and SuperPoint's key-point branch
 // (lt_keypoints.h).  Training and evaluation are linetr_train.hip.
 #include <algorithm>

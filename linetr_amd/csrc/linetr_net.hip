@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 2 of 5: tokenise / forward / describe and the diagnostics entry points of the C ABI, the
+// liblinetr_hip.so, translation unit 2 of 6: tokenise / forward / describe and the diagnostics entry points of the C ABI, the
 // GEMM dispatcher, and every kernel of the descriptor network (csrc/lt_*.h).  The experiments build adds its paths through a
 // few hooks, defined in experiments/csrc/lt_x_net.h, which this file includes behind sig_network.
 #include <algorithm>

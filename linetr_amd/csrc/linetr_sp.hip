@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 5 of 5: the image front end.  The native SuperPoint encoder (C ABI in include/linetr_hip.h; kernels
+// liblinetr_hip.so, translation unit 5 of 6: the image front end.  The native SuperPoint encoder (C ABI in include/linetr_hip.h; kernels
 // in lt_spconv.h): inference only, float32 in and out, channel-last inside, deterministic.  The two dense-map entry points that consume
 // its rows (linetr_superpoint_heads_rows) live next to linetr_superpoint_heads in linetr_match.hip.  In front of it the homography views
 // of the dataset builder (lt_warp.h): linetr_warp_images and linetr_mask_erode.

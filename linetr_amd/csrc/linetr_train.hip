@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 4 of 5: training and evaluation (C ABI in include/linetr_hip.h).
+// liblinetr_hip.so, translation unit 4 of 6: training and evaluation (C ABI in include/linetr_hip.h).
 //   lt_valstep.h    the validation step
 //   lt_lossgrad.h   the criterion's gradient
 //   lt_linbwd.h     the backward of the 1x1 layers and the descriptor head

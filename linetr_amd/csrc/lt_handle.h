@@ -9,6 +9,7 @@
 //                     whose kernels are static: the header is compiled into this unit and into linetr_net.hip)
 //   linetr_sp.hip     the image front end: the native SuperPoint encoder (its own LinetrSpEncoder object; no LinetrHandle state) and the
 //                     homography views in front of it (lt_warp.h: warped image batches, valid masks, mask erosion)
+//   linetr_det.hip    the line segment detector (lt_linedet.h): linetr_detect_lines and its two debug entry points; no LinetrHandle state
 //   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once
 #include <map>

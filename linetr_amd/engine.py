@@ -926,6 +926,112 @@ class Engine(_TrainSurface, _DebugSurface):
         self._call("linetr_mask_erode", mk.data_ptr(), int(B), int(H), int(W), int(radius), out.data_ptr())
         return out
 
+    # ------------------------------------------------------------------ line segment detector (csrc/lt_linedet.h; linetr_amd/frontends)
+    DETECT_DEFAULTS = {"n_octave": 2, "scale": 2, "grad_threshold": 28160, "min_region_size": 16, "density": 0.6}
+
+    def detect_tile(self):
+        """(TH, TW): the tile of the detector's gradient and labelling kernels in cells"""
+        th, tw = C.c_int32(), C.c_int32()
+        nat.check(self._L.linetr_detect_tile(C.byref(th), C.byref(tw)), self._L)
+        return th.value, tw.value
+
+    @classmethod
+    def detect_config(cls, **config) -> nat.DetectConfig:
+        """LinetrDetectConfig from the keys of DETECT_DEFAULTS (the reference's 'n_octave' / 'scale' and the detector's own three)"""
+        unknown = set(config) - set(cls.DETECT_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown detector settings {sorted(unknown)}")
+        c = {**cls.DETECT_DEFAULTS, **config}
+        return nat.DetectConfig(int(c["n_octave"]), int(c["scale"]), int(c["grad_threshold"]), int(c["min_region_size"]), float(c["density"]))
+
+    def _detect_images(self, images):
+        """a device image batch as the detector takes it: contiguous [B,H,W], uint8 or float32"""
+        img = self._on_device(images, "images")
+        if img.dim() == 2:
+            img = img[None]
+        elif img.dim() == 4 and img.shape[1] == 1:
+            img = img[:, 0]
+        if img.dim() != 3:
+            raise ValueError(f"images must be [B,H,W], [B,1,H,W] or [H,W], got {tuple(img.shape)}")
+        if img.dtype != torch.uint8:
+            if not img.dtype.is_floating_point:
+                raise ValueError(f"images must be uint8 or floating point in [0,1], got {img.dtype}")
+            img = img.to(torch.float32)
+        return img.contiguous()
+
+    def detect_lines(self, images, *, capacity=None, debug=False, **config):
+        """The line segments of a device image batch [B,H,W] / [B,1,H,W] / [H,W], uint8 or float in [0,1], in one native call
+        (linetr_detect_lines): (rows [K,6] float64 ndarray, offsets [B+1] int32), image b's rows at offsets[b]:offsets[b+1], each
+        (startX, startY, endX, endY, lineLength, octave) -- what Engine.prefilter takes as (lines6, offsets=).  The pixels stay on the
+        device; the host waits once, reads the counts from pinned memory and copies exactly the rows.  `capacity`: rows per image the
+        first call has room for (default: what the largest image needed so far, at least 512); where an image holds more the call runs
+        once more with room for all.  config: the keys of DETECT_DEFAULTS.  debug=True: also the int64 [K,10] region rows
+        (octave, partition, label, n, sw, swx, swy, swxx, swxy, swyy) and the counts [B, n_octave]."""
+        img = self._detect_images(images)
+        B, H, W = (int(v) for v in img.shape)
+        cfg = self.detect_config(**config)
+        n_oct = cfg.n_octaves
+        nbytes = self._L.linetr_detect_lines_workspace_bytes(B, H, W, n_oct)
+        ws = self._workspace("detect_lines", max(int(nbytes), 256))
+        pinned = self.__dict__.get("_detect_counts")
+        if pinned is None or pinned.numel() < B * max(n_oct, 1):
+            pinned = self.__dict__["_detect_counts"] = torch.empty(max(B * max(n_oct, 1), 64), dtype=torch.int32, pin_memory=True)
+        cap = int(capacity) if capacity is not None else max(512, self.__dict__.get("_detect_cap", 0))
+        for attempt in range(2):
+            rows = torch.empty((B, cap, 6), dtype=torch.float64, device=self.device)
+            dbg = torch.empty((B, cap, 10), dtype=torch.int64, device=self.device) if debug else None
+            self._call("linetr_detect_lines", img.data_ptr(), int(img.dtype != torch.uint8), B, H, W, C.byref(cfg), cap, rows.data_ptr(),
+                       pinned.data_ptr(), ptr(dbg), ws.data_ptr(), ws.numel())
+            torch.cuda.current_stream(self.device).synchronize()
+            counts = pinned[:B * n_oct].numpy().reshape(B, n_oct).copy()
+            per_image = counts.sum(axis=1)
+            if int(per_image.max()) <= cap:
+                break
+            cap = int(per_image.max())
+        if capacity is None:
+            self.__dict__["_detect_cap"] = max(cap, self.__dict__.get("_detect_cap", 0))
+        offsets = np.zeros(B + 1, dtype=np.int32)
+        np.cumsum(per_image, out=offsets[1:])
+
+        def gather(t):
+            return (t[0, :int(per_image[0])] if B == 1 else torch.cat([t[b, :int(per_image[b])] for b in range(B)])).cpu().numpy()
+        out = gather(rows)
+        return (out, offsets, gather(dbg), counts) if debug else (out, offsets)
+
+    def detect_debug_labels(self, buckets: torch.Tensor, out=None) -> torch.Tensor:
+        """the labelling kernels alone: int8 [B,H,W] bucket maps (-1 = unused) -> int32 [B,H,W] labels (into `out` if given)"""
+        bk = self._on_device(buckets, "buckets")
+        if bk.dtype != torch.int8 or bk.dim() != 3:
+            raise ValueError(f"buckets must be int8 [B,H,W], got {bk.dtype} {tuple(bk.shape)}")
+        bk = bk.contiguous()
+        B, H, W = (int(v) for v in bk.shape)
+        ws = self._workspace("detect_labels", max(int(self._L.linetr_detect_debug_labels_workspace_bytes(B, H, W)), 256))
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.int32, device=self.device)
+        if tuple(out.shape) != (B, H, W) or out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int32 {(B, H, W)} tensor on {self.device}")
+        self._call("linetr_detect_debug_labels", bk.data_ptr(), B, H, W, out.data_ptr(), ws.data_ptr(), ws.numel())
+        return out
+
+    def detect_debug_gradient(self, images, octave=0, **config):
+        """quantisation, pyramid and gradient kernel alone: (m2 int32, bucket A int8, bucket B int8), each [B, Ho - 1, Wo - 1] of `octave`"""
+        img = self._detect_images(images)
+        B, H, W = (int(v) for v in img.shape)
+        cfg = self.detect_config(**config)
+        Ho, Wo = H, W
+        for _ in range(int(octave)):
+            Ho, Wo = (Ho + 1) // 2, (Wo + 1) // 2
+        shape = (B, Ho - 1, Wo - 1) if Ho >= 2 and Wo >= 2 else (B, 0, 0)
+        m2 = torch.empty(shape, dtype=torch.int32, device=self.device)
+        bka, bkb = (torch.empty(shape, dtype=torch.int8, device=self.device) for _ in range(2))
+        ws = self._workspace("detect_lines", max(int(self._L.linetr_detect_lines_workspace_bytes(B, H, W, cfg.n_octaves)), 256))
+        # an empty tensor has no address: the library wants non-NULL pointers even where it writes nothing
+        dummy = torch.empty(16, dtype=torch.int32, device=self.device)
+        p = (lambda t: t.data_ptr() if t.numel() else dummy.data_ptr())
+        self._call("linetr_detect_debug_gradient", img.data_ptr(), int(img.dtype != torch.uint8), B, H, W, C.byref(cfg), int(octave), p(m2), p(bka),
+                   p(bkb), ws.data_ptr(), ws.numel())
+        return m2, bka, bkb
+
     # ------------------------------------------------------------------ native SuperPoint encoder (off by default everywhere)
     SP_CONV_NAMES = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb")
 
