@@ -38,6 +38,8 @@
  *                symbols, the version stays.
  *                + LinetrAdamTensor, LinetrAdamHyper, linetr_adam_step, linetr_grad_norm and their _workspace_bytes (the optimizer
  *                step over a table of tensors and the gradient norm that can feed it): added symbols, the version stays.
+ *                + linetr_debug_stage, linetr_debug_stage_workspace_bytes (the descriptive layer's tail or the signature network
+ *                alone, through the forward pass's own host functions, for the unit tests): added diagnostics symbols, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -1238,6 +1240,33 @@ int linetr_debug_match(LinetrHandle* h, int32_t P, const int32_t* dims, const fl
                        int32_t mutual, float* d_dk, const int64_t* off_dk, int32_t* d_match01, const int64_t* off_k0, void* d_ws,
                        int64_t ws_bytes, int32_t path, int32_t seg1_global, int32_t cache_dk, int32_t device_table,
                        int32_t* path_used, void* stream);
+
+/* Runs ONE stage from the middle of the forward pass alone on the caller's rows, with the handle's (folded) weights and at its
+ * precision mode, for the unit tests (tests/test_gpu_stages.py: both stages against float64 references built from the unfolded
+ * state dict).  The stage is run by the host functions the forward pass itself calls, in the forward pass's workspace layout.
+ * stage LINETR_STAGE_TAIL: the descriptive layer behind the CLS pooling (models/line_attention.py:36-40, 79-83,
+ *     models/line_transformer.py:128).  d_in0 = pooled [N][4][544] rows as linetr_debug_cls_pool writes them, d_in1 = line_pos
+ *     [N][256].  d_out0 = att [N][256] (the value projection, head-major), d_out1 = o = LN(fc(att) + cls), d_out2 = the sentence
+ *     rows line_pos + LN(w_2(gelu(w_1 o)) + o); each may be NULL.  h_cu_sub and n_images are not read; plan must be -1.
+ * stage LINETR_STAGE_SIG: the line-signature network, final projection and L2 normalisation (models/line_transformer.py:132-183,
+ *     245-246).  d_in0 = the sentence rows z0 [N][256] (copied into the workspace: not written), h_cu_sub [n_images + 1] the images'
+ *     prefix sums ending at N, d_in1 not read.  d_out0 = line_desc [N][256]; d_out1 (may be NULL) = taps [L - 1][N][256], x_out
+ *     behind the signature layers 0 .. L - 2 of the handle's L (the last layer's x_out exists only inside the final projection);
+ *     d_out2 not read.
+ *     plan: -1 = what the forward pass takes for this batch, or the signature-attention kernel 0 .. 4 as linetr_debug_sig_attention
+ *     numbers them (4: the fused projection + attention) + LINETR_STAGE_FOLD_NEXT for the single-pair path whose x_out and next
+ *     q/k/v projection come out of one contraction.  *plan_used (may be NULL) receives the plan that ran, in the same encoding.
+ *     A forced plan the stage's buffers or kernels cannot serve is refused: kernels 1-3 or 4 in f32 mode, 4 outside bf16x6 mode,
+ *     with an image above 256 sub-lines or with fold_next, fold_next with a kernel other than 1 or above 960 sub-lines.
+ * d_ws: linetr_debug_stage_workspace_bytes(h, N, n_images) bytes (n_images = 1 for the tail; -1 on bad arguments): the forward
+ * pass's workspace without its token rows.  Refused with LINETR_E_ARG, nothing launched or written: a training-mode handle, a bad
+ * stage / plan / cu_sub, NULL tensors, tensors or a workspace that are not 16-byte aligned, a workspace that is too small
+ * (LINETR_E_ARG here too).  N = 0 launches nothing.  Synchronises `stream` before returning. */
+enum { LINETR_STAGE_TAIL = 0, LINETR_STAGE_SIG = 1, LINETR_STAGE_FOLD_NEXT = 8 };
+int64_t linetr_debug_stage_workspace_bytes(const LinetrHandle* h, int32_t N, int32_t n_images);
+int linetr_debug_stage(LinetrHandle* h, int32_t stage, int32_t N, const float* d_in0, const float* d_in1, const int32_t* h_cu_sub,
+                       int32_t n_images, int32_t plan, float* d_out0, float* d_out1, float* d_out2, int32_t* plan_used, void* d_ws,
+                       int64_t ws_bytes, void* stream);
 
 #ifdef LINETR_EXPERIMENTS
 /* ---- split-tile ("ST") operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h): experiments build only --------------------

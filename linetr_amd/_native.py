@@ -224,6 +224,8 @@ ABI = {
     "linetr_debug_bn_train": (i32, [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_debug_cls_pool": (i32, [vp, i32, vp, i32, vp, i32, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "linetr_debug_match": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
+    "linetr_debug_stage_workspace_bytes": (i64, [vp, i32, i32]),
+    "linetr_debug_stage": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_allgather_desc": (i32, [vp, vp, vp, i64, vp]),
     "linetr_set_allgather_fn": (i32, [vp]),
     "linetr_pack_slab": (i32, [vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp]),

@@ -416,6 +416,7 @@ struct FwdWs {
   float *pooled, *att, *fc, *o, *f1, *f2, *lpos, *zA, *zB, *qkv, *msgp, *msg, *hid;
   float *zqA, *zqB;                                // [N][4D] = [x_out | q/k/v of the next layer] (single-pair sizes: SigLayer::Wnext)
   int* cu;
+  float* tap = nullptr;                            // linetr_debug_stage only: [L-1][N][D], x_out behind signature layers 0 .. L-2
   char* x = nullptr;                               // experiments build: where its own buffers start (lt_x_net.h)
   int64_t total;
 };
@@ -689,11 +690,16 @@ int cls_pool_launch(LinetrHandle* h, hipStream_t st, int kernel, const TokenStag
   return LINETR_OK;
 }
 
+// value / last-MLP projection of the pooled rows [N][4][544] -> att [N][256] (cls_pooling and linetr_debug_stage both call it):
+// one product per head, the head's DH rows of Watt over its pooled row
+int value_projection(LinetrHandle* h, hipStream_t st, int N, const float* pooled, float* att) {
+  const GemmGroups heads{HEADS, DH, POOLW, DH};
+  return run_gemm(h, st, h->Watt, N, {pooled, HEADS * POOLW}, {att, D}, ACT_NONE, nullptr, &heads);
+}
+
 int cls_pooling(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, int n_images, int N, int T, FwdWs& w) {
   if (int e = cls_pool_launch(h, st, cls_pool_plan(ts.cpnt != nullptr, N), ts, n_images, N, T, w.act[ENC_WORD][3], w.pooled)) return e;
-  // one product per head: the head's DH rows of Watt over its pooled row
-  const GemmGroups heads{HEADS, DH, POOLW, DH};
-  return run_gemm(h, st, h->Watt, N, {w.pooled, HEADS * POOLW}, {w.att, D}, ACT_NONE, nullptr, &heads);
+  return value_projection(h, st, N, w.pooled, w.att);
 }
 
 // ---- the descriptive layer's tail (up to CUT_SENTENCE): the sentence rows zA, input of the line-signature network
@@ -735,6 +741,26 @@ SigAttnPlan sig_attn_plan(const LinetrHandle* h, int n_images, int N, int max_n)
   return p;
 }
 
+// Can sig_network run plan `p`, chosen by hand (linetr_debug_stage), on this batch?  What its buffers and kernels cannot serve is
+// refused here, before anything is launched; every plan sig_attn_plan makes passes.
+int sig_plan_servable(const LinetrHandle* h, const SigAttnPlan& p, int N, int max_n) {
+  if (p.attn < SIGK_F32 || p.attn > SIGK_SPLIT8) return fail(LINETR_E_ARG, "sig plan: attention kernel %d outside 0 .. 3", p.attn);
+  if (h->precision == LINETR_PREC_F32 && (p.attn != SIGK_F32 || p.fused))
+    return fail(LINETR_E_ARG, "sig plan: the f32 mode runs sig_attn_kernel (0) only");
+  if (p.fold_next) {
+    if (p.fused) return fail(LINETR_E_ARG, "sig plan: fold_next and the fused projection + attention exclude each other");
+    if (p.attn != SIGK_SMALL) return fail(LINETR_E_ARG, "sig plan: fold_next leaves q/k/v at row stride 1024, which sig_attn_small (1) alone reads");
+    if (N > SIG_FOLD_MAX_ROWS) return fail(LINETR_E_ARG, "sig plan: fold_next has buffers for up to %d sub-lines (got %d)", SIG_FOLD_MAX_ROWS, N);
+  }
+  if (p.fused) {
+    if (h->precision != LINETR_PREC_BF16X6) return fail(LINETR_E_ARG, "sig plan: the fused projection + attention runs in bf16x6 mode only");
+    if (max_n > 256) return fail(LINETR_E_ARG, "sig plan: the fused projection + attention takes images of up to 256 sub-lines (got %d)", max_n);
+    for (const SigLayer& S : h->sig)
+      if (!S.Wqkv.st) return fail(LINETR_E_ARG, "sig plan: a layer has no split-tile weight image for the fused projection + attention");
+  }
+  return LINETR_OK;
+}
+
 // one signature layer's attention by kernel `kernel` (SIGK_F32 .. SIGK_SPLIT8), q/k/v rows at qkv (row stride ldq) -> msg: exact-fp32
 // MFMA attention (f32 mode), fp32-faithful split-bf16 (6 products) otherwise.  SIGK_SMALL is the only kernel that takes ldq != 3 D.
 int sig_attention(LinetrHandle* h, hipStream_t st, int kernel, const float* qkv, int ldq, const int* cu_dev, int n_images, int N,
@@ -770,8 +796,10 @@ int sig_qkv_attention(LinetrHandle* h, hipStream_t st, const SigLayer& S, const 
 
 // ---- line-signature network + final projection and L2 normalisation (CUT_SIG0 + l behind layer l).
 // models/line_transformer.py:132-183, 245-246
+// `forced` (linetr_debug_stage only, checked by sig_plan_servable): the plan to run instead of sig_attn_plan's; w.tap (the same
+// caller only): where x_out behind every layer but the last is copied.  Every product call leaves both null.
 int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const int32_t* h_cu, const int* cu_dev, int n_images, int N,
-                float* d_line_desc, FwdWs& w) {
+                float* d_line_desc, FwdWs& w, const SigAttnPlan* forced = nullptr) {
   const LinetrModelConfig& c = h->cfg;
   int max_n = 0;
   for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
@@ -779,7 +807,7 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
   const double attn_fl = attn_flops(h_cu, n_images);
   // the signature layers' slots behind the two encoders' in the packed BatchNorm statistics
   const int64_t sig_bn_off = 4 * (int64_t)(c.enc_channels[0] + c.enc_channels[1] + c.enc_channels[2] + c.enc_channels[3]);
-  const SigAttnPlan plan = sig_attn_plan(h, n_images, N, max_n);
+  const SigAttnPlan plan = forced ? *forced : sig_attn_plan(h, n_images, N, max_n);
   const bool fold_next = plan.fold_next, fused_qkv_attn = plan.fused;
   float *z = w.zA, *zn = w.zB;     // the layer's input rows (row stride ldz) and the next layer's
   int ldz = D;
@@ -807,6 +835,9 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
       if ((e = run_gemm(h, st, S.W2, N, {w.hid, 2 * D}, {zn, D}, ACT_NONE, z))) return e;
       std::swap(z, zn);
     }
+    if (w.tap)
+      LT_HIP(hipMemcpy2DAsync(w.tap + (int64_t)l * N * D, D * sizeof(float), z, ldz * sizeof(float), D * sizeof(float), N,
+                              hipMemcpyDeviceToDevice, st));
     if ((e = pipe_boundary(ts.pipe, CUT_SIG0 + (int)l, st))) return e;
   }
   NormSpec l2; l2.mode = 2;      // F.normalize(final_proj(.), dim=1)  (line_transformer.py:245-246)
@@ -1429,5 +1460,75 @@ extern "C" int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const Line
   if (!e) e = cls_pool_launch(h, st, kernel, ts, n_images, N, T, d_a4, d_pooled);
   (void)hipStreamSynchronize(st);
   if (buf) (void)hipFree(buf);
+  return e;
+}
+
+// One stage of forward_core alone on the caller's rows: the same host functions, the handle's weights, forward_core's own workspace
+// layout (no token rows).  Everything is checked before the first launch or copy.
+extern "C" int64_t linetr_debug_stage_workspace_bytes(const LinetrHandle* h, int32_t N, int32_t n_images) {
+  if (!h || N < 0 || n_images < 0) return -1;
+  return fwd_layout(h, std::max(N, 1), 0, std::max(n_images, 1), nullptr).total;
+}
+
+extern "C" int linetr_debug_stage(LinetrHandle* h, int32_t stage, int32_t N, const float* d_in0, const float* d_in1,
+                                  const int32_t* h_cu, int32_t n_images, int32_t plan, float* d_out0, float* d_out1, float* d_out2,
+                                  int32_t* plan_used, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!h) return fail(LINETR_E_ARG, "debug_stage: null handle");
+  if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_stage: a training-mode handle (bn_batch_stats = 1) is not served");
+  if (stage != LINETR_STAGE_TAIL && stage != LINETR_STAGE_SIG) return fail(LINETR_E_ARG, "debug_stage: stage must be 0 (tail) or 1 (sig)");
+  if (N < 0 || N > INT32_MAX / (HEADS * POOLW)) return fail(LINETR_E_ARG, "debug_stage: row count must be 0 .. %d", INT32_MAX / (HEADS * POOLW));
+  const bool sig = stage == LINETR_STAGE_SIG;
+  SigAttnPlan p{};
+  if (sig) {
+    if (int e = check_cu(h_cu, n_images)) return e;
+    if (h_cu[n_images] != N) return fail(LINETR_E_ARG, "debug_stage: cu_sub does not end at N");
+    if (plan < -1 || (plan & ~LINETR_STAGE_FOLD_NEXT) > SIGK_FUSED)
+      return fail(LINETR_E_ARG, "debug_stage: plan must be -1 or a kernel 0 .. 4 (+ %d: fold_next)", LINETR_STAGE_FOLD_NEXT);
+    int max_n = 0;
+    for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
+    p = sig_attn_plan(h, n_images, N, max_n);
+    if (plan >= 0) {
+      const int kernel = plan & ~LINETR_STAGE_FOLD_NEXT;
+      // (a fused plan reads no q/k/v rows: its attention kernel stays the dispatcher's, as in every plan sig_attn_plan makes)
+      p.fused = kernel == SIGK_FUSED;
+      if (!p.fused) p.attn = kernel;
+      p.fold_next = (plan & LINETR_STAGE_FOLD_NEXT) != 0;
+      if (int e = sig_plan_servable(h, p, N, max_n)) return e;
+    }
+    if (plan_used) *plan_used = p.kernel() | (p.fold_next ? LINETR_STAGE_FOLD_NEXT : 0);
+  } else if (plan != -1) {
+    return fail(LINETR_E_ARG, "debug_stage: the tail has no plan to force (plan must be -1)");
+  }
+  if (N == 0) return LINETR_OK;
+  if (!d_in0 || (!sig && !d_in1) || (sig && !d_out0) || !d_ws) return fail(LINETR_E_ARG, "debug_stage: null pointer");
+  if (((uintptr_t)d_in0 | (uintptr_t)d_in1 | (uintptr_t)d_out0 | (uintptr_t)d_out1 | (uintptr_t)d_out2 | (uintptr_t)d_ws) % 16)
+    return fail(LINETR_E_ARG, "debug_stage: tensors and the workspace must be 16-byte aligned");
+  const int n_cu = sig ? n_images : 1;
+  // (a short workspace is an argument error here, like every other refusal of this entry point)
+  const int64_t ws_need = linetr_debug_stage_workspace_bytes(h, N, n_cu);
+  if (ws_bytes < ws_need)
+    return fail(LINETR_E_ARG, "debug_stage: workspace too small (%lld < %lld bytes)", (long long)ws_bytes, (long long)ws_need);
+  LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  FwdWs w = fwd_layout(h, N, 0, n_cu, (char*)d_ws);
+  const size_t row_bytes = (size_t)N * D * sizeof(float);
+  int e = LINETR_OK;
+  auto copy = [&](float* dst, const float* src, size_t bytes) {
+    if (!e && dst && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) e = fail(LINETR_E_HIP, "debug_stage: a device copy failed");
+  };
+  if (!sig) {
+    w.lpos = const_cast<float*>(d_in1);   // read only (the second LayerNorm's add2)
+    e = value_projection(h, st, N, d_in0, w.att);
+    if (!e) e = sentence(h, st, N, w);
+    copy(d_out0, w.att, row_bytes); copy(d_out1, w.o, row_bytes); copy(d_out2, w.zA, row_bytes);
+  } else {
+    // (sig_network writes every other layer's x_out over its input rows: the caller's stay as they are)
+    copy(w.zA, d_in0, row_bytes);
+    const int* cu_dev = nullptr;
+    if (!e) e = cu_on_device(h_cu, nullptr, n_images, w, st, cu_dev);
+    w.tap = h->sig.size() > 1 ? d_out1 : nullptr;
+    if (!e) e = sig_network(h, st, TokenStage{}, h_cu, cu_dev, n_images, N, d_out0, w, plan >= 0 ? &p : nullptr);
+  }
+  (void)hipStreamSynchronize(st);
   return e;
 }

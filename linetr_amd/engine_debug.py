@@ -276,6 +276,31 @@ class _DebugSurface:
                    int(Wc), int(bool(align_corners)), ptr(desc_dense), ptr(out), C.byref(used))
         return out, used.value
 
+    STAGES = ("tail", "sig")
+    SIG_FOLD_NEXT = 8            # LINETR_STAGE_FOLD_NEXT: added to an index into SIG_KERNELS in debug_stage's `plan`
+
+    def debug_stage(self, stage, in0, in1=None, cu_sub=None, plan=-1, outs=(None, None, None)):
+        """ONE stage from the middle of the forward pass alone (linetr_debug_stage; diagnostics / unit tests), by the host functions
+        the forward pass calls.  'tail': in0 = pooled [>= N, 4, 544], in1 = line_pos [>= N, 256], N = cu_sub (an int here);
+        outs = (att, o, zA), each [>= N, 256] or None.  'sig': in0 = z0 [>= N, 256], cu_sub the images' prefix sums; outs =
+        (line_desc [>= N, 256], taps [>= L - 1, N, 256] or None, None); plan: -1 (the forward pass's choice) or an index into
+        SIG_KERNELS (+ SIG_FOLD_NEXT).  Tensors are contiguous float32 on the engine's device and go to the library as they are.
+        Returns the plan that ran (-1 for the tail)."""
+        sig = self.STAGES.index(stage) == 1
+        cu = np.ascontiguousarray(np.asarray(cu_sub, dtype=np.int32)) if sig else None
+        N = (int(cu[-1]) if len(cu) else 0) if sig else int(cu_sub)
+        n_taps = max(int(self.cfg["n_sig_layers"]) - 1, 0)
+        need = (N * D, 0, N * D, N * n_taps * D, 0) if sig else (N * 4 * 544, N * D, N * D, N * D, N * D)
+        for t, n in zip((in0, in1, *outs), need):
+            if t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"contiguous float32 tensors of at least {n} elements on the engine's device expected")
+        n_images = len(cu) - 1 if sig else 1
+        ws = self._workspace("stage", max(self._L.linetr_debug_stage_workspace_bytes(self._h, N, n_images), 0))
+        used = C.c_int32(-1)
+        self._call("linetr_debug_stage", int(sig), N, ptr(in0), ptr(in1), cu.ctypes.data if sig else None, n_images, int(plan),
+                   ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), C.byref(used), ws.data_ptr(), ws.numel())
+        return used.value
+
     MATCH_PATHS = ("pair_dist + pair_pool + pair_final", "pair_match_fused<false>", "pair_match_fused<true>")
 
     def match_path(self, dims) -> int:
