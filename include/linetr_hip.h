@@ -363,7 +363,10 @@ int linetr_pool_distmat_dense(LinetrHandle* h, const float* d_dist, int32_t n0, 
                               void* stream);
 
 /* nn_matcher (models/nn_matcher.py:33-42): point-descriptor variant, desc given [256,n] column-major
- * like SuperPoint's `descriptors` -- section 8(f) "next" row, same kernels. */
+ * like SuperPoint's `descriptors` -- section 8(f) "next" row, same kernels.  `h` may be NULL (the current device is used).
+ * d_workspace: linetr_match_points_workspace_bytes(n0, n1) bytes (negative counts count as 0); a smaller one is refused with
+ * LINETR_E_WORKSPACE before anything is launched. */
+int64_t linetr_match_points_workspace_bytes(int32_t n0, int32_t n1);
 int linetr_match_points(LinetrHandle* h, const float* d_desc0_cn, int32_t n0, const float* d_desc1_cn,
                         int32_t n1, float nn_thresh, int32_t mutual, float* d_dist, int32_t* d_match01,
                         void* d_workspace, int64_t workspace_bytes, void* stream);

@@ -132,6 +132,7 @@ ABI = {
     "linetr_pool_distmat": (i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]),
     "linetr_pool_distmat_dense_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "linetr_pool_distmat_dense": (i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]),
+    "linetr_match_points_workspace_bytes": (i64, [i32, i32]),
     "linetr_match_points": (i32, [vp, vp, i32, vp, i32, f32, i32, vp, vp, vp, i64, vp]),
     "linetr_pair_tail_workspace_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
     "linetr_pair_tail_output_bytes": (i64, [i32, i32, i32, i32, vp]),

@@ -112,14 +112,25 @@ PairSlot* fused_pair_slot(int n0, int k0, int n1, int k1, hipStream_t st) {
 
 // ints of argmin scratch one pair needs (layout in lt_match.h)
 int64_t pair_scratch_ints(int k0, int k1) { return 2 * (int64_t)k0 + 2 * (int64_t)k1 + 1 + 2 * (int64_t)cdiv(std::max(k0, 1), PM_ROWS) * k1 + 8; }
+
+// workspace of linetr_match / linetr_match_gathered: device pair table | distance matrices | argmin scratch
+struct MatchLayout { int64_t o_table, o_dist, o_scratch, total; };
+MatchLayout match_layout(int P, int64_t sum_n0n1, int64_t sum_k) {
+  MatchLayout L{};
+  Carve c;
+  L.o_table = c.take((int64_t)P * sizeof(PairDesc));
+  L.o_dist = c.take(sum_n0n1 * 4);
+  // scratch bound: sum over pairs of pair_scratch_ints(k0,k1) <= 4 sum_k + 2 (sum_k0k1 / PM_ROWS + sum_k) + 9 P, and
+  // k0 k1 <= n0 n1
+  L.o_scratch = c.take((6 * sum_k + 2 * (sum_n0n1 / PM_ROWS + 1) + 9 * (int64_t)P) * 4);
+  L.total = c.o + 256;
+  return L;
+}
 }  // namespace
 
 extern "C" int64_t linetr_match_workspace_bytes(int32_t n_pairs, int64_t sum_n0n1, int64_t sum_k0k1, int64_t sum_k) {
   (void)sum_k0k1;
-  // scratch bound: sum over pairs of pair_scratch_ints(k0,k1) <= 4 sum_k + 2 (sum_k0k1 / PM_ROWS + sum_k) + 9 P, and
-  // k0 k1 <= n0 n1
-  const int64_t scratch = 6 * sum_k + 2 * (sum_n0n1 / PM_ROWS + 1) + 9 * (int64_t)n_pairs;
-  return align_up((int64_t)n_pairs * sizeof(PairDesc), 256) + align_up(sum_n0n1 * 4, 256) + align_up(scratch * 4, 256) + 256;
+  return match_layout(n_pairs, sum_n0n1, sum_k).total;
 }
 
 namespace {
@@ -210,11 +221,12 @@ int match_run(LinetrHandle* h, int32_t P, const int32_t* dims, const float* d_de
     max_k1 = std::max(max_k1, d.k1); max_chunks = std::max(max_chunks, d.chunks);
     flops += 2.0 * d.n0 * d.n1 * D;
   }
-  if (ws_bytes < linetr_match_workspace_bytes(P, od, 0, sum_k)) return fail(LINETR_E_WORKSPACE, "match: workspace too small");
+  const MatchLayout L = match_layout(P, od, sum_k);
+  if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "match: workspace too small");
   char* base = (char*)d_ws;
-  PairDesc* d_pd = (PairDesc*)base;
-  float* d_dist = (float*)(base + align_up((int64_t)P * sizeof(PairDesc), 256));
-  int* d_scr = (int*)((char*)d_dist + align_up(od * 4, 256));
+  PairDesc* d_pd = (PairDesc*)(base + L.o_table);
+  float* d_dist = (float*)(base + L.o_dist);
+  int* d_scr = (int*)(base + L.o_scratch);
   if (slot >= 0) {
     LT_HIP(hipMemcpyAsync(d_pd, pd, P * sizeof(PairDesc), hipMemcpyHostToDevice, st));
     if (int e = staging_ring().commit(slot, st)) return e;
@@ -319,6 +331,27 @@ extern "C" int linetr_debug_match(LinetrHandle* h, int32_t P, const int32_t* dim
   return LINETR_OK;
 }
 
+namespace {
+// workspace of linetr_match_points: row-major copies | identity sub2line maps | the generic matcher's workspace
+struct PointsLayout { int64_t o_r0, o_r1, o_id0, o_id1, o_match, match_bytes, total; };
+PointsLayout points_layout(int n0, int n1) {
+  PointsLayout L{};
+  Carve c;
+  L.o_r0 = c.take((int64_t)n0 * D * 4);
+  L.o_r1 = c.take((int64_t)std::max(n1, 1) * D * 4);
+  L.o_id0 = c.take((int64_t)n0 * 4);
+  L.o_id1 = c.take((int64_t)std::max(n1, 1) * 4);
+  L.match_bytes = match_layout(1, (int64_t)n0 * n1, n0 + n1).total;
+  L.o_match = c.take(L.match_bytes);
+  L.total = c.o;
+  return L;
+}
+}  // namespace
+
+extern "C" int64_t linetr_match_points_workspace_bytes(int32_t n0, int32_t n1) {
+  return points_layout(std::max(n0, 0), std::max(n1, 0)).total;
+}
+
 extern "C" int linetr_match_points(LinetrHandle* h, const float* d0_cn, int32_t n0, const float* d1_cn, int32_t n1,
                                    float thr, int32_t mutual, float* d_dist, int32_t* d_match01, void* d_ws,
                                    int64_t ws_bytes, void* stream) {
@@ -326,15 +359,11 @@ extern "C" int linetr_match_points(LinetrHandle* h, const float* d0_cn, int32_t 
   if (n0 == 0) return LINETR_OK;
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  // scratch: row-major copies + identity sub2line maps + the generic matcher's workspace
-  Carve c;
-  const int64_t o_r0 = c.take((int64_t)n0 * D * 4), o_r1 = c.take((int64_t)std::max(n1, 1) * D * 4);
-  const int64_t o_id0 = c.take((int64_t)n0 * 4), o_id1 = c.take((int64_t)std::max(n1, 1) * 4);
-  const int64_t need_t = c.o, need_m = linetr_match_workspace_bytes(1, (int64_t)n0 * n1, 0, n0 + n1);
-  if (ws_bytes < need_t + need_m) return fail(LINETR_E_WORKSPACE, "match_points: workspace too small (need %lld)", (long long)(need_t + need_m));
+  const PointsLayout L = points_layout(n0, n1);
+  if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "match_points: workspace too small (need %lld)", (long long)L.total);
   char* base = (char*)d_ws;
-  float *r0 = (float*)(base + o_r0), *r1 = (float*)(base + o_r1);
-  int *id0 = (int*)(base + o_id0), *id1 = (int*)(base + o_id1);
+  float *r0 = (float*)(base + L.o_r0), *r1 = (float*)(base + L.o_r1);
+  int *id0 = (int*)(base + L.o_id0), *id1 = (int*)(base + L.o_id1);
   if (!fused_pair_slot(n0, n0, n1, n1, st)) {      // (the one-launch identity path never reads the maps: no upload on the latency path)
     int slot = 0;
     const int m = std::max(n0, n1);
@@ -350,8 +379,8 @@ extern "C" int linetr_match_points(LinetrHandle* h, const float* d0_cn, int32_t 
   LT_LAUNCH_CHECK();
   const int32_t dims[4] = {n0, n0, n1, n1};
   const int64_t zero = 0;
-  return linetr_match(h, 1, dims, r0, &zero, id0, r1, &zero, id1, thr, mutual, d_dist, &zero, d_match01, &zero, base + need_t,
-                      ws_bytes - need_t, stream);
+  return linetr_match(h, 1, dims, r0, &zero, id0, r1, &zero, id1, thr, mutual, d_dist, &zero, d_match01, &zero, base + L.o_match,
+                      L.match_bytes, stream);
 }
 
 // The matching tail of Matching.forward (models/matching.py:67-84) in ONE call: point matcher (nn_matcher on the two [256,n] SuperPoint
@@ -360,7 +389,8 @@ extern "C" int linetr_match_points(LinetrHandle* h, const float* d0_cn, int32_t 
 // be switched off (np0 = 0 / k0 = 0).  Layout of the pinned block (byte offsets returned in h_offsets[4], every segment 256-aligned):
 //   point distances [np0][np1] f32 | point match01 [np0] i32 | key-line distances Dk [k0][k1] f32 | line match01 [k0] i32
 namespace {
-struct TailLayout { int64_t o_pd, o_pm, o_ld, o_lm, out_total, ws_points, ws_lines, ws_total; };
+// (the workspace: device image of the output block, at offset 0 | the point matcher's | the line matcher's)
+struct TailLayout { int64_t o_pd, o_pm, o_ld, o_lm, out_total, ws_points, ws_lines, o_ws_points, o_ws_lines, ws_total; };
 TailLayout tail_layout(int np0, int np1, int n0, int k0, int n1, int k1) {
   TailLayout L{};
   Carve c;
@@ -369,9 +399,13 @@ TailLayout tail_layout(int np0, int np1, int n0, int k0, int n1, int k1) {
   L.o_ld = c.take((int64_t)k0 * k1 * 4);
   L.o_lm = c.take((int64_t)k0 * 4);
   L.out_total = c.o;
-  L.ws_points = np0 > 0 && np1 > 0 ? 4 * (int64_t)(np0 + np1) * (D + 1) + 2048 + linetr_match_workspace_bytes(1, (int64_t)np0 * np1, 0, np0 + np1) : 0;
-  L.ws_lines = k0 > 0 && k1 > 0 ? linetr_match_workspace_bytes(1, (int64_t)n0 * n1, 0, k0 + k1) : 0;
-  L.ws_total = align_up(L.out_total, 256) + align_up(L.ws_points, 256) + align_up(L.ws_lines, 256) + 256;
+  L.ws_points = np0 > 0 && np1 > 0 ? points_layout(np0, np1).total : 0;
+  L.ws_lines = k0 > 0 && k1 > 0 ? match_layout(1, (int64_t)n0 * n1, k0 + k1).total : 0;
+  Carve w;
+  w.take(L.out_total);
+  L.o_ws_points = w.take(L.ws_points);
+  L.o_ws_lines = w.take(L.ws_lines);
+  L.ws_total = w.o + 256;
   return L;
 }
 }  // namespace
@@ -398,8 +432,8 @@ extern "C" int linetr_pair_tail(LinetrHandle* h, const float* d_pdesc0_cn, int32
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
   char* dout = (char*)d_ws;                                       // device image of the output block
-  char* wsp = dout + align_up(L.out_total, 256);
-  char* wsl = wsp + align_up(L.ws_points, 256);
+  char* wsp = dout + L.o_ws_points;
+  char* wsl = dout + L.o_ws_lines;
   char* hout = (char*)h_pinned_out;
   if (points) {
     if (!d_pdesc0_cn || !d_pdesc1_cn) return fail(LINETR_E_ARG, "pair_tail: null point descriptors");
@@ -421,10 +455,24 @@ extern "C" int linetr_pair_tail(LinetrHandle* h, const float* d_pdesc0_cn, int32
   return LINETR_OK;
 }
 
+namespace {
+// workspace of linetr_match_distmat: 256 bytes nobody reads (the pair table travels inline) | identity maps | Dk copy | argmin ints
+struct DistmatLayout { int64_t o_id0, o_id1, o_dk, o_scr, total; };
+DistmatLayout distmat_layout(int n0, int n1) {
+  DistmatLayout L{};
+  Carve c;
+  c.take(256);
+  L.o_id0 = c.take((int64_t)n0 * 4);
+  L.o_id1 = c.take((int64_t)std::max(n1, 1) * 4);
+  L.o_dk = c.take((int64_t)n0 * std::max(n1, 1) * 4);
+  L.o_scr = c.take(pair_scratch_ints(n0, n1) * 4);
+  L.total = c.o;
+  return L;
+}
+}  // namespace
+
 extern "C" int64_t linetr_match_distmat_workspace_bytes(int32_t n0, int32_t n1) {
-  n0 = std::max(n0, 0); n1 = std::max(n1, 0);
-  return 256 + align_up((int64_t)n0 * 4, 256) + align_up((int64_t)std::max(n1, 1) * 4, 256) +
-         align_up((int64_t)n0 * std::max(n1, 1) * 4, 256) + align_up(pair_scratch_ints(n0, n1) * 4, 256);
+  return distmat_layout(std::max(n0, 0), std::max(n1, 0)).total;
 }
 
 extern "C" int linetr_match_distmat(LinetrHandle* h, const float* d_dist, int32_t n0, int32_t n1, float thr,
@@ -434,12 +482,8 @@ extern "C" int linetr_match_distmat(LinetrHandle* h, const float* d_dist, int32_
   if (!d_match01 || !d_ws || (n1 > 0 && !d_dist)) return fail(LINETR_E_ARG, "match_distmat: null pointer");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  // scratch: PairDesc | identity maps | Dk copy | argmin ints
-  const int64_t o_id0 = 256, o_id1 = o_id0 + align_up((int64_t)n0 * 4, 256);
-  const int64_t o_dk = o_id1 + align_up((int64_t)std::max(n1, 1) * 4, 256);
-  const int64_t o_scr = o_dk + align_up((int64_t)n0 * std::max(n1, 1) * 4, 256);
-  const int64_t need = linetr_match_distmat_workspace_bytes(n0, n1);
-  if (!d_ws || ws_bytes < need) return fail(LINETR_E_WORKSPACE, "match_distmat: workspace too small (need %lld)", (long long)need);
+  const DistmatLayout L = distmat_layout(n0, n1);
+  if (!d_ws || ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "match_distmat: workspace too small (need %lld)", (long long)L.total);
   char* base = (char*)d_ws;
   const int m = std::max(n0, n1);
   int slot = 0;
@@ -451,20 +495,33 @@ extern "C" int linetr_match_distmat(LinetrHandle* h, const float* d_dist, int32_
   pd->n0 = pd->k0 = n0; pd->n1 = pd->k1 = n1;
   pd->chunks = cdiv(n0, PM_ROWS);
   std::iota(iota, iota + m, 0);
-  LT_HIP(hipMemcpyAsync(base + o_id0, iota, n0 * 4, hipMemcpyHostToDevice, st));
-  if (n1 > 0) LT_HIP(hipMemcpyAsync(base + o_id1, iota, n1 * 4, hipMemcpyHostToDevice, st));
+  LT_HIP(hipMemcpyAsync(base + L.o_id0, iota, n0 * 4, hipMemcpyHostToDevice, st));
+  if (n1 > 0) LT_HIP(hipMemcpyAsync(base + L.o_id1, iota, n1 * 4, hipMemcpyHostToDevice, st));
   if (int e = staging_ring().commit(slot, st)) return e;
   if (n1 > 0)
-    if (int e = pool_stage(st, tab, 1, n1, n1, pd->chunks, (const int*)(base + o_id0), (const int*)(base + o_id1), d_dist, (float*)(base + o_dk),
-                           (int*)(base + o_scr))) return e;
-  hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, st, tab, thr, mutual, d_match01, (int*)(base + o_scr));
+    if (int e = pool_stage(st, tab, 1, n1, n1, pd->chunks, (const int*)(base + L.o_id0), (const int*)(base + L.o_id1), d_dist,
+                           (float*)(base + L.o_dk), (int*)(base + L.o_scr))) return e;
+  hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, st, tab, thr, mutual, d_match01, (int*)(base + L.o_scr));
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
 
+namespace {
+// workspace of linetr_match_distmat_f64: row minima | row argmins | column argmins
+struct DistmatF64Layout { int64_t o_row_min, o_row_arg, o_col_arg, total; };
+DistmatF64Layout distmat_f64_layout(int n0, int n1) {
+  DistmatF64Layout L{};
+  Carve c;
+  L.o_row_min = c.take((int64_t)n0 * 8);
+  L.o_row_arg = c.take((int64_t)n0 * 4);
+  L.o_col_arg = c.take((int64_t)std::max(n1, 1) * 4);
+  L.total = c.o + 256;
+  return L;
+}
+}  // namespace
+
 extern "C" int64_t linetr_match_distmat_f64_workspace_bytes(int32_t n0, int32_t n1) {
-  n0 = std::max(n0, 0); n1 = std::max(n1, 0);
-  return align_up((int64_t)n0 * 8, 256) + align_up((int64_t)n0 * 4, 256) + align_up((int64_t)std::max(n1, 1) * 4, 256) + 256;
+  return distmat_f64_layout(std::max(n0, 0), std::max(n1, 0)).total;
 }
 
 extern "C" int linetr_match_distmat_f64(LinetrHandle* h, const double* d_dist, int32_t n0, int32_t n1, double thr, int32_t mutual,
@@ -472,14 +529,15 @@ extern "C" int linetr_match_distmat_f64(LinetrHandle* h, const double* d_dist, i
   if (n0 < 0 || n1 < 0) return fail(LINETR_E_ARG, "match_distmat_f64: bad argument");
   if (n0 == 0) return LINETR_OK;
   if (!d_match01 || !d_ws || (n1 > 0 && !d_dist)) return fail(LINETR_E_ARG, "match_distmat_f64: null pointer");
-  if (ws_bytes < linetr_match_distmat_f64_workspace_bytes(n0, n1)) return fail(LINETR_E_WORKSPACE, "match_distmat_f64: workspace too small");
+  const DistmatF64Layout L = distmat_f64_layout(n0, n1);
+  if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "match_distmat_f64: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
   if (n1 == 0) { LT_HIP(hipMemsetAsync(d_match01, 0xff, (size_t)n0 * 4, st)); return LINETR_OK; }
   char* base = (char*)d_ws;
-  double* row_min = (double*)base;
-  int* row_arg = (int*)(base + align_up((int64_t)n0 * 8, 256));
-  int* col_arg = (int*)((char*)row_arg + align_up((int64_t)n0 * 4, 256));
+  double* row_min = (double*)(base + L.o_row_min);
+  int* row_arg = (int*)(base + L.o_row_arg);
+  int* col_arg = (int*)(base + L.o_col_arg);
   hipLaunchKernelGGL(argmin_rows_f64_kernel, dim3(cdiv(n0, 4)), dim3(256), 0, st, d_dist, n0, n1, row_arg, row_min);
   hipLaunchKernelGGL(argmin_cols_f64_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, d_dist, n0, n1, col_arg);
   hipLaunchKernelGGL(match_final_f64_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, st, (const int*)row_arg, (const double*)row_min,

@@ -310,11 +310,22 @@ int token_front(LinetrHandle* h, hipStream_t st, const TokenFront& a, const Line
   }
   return LINETR_OK;
 }
+
+// workspace of linetr_tokenize: channel-last copy of an NCHW descriptor map | global sub-line -> key-line map
+struct TokLayout { int64_t o_nhwc, o_s2l, total; };
+TokLayout tok_layout(int n_images, int height, int width, int N) {
+  TokLayout L{};
+  const int64_t P = (int64_t)(height / 8) * (width / 8);
+  Carve c;
+  L.o_nhwc = c.take(n_images * P * D * 4);
+  L.o_s2l = c.take((int64_t)std::max(N, 1) * 4);
+  L.total = c.o + 256;
+  return L;
+}
 }  // namespace
 
 extern "C" int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t N) {
-  const int64_t P = (int64_t)(height / 8) * (width / 8);
-  return align_up(n_images * P * D * 4, 256) + align_up((int64_t)std::max(N, 1) * 4, 256) + 256;
+  return tok_layout(n_images, height, width, N).total;
 }
 
 extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, double td,
@@ -334,15 +345,14 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
   if (out.mat && n_images != 1) return fail(LINETR_E_ARG, "tokenize: mat_klines2sublines of several images: use linetr_describe (it has the sub-line prefix sums)");
   K2sTable k2s;
   if (int e = k2s_table(out, n_images, K, N, nullptr, k2s, "tokenize")) return e;
-  if (ws_bytes < linetr_tokenize_workspace_bytes(n_images, height, width, N))
-    return fail(LINETR_E_WORKSPACE, "tokenize: workspace too small");
+  const TokLayout L = tok_layout(n_images, height, width, N);
+  if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "tokenize: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));   // no weights involved: without a handle the current device is used
-  const int64_t P = (int64_t)(height / 8) * (width / 8);
   TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, dense_is_nhwc,
                (double)clip_width - 0.6, (double)clip_height - 0.6, out.sublines, out.resp, out.angle_sub};
-  f.nhwc_buf = (float*)d_ws;
-  f.s2l_g = (int*)((char*)d_ws + align_up(n_images * P * D * 4, 256));
+  f.nhwc_buf = (float*)((char*)d_ws + L.o_nhwc);
+  f.s2l_g = (int*)((char*)d_ws + L.o_s2l);
   f.map_always = false;
   f.tokenize_bytes = (double)N * T * 16;
   const float* nhwc;

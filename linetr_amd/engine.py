@@ -702,7 +702,7 @@ class Engine(_TrainSurface, _DebugSurface):
         out = torch.empty((n, D), dtype=torch.float32, device=self.device)
         if n == 0:
             return out
-        ws = self._workspace("sample", self._L.linetr_sample_descriptors_workspace_bytes(Hc, Wc, int(nhwc)) + 256)
+        ws = self._workspace("sample", self._L.linetr_sample_descriptors_workspace_bytes(Hc, Wc, int(nhwc)))
         with torch.cuda.device(self.device):
             nat.check(self._L.linetr_sample_descriptors(self._h, pts.data_ptr(), n, dd.data_ptr(), Hc, Wc, int(bool(align_corners)),
                                                         int(nhwc), out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
@@ -807,8 +807,7 @@ class Engine(_TrainSurface, _DebugSurface):
         m01 = torch.full((n0,), -1, dtype=torch.int32, device=self.device)
         if n0 == 0 or n1 == 0:
             return dist, m01
-        need = 4 * (n0 + n1) * (D + 1) + 2048 + self._L.linetr_match_workspace_bytes(1, n0 * n1, 0, n0 + n1)
-        ws = self._workspace("match", need)
+        ws = self._workspace("match", self._L.linetr_match_points_workspace_bytes(n0, n1))
         nat.check(self._L.linetr_match_points(self._h, d0.data_ptr(), n0, d1.data_ptr(), n1, float(thr),
                                               int(bool(mutual)), dist.data_ptr(), m01.data_ptr(), ws.data_ptr(),
                                               ws.numel(), self._stream()), self._L)
@@ -1184,7 +1183,7 @@ class Engine(_TrainSurface, _DebugSurface):
             if dd is not None:
                 desc = torch.empty((D * n_total,), dtype=torch.float32, device=self.device)
                 if n_total > 0:
-                    wd = self._workspace("sample", self._L.linetr_point_descriptors_workspace_bytes(B, Hc, Wc, int(nhwc)) + 256)
+                    wd = self._workspace("sample", self._L.linetr_point_descriptors_workspace_bytes(B, Hc, Wc, int(nhwc)))
                     nat.check(self._L.linetr_point_descriptors(self._h, kp.data_ptr(), cu.data_ptr(), B, n_total, dd.data_ptr(), Hc, Wc,
                                                                int(bool(align_corners)), int(nhwc), desc.data_ptr(), wd.data_ptr(),
                                                                wd.numel(), self._stream()), self._L)

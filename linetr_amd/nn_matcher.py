@@ -84,8 +84,7 @@ def nn_matcher(desc0, desc1, nn_thresh=0.8, is_mutual_NN=True):
     dist = torch.empty((n0, n1), dtype=torch.float32, device=dev)
     m01 = torch.empty((n0,), dtype=torch.int32, device=dev)
     L = nat.lib()
-    need = 4 * (n0 + n1) * 257 + 4096 + L.linetr_match_workspace_bytes(1, n0 * n1, 0, n0 + n1)
-    ws = _workspace(dev, need)
+    ws = _workspace(dev, L.linetr_match_points_workspace_bytes(n0, n1))
     nat.check(L.linetr_match_points(None, d0.data_ptr(), n0, d1.data_ptr(), n1, float(np.float32(nn_thresh)),
                                     int(bool(is_mutual_NN)), dist.data_ptr(), m01.data_ptr(), ws.data_ptr(), ws.numel(),
                                     _stream(dev)))
