@@ -946,6 +946,89 @@ int linetr_warp_tile(int32_t* tile_h, int32_t* tile_w, int32_t* erode_tile_h, in
  * radius outside 0 .. 8, d_out overlapping d_mask. */
 int linetr_mask_erode(LinetrHandle* h, const uint8_t* d_mask, int32_t B, int32_t H, int32_t W, int32_t radius, uint8_t* d_out, void* stream);
 
+/* ---- photometric augmentation (dataloaders/build_homography_dataset.py:105-121, 154-158; dataloaders/utils/photometric.py) ----------- */
+
+/* The distortions of the dataset builder for batches of float32 grey images, seeded and deterministic: ImgAugTransform followed by
+ * customizedTransform, the same stages in the same order with the same 0..255 quantisation between them.  linetr_amd/csrc/lt_photometric.h
+ * is the contract (every stage down to its operation order, the Philox counter layout, the deviations from imgaug / OpenCV);
+ * tests/photometric_reference.py restates it in NumPy float64.  Stage bits of LinetrPhotoParams.stages / LinetrPhotoConfig.stages: */
+#define LINETR_PHOTO_BRIGHTNESS 1
+#define LINETR_PHOTO_CONTRAST 2
+#define LINETR_PHOTO_NOISE 4
+#define LINETR_PHOTO_IMPULSE 8
+#define LINETR_PHOTO_MOTION 16
+#define LINETR_PHOTO_BLUR 32
+#define LINETR_PHOTO_SHADE 64
+#define LINETR_PHOTO_MAX_K 7
+#define LINETR_PHOTO_MAX_KSIZE 351
+#define LINETR_PHOTO_MAX_ELLIPSES 20
+
+/* The ranges of homography.yaml's augmentation.photometric.params (a stage whose bit is clear is never drawn as enabled). */
+typedef struct LinetrPhotoConfig {
+  int32_t stages;              /* LINETR_PHOTO_* of the primitives the configuration has */
+  int32_t max_abs_change;      /* random_brightness: d uniform on the integers -max .. max; 0 .. 255 */
+  double strength_range[2];    /* random_contrast: alpha uniform in [lo, hi) */
+  double stddev_range[2];      /* additive_gaussian_noise: sigma uniform in [lo, hi), in levels */
+  double prob_range[2];        /* additive_speckle_noise: p uniform in [lo, hi), inside 0 .. 1; thr = floor(p 2^32) */
+  int32_t max_kernel_size;     /* motion_blur: applied with probability 1/2 with an odd K uniform on 3 .. max; 3 .. 7 */
+  int32_t nb_ellipses;         /* additive_shade: 0 .. 20 */
+  double blur_sigma;           /* GaussianBlur: sigma > 0; ksize by imgaug's rule (2.6 / 3.3 / 5.21 sigma below 3 / below 5 / above, at least 5, made odd) */
+  double transparency_range[2];/* additive_shade: t uniform in [lo, hi) */
+  int32_t kernel_size_range[2];/* additive_shade: ksize uniform on the integers lo .. hi - 1, made odd by + 1; the result within 1 .. 351 */
+} LinetrPhotoConfig;
+
+/* One image's drawn values: what the device call reads.  A field of a stage whose bit is clear is ignored but must still be valid. */
+typedef struct LinetrPhotoParams {
+  int32_t stages;              /* LINETR_PHOTO_* */
+  int32_t d;                   /* brightness, -255 .. 255 */
+  double alpha;                /* contrast */
+  double sigma;                /* noise, >= 0 */
+  uint32_t thr;                /* impulse threshold on a 32-bit word */
+  int32_t K;                   /* motion kernel extent: 1, 3, 5 or 7 */
+  float weights[49];           /* the K x K kernel row-major in the first K K entries */
+  int32_t blur_ksize;          /* stage 6: odd, 1 .. 351 */
+  double blur_sigma;           /* stage 6: >= 0; 0 = 0.3 ((ksize - 1) / 2 - 1) + 0.8 */
+  int32_t n_ellipses;          /* 0 .. 20 */
+  double ellipse[20][6];       /* cx, cy, ax, ay, c, s: centre, half axes (> 0), cosine and sine of the rotation */
+  double t;                    /* shade transparency */
+  int32_t shade_ksize;         /* odd, 1 .. 351 */
+} LinetrPhotoParams;
+
+/* linetr_photometric_sample: HOST only.  Fills h_params[0 .. B) for the images first .. first + B - 1 of an H x W batch from Philox4x32-10
+ * with key (seed, image) and counter (n, 0, 0, 1); u(n, 0) / u(n, 1) are the 53-bit uniforms of words 0, 1 / 2, 3 of call n:
+ *   n = 0: d = floor(u0 (2 max + 1)) - max; alpha.   n = 1: sigma; p.   n = 2: motion iff u0 < 1/2; K = 3 + 2 floor(u1 ((max - 3) / 2 + 1)).
+ *   n = 3: theta = pi u0; weights[i][j] = max(0, 1 - |cos(theta) (i - K / 2) - sin(theta) (j - K / 2)|), normalised in float64, rounded once.
+ *   n = 4: t; shade ksize.   n = 5 + 3 e, 6 + 3 e, 7 + 3 e for ellipse e: (ax, ay) = int(max(u min_dim, min_dim / 5)) with min_dim = min(H, W) / 4;
+ *   (cx, cy) = max_rad + floor(u (extent - 2 max_rad)) with max_rad = max(ax, ay); angle = 90 u0 degrees.
+ * Every range is lo + u (hi - lo).  The reference's randint(max_rad, extent - max_rad) cannot raise for any extent (2 max_rad <= min(H, W) / 2),
+ * but below min(H, W) = 20 an axis can become 0, which the analytic ellipse does not define: LINETR_E_ARG there when the shade is configured.
+ * LINETR_E_ARG also: NULL pointers, B, H or W below 1, first < 0, a seed beyond 32 bits, a range outside the above or with hi < lo.
+ *
+ * linetr_photometric: d_dst[b] = the stages of h_params[b] applied to d_src[b], float32 [B,1,H,W] in [0,1] in and out (an input outside
+ * [0,1] is clamped by stage 0).  Image b draws its per-pixel randomness with key (seed, first + b): a batch gives each image the bits it
+ * gets alone.  quantise_out = 1: floor of the shaded level (see the contract).  h_params is read before the call returns (it travels in the
+ * arguments of one small launch per 3 images; no host buffer has to outlive the call).  Asynchronous on `stream`; nothing inside allocates,
+ * waits or uses atomics; the same call gives the same bits; `h` may be NULL.
+ * linetr_gaussian_blur: stage 6 alone on float32 [B,C,H,W] of any values: per image an odd h_ksize[b] in 1 .. 351 and h_sigma[b] >= 0
+ * (0 = OpenCV's rule); quantise = 1 rounds the result to levels 0..255, 0 leaves the float32 sums.
+ * linetr_photometric_workspace_bytes: the bytes both calls need for [B,C,H,W] (C = 1 for linetr_photometric), 0 for a shape they refuse.
+ * linetr_photometric_tile: tile (rows, columns) and halo of the point kernel, strip (rows, columns) of the row pass, tile (rows, columns) of
+ * the column pass and the largest blur radius (the unit tests walk their edges).
+ * LINETR_E_ARG, nothing launched, no output changed: a NULL pointer; B, C, H or W below 1, B C above 65 535, H or W above 32 768, H W C at or
+ * beyond 2^31; a seed beyond 32 bits, first < 0 or first + B beyond 2^31; unknown stage bits; an even ksize or one outside 1 .. 351; K outside
+ * {1, 3, 5, 7}; n_ellipses outside 0 .. 20; d outside -255 .. 255; a non-finite parameter, a negative sigma, ax or ay <= 0; quantise_out /
+ * quantise other than 0 or 1; d_dst == d_src; a tensor that is not 4-byte or a workspace that is not 256-byte aligned.
+ * LINETR_E_WORKSPACE, nothing launched: a workspace shorter than linetr_photometric_workspace_bytes says. */
+int linetr_photometric_sample(const LinetrPhotoConfig* cfg, uint64_t seed, int32_t first, int32_t B, int32_t H, int32_t W,
+                              LinetrPhotoParams* h_params);
+int64_t linetr_photometric_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int linetr_photometric(LinetrHandle* h, const float* d_src, int32_t B, int32_t H, int32_t W, const LinetrPhotoParams* h_params, uint64_t seed,
+                       int32_t first, int32_t quantise_out, float* d_dst, void* d_workspace, int64_t workspace_bytes, void* stream);
+int linetr_gaussian_blur(LinetrHandle* h, const float* d_src, int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* h_ksize,
+                         const double* h_sigma, int32_t quantise, float* d_dst, void* d_workspace, int64_t workspace_bytes, void* stream);
+int linetr_photometric_tile(int32_t* tile_h, int32_t* tile_w, int32_t* halo, int32_t* row_tile_h, int32_t* row_tile_w, int32_t* col_tile_h,
+                            int32_t* col_tile_w, int32_t* max_radius);
+
 /* ---- line segment detector (the surface of models/line_detector.py:11-28; NOT OpenCV's LSD) ------------------------------------------ */
 
 /* A detector of the LSD / Burns family whose every step is independent of any processing order (DESIGN.md 4.18 has the algorithm down to

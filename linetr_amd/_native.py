@@ -87,6 +87,29 @@ class DetectConfig(C.Structure):
                 ("density", C.c_double)]
 
 
+class PhotoConfig(C.Structure):
+    """LinetrPhotoConfig: the ranges of homography.yaml's augmentation.photometric.params"""
+    _fields_ = [("stages", C.c_int32), ("max_abs_change", C.c_int32), ("strength_range", C.c_double * 2), ("stddev_range", C.c_double * 2),
+                ("prob_range", C.c_double * 2), ("max_kernel_size", C.c_int32), ("nb_ellipses", C.c_int32), ("blur_sigma", C.c_double),
+                ("transparency_range", C.c_double * 2), ("kernel_size_range", C.c_int32 * 2)]
+
+
+class PhotoParams(C.Structure):
+    """LinetrPhotoParams: one image's drawn values"""
+    _fields_ = [("stages", C.c_int32), ("d", C.c_int32), ("alpha", C.c_double), ("sigma", C.c_double), ("thr", C.c_uint32), ("K", C.c_int32),
+                ("weights", C.c_float * 49), ("blur_ksize", C.c_int32), ("blur_sigma", C.c_double), ("n_ellipses", C.c_int32),
+                ("ellipse", (C.c_double * 6) * 20), ("t", C.c_double), ("shade_ksize", C.c_int32)]
+
+
+# the same 1224 bytes as a NumPy record (arrays of images: np.zeros(B, PHOTO_PARAMS_DTYPE))
+PHOTO_PARAMS_DTYPE = np.dtype({"names": ["stages", "d", "alpha", "sigma", "thr", "K", "weights", "blur_ksize", "blur_sigma", "n_ellipses",
+                                         "ellipse", "t", "shade_ksize"],
+                               "formats": ["<i4", "<i4", "<f8", "<f8", "<u4", "<i4", ("<f4", 49), "<i4", "<f8", "<i4", ("<f8", (20, 6)), "<f8", "<i4"],
+                               "offsets": [0, 4, 8, 16, 24, 28, 32, 228, 232, 240, 248, 1208, 1216], "itemsize": 1224})
+assert PHOTO_PARAMS_DTYPE.itemsize == C.sizeof(PhotoParams) == 1224 and C.sizeof(PhotoConfig) == 96
+PHOTO_STAGES = {"brightness": 1, "contrast": 2, "noise": 4, "impulse": 8, "motion": 16, "blur": 32, "shade": 64}      # LINETR_PHOTO_*
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("calls", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -198,6 +221,11 @@ ABI = {
     "linetr_warp_images": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "linetr_warp_tile": (i32, [_P(i32), _P(i32), _P(i32), _P(i32)]),
     "linetr_mask_erode": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "linetr_photometric_sample": (i32, [_P(PhotoConfig), C.c_uint64, i32, i32, i32, i32, vp]),
+    "linetr_photometric_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "linetr_photometric": (i32, [vp, vp, i32, i32, i32, vp, C.c_uint64, i32, i32, vp, vp, i64, vp]),
+    "linetr_gaussian_blur": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp]),
+    "linetr_photometric_tile": (i32, [_P(i32)] * 8),
     "linetr_detect_lines_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "linetr_detect_lines": (i32, [vp, vp, i32, i32, i32, i32, _P(DetectConfig), i32, vp, vp, vp, vp, i64, vp]),
     "linetr_detect_tile": (i32, [_P(i32), _P(i32)]),

@@ -10,6 +10,8 @@
 //   linetr_sp.hip     the image front end: the native SuperPoint encoder (its own LinetrSpEncoder object; no LinetrHandle state) and the
 //                     homography views in front of it (lt_warp.h: warped image batches, valid masks, mask erosion)
 //   linetr_det.hip    the line segment detector (lt_linedet.h): linetr_detect_lines and its two debug entry points; no LinetrHandle state
+//   linetr_photo.hip  the photometric augmentation of the dataset builder (lt_photometric.h): host sampler, linetr_photometric,
+//                     linetr_gaussian_blur; no LinetrHandle state
 //   linetr_pair.hip   (experiments build only, experiments/csrc/) the single-pair persistent signature network
 #pragma once
 #include <map>

@@ -925,6 +925,68 @@ class Engine(_TrainSurface, _DebugSurface):
         self._call("linetr_mask_erode", mk.data_ptr(), int(B), int(H), int(W), int(radius), out.data_ptr())
         return out
 
+    # ------------------------------------------------------------------ photometric augmentation (csrc/lt_photometric.h; linetr_amd/photometric.py)
+    def photometric_tile(self):
+        """dict of the photometric kernels' tiles in pixels: 'point' (TH, TW, halo), 'row' (TH, TW), 'col' (TH, TW), 'max_radius'"""
+        v = [C.c_int32() for _ in range(8)]
+        nat.check(self._L.linetr_photometric_tile(*(C.byref(x) for x in v)), self._L)
+        v = [x.value for x in v]
+        return {"point": tuple(v[0:3]), "row": tuple(v[3:5]), "col": tuple(v[5:7]), "max_radius": v[7]}
+
+    def photometric_params(self, config, B, H, W, seed, first=0):
+        """The drawn values of the images first .. first + B - 1 of an H x W batch as a NumPy record array (nat.PHOTO_PARAMS_DTYPE), by the
+        host sampler linetr_photometric_sample.  config: a nat.PhotoConfig, or the reference's `augmentation` dict (homography.yaml)."""
+        if not isinstance(config, nat.PhotoConfig):
+            from .photometric import photo_config
+            config = photo_config(config)
+        params = np.zeros(int(B), nat.PHOTO_PARAMS_DTYPE)
+        nat.check(self._L.linetr_photometric_sample(C.byref(config), int(seed), int(first), int(B), int(H), int(W), nat.np_ptr(params)), self._L)
+        return params
+
+    def _plane_batch(self, images, channels=None):
+        img = self._on_device(images, "images")
+        if img.dim() != 4 or img.dtype != torch.float32 or (channels is not None and img.shape[1] != channels):
+            raise ValueError(f"images must be float32 [B,{channels or 'C'},H,W], got {img.dtype} {tuple(img.shape)}")
+        return img.contiguous()
+
+    def _like(self, out, img):
+        if out is None:
+            return torch.empty_like(img)
+        if tuple(out.shape) != tuple(img.shape) or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {tuple(img.shape)} tensor on {self.device}")
+        return out
+
+    def photometric(self, images: torch.Tensor, params, seed, quantise_out=False, out=None, first=0):
+        """The photometric stages of params[b] applied to image b of a float32 [B,1,H,W] batch in [0,1], in one native call
+        (linetr_photometric; csrc/lt_photometric.h states every stage).  params: the record array of photometric_params (or planted
+        values of the same dtype), read on the host.  Image b draws its per-pixel randomness with the key (seed, first + b).
+        quantise_out: the builder's (... * 255).astype('uint8') / 255 of the result."""
+        img = self._plane_batch(images, 1)
+        B, _, H, W = (int(v) for v in img.shape)
+        params = np.ascontiguousarray(params, dtype=nat.PHOTO_PARAMS_DTYPE)
+        if params.shape != (B,):
+            raise ValueError(f"{params.shape} parameter records for {B} images")
+        out = self._like(out, img)
+        ws = self._workspace("photo", self._L.linetr_photometric_workspace_bytes(B, 1, H, W))
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_photometric(self._h, img.data_ptr(), B, H, W, nat.np_ptr(params), int(seed), int(first), int(bool(quantise_out)),
+                                                 out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return out
+
+    def gaussian_blur(self, images: torch.Tensor, ksize, sigma=0.0, quantise=False, out=None):
+        """The separable Gaussian of stage 6 alone on a float32 [B,C,H,W] batch (linetr_gaussian_blur): odd ksize <= 351 and sigma (0 =
+        OpenCV's 0.3 ((ksize - 1) / 2 - 1) + 0.8), each one value or one per image; border reflect-101.  quantise: round to levels 0..255."""
+        img = self._plane_batch(images)
+        B, Cn, H, W = (int(v) for v in img.shape)
+        ks = np.ascontiguousarray(np.broadcast_to(np.asarray(ksize, dtype=np.int32), (B,)))
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (B,)))
+        out = self._like(out, img)
+        ws = self._workspace("photo", self._L.linetr_photometric_workspace_bytes(B, Cn, H, W))
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_gaussian_blur(self._h, img.data_ptr(), B, Cn, H, W, nat.np_ptr(ks), nat.np_ptr(sg), int(bool(quantise)),
+                                                   out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return out
+
     # ------------------------------------------------------------------ line segment detector (csrc/lt_linedet.h; linetr_amd/frontends)
     DETECT_DEFAULTS = {"n_octave": 2, "scale": 2, "grad_threshold": 28160, "min_region_size": 16, "density": 0.6}
 
