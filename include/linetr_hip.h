@@ -40,6 +40,8 @@
  *                step over a table of tensors and the gradient norm that can feed it): added symbols, the version stays.
  *                + linetr_debug_stage, linetr_debug_stage_workspace_bytes (the descriptive layer's tail or the signature network
  *                alone, through the forward pass's own host functions, for the unit tests): added diagnostics symbols, the version stays.
+ *                + LinetrPreparedEntry, linetr_debug_prepare (linetr_create's weight preparation alone, on the host, for the unit
+ *                tests): an added diagnostics symbol, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -1353,6 +1355,37 @@ int64_t linetr_debug_stage_workspace_bytes(const LinetrHandle* h, int32_t N, int
 int linetr_debug_stage(LinetrHandle* h, int32_t stage, int32_t N, const float* d_in0, const float* d_in1, const int32_t* h_cu_sub,
                        int32_t n_images, int32_t plan, float* d_out0, float* d_out1, float* d_out2, int32_t* plan_used, void* d_ws,
                        int64_t ws_bytes, void* stream);
+
+/* The weight preparation of linetr_create alone, on the host: no device, no handle (tests/test_prepare_cpu.py: every fold against a
+ * float64 restatement, bit for bit).  cfg .. numel as linetr_create takes them, refused with the same codes and texts.  One call
+ * prepares once and returns everything:
+ *   h_image  the float32 image of the weight arena exactly as linetr_create uploads it (every entry starts at a multiple of 64
+ *            floats), and behind it 8 more floats, c_tok[4] and s_cls[4] of the CLS pooling, which the handle keeps on the host;
+ *   h_table  one LinetrPreparedEntry per tensor, in placement order.
+ * *n_floats / *n_entries receive the two sizes whenever the preparation itself succeeded.  h_image and h_table both NULL: only the
+ * sizes.  A buffer shorter than its size (image_capacity in floats, table_capacity in entries): LINETR_E_CAPACITY, nothing written
+ * but the sizes.
+ * Entry names.  A GEMM weight W<x> [rows][K = cols] (LINETR_PREP_GEMM) is followed by its bias b<x> [rows]:
+ *   Wword1 bword1 (no GEMM), Wword2 .. Wword4, Wline1 bline1 (no GEMM), Wline2 .. Wline5   the positional encoders, BatchNorm folded
+ *   U, U2 [4][256], c_tok, s_cls [4]                                                       the CLS pooling constants
+ *   Watt [256][544], Wfc (bias + cls_token), ln1g, ln1b, Wf1, Wf2, ln2g, ln2b              the descriptive layer behind the pooling
+ *   Wqkv<l> [768][256] (head-major rows, q / 8), W1m<l> [512][512] (BatchNorm and merge folded), W2<l>      signature layer l
+ *   Wnext<l> [1024][768]                                                                   layers 0 .. L - 2
+ *   Wfin, Wfin2 [256][768] (L > 0)
+ *   bn_g<s>, bn_b<s> [channels]      a training-mode configuration: gamma / beta of slot s of the packed statistics, placed in front of
+ *                                    their (then unfolded) convolution
+ * LINETR_PREP_ST: linetr_create also makes a split-tile image of the weight. */
+typedef struct {
+  char name[24];      /* NUL-terminated                         */
+  int64_t offset;     /* in floats from h_image                 */
+  int32_t rows, cols;
+  int32_t flags;      /* LINETR_PREP_*                          */
+  int32_t reserved;
+} LinetrPreparedEntry; /* 48 bytes */
+enum { LINETR_PREP_GEMM = 1, LINETR_PREP_ST = 2 };
+int linetr_debug_prepare(const LinetrModelConfig* cfg, int32_t n_tensors, const char* const* names, const float* const* h_data,
+                         const int64_t* numel, float* h_image, int64_t image_capacity, LinetrPreparedEntry* h_table,
+                         int32_t table_capacity, int64_t* n_floats, int32_t* n_entries);
 
 #ifdef LINETR_EXPERIMENTS
 /* ---- split-tile ("ST") operands (csrc/lt_st_image.h; the GEMM on them: experiments/csrc/lt_gemm_st.h): experiments build only --------------------

@@ -110,6 +110,11 @@ assert PHOTO_PARAMS_DTYPE.itemsize == C.sizeof(PhotoParams) == 1224 and C.sizeof
 PHOTO_STAGES = {"brightness": 1, "contrast": 2, "noise": 4, "impulse": 8, "motion": 16, "blur": 32, "shade": 64}      # LINETR_PHOTO_*
 
 
+# LinetrPreparedEntry: one row of the table linetr_debug_prepare fills
+PREPARED_ENTRY_DTYPE = np.dtype([("name", "S24"), ("offset", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
+assert PREPARED_ENTRY_DTYPE.itemsize == 48
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("calls", C.c_int32), ("ms", C.c_float), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -255,6 +260,7 @@ ABI = {
     "linetr_debug_match": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
     "linetr_debug_stage_workspace_bytes": (i64, [vp, i32, i32]),
     "linetr_debug_stage": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "linetr_debug_prepare": (i32, [_P(ModelConfig), i32, _P(C.c_char_p), _P(vp), _P(i64), vp, i64, vp, i32, _P(i64), _P(i32)]),
     "linetr_allgather_desc": (i32, [vp, vp, vp, i64, vp]),
     "linetr_set_allgather_fn": (i32, [vp]),
     "linetr_pack_slab": (i32, [vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp]),

@@ -1,4 +1,4 @@
-// liblinetr_hip.so, translation unit 1 of 6: lifetime (float64 weight preparation), host pre-filter, the collective entry point
+// liblinetr_hip.so, translation unit 1 of 6: lifetime (the float64 weight preparation itself: lt_prepare.h), host pre-filter, the collective entry point
 // and the profiling entry points of the C ABI declared in include/linetr_hip.h.  No device code lives here.
 #include <dlfcn.h>
 
@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "lt_handle.h"
+#include "lt_prepare.h"
 
 using namespace lt;
 
@@ -83,48 +84,23 @@ class WorkPool {
   uint64_t gen_ = 0;
 };
 
-// ---- float64 weight preparation ---------------------------------------------------------------
-
-struct TensorMap {
-  std::map<std::string, std::pair<const float*, int64_t>> t;
-  const float* get(const std::string& k, int64_t numel, int& err) const {
-    auto it = t.find(k);
-    if (it == t.end() || it->second.first == nullptr) {
-      err = fail(LINETR_E_WEIGHTS, "state_dict tensor '%s' missing", k.c_str());
-      return nullptr;
-    }
-    if (it->second.second != numel) {
-      err = fail(LINETR_E_WEIGHTS, "state_dict tensor '%s' has %lld elements, expected %lld", k.c_str(),
-                 (long long)it->second.second, (long long)numel);
-      return nullptr;
-    }
-    return it->second.first;
+// Where the entries of the prepared table (lt_prepare.h) land in the handle, by entry name: GEMM weights (the bias goes along) and plain
+// vectors.  The handle's per-layer vectors have their final size before this is called.
+struct HandleSlots { std::map<std::string, GemmW*> gemm; std::map<std::string, const float**> vec; };
+HandleSlots slots_of(LinetrHandle* H) {
+  PosEncoder &w = H->enc[ENC_WORD], &l = H->enc[ENC_LINE];
+  HandleSlots s{{{"Wword2", &w.W2}, {"Wword3", &w.W3}, {"Wword4", &w.W4}, {"Wline2", &l.W2}, {"Wline3", &l.W3}, {"Wline4", &l.W4},
+                 {"Wline5", &H->lW5}, {"Watt", &H->Watt}, {"Wfc", &H->Wfc}, {"Wf1", &H->Wf1}, {"Wf2", &H->Wf2}, {"Wfin", &H->Wfin},
+                 {"Wfin2", &H->Wfin2}},
+                {{"Wword1", &w.W1}, {"bword1", &w.b1}, {"Wline1", &l.W1}, {"bline1", &l.b1}, {"U", &H->pool.U}, {"U2", &H->pool.U2},
+                 {"ln1g", &H->ln1g}, {"ln1b", &H->ln1b}, {"ln2g", &H->ln2g}, {"ln2b", &H->ln2b}}};
+  for (size_t i = 0; i < H->sig.size(); ++i) {
+    const std::string n = std::to_string(i);
+    s.gemm["Wqkv" + n] = &H->sig[i].Wqkv; s.gemm["W1m" + n] = &H->sig[i].W1; s.gemm["W2" + n] = &H->sig[i].W2; s.gemm["Wnext" + n] = &H->sig[i].Wnext;
   }
-};
-
-struct Arena {
-  std::vector<float> host;
-  size_t put(const std::vector<double>& v) {
-    size_t off = (host.size() + 63) / 64 * 64;
-    host.resize(off + v.size());
-    for (size_t i = 0; i < v.size(); ++i) host[off + i] = (float)v[i];
-    return off;
-  }
-};
-
-// Conv1d(k=1)+BatchNorm1d(eval) -> one affine map (models/line_transformer.py:9-20)
-void fold_bn(const float* W, const float* b, const float* g, const float* beta, const float* mean,
-             const float* var, int out, int in, std::vector<double>& Wf, std::vector<double>& bf) {
-  Wf.resize((size_t)out * in);
-  bf.resize(out);
-  for (int o = 0; o < out; ++o) {
-    const double s = (double)g[o] / std::sqrt((double)var[o] + 1e-5);
-    for (int i = 0; i < in; ++i) Wf[(size_t)o * in + i] = (double)W[(size_t)o * in + i] * s;
-    bf[o] = ((double)b[o] - (double)mean[o]) * s + (double)beta[o];
-  }
+  for (size_t i = 0; i < H->bn_g.size(); ++i) { s.vec["bn_g" + std::to_string(i)] = &H->bn_g[i]; s.vec["bn_b" + std::to_string(i)] = &H->bn_b[i]; }
+  return s;
 }
-
-std::vector<double> to_d(const float* p, size_t n) { return std::vector<double>(p, p + n); }
 
 }  // namespace
 
@@ -139,289 +115,38 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
                              const float* const* h_data, const int64_t* numel, int32_t device,
                              LinetrHandle** out) {
   if (!cfg || !out || !names || !h_data || !numel) return fail(LINETR_E_ARG, "null argument");
-  if (cfg->d_model != D || cfg->n_heads != HEADS)
-    return fail(LINETR_E_ARG, "only descriptor_dim=256 / n_heads=4 are supported");
-  if (cfg->d_inner % 128 != 0 || cfg->n_sig_layers < 0 || cfg->n_desc_layers < 1)
-    return fail(LINETR_E_ARG, "bad d_inner / layer counts");
-  const int e0 = cfg->enc_channels[0], e1 = cfg->enc_channels[1], e2 = cfg->enc_channels[2], e3 = cfg->enc_channels[3];
-  if (e0 != 32 || e1 % 64 || e2 % 64 || e3 % 64 || e3 != D)
-    return fail(LINETR_E_ARG, "keyline_encoder must be [32, 64k, 64k, 256] (got %d,%d,%d,%d)", e0, e1, e2, e3);
+  if (int e = check_model_config(cfg)) return e;
   int ndev = 0;
   LT_HIP(hipGetDeviceCount(&ndev));
   if (ndev <= 0 || device >= ndev) return fail(LINETR_E_HIP, "no usable HIP device (count=%d)", ndev);
   LT_HIP(hipSetDevice(device));
 
-  TensorMap tm;
-  for (int i = 0; i < n_tensors; ++i) tm.t[names[i]] = {h_data[i], numel[i]};
-  int err = 0;
-  Arena ar;
+  // the weights, prepared in float64 on the host (lt_prepare.h), as one upload
+  TensorMap tm(n_tensors, names, h_data, numel);
+  Prepared P;
+  if (int e = prepare_weights(*cfg, tm, P)) return e;
   auto H = std::make_unique<LinetrHandle>();
-  H->cfg = *cfg;
-  H->device = device;
-  struct Fix { const float** dst; size_t off; };
-  std::vector<Fix> fix;
-  auto place = [&](const float** dst, const std::vector<double>& v) { fix.push_back({dst, ar.put(v)}); };
-  std::vector<GemmWSpec> gemm_w;
-  // a GEMM weight [rows, K] and its bias.  st: the weight also gets a split-tile image (lt_st_image.h) -- the q/k/v projections,
-  // which the fused projection + attention kernel streams by LDS-DMA (lt_attn_fused.h); in the experiments build every eligible
-  // weight gets one
-  auto place_w = [&](GemmW* dst, const std::vector<double>& W, const std::vector<double>& b, int rows, int K, bool st = false) {
-    place(&dst->W, W);
-    place(&dst->b, b);
-    dst->rows = rows; dst->K = K;
-    gemm_w.push_back({dst, st});
-  };
-
-  // training-mode handle: gamma / beta of the 8 + n_sig_layers BatchNorm layers (the vectors are sized up front: place() keeps
-  // pointers to their elements until the arena is uploaded)
-  int bn_slot = 0;
-  if (cfg->bn_batch_stats) {
-    // the statistics scratch of linetr_forward_train is sized for BN_MAX_CHANNELS channels per BatchNorm layer
-    if (std::max(std::max(e0, e1), std::max(std::max(e2, e3), 2 * D)) > lt::BN_MAX_CHANNELS)
-      return fail(LINETR_E_ARG, "create: a training-mode handle (bn_batch_stats = 1) takes keyline_encoder widths up to %d (got %d, %d, %d, %d)",
-                  lt::BN_MAX_CHANNELS, e0, e1, e2, e3);
-    H->bn_g.reserve(8 + cfg->n_sig_layers); H->bn_b.reserve(8 + cfg->n_sig_layers); H->bn_c.reserve(8 + cfg->n_sig_layers);
-  }
-  // ---- positional encoders: 4 x (conv + BN + ReLU) + linear ------------------------------------
-  const int ch_w[6] = {3, e0, e1, e2, e3, D}, ch_l[6] = {5, e0, e1, e2, e3, D};
-  std::vector<double> W5w, b5w;  // last (linear) layer of the word encoder, consumed algebraically
-  for (int enc = 0; enc < 2; ++enc) {
-    const std::string pre = enc == 0 ? "klenc.word_position_enc.encoder." : "klenc.line_position_enc.encoder.";
-    const int* ch = enc == 0 ? ch_w : ch_l;
-    PosEncoder& E = H->enc[enc];
-    GemmW* const Wdst[4] = {nullptr, &E.W2, &E.W3, &E.W4};   // (layer 1 is no GEMM)
-    for (int i = 0; i < 4; ++i) {
-      const std::string c = pre + std::to_string(3 * i), bn = pre + std::to_string(3 * i + 1);
-      const float* W = tm.get(c + ".weight", (int64_t)ch[i + 1] * ch[i], err);
-      const float* b = tm.get(c + ".bias", ch[i + 1], err);
-      const float* g = tm.get(bn + ".weight", ch[i + 1], err);
-      const float* be = tm.get(bn + ".bias", ch[i + 1], err);
-      const float* mu = tm.get(bn + ".running_mean", ch[i + 1], err);
-      const float* va = tm.get(bn + ".running_var", ch[i + 1], err);
-      if (err) return err;
-      std::vector<double> Wf, bf;
-      if (cfg->bn_batch_stats) {     // training-mode handle: the convolution as it is, BatchNorm applied by lt_bntrain.h
-        Wf = to_d(W, (size_t)ch[i + 1] * ch[i]); bf = to_d(b, ch[i + 1]);
-        H->bn_g.push_back(nullptr); H->bn_b.push_back(nullptr); H->bn_c.push_back(ch[i + 1]);
-        place(&H->bn_g[bn_slot], to_d(g, ch[i + 1])); place(&H->bn_b[bn_slot], to_d(be, ch[i + 1]));
-        ++bn_slot;
-      } else
-      fold_bn(W, b, g, be, mu, va, ch[i + 1], ch[i], Wf, bf);
-      // layers 2-4 also get split-tile images: the one-kernel MLP of lt_tokmlp.h keeps layers 2 / 3 in LDS and layer 4 in registers as
-      // such, and the weight-stationary GEMM of lt_gemm_ws.h reads layer 4's planes from one
-      if (i == 0) { place(&E.W1, Wf); place(&E.b1, bf); }
-      else place_w(Wdst[i], Wf, bf, ch[i + 1], ch[i], true);
-    }
-    const float* W = tm.get(pre + "12.weight", (int64_t)D * e3, err);
-    const float* b = tm.get(pre + "12.bias", D, err);
-    if (err) return err;
-    if (enc == 0) { W5w = to_d(W, (size_t)D * D); b5w = to_d(b, D); }
-    else place_w(&H->lW5, to_d(W, (size_t)D * D), to_d(b, D), D, e3);
-  }
-
-  // ---- line-descriptive layer: only the last one matters (line_transformer.py:123-125) ----------
-  {
-    const std::string p = "klenc.desc_layers." + std::to_string(cfg->n_desc_layers - 1) + ".";
-    const float* cls = tm.get("klenc.cls_token", D, err);
-    const float* Wq = tm.get(p + "slf_attn.w_qs.weight", D * D, err);
-    const float* bq = tm.get(p + "slf_attn.w_qs.bias", D, err);
-    const float* Wk = tm.get(p + "slf_attn.w_ks.weight", D * D, err);
-    const float* bk = tm.get(p + "slf_attn.w_ks.bias", D, err);
-    const float* Wv = tm.get(p + "slf_attn.w_vs.weight", D * D, err);
-    const float* bv = tm.get(p + "slf_attn.w_vs.bias", D, err);
-    const float* Wfc = tm.get(p + "slf_attn.fc.weight", D * D, err);
-    const float* bfc = tm.get(p + "slf_attn.fc.bias", D, err);
-    const float* g1 = tm.get(p + "slf_attn.layer_norm.weight", D, err);
-    const float* b1 = tm.get(p + "slf_attn.layer_norm.bias", D, err);
-    const int DI = cfg->d_inner;
-    const float* W1 = tm.get(p + "pos_ffn.w_1.weight", (int64_t)DI * D, err);
-    const float* bb1 = tm.get(p + "pos_ffn.w_1.bias", DI, err);
-    const float* W2 = tm.get(p + "pos_ffn.w_2.weight", (int64_t)D * DI, err);
-    const float* bb2 = tm.get(p + "pos_ffn.w_2.bias", D, err);
-    const float* g2 = tm.get(p + "pos_ffn.layer_norm.weight", D, err);
-    const float* b2 = tm.get(p + "pos_ffn.layer_norm.bias", D, err);
-    if (err) return err;
-    // CLS query, pre-scaled by 1/sqrt(64) (line_attention.py:14)
-    std::vector<double> q(D);
-    for (int o = 0; o < D; ++o) {
-      double s = bq[o];
-      for (int i = 0; i < D; ++i) s += (double)Wq[o * D + i] * cls[i];
-      q[o] = s / 8.0;
-    }
-    std::vector<double> U(HEADS * D, 0.0), U2(HEADS * D, 0.0);
-    for (int h = 0; h < HEADS; ++h) {
-      double c = 0.0;
-      for (int d = 0; d < DH; ++d) {
-        const int o = h * DH + d;  // descriptive heads are head-major (line_attention.py:55-57)
-        c += q[o] * bk[o];
-        for (int i = 0; i < D; ++i) U[h * D + i] += q[o] * Wk[o * D + i];
-      }
-      for (int i = 0; i < D; ++i) {  // U2 = W5^T u_h
-        double s = 0.0;
-        for (int o = 0; o < D; ++o) s += W5w[(size_t)o * D + i] * U[h * D + o];
-        U2[h * D + i] = s;
-      }
-      double ub5 = 0.0, ucls = 0.0;
-      for (int i = 0; i < D; ++i) { ub5 += U[h * D + i] * b5w[i]; ucls += U[h * D + i] * cls[i]; }
-      H->pool.c_tok[h] = (float)(ub5 + c);
-      H->pool.s_cls[h] = (float)(ucls + c);
-    }
-    place(&H->pool.U, U);
-    place(&H->pool.U2, U2);
-    // value path after pooling: att_h = Wv_h dbar + (Wv_h W5) abar + p0 * Wv_h (cls - b5) + (Wv_h b5 + bv_h)
-    std::vector<double> Watt((size_t)HEADS * DH * POOLW, 0.0), batt(HEADS * DH);
-    for (int h = 0; h < HEADS; ++h)
-      for (int d = 0; d < DH; ++d) {
-        const int o = h * DH + d;
-        double* row = &Watt[((size_t)h * DH + d) * POOLW];
-        double r = 0.0, bb = bv[o];
-        for (int i = 0; i < D; ++i) {
-          row[i] = Wv[o * D + i];
-          r += (double)Wv[o * D + i] * ((double)cls[i] - b5w[i]);
-          bb += (double)Wv[o * D + i] * b5w[i];
-        }
-        for (int i = 0; i < D; ++i) {
-          double s = 0.0;
-          for (int m = 0; m < D; ++m) s += (double)Wv[o * D + m] * W5w[(size_t)m * D + i];
-          row[D + i] = s;
-        }
-        row[2 * D] = r;
-        batt[o] = bb;
-      }
-    place_w(&H->Watt, Watt, batt, HEADS * DH, POOLW);
-    std::vector<double> bfc2(D);
-    for (int i = 0; i < D; ++i) bfc2[i] = (double)bfc[i] + cls[i];  // residual of the CLS row is the constant token
-    place_w(&H->Wfc, to_d(Wfc, D * D), bfc2, D, D);
-    place(&H->ln1g, to_d(g1, D)); place(&H->ln1b, to_d(b1, D));
-    place_w(&H->Wf1, to_d(W1, (size_t)DI * D), to_d(bb1, DI), DI, D);
-    place_w(&H->Wf2, to_d(W2, (size_t)D * DI), to_d(bb2, D), D, DI);
-    place(&H->ln2g, to_d(g2, D)); place(&H->ln2b, to_d(b2, D));
-  }
-
-  // ---- signature layers --------------------------------------------------------------------------
+  H->cfg = *cfg; H->device = device;
+  LT_HIP(hipMalloc((void**)&H->arena, P.image.size() * sizeof(float)));
+  LT_HIP(hipMemcpy(H->arena, P.image.data(), P.image.size() * sizeof(float), hipMemcpyHostToDevice));
+  // every table entry to its field.  A training-mode handle: gamma / beta / channel count of the 8 + n_sig_layers BatchNorm layers
   H->sig.resize(cfg->n_sig_layers);
-  std::vector<std::vector<double>> sig_qkv_d, sig_bqkv_d, sig_w2_d, sig_b2_d;   // kept for the W2 + next-projection fold below
-  for (int l = 0; l < cfg->n_sig_layers; ++l) {
-    const std::string p = "selfattn.layers." + std::to_string(l) + ".";
-    const float* Wp[3];
-    const float* bp[3];
-    for (int j = 0; j < 3; ++j) {
-      Wp[j] = tm.get(p + "attn.proj." + std::to_string(j) + ".weight", D * D, err);
-      bp[j] = tm.get(p + "attn.proj." + std::to_string(j) + ".bias", D, err);
-    }
-    const float* Wm = tm.get(p + "attn.merge.weight", D * D, err);
-    const float* bm = tm.get(p + "attn.merge.bias", D, err);
-    const float* W1 = tm.get(p + "mlp.0.weight", 4 * D * D, err);
-    const float* b1 = tm.get(p + "mlp.0.bias", 2 * D, err);
-    const float* g = tm.get(p + "mlp.1.weight", 2 * D, err);
-    const float* be = tm.get(p + "mlp.1.bias", 2 * D, err);
-    const float* mu = tm.get(p + "mlp.1.running_mean", 2 * D, err);
-    const float* va = tm.get(p + "mlp.1.running_var", 2 * D, err);
-    const float* W2 = tm.get(p + "mlp.3.weight", 2 * D * D, err);
-    const float* b2 = tm.get(p + "mlp.3.bias", D, err);
-    if (err) return err;
-    // reference channel c = d*4 + h (line_transformer.py:151)  ->  head-major c' = h*64 + d;
-    // q additionally scaled by 1/sqrt(64) (:134), an exact power of two.
-    std::vector<double> Wqkv((size_t)3 * D * D), bqkv(3 * D);
-    for (int j = 0; j < 3; ++j)
-      for (int h = 0; h < HEADS; ++h)
-        for (int d = 0; d < DH; ++d) {
-          const int src = d * HEADS + h, dst = j * D + h * DH + d;
-          const double sc = j == 0 ? 0.125 : 1.0;
-          for (int i = 0; i < D; ++i) Wqkv[(size_t)dst * D + i] = (double)Wp[j][src * D + i] * sc;
-          bqkv[dst] = (double)bp[j][src] * sc;
-        }
-    std::vector<double> Wm2((size_t)D * D);
-    for (int o = 0; o < D; ++o)
-      for (int h = 0; h < HEADS; ++h)
-        for (int d = 0; d < DH; ++d) Wm2[(size_t)o * D + h * DH + d] = Wm[o * D + d * HEADS + h];
-    std::vector<double> W1f, b1f;
-    if (cfg->bn_batch_stats) {
-      W1f = to_d(W1, (size_t)4 * D * D); b1f = to_d(b1, 2 * D);
-      H->bn_g.push_back(nullptr); H->bn_b.push_back(nullptr); H->bn_c.push_back(2 * D);
-      place(&H->bn_g[bn_slot], to_d(g, 2 * D)); place(&H->bn_b[bn_slot], to_d(be, 2 * D));
-      ++bn_slot;
-    } else
-    fold_bn(W1, b1, g, be, mu, va, 2 * D, 2 * D, W1f, b1f);
-    // fold the attention's merge conv into the MLP's first layer (both linear, nothing in between):
-    //   W1 [x ; Wm a + bm] + b1 = W1a x + (W1b Wm) a + (W1b bm + b1)            (line_transformer.py:154,:166)
-    std::vector<double> W1m((size_t)2 * D * 2 * D);
-    for (int o = 0; o < 2 * D; ++o) {
-      const double* w1b = &W1f[(size_t)o * 2 * D + D];
-      for (int i = 0; i < D; ++i) W1m[(size_t)o * 2 * D + i] = W1f[(size_t)o * 2 * D + i];
-      for (int i = 0; i < D; ++i) {
-        double sacc = 0.0;
-        for (int m = 0; m < D; ++m) sacc += w1b[m] * Wm2[(size_t)m * D + i];
-        W1m[(size_t)o * 2 * D + D + i] = sacc;
-      }
-      double bacc = b1f[o];
-      for (int m = 0; m < D; ++m) bacc += w1b[m] * (double)bm[m];
-      b1f[o] = bacc;
-    }
-    SigLayer& S = H->sig[l];
-    sig_qkv_d.push_back(Wqkv); sig_bqkv_d.push_back(bqkv);
-    sig_w2_d.push_back(to_d(W2, (size_t)2 * D * D)); sig_b2_d.push_back(to_d(b2, D));
-    place_w(&S.Wqkv, Wqkv, bqkv, 3 * D, D, true);
-    place_w(&S.W1, W1m, b1f, 2 * D, 2 * D);
-    place_w(&S.W2, to_d(W2, (size_t)2 * D * D), to_d(b2, D), D, 2 * D);
-  }
-  // x_out = z + W2 hid + b2 (line_transformer.py:180-183) and the next layer's q/k/v projection is linear in x_out (:141-143), so
-  //   [x_out ; qkv_next] = [[I, W2], [Wqkv, Wqkv W2]] [z ; hid] + [b2 ; Wqkv b2 + bqkv]                      (float64, once)
-  // one contraction instead of two dependent ones -- 2.4x the flops, which only pays at single-pair sizes (linetr_net.hip)
-  for (int l = 0; l + 1 < cfg->n_sig_layers; ++l) {
-    const std::vector<double>&W2 = sig_w2_d[l], &b2 = sig_b2_d[l], &Wq = sig_qkv_d[l + 1], &bq = sig_bqkv_d[l + 1];
-    std::vector<double> Wn((size_t)4 * D * 3 * D, 0.0), bn(4 * D);
-    for (int o = 0; o < D; ++o) {
-      Wn[(size_t)o * 3 * D + o] = 1.0;
-      for (int j = 0; j < 2 * D; ++j) Wn[(size_t)o * 3 * D + D + j] = W2[(size_t)o * 2 * D + j];
-      bn[o] = b2[o];
-    }
-    for (int r = 0; r < 3 * D; ++r) {
-      double* row = &Wn[(size_t)(D + r) * 3 * D];
-      const double* wq = &Wq[(size_t)r * D];
-      for (int i = 0; i < D; ++i) row[i] = wq[i];
-      double bacc = bq[r];
-      for (int m2 = 0; m2 < D; ++m2) {          // row[D + j] += wq[m] * W2[m][j]: contiguous in j
-        const double a = wq[m2];
-        const double* w2r = &W2[(size_t)m2 * 2 * D];
-        for (int j = 0; j < 2 * D; ++j) row[D + j] += a * w2r[j];
-        bacc += a * b2[m2];
-      }
-      bn[D + r] = bacc;
-    }
-    place_w(&H->sig[l].Wnext, Wn, bn, 4 * D, 3 * D);
-  }
-  {
-    const float* W = tm.get("final_proj.weight", D * D, err);
-    const float* b = tm.get("final_proj.bias", D, err);
-    if (err) return err;
-    place_w(&H->Wfin, to_d(W, D * D), to_d(b, D), D, D);
-    if (cfg->n_sig_layers > 0) {
-      // x_out = z + W2 hid + b2 (line_transformer.py:180-183) and final_proj is linear (:245), so
-      //   final_proj(x_out) = [Wfin | Wfin W2] [z ; hid] + (Wfin b2 + bfin)          (float64, once)
-      const std::string p = "selfattn.layers." + std::to_string(cfg->n_sig_layers - 1) + ".";
-      const float* W2 = tm.get(p + "mlp.3.weight", 2 * D * D, err);
-      const float* b2 = tm.get(p + "mlp.3.bias", D, err);
-      if (err) return err;
-      std::vector<double> Wf((size_t)D * 3 * D), bf(D);
-      for (int o = 0; o < D; ++o) {
-        for (int i = 0; i < D; ++i) Wf[(size_t)o * 3 * D + i] = W[o * D + i];
-        for (int j = 0; j < 2 * D; ++j) {
-          double sacc = 0.0;
-          for (int m = 0; m < D; ++m) sacc += (double)W[o * D + m] * (double)W2[(size_t)m * 2 * D + j];
-          Wf[(size_t)o * 3 * D + D + j] = sacc;
-        }
-        double bacc = b[o];
-        for (int m = 0; m < D; ++m) bacc += (double)W[o * D + m] * (double)b2[m];
-        bf[o] = bacc;
-      }
-      place_w(&H->Wfin2, Wf, bf, D, 3 * D);
+  const size_t n_bn = cfg->bn_batch_stats ? 8 + cfg->n_sig_layers : 0;
+  H->bn_g.resize(n_bn); H->bn_b.resize(n_bn); H->bn_c.resize(n_bn);
+  const HandleSlots slots = slots_of(H.get());
+  std::vector<GemmWSpec> gemm_w;
+  for (size_t i = 0; i < P.table.size(); ++i) {
+    const PreparedEntry& e = P.table[i];
+    if (e.gemm) {   // a GEMM weight [rows, K] and, behind it, its bias
+      GemmW* w = slots.gemm.at(e.name);
+      w->W = H->arena + e.off; w->b = H->arena + P.table[++i].off; w->rows = e.rows; w->K = e.cols;
+      gemm_w.push_back({w, e.st});
+    } else {
+      *slots.vec.at(e.name) = H->arena + e.off;
+      if (e.name.compare(0, 4, "bn_g") == 0) H->bn_c[atoi(e.name.c_str() + 4)] = e.rows;   // bn_g<slot>: one row per channel
     }
   }
-
-  LT_HIP(hipMalloc((void**)&H->arena, ar.host.size() * sizeof(float)));
-  LT_HIP(hipMemcpy(H->arena, ar.host.data(), ar.host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& f : fix) *f.dst = H->arena + f.off;
+  for (int h = 0; h < HEADS; ++h) { H->pool.c_tok[h] = P.c_tok[h]; H->pool.s_cls[h] = P.s_cls[h]; }
   // split-precision copies of the GEMM weights: made on the device (linetr_net.hip owns the kernels)
   if (int e = make_split_copies(H.get(), gemm_w)) return e;
   if (const char* e = getenv("LINETR_PRECISION")) {
@@ -432,6 +157,40 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
     else return fail(LINETR_E_ARG, "LINETR_PRECISION must be f32, bf16x3, bf16x6 or f16x3 (got '%s')", e);
   }
   *out = H.release();
+  return LINETR_OK;
+}
+
+extern "C" int linetr_debug_prepare(const LinetrModelConfig* cfg, int32_t n_tensors, const char* const* names, const float* const* h_data,
+                                    const int64_t* numel, float* h_image, int64_t image_capacity, LinetrPreparedEntry* h_table,
+                                    int32_t table_capacity, int64_t* n_floats, int32_t* n_entries) {
+  if (!cfg || !names || !h_data || !numel || !n_floats || !n_entries) return fail(LINETR_E_ARG, "null argument");
+  if (int e = check_model_config(cfg)) return e;
+  TensorMap tm(n_tensors, names, h_data, numel);
+  Prepared P;
+  if (int e = prepare_weights(*cfg, tm, P)) return e;
+  const size_t arena = P.image.size();
+  *n_floats = (int64_t)arena + 2 * HEADS;
+  *n_entries = (int32_t)P.table.size() + 2;
+  if ((h_image && image_capacity < *n_floats) || (h_table && table_capacity < *n_entries))
+    return fail(LINETR_E_CAPACITY, "debug_prepare: %lld floats and %d entries do not fit %lld and %d", (long long)*n_floats, *n_entries,
+                (long long)image_capacity, table_capacity);
+  if (h_image) {
+    memcpy(h_image, P.image.data(), arena * sizeof(float));
+    memcpy(h_image + arena, P.c_tok, HEADS * sizeof(float));
+    memcpy(h_image + arena + HEADS, P.s_cls, HEADS * sizeof(float));
+  }
+  if (h_table) {
+    P.table.push_back({"c_tok", arena, HEADS, 1, false, false});
+    P.table.push_back({"s_cls", arena + HEADS, HEADS, 1, false, false});
+    for (size_t i = 0; i < P.table.size(); ++i) {
+      const PreparedEntry& e = P.table[i];
+      LinetrPreparedEntry o{};
+      snprintf(o.name, sizeof o.name, "%s", e.name.c_str());
+      o.offset = (int64_t)e.off; o.rows = e.rows; o.cols = e.cols;
+      o.flags = (e.gemm ? LINETR_PREP_GEMM : 0) | (e.st ? LINETR_PREP_ST : 0);
+      h_table[i] = o;
+    }
+  }
   return LINETR_OK;
 }
 

@@ -23,7 +23,7 @@
 namespace lt {
 
 constexpr int BN_MAX_BLOCKS = 512;     // row chunks of bn_partial_kernel (two per CU)
-// (BN_MAX_CHANNELS, lt_handle.h: the widest BatchNorm layer the statistics scratch is sized for)
+// (BN_MAX_CHANNELS, lt_common.h: the widest BatchNorm layer the statistics scratch is sized for)
 
 // what a training-time forward hands down to forward_core (linetr_forward_train)
 struct BnTrain {

@@ -20,6 +20,9 @@ constexpr int HEADS = 4;
 constexpr int DH = 64;      // D / HEADS
 constexpr int POOLW = 544;  // pooled row per head: [dbar(256) | abar(256) | p0 | 31 zeros]
 constexpr int WAVE = 64;
+// widest BatchNorm layer the statistics scratch of linetr_forward_train is sized for (2 D of the signature MLPs at D = 256, lt_bntrain.h);
+// the weight preparation (lt_prepare.h) refuses a training-mode handle with a wider layer
+constexpr int BN_MAX_CHANNELS = 512;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -128,7 +131,7 @@ __host__ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1,
 
 // ---- device helpers -------------------------------------------------------------------------
 
-// constants of the CLS-row attention pooling (lt_model.h: the cls_pool kernels; prepared in float64 by linetr_create)
+// constants of the CLS-row attention pooling (lt_model.h: the cls_pool kernels; prepared in float64 by lt_prepare.h)
 struct ClsPoolConst {
   const float* U;     // [4][256]  u_h
   const float* U2;    // [4][256]  W5^T u_h

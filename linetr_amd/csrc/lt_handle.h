@@ -1,6 +1,7 @@
 // The library handle and what every translation unit of liblinetr_hip.so shares: the prepared-weight table, the per-kernel-class
 // HIP-event profiler and the declarations of the few host functions that cross translation units.
-//   linetr_core.hip   lifetime (float64 weight preparation), host pre-filter, collective, profiling entry points
+//   linetr_core.hip   lifetime, host pre-filter, collective, profiling entry points.  linetr_create's float64 weight preparation is
+//                     lt_prepare.h: host only, no handle, one function per fold; create uploads its image and binds the handle by table entry
 //   linetr_net.hip    tokenise / forward / describe + the GEMM dispatcher and every model kernel (the experiments build includes
 //                     experiments/csrc/lt_x_net.h into it: the host code of its alternative paths and the hooks that select them)
 //   linetr_match.hip  matcher, dense-map producer, slab packing, SuperPoint's key-point branch
@@ -108,10 +109,6 @@ struct LinetrHandle {
 };
 
 namespace lt {
-
-// widest BatchNorm layer the statistics scratch of linetr_forward_train is sized for (2 D of the signature MLPs at D = 256, lt_bntrain.h);
-// linetr_create refuses a training-mode handle with a wider layer
-constexpr int BN_MAX_CHANNELS = 512;
 
 inline int prof_class(LinetrHandle* h, const char* name) {
   for (size_t i = 0; i < h->classes.size(); ++i)

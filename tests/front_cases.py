@@ -4,8 +4,10 @@ reused by tools/front_unit_report.py, which writes profiles/front_unit_errors.tx
 The descriptive layer's front end is the positional encoders' MLP up to its fourth ReLU (lt_tokmlp.h) and the CLS-row attention
 pooling (lt_model.h), fed through the NCHW -> NHWC layout pass.  Every case has two CPU references of the same formula, built from
 the UNFOLDED state dict -- conv + BatchNorm(eval) + ReLU layer by layer, w_qs / w_ks applied to cls_token and to every key -- in
-float64 (`ref64`) and in plain float32 torch (`ref32`); none of the constants linetr_create derives (U, U2, c_tok, s_cls, the folded
-weights) enters them, so the tests are the check of those constants too.  A kernel passes a unit (a 64-row tile of the MLP; a
+float64 (`ref64`) and in plain float32 torch (`ref32`); none of the constants the preparation (linetr_amd/csrc/lt_prepare.h, run by
+linetr_create) derives -- U, U2, c_tok, s_cls, the folded weights -- enters them, so the tests check the kernels on those constants
+end to end.  The constants themselves are pinned on the CPU: tests/test_prepare_cpu.py compares them with a float64 restatement from
+`_pool_consts` below, within one float32 ulp.  A kernel passes a unit (a 64-row tile of the MLP; a
 sub-line of the pooling, its 512 vector columns and its CLS weight p_0 measured separately) when
 
     max |gpu - ref64|  <=  FACTOR * max( max |ref32 - ref64| ,  2^-23 * max |ref64| )        (FACTOR = 8, as attn_cases.py)

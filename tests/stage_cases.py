@@ -4,8 +4,10 @@ reused by tools/stage_unit_report.py, which writes profiles/stage_unit_errors.tx
 Two stages from the middle of the forward pass run alone through linetr_debug_stage: the descriptive layer's tail (value projection,
 fc + LayerNorm, FFN with GELU, second LayerNorm + line_pos) and the line-signature network (0 .. 7 layers, final projection, L2
 norm).  Their references are built from the UNFOLDED torch state dict, in float64 (`ref64`) and in plain float32 torch (`ref32`);
-none of the weights linetr_create derives (Watt, the fc bias with the CLS residual, the permuted / scaled q/k/v projections, the
-BatchNorm and merge folds, Wnext, Wfin2) enters them, so the tests are the check of those folds too.
+none of the weights the preparation (linetr_amd/csrc/lt_prepare.h, run by linetr_create) derives -- Watt, the fc bias with the CLS
+residual, the permuted / scaled q/k/v projections, the BatchNorm and merge folds, Wnext, Wfin2 -- enters them, so the tests check the
+kernels on those folds end to end.  The folds themselves are pinned on the CPU: tests/test_prepare_cpu.py compares every prepared
+tensor with `folded` below, within one float32 ulp.
 
 TEACHER FORCING.  No bar compounds over layers: the reference of every tensor is computed from the tensor the device itself handed
 to that step -- o from the device's att, zA from the device's o, x_out behind layer l from the device's x_out behind layer l - 1
@@ -15,7 +17,7 @@ to that step -- o from the device's att, zA from the device's o, x_out behind la
 
 per tensor (tail) or per image and tensor (signature network).  The bar is a property of the CPU references alone.
 
-The second half of the file restates linetr_create's folds (float64, rounded once to float32) and the forward pass's float32 graph
+The second half of the file restates the folds of lt_prepare.h (float64, rounded once to float32) and the forward pass's float32 graph
 over them, with switches that plant one mistake each: tests/test_stage_cases_cpu.py runs it through the same checks in the device's
 place, to show that the cases leave the kernels headroom and that every planted mistake breaks a bar."""
 import functools
@@ -288,7 +290,7 @@ def worst(rows):
 
 
 # =================================================================================================================================
-# linetr_create's folds restated (float64, rounded once to float32) and the forward pass's float32 graph over them
+# the folds of lt_prepare.h restated (float64, rounded once to float32) and the forward pass's float32 graph over them
 # =================================================================================================================================
 
 MISTAKES = ("wfin2_bias_without_wfin_b2", "mlp0_bias_without_w1b_bm", "bn_eps_1e-6", "ln_eps_1e-5", "merge_columns_not_permuted",
@@ -302,7 +304,8 @@ def _head_major(W):
 
 @functools.lru_cache(maxsize=None)
 def folded(weights, n_layers=7, mistake=None):
-    """the weights linetr_create (linetr_core.hip) derives, as float32 tensors; `mistake`: one of MISTAKES planted"""
+    """the weights the preparation (lt_prepare.h) derives, as float32 tensors under its entry names; `mistake`: one of MISTAKES planted.
+    tests/test_prepare_cpu.py holds the library's own tensors to these"""
     assert mistake is None or mistake in MISTAKES
     sd = _cast(weights, n_layers, torch.float64)
     f = {}
