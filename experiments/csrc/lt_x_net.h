@@ -216,7 +216,7 @@ int sig_network_fused_mlp(LinetrHandle* h, hipStream_t st, const TokenStage& ts,
   for (size_t l = 0;; ++l) {
     const SigLayer& S = h->sig[l];
     if (fused_qkv_attn && S.Wqkv.st) {
-      if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, attn_fl, w.msgp))) return e;
+      if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, max_n, false, attn_fl, w.msgp))) return e;
     } else {
       if ((e = run_gemm(h, st, S.Wqkv, N, {z, D}, {w.qkv, 3 * D}, ACT_NONE))) return e;
       if ((e = sig_attention(h, st, attn_kernel, w.qkv, 3 * D, cu_dev, n_images, N, max_n, attn_fl, w.msgp))) return e;

@@ -1217,6 +1217,11 @@ int linetr_debug_gemm_case(LinetrHandle* h, const LinetrGemmCase* c, int32_t* ti
  *          3 sig_attn_split_kernel<8>                   -- otherwise, max_n > 128
  *          4 sig_qkv_attn_kernel (projection + attention fused) -- bf16x6, max_n <= 256, n_images * 4 >= 128, not the
  *                                                          folded single-pair path (small kernel and N <= 960)
+ *          4 + LINETR_SIG_EIGHT_WAVES (36): kernel 4 in its eight-compute-wave form whatever the size.  Kernel 4 itself runs
+ *            images of up to 224 sub-lines (max_n <= 224) with seven row-owning waves and the eighth as the operand ring's only
+ *            DMA issuer, and max_n 225 .. 256 with eight row-owning waves that each issue their share; both forms give the same
+ *            bits.  Forced only -- never the dispatcher's choice, never reported for kernel = -1 -- and reported back in
+ *            *kernel_used as 36.  Everything said of kernel 4 below holds for it.  (5 .. 35 stay refused.)
  * kernel 0-3: d_in = q/k/v rows [N][ld_in], head-major (q at column h*64 + d, k at 256 +, v at 512 +), q pre-scaled by 1/8 as
  *             the library's projection weights make them.  ld_in = 768; 1024 is legal for kernel 1 only (q/k/v behind x_out,
  *             the folded single-pair layout: d_in points at q, i.e. at column 256 of the [N][1024] rows).  `layer` is not read.
@@ -1228,6 +1233,7 @@ int linetr_debug_gemm_case(LinetrHandle* h, const LinetrGemmCase* c, int32_t* ti
  * with max_n > 256, a precision other than bf16x6, `layer` out of range or ld_in != 256; ld_in other than 768 (1024: kernel 1)
  * for kernels 0-3; a training-mode handle; misaligned (16 bytes) or NULL tensors.  With kernel = -1 and d_in = d_msg = NULL
  * only the choice is reported and nothing is launched.  kernel_used may be NULL.  Synchronises `stream` before returning. */
+enum { LINETR_SIG_EIGHT_WAVES = 32 };
 int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32_t layer, const float* d_in, int32_t ld_in,
                                const int32_t* h_cu_sub, int32_t n_images, float* d_msg, int32_t* kernel_used, void* stream);
 
@@ -1343,7 +1349,8 @@ int linetr_debug_match(LinetrHandle* h, int32_t P, const int32_t* dims, const fl
  *     d_out2 not read.
  *     plan: -1 = what the forward pass takes for this batch, or the signature-attention kernel 0 .. 4 as linetr_debug_sig_attention
  *     numbers them (4: the fused projection + attention) + LINETR_STAGE_FOLD_NEXT for the single-pair path whose x_out and next
- *     q/k/v projection come out of one contraction.  *plan_used (may be NULL) receives the plan that ran, in the same encoding.
+ *     q/k/v projection come out of one contraction, or 4 + LINETR_SIG_EIGHT_WAVES (the fused kernel's eight-compute-wave form at
+ *     any size).  *plan_used (may be NULL) receives the plan that ran, in the same encoding.
  *     A forced plan the stage's buffers or kernels cannot serve is refused: kernels 1-3 or 4 in f32 mode, 4 outside bf16x6 mode,
  *     with an image above 256 sub-lines or with fold_next, fold_next with a kernel other than 1 or above 960 sub-lines.
  * d_ws: linetr_debug_stage_workspace_bytes(h, N, n_images) bytes (n_images = 1 for the tail; -1 on bad arguments): the forward

@@ -733,6 +733,7 @@ enum { SIGK_F32 = 0, SIGK_SMALL = 1, SIGK_SPLIT4 = 2, SIGK_SPLIT8 = 3, SIGK_FUSE
 struct SigAttnPlan {
   int attn;
   bool fold_next, fused;
+  bool eight_waves = false;   // forced plans only (LINETR_SIG_EIGHT_WAVES): the fused kernel's eight-compute-wave form at any size
   int kernel() const { return fused ? SIGK_FUSED : attn; }
 };
 // The ONE place where the choice is made: sig_network and linetr_debug_sig_attention(kernel = -1) both call it.
@@ -794,12 +795,16 @@ int sig_attention(LinetrHandle* h, hipStream_t st, int kernel, const float* qkv,
 }
 
 // q/k/v projection + attention of an (image, head) in one launch (lt_attn_fused.h), z -> msg: q, k, v never reach HBM
+// Images of up to 224 sub-lines leave the eighth wave without rows: it becomes the ring's only DMA issuer (the producer form) and
+// the seven others keep MFMAs, LDS reads and the split in their loop.  Larger images, or `eight_waves` (a forced plan of the debug
+// entry points), take the form in which all eight waves compute and each issues its share.  Same bits either way.
 int sig_qkv_attention(LinetrHandle* h, hipStream_t st, const SigLayer& S, const float* z, const int* cu_dev, int n_images, int N,
-                      double attn_fl, float* msg) {
-  LT_HIP(allow_dynamic_lds<sig_qkv_attn_kernel>(FQA_LDS));
+                      int max_n, bool eight_waves, double attn_fl, float* msg) {
+  const bool producer = !eight_waves && max_n <= FQA_PRODUCER_ROWS;
+  LT_HIP(producer ? allow_dynamic_lds<sig_qkv_attn_kernel<true>>(FQA_LDS) : allow_dynamic_lds<sig_qkv_attn_kernel<false>>(FQA_LDS));
   ProfScope ps(h, st, "sig_qkv_attn_bf16x6", 2.0 * N * 3.0 * D * D + attn_fl, (double)N * D * 8);
-  hipLaunchKernelGGL(sig_qkv_attn_kernel, dim3(n_images, HEADS), dim3(512), FQA_LDS, st, z, S.Wqkv.st, S.Wqkv.b,
-                     cu_dev, msg);
+  hipLaunchKernelGGL(producer ? sig_qkv_attn_kernel<true> : sig_qkv_attn_kernel<false>, dim3(n_images, HEADS), dim3(512), FQA_LDS,
+                     st, z, S.Wqkv.st, S.Wqkv.b, cu_dev, msg);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
@@ -827,7 +832,7 @@ int sig_network(LinetrHandle* h, hipStream_t& st, const TokenStage& ts, const in
   for (size_t l = 0; l < h->sig.size(); ++l) {
     const SigLayer& S = h->sig[l];
     if (fused_qkv_attn && S.Wqkv.st) {
-      if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, attn_fl, w.msgp))) return e;
+      if ((e = sig_qkv_attention(h, st, S, z, cu_dev, n_images, N, max_n, plan.eight_waves, attn_fl, w.msgp))) return e;
     } else {
       // (with fold_next the previous layer has made them already)
       if (!fold_next || l == 0)
@@ -1247,14 +1252,17 @@ extern "C" int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32
                                           const int32_t* h_cu, int32_t n_images, float* d_msg, int32_t* kernel_used, void* stream) {
   if (!h) return fail(LINETR_E_ARG, "debug_sig_attention: null handle");
   if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_sig_attention: a training-mode handle (bn_batch_stats = 1) is not served");
-  if (kernel < -1 || kernel > SIGK_FUSED) return fail(LINETR_E_ARG, "debug_sig_attention: kernel must be -1 .. 4");
+  const bool eight_waves = kernel == (SIGK_FUSED | LINETR_SIG_EIGHT_WAVES);
+  if (eight_waves) kernel = SIGK_FUSED;
+  if (kernel < -1 || kernel > SIGK_FUSED)
+    return fail(LINETR_E_ARG, "debug_sig_attention: kernel must be -1 .. 4 (or 4 + %d: eight compute waves)", LINETR_SIG_EIGHT_WAVES);
   if (int e = check_cu(h_cu, n_images)) return e;
   const int N = h_cu[n_images];
   int max_n = 0;
   for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
   const bool query_only = kernel == -1 && !d_in && !d_msg;
   if (kernel == -1) kernel = sig_attn_plan(h, n_images, N, max_n).kernel();
-  if (kernel_used) *kernel_used = kernel;
+  if (kernel_used) *kernel_used = kernel | (eight_waves ? LINETR_SIG_EIGHT_WAVES : 0);
   if (query_only) return LINETR_OK;
   // what a kernel is not written for is refused, not launched
   if (kernel == SIGK_FUSED) {
@@ -1278,7 +1286,7 @@ extern "C" int linetr_debug_sig_attention(LinetrHandle* h, int32_t kernel, int32
     e = fail(LINETR_E_HIP, "debug_sig_attention: cu_sub upload failed");
   const double fl = attn_flops(h_cu, n_images);
   if (!e)
-    e = kernel == SIGK_FUSED ? sig_qkv_attention(h, st, h->sig[layer], d_in, cu_dev, n_images, N, fl, d_msg)
+    e = kernel == SIGK_FUSED ? sig_qkv_attention(h, st, h->sig[layer], d_in, cu_dev, n_images, N, max_n, eight_waves, fl, d_msg)
                              : sig_attention(h, st, kernel, d_in, ld_in, cu_dev, n_images, N, max_n, fl, d_msg);
   (void)hipStreamSynchronize(st);
   (void)hipFree(cu_dev);
@@ -1492,8 +1500,11 @@ extern "C" int linetr_debug_stage(LinetrHandle* h, int32_t stage, int32_t N, con
   if (sig) {
     if (int e = check_cu(h_cu, n_images)) return e;
     if (h_cu[n_images] != N) return fail(LINETR_E_ARG, "debug_stage: cu_sub does not end at N");
+    const bool eight_waves = plan == (SIGK_FUSED | LINETR_SIG_EIGHT_WAVES);
+    if (eight_waves) plan = SIGK_FUSED;
     if (plan < -1 || (plan & ~LINETR_STAGE_FOLD_NEXT) > SIGK_FUSED)
-      return fail(LINETR_E_ARG, "debug_stage: plan must be -1 or a kernel 0 .. 4 (+ %d: fold_next)", LINETR_STAGE_FOLD_NEXT);
+      return fail(LINETR_E_ARG, "debug_stage: plan must be -1 or a kernel 0 .. 4 (+ %d: fold_next; 4 + %d: eight compute waves)",
+                  LINETR_STAGE_FOLD_NEXT, LINETR_SIG_EIGHT_WAVES);
     int max_n = 0;
     for (int i = 0; i < n_images; ++i) max_n = std::max(max_n, h_cu[i + 1] - h_cu[i]);
     p = sig_attn_plan(h, n_images, N, max_n);
@@ -1503,9 +1514,10 @@ extern "C" int linetr_debug_stage(LinetrHandle* h, int32_t stage, int32_t N, con
       p.fused = kernel == SIGK_FUSED;
       if (!p.fused) p.attn = kernel;
       p.fold_next = (plan & LINETR_STAGE_FOLD_NEXT) != 0;
+      p.eight_waves = eight_waves;
       if (int e = sig_plan_servable(h, p, N, max_n)) return e;
     }
-    if (plan_used) *plan_used = p.kernel() | (p.fold_next ? LINETR_STAGE_FOLD_NEXT : 0);
+    if (plan_used) *plan_used = p.kernel() | (p.fold_next ? LINETR_STAGE_FOLD_NEXT : 0) | (p.eight_waves ? LINETR_SIG_EIGHT_WAVES : 0);
   } else if (plan != -1) {
     return fail(LINETR_E_ARG, "debug_stage: the tail has no plan to force (plan must be -1)");
   }

@@ -17,6 +17,17 @@
 //   3. attention exactly as sig_attn_split_kernel (lt_attn.h): S^T by split-bf16 MFMA, in-lane softmax, P^T from the
 //      accumulator registers, V^T fragments by transposing LDS reads; the message leaves as fp32 rows.
 // q, k, v never reach HBM; one launch per layer instead of two.  Images of up to 256 sub-lines (eight waves).
+//
+// Two forms, one body (template parameter PRODUCER; the launcher sig_qkv_attention picks by the batch's largest image):
+//   PRODUCER = false  eight row-owning waves, each issuing its share of a K step's 34 DMA pieces inside its MFMA phases and
+//                     doing its own counted wait.  Images of 225 .. 256 sub-lines.
+//   PRODUCER = true   images of at most 224 sub-lines leave wave 7 without rows (cfg3: 199 sub-lines).  It becomes the ring's only
+//                     issuer -- 32 pieces per K step, the counted wait in front of every publishing barrier -- and executes no MFMA,
+//                     no LDS read and no store; waves 0 .. 6 keep MFMAs, LDS reads and the split in their loop.  Gone: the eighth
+//                     wave's 576 projection MFMAs on rows nobody reads (1/8 of the projection, 8.3 % of the kernel's MFMAs) and
+//                     the DMA issue inside the MFMA phases of the SIMDs that carry two row-owning waves.
+// Per-row arithmetic is the same in both: the same bits for every image of at most 224 sub-lines (tests/test_gpu_attn_producer.py).
+// Measured (profiles/attn_producer_ab.txt).
 #pragma once
 #include "lt_st_image.h"
 #include "lt_attn.h"
@@ -28,6 +39,10 @@ constexpr int FQA_SLOT = FQA_W_BYTES + 256 * 64;        // + 256 rows x 16 fp32 
 constexpr int FQA_KEYS = 128;                           // keys per LDS half
 constexpr int FQA_LDS = 4 * FQA_SLOT;                   // 139 264 B; the K / V half images (124 928 B) alias the dead ring
 
+constexpr int FQA_PRODUCER_ROWS = 224;                  // the producer form: seven row-owning waves, the eighth feeds the ring
+constexpr int FQA_PRODUCER_DMA = 18 + FQA_PRODUCER_ROWS / 16;   // its pieces per K step: 18 of weights, 14 of activations
+
+template <bool PRODUCER>
 __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restrict__ z /*[N][256]*/,
                                                            const unsigned char* __restrict__ Wst /*ST image of Wqkv [768][256]*/,
                                                            const float* __restrict__ bqkv /*[768]*/,
@@ -40,8 +55,14 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h2 = lane >> 5, lq = lane & 31;
   const int q = wave * 32 + lq;                          // row of the image this lane owns (query AND key)
-  const bool wave_active = wave * 32 < Ni;               // wave-uniform
+  const bool producer = PRODUCER && wave == 7;           // wave-uniform: feeds the ring, owns no rows (Ni <= 224: the launcher)
+  const bool wave_active = !producer && wave * 32 < Ni;  // wave-uniform
   constexpr int RBW = 3 * D / 16, NK = D / 16;           // 48 row blocks of the weight image, 16 K steps
+  // Barriers a wave executes, identical for all eight on every path (a wave that owns no rows still walks every one of them):
+  //   Ni == 0: none (the whole block has returned above);
+  //   1. projection: 16 = one that publishes steps 0 and 1 + one at the end of each of steps 0 .. 14 (publishes step s + 2);
+  //   3. attention: 2 per key half (ring / previous half dead; half staged) = 2 for Ni <= 128, 4 above.
+  // The producer wave takes its 16 in its own loop below and the attention's in the shared loop, as a wave without rows.
 
   // ---- 1. projection --------------------------------------------------------------------------------------------
   // Ring slot of a K step (34 KiB): [weights: (q | k | v) x 4 row blocks x 3 planes x 512 B = 18 KiB][activations: 256 rows x 16
@@ -52,8 +73,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
   // next to 96 accumulators, and ordinary loads in flight beside LDS-DMA make hipcc drain the whole queue at their use.)
   const int n_dma = wave < 2 ? 5 : 4;
   const unsigned lane16 = lane * 16;
-  auto issue_one = [&](int d, int k, int slot) {
-    const int x = wave + 8 * d;
+  auto issue_piece = [&](int x, int k, int slot) {
     unsigned char* dst = fq_smem + slot * FQA_SLOT + x * 1024;
     if (x < 18) {
       const unsigned char* g = Wst + ((int64_t)k * RBW + (x / 6) * 16 + head * 4) * ST_RB + (x % 6) * 1024;
@@ -70,6 +90,7 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
       LT_GLDS(g, dst, 0);
     }
   };
+  auto issue_one = [&](int d, int k, int slot) { issue_piece(wave + 8 * d, k, slot); };
   auto issue_step = [&](int k, int slot) {
 #pragma unroll
     for (int d = 0; d < 5; ++d)
@@ -85,94 +106,8 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     }
   };
-#pragma unroll
-  for (int k = 0; k < 4; ++k) issue_step(k, k);
-  // accumulators start at the bias: in the transposed C/D layout register 4 b + c of tile i is channel 32 (i & 1) + 8 b + 4 h2 + c
-  // of q / k / v, so a group of four registers is one dwordx4 of the bias vector.  (Ordinary loads beside the DMA: hipcc
-  // drains the queue at their use, which here only means waiting for the prologue's four steps a little early.)
   f32x16 acc[6];
-  {
-    const float* bp = bqkv + head * DH + 4 * h2;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int bq = 0; bq < 4; ++bq) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(bp + (i >> 1) * D + (i & 1) * 32 + 8 * bq);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[i][4 * bq + c] = v[c];
-      }
-  }
-  wait_dma(2);                                             // steps 0 and 1 landed
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-
-  const int lfrag = ((lane >> 4) & 1) * ST_RB + (lane >> 5) * 256 + (lane & 15) * 16;
-  // this lane's two quarters (8 fp32 = k 8 h2 .. + 8 of its row) at their rotated slots (issue_one)
-  const int zrot = (lq >> 2) & 3;
-  const int zoff0 = FQA_W_BYTES + (wave * 32 + lq) * 64 + ((2 * h2 + zrot) & 3) * 16;
-  const int zoff1 = FQA_W_BYTES + (wave * 32 + lq) * 64 + ((2 * h2 + 1 + zrot) & 3) * 16;
-  using Terms = split_terms<3>;                            // the weights are the MFMA's A operand
-  // Fixed issue order (sched_barrier after every MFMA slot, as in the GEMMs): while n-tile i of step s multiplies, the weight
-  // fragments of n-tile i+1 are fetched; the activations of step s+1 are fetched at the start of step s and split into their
-  // planes under its MFMAs; during the last n-tile the first weight fragments of step s+1 arrive.  Steps s and s+1 are both
-  // visible while step s runs (the barrier at the end of step s-1 published step s+1), the DMA of step s+3 is issued from
-  // inside step s into the slot step s-1 left.
-  auto read_w = [&](int k, int i, int p, bf16x8 (&wf)[3]) {
-    wf[p] = *reinterpret_cast<const bf16x8*>(fq_smem + (k & 3) * FQA_SLOT + lfrag + ((i >> 1) * 4 + (i & 1) * 2) * ST_RB + p * ST_CHUNK);
-  };
-  auto split_z = [&](const f32x4& x0, const f32x4& x1, bf16x8 (&zf)[3]) {
-    unsigned a[3], b[3], c[3], d[3];
-    split_pair<3>(x0[0], x0[1], a); split_pair<3>(x0[2], x0[3], b);
-    split_pair<3>(x1[0], x1[1], c); split_pair<3>(x1[2], x1[3], d);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      union { bf16x8 v; unsigned w[4]; } u;
-      u.w[0] = a[p]; u.w[1] = b[p]; u.w[2] = c[p]; u.w[3] = d[p];
-      zf[p] = u.v;
-    }
-  };
-  bf16x8 zfA[3], zfB[3], wfA[3], wfB[3];
-  {
-    const f32x4 x0 = *reinterpret_cast<const f32x4*>(fq_smem + zoff0), x1 = *reinterpret_cast<const f32x4*>(fq_smem + zoff1);
-    split_z(x0, x1, zfA);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) read_w(0, 0, p, wfA);
-  }
-  auto step = [&](int s, bf16x8 (&zc)[3], bf16x8 (&zn)[3]) {
-    f32x4 zr0, zr1;
-    const bool more = s + 1 < NK;
-#pragma unroll
-    for (int m = 0; m < 36; ++m) {
-      const int i = m / 6, t = m % 6;
-      bf16x8 (&wc)[3] = (i & 1) ? wfB : wfA;
-      bf16x8 (&wn)[3] = (i & 1) ? wfA : wfB;
-      acc[i] = mfma_split<0>(wc[Terms::pa(t)], zc[Terms::pb(t)], acc[i]);
-      if (t < 3) {                                         // next weight fragments: n-tile i+1 of this step, or n-tile 0 of the next
-        if (i < 5) read_w(s, i + 1, t, wn);
-        else read_w(s + 1, 0, t, wn);                      // (past the last step: reads a slot that is never used; harmless)
-      }
-      if (m == 3) zr0 = *reinterpret_cast<const f32x4*>(fq_smem + ((s + 1) & 3) * FQA_SLOT + zoff0);
-      if (m == 4) zr1 = *reinterpret_cast<const f32x4*>(fq_smem + ((s + 1) & 3) * FQA_SLOT + zoff1);
-      if (m == 15) split_z(zr0, zr1, zn);
-      if (m >= 18 && m < 23 && s >= 1 && s + 3 < NK) { if (m - 18 < n_dma) issue_one(m - 18, s + 3, (s + 3) & 3); }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (more) {
-      wait_dma(s + 3 < NK ? 1 : 0);                        // step s+2 has landed; step s+3 may stay in flight
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#pragma unroll 1
-  for (int s = 0; s < NK; s += 2) {
-    step(s, zfA, zfB);         // six n-tiles: the weight fragments alternate A, B, A, B, A, B and hand A to the next step
-    step(s + 1, zfB, zfA);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  // ---- 2. Q to B fragments (registers), K / V pieces (registers until their half is staged) ----------------------------
+  bf16x8 qf[4][3];
   // piece g of accumulator tile i = channels 32 (i & 1) + 16 g + 8 h2 .. + 8 of this lane's row, after the half-wave swap
   auto pieces = [&](const f32x16& a, float scale, float (&v)[16]) {
 #pragma unroll
@@ -193,14 +128,134 @@ __global__ __launch_bounds__(512) void sig_qkv_attn_kernel(const float* __restri
       o[p] = u.v;
     }
   };
-  bf16x8 qf[4][3];
+  if (producer) {
+    // The eighth wave as the ring's only issuer (PRODUCER): all FQA_PRODUCER_DMA = 32 pieces of a K step (the activation rows
+    // of waves 0 .. 6; nobody reads rows 224 ..), the same sources and the same slot image as the distributed plan above.  Step
+    // s + 3 is issued as soon as the barrier that ends step s - 1 has freed its slot, and has until the barrier that ends step
+    // s + 1 to land: LDS-DMA completion is visible to the issuing wave's vmcnt alone, so the counted wait in front of every
+    // publishing barrier is this wave's.  (vmcnt has six bits: one step of 32 pieces can stay behind a counted wait, two cannot --
+    // which is why step 3 is issued behind the first barrier and not in front of it.)
+    static_assert(FQA_PRODUCER_DMA == 32, "the counted waits below say vmcnt(32)");
+    auto feed = [&](int k, int slot) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    float v[16];
-    pieces(acc[i], LOG2E, v);                              // scores in log2 units: exp -> v_exp_f32 (q is pre-scaled by 1/8)
-    split_run(v, qf[2 * i]);
-    split_run(v + 8, qf[2 * i + 1]);
-  }
+      for (int x = 0; x < FQA_PRODUCER_DMA; ++x) issue_piece(x, k, slot);
+    };
+    feed(0, 0);
+    feed(1, 1);
+    feed(2, 2);
+    asm volatile("s_waitcnt vmcnt(32)" ::: "memory");      // steps 0 and 1 landed
+    __builtin_amdgcn_s_barrier();                          // barrier 1 of 16
+    asm volatile("" ::: "memory");
+    feed(3, 3);
+#pragma unroll 1
+    for (int s = 0; s + 1 < NK; ++s) {                     // barriers 2 .. 16: the end of step s, publishing step s + 2
+      if (s >= 1 && s + 3 < NK) feed(s + 3, (s + 3) & 3);
+      if (s + 3 < NK) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");     // step s + 2 landed, step s + 3 may stay in flight
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    }
+  } else {
+    if constexpr (!PRODUCER) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) issue_step(k, k);
+    }
+    // accumulators start at the bias: in the transposed C/D layout register 4 b + c of tile i is channel 32 (i & 1) + 8 b + 4 h2 + c
+    // of q / k / v, so a group of four registers is one dwordx4 of the bias vector.  (Ordinary loads beside the DMA: hipcc
+    // drains the queue at their use, which here only means waiting for the prologue's four steps a little early.  With the
+    // producer wave a row-owning wave has no DMA in its queue and the loads wait for nothing but themselves.)
+    {
+      const float* bp = bqkv + head * DH + 4 * h2;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int bq = 0; bq < 4; ++bq) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(bp + (i >> 1) * D + (i & 1) * 32 + 8 * bq);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[i][4 * bq + c] = v[c];
+        }
+    }
+    if constexpr (!PRODUCER) wait_dma(2);                    // steps 0 and 1 landed
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    const int lfrag = ((lane >> 4) & 1) * ST_RB + (lane >> 5) * 256 + (lane & 15) * 16;
+    // this lane's two quarters (8 fp32 = k 8 h2 .. + 8 of its row) at their rotated slots (issue_piece)
+    const int zrot = (lq >> 2) & 3;
+    const int zoff0 = FQA_W_BYTES + (wave * 32 + lq) * 64 + ((2 * h2 + zrot) & 3) * 16;
+    const int zoff1 = FQA_W_BYTES + (wave * 32 + lq) * 64 + ((2 * h2 + 1 + zrot) & 3) * 16;
+    using Terms = split_terms<3>;                            // the weights are the MFMA's A operand
+    // Fixed issue order (sched_barrier after every MFMA slot, as in the GEMMs): while n-tile i of step s multiplies, the weight
+    // fragments of n-tile i+1 are fetched; the activations of step s+1 are fetched at the start of step s and split into their
+    // planes under its MFMAs; during the last n-tile the first weight fragments of step s+1 arrive.  Steps s and s+1 are both
+    // visible while step s runs (the barrier at the end of step s-1 published step s+1), the DMA of step s+3 is issued from
+    // inside step s into the slot step s-1 left.
+    auto read_w = [&](int k, int i, int p, bf16x8 (&wf)[3]) {
+      wf[p] = *reinterpret_cast<const bf16x8*>(fq_smem + (k & 3) * FQA_SLOT + lfrag + ((i >> 1) * 4 + (i & 1) * 2) * ST_RB + p * ST_CHUNK);
+    };
+    auto split_z = [&](const f32x4& x0, const f32x4& x1, bf16x8 (&zf)[3]) {
+      unsigned a[3], b[3], c[3], d[3];
+      split_pair<3>(x0[0], x0[1], a); split_pair<3>(x0[2], x0[3], b);
+      split_pair<3>(x1[0], x1[1], c); split_pair<3>(x1[2], x1[3], d);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        union { bf16x8 v; unsigned w[4]; } u;
+        u.w[0] = a[p]; u.w[1] = b[p]; u.w[2] = c[p]; u.w[3] = d[p];
+        zf[p] = u.v;
+      }
+    };
+    bf16x8 zfA[3], zfB[3], wfA[3], wfB[3];
+    {
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(fq_smem + zoff0), x1 = *reinterpret_cast<const f32x4*>(fq_smem + zoff1);
+      split_z(x0, x1, zfA);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) read_w(0, 0, p, wfA);
+    }
+    auto step = [&](int s, bf16x8 (&zc)[3], bf16x8 (&zn)[3]) {
+      f32x4 zr0, zr1;
+      const bool more = s + 1 < NK;
+#pragma unroll
+      for (int m = 0; m < 36; ++m) {
+        const int i = m / 6, t = m % 6;
+        bf16x8 (&wc)[3] = (i & 1) ? wfB : wfA;
+        bf16x8 (&wn)[3] = (i & 1) ? wfA : wfB;
+        acc[i] = mfma_split<0>(wc[Terms::pa(t)], zc[Terms::pb(t)], acc[i]);
+        if (t < 3) {                                         // next weight fragments: n-tile i+1 of this step, or n-tile 0 of the next
+          if (i < 5) read_w(s, i + 1, t, wn);
+          else read_w(s + 1, 0, t, wn);                      // (past the last step: reads a slot that is never used; harmless)
+        }
+        if (m == 3) zr0 = *reinterpret_cast<const f32x4*>(fq_smem + ((s + 1) & 3) * FQA_SLOT + zoff0);
+        if (m == 4) zr1 = *reinterpret_cast<const f32x4*>(fq_smem + ((s + 1) & 3) * FQA_SLOT + zoff1);
+        if (m == 15) split_z(zr0, zr1, zn);
+        if constexpr (!PRODUCER)
+          if (m >= 18 && m < 23 && s >= 1 && s + 3 < NK) { if (m - 18 < n_dma) issue_one(m - 18, s + 3, (s + 3) & 3); }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (more) {
+        if constexpr (!PRODUCER) wait_dma(s + 3 < NK ? 1 : 0);   // step s+2 has landed; step s+3 may stay in flight
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll 1
+    for (int s = 0; s < NK; s += 2) {
+      step(s, zfA, zfB);         // six n-tiles: the weight fragments alternate A, B, A, B, A, B and hand A to the next step
+      step(s + 1, zfB, zfA);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+    // ---- 2. Q to B fragments (registers), K / V pieces (registers until their half is staged) ----------------------------
+    // (pieces and split_run: above the projection)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      float v[16];
+      pieces(acc[i], LOG2E, v);                              // scores in log2 units: exp -> v_exp_f32 (q is pre-scaled by 1/8)
+      split_run(v, qf[2 * i]);
+      split_run(v + 8, qf[2 * i + 1]);
+    }
+  }  // !producer
   unsigned char* Ks = fq_smem;                             // [128][ATS_RK]
   unsigned char* Vs = fq_smem + FQA_KEYS * ATS_RK;         // [128][ATS_RV]
   auto stage_kv = [&]() {                                  // this wave's 32 keys into the current half

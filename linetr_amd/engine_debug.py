@@ -130,6 +130,7 @@ class _DebugSurface:
         return (full if groups > 1 or full is out else out), self._gemm_tile_name(used.value)
 
     SIG_KERNELS = ("sig_attn", "sig_attn_small", "sig_attn_split4", "sig_attn_split8", "sig_qkv_attn")
+    SIG_EIGHT_WAVES = 32         # LINETR_SIG_EIGHT_WAVES: added to 4 (forced only), sig_qkv_attn with eight compute waves at any size
 
     def sig_attention_kernel(self, cu_sub) -> int:
         """Which signature-attention kernel (index into SIG_KERNELS) the forward pass takes for a batch with these sub-line
