@@ -9,6 +9,14 @@
  * calling thread.  Nothing here ever falls back to a CPU implementation: if no HIP device is
  * usable, linetr_create() fails.
  *
+ * Host-side contract of every entry point.  No C++ exception leaves this interface because of an argument's value: a count, an offset
+ * table, a capacity or a name that cannot be served is refused with a LINETR_E_* code and a message (running out of memory has no
+ * code and is the one thing left out).  A size query (`*_workspace_bytes`, `*_output_bytes`, `*_pack_bytes`) never returns a wrapped
+ * number: its byte count is formed in int64_t behind a range check, and a shape whose size cannot be formed (beyond 2^56 bytes, far
+ * beyond any device) answers 0, as does a shape the query's own text says its entry point refuses; the entry point refuses such a
+ * shape whatever workspace it is given.  Where a query's text says nothing else, a negative count counts as 0.  The answer for every
+ * shape an entry point serves is the exact number of bytes it asks for.
+ *
  * Call sequence for one batch of B images (one image = B=1):
  *     linetr_prefilter / linetr_pack_lines   (host, O(K) per image)  -> line records
  *     linetr_tokenize                         (device)                -> the tensors of `preprocess`
@@ -145,7 +153,13 @@ void linetr_destroy(LinetrHandle* h);
  * returns K' in *k_out, the number of sub-lines of this image in *n_out.  LINETR_E_ASSERT if a token distance
  * exceeds the geometric line length (the reference's AssertionError, line_process.py:44-45).
  * Survivors are written straight into h_recs: on ANY error return the contents of h_recs are unspecified (the same holds
- * for linetr_prefilter_batch). */
+ * for linetr_prefilter_batch).
+ * LINETR_E_ARG, before a line is read: K < 0, h_lines6 NULL with K > 0, a NULL k_out / n_out, a negative height, width, border,
+ * capacity, sub_base or tok_base, h_recs NULL with capacity > 0, token_distance that is not > 0 (NaN included), max_tokens < 1.
+ * A line with a NaN or infinite coordinate, length or octave fails remove_borders' / filter_by_length's comparisons the way it does
+ * in the reference and is dropped; one whose length comes out infinite (an infinite lineLength, an octave beyond the exponent range)
+ * and survives them is refused with LINETR_E_ARG (its token count is absurd), as is a batch of more than 2^31 - 1 sub-lines or tokens.
+ * max_keylines may be any int32 (INT32_MIN: the slice [:-2^31], nothing survives). */
 int linetr_prefilter(const double* h_lines6, int32_t K, int32_t height, int32_t width, int32_t border,
                      double min_length, int32_t max_keylines, const double* h_valid_mask,
                      double token_distance, int32_t max_tokens, int32_t image_index, int32_t sub_base,
@@ -155,7 +169,11 @@ int linetr_prefilter(const double* h_lines6, int32_t K, int32_t height, int32_t 
  * 0 = library default).  h_lines6 holds the [K_i,6] blocks of all images back to back, h_line_off [B+1]
  * their row offsets; h_valid_masks is NULL or an array of B (nullable) [height,width] float64 pointers.
  * Writes the records image-major into h_recs (may be pinned memory) and the prefix sums of surviving
- * key-lines / sub-lines into h_cu_k / h_cu_n [B+1]. */
+ * key-lines / sub-lines into h_cu_k / h_cu_n [B+1].
+ * LINETR_E_ARG as linetr_prefilter, and: n_images < 0, n_threads < 0, a NULL offset table or prefix-sum array, an offset table that
+ * starts below 0 or decreases anywhere (image i owns rows h_line_off[i] .. h_line_off[i+1] of h_lines6; overlapping images cannot be
+ * written in this form).  The table's last entry is the number of rows the call reads: the interface carries no other count of the
+ * rows given, so a table that ends beyond the caller's array is the caller's to avoid, like any length. */
 int linetr_prefilter_batch(const double* h_lines6, const int32_t* h_line_off, int32_t n_images, int32_t height,
                            int32_t width, int32_t border, double min_length, int32_t max_keylines,
                            const double* const* h_valid_masks, double token_distance, int32_t max_tokens,
@@ -173,7 +191,10 @@ int32_t linetr_prefilter_tied_images(int32_t* h_images, int32_t capacity);
 
 /* Same record packing for lines that were already filtered/sorted by the caller (the Python shim
  * keeps NumPy's own argsort so that tie order is the reference's on the same machine).
- * h_klines [K,2,2], h_length [K], h_angles [K,2] float64. */
+ * h_klines [K,2,2], h_length [K], h_angles [K,2] float64.
+ * LINETR_E_ARG: K < 0, a NULL array with K > 0, a negative base, token_distance not > 0 (NaN included) or max_tokens < 1 (lines or no
+ * lines), a length that is NaN, infinite or not positive, more than 2^31 - 1 sub-lines or tokens; LINETR_E_ASSERT as linetr_prefilter
+ * (a NaN end point fails that comparison too). */
 int linetr_pack_lines(const double* h_klines, const double* h_length, const double* h_angles, int32_t K,
                       double token_distance, int32_t max_tokens, int32_t image_index, int32_t sub_base,
                       int32_t tok_base, LinetrLineRec* h_recs, int32_t* n_out);
@@ -759,7 +780,8 @@ int linetr_make_pseudo_lines(uint64_t seed, int32_t image_index, int32_t n, doub
 /* find_line_attributes (util_lines.py:634-668), host, float64: end points swapped unless sp_x < ep_x, length = sqrt(dx dx + dy dy),
  * lines shorter than min_length dropped, sorted by descending length under linetr_prefilter's tie rule (equal lengths by descending
  * original index), cut to [:max_sublines], angles as get_angles (the pre-filter's).  Writes *n_out rows of h_klines [n][2][2],
- * h_length [n], h_angles [n][2] (each sized for all n lines). */
+ * h_length [n], h_angles [n][2] (each sized for all n lines).  LINETR_E_ARG: n < 0, a NULL array with n > 0, a NULL n_out, a coordinate
+ * that is NaN or infinite (its length has no place in the order).  max_sublines may be any int32 (negative: the slice [:max_sublines]). */
 int linetr_find_line_attributes(const double* h_lines, int32_t n, double min_length, int32_t max_sublines, double* h_klines,
                                 double* h_length, double* h_angles, int32_t* n_out);
 
@@ -892,7 +914,8 @@ int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const 
  * candidates before the top-k, never capped: an image with d_found[b] > cap_per_image has been truncated to its first
  * cap_per_image candidates -- nothing is written past the capacity, the call still returns 0, and the caller repeats it with a
  * larger one.  nms_radius 0..8; max_keypoints -1 (all) or 1..4096; keypoint_threshold >= 0; other values: LINETR_E_ARG.
- * Asynchronous on `stream`; nothing inside allocates or waits.  `h` may be NULL (no weights involved; current HIP device). */
+ * Asynchronous on `stream`; nothing inside allocates or waits.  `h` may be NULL (no weights involved; current HIP device).
+ * The query answers 0 for H W or B H beyond 2^31 - 1, which the entry point refuses. */
 int64_t linetr_superpoint_keypoints_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap_per_image);
 int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense_score, int32_t B, int32_t H, int32_t W, int32_t nms_radius,
                                 float keypoint_threshold, int32_t remove_borders, int32_t max_keypoints, int32_t cap_per_image,
@@ -1120,7 +1143,7 @@ int linetr_sp_conv1a(LinetrHandle* h, const float* d_image, int32_t B, int32_t H
  *                                   nothing inside allocates or waits.
  * LINETR_E_ARG, nothing launched, no output changed: a NULL encoder or one without weights, B < 1 (or above 65 535), H or W below 8 (or
  * above 32 768), a required pointer that is NULL or not 16-byte aligned (d_feat: misaligned), a workspace smaller than
- * linetr_sp_encoder_workspace_bytes says. */
+ * linetr_sp_encoder_workspace_bytes says.  The query answers 0 for a B, H or W outside those ranges. */
 #define LINETR_SP_SCORE_LD 68
 typedef struct LinetrSpEncoder LinetrSpEncoder;
 int linetr_sp_encoder_create(int32_t device, LinetrSpEncoder** out);
@@ -1381,7 +1404,8 @@ int linetr_debug_stage(LinetrHandle* h, int32_t stage, int32_t N, const float* d
  *   Wfin, Wfin2 [256][768] (L > 0)
  *   bn_g<s>, bn_b<s> [channels]      a training-mode configuration: gamma / beta of slot s of the packed statistics, placed in front of
  *                                    their (then unfolded) convolution
- * LINETR_PREP_ST: linetr_create also makes a split-tile image of the weight. */
+ * LINETR_PREP_ST: linetr_create also makes a split-tile image of the weight.
+ * LINETR_E_ARG (linetr_create too): n_tensors < 0, a NULL entry of `names` (a NULL h_data[i] is an omitted tensor), a negative capacity. */
 typedef struct {
   char name[24];      /* NUL-terminated                         */
   int64_t offset;     /* in floats from h_image                 */

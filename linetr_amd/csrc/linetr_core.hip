@@ -102,6 +102,14 @@ HandleSlots slots_of(LinetrHandle* H) {
   return s;
 }
 
+// the state dict as an argument: a count and names a std::string can be made of (TensorMap, lt_prepare.h)
+int check_tensor_table(int32_t n_tensors, const char* const* names) {
+  if (n_tensors < 0) return fail(LINETR_E_ARG, "a negative number of state_dict tensors (%d)", n_tensors);
+  for (int32_t i = 0; i < n_tensors; ++i)
+    if (!names[i]) return fail(LINETR_E_ARG, "state_dict tensor %d has a NULL name", i);
+  return 0;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -115,6 +123,7 @@ extern "C" int linetr_create(const LinetrModelConfig* cfg, int32_t n_tensors, co
                              const float* const* h_data, const int64_t* numel, int32_t device,
                              LinetrHandle** out) {
   if (!cfg || !out || !names || !h_data || !numel) return fail(LINETR_E_ARG, "null argument");
+  if (int e = check_tensor_table(n_tensors, names)) return e;
   if (int e = check_model_config(cfg)) return e;
   int ndev = 0;
   LT_HIP(hipGetDeviceCount(&ndev));
@@ -164,6 +173,8 @@ extern "C" int linetr_debug_prepare(const LinetrModelConfig* cfg, int32_t n_tens
                                     const int64_t* numel, float* h_image, int64_t image_capacity, LinetrPreparedEntry* h_table,
                                     int32_t table_capacity, int64_t* n_floats, int32_t* n_entries) {
   if (!cfg || !names || !h_data || !numel || !n_floats || !n_entries) return fail(LINETR_E_ARG, "null argument");
+  if (image_capacity < 0 || table_capacity < 0) return fail(LINETR_E_ARG, "debug_prepare: a negative capacity");
+  if (int e = check_tensor_table(n_tensors, names)) return e;
   if (int e = check_model_config(cfg)) return e;
   TensorMap tm(n_tensors, names, h_data, numel);
   Prepared P;
@@ -229,8 +240,14 @@ extern "C" void linetr_destroy(LinetrHandle* h) {
 // host pre-filter
 // =============================================================================================
 
-static int pack_one(LinetrLineRec& r, double td, int T, int image, int line_local, int& sub_cursor, int& tok_cursor) {
+// what every packing entry point asks of its two tokeniser settings, lines or no lines (a NaN distance fails the comparison)
+static int check_token_args(double td, int T) {
   if (!(td > 0) || T < 1) return fail(LINETR_E_ARG, "token_distance must be > 0 and max_tokens >= 1");
+  return 0;
+}
+
+static int pack_one(LinetrLineRec& r, double td, int T, int image, int line_local, int& sub_cursor, int& tok_cursor) {
+  if (int e = check_token_args(td, T)) return e;
   const double nt = std::ceil(r.length / td);          // line_process.py:109
   if (!(nt >= 1) || nt > 1e7) return fail(LINETR_E_ARG, "key-line %d has a non-positive / absurd token count", line_local);
   r.n_tok = (int)nt;
@@ -239,6 +256,8 @@ static int pack_one(LinetrLineRec& r, double td, int T, int image, int line_loca
   r.image = image;
   r.line_local = line_local;
   r.first_tok = tok_cursor;
+  if ((int64_t)sub_cursor + r.n_sub > INT32_MAX || (int64_t)tok_cursor + r.n_tok > INT32_MAX)
+    return fail(LINETR_E_ARG, "more than 2^31 - 1 sub-lines or tokens in one batch (at key-line %d of image %d)", line_local, image);
   sub_cursor += r.n_sub;
   tok_cursor += r.n_tok;
   // the reference asserts every walked distance <= geometric length (:44-45)
@@ -267,6 +286,8 @@ extern "C" int linetr_pack_lines(const double* h_klines, const double* h_length,
                                  double td, int32_t T, int32_t image_index, int32_t sub_base, int32_t tok_base,
                                  LinetrLineRec* h_recs, int32_t* n_out) {
   if (K < 0 || (K > 0 && (!h_klines || !h_length || !h_angles || !h_recs))) return fail(LINETR_E_ARG, "null argument");
+  if (sub_base < 0 || tok_base < 0) return fail(LINETR_E_ARG, "pack_lines: a negative sub-line or token base");
+  if (int e = check_token_args(td, T)) return e;
   int cur = sub_base, tcur = tok_base;
   for (int k = 0; k < K; ++k) {
     LinetrLineRec& r = h_recs[k];
@@ -330,6 +351,9 @@ extern "C" int linetr_find_line_attributes(const double* h_lines, int32_t n, dou
   keep.reserve(n);
   for (int i = 0; i < n; ++i) {
     const double* l = h_lines + (size_t)i * 4;
+    // (a NaN length would pass the filter below and has no place in the sort's order)
+    if (!std::isfinite(l[0]) || !std::isfinite(l[1]) || !std::isfinite(l[2]) || !std::isfinite(l[3]))
+      return fail(LINETR_E_ARG, "find_line_attributes: line %d has a coordinate that is not finite", i);
     KeptLineAttr r;
     if (l[0] < l[2]) { r.sp[0] = l[0]; r.sp[1] = l[1]; r.ep[0] = l[2]; r.ep[1] = l[3]; }      // :641-646
     else { r.sp[0] = l[2]; r.sp[1] = l[3]; r.ep[0] = l[0]; r.ep[1] = l[1]; }
@@ -421,11 +445,21 @@ static void prefilter_core(const double* L, int32_t K, int32_t height, int32_t w
   }
 }
 
+// What both pre-filter entry points ask of the arguments they share, before a line is looked at.  A negative border would make the
+// valid mask's index wrap a second time; a negative image size has no pixels to be inside of.
+static int check_prefilter_args(int32_t height, int32_t width, int32_t border, double td, int32_t T, const LinetrLineRec* h_recs, int32_t capacity) {
+  if (height < 0 || width < 0 || border < 0) return fail(LINETR_E_ARG, "prefilter: negative height, width or border (%d, %d, %d)", height, width, border);
+  if (capacity < 0 || (capacity > 0 && !h_recs)) return fail(LINETR_E_ARG, "prefilter: a negative capacity, or records missing for a capacity of %d", capacity);
+  return check_token_args(td, T);
+}
+
 extern "C" int linetr_prefilter(const double* L, int32_t K, int32_t height, int32_t width, int32_t border,
                                 double min_length, int32_t max_keylines, const double* vm, double td, int32_t T,
                                 int32_t image_index, int32_t sub_base, int32_t tok_base, LinetrLineRec* h_recs,
                                 int32_t capacity, int32_t* k_out, int32_t* n_out) {
   if (K < 0 || (K > 0 && !L) || !k_out || !n_out) return fail(LINETR_E_ARG, "null argument");
+  if (sub_base < 0 || tok_base < 0) return fail(LINETR_E_ARG, "prefilter: a negative sub-line or token base");
+  if (int e = check_prefilter_args(height, width, border, td, T, h_recs, capacity)) return e;
   int64_t n_sel = -1;
   bool tied = false;
   g_tied_images.clear();
@@ -447,7 +481,14 @@ extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32
                                       int32_t border, double min_length, int32_t max_keylines,
                                       const double* const* vms, double td, int32_t T, int32_t n_threads,
                                       LinetrLineRec* h_recs, int32_t capacity, int32_t* cu_k, int32_t* cu_n) {
-  if (B < 0 || !off || !cu_k || !cu_n || (B > 0 && off[B] > 0 && !L)) return fail(LINETR_E_ARG, "null argument");
+  if (B < 0 || !off || !cu_k || !cu_n) return fail(LINETR_E_ARG, "null argument");
+  if (n_threads < 0) return fail(LINETR_E_ARG, "prefilter_batch: n_threads %d (0 = the library's default)", n_threads);
+  if (int e = check_prefilter_args(height, width, border, td, T, h_recs, capacity)) return e;
+  // the offset table: starts at or above 0 and never decreases (image i owns rows off[i] .. off[i + 1])
+  if (off[0] < 0) return fail(LINETR_E_ARG, "prefilter_batch: line offset 0 is negative (%d)", off[0]);
+  for (int i = 0; i < B; ++i)
+    if (off[i + 1] < off[i]) return fail(LINETR_E_ARG, "prefilter_batch: line offset %d (%d) is below offset %d (%d)", i + 1, off[i + 1], i, off[i]);
+  if (B > 0 && off[B] > off[0] && !L) return fail(LINETR_E_ARG, "null argument");
   WorkPool& pool = WorkPool::get();
   int nt = n_threads > 0 ? n_threads : pool.size();
   nt = std::max(1, std::min(nt, B / 4));  // not worth a hand-off for fewer than 4 images per chunk

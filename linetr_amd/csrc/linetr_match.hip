@@ -111,26 +111,26 @@ PairSlot* fused_pair_slot(int n0, int k0, int n1, int k1, hipStream_t st) {
 }
 
 // ints of argmin scratch one pair needs (layout in lt_match.h)
-int64_t pair_scratch_ints(int k0, int k1) { return 2 * (int64_t)k0 + 2 * (int64_t)k1 + 1 + 2 * (int64_t)cdiv(std::max(k0, 1), PM_ROWS) * k1 + 8; }
+int64_t pair_scratch_ints(int k0, int k1) { return sz_add(2 * (int64_t)k0 + 2 * (int64_t)k1 + 1, sz_mul(2 * (int64_t)cdiv(std::max(k0, 1), PM_ROWS), k1), 8); }
 
 // workspace of linetr_match / linetr_match_gathered: device pair table | distance matrices | argmin scratch
 struct MatchLayout { int64_t o_table, o_dist, o_scratch, total; };
 MatchLayout match_layout(int P, int64_t sum_n0n1, int64_t sum_k) {
   MatchLayout L{};
   Carve c;
-  L.o_table = c.take((int64_t)P * sizeof(PairDesc));
-  L.o_dist = c.take(sum_n0n1 * 4);
+  L.o_table = c.take(sz_mul(P, sizeof(PairDesc)));
+  L.o_dist = c.take(sz_mul(sum_n0n1, 4));
   // scratch bound: sum over pairs of pair_scratch_ints(k0,k1) <= 4 sum_k + 2 (sum_k0k1 / PM_ROWS + sum_k) + 9 P, and
   // k0 k1 <= n0 n1
-  L.o_scratch = c.take((6 * sum_k + 2 * (sum_n0n1 / PM_ROWS + 1) + 9 * (int64_t)P) * 4);
-  L.total = c.o + 256;
+  L.o_scratch = c.take(sz_mul(sz_add(sz_mul(6, sum_k), 2 * (sum_n0n1 / PM_ROWS + 1), sz_mul(9, P)), 4));
+  L.total = sz_add(c.o, 256);
   return L;
 }
 }  // namespace
 
 extern "C" int64_t linetr_match_workspace_bytes(int32_t n_pairs, int64_t sum_n0n1, int64_t sum_k0k1, int64_t sum_k) {
   (void)sum_k0k1;
-  return match_layout(n_pairs, sum_n0n1, sum_k).total;
+  return sz_answer(match_layout(n_pairs, sum_n0n1, sum_k).total);
 }
 
 namespace {
@@ -341,7 +341,7 @@ PointsLayout points_layout(int n0, int n1) {
   L.o_r1 = c.take((int64_t)std::max(n1, 1) * D * 4);
   L.o_id0 = c.take((int64_t)n0 * 4);
   L.o_id1 = c.take((int64_t)std::max(n1, 1) * 4);
-  L.match_bytes = match_layout(1, (int64_t)n0 * n1, n0 + n1).total;
+  L.match_bytes = match_layout(1, (int64_t)n0 * n1, (int64_t)n0 + n1).total;
   L.o_match = c.take(L.match_bytes);
   L.total = c.o;
   return L;
@@ -349,7 +349,7 @@ PointsLayout points_layout(int n0, int n1) {
 }  // namespace
 
 extern "C" int64_t linetr_match_points_workspace_bytes(int32_t n0, int32_t n1) {
-  return points_layout(std::max(n0, 0), std::max(n1, 0)).total;
+  return sz_answer(points_layout(std::max(n0, 0), std::max(n1, 0)).total);
 }
 
 extern "C" int linetr_match_points(LinetrHandle* h, const float* d0_cn, int32_t n0, const float* d1_cn, int32_t n1,
@@ -394,30 +394,31 @@ struct TailLayout { int64_t o_pd, o_pm, o_ld, o_lm, out_total, ws_points, ws_lin
 TailLayout tail_layout(int np0, int np1, int n0, int k0, int n1, int k1) {
   TailLayout L{};
   Carve c;
-  L.o_pd = c.take((int64_t)np0 * np1 * 4);
+  L.o_pd = c.take(sz_mul(np0, np1, 4));
   L.o_pm = c.take((int64_t)np0 * 4);
-  L.o_ld = c.take((int64_t)k0 * k1 * 4);
+  L.o_ld = c.take(sz_mul(k0, k1, 4));
   L.o_lm = c.take((int64_t)k0 * 4);
   L.out_total = c.o;
   L.ws_points = np0 > 0 && np1 > 0 ? points_layout(np0, np1).total : 0;
-  L.ws_lines = k0 > 0 && k1 > 0 ? match_layout(1, (int64_t)n0 * n1, k0 + k1).total : 0;
+  L.ws_lines = k0 > 0 && k1 > 0 ? match_layout(1, (int64_t)n0 * n1, (int64_t)k0 + k1).total : 0;
   Carve w;
   w.take(L.out_total);
   L.o_ws_points = w.take(L.ws_points);
   L.o_ws_lines = w.take(L.ws_lines);
-  L.ws_total = w.o + 256;
+  L.ws_total = sz_add(w.o, 256);
   return L;
 }
 }  // namespace
 
 extern "C" int64_t linetr_pair_tail_workspace_bytes(int32_t np0, int32_t np1, int32_t n0, int32_t k0, int32_t n1, int32_t k1) {
-  return tail_layout(std::max(np0, 0), std::max(np1, 0), std::max(n0, 0), std::max(k0, 0), std::max(n1, 0), std::max(k1, 0)).ws_total;
+  return sz_answer(tail_layout(std::max(np0, 0), std::max(np1, 0), std::max(n0, 0), std::max(k0, 0), std::max(n1, 0), std::max(k1, 0)).ws_total);
 }
 
 extern "C" int64_t linetr_pair_tail_output_bytes(int32_t np0, int32_t np1, int32_t k0, int32_t k1, int64_t* h_offsets) {
   const TailLayout L = tail_layout(std::max(np0, 0), std::max(np1, 0), 0, std::max(k0, 0), 0, std::max(k1, 0));
-  if (h_offsets) { h_offsets[0] = L.o_pd; h_offsets[1] = L.o_pm; h_offsets[2] = L.o_ld; h_offsets[3] = L.o_lm; }
-  return L.out_total;
+  const bool served = sz_answer(L.out_total) == L.out_total;      // a block beyond any size: 0, and the offsets with it
+  if (h_offsets) { h_offsets[0] = served ? L.o_pd : 0; h_offsets[1] = served ? L.o_pm : 0; h_offsets[2] = served ? L.o_ld : 0; h_offsets[3] = served ? L.o_lm : 0; }
+  return sz_answer(L.out_total);
 }
 
 extern "C" int linetr_pair_tail(LinetrHandle* h, const float* d_pdesc0_cn, int32_t np0, const float* d_pdesc1_cn, int32_t np1, float thr_p,
@@ -464,15 +465,15 @@ DistmatLayout distmat_layout(int n0, int n1) {
   c.take(256);
   L.o_id0 = c.take((int64_t)n0 * 4);
   L.o_id1 = c.take((int64_t)std::max(n1, 1) * 4);
-  L.o_dk = c.take((int64_t)n0 * std::max(n1, 1) * 4);
-  L.o_scr = c.take(pair_scratch_ints(n0, n1) * 4);
+  L.o_dk = c.take(sz_mul(n0, std::max(n1, 1), 4));
+  L.o_scr = c.take(sz_mul(pair_scratch_ints(n0, n1), 4));
   L.total = c.o;
   return L;
 }
 }  // namespace
 
 extern "C" int64_t linetr_match_distmat_workspace_bytes(int32_t n0, int32_t n1) {
-  return distmat_layout(std::max(n0, 0), std::max(n1, 0)).total;
+  return sz_answer(distmat_layout(std::max(n0, 0), std::max(n1, 0)).total);
 }
 
 extern "C" int linetr_match_distmat(LinetrHandle* h, const float* d_dist, int32_t n0, int32_t n1, float thr,
@@ -515,13 +516,13 @@ DistmatF64Layout distmat_f64_layout(int n0, int n1) {
   L.o_row_min = c.take((int64_t)n0 * 8);
   L.o_row_arg = c.take((int64_t)n0 * 4);
   L.o_col_arg = c.take((int64_t)std::max(n1, 1) * 4);
-  L.total = c.o + 256;
+  L.total = sz_add(c.o, 256);
   return L;
 }
 }  // namespace
 
 extern "C" int64_t linetr_match_distmat_f64_workspace_bytes(int32_t n0, int32_t n1) {
-  return distmat_f64_layout(std::max(n0, 0), std::max(n1, 0)).total;
+  return sz_answer(distmat_f64_layout(std::max(n0, 0), std::max(n1, 0)).total);
 }
 
 extern "C" int linetr_match_distmat_f64(LinetrHandle* h, const double* d_dist, int32_t n0, int32_t n1, double thr, int32_t mutual,
@@ -548,16 +549,15 @@ extern "C" int linetr_match_distmat_f64(LinetrHandle* h, const double* d_dist, i
 
 // subline2keyline (models/line_transformer.py:277-282) alone: Dk = A0 D A1^T for the segmented-mean matrices the tokeniser
 // produces, given as sub-line -> key-line maps (non-decreasing).  Same kernel as linetr_match's pooling stage.
-extern "C" int64_t linetr_pool_distmat_workspace_bytes(int32_t k0, int32_t k1) {
-  return align_up(pair_scratch_ints(std::max(k0, 0), std::max(k1, 0)) * 4, 256) + 256;
-}
+static int64_t pool_distmat_bytes(int k0, int k1) { return sz_add(align_up(sz_mul(pair_scratch_ints(std::max(k0, 0), std::max(k1, 0)), 4), 256), 256); }
+extern "C" int64_t linetr_pool_distmat_workspace_bytes(int32_t k0, int32_t k1) { return sz_answer(pool_distmat_bytes(k0, k1)); }
 
 extern "C" int linetr_pool_distmat(LinetrHandle* h, const float* d_dist, int32_t n0, int32_t n1, const int32_t* d_s2l0, int32_t k0,
                                    const int32_t* d_s2l1, int32_t k1, float* d_dk, void* d_ws, int64_t ws_bytes, void* stream) {
   if (n0 < 0 || n1 < 0 || k0 < 0 || k1 < 0 || k0 > n0 || k1 > n1) return fail(LINETR_E_ARG, "pool_distmat: bad dims");
   if (k0 == 0 || k1 == 0) return LINETR_OK;
   if (!d_dist || !d_s2l0 || !d_s2l1 || !d_dk || !d_ws) return fail(LINETR_E_ARG, "pool_distmat: null pointer");
-  if (ws_bytes < linetr_pool_distmat_workspace_bytes(k0, k1)) return fail(LINETR_E_WORKSPACE, "pool_distmat: workspace too small");
+  if (ws_bytes < pool_distmat_bytes(k0, k1)) return fail(LINETR_E_WORKSPACE, "pool_distmat: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
   PairTable tab{};
@@ -582,15 +582,15 @@ DensePoolLayout dense_pool_layout(int k0, int n0, int k1, int n1) {
   L.o_map1 = c.take((int64_t)std::max(n1, 1) * 4);
   L.o_val0 = c.take((int64_t)std::max(n0, 1) * 4);
   L.o_val1 = c.take((int64_t)std::max(n1, 1) * 4);
-  L.o_tmp = c.take((int64_t)std::max(k0, 1) * std::max(n1, 1) * 4);
-  L.o_pool = c.take(linetr_pool_distmat_workspace_bytes(std::min(k0, n0), std::min(k1, n1)));
+  L.o_tmp = c.take(sz_mul(std::max(k0, 1), std::max(n1, 1), 4));
+  L.o_pool = c.take(pool_distmat_bytes(std::min(k0, n0), std::min(k1, n1)));
   L.total = c.o;
   return L;
 }
 }  // namespace
 
 extern "C" int64_t linetr_pool_distmat_dense_workspace_bytes(int32_t k0, int32_t n0, int32_t k1, int32_t n1) {
-  return dense_pool_layout(std::max(k0, 0), std::max(n0, 0), std::max(k1, 0), std::max(n1, 0)).total;
+  return sz_answer(dense_pool_layout(std::max(k0, 0), std::max(n0, 0), std::max(k1, 0), std::max(n1, 0)).total);
 }
 
 extern "C" int linetr_pool_distmat_dense(LinetrHandle* h, const float* d_dist, int32_t n0, int32_t n1, const float* d_A0, int32_t k0,
@@ -708,10 +708,10 @@ KpLayout kp_layout(int B, int H, int W, int cap) {
   KpLayout L{};
   L.Wm = cdiv(W, 32);
   Carve c;
-  L.o_mask = c.take((int64_t)B * H * L.Wm * 4);
-  L.o_rowoff = c.take((int64_t)B * H * 4);
-  L.o_keys = c.take((int64_t)B * cap * 8);
-  L.total = c.o + 256;
+  L.o_mask = c.take(sz_mul(B, H, L.Wm, 4));
+  L.o_rowoff = c.take(sz_mul(B, H, 4));
+  L.o_keys = c.take(sz_mul(B, cap, 8));
+  L.total = sz_add(c.o, 256);
   return L;
 }
 
@@ -720,7 +720,8 @@ bool kp_lds_ok() { return allow_dynamic_lds<sp_nms_kernel>((int)kp_nms_lds(KP_MA
 }  // namespace
 
 extern "C" int64_t linetr_superpoint_keypoints_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap_per_image) {
-  return kp_layout(std::max(B, 0), std::max(H, 0), std::max(W, 0), std::max(cap_per_image, 0)).total;
+  if ((int64_t)std::max(H, 0) * std::max(W, 0) > INT32_MAX || (int64_t)std::max(B, 0) * std::max(H, 0) > INT32_MAX) return 0;   // refused by the entry point
+  return sz_answer(kp_layout(std::max(B, 0), std::max(H, 0), std::max(W, 0), std::max(cap_per_image, 0)).total);
 }
 
 extern "C" int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense_score, int32_t B, int32_t H, int32_t W, int32_t nms_radius,

@@ -315,17 +315,16 @@ int token_front(LinetrHandle* h, hipStream_t st, const TokenFront& a, const Line
 struct TokLayout { int64_t o_nhwc, o_s2l, total; };
 TokLayout tok_layout(int n_images, int height, int width, int N) {
   TokLayout L{};
-  const int64_t P = (int64_t)(height / 8) * (width / 8);
   Carve c;
-  L.o_nhwc = c.take(n_images * P * D * 4);
+  L.o_nhwc = c.take(sz_mul(n_images, height / 8, width / 8, D * 4));
   L.o_s2l = c.take((int64_t)std::max(N, 1) * 4);
-  L.total = c.o + 256;
+  L.total = sz_add(c.o, 256);
   return L;
 }
 }  // namespace
 
 extern "C" int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t N) {
-  return tok_layout(n_images, height, width, N).total;
+  return sz_answer(tok_layout(n_images, height, width, N).total);
 }
 
 extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, double td,
@@ -360,8 +359,9 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
 }
 
 // sample_descriptors (models/line_process.py:86-98) on its own: n points of ONE image
+static int64_t nhwc_copy_bytes(int B, int Hc, int Wc, int dense_is_nhwc) { return dense_is_nhwc ? 0 : align_up(sz_mul(B, Hc, Wc, D * 4), 256); }
 extern "C" int64_t linetr_sample_descriptors_workspace_bytes(int32_t Hc, int32_t Wc, int32_t dense_is_nhwc) {
-  return dense_is_nhwc ? 0 : align_up((int64_t)Hc * Wc * D * 4, 256);
+  return sz_answer(nhwc_copy_bytes(1, Hc, Wc, dense_is_nhwc));
 }
 
 extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points, int64_t n, const float* d_dense_desc, int32_t Hc,
@@ -372,7 +372,7 @@ extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points,
   if (!d_points || !d_dense_desc || !d_out) return fail(LINETR_E_ARG, "sample_descriptors: null pointer");
   if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(d_out) || !aligned16(d_ws))
     return fail(LINETR_E_ARG, "sample_descriptors: a channel-last descriptor map, the output and the workspace must be 16-byte aligned");
-  if (ws_bytes < linetr_sample_descriptors_workspace_bytes(Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
+  if (ws_bytes < nhwc_copy_bytes(1, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
     return fail(LINETR_E_WORKSPACE, "sample_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
@@ -388,7 +388,7 @@ extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points,
 
 // sample_descriptors (models/superpoint.py:81-93) for the packed key points of a batch (the output of linetr_superpoint_keypoints)
 extern "C" int64_t linetr_point_descriptors_workspace_bytes(int32_t B, int32_t Hc, int32_t Wc, int32_t dense_is_nhwc) {
-  return dense_is_nhwc ? 0 : align_up((int64_t)std::max(B, 0) * std::max(Hc, 0) * std::max(Wc, 0) * D * 4, 256);
+  return sz_answer(nhwc_copy_bytes(std::max(B, 0), std::max(Hc, 0), std::max(Wc, 0), dense_is_nhwc));
 }
 
 extern "C" int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const int32_t* d_cu_kp, int32_t B, int64_t n_total,
@@ -399,7 +399,7 @@ extern "C" int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoint
   if (!d_keypoints || !d_cu_kp || !d_dense_desc || !d_desc_cn) return fail(LINETR_E_ARG, "point_descriptors: null pointer");
   if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(d_ws))
     return fail(LINETR_E_ARG, "point_descriptors: a channel-last descriptor map and the workspace must be 16-byte aligned");
-  if (ws_bytes < linetr_point_descriptors_workspace_bytes(B, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
+  if (ws_bytes < nhwc_copy_bytes(B, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
     return fail(LINETR_E_WORKSPACE, "point_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));

@@ -69,8 +69,8 @@ struct SpLayout { int64_t o_a, o_b, total; };
 SpLayout sp_layout(int B, int H, int W) {
   SpLayout L{};
   Carve c;
-  L.o_a = c.take((int64_t)B * H * W * 64 * 4);                   // conv1a's output; every later "a" layer and the [cells, 512] rows fit
-  L.o_b = c.take((int64_t)B * (H / 2) * (W / 2) * 64 * 4);       // conv1b's pooled output; every later pooled map and conv4b's fit
+  L.o_a = c.take(sz_mul(B, H, W, 64 * 4));                   // conv1a's output; every later "a" layer and the [cells, 512] rows fit
+  L.o_b = c.take(sz_mul(B, H / 2, W / 2, 64 * 4));       // conv1b's pooled output; every later pooled map and conv4b's fit
   L.total = c.o;
   return L;
 }
@@ -178,7 +178,8 @@ extern "C" int linetr_sp_encoder_set_weights(LinetrSpEncoder* enc, const float* 
 }
 
 extern "C" int64_t linetr_sp_encoder_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-  return sp_layout(std::max(B, 0), std::max(H, 0), std::max(W, 0)).total;
+  if (B < 1 || B > SP_MAX_B || H < 8 || W < 8 || H > SP_MAX_DIM || W > SP_MAX_DIM) return 0;   // what linetr_sp_encoder_forward refuses
+  return sz_answer(sp_layout(B, H, W).total);
 }
 
 extern "C" int linetr_sp_encoder_forward(LinetrSpEncoder* enc, const float* d_image, int32_t B, int32_t H, int32_t W, float* d_score_rows,

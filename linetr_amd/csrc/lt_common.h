@@ -69,13 +69,30 @@ inline int fail(int code, const char* fmt, ...) {
                       __FILE__, __LINE__);                                                  \
   } while (0)
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// Sizes.  Every byte count a size query or a layout function forms goes through sz_mul / sz_add / align_up / Carve: non-negative
+// int64_t arithmetic that SATURATES at SZ_LIMIT instead of leaving its type (a negative operand saturates too).  No workspace is
+// anywhere near 2^56 bytes, so a saturated total means "a shape no entry point serves": a query returns sz_answer(total) = 0 for it and
+// never a wrapped number, and an entry point's `workspace_bytes < total` refuses it.  Below the limit every value is what plain
+// arithmetic gives.
+constexpr int64_t SZ_LIMIT = int64_t(1) << 56;
+inline int64_t sz_mul(int64_t a, int64_t b) {
+  int64_t r;
+  return (a < 0 || b < 0 || __builtin_mul_overflow(a, b, &r) || r > SZ_LIMIT) ? SZ_LIMIT : r;
+}
+template <class... T> inline int64_t sz_mul(int64_t a, int64_t b, T... more) { return sz_mul(sz_mul(a, b), more...); }
+inline int64_t sz_add(int64_t a, int64_t b) {
+  int64_t r;
+  return (a < 0 || b < 0 || __builtin_add_overflow(a, b, &r) || r > SZ_LIMIT) ? SZ_LIMIT : r;
+}
+template <class... T> inline int64_t sz_add(int64_t a, int64_t b, T... more) { return sz_add(sz_add(a, b), more...); }
+inline int64_t sz_answer(int64_t total) { return total >= SZ_LIMIT || total < 0 ? 0 : total; }
+inline int64_t align_up(int64_t v, int64_t a) { return (v < 0 || v > SZ_LIMIT - a) ? SZ_LIMIT : (v + a - 1) / a * a; }
 // What every entry point asks of a pointer its kernels access with 16-byte vectors (NULL passes: an absent optional pointer).
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // A workspace carved into 256-byte aligned segments: take(bytes) is the next segment's offset, `o` what has been handed out so far.
 struct Carve {
   int64_t o = 0;
-  int64_t take(int64_t bytes) { const int64_t at = o; o += align_up(bytes, 256); return at; }
+  int64_t take(int64_t bytes) { const int64_t at = o; o = sz_add(o, align_up(bytes, 256)); return at; }
 };
 // A launch with more dynamic LDS than the default limit needs the kernel opted in first, on every device it runs on.  Makes that
 // call once per kernel and device (one flag word per kernel, one bit per device) and is safe from several host threads: a thread
@@ -93,7 +110,7 @@ inline hipError_t allow_dynamic_lds(int bytes) {
   else (void)hipGetLastError();
   return e;
 }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+inline int cdiv(int a, int b) { return (int)(((int64_t)a + b - 1) / b); }   // the sum in int64_t: a may be INT32_MAX
 // Compute units of the device that is current at the first call (256 if it cannot be asked), cached for the process: what
 // the persistent launchers size their grids by.
 inline int cu_count() {
