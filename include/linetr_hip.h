@@ -50,6 +50,8 @@
  *                alone, through the forward pass's own host functions, for the unit tests): added diagnostics symbols, the version stays.
  *                + LinetrPreparedEntry, linetr_debug_prepare (linetr_create's weight preparation alone, on the host, for the unit
  *                tests): an added diagnostics symbol, the version stays.
+ *                + linetr_hardnet_loss_grad, linetr_hardnet_loss_grad_workspace_bytes (the HardNet criterion, value and gradient):
+ *                added symbols, nothing existing changes, the version stays.
  */
 #ifndef LINETR_HIP_H
 #define LINETR_HIP_H
@@ -463,6 +465,38 @@ int64_t linetr_desc_loss_grad_workspace_bytes(int32_t B, int32_t n);
 int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1, const float* d_assign,
                           int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1, void* h_pinned_out, int64_t pinned_bytes,
                           void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The reference's second criterion, descriptor_loss.compute_distances_hardnet (evaluations/criteria.py:126-171; its call site is the
+ * commented line of forward, :175-176): HardNet mining, value and gradient as torch autograd differentiates it, from one selection.
+ * Per item, with D[a][c] = 2 - 2 <d0[a], d1[c]> (float32, not clipped), match = assign > 0.3, unmatch = assign <= 0 on the [n][n] part
+ * (an entry in (0, 0.3] is neither; the dustbin row and column are not read) and cand = unmatch ? D : 10000:
+ *   rowmin[a] = min_c cand[a][c], colmin[c] = min_a cand[a][c].  There are 2n anchor lines: the n rows of D, then its n columns.
+ *   For a line r: pos_r = max(0, largest matched D on the line); it is an anchor iff pos_r > 0; p_r is the FIRST index attaining pos_r
+ *   (torch.max(dim)).  neg_r = min(own, cross): a row anchor a has own = rowmin[a], cross = colmin[p]; a column anchor c has
+ *   own = colmin[c], cross = rowmin[p].  No anchor is ever dropped: a line without an unmatched entry on either side has neg = 10000.
+ *   loss = mean over the V anchors of relu(pos - neg + 1), hardest_positive = max pos, hardest_negative = min neg (may be 10000),
+ *   reduced in a fixed order in float64.  V == 0: the three are NaN.  n = 1 with a match: loss 0, hardest_negative 10000, gradients zero.
+ * Gradient, w = upstream / V.  An anchor is live iff pos - neg + 1 > 0 (strict: relu'(0) = 0).  A live anchor gives +w to its positive
+ * entry at index p_r ONLY (nothing is split over tied positives).  Its -w goes to the own line if own < cross, to the cross line if
+ * own > cross, w / 2 to each if they are equal (the element-wise torch.min); on the chosen line the share is divided evenly over every
+ * unmatched entry equal to the minimum (amin's backward); entries valued 10000 carry nothing.  An entry of D collects the sum of what
+ * row anchors and column anchors give it.  grad0[a] = -2 sum_c G[a][c] d1[c],   grad1[c] = -2 sum_a G[a][c] d0[a].
+ * G is gathered tile by tile on the chip and never stored; no floating-point atomics, every reduction has a fixed order: two calls give
+ * the same bits.  Five launches and one copy; four when both gradients are NULL (the value-only call: the same scalars, bit for bit).
+ *   d_desc0 / d_desc1, d_assign, d_upstream, d_grad0 / d_grad1   as linetr_desc_loss_grad documents them; EVERY gradient row is
+ *       written and zeros are +0
+ *   d_row_pos / d_row_neg  [B][2n] float32 or NULL: pos of every line; neg, or -1 where the line is no anchor
+ *   d_row_arg          [B][2n] int32 or NULL: the positive's index along the line, or -1 where the line is no anchor
+ *   h_pinned_out       PINNED host block of at least 40 bytes, filled by one asynchronous copy:
+ *       float64 [3] loss, hardest_positive, hardest_negative | int64 [2] V, the number of live anchors
+ * Asynchronous on `stream`; nothing inside allocates or waits; `h` may be NULL.  n0 != n1, B <= 0, n <= 0 (or beyond 65535 items / 32768
+ * sub-lines), a NULL required pointer, an output block shorter than 40 bytes or a workspace smaller than
+ * linetr_hardnet_loss_grad_workspace_bytes says: LINETR_E_ARG, nothing launched. */
+int64_t linetr_hardnet_loss_grad_workspace_bytes(int32_t B, int32_t n);
+int linetr_hardnet_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1,
+                             const float* d_assign, int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1,
+                             float* d_row_pos, float* d_row_neg, int32_t* d_row_arg,
+                             void* h_pinned_out, int64_t pinned_bytes, void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- backward of the 1x1 layers and the descriptor head (section 8(f) "next" row 4: the second link) ---------- */
 

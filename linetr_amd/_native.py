@@ -171,6 +171,8 @@ ABI = {
     "linetr_assign_from_matches": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "linetr_desc_loss_grad_workspace_bytes": (i64, [i32, i32]),
     "linetr_desc_loss_grad": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, i64, vp]),
+    "linetr_hardnet_loss_grad_workspace_bytes": (i64, [i32, i32]),
+    "linetr_hardnet_loss_grad": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),
     "linetr_linear_backward_chunk_rows": (i32, []),
     "linetr_linear_backward_workspace_bytes": (i64, [i64, i32, i32]),
     "linetr_linear_forward": (i32, [vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, i64, vp]),

@@ -1,6 +1,7 @@
 // liblinetr_hip.so, translation unit 4 of 6: training and evaluation (C ABI in include/linetr_hip.h).
 //   lt_valstep.h    the validation step
 //   lt_lossgrad.h   the criterion's gradient
+//   lt_hardnet.h    the HardNet criterion, value and gradient
 //   lt_linbwd.h     the backward of the 1x1 layers and the descriptor head
 //   lt_attnbwd.h    the neighbour-line attention's forward with statistics and its backward
 //   lt_bnbwd.h      BatchNorm on batch statistics with its backward
@@ -15,6 +16,7 @@
 #include "lt_handle.h"
 #include "lt_valstep.h"
 #include "lt_lossgrad.h"
+#include "lt_hardnet.h"
 #include "lt_linbwd.h"
 #include "lt_attnbwd.h"
 #include "lt_bnbwd.h"
@@ -67,7 +69,7 @@ ValWsLayout val_ws_layout(int B, int n) {
 }
 bool val_dims_ok(int B, int n) { return B > 0 && B <= VS_MAX_B && n > 0 && n <= VS_MAX_N; }
 
-// The prologue of the two criterion entry points (linetr_val_step, linetr_desc_loss_grad), for `who`.  First their refusals, every one
+// The prologue of the criterion entry points (linetr_val_step, linetr_desc_loss_grad, linetr_hardnet_loss_grad), for `who`.  First their refusals, every one
 // before the first launch (out_need / ws_need: what the entry point's own _output_bytes / _workspace_bytes answer, safe for any shape) ...
 int criterion_check(const char* who, int n0, int n1, int B, const float* d_desc0, const float* d_desc1, const float* d_assign,
                     const void* h_pinned_out, int64_t pinned_bytes, int64_t out_need, const void* d_ws, int64_t ws_bytes, int64_t ws_need) {
@@ -220,6 +222,90 @@ extern "C" int linetr_desc_loss_grad(LinetrHandle* h, const float* d_desc0, int3
     LT_LAUNCH_CHECK();
   }
   LT_HIP(hipMemcpyAsync(h_pinned_out, scalars, (size_t)LG_OUT_BYTES, hipMemcpyDeviceToHost, st));
+  return LINETR_OK;
+}
+
+// =============================================================================================
+// the HardNet criterion, value and gradient (lt_hardnet.h)
+// =============================================================================================
+
+namespace {
+constexpr int64_t HN_OUT_BYTES = 40;   // f64 [3] loss, hardest_positive, hardest_negative | i64 [2] V, live anchors
+// workspace: device image of the result block | dots | norms (val_dot_kernel writes them) | per-line records
+struct HardnetWsLayout { int64_t o_out, o_dots, o_sq0, o_sq1, o_pos, o_neg, o_arg, o_min, o_cnt, o_live, o_share, total; };
+HardnetWsLayout hardnet_ws_layout(int B, int n) {
+  HardnetWsLayout L{};
+  const int64_t rows = align_up((int64_t)B * n * 4, 256);
+  Carve c;
+  L.o_out = c.take(HN_OUT_BYTES);
+  L.o_dots = c.take((int64_t)B * n * n * 4);
+  L.o_sq0 = c.take(rows);
+  L.o_sq1 = c.take(rows);
+  L.o_pos = c.take(2 * rows);
+  L.o_neg = c.take(2 * rows);
+  L.o_arg = c.take(2 * rows);
+  L.o_min = c.take(2 * rows);
+  L.o_cnt = c.take(2 * rows);
+  L.o_live = c.take(2 * rows);
+  L.o_share = c.take(2 * rows);
+  L.total = c.o + 256;
+  return L;
+}
+}  // namespace
+
+extern "C" int64_t linetr_hardnet_loss_grad_workspace_bytes(int32_t B, int32_t n) {
+  return val_dims_ok(B, n) ? hardnet_ws_layout(B, n).total : 0;
+}
+
+extern "C" int linetr_hardnet_loss_grad(LinetrHandle* h, const float* d_desc0, int32_t n0, const float* d_desc1, int32_t n1,
+                                        const float* d_assign, int32_t B, const float* d_upstream, float* d_grad0, float* d_grad1,
+                                        float* d_row_pos, float* d_row_neg, int32_t* d_row_arg, void* h_pinned_out, int64_t pinned_bytes,
+                                        void* d_ws, int64_t ws_bytes, void* stream) {
+  if (int e = criterion_check("hardnet_loss_grad", n0, n1, B, d_desc0, d_desc1, d_assign, h_pinned_out, pinned_bytes, HN_OUT_BYTES, d_ws,
+                              ws_bytes, linetr_hardnet_loss_grad_workspace_bytes(B, n0))) return e;
+  const int n = n0;
+  const HardnetWsLayout W = hardnet_ws_layout(B, n);
+  hipStream_t st = (hipStream_t)stream;
+  if (h) LT_HIP(hipSetDevice(h->device));
+  char* base = (char*)d_ws;
+  float* dots = (float*)(base + W.o_dots);
+  float* line_pos = d_row_pos ? d_row_pos : (float*)(base + W.o_pos);
+  float* row_neg = d_row_neg ? d_row_neg : (float*)(base + W.o_neg);
+  int* line_arg = d_row_arg ? d_row_arg : (int*)(base + W.o_arg);
+  float* line_min = (float*)(base + W.o_min);
+  int* line_cnt = (int*)(base + W.o_cnt);
+  int* live_arg = (int*)(base + W.o_live);
+  float* neg_share = (float*)(base + W.o_share);
+  double* scalars = (double*)(base + W.o_out);
+  long long* count = (long long*)(base + W.o_out + 24);
+  if (int e = criterion_dots(h, st, d_desc0, d_desc1, B, n, dots, (float*)(base + W.o_sq0), (float*)(base + W.o_sq1))) return e;
+  {
+    ProfScope ps(h, st, "hardnet_select", 0, 8.0 * B * n * n);
+    hipLaunchKernelGGL(hn_select_kernel, dim3(cdiv(n, VS_ROWS) + cdiv(n, VS_COLS), B), dim3(256), 0, st, (const float*)dots, d_assign, n,
+                       line_pos, line_arg, line_min, line_cnt);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "hardnet_resolve", 0, 40.0 * B * n);
+    hipLaunchKernelGGL(hn_resolve_kernel, dim3(cdiv(2 * n, 256), B), dim3(256), 0, st, (const float*)line_pos, (const int*)line_arg,
+                       (const float*)line_min, (const int*)line_cnt, n, row_neg, live_arg, neg_share);
+    LT_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps(h, st, "hardnet_loss", 0, 24.0 * B * n);
+    hipLaunchKernelGGL(hn_loss_kernel, dim3(1), dim3(256), 0, st, (const float*)line_pos, (const float*)row_neg, (const int*)line_arg, B, n,
+                       scalars, count);
+    LT_LAUNCH_CHECK();
+  }
+  if (d_grad0 || d_grad1) {
+    const int sides = (d_grad0 ? 1 : 0) + (d_grad1 ? 1 : 0);
+    ProfScope ps(h, st, "hardnet_grad", 0, sides * 4.0 * B * (2.0 * n * n + (double)n * D));
+    hipLaunchKernelGGL(hn_grad_kernel, dim3(cdiv(n, 64), 2, B), dim3(256), 0, st, d_desc0, d_desc1, (const float*)dots, d_assign, n,
+                       (const int*)live_arg, (const float*)line_min, (const float*)neg_share, (const long long*)count, d_upstream, d_grad0,
+                       d_grad1);
+    LT_LAUNCH_CHECK();
+  }
+  LT_HIP(hipMemcpyAsync(h_pinned_out, scalars, (size_t)HN_OUT_BYTES, hipMemcpyDeviceToHost, st));
   return LINETR_OK;
 }
 

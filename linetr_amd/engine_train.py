@@ -98,6 +98,42 @@ class _TrainSurface:
         return {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
                 "count": int(host[24:32].view(np.int64)[0]), "grad0": grad0, "grad1": grad1}
 
+    def hardnet_step(self, desc0, desc1, assign=None, lmatches=None, upstream=None, need_grad=True, rows=False):
+        """The reference's HardNet criterion (descriptor_loss.compute_distances_hardnet under its forward, evaluations/criteria.py:126-192)
+        and, with `need_grad`, its gradient with respect to both descriptor sets in one native call (linetr_hardnet_loss_grad): the
+        hardest positive of every anchor line against the hardest negative of that line and of its positive's line.  Inputs and
+        `upstream` as loss_step takes them.  One host wait.  Returns a dict: loss, hardest_positive, hardest_negative (float; NaN when
+        count == 0; hardest_negative may be 10000), count, live (the anchors with pos - neg + 1 > 0); with need_grad the device tensors
+        grad0 / grad1 in the shape of desc0 / desc1 (need_grad=False: the value-only call, the same scalars bit for bit, no gradient
+        kernel); with `rows` the device tensors row_pos, row_neg [B, 2n] float32 and row_arg [B, 2n] int32 (row_neg and row_arg -1
+        where the line is no anchor).  The engine's one cached workspace, as loss_step."""
+        d0, d1, B, n0, n1, assign = self._criterion_args("hardnet_step", desc0, desc1, assign, lmatches)
+        n = n0
+        if upstream is not None:
+            upstream = self._f32(upstream.detach().reshape(-1))
+            if upstream.numel() != 1:
+                raise ValueError("hardnet_step: upstream must hold one element")
+        ws = self._workspace("hardnet_step", max(int(self._L.linetr_hardnet_loss_grad_workspace_bytes(B, n)), 256))
+        stage, *gen = self._host_stage(40)
+        grad0, grad1 = (torch.empty_like(d0), torch.empty_like(d1)) if need_grad else (None, None)
+        row_pos = row_neg = row_arg = None
+        if rows:
+            row_pos, row_neg = (torch.empty((B, 2 * n), dtype=torch.float32, device=self.device) for _ in range(2))
+            row_arg = torch.empty((B, 2 * n), dtype=torch.int32, device=self.device)
+        self._call("linetr_hardnet_loss_grad", d0.data_ptr(), n0, d1.data_ptr(), n1, assign.data_ptr(), B, ptr(upstream), ptr(grad0),
+                   ptr(grad1), ptr(row_pos), ptr(row_neg), ptr(row_arg), stage.data_ptr(), stage.numel(), ws.data_ptr(), ws.numel())
+        self._await_stage("hardnet_step", self._event(), *gen)
+        host = stage.numpy()
+        scalars, counts = host[:24].view(np.float64), host[24:40].view(np.int64)
+        res = {"loss": float(scalars[0]), "hardest_positive": float(scalars[1]), "hardest_negative": float(scalars[2]),
+               "count": int(counts[0]), "live": int(counts[1])}
+        if need_grad:
+            res["grad0"], res["grad1"] = (g.view(B, n, D).transpose(1, 2) if d.dim() == 3 else g
+                                          for g, d in ((grad0, desc0), (grad1, desc1)))
+        if rows:
+            res.update(row_pos=row_pos, row_neg=row_neg, row_arg=row_arg)
+        return res
+
     # ------------------------------------------------------------------ backward of the 1x1 layers and the descriptor head
     def _act_rows(self, t: torch.Tensor, width: int, what: str, strided=True):
         """Activations as the point-wise layers read them: a float32 [rows, width] tensor whose rows are `stride(0)` floats apart

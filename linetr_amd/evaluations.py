@@ -1,9 +1,11 @@
-"""The reference's evaluation names on top of Engine.val_step (linetr_val_step, csrc/lt_valstep.h) and Engine.loss_step
-(linetr_desc_loss_grad, csrc/lt_lossgrad.h):
+"""The reference's evaluation names on top of Engine.val_step (linetr_val_step, csrc/lt_valstep.h), Engine.loss_step
+(linetr_desc_loss_grad, csrc/lt_lossgrad.h) and Engine.hardnet_step (linetr_hardnet_loss_grad, csrc/lt_hardnet.h):
 
     descriptor_loss      evaluations/criteria.py:35-192     differentiable with respect to line_desc0 / line_desc1: loss.backward()
                                                             reaches whatever torch graph produced them (the gradient of the
-                                                            criterion is native; no gradient is taken where none is asked for)
+                                                            criterion is native; no gradient is taken where none is asked for);
+                                                            mining="hardnet": compute_distances_hardnet (:126-171), the switch the
+                                                            reference keeps as a commented line of forward (:175-176)
     nn_matcher_batches   evaluations/matcher.py:51-102
     Evaluate_PR          evaluations/evaluate_pr.py:3-35
     Result, AverageMeter evaluations/metric.py:7-112        the interface train.py and its logger use; no save_matching_image
@@ -42,21 +44,27 @@ def _on_device(desc0, desc1):
     return desc0, desc1
 
 
-def _require_anchors(res):
-    if res["count"] == 0:     # the reference stacks an empty list (criteria.py:117)
-        raise RuntimeError("descriptor_loss: no anchor has a semi-hard negative (stack expects a non-empty TensorList)")
+def _require_anchors(res, mining="semi-hard"):
+    if res["count"] == 0:     # the reference stacks an empty list (criteria.py:117, :148)
+        what = "no anchor has a semi-hard negative" if mining == "semi-hard" else "no line has a positive"
+        raise RuntimeError(f"descriptor_loss: {what} (stack expects a non-empty TensorList)")
+
+
+MININGS = ("semi-hard", "hardnet")
 
 
 class _DescriptorLossGrad(torch.autograd.Function):
-    """(loss, hardest_positive, hardest_negative) = criterion(desc0, desc1): forward is Engine.loss_step, which also leaves
-    d loss / d desc for an upstream of 1; backward scales them by the gradient arriving at the loss (on the device: nothing is waited
-    for).  The two hardest values are not differentiable.  The gradients live in the graph only: `owner.last` gets the scalars."""
+    """(loss, hardest_positive, hardest_negative) = criterion(desc0, desc1): forward is Engine.loss_step (mining "semi-hard") or
+    Engine.hardnet_step (mining "hardnet"), which also leaves d loss / d desc for an upstream of 1; backward scales them by the gradient
+    arriving at the loss (on the device: nothing is waited for).  The two hardest values are not differentiable.  The gradients live in
+    the graph only: `owner.last` gets the scalars."""
 
     @staticmethod
-    def forward(ctx, desc0, desc1, assign, owner):
-        res = _engine(desc0.device).loss_step(desc0, desc1, assign=assign)
+    def forward(ctx, desc0, desc1, assign, owner, mining="semi-hard"):
+        eng = _engine(desc0.device)
+        res = eng.loss_step(desc0, desc1, assign=assign) if mining == "semi-hard" else eng.hardnet_step(desc0, desc1, assign=assign)
         owner.last = {k: res[k] for k in ("loss", "hardest_positive", "hardest_negative", "count")}
-        _require_anchors(res)
+        _require_anchors(res, mining)
         ctx.save_for_backward(res["grad0"], res["grad1"])
         loss, hp, hn = (torch.tensor(res[k], dtype=torch.float32, device=desc0.device) for k in ("loss", "hardest_positive", "hardest_negative"))
         ctx.mark_non_differentiable(hp, hn)
@@ -66,28 +74,36 @@ class _DescriptorLossGrad(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_hp, _grad_hn):
         grad0, grad1 = ctx.saved_tensors
         return (grad_loss * grad0 if ctx.needs_input_grad[0] else None, grad_loss * grad1 if ctx.needs_input_grad[1] else None,
-                None, None)
+                None, None, None)
 
 
 class descriptor_loss(torch.nn.Module):
     """forward(pred, target) -> (loss, hardest_positive, hardest_negative): 0-dim float32 tensors on the descriptors' device.
     pred: 'line_desc0', 'line_desc1' [B, 256, n]; target: 'mat_assign_sublines' [B, n+1, n+1].
     With grad enabled and a descriptor set that requires grad, `loss` carries a grad_fn (Engine.loss_step: value and gradient from one
-    selection); the two hardest values never do (the reference never differentiates them).  Otherwise nothing carries one."""
+    selection); the two hardest values never do (the reference never differentiates them).  Otherwise nothing carries one.
+    mining: "semi-hard" (the default: the reference's compute_distances) or "hardnet" (its compute_distances_hardnet, through
+    Engine.hardnet_step: with a gradient under autograd, the value-only call otherwise)."""
 
-    def __init__(self):
+    def __init__(self, mining="semi-hard"):
         super().__init__()
+        if mining not in MININGS:
+            raise ValueError(f"descriptor_loss: mining must be one of {MININGS}, got {mining!r}")
         self.margin = 0.5
+        self.mining = mining
 
     def forward(self, pred, target):
         desc0, desc1 = pred["line_desc0"], pred["line_desc1"]
         assign = target["mat_assign_sublines"]
         if torch.is_grad_enabled() and (desc0.requires_grad or desc1.requires_grad):
-            return _DescriptorLossGrad.apply(desc0, desc1, assign, self)
+            return _DescriptorLossGrad.apply(desc0, desc1, assign, self, self.mining)
         with torch.no_grad():
-            res = _engine(desc0.device).val_step(desc0, desc1, assign=assign)
+            if self.mining == "semi-hard":
+                res = _engine(desc0.device).val_step(desc0, desc1, assign=assign)
+            else:
+                res = _engine(desc0.device).hardnet_step(desc0, desc1, assign=assign, need_grad=False)
             self.last = res
-            _require_anchors(res)
+            _require_anchors(res, self.mining)
             return tuple(torch.tensor(res[k], dtype=torch.float32, device=desc0.device)
                          for k in ("loss", "hardest_positive", "hardest_negative"))
 
