@@ -182,7 +182,25 @@ int linetr_prefilter_batch(const double* h_lines6, const int32_t* h_line_off, in
                            int32_t n_threads, LinetrLineRec* h_recs, int32_t capacity, int32_t* h_cu_k,
                            int32_t* h_cu_n);
 
-/* Which images of the LAST linetr_prefilter / linetr_prefilter_batch call on the calling thread had two candidates of EQUAL
+/* One image's settings for linetr_prefilter_ragged: what linetr_prefilter_batch takes once for the whole batch. */
+typedef struct {
+  int32_t height, width;       /* the image's own size in pixels                                                  */
+  double min_length;           /* filter_by_length's bound for THIS image (auto_min_length: max(16, max(shape) / 40))   */
+  double token_distance;       /* > 0; auto_min_length: max(8, max(shape) / 80)                                    */
+  const double* valid_mask;    /* NULL, or this image's own [height][width] float64                                */
+} LinetrPrefilterImage;        /* 32 bytes */
+
+/* linetr_prefilter_batch for images of DIFFERENT sizes (the reference runs every image at its own size with --resize -1, and with
+ * auto_min_length recomputes min_length and token_distance from each image's shape, models/matching.py:29-32,45-48): h_images [B]
+ * gives every image its height, width, min_length, token_distance and valid mask; border, max_keylines, max_tokens, n_threads, the
+ * outputs and the worker pool are linetr_prefilter_batch's.  Both entry points run the same per-image code: a table of B equal
+ * entries gives linetr_prefilter_batch's bytes.
+ * LINETR_E_ARG as linetr_prefilter_batch, with every table entry checked before a line is read, and: a NULL table with B > 0. */
+int linetr_prefilter_ragged(const double* h_lines6, const int32_t* h_line_off, int32_t n_images,
+                            const LinetrPrefilterImage* h_images, int32_t border, int32_t max_keylines, int32_t max_tokens,
+                            int32_t n_threads, LinetrLineRec* h_recs, int32_t capacity, int32_t* h_cu_k, int32_t* h_cu_n);
+
+/* Which images of the LAST linetr_prefilter / linetr_prefilter_batch / linetr_prefilter_ragged call on the calling thread had two candidates of EQUAL
  * length in front of the length sort (models/line_process.py:15-16): there the reference's order -- np.argsort, an unstable,
  * CPU-dispatched sort -- is whatever NumPy does on the host, and a tie across the [:max_keylines] cut even changes the set.
  * Writes up to `capacity` image indices (ascending; 0 for linetr_prefilter) and returns their number.  A host that has NumPy
@@ -286,6 +304,37 @@ int linetr_describe(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int
                     int32_t width, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
                     int32_t* d_sub2line, float* d_line_desc, void* d_workspace, int64_t workspace_bytes,
                     void* stream);
+
+/* One image of a linetr_describe_ragged batch: its own maps, size and token distance.  The maps are separate allocations; nothing
+ * requires the caller to pack them. */
+typedef struct {
+  const float* d_dense_desc;   /* [256,height/8,width/8] (dense_is_nhwc = 0) or [height/8,width/8,256]; device memory */
+  const float* d_dense_score;  /* [height,width]; device memory                                                        */
+  int32_t height, width;       /* positive multiples of 8                                                              */
+  double token_distance;       /* > 0 (auto_min_length: max(8, max(shape) / 80) of THIS image)                         */
+} LinetrImage;                 /* 32 bytes */
+
+/* linetr_describe for a batch whose images differ in size (the reference has no size restriction: match_line_pairs.py --resize -1
+ * runs every image at its own size, and models/matching.py:29-32,45-48 recompute token_distance per image).  linetr_describe's
+ * arguments with (d_dense_desc, d_dense_score, height, width, token_distance) replaced by the HOST table h_images [n_images], which
+ * may be pageable and is not read after the call returns: the library builds its device-side table in the workspace.  The records
+ * come from linetr_prefilter_ragged (or linetr_pack_lines per image) with the same token distances; the end-point clip of image i is
+ * (width_i - 0.6, height_i - 0.6).  h_recs: the records on the host as well, or NULL -- with it, every record's `image` is checked
+ * against the table before anything is launched (the kernels index the table with it; d_recs alone cannot be checked without a
+ * device round trip).  NULL means NO check: a record of d_recs whose image is not in 0 .. n_images - 1 then makes the kernels read
+ * beyond the table, which is undefined behaviour -- pass NULL only for records whose images the caller vouches for.  All LinetrTokens outputs are supported, `mat` for up to 8 images as in linetr_describe.  Asynchronous on
+ * `stream`; no device allocation (the table travels through a pinned staging ring the library keeps).  Everything behind the CLS
+ * pooling is linetr_describe's own code: a table of equal entries gives its results bit for bit.
+ * LINETR_E_ARG before any launch: a NULL or empty table; a height or width that is not a positive multiple of 8; a NULL map; a
+ * channel-last map, out.desc or workspace that is not 16-byte aligned; a token_distance that is not > 0; a record of h_recs whose
+ * image lies outside the table; and what linetr_describe refuses.  LINETR_E_WORKSPACE: a workspace below the query's answer.
+ * linetr_describe_ragged_workspace_bytes returns -1 for a table the call would refuse. */
+int64_t linetr_describe_ragged_workspace_bytes(const LinetrHandle* h, const LinetrImage* h_images, int32_t n_images,
+                                               int32_t dense_is_nhwc, int32_t N, int64_t n_real_tokens);
+int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_recs, const LinetrLineRec* h_recs, int32_t K, int32_t N,
+                           int64_t n_real_tokens, const int32_t* h_cu_sub, const int32_t* d_cu_sub, const LinetrImage* h_images,
+                           int32_t n_images, int32_t max_tokens, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
+                           int32_t* d_sub2line, float* d_line_desc, void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* linetr_describe as a software pipeline over CONSECUTIVE batches ("batch/varlen plumbing + stream
  * pipelining"; the reference is serial per pair, models/matching.py:34-60).  A batch is cut into stages at fixed points of the network

@@ -41,6 +41,12 @@ class Tokens(C.Structure):
                                           "angle_sub", "desc", "score", "mat", "h_cu_klines")]
 
 
+# LinetrPrefilterImage / LinetrImage: one row of the HOST tables linetr_prefilter_ragged / linetr_describe_ragged take (pointers: 0 = NULL)
+PREFILTER_IMAGE_DTYPE = np.dtype([("height", "<i4"), ("width", "<i4"), ("min_length", "<f8"), ("token_distance", "<f8"), ("valid_mask", "<u8")])
+IMAGE_DTYPE = np.dtype([("d_dense_desc", "<u8"), ("d_dense_score", "<u8"), ("height", "<i4"), ("width", "<i4"), ("token_distance", "<f8")])
+assert PREFILTER_IMAGE_DTYPE.itemsize == IMAGE_DTYPE.itemsize == 32
+
+
 class GemmCase(C.Structure):
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int32), ("K1", C.c_int32),
                 ("W", C.c_void_p), ("bias", C.c_void_p), ("R", C.c_void_p), ("Y", C.c_void_p), ("ldy", C.c_int32),
@@ -132,6 +138,7 @@ ABI = {
     "linetr_destroy": (None, [vp]),
     "linetr_prefilter": (i32, [vp, i32, i32, i32, i32, f64, i32, vp, f64, i32, i32, i32, i32, vp, i32, _P(i32), _P(i32)]),
     "linetr_prefilter_batch": (i32, [vp, vp, i32, i32, i32, i32, f64, i32, vp, f64, i32, i32, vp, i32, vp, vp]),
+    "linetr_prefilter_ragged": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp]),
     "linetr_prefilter_tied_images": (i32, [vp, i32]),
     "linetr_pack_lines": (i32, [vp, vp, vp, i32, f64, i32, i32, i32, i32, vp, _P(i32)]),
     "linetr_tokenize_workspace_bytes": (i64, [i32, i32, i32, i32]),
@@ -145,6 +152,8 @@ ABI = {
     "linetr_forward_train": (i32, [vp, _P(Tokens), vp, vp, i32, i32, f32, vp, vp, vp, vp, i64, vp]),
     "linetr_describe_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i64]),
     "linetr_describe": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, i32, i32, i32, i32, Tokens, vp, vp, vp, i64, vp]),
+    "linetr_describe_ragged_workspace_bytes": (i64, [vp, vp, i32, i32, i32, i64]),
+    "linetr_describe_ragged": (i32, [vp, vp, vp, i32, i32, i64, vp, vp, vp, i32, i32, i32, i32, Tokens, vp, vp, vp, i64, vp]),
     "linetr_describe_submit": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, i32, i32, i32, i32, Tokens, vp, vp, vp, i64, i32,
                                      i32, vp]),
     "linetr_pipeline_max_slots": (i32, []),

@@ -477,17 +477,17 @@ extern "C" int linetr_prefilter(const double* L, int32_t K, int32_t height, int3
   return LINETR_OK;
 }
 
-extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32_t B, int32_t height, int32_t width,
-                                      int32_t border, double min_length, int32_t max_keylines,
-                                      const double* const* vms, double td, int32_t T, int32_t n_threads,
-                                      LinetrLineRec* h_recs, int32_t capacity, int32_t* cu_k, int32_t* cu_n) {
-  if (B < 0 || !off || !cu_k || !cu_n) return fail(LINETR_E_ARG, "null argument");
-  if (n_threads < 0) return fail(LINETR_E_ARG, "prefilter_batch: n_threads %d (0 = the library's default)", n_threads);
-  if (int e = check_prefilter_args(height, width, border, td, T, h_recs, capacity)) return e;
+// The per-image body of both batched entry points, written once: image i is filtered with the settings image_of(i) returns
+// (linetr_prefilter_batch: the same four scalars for every image; linetr_prefilter_ragged: the caller's table entry).  The callers
+// have checked every argument that does not depend on the lines.
+template <class ImageOf>
+static int prefilter_images(const char* who, const double* L, const int32_t* off, int32_t B, ImageOf image_of, int32_t border,
+                            int32_t max_keylines, int32_t T, int32_t n_threads, LinetrLineRec* h_recs, int32_t capacity,
+                            int32_t* cu_k, int32_t* cu_n) {
   // the offset table: starts at or above 0 and never decreases (image i owns rows off[i] .. off[i + 1])
-  if (off[0] < 0) return fail(LINETR_E_ARG, "prefilter_batch: line offset 0 is negative (%d)", off[0]);
+  if (off[0] < 0) return fail(LINETR_E_ARG, "%s: line offset 0 is negative (%d)", who, off[0]);
   for (int i = 0; i < B; ++i)
-    if (off[i + 1] < off[i]) return fail(LINETR_E_ARG, "prefilter_batch: line offset %d (%d) is below offset %d (%d)", i + 1, off[i + 1], i, off[i]);
+    if (off[i + 1] < off[i]) return fail(LINETR_E_ARG, "%s: line offset %d (%d) is below offset %d (%d)", who, i + 1, off[i + 1], i, off[i]);
   if (B > 0 && off[B] > off[0] && !L) return fail(LINETR_E_ARG, "null argument");
   WorkPool& pool = WorkPool::get();
   int nt = n_threads > 0 ? n_threads : pool.size();
@@ -503,15 +503,16 @@ extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32
     for (int i = 0; i < B; ++i) {
       int64_t n_sel = -1;
       bool tied = false;
-      prefilter_core(L + (size_t)off[i] * 6, off[i + 1] - off[i], height, width, border, min_length, max_keylines,
-                     vms ? vms[i] : nullptr, &tied, [&](int64_t n) -> LinetrLineRec* {
+      const LinetrPrefilterImage im = image_of(i);
+      prefilter_core(L + (size_t)off[i] * 6, off[i + 1] - off[i], im.height, im.width, border, im.min_length, max_keylines,
+                     im.valid_mask, &tied, [&](int64_t n) -> LinetrLineRec* {
                        n_sel = n;
                        return k + n <= capacity ? h_recs + k : nullptr;
                      });
       if (tied) g_tied_images.push_back(i);
-      if (k + n_sel > capacity) return fail(LINETR_E_CAPACITY, "prefilter_batch: more than %d surviving lines", capacity);
+      if (k + n_sel > capacity) return fail(LINETR_E_CAPACITY, "%s: more than %d surviving lines", who, capacity);
       for (int64_t j = 0; j < n_sel; ++j)
-        if (int e = pack_one(h_recs[k + j], td, T, i, (int)j, cur, tcur)) return e;
+        if (int e = pack_one(h_recs[k + j], im.token_distance, T, i, (int)j, cur, tcur)) return e;
       k += n_sel;
       cu_k[i + 1] = (int)k;
       cu_n[i + 1] = cur;
@@ -524,8 +525,9 @@ extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32
     const int i0 = (int)((int64_t)B * c / chunks), i1 = (int)((int64_t)B * (c + 1) / chunks);
     for (int i = i0; i < i1; ++i) {
       bool tied = false;
-      prefilter_core(L + (size_t)off[i] * 6, off[i + 1] - off[i], height, width, border, min_length, max_keylines,
-                     vms ? vms[i] : nullptr, &tied, [&](int64_t n) -> LinetrLineRec* {
+      const LinetrPrefilterImage im = image_of(i);
+      prefilter_core(L + (size_t)off[i] * 6, off[i + 1] - off[i], im.height, im.width, border, im.min_length, max_keylines,
+                     im.valid_mask, &tied, [&](int64_t n) -> LinetrLineRec* {
                        sel[i].resize(n);
                        return sel[i].data();
                      });
@@ -537,7 +539,8 @@ extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32
     if (tied_img[i]) g_tied_images.push_back(i);
   for (int i = 0; i < B; ++i) {
     if (k + (int64_t)sel[i].size() > capacity)
-      return fail(LINETR_E_CAPACITY, "prefilter_batch: more than %d surviving lines", capacity);
+      return fail(LINETR_E_CAPACITY, "%s: more than %d surviving lines", who, capacity);
+    const double td = image_of(i).token_distance;
     for (size_t j = 0; j < sel[i].size(); ++j) {
       if (int e = pack_one(sel[i][j], td, T, i, (int)j, cur, tcur)) return e;
       h_recs[k++] = sel[i][j];
@@ -546,6 +549,31 @@ extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32
     cu_n[i + 1] = cur;
   }
   return LINETR_OK;
+}
+
+extern "C" int linetr_prefilter_batch(const double* L, const int32_t* off, int32_t B, int32_t height, int32_t width,
+                                      int32_t border, double min_length, int32_t max_keylines,
+                                      const double* const* vms, double td, int32_t T, int32_t n_threads,
+                                      LinetrLineRec* h_recs, int32_t capacity, int32_t* cu_k, int32_t* cu_n) {
+  if (B < 0 || !off || !cu_k || !cu_n) return fail(LINETR_E_ARG, "null argument");
+  if (n_threads < 0) return fail(LINETR_E_ARG, "prefilter_batch: n_threads %d (0 = the library's default)", n_threads);
+  if (int e = check_prefilter_args(height, width, border, td, T, h_recs, capacity)) return e;
+  // the ragged call with a constant table
+  auto image_of = [&](int i) { return LinetrPrefilterImage{height, width, min_length, td, vms ? vms[i] : nullptr}; };
+  return prefilter_images("prefilter_batch", L, off, B, image_of, border, max_keylines, T, n_threads, h_recs, capacity, cu_k, cu_n);
+}
+
+extern "C" int linetr_prefilter_ragged(const double* L, const int32_t* off, int32_t B, const LinetrPrefilterImage* h_images,
+                                       int32_t border, int32_t max_keylines, int32_t T, int32_t n_threads, LinetrLineRec* h_recs,
+                                       int32_t capacity, int32_t* cu_k, int32_t* cu_n) {
+  if (B < 0 || !off || !cu_k || !cu_n || (B > 0 && !h_images)) return fail(LINETR_E_ARG, "null argument");
+  if (n_threads < 0) return fail(LINETR_E_ARG, "prefilter_ragged: n_threads %d (0 = the library's default)", n_threads);
+  // every image's settings, before a line is looked at (no image: what does not belong to one)
+  if (int e = check_prefilter_args(0, 0, border, 1.0, T, h_recs, capacity)) return e;
+  for (int i = 0; i < B; ++i)
+    if (int e = check_prefilter_args(h_images[i].height, h_images[i].width, border, h_images[i].token_distance, T, h_recs, capacity)) return e;
+  auto image_of = [&](int i) { return h_images[i]; };
+  return prefilter_images("prefilter_ragged", L, off, B, image_of, border, max_keylines, T, n_threads, h_recs, capacity, cu_k, cu_n);
 }
 
 extern "C" int32_t linetr_prefilter_tied_images(int32_t* h_images, int32_t capacity) {

@@ -16,48 +16,6 @@ using namespace lt;
 // =============================================================================================
 
 namespace {
-// Pinned staging ring for the small host tables the matcher uploads (PairDesc array, identity maps).  A slot is
-// reused only after the copy that read it has completed (event), so no entry point has to synchronise the stream.
-struct PinnedRing {
-  struct Slot { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
-  Slot slots[8];
-  int next = 0;
-  std::mutex m;
-  // returns a host pointer of >= bytes, or nullptr; *slot_out identifies the slot for commit()
-  void* acquire(size_t bytes, int* slot_out) {
-    std::lock_guard<std::mutex> lk(m);
-    Slot& s = slots[next];
-    *slot_out = next;
-    next = (next + 1) % 8;
-    if (s.busy) { (void)hipEventSynchronize(s.ev); s.busy = false; }
-    if (s.cap < bytes) {
-      if (s.p) (void)hipHostFree(s.p);
-      s.p = nullptr; s.cap = 0;
-      const size_t cap = std::max<size_t>(align_up((int64_t)bytes * 2, 4096), 16384);
-      if (hipHostMalloc(&s.p, cap, hipHostMallocDefault) != hipSuccess) { s.p = nullptr; return nullptr; }
-      s.cap = cap;
-    }
-    if (!s.ev && hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) { s.ev = nullptr; return nullptr; }
-    return s.p;
-  }
-  int commit(int slot, hipStream_t st) {   // call after the last async copy out of the slot has been enqueued
-    std::lock_guard<std::mutex> lk(m);
-    LT_HIP(hipEventRecord(slots[slot].ev, st));
-    slots[slot].busy = true;
-    return 0;
-  }
-};
-PinnedRing& staging_ring() {   // one ring per device (its events belong to the device current at creation); leaked: see WorkPool
-  static PinnedRing* rings[64] = {};
-  static std::mutex m;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(m);
-  PinnedRing*& r = rings[dev & 63];
-  if (!r) r = new PinnedRing();
-  return *r;
-}
-
 // Scratch of the one-launch single-pair matcher (pair_match_fused_kernel): column keys, row results, arrival counter.  One slot per
 // (device, stream): launches on a stream are ordered and the kernel leaves its slot clean, so a slot is never shared by two
 // launches in flight.  A slot is initialised (column and row keys all-ones, counter 0) by memsets queued on ITS stream in front of

@@ -280,29 +280,55 @@ struct TokenFront {
   double tokenize_bytes;               // what the `tokenize` profile class is charged
   // describe only: the compact list of real tokens, closed by one padding row per image (written by cdiv(n_pad_images, 64) more blocks)
   float *cpnt = nullptr, *cscore = nullptr; int n_pad_images = 0; int64_t first_pad = 0;
+  // ragged (linetr_describe_ragged): the image table in the workspace; the kernels take size, token distance, clip and maps from it and
+  // the nine uniform fields above are unused.  max_cells = the largest image's Hc * Wc, cells = their sum (the layout pass)
+  const RaggedImage* tab = nullptr; int max_cells = 0; double cells = 0;
 };
 int token_front(LinetrHandle* h, hipStream_t st, const TokenFront& a, const LinetrTokens& out, const K2sTable& k2s, int32_t* d_sub2line,
                 const float*& nhwc) {
   {
     ProfScope ps(h, st, "line_fill", 0, (double)a.K * 80 + (double)a.N * 8);
-    hipLaunchKernelGGL(line_fill_kernel, dim3(cdiv(a.K, 256)), dim3(256), 0, st, a.recs, a.K, a.clip_x, a.clip_y, out.klines, out.length,
-                       out.angles, a.s2l_g, d_sub2line);
+    if (a.tab)
+      hipLaunchKernelGGL(line_fill_ragged_kernel, dim3(cdiv(a.K, 256)), dim3(256), 0, st, a.recs, a.K, a.tab, out.klines, out.length,
+                         out.angles, a.s2l_g, d_sub2line);
+    else
+      hipLaunchKernelGGL(line_fill_kernel, dim3(cdiv(a.K, 256)), dim3(256), 0, st, a.recs, a.K, a.clip_x, a.clip_y, out.klines, out.length,
+                         out.angles, a.s2l_g, d_sub2line);
     LT_LAUNCH_CHECK();
   }
   {
     ProfScope ps(h, st, "tokenize", 0, a.tokenize_bytes);
     // (with out.mat: K more blocks write the rows of mat_klines2sublines in the same launch)
-    hipLaunchKernelGGL(tokenize_kernel, dim3(a.N + cdiv(a.n_pad_images, 64) + (out.mat ? a.K : 0)), dim3(64), 0, st, a.recs, a.s2l_g, a.N,
-                       a.td, a.T, a.height, a.width, a.clip_x, a.clip_y, a.dense_score, a.sublines, out.pnt, out.mask, a.resp, a.angle_sub,
-                       out.score, a.cpnt, a.cscore, a.n_pad_images, a.first_pad, out.mat, k2s);
+    const dim3 grid(a.N + cdiv(a.n_pad_images, 64) + (out.mat ? a.K : 0));
+    if (a.tab)
+      hipLaunchKernelGGL(tokenize_ragged_kernel, grid, dim3(64), 0, st, a.recs, a.s2l_g, a.N, a.T, a.tab, a.sublines, out.pnt, out.mask,
+                         a.resp, a.angle_sub, out.score, a.cpnt, a.cscore, a.n_pad_images, a.first_pad, out.mat, k2s);
+    else
+      hipLaunchKernelGGL(tokenize_kernel, grid, dim3(64), 0, st, a.recs, a.s2l_g, a.N,
+                         a.td, a.T, a.height, a.width, a.clip_x, a.clip_y, a.dense_score, a.sublines, out.pnt, out.mask, a.resp, a.angle_sub,
+                         out.score, a.cpnt, a.cscore, a.n_pad_images, a.first_pad, out.mat, k2s);
     LT_LAUNCH_CHECK();
   }
-  const int Hc = a.height / 8, Wc = a.width / 8;
+  const int64_t ntok = (int64_t)a.N * a.T;
   nhwc = nullptr;
+  if (a.tab) {   // every image's channel-last map is where its table entry says: the caller's own, or the copy this pass makes
+    if (!a.dense_is_nhwc) {
+      ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * a.cells * D * 4);
+      hipLaunchKernelGGL(nchw_to_nhwc_ragged_kernel, dim3(cdiv(a.max_cells, 64), D / 64, a.n_images), dim3(256), 0, st, a.tab, D);
+      LT_LAUNCH_CHECK();
+    }
+    if (out.desc) {
+      ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
+      hipLaunchKernelGGL(sample_desc_ragged_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, a.s2l_g, a.recs, ntok, a.T,
+                         a.tab, a.align_corners, out.desc);
+      LT_LAUNCH_CHECK();
+    }
+    return LINETR_OK;
+  }
+  const int Hc = a.height / 8, Wc = a.width / 8;
   if (a.map_always || out.desc)
     if (int e = nhwc_map(h, st, a.dense_desc, a.dense_is_nhwc, a.n_images, Hc * Wc, a.nhwc_buf, nhwc)) return e;
   if (out.desc) {   // the reference's dense [N, T, 256] tensor
-    const int64_t ntok = (int64_t)a.N * a.T;
     ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
     hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, a.s2l_g, a.recs, ntok, a.T, nhwc,
                        Hc, Wc, a.align_corners, out.desc);
@@ -496,6 +522,8 @@ struct TokenStage {            // how the token stage (word MLP + CLS pooling) i
   int64_t rows = 0;            // rows of the word-MLP GEMMs (N*T dense, n_real + n_images fused)
   int64_t first_pad = 0;
   int Hc = 0, Wc = 0, align_corners = 0;
+  // ragged fused path (linetr_describe_ragged): the image table instead of nhwc / Hc / Wc, and the cells of all its maps
+  const RaggedImage* tab = nullptr; double cells = 0;
   const BnTrain* bn = nullptr; // training-time forward (linetr_forward_train): BatchNorm on batch statistics, convolutions unfolded
   PipeStages* pipe = nullptr;  // pipelined call (linetr_describe_submit): where the launch sequence moves on to the next stream
 };
@@ -683,9 +711,16 @@ int cls_pool_launch(LinetrHandle* h, hipStream_t st, int kernel, const TokenStag
   const int64_t rows = ts.rows;
   if (kernel != POOLK_DENSE) {
     // algorithmic bytes: the dense map once (or the four taps of every token, whichever is less), one a4 row per token, the pooled rows out
-    const double tap_bytes = std::min((double)n_images * ts.Hc * ts.Wc * D * 4, (double)rows * D * 4 * 4);
+    const double map_cells = ts.tab ? ts.cells : (double)n_images * ts.Hc * ts.Wc;   // ragged: summed over the table
+    const double tap_bytes = std::min(map_cells * D * 4, (double)rows * D * 4 * 4);
     ProfScope ps(h, st, "cls_pool_online", 2.0 * rows * (2.0 * HEADS * D * 2), tap_bytes + (double)rows * D * 4 + (double)N * HEADS * POOLW * 4);
-    if (kernel == POOLK_SPLIT4)
+    if (ts.tab && kernel == POOLK_SPLIT4)
+      hipLaunchKernelGGL(cls_pool_online_ragged_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
+                         a4, ts.first_pad, N, T, ts.tab, ts.align_corners, h->pool, pooled, 0);
+    else if (ts.tab)
+      hipLaunchKernelGGL(cls_pool_online_ragged_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
+                         a4, ts.first_pad, N, T, ts.tab, ts.align_corners, h->pool, pooled, kernel == POOLK_ONLINE_REV ? 1 : 0);
+    else if (kernel == POOLK_SPLIT4)
       hipLaunchKernelGGL(cls_pool_online_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
                          a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, pooled, 0);
     else
@@ -997,6 +1032,34 @@ extern "C" int64_t linetr_describe_workspace_bytes(const LinetrHandle* h, int32_
 }
 
 namespace {
+// The launches of a describe call behind its argument checks: the token front `f` (its geometry set by the caller: one size for the
+// batch, or the image table), then the network.  `dw` / `fwd_base`: the workspace behind whatever the caller put in front of it.
+int describe_launch(LinetrHandle* h, hipStream_t st, TokenFront f, const DescWs& dw, char* fwd_base, const LinetrTokens& out,
+                    const K2sTable& k2s, int32_t* d_sub2line, float* d_line_desc, const int32_t* h_cu, const int32_t* d_cu, int64_t n_real,
+                    PipeStages* pipe) {
+  const int n_images = f.n_images, N = f.N;
+  const int64_t rows = n_real + n_images;
+  FwdWs w = fwd_layout(h, N, rows, n_images, fwd_base);
+  const int* cu_dev;
+  if (int e = cu_on_device(h_cu, d_cu, n_images, w, st, cu_dev)) return e;
+  f.sublines = out.sublines ? out.sublines : dw.sublines;
+  f.resp = out.resp ? out.resp : dw.resp;
+  f.angle_sub = out.angle_sub ? out.angle_sub : dw.angle_sub;
+  f.s2l_g = dw.s2l_g; f.nhwc_buf = dw.nhwc;
+  f.map_always = true;
+  f.tokenize_bytes = (double)n_real * 16;
+  f.cpnt = dw.cpnt; f.cscore = dw.cscore; f.n_pad_images = n_images; f.first_pad = n_real;
+  const float* nhwc_map;
+  if (int e = token_front(h, st, f, out, k2s, d_sub2line, nhwc_map)) return e;
+  TokenStage ts;
+  ts.cpnt = dw.cpnt; ts.cscore = dw.cscore; ts.nhwc = nhwc_map; ts.recs = f.recs; ts.sub2line_g = dw.s2l_g;
+  ts.rows = rows; ts.first_pad = n_real; ts.Hc = f.height / 8; ts.Wc = f.width / 8; ts.align_corners = f.align_corners;
+  ts.tab = f.tab; ts.cells = f.cells;
+  ts.pipe = pipe;
+  if (int e = pipe_boundary(pipe, CUT_TOKENS, st)) return e;
+  return forward_core(h, st, ts, f.sublines, f.resp, f.angle_sub, h_cu, cu_dev, n_images, N, f.T, d_line_desc, w);
+}
+
 // linetr_describe proper.  pipe != nullptr (linetr_describe_submit): the launch sequence moves from stream to stream at the plan's
 // cut points; `st` is the first stage's stream.
 int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, int64_t n_real,
@@ -1023,25 +1086,107 @@ int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32
   if (rows > INT32_MAX / 8) return fail(LINETR_E_ARG, "describe: batch too large");
   LT_HIP(hipSetDevice(h->device));
   DescWs dw = desc_layout(n_images, height, width, N, rows, (char*)d_ws);
-  FwdWs w = fwd_layout(h, N, rows, n_images, (char*)d_ws + dw.fwd_off);
-  const int* cu_dev;
-  if (int e = cu_on_device(h_cu, d_cu, n_images, w, st, cu_dev)) return e;
   TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, dense_is_nhwc,
-               (double)width - 0.6, (double)height - 0.6, out.sublines ? out.sublines : dw.sublines, out.resp ? out.resp : dw.resp,
-               out.angle_sub ? out.angle_sub : dw.angle_sub};
-  f.s2l_g = dw.s2l_g; f.nhwc_buf = dw.nhwc;
-  f.map_always = true;
-  f.tokenize_bytes = (double)n_real * 16;
-  f.cpnt = dw.cpnt; f.cscore = dw.cscore; f.n_pad_images = n_images; f.first_pad = n_real;
-  const float* nhwc_map;
-  if (int e = token_front(h, st, f, out, k2s, d_sub2line, nhwc_map)) return e;
-  TokenStage ts;
-  ts.cpnt = dw.cpnt; ts.cscore = dw.cscore; ts.nhwc = nhwc_map; ts.recs = d_recs; ts.sub2line_g = dw.s2l_g;
-  ts.rows = rows; ts.first_pad = n_real; ts.Hc = height / 8; ts.Wc = width / 8; ts.align_corners = align_corners;
-  ts.pipe = pipe;
-  if (int e = pipe_boundary(pipe, CUT_TOKENS, st)) return e;
-  return forward_core(h, st, ts, f.sublines, f.resp, f.angle_sub, h_cu, cu_dev, n_images, N, T, d_line_desc, w);
+               (double)width - 0.6, (double)height - 0.6};
+  return describe_launch(h, st, f, dw, (char*)d_ws + dw.fwd_off, out, k2s, d_sub2line, d_line_desc, h_cu, d_cu, n_real, pipe);
 }
+
+// Workspace of linetr_describe_ragged in front of linetr_describe's own segments: image table | channel-last copy of every NCHW-fed
+// map.  The ONE function that lays it out and the one that makes the table: the size query passes no table, the entry point the
+// host copy it uploads (`base`: where the workspace is on the device).
+struct RaggedFront { int64_t o_tab, total; int max_cells; double cells; };
+RaggedFront ragged_front(const LinetrImage* imgs, int n_images, int dense_is_nhwc, char* base, RaggedImage* tab) {
+  RaggedFront L{};
+  Carve c;
+  L.o_tab = c.take(sz_mul(n_images, sizeof(RaggedImage)));
+  for (int i = 0; i < n_images; ++i) {
+    const LinetrImage& im = imgs[i];
+    const int Hc = im.height / 8, Wc = im.width / 8;
+    const int64_t o_copy = dense_is_nhwc ? 0 : c.take(sz_mul(Hc, Wc, D * 4));
+    L.max_cells = std::max(L.max_cells, Hc * Wc);
+    L.cells += (double)Hc * Wc;
+    if (tab)
+      tab[i] = RaggedImage{dense_is_nhwc ? im.d_dense_desc : (const float*)(base + o_copy), im.d_dense_score,
+                           dense_is_nhwc ? nullptr : im.d_dense_desc, im.height, im.width, Hc, Wc, im.token_distance,
+                           (double)im.width - 0.6, (double)im.height - 0.6};
+  }
+  L.total = c.o;
+  return L;
+}
+// what the table must be like for ragged_front's arithmetic to mean anything (the query answers 0 otherwise, the entry point refuses)
+int check_images(const LinetrImage* imgs, int n_images, int dense_is_nhwc) {
+  if (!imgs || n_images < 1) return fail(LINETR_E_ARG, "describe_ragged: a NULL or empty image table");
+  for (int i = 0; i < n_images; ++i) {
+    const LinetrImage& im = imgs[i];
+    if (im.height <= 0 || im.width <= 0 || im.height % 8 || im.width % 8)
+      return fail(LINETR_E_ARG, "describe_ragged: image %d is %d x %d, not a positive multiple of 8 each way", i, im.height, im.width);
+    if ((int64_t)(im.height / 8) * (im.width / 8) > INT32_MAX / D) return fail(LINETR_E_ARG, "describe_ragged: image %d is too large", i);
+    if (!im.d_dense_desc || !im.d_dense_score) return fail(LINETR_E_ARG, "describe_ragged: image %d has a NULL map", i);
+    if (dense_is_nhwc && !aligned16(im.d_dense_desc))
+      return fail(LINETR_E_ARG, "describe_ragged: the channel-last descriptor map of image %d is not 16-byte aligned", i);
+    if (!(im.token_distance > 0)) return fail(LINETR_E_ARG, "describe_ragged: image %d: token_distance must be > 0", i);
+  }
+  return 0;
+}
+}  // namespace
+
+// the whole workspace of a checked table, saturating (SZ_LIMIT: a shape no call serves): what the query answers and the call compares
+static int64_t describe_ragged_total(const LinetrHandle* h, const LinetrImage* h_images, int n_images, int dense_is_nhwc, int N, int64_t n_real) {
+  const int64_t rows = n_real + n_images;
+  return sz_add(ragged_front(h_images, n_images, dense_is_nhwc, nullptr, nullptr).total,
+                desc_layout(0, 0, 0, std::max(N, 1), rows, nullptr).total, fwd_layout(h, std::max(N, 1), rows, n_images, nullptr).total);
+}
+
+extern "C" int64_t linetr_describe_ragged_workspace_bytes(const LinetrHandle* h, const LinetrImage* h_images, int32_t n_images,
+                                                          int32_t dense_is_nhwc, int32_t N, int64_t n_real) {
+  if (!h || check_images(h_images, n_images, dense_is_nhwc)) return -1;
+  return sz_answer(describe_ragged_total(h, h_images, n_images, dense_is_nhwc, N, n_real));
+}
+
+extern "C" int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_recs, const LinetrLineRec* h_recs, int32_t K, int32_t N,
+                                      int64_t n_real, const int32_t* h_cu, const int32_t* d_cu, const LinetrImage* h_images,
+                                      int32_t n_images, int32_t T, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
+                                      int32_t* d_sub2line, float* d_line_desc, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!h) return fail(LINETR_E_ARG, "describe_ragged: null handle");
+  if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "describe_ragged: a training-mode handle (bn_batch_stats = 1) runs linetr_forward_train only");
+  if (int e = check_cu(h_cu, n_images)) return e;
+  if (h_cu[n_images] != N) return fail(LINETR_E_ARG, "describe_ragged: cu_sub does not end at N");
+  if (int e = check_images(h_images, n_images, dense_is_nhwc)) return e;
+  if (K <= 0 || N <= 0) return LINETR_OK;
+  if (!d_recs || !d_line_desc || !d_ws) return fail(LINETR_E_ARG, "describe_ragged: null pointer");
+  if (T < 1 || T > 4096) return fail(LINETR_E_ARG, "describe_ragged: bad max_tokens");
+  if (n_real < N || n_real > (int64_t)N * T) return fail(LINETR_E_ARG, "describe_ragged: implausible real-token count");
+  if (out.desc && !out.pnt) return fail(LINETR_E_ARG, "describe_ragged: out.desc requires out.pnt");
+  if (!aligned16(out.desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "describe_ragged: out.desc and the workspace must be 16-byte aligned");
+  // the kernels index the table with the records' image: with the host copy of the records at hand, every one is looked at first
+  for (int k = 0; h_recs && k < K; ++k)
+    if (h_recs[k].image < 0 || h_recs[k].image >= n_images)
+      return fail(LINETR_E_ARG, "describe_ragged: record %d belongs to image %d, outside the table of %d", k, h_recs[k].image, n_images);
+  K2sTable k2s;
+  if (int e = k2s_table(out, n_images, K, N, h_cu, k2s, "describe_ragged")) return e;
+  if (ws_bytes < describe_ragged_total(h, h_images, n_images, dense_is_nhwc, N, n_real))   // (a saturated total refuses every workspace)
+    return fail(LINETR_E_WORKSPACE, "describe_ragged: workspace too small");
+  const int64_t rows = n_real + n_images;
+  if (rows > INT32_MAX / 8) return fail(LINETR_E_ARG, "describe_ragged: batch too large");
+  LT_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the image table: made in a pinned staging slot (the caller's array is not read after this call), one asynchronous copy
+  int slot = -1;
+  RaggedImage* tab = (RaggedImage*)staging_ring().acquire((size_t)n_images * sizeof(RaggedImage), &slot);
+  if (!tab) return fail(LINETR_E_HIP, "describe_ragged: pinned staging allocation failed");
+  const RaggedFront rf = ragged_front(h_images, n_images, dense_is_nhwc, (char*)d_ws, tab);
+  RaggedImage* d_tab = (RaggedImage*)((char*)d_ws + rf.o_tab);
+  LT_HIP(hipMemcpyAsync(d_tab, tab, (size_t)n_images * sizeof(RaggedImage), hipMemcpyHostToDevice, st));
+  if (int e = staging_ring().commit(slot, st)) return e;
+  char* rest = (char*)d_ws + rf.total;
+  DescWs dw = desc_layout(0, 0, 0, N, rows, rest);
+  TokenFront f{d_recs, K, N, 0.0, T, nullptr, nullptr, n_images, 0, 0, align_corners, dense_is_nhwc, 0.0, 0.0};
+  f.tab = d_tab; f.max_cells = rf.max_cells; f.cells = rf.cells;
+  return describe_launch(h, st, f, dw, rest + dw.fwd_off, out, k2s, d_sub2line, d_line_desc, h_cu, d_cu, n_real, nullptr);
+}
+
+namespace {
 
 // the streams and events of the describe pipeline, made at the first submit: all or nothing
 int pipe_ready(LinetrHandle* h) {

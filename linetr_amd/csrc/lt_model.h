@@ -330,162 +330,28 @@ __global__ __launch_bounds__(256) void cls_pool_kernel(const float* __restrict__
 // SPLIT = 4 (a few hundred sub-lines: a single pair): the block's four waves share ONE sub-line, wave w taking tokens w, w + 4, ..;
 // the four partial (max, sum, pooled sums) states are merged through LDS, wave h finishing head h.  The dependent chain per wave is a
 // quarter as long (21 tokens -> 6): 24 -> 10 us at cfg2.
-template <int SPLIT>
-__global__ __launch_bounds__(256, 3) void cls_pool_online_kernel(   // 3 = waves per SIMD the register allocation must allow
-    const LinetrLineRec* __restrict__ recs, const int* __restrict__ sub2line_g, const float* __restrict__ cpnt,
-    const float* __restrict__ a4, int64_t first_pad, int N, int T, const float* __restrict__ nhwc, int Hc, int Wc,
-    int align_corners, ClsPoolConst cc, float* __restrict__ pooled /*[N][4][544]*/, int reverse) {
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  // reverse: the LAST sub-lines first -- their a4 rows are the ones the token MLP wrote most recently and are still in the
-  // Infinity Cache (a4 of a cfg3 batch is 298 MB, the cache 256 MB: walking forward finds none of it)
-  const int n_fwd = SPLIT == 1 ? blockIdx.x * 4 + wv : blockIdx.x;
-  if (n_fwd >= N) return;
-  const int n = reverse ? N - 1 - n_fwd : n_fwd;
-  const LinetrLineRec r = recs[sub2line_g[n]];
-  const int j = n - r.first_sub;
-  const int n_valid = min(T, r.n_tok - j * T);
-  const int n_pad = T - n_valid;
-  const int ntk = n_valid + (n_pad > 0 ? 1 : 0);
-  const int64_t tok0 = (int64_t)r.first_tok + (int64_t)j * T;
-  const int64_t padrow = first_pad + r.image;
-  const float* nhwc_img = nhwc + (int64_t)r.image * Hc * Wc * D;
-  f32x4 u[4], u2[4];
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    u[h] = *reinterpret_cast<const f32x4*>(cc.U + h * D + lane * 4);
-    u2[h] = *reinterpret_cast<const f32x4*>(cc.U2 + h * D + lane * 4);
-  }
-  // running state per head: max m, sum l, weight of the CLS key w0, pooled sums (this lane's 4 channels)
-  float m[4], l[4], w0[4];
-  f32x4 db[4], ab[4];
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    m[h] = cc.s_cls[h] * LOG2E; l[h] = 1.f; w0[h] = 1.f;
-    if (SPLIT > 1 && wv != 0) { m[h] = -INFINITY; l[h] = 0.f; w0[h] = 0.f; }   // the CLS key belongs to wave 0's share
-    db[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-    ab[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  auto row_of = [&](int jj) -> int64_t { return jj < n_valid ? tok0 + jj : padrow; };
-  // The tap geometry of a token is wave-uniform and costs ~150 VALU instructions (two divisions, floor, clamps):
-  // lane i computes it once for token chunk + i, and the loop below fetches a token's 4 offsets + 4 weights with
-  // 8 v_readlane instead of recomputing them in all 64 lanes.
-  int t_off[4];
-  float t_w[4];
-  auto fill_taps = [&](int chunk) {
-    const int jj = chunk + lane;
-    const int64_t row = row_of(jj < ntk ? jj : ntk - 1);
-    tap_coords(cpnt[row * 2], cpnt[row * 2 + 1], Hc, Wc, align_corners, t_off, t_w);
-  };
-  auto issue = [&](int jj, TapSet& t, f32x4& a) {
-    int off[4];
-    float wt[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      off[k] = __builtin_amdgcn_readlane(t_off[k], jj & 63);
-      wt[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t_w[k]), jj & 63));
-    }
-    taps_load(nhwc_img, off, wt, lane, t);
-    a = *reinterpret_cast<const f32x4*>(a4 + row_of(jj) * D + lane * 4);
-  };
-  TapSet cur, nxt;
-  f32x4 a_cur, a_nxt;
-  const int jj0 = SPLIT == 1 ? 0 : wv;
-  fill_taps(0);
-  if (jj0 < ntk) issue(jj0, cur, a_cur);
-  for (int jj = jj0; jj < ntk; jj += SPLIT) {
-    if (jj + SPLIT < ntk) {  // wave-uniform
-      if (((jj + SPLIT) >> 6) != (jj >> 6)) fill_taps((jj + SPLIT) & ~63);
-      issue(jj + SPLIT, nxt, a_nxt);
-    }
-    const f32x4 dv = taps_finish<true>(cur);
-    const float mult = jj < n_valid ? 1.f : (float)n_pad;
-    float sc[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      float p = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) p += dv[c] * u[h][c] + a_cur[c] * u2[h][c];
-      sc[h] = p;
-    }
-    wave_sum_n<4>(sc);                      // the four head scores reduce together
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      // running softmax in the log2 domain: one v_exp_f32 per exponential (m / l / w0 are only ever used as ratios)
-      const float sh = (sc[h] + cc.c_tok[h]) * LOG2E;
-      if (__any(sh > m[h])) {   // wave-uniform (sh and m are): the running maximum moves on few tokens only
-        const float alpha = __builtin_amdgcn_exp2f(m[h] - sh);
-        m[h] = sh;
-        l[h] *= alpha;
-        w0[h] *= alpha;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { db[h][c] *= alpha; ab[h][c] *= alpha; }
-      }
-      const float e = __builtin_amdgcn_exp2f(sh - m[h]) * mult;
-      l[h] += e;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        db[h][c] += e * dv[c];
-        ab[h][c] += e * a_cur[c];
-      }
-    }
-    cur = nxt;
-    a_cur = a_nxt;
-  }
-  float* out = pooled + (int64_t)n * 4 * POOLW;
-  if constexpr (SPLIT > 1) {
-    // merge the four waves' states: wave h finishes head h
-    __shared__ float st_ml[4][4][4];                        // [wave][head][m, l, w0, -]
-    __shared__ f32x4 st_v[4][4][2][64];                     // [wave][head][d / a][lane]
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      if (lane == 0) { st_ml[wv][h][0] = m[h]; st_ml[wv][h][1] = l[h]; st_ml[wv][h][2] = w0[h]; }
-      st_v[wv][h][0][lane] = db[h];
-      st_v[wv][h][1][lane] = ab[h];
-    }
-    __syncthreads();
-    const int h = wv;
-    float M = st_ml[0][h][0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) M = fmaxf(M, st_ml[w][h][0]);
-    float L = 0.f, W0 = 0.f;
-    f32x4 d = {0.f, 0.f, 0.f, 0.f}, a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float sc = __builtin_amdgcn_exp2f(st_ml[w][h][0] - M);     // a wave without tokens has m = -inf: weight 0
-      L += st_ml[w][h][1] * sc;
-      W0 += st_ml[w][h][2] * sc;
-      const f32x4 dv = st_v[w][h][0][lane], av = st_v[w][h][1][lane];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { d[c] += dv[c] * sc; a[c] += av[c] * sc; }
-    }
-    const float inv = 1.f / L;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { d[c] *= inv; a[c] *= inv; }
-    *reinterpret_cast<f32x4*>(out + h * POOLW + lane * 4) = d;
-    *reinterpret_cast<f32x4*>(out + h * POOLW + 256 + lane * 4) = a;
-    if (lane < 8) {  // [p_h0, 0 x 31]
-      f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      if (lane == 0) z[0] = W0 * inv;
-      *reinterpret_cast<f32x4*>(out + h * POOLW + 512 + lane * 4) = z;
-    }
-    return;
-  }
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    const float inv = 1.f / l[h];
-    f32x4 d = db[h], a = ab[h];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { d[c] *= inv; a[c] *= inv; }
-    *reinterpret_cast<f32x4*>(out + h * POOLW + lane * 4) = d;
-    *reinterpret_cast<f32x4*>(out + h * POOLW + 256 + lane * 4) = a;
-    if (lane < 8) {  // [p_h0, 0 x 31]
-      f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      if (lane == 0) z[0] = w0[h] * inv;
-      *reinterpret_cast<f32x4*>(out + h * POOLW + 512 + lane * 4) = z;
-    }
-  }
-}
+// The kernel's text is lt_cls_pool_online_body.h, included once per geometry.  All images of one size: their channel-last maps lie back to
+// back, image i at i * Hc * Wc * 256 floats.
+#define LT_POOL_KERNEL cls_pool_online_kernel
+#define LT_POOL_MAP_PARAMS const float* __restrict__ nhwc, int Hc, int Wc
+#define LT_POOL_MAP(image) const float* nhwc_img = nhwc + (int64_t)image * Hc * Wc * D;
+#include "lt_cls_pool_online_body.h"
+#undef LT_POOL_KERNEL
+#undef LT_POOL_MAP_PARAMS
+#undef LT_POOL_MAP
+
+// ragged (linetr_describe_ragged): the sub-line's image has its own map and size in the image table.  The entry is wave-uniform (a wave
+// works on one sub-line): it is loaded once per wave, through the scalar unit.
+#define LT_POOL_KERNEL cls_pool_online_ragged_kernel
+#define LT_POOL_MAP_PARAMS const RaggedImage* __restrict__ tab
+#define LT_POOL_MAP(image)                                                  \
+  const RaggedImage& im_ = tab[__builtin_amdgcn_readfirstlane(image)];      \
+  const float* nhwc_img = im_.nhwc;                                         \
+  const int Hc = im_.Hc, Wc = im_.Wc;
+#include "lt_cls_pool_online_body.h"
+#undef LT_POOL_KERNEL
+#undef LT_POOL_MAP_PARAMS
+#undef LT_POOL_MAP
 
 // ---------------------------------------------------------------------------------------------
 // Row kernels over [rows][256]; one wave64 per row, lane = 4 channels.

@@ -6,20 +6,28 @@
 
 namespace lt {
 
+// One image of a ragged batch (linetr_describe_ragged: every image at its own size): what the kernels of the front of the pipeline read
+// from their arguments when all images have one size.  The table is built on the host and lives in the call's workspace.
+struct RaggedImage {
+  const float* nhwc;    // the image's channel-last descriptor map: the caller's own, or its copy in the workspace
+  const float* score;   // its score map [height][width]
+  const float* nchw;    // the caller's [256][Hc][Wc] map the layout pass reads (NULL: the feed is channel-last)
+  int height, width, Hc, Wc;
+  double td;            // token_distance
+  double clip_x, clip_y;   // end-point clip (width - 0.6, height - 0.6)
+};                      // 64 bytes
+static_assert(sizeof(RaggedImage) == 64, "RaggedImage is copied as 64-byte entries");
+
 // ---------------------------------------------------------------------------------------------
 // NCHW -> NHWC copy of the dense descriptor map so that each bilinear tap is one coalesced 1 KiB
 // row (SuperPoint emits [1,256,H/8,W/8], models/superpoint.py:193).  32x32 LDS-tiled transpose.
 // grid (P/64 ceil, C/64, B), block 256
 // ---------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                           int C, int P) {
+// one block's 64 channels x 64 positions of ONE image: src [C][P] -> dst [P][C]
+__device__ __forceinline__ void nchw_to_nhwc_tile(const float* src, float* dst, int C, int P, int p0, int c0) {
   // 64 channels x 64 positions per block, dwordx4 on both sides: reads 16 B along p (NCHW rows), writes 16 B along c
   // (NHWC rows).  LDS tile [64 c][64 p + 1]: the odd stride keeps the 4-way column gather conflict-free.
   __shared__ float tile[64][65];
-  const int b = blockIdx.z;
-  const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  const float* src = in + (int64_t)b * C * P;
-  float* dst = out + (int64_t)b * C * P;
   const int tid = threadIdx.x;
   {
     const int pq = (tid & 15) * 4;          // 16 threads cover 64 positions
@@ -53,6 +61,21 @@ static __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* _
   }
 }
 
+static __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                           int C, int P) {
+  const int b = blockIdx.z;
+  nchw_to_nhwc_tile(in + (int64_t)b * C * P, out + (int64_t)b * C * P, C, P, blockIdx.x * 64, blockIdx.y * 64);
+}
+
+// ragged: image blockIdx.z has its own P = Hc * Wc (an odd P leaves every other row off the 16-byte grid: the aligned and the
+// unaligned load are chosen row by row, as above); grid.x covers the largest image, the blocks past a smaller one leave
+static __global__ __launch_bounds__(256) void nchw_to_nhwc_ragged_kernel(const RaggedImage* __restrict__ tab, int C) {
+  const RaggedImage im = tab[blockIdx.z];
+  const int P = im.Hc * im.Wc, p0 = blockIdx.x * 64;
+  if (p0 >= P) return;
+  nchw_to_nhwc_tile(im.nchw, const_cast<float*>(im.nhwc), C, P, p0, blockIdx.y * 64);
+}
+
 // ---------------------------------------------------------------------------------------------
 // per key-line: float32 copies of klines/length/angles (models/line_process.py:182-184, with the
 // end-point clip of :114-116 already applied) and the sub-line -> key-line maps.
@@ -69,6 +92,15 @@ __device__ __forceinline__ void kline_row(const LinetrLineRec& r, double wclip, 
   angle[1] = (float)r.angle[1];
 }
 
+__device__ __forceinline__ void line_fill_one(const LinetrLineRec& r, int k, double wclip, double hclip, float* klines, float* length,
+                                              float* angles, int* sub2line_g, int* sub2line_l) {
+  if (klines) kline_row(r, wclip, hclip, klines + k * 4, length + k, angles + k * 2);
+  for (int s = 0; s < r.n_sub; ++s) {
+    sub2line_g[r.first_sub + s] = k;
+    if (sub2line_l) sub2line_l[r.first_sub + s] = r.line_local;
+  }
+}
+
 static __global__ void line_fill_kernel(const LinetrLineRec* __restrict__ recs, int K, double wclip, double hclip,
                                  float* __restrict__ klines, float* __restrict__ length,
                                  float* __restrict__ angles, int* __restrict__ sub2line_g,
@@ -76,11 +108,17 @@ static __global__ void line_fill_kernel(const LinetrLineRec* __restrict__ recs, 
   int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
   const LinetrLineRec r = recs[k];
-  if (klines) kline_row(r, wclip, hclip, klines + k * 4, length + k, angles + k * 2);
-  for (int s = 0; s < r.n_sub; ++s) {
-    sub2line_g[r.first_sub + s] = k;
-    if (sub2line_l) sub2line_l[r.first_sub + s] = r.line_local;
-  }
+  line_fill_one(r, k, wclip, hclip, klines, length, angles, sub2line_g, sub2line_l);
+}
+
+// ragged: the end-point clip is the key-line's own image's
+static __global__ void line_fill_ragged_kernel(const LinetrLineRec* __restrict__ recs, int K, const RaggedImage* __restrict__ tab,
+                                        float* __restrict__ klines, float* __restrict__ length, float* __restrict__ angles,
+                                        int* __restrict__ sub2line_g, int* __restrict__ sub2line_l) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const LinetrLineRec r = recs[k];
+  line_fill_one(r, k, tab[r.image].clip_x, tab[r.image].clip_y, klines, length, angles, sub2line_g, sub2line_l);
 }
 
 // mat_klines2sublines of a small batch: where every image's [K_i][N_i] block starts (floats), its row length and the batch-wide index
@@ -171,6 +209,34 @@ __device__ __forceinline__ void tokenize_subline(
   }
 }
 
+// The tokeniser's blocks past the sub-lines (block `x` of them), written once for both kernels below; score_of(i) = image i's score map.
+template <class ScoreOf>
+__device__ __forceinline__ void tokenize_extra_block(int x, const LinetrLineRec* recs, float* cpnt, float* cscore, int n_pad_images,
+                                                     int64_t first_pad, ScoreOf score_of, float* mat_k2s, const K2sTable& k2s) {
+  const int pad_blocks = (n_pad_images + 63) / 64;
+  if (x < pad_blocks) {
+    // one shared padding token per image for the compact token list -- coordinate (0, 0), score
+    // dense_score[img][0][0] (the reference pads with zeros and gathers the score at the rounded coordinate, line_process.py:174-179)
+    const int i = x * 64 + threadIdx.x;
+    if (i < n_pad_images) {
+      cpnt[(first_pad + i) * 2 + 0] = 0.f;
+      cpnt[(first_pad + i) * 2 + 1] = 0.f;
+      cscore[first_pad + i] = *score_of(i);
+    }
+    return;
+  }
+  // one more block per key-line (calls of up to K2S_MAX_IMAGES images): its row of the image's mat_klines2sublines [K_i][N_i],
+  // 1 / num_sublines over the key-line's own sub-lines and 0 elsewhere (line_process.py:160-165; Python's 1/num is a float64
+  // quotient stored as float32)
+  const int k = x - pad_blocks;
+  const LinetrLineRec r = recs[k];
+  const K2sImage im = k2s.img[r.image & (K2S_MAX_IMAGES - 1)];
+  float* row = mat_k2s + im.off + (int64_t)r.line_local * im.n_sub;
+  const float w = k2s_weight(r);
+  const int j0 = r.first_sub - im.sub_base;
+  for (int j = threadIdx.x; j < im.n_sub; j += 64) row[j] = (j >= j0 && j < j0 + r.n_sub) ? w : 0.f;
+}
+
 // ---------------------------------------------------------------------------------------------
 // One 64-thread block per sub-line; thread t < T produces token t.
 // ---------------------------------------------------------------------------------------------
@@ -182,34 +248,33 @@ static __global__ __launch_bounds__(64) void tokenize_kernel(
     float* __restrict__ cscore, int n_pad_images, int64_t first_pad, float* __restrict__ mat_k2s, const K2sTable k2s) {
 #pragma clang fp contract(off)
   const int n = blockIdx.x;
-  if (n >= N) {
-    const int pad_blocks = (n_pad_images + 63) / 64;
-    if (n - N < pad_blocks) {
-      // blocks past the sub-lines: one shared padding token per image for the compact token list -- coordinate (0, 0), score
-      // dense_score[img][0][0] (the reference pads with zeros and gathers the score at the rounded coordinate, line_process.py:174-179)
-      const int i = (n - N) * 64 + threadIdx.x;
-      if (i < n_pad_images) {
-        cpnt[(first_pad + i) * 2 + 0] = 0.f;
-        cpnt[(first_pad + i) * 2 + 1] = 0.f;
-        cscore[first_pad + i] = dense_score[(int64_t)i * height * width];
-      }
-      return;
-    }
-    // one more block per key-line (calls of up to K2S_MAX_IMAGES images): its row of the image's mat_klines2sublines [K_i][N_i],
-    // 1 / num_sublines over the key-line's own sub-lines and 0 elsewhere (line_process.py:160-165; Python's 1/num is a float64
-    // quotient stored as float32)
-    const int k = n - N - pad_blocks;
-    const LinetrLineRec r = recs[k];
-    const K2sImage im = k2s.img[r.image & (K2S_MAX_IMAGES - 1)];
-    float* row = mat_k2s + im.off + (int64_t)r.line_local * im.n_sub;
-    const float w = k2s_weight(r);
-    const int j0 = r.first_sub - im.sub_base;
-    for (int j = threadIdx.x; j < im.n_sub; j += 64) row[j] = (j >= j0 && j < j0 + r.n_sub) ? w : 0.f;
+  if (n >= N) {   // blocks past the sub-lines: the images' padding tokens, then (out.mat) the rows of mat_klines2sublines
+    tokenize_extra_block(n - N, recs, cpnt, cscore, n_pad_images, first_pad,
+                         [&](int i) { return dense_score + (int64_t)i * height * width; }, mat_k2s, k2s);
     return;
   }
   const LinetrLineRec r = recs[sub2line_g[n]];
   tokenize_subline(r, n - r.first_sub, n, td, T, height, width, clip_x, clip_y, dense_score, sublines, pnt, mask, resp, angle_sub, score,
                    cpnt, cscore);
+}
+
+// ragged: size, token distance, clip and score map come from the key-line's own table entry
+static __global__ __launch_bounds__(64) void tokenize_ragged_kernel(
+    const LinetrLineRec* __restrict__ recs, const int* __restrict__ sub2line_g, int N, int T, const RaggedImage* __restrict__ tab,
+    float* __restrict__ sublines, float* __restrict__ pnt, float* __restrict__ mask, float* __restrict__ resp,
+    float* __restrict__ angle_sub, float* __restrict__ score, float* __restrict__ cpnt, float* __restrict__ cscore, int n_pad_images,
+    int64_t first_pad, float* __restrict__ mat_k2s, const K2sTable k2s) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x;
+  if (n >= N) {
+    tokenize_extra_block(n - N, recs, cpnt, cscore, n_pad_images, first_pad, [&](int i) { return tab[i].score; }, mat_k2s, k2s);
+    return;
+  }
+  LinetrLineRec r = recs[sub2line_g[n]];
+  const RaggedImage im = tab[r.image];
+  r.image = 0;   // im.score is the map of this image alone: image 0 of a batch of one (nothing else below reads the field)
+  tokenize_subline(r, n - r.first_sub, n, im.td, T, im.height, im.width, im.clip_x, im.clip_y, im.score, sublines, pnt, mask, resp,
+                   angle_sub, score, cpnt, cscore);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -355,6 +420,19 @@ static __global__ __launch_bounds__(256) void sample_desc_kernel(
   const int img = recs ? recs[sub2line_g[n]].image : 0;   // no records: all points belong to one image (linetr_sample_descriptors)
   const f32x4 o = sample_one(pnt[tok * 2 + 0], pnt[tok * 2 + 1], nhwc + (int64_t)img * Hc * Wc * D, Hc, Wc,
                              align_corners, lane);
+  *reinterpret_cast<f32x4*>(desc + tok * D + lane * 4) = o;
+}
+
+// ragged: map and size from the table entry of the token's image
+static __global__ __launch_bounds__(256) void sample_desc_ragged_kernel(
+    const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs, int64_t n_tokens, int T,
+    const RaggedImage* __restrict__ tab, int align_corners, float* __restrict__ desc) {
+  const int64_t tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tok >= n_tokens) return;
+  const int lane = threadIdx.x & 63;
+  const int n = (int)(tok / T);
+  const int img = __builtin_amdgcn_readfirstlane(recs[sub2line_g[n]].image);   // one token per wave: its image is wave-uniform
+  const f32x4 o = sample_one(pnt[tok * 2 + 0], pnt[tok * 2 + 1], tab[img].nhwc, tab[img].Hc, tab[img].Wc, align_corners, lane);
   *reinterpret_cast<f32x4*>(desc + tok * D + lane * 4) = o;
 }
 

@@ -227,16 +227,10 @@ class Engine(_TrainSurface, _DebugSurface):
         self._last_host = {"slot": slot, "recs_ptr": recs.ctypes.data, "rec_bytes": rec_bytes, "B": B}
         return recs, cu_k, cu_n
 
-    def prefilter(self, lines6, height, width, *, remove_borders, min_length, max_keylines, token_distance,
-                  max_tokens, valid_masks=None, offsets=None, n_threads=0, tie_order="numpy"):
-        """a1-a3 for a batch.  `lines6` is a list of [K_i,6] float64 arrays, or one concatenated [sum K,6] array
-        with `offsets` [B+1].  Returns (recs, cu_k, cu_n); recs lives in pinned memory ready for an async H2D.
-
-        tie_order: the length sort of models/line_process.py:15-16 is np.argsort, whose order among EQUAL lengths is NumPy's
-        business (unstable, CPU-dispatched).  "numpy" (default): the images the native pre-filter reports as holding equal
-        lengths (linetr_prefilter_tied_images; rare with a real detector) are re-ordered with NumPy itself and re-packed, so the
-        batched path gives the reference's rows on this machine, like the per-image path does.  "stable": keep the native order
-        (stable ascending argsort, reversed) -- machine-independent."""
+    @staticmethod
+    def _lines_blob(lines6, offsets, tie_order):
+        """The lines of a batch as the pre-filter entry points take them: (one [sum K,6] float64 array, row offsets [B+1] int32, B,
+        the number of rows)."""
         if tie_order not in ("numpy", "stable"):
             raise ValueError("tie_order must be 'numpy' or 'stable'")
         if offsets is None:
@@ -249,8 +243,19 @@ class Engine(_TrainSurface, _DebugSurface):
             cat = lines6
             offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         cat = np.ascontiguousarray(cat, dtype=np.float64)
-        B = len(offsets) - 1
-        cap = int(offsets[-1])
+        return cat, offsets, len(offsets) - 1, int(offsets[-1])
+
+    def prefilter(self, lines6, height, width, *, remove_borders, min_length, max_keylines, token_distance,
+                  max_tokens, valid_masks=None, offsets=None, n_threads=0, tie_order="numpy"):
+        """a1-a3 for a batch.  `lines6` is a list of [K_i,6] float64 arrays, or one concatenated [sum K,6] array
+        with `offsets` [B+1].  Returns (recs, cu_k, cu_n); recs lives in pinned memory ready for an async H2D.
+
+        tie_order: the length sort of models/line_process.py:15-16 is np.argsort, whose order among EQUAL lengths is NumPy's
+        business (unstable, CPU-dispatched).  "numpy" (default): the images the native pre-filter reports as holding equal
+        lengths (linetr_prefilter_tied_images; rare with a real detector) are re-ordered with NumPy itself and re-packed, so the
+        batched path gives the reference's rows on this machine, like the per-image path does.  "stable": keep the native order
+        (stable ascending argsort, reversed) -- machine-independent."""
+        cat, offsets, B, cap = self._lines_blob(lines6, offsets, tie_order)
         recs, cu_k, cu_n = self._record_blob(cap, B)
         vm_ptrs = None
         keep = []
@@ -277,6 +282,40 @@ class Engine(_TrainSurface, _DebugSurface):
                 repack_like_numpy(self._L, recs, cu_k, cu_n, i, cat[offsets[i]:offsets[i + 1]], int(height), int(width),
                                   remove_borders, min_length, max_keylines, token_distance, max_tokens,
                                   valid_masks[i] if valid_masks is not None else None)
+        return recs[:int(cu_k[-1])], cu_k.copy(), cu_n.copy()
+
+    def prefilter_ragged(self, lines6, shapes, *, remove_borders, min_length, max_keylines, token_distance, max_tokens,
+                         valid_masks=None, offsets=None, n_threads=0, tie_order="numpy"):
+        """prefilter() for images of DIFFERENT sizes (linetr_prefilter_ragged).  `shapes` [B] holds every image's (height, width);
+        `min_length` and `token_distance` are one value for the batch or one per image (the reference's auto_min_length gives every
+        image max(16, max(shape) / 40) and max(8, max(shape) / 80) of its own shape); a valid mask has its own image's shape.  The rest,
+        the returned (recs, cu_k, cu_n) and tie_order are prefilter()'s."""
+        cat, offsets, B, cap = self._lines_blob(lines6, offsets, tie_order)
+        if len(shapes) != B:
+            raise ValueError(f"{len(shapes)} image shapes for {B} images")
+        per_image = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float64), (B,))
+        table = np.zeros(B, dtype=nat.PREFILTER_IMAGE_DTYPE)
+        table["height"], table["width"] = [int(s[0]) for s in shapes], [int(s[1]) for s in shapes]
+        table["min_length"], table["token_distance"] = per_image(min_length), per_image(token_distance)
+        keep = []
+        for i, vm in enumerate(valid_masks if valid_masks is not None else []):
+            if vm is not None:
+                if np.ndim(vm) != 2 or np.shape(vm) != (int(table["height"][i]), int(table["width"][i])):
+                    raise ValueError(f"valid mask {i} has shape {np.shape(vm)}, the native pre-filter needs its image's "
+                                     f"({int(table['height'][i])}, {int(table['width'][i])})")
+                keep.append(np.ascontiguousarray(vm, dtype=np.float64))
+                table["valid_mask"][i] = keep[-1].ctypes.data
+        recs, cu_k, cu_n = self._record_blob(cap, B)
+        nat.check(self._L.linetr_prefilter_ragged(nat.np_ptr(cat), nat.np_ptr(offsets), B, nat.np_ptr(table), int(remove_borders),
+                                                  int(max_keylines), int(max_tokens), int(n_threads), nat.np_ptr(recs), cap,
+                                                  nat.np_ptr(cu_k), nat.np_ptr(cu_n)), self._L)
+        if tie_order == "numpy":
+            tied = np.empty(max(B, 1), dtype=np.int32)
+            n_tied = self._L.linetr_prefilter_tied_images(nat.np_ptr(tied), B)
+            for i in tied[:n_tied].tolist():     # every tied image with the settings of ITS table entry
+                repack_like_numpy(self._L, recs, cu_k, cu_n, i, cat[offsets[i]:offsets[i + 1]], int(table["height"][i]),
+                                  int(table["width"][i]), remove_borders, float(table["min_length"][i]), max_keylines,
+                                  float(table["token_distance"][i]), max_tokens, valid_masks[i] if valid_masks is not None else None)
         return recs[:int(cu_k[-1])], cu_k.copy(), cu_n.copy()
 
     def pack(self, klines, length, angles, token_distance, max_tokens, image=0, sub_base=0):
@@ -395,33 +434,11 @@ class Engine(_TrainSurface, _DebugSurface):
         B = len(cu_k) - 1
         K, N, T = int(cu_k[-1]), int(cu_n[-1]), int(max_tokens)
         dense_desc, dense_score, H, W, nhwc = self._dense_maps(dense_desc, dense_score, B, dense_layout)
-        f = dict(dtype=torch.float32, device=self.device)
-        # the small outputs and line_desc are views of ONE allocation
-        shapes = [("ld", (N, D)), ("klines", (K, 2, 2)), ("length", (K,)), ("angles", (K, 2)), ("sublines", (N, 2, 2)),
-                  ("resp", (N,)), ("angle_sub", (N, 2)), ("sub2line", (N,))]
-        if want_tokens:
-            shapes += [("pnt", (N, T, 2)), ("mask", (N, T + 1)), ("score", (N, T))]
-        if want_mat:     # the per-image [K_i,N_i] blocks back to back, written by extra blocks of the tokeniser's launch (<= 8 images)
-            shapes.append(("mat", (int((np.diff(np.asarray(cu_k, np.int64)) * np.diff(np.asarray(cu_n, np.int64))).sum()),)))
-        views, pool = self._pooled(shapes)
-        ld = views.pop("ld")
-        z = pool[:0]
-        for name in ("pnt", "mask", "score"):
-            views.setdefault(name, z)
-        tb = TokenBatch(n_images=B, max_tokens=T, cu_k=np.asarray(cu_k, np.int32), cu_n=np.asarray(cu_n, np.int32), recs=recs,
-                        desc=torch.empty((N, T, D), **f) if want_tokens else z, **views)
+        tb, ld, ct = self._describe_outputs(recs, cu_k, cu_n, T, want_tokens, want_mat)
         if K == 0 or N == 0:
             return tb, ld
         n_real = int(recs["n_tok"][:K].sum())
         d_recs, d_cu = self._upload_recs(recs, K, B, tb)
-        ct = tb.c_tokens()
-        if not want_tokens:
-            ct.pnt = ct.mask = ct.desc = ct.score = None
-        cu_k32 = np.ascontiguousarray(cu_k, dtype=np.int32)
-        if want_mat:
-            ct.h_cu_klines = cu_k32.ctypes.data
-            if B == 1:
-                tb.mat = tb.mat.view(K, N)
         nbytes = self._L.linetr_describe_workspace_bytes(self._h, B, H, W, N, n_real)
         cu = np.ascontiguousarray(cu_n, dtype=np.int32)
         args = (self._h, d_recs.data_ptr(), K, N, n_real, nat.np_ptr(cu), d_cu.data_ptr() if d_cu is not None else None, B,
@@ -442,6 +459,96 @@ class Engine(_TrainSurface, _DebugSurface):
             tb.extra["dense"] = (dense_desc, dense_score)          # read by the stage streams after this call returns
             nat.check(self._L.linetr_describe_submit(*args, ws.data_ptr(), ws.numel(), slot, n_slots, self._stream()), self._L)
         return tb, ld
+
+    def _describe_outputs(self, recs, cu_k, cu_n, T, want_tokens, want_mat):
+        """The outputs of a fused describe call (describe / describe_ragged): (TokenBatch, line_desc [N,256], the native Tokens struct
+        that points into them)."""
+        B = len(cu_k) - 1
+        K, N = int(cu_k[-1]), int(cu_n[-1])
+        f = dict(dtype=torch.float32, device=self.device)
+        # the small outputs and line_desc are views of ONE allocation
+        shapes = [("ld", (N, D)), ("klines", (K, 2, 2)), ("length", (K,)), ("angles", (K, 2)), ("sublines", (N, 2, 2)),
+                  ("resp", (N,)), ("angle_sub", (N, 2)), ("sub2line", (N,))]
+        if want_tokens:
+            shapes += [("pnt", (N, T, 2)), ("mask", (N, T + 1)), ("score", (N, T))]
+        if want_mat:     # the per-image [K_i,N_i] blocks back to back, written by extra blocks of the tokeniser's launch (<= 8 images)
+            shapes.append(("mat", (int((np.diff(np.asarray(cu_k, np.int64)) * np.diff(np.asarray(cu_n, np.int64))).sum()),)))
+        views, pool = self._pooled(shapes)
+        ld = views.pop("ld")
+        z = pool[:0]
+        for name in ("pnt", "mask", "score"):
+            views.setdefault(name, z)
+        tb = TokenBatch(n_images=B, max_tokens=T, cu_k=np.asarray(cu_k, np.int32), cu_n=np.asarray(cu_n, np.int32), recs=recs,
+                        desc=torch.empty((N, T, D), **f) if want_tokens else z, **views)
+        ct = tb.c_tokens()
+        if not want_tokens:
+            ct.pnt = ct.mask = ct.desc = ct.score = None
+        if want_mat and K and N:
+            tb.extra["cu_k32"] = cu_k32 = np.ascontiguousarray(cu_k, dtype=np.int32)     # read by the native call: kept with the batch
+            ct.h_cu_klines = cu_k32.ctypes.data
+            if B == 1:
+                tb.mat = tb.mat.view(K, N)
+        return tb, ld, ct
+
+    def describe_ragged(self, recs, cu_k, cu_n, dense_descs, dense_scores, *, token_distance, max_tokens, align_corners=False,
+                        want_tokens=False, dense_layout="nchw", want_mat=False):
+        """describe() for images of DIFFERENT sizes (linetr_describe_ragged).  `dense_descs` / `dense_scores` are lists with one map per
+        image, each its own tensor of its own shape -- [256,H/8,W/8] ('nchw') or [H/8,W/8,256] ('nhwc'), and [H,W]; a leading batch axis
+        of 1 is accepted -- and need not be packed.  `token_distance`: one value, or one per image (what the records were made with:
+        prefilter_ragged).  Returns (TokenBatch, line_desc [N,256]) like describe(); want_mat serves up to 8 images."""
+        B = len(cu_k) - 1
+        K, N, T = int(cu_k[-1]), int(cu_n[-1]), int(max_tokens)
+        if len(dense_descs) != B or len(dense_scores) != B:
+            raise ValueError("dense maps must have one entry per image")
+        nhwc = dense_layout == "nhwc"
+        table = np.zeros(B, dtype=nat.IMAGE_DTYPE)
+        table["token_distance"] = np.broadcast_to(np.asarray(token_distance, dtype=np.float64), (B,))
+        maps = []
+        for i, (dd, ds) in enumerate(zip(dense_descs, dense_scores)):
+            dd, ds = self._f32(dd), self._f32(ds)
+            dd, ds = (dd[0] if dd.dim() == 4 else dd), (ds[0] if ds.dim() == 3 else ds)
+            H, W = int(ds.shape[-2]), int(ds.shape[-1])
+            want = (H // 8, W // 8, D) if nhwc else (D, H // 8, W // 8)
+            if ds.dim() != 2 or tuple(dd.shape) != want:
+                raise ValueError(f"image {i}: dense_descriptor shape {tuple(dd.shape)} does not match {want} ({dense_layout}) of its "
+                                 f"{H} x {W} score map")
+            maps.append((dd, ds))
+            table[i] = (dd.data_ptr(), ds.data_ptr(), H, W, table["token_distance"][i])
+        tb, ld, ct = self._describe_outputs(recs, cu_k, cu_n, T, want_tokens, want_mat)
+        if K == 0 or N == 0:
+            return tb, ld
+        tb.extra["dense"] = maps          # the stream reads them after this call returns
+        n_real = int(recs["n_tok"][:K].sum())
+        d_recs, d_cu = self._upload_recs(recs, K, B, tb)
+        nbytes = self._L.linetr_describe_ragged_workspace_bytes(self._h, nat.np_ptr(table), B, int(nhwc), N, n_real)
+        if nbytes < 0:      # the table is refused: the call says why
+            nbytes = 0
+        ws = self._workspace("desc", nbytes)
+        cu = np.ascontiguousarray(cu_n, dtype=np.int32)
+        recs_c = np.ascontiguousarray(recs[:K])
+        with torch.cuda.device(self.device):
+            nat.check(self._L.linetr_describe_ragged(self._h, d_recs.data_ptr(), nat.np_ptr(recs_c), K, N, n_real, nat.np_ptr(cu),
+                                                     d_cu.data_ptr() if d_cu is not None else None, nat.np_ptr(table), B, T,
+                                                     int(bool(align_corners)), int(nhwc), ct, tb.sub2line.data_ptr(), ld.data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), self._stream()), self._L)
+        return tb, ld
+
+    def describe_lines_ragged(self, lines6, offsets, dense_descs, dense_scores, *, remove_borders, min_length, max_keylines,
+                              token_distance, max_tokens, align_corners=False, want_tokens=False, dense_layout="nchw",
+                              angles="native", want_mat=False, valid_masks=None):
+        """describe_lines() for images of DIFFERENT sizes: prefilter_ragged + describe_ragged.  The image sizes are those of the score
+        maps; `min_length` / `token_distance`: one value or one per image; `angles` as in describe_lines()."""
+        if angles not in ("native", "numpy"):
+            raise ValueError("angles must be 'native' or 'numpy'")
+        shapes = [(int(ds.shape[-2]), int(ds.shape[-1])) for ds in dense_scores]
+        recs, cu_k, cu_n = self.prefilter_ragged(lines6, shapes, offsets=offsets, remove_borders=remove_borders, min_length=min_length,
+                                                 max_keylines=max_keylines, token_distance=token_distance, max_tokens=max_tokens,
+                                                 valid_masks=valid_masks)
+        if angles == "numpy" and len(recs):
+            from .line_process import get_angles
+            recs["angle"] = get_angles(np.stack([recs["sp"], recs["ep"]], axis=1))     # (records live in the pinned upload slot)
+        return self.describe_ragged(recs, cu_k, cu_n, dense_descs, dense_scores, token_distance=token_distance, max_tokens=max_tokens,
+                                    align_corners=align_corners, want_tokens=want_tokens, dense_layout=dense_layout, want_mat=want_mat)
 
     def describe_join(self, slot: int):
         """The current stream waits for the batch last submitted to `slot` (linetr_describe_join)."""

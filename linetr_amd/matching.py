@@ -59,16 +59,22 @@ class Matching(torch.nn.Module):
         every tensor of the reference's dict materialised, mat_klines2sublines from the same launch): 45 launches instead of 2 x 44,
         and the pair's GEMMs see 398 rows instead of twice 199.  Every tensor of the two dicts equals the per-image path's bit for bit
         except the descriptors (fp32 round-off: other GEMM tiles for 398 rows; tests/test_gpu_dropin.py).
+        A pair of two image sizes takes the same call in its ragged form (linetr_prefilter_ragged + linetr_describe_ragged): each image
+        with min_length / token_distance of its own shape (_auto_lengths), lt.config left on image1's values as in the reference.
         Returns the two dicts (preprocess + forward of models/line_transformer.py:225-275), or None when the pair does not
-        qualify (an image without lines, maps of different shapes or not on the device)."""
-        from .line_process import attach_sub2line, get_angles, keylines_to_array, mask_fits_image
+        qualify (an image without lines, maps that do not fit their images or are not on the device)."""
+        from .line_process import get_angles, keylines_to_array, mask_fits_image
         lt = self.linetransformer
         imgs = [data["image" + s] for s in sides]
         shape = tuple(imgs[0].shape)
         nhwc = all(sp[s].get("dense_descriptor_nhwc") is not None for s in sides)
         key = "dense_descriptor_nhwc" if nhwc else "dense_descriptor"
         dds, dss = [sp[s][key] for s in sides], [sp[s]["dense_score"] for s in sides]
-        if tuple(imgs[1].shape) != shape or not all(t.is_cuda for t in dds + dss) or dds[0].shape != dds[1].shape:
+        if not all(t.is_cuda for t in dds + dss):
+            return None
+        if tuple(imgs[1].shape) != shape:
+            return self._describe_fused_ragged(data, sides, detected, imgs, dds, dss, nhwc)
+        if dds[0].shape != dds[1].shape:
             return None
         _, _, height, width = lt.config["image_shape"] = shape   # (LineTransformer.preprocess writes it too: line_transformer.py:258)
         c = lt.config
@@ -92,6 +98,45 @@ class Matching(torch.nn.Module):
         align = int(torch.__version__[2]) > 2                     # the reference's own version switch (line_process.py:93)
         tb, ld = eng.describe(recs, cu_k, cu_n, torch.cat(dds), torch.cat(dss), token_distance=td, max_tokens=T,
                               align_corners=align, want_tokens=True, dense_layout="nhwc" if nhwc else "nchw", want_mat=True)
+        return self._fused_dicts(tb, ld)
+
+    def _describe_fused_ragged(self, data, sides, detected, imgs, dds, dss, nhwc):
+        """_describe_fused for a pair of two image sizes."""
+        from .line_process import get_angles, keylines_to_array, mask_fits_image
+        lt = self.linetransformer
+        c = lt.config
+        hw, mls, tds = [], [], []
+        for img in imgs:      # thresholds per image, in order: the config ends on image1's (matching.py:29-32, :45-48)
+            self._auto_lengths(img.shape)
+            c["image_shape"] = tuple(img.shape)
+            hw.append((int(img.shape[-2]), int(img.shape[-1])))
+            mls.append(c["min_length"])
+            tds.append(c["token_distance"])
+        if any(tuple(ds.shape[-2:]) != s for ds, s in zip(dss, hw)):
+            return None
+        masks = [data["valid_mask" + s] if isinstance(data["valid_mask" + s], np.ndarray) else None for s in sides]
+        if any(m is not None and not mask_fits_image(m, *s) for m, s in zip(masks, hw)):
+            return None
+        T = c["max_tokens"]
+        eng = lt.engine(dds[0].device)
+        recs, cu_k, cu_n = eng.prefilter_ragged([keylines_to_array(detected[s]) for s in sides], hw, remove_borders=c["remove_borders"],
+                                                min_length=mls, max_keylines=c["max_keylines"], token_distance=tds, max_tokens=T,
+                                                valid_masks=masks if any(m is not None for m in masks) else None)
+        if cu_k[1] == 0 or cu_k[2] == cu_k[1]:
+            return None
+        for i in range(2):
+            r = recs[cu_k[i]:cu_k[i + 1]]
+            r["angle"] = get_angles(np.stack([r["sp"], r["ep"]], axis=1))
+        align = int(torch.__version__[2]) > 2
+        tb, ld = eng.describe_ragged(recs, cu_k, cu_n, dds, dss, token_distance=tds, max_tokens=T, align_corners=align,
+                                     want_tokens=True, dense_layout="nhwc" if nhwc else "nchw", want_mat=True)
+        return self._fused_dicts(tb, ld)
+
+    @staticmethod
+    def _fused_dicts(tb, ld):
+        """the two dicts of the reference out of a fused two-image call's TokenBatch and descriptors"""
+        from .line_process import attach_sub2line
+        cu_k, cu_n = tb.cu_k, tb.cu_n
         outs = []
         for i in range(2):      # one indexing call per entry (a torch view costs ~2 us of host time; there are 24 of them)
             k = slice(int(cu_k[i]), int(cu_k[i + 1]))
@@ -104,6 +149,12 @@ class Matching(torch.nn.Module):
                          "score_sublines": tb.score[None, n, :, None], "mat_klines2sublines": mat,
                          "line_desc": ld[None, n].transpose(1, 2)})
         return outs
+
+    def _auto_lengths(self, shape):
+        """min_length / token_distance follow the image about to be tokenised -- per image, matching.py:29-32 and :45-48."""
+        if self.auto_min_length:
+            self.linetransformer.config["min_length"] = max(16, max(shape) / 40)
+            self.linetransformer.config["token_distance"] = max(8, max(shape) / 80)
 
     def forward(self, data):
         pred = {}
@@ -126,19 +177,15 @@ class Matching(torch.nn.Module):
                 data["valid_mask" + s] = torch.ones_like(data["image" + s])   # a tensor: ignored downstream (matching.py:37-40)
         lt = self.linetransformer
 
-        def auto_lengths(shape):
-            """min_length / token_distance follow the image about to be tokenised -- per image, matching.py:29-32 and :45-48."""
-            if self.auto_min_length:
-                lt.config["min_length"] = max(16, max(shape) / 40)
-                lt.config["token_distance"] = max(8, max(shape) / 80)
-
+        auto_lengths = self._auto_lengths
         detected = {s: self.lsd.detect_torch(data["image" + s]) for s in sides}
         outs = None
-        if len(sides) == 2 and tuple(data["image0"].shape) == tuple(data["image1"].shape):
-            auto_lengths(data["image0"].shape)                    # one shape: both images get the same two values
-            outs = self._describe_fused(data, sp, sides, detected)
-        if outs is None:     # one image (anchor cached), an image without lines, host tensors, two image sizes: tokenised image by
-            pres = []        # image, each with the thresholds of ITS shape (lt.config ends on the last image's, as in the reference)
+        if len(sides) == 2:
+            if tuple(data["image0"].shape) == tuple(data["image1"].shape):
+                auto_lengths(data["image0"].shape)                # one shape: both images get the same two values
+            outs = self._describe_fused(data, sp, sides, detected)     # (two shapes: it gives each image the values of its own)
+        if outs is None:     # one image (anchor cached), an image without lines, host tensors: tokenised image by image, each
+            pres = []        # with the thresholds of ITS shape (lt.config ends on the last image's, as in the reference)
             for s in sides:
                 auto_lengths(data["image" + s].shape)
                 pres.append(lt.preprocess(detected[s], data["image" + s].shape, sp[s], data["valid_mask" + s]))
@@ -191,9 +238,11 @@ class Matching(torch.nn.Module):
     def forward_batch(self, pairs):
         """Batched counterpart of forward() (section 8(f)-3: the reference's surface is one pair per call).
 
-        `pairs` is a list of dicts with 'image0' / 'image1' ([1,1,H,W], all pairs the same size).  SuperPoint and
-        LSD still run per image (out-of-scope front-ends); line tokenisation + description of ALL 2P images is ONE
-        fused native call (linetr_prefilter_batch + linetr_describe) and the line matching of all P pairs is ONE
+        `pairs` is a list of dicts with 'image0' / 'image1' ([1,1,H,W]; the images may differ in size, inside a pair and between
+        pairs).  SuperPoint and LSD still run per image (out-of-scope front-ends); line tokenisation + description of ALL 2P images
+        is ONE fused native call (equal sizes: linetr_prefilter_batch + linetr_describe, exactly as before; otherwise
+        linetr_prefilter_ragged + linetr_describe_ragged, every image with the min_length / token_distance of its own shape under
+        auto_min_length, lt.config left on the last image's values) and the line matching of all P pairs is ONE
         linetr_match call.  Returns a list of P dicts with the keys forward() produces, except that the dense
         per-token tensors (pnt/mask/desc/score_sublines) are not materialised.  Key-line order is forward()'s: the native
         pre-filter sorts, and images that hold equal lengths are ordered by NumPy's own argsort (Engine.prefilter, tie_order); the
@@ -204,33 +253,37 @@ class Matching(torch.nn.Module):
         P = len(pairs)
         if P == 0:
             return []
-        shape = tuple(pairs[0]["image0"].shape)
+        shapes = [tuple(d["image" + s].shape) for d in pairs for s in ("0", "1")]
         sp_out, lines, valid = [], [], []
         for d in pairs:
             for s in ("0", "1"):
                 img = d["image" + s]
-                if tuple(img.shape) != shape:
-                    raise ValueError("forward_batch needs equally sized images")
                 sp = self.superpoint({"image": img})
                 sp_out.append(sp)
                 lines.append(keylines_to_array(self.lsd.detect_torch(img)))
-        if self.auto_min_length:
-            lt.config["min_length"] = max(16, max(shape) / 40)
-            lt.config["token_distance"] = max(8, max(shape) / 80)
-        lt.config["image_shape"] = shape
+        mls, tds = [], []
+        for shape in shapes:      # (equal sizes: the same two values every time)
+            self._auto_lengths(shape)
+            mls.append(lt.config["min_length"])
+            tds.append(lt.config["token_distance"])
+        lt.config["image_shape"] = shapes[-1]
         c = lt.config
         # a producer that already emits the tokeniser's layout (linetr_amd.superpoint.FusedHeadSuperPoint) saves the
         # NCHW -> NHWC pass inside linetr_describe
         layout = "nhwc" if all("dense_descriptor_nhwc" in sp for sp in sp_out) else "nchw"
-        dd = torch.cat([sp["dense_descriptor_nhwc" if layout == "nhwc" else "dense_descriptor"] for sp in sp_out])
-        ds = torch.cat([sp["dense_score"] for sp in sp_out])
-        eng = lt.engine(dd.device)
+        dds = [sp["dense_descriptor_nhwc" if layout == "nhwc" else "dense_descriptor"] for sp in sp_out]
+        dss = [sp["dense_score"] for sp in sp_out]
+        eng = lt.engine(dds[0].device)
         off = np.concatenate([[0], np.cumsum([len(l) for l in lines])]).astype(np.int32)
         cat = np.concatenate(lines) if off[-1] else np.zeros((0, 6))
         align = int(torch.__version__[2]) > 2
-        tb, ld = eng.describe_lines(cat, off, dd, ds, remove_borders=c["remove_borders"], min_length=c["min_length"],
-                                    max_keylines=c["max_keylines"], token_distance=c["token_distance"],
-                                    max_tokens=c["max_tokens"], align_corners=align, dense_layout=layout, angles="numpy")
+        kw = dict(remove_borders=c["remove_borders"], max_keylines=c["max_keylines"], max_tokens=c["max_tokens"], align_corners=align,
+                  dense_layout=layout, angles="numpy")
+        if all(shape == shapes[0] for shape in shapes):
+            tb, ld = eng.describe_lines(cat, off, torch.cat(dds), torch.cat(dss), min_length=c["min_length"],
+                                        token_distance=c["token_distance"], **kw)
+        else:
+            tb, ld = eng.describe_lines_ragged(cat, off, dds, dss, min_length=mls, token_distance=tds, **kw)
         cu_n, cu_k = tb.cu_n, tb.cu_k
         n, k = np.diff(cu_n), np.diff(cu_k)
         dev = ld.device
