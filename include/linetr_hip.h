@@ -221,6 +221,21 @@ int linetr_pack_lines(const double* h_klines, const double* h_length, const doub
 
 /* ---- device: tokenise ----------------------------------------------------------------------- */
 
+/* Element type of a dense descriptor map, OR-ed into an entry point's `dense_is_nhwc` argument.  Without these bits the argument means
+ * what it always meant: 0 = NCHW float32, any other value below 0x100 (a negative one too) = NHWC float32, with the alignment rules each
+ * entry point states (a float32 NCHW map may lie anywhere).  LINETR_DENSE_F16: the map holds IEEE float16,
+ * LINETR_DENSE_BF16: bfloat16; both bits together, or any higher bit, are refused with LINETR_E_ARG before anything is launched.  A half
+ * map is read in place (no float32 copy): every element is converted exactly at the load (fp16 subnormals are kept) and all arithmetic
+ * is the float32 call's, so the results equal those of the same call on the map's float32 upcast.  One call has ONE element type for all
+ * its images.  A half NHWC map must be 8-byte aligned (a lane owns 4 channels); a half NCHW map may lie at any 2-byte address, its layout
+ * pass transposes halves into a half scratch.  dense_score, token outputs and line descriptors are float32 always.
+ * The bits are accepted by linetr_tokenize, linetr_sample_descriptors, linetr_point_descriptors, linetr_describe,
+ * linetr_describe_ragged, linetr_describe_submit and linetr_debug_cls_pool (and by the size queries that take dense_is_nhwc: a half
+ * format may need less, never more; a refused format gives the query's own "refused" answer).  Every other entry point that takes a
+ * dense map (linetr_fixed_size) refuses them. */
+#define LINETR_DENSE_F16 0x100
+#define LINETR_DENSE_BF16 0x200
+
 /* Bytes of scratch linetr_tokenize needs (NHWC copy of the dense descriptor maps + index maps). */
 int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t N);
 
@@ -238,7 +253,7 @@ int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t height, int32_
  * A channel-last d_dense_desc, out.desc and d_workspace are accessed with 16-byte vectors: one that is not 16-byte aligned is refused
  * with LINETR_E_ARG before anything is launched (linetr_describe / linetr_describe_submit: the same three). */
 int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N,
-                    double token_distance, int32_t max_tokens, const float* d_dense_desc,
+                    double token_distance, int32_t max_tokens, const void* d_dense_desc,
                     const float* d_dense_score, int32_t n_images, int32_t height, int32_t width,
                     int32_t clip_height, int32_t clip_width, int32_t align_corners, int32_t dense_is_nhwc,
                     LinetrTokens out, int32_t* d_sub2line, void* d_workspace, int64_t workspace_bytes, void* stream);
@@ -248,7 +263,7 @@ int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int
  * ([256,Hc,Wc], or [Hc,Wc,256] with dense_is_nhwc) and L2-normalised; d_out [n,256] row-major.  `h` may be NULL.
  * A channel-last map, d_out and d_workspace must be 16-byte aligned (LINETR_E_ARG otherwise; an NCHW map and d_points may lie anywhere). */
 int64_t linetr_sample_descriptors_workspace_bytes(int32_t Hc, int32_t Wc, int32_t dense_is_nhwc);
-int linetr_sample_descriptors(LinetrHandle* h, const float* d_points, int64_t n, const float* d_dense_desc, int32_t Hc,
+int linetr_sample_descriptors(LinetrHandle* h, const float* d_points, int64_t n, const void* d_dense_desc, int32_t Hc,
                               int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc, float* d_out, void* d_workspace,
                               int64_t workspace_bytes, void* stream);
 
@@ -300,7 +315,7 @@ int64_t linetr_describe_workspace_bytes(const LinetrHandle* h, int32_t n_images,
  * `out` are non-NULL; pnt / mask / score / desc are written only if non-NULL (dense [N,T,...] layout). */
 int linetr_describe(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, int64_t n_real_tokens,
                     const int32_t* h_cu_sub, const int32_t* d_cu_sub, int32_t n_images, double token_distance,
-                    int32_t max_tokens, const float* d_dense_desc, const float* d_dense_score, int32_t height,
+                    int32_t max_tokens, const void* d_dense_desc, const float* d_dense_score, int32_t height,
                     int32_t width, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
                     int32_t* d_sub2line, float* d_line_desc, void* d_workspace, int64_t workspace_bytes,
                     void* stream);
@@ -308,7 +323,7 @@ int linetr_describe(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int
 /* One image of a linetr_describe_ragged batch: its own maps, size and token distance.  The maps are separate allocations; nothing
  * requires the caller to pack them. */
 typedef struct {
-  const float* d_dense_desc;   /* [256,height/8,width/8] (dense_is_nhwc = 0) or [height/8,width/8,256]; device memory */
+  const void* d_dense_desc;    /* [256,height/8,width/8] (dense_is_nhwc = 0) or [height/8,width/8,256]; device memory */
   const float* d_dense_score;  /* [height,width]; device memory                                                        */
   int32_t height, width;       /* positive multiples of 8                                                              */
   double token_distance;       /* > 0 (auto_min_length: max(8, max(shape) / 80) of THIS image)                         */
@@ -354,7 +369,7 @@ int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_recs, const L
  * the library's streams idle and the slot free (nothing half-queued survives it). */
 int linetr_describe_submit(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, int64_t n_real_tokens,
                            const int32_t* h_cu_sub, const int32_t* d_cu_sub, int32_t n_images, double token_distance,
-                           int32_t max_tokens, const float* d_dense_desc, const float* d_dense_score, int32_t height,
+                           int32_t max_tokens, const void* d_dense_desc, const float* d_dense_score, int32_t height,
                            int32_t width, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
                            int32_t* d_sub2line, float* d_line_desc, void* d_workspace, int64_t workspace_bytes,
                            int32_t slot, int32_t n_slots, void* stream);
@@ -986,6 +1001,17 @@ int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const 
                             int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
                             float* d_dense_desc_nchw, void* stream);
 
+/* linetr_superpoint_heads for raw head outputs and descriptor maps of another element type (a SuperPoint run under autocast).
+ * in_type: the type of d_score_logits AND d_desc_raw; out_type: the type of d_dense_desc_nhwc AND d_dense_desc_nchw; each 0 (float32),
+ * LINETR_DENSE_F16 or LINETR_DENSE_BF16, anything else is refused with nothing written.  d_dense_score is float32 always.  The
+ * arithmetic is linetr_superpoint_heads': half inputs are converted exactly at the load, so the results equal that call's on the upcast
+ * inputs; half outputs are its float32 outputs rounded to nearest-even.  linetr_superpoint_heads is this call with 0, 0.
+ * Alignment (LINETR_E_ARG otherwise): float32 pointers 16 bytes as there; half outputs 8 bytes; half inputs 8 bytes when Hc * Wc is a
+ * multiple of 4 (the vector path), else 2. */
+int linetr_superpoint_heads_typed(LinetrHandle* h, const void* d_score_logits, const void* d_desc_raw, int32_t in_type, int32_t B,
+                                  int32_t Hc, int32_t Wc, float* d_dense_score, void* d_dense_desc_nhwc, void* d_dense_desc_nchw,
+                                  int32_t out_type, void* stream);
+
 /* ---- SuperPoint key-point branch (models/superpoint.py:48-93, 168-187, 195-197) ---------------------- */
 
 /* Non-maximum suppression, threshold, border filter, optional top-k and (x, y) conversion for a batch of score maps, on the device:
@@ -1013,7 +1039,7 @@ int linetr_superpoint_keypoints(LinetrHandle* h, const float* d_dense_score, int
  * (LINETR_E_ARG otherwise); d_keypoints, d_desc_cn and an NCHW map may lie anywhere. */
 int64_t linetr_point_descriptors_workspace_bytes(int32_t B, int32_t Hc, int32_t Wc, int32_t dense_is_nhwc);
 int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const int32_t* d_cu_kp, int32_t B, int64_t n_total,
-                             const float* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
+                             const void* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
                              float* d_desc_cn, void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* linetr_superpoint_heads for channel-last raw head outputs: d_score_rows [B*Hc*Wc][ld_score >= 65] and d_desc_rows
@@ -1410,7 +1436,7 @@ int linetr_debug_bn_train(LinetrHandle* h, int32_t which, float* d_z, int64_t ro
  * a training-mode handle.  Synchronises `stream` before returning. */
 int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const LinetrLineRec* d_recs, int32_t K, const int32_t* d_sub2line,
                           int32_t N, int32_t T, const float* d_cpnt, const float* d_a4, int64_t first_pad, int32_t n_images,
-                          const float* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
+                          const void* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
                           const float* d_desc_dense, float* d_pooled, int32_t* kernel_used, void* stream);
 
 /* Runs ONE path of the descriptor-distance matcher alone, for the unit tests (tests/test_gpu_match_kernels.py: every matcher kernel

@@ -16,6 +16,15 @@ LIB_PATH = os.path.join(_HERE, "csrc", "liblinetr_hip.so")
 EXPERIMENTS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "experiments", "liblinetr_hip_experiments.so")
 
 E_ARG, E_ASSERT, E_WORKSPACE = -1, -4, -5     # LinetrStatus codes that callers tell apart (include/linetr_hip.h)
+# element type of a dense descriptor map, OR-ed into `dense_is_nhwc` (LINETR_DENSE_F16 / LINETR_DENSE_BF16); also the type codes of
+# linetr_superpoint_heads_typed
+DENSE_F16, DENSE_BF16 = 0x100, 0x200
+
+
+def dense_type_bits(dtype) -> int:
+    """The format bits of a torch dtype the kernels read in place (0: float32); None for every other dtype."""
+    import torch
+    return {torch.float32: 0, torch.float16: DENSE_F16, torch.bfloat16: DENSE_BF16}.get(dtype)
 
 
 class ModelConfig(C.Structure):
@@ -229,6 +238,7 @@ ABI = {
     "linetr_grad_norm_workspace_bytes": (i64, [i32, i64]),
     "linetr_grad_norm": (i32, [vp, vp, i32, f64, vp, vp, vp, i64, vp]),
     "linetr_superpoint_heads": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "linetr_superpoint_heads_typed": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "linetr_superpoint_keypoints_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "linetr_superpoint_keypoints": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     "linetr_point_descriptors_workspace_bytes": (i64, [i32, i32, i32, i32]),

@@ -605,36 +605,69 @@ extern "C" int linetr_pack_slab(const float* d_line_desc, int32_t N, const int32
 }
 
 namespace {
+// a type code of linetr_superpoint_heads_typed -> MapType, or -1
+int head_type(int32_t code) { return code == 0 ? MT_F32 : code == LINETR_DENSE_F16 ? MT_F16 : code == LINETR_DENSE_BF16 ? MT_BF16 : -1; }
+bool aligned_to(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+
+// the NCHW descriptor head for raw inputs of type EI: the float32 / float32 pair is the kernel that was always there
+template <class EI, class EO>
+void desc_head_launch(hipStream_t st, int B, int HW, const void* raw, void* nhwc, void* nchw) {
+  const dim3 grid((unsigned)cdiv(HW, 32), (unsigned)B);
+  if constexpr (sizeof(EI) == 4 && sizeof(EO) == 4)
+    hipLaunchKernelGGL((sp_desc_head_kernel<32, false>), grid, dim3(256), 0, st, (const float*)raw, (float*)nhwc, (float*)nchw, HW, (int64_t)0);
+  else
+    hipLaunchKernelGGL((sp_desc_head_typed_kernel<32, EI, EO>), grid, dim3(256), 0, st, (const EI*)raw, (EO*)nhwc, (EO*)nchw, HW);
+}
+template <class EI>
+void desc_head_launch_in(hipStream_t st, int out_type, int B, int HW, const void* raw, void* nhwc, void* nchw) {
+  if (out_type == MT_F32) desc_head_launch<EI, float>(st, B, HW, raw, nhwc, nchw);
+  else if (out_type == MT_F16) desc_head_launch<EI, f16_t>(st, B, HW, raw, nhwc, nchw);
+  else desc_head_launch<EI, bf16_t>(st, B, HW, raw, nhwc, nchw);
+}
+
 // Both layouts of the raw head outputs: NCHW (rows = false; the strides are unused) or channel-last rows of ld_score / ld_desc floats.
+// in_type / out_type (MapType): the element type of the two raw inputs and of the two descriptor outputs; rows are float32 only.
 template <bool ROWS>
-int superpoint_heads_any(LinetrHandle* h, const char* who, const float* d_score, int64_t ld_score, const float* d_desc, int64_t ld_desc,
-                         int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc, float* d_dense_desc_nchw,
-                         void* stream) {
+int superpoint_heads_any(LinetrHandle* h, const char* who, const void* d_score, int64_t ld_score, const void* d_desc, int64_t ld_desc,
+                         int in_type, int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score, void* d_dense_desc_nhwc,
+                         void* d_dense_desc_nchw, int out_type, void* stream) {
+  if (in_type < 0 || out_type < 0 || (ROWS && (in_type != MT_F32 || out_type != MT_F32)))
+    return fail(LINETR_E_ARG, "%s: a type code must be 0 (float32), LINETR_DENSE_F16 or LINETR_DENSE_BF16", who);
   if (B < 0 || Hc <= 0 || Wc <= 0) return fail(LINETR_E_ARG, "%s: bad shape B=%d Hc=%d Wc=%d", who, B, Hc, Wc);
   if (d_dense_score && !d_score) return fail(LINETR_E_ARG, "%s: score output without score logits", who);
   if ((d_dense_desc_nhwc || d_dense_desc_nchw) && !d_desc) return fail(LINETR_E_ARG, "%s: descriptor output without the raw descriptor head", who);
   if (ROWS && ((d_score && ld_score < 65) || (d_desc && ld_desc < D))) return fail(LINETR_E_ARG, "%s: row stride below the row's length", who);
   // 16-byte vectors: every output (the score map and the NCHW map are stored so, the channel-last map is what the samplers load so) and
-  // the NCHW head outputs when a channel's plane is a multiple of 4 floats; rows are read scalar-wise
+  // the NCHW head outputs when a channel's plane is a multiple of 4 floats; rows are read scalar-wise.  A half side moves 4 elements as
+  // 8 bytes; off the vector path a half input needs its own 2.
   const bool vec_in = !ROWS && ((int64_t)Hc * Wc) % 4 == 0;
-  if (!aligned16(d_dense_score) || !aligned16(d_dense_desc_nhwc) || !aligned16(d_dense_desc_nchw) ||
-      (vec_in && (!aligned16(d_score) || !aligned16(d_desc))))
-    return fail(LINETR_E_ARG, "%s: the dense maps%s must be 16-byte aligned", who, vec_in ? " and the raw head outputs" : "");
+  const int in_align = in_type == MT_F32 ? (vec_in ? 16 : 1) : (vec_in ? 8 : 2), out_align = out_type == MT_F32 ? 16 : 8;
+  if (!aligned16(d_dense_score) || !aligned_to(d_dense_desc_nhwc, out_align) || !aligned_to(d_dense_desc_nchw, out_align) ||
+      !aligned_to(d_score, in_align) || !aligned_to(d_desc, in_align))
+    return fail(LINETR_E_ARG, "%s: the dense maps%s must be 16-byte aligned (half descriptor maps and half inputs: 8)", who,
+                vec_in ? " and the raw head outputs" : "");
   if (B == 0) return LINETR_OK;
   if (h) LT_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   const int HW = Hc * Wc;
   const dim3 grid((unsigned)cdiv(HW, 64), (unsigned)B);
+  const double in_b = in_type == MT_F32 ? 4.0 : 2.0, out_b = out_type == MT_F32 ? 4.0 : 2.0;
   if (d_dense_desc_nhwc || d_dense_desc_nchw) {
-    const double by = (double)B * HW * D * 4.0 * (1 + (d_dense_desc_nhwc ? 1 : 0) + (d_dense_desc_nchw ? 1 : 0));
+    const double by = (double)B * HW * D * (in_b + out_b * ((d_dense_desc_nhwc ? 1 : 0) + (d_dense_desc_nchw ? 1 : 0)));
     ProfScope ps(h, st, "sp_desc_head", 3.0 * B * HW * D, by);
-    hipLaunchKernelGGL((sp_desc_head_kernel<32, ROWS>), dim3((unsigned)cdiv(HW, 32), (unsigned)B), dim3(256), 0, st, d_desc, d_dense_desc_nhwc,
-                       d_dense_desc_nchw, HW, ld_desc);
+    if constexpr (ROWS)
+      hipLaunchKernelGGL((sp_desc_head_kernel<32, true>), dim3((unsigned)cdiv(HW, 32), (unsigned)B), dim3(256), 0, st, (const float*)d_desc,
+                         (float*)d_dense_desc_nhwc, (float*)d_dense_desc_nchw, HW, ld_desc);
+    else if (in_type == MT_F32) desc_head_launch_in<float>(st, out_type, B, HW, d_desc, d_dense_desc_nhwc, d_dense_desc_nchw);
+    else if (in_type == MT_F16) desc_head_launch_in<f16_t>(st, out_type, B, HW, d_desc, d_dense_desc_nhwc, d_dense_desc_nchw);
+    else desc_head_launch_in<bf16_t>(st, out_type, B, HW, d_desc, d_dense_desc_nhwc, d_dense_desc_nchw);
     LT_LAUNCH_CHECK();
   }
   if (d_dense_score) {
-    ProfScope ps(h, st, "sp_score_head", 0, (double)B * HW * (65 + 64) * 4.0);
-    hipLaunchKernelGGL(sp_score_head_kernel<ROWS>, grid, dim3(256), 0, st, d_score, d_dense_score, Hc, Wc, ld_score);
+    ProfScope ps(h, st, "sp_score_head", 0, (double)B * HW * (65 * in_b + 64 * 4.0));
+    if (in_type == MT_F32) hipLaunchKernelGGL(sp_score_head_kernel<ROWS>, grid, dim3(256), 0, st, (const float*)d_score, d_dense_score, Hc, Wc, ld_score);
+    else if (in_type == MT_F16) hipLaunchKernelGGL(sp_score_head_typed_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t*)d_score, d_dense_score, Hc, Wc);
+    else hipLaunchKernelGGL(sp_score_head_typed_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)d_score, d_dense_score, Hc, Wc);
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;
@@ -644,15 +677,22 @@ int superpoint_heads_any(LinetrHandle* h, const char* who, const float* d_score,
 extern "C" int linetr_superpoint_heads(LinetrHandle* h, const float* d_score_logits, const float* d_desc_raw, int32_t B,
                                        int32_t Hc, int32_t Wc, float* d_dense_score, float* d_dense_desc_nhwc,
                                        float* d_dense_desc_nchw, void* stream) {
-  return superpoint_heads_any<false>(h, "superpoint_heads", d_score_logits, 0, d_desc_raw, 0, B, Hc, Wc, d_dense_score, d_dense_desc_nhwc,
-                                     d_dense_desc_nchw, stream);
+  return superpoint_heads_any<false>(h, "superpoint_heads", d_score_logits, 0, d_desc_raw, 0, MT_F32, B, Hc, Wc, d_dense_score,
+                                     d_dense_desc_nhwc, d_dense_desc_nchw, MT_F32, stream);
+}
+
+extern "C" int linetr_superpoint_heads_typed(LinetrHandle* h, const void* d_score_logits, const void* d_desc_raw, int32_t in_type, int32_t B,
+                                             int32_t Hc, int32_t Wc, float* d_dense_score, void* d_dense_desc_nhwc,
+                                             void* d_dense_desc_nchw, int32_t out_type, void* stream) {
+  return superpoint_heads_any<false>(h, "superpoint_heads_typed", d_score_logits, 0, d_desc_raw, 0, head_type(in_type), B, Hc, Wc,
+                                     d_dense_score, d_dense_desc_nhwc, d_dense_desc_nchw, head_type(out_type), stream);
 }
 
 extern "C" int linetr_superpoint_heads_rows(LinetrHandle* h, const float* d_score_rows, int64_t ld_score, const float* d_desc_rows,
                                             int64_t ld_desc, int32_t B, int32_t Hc, int32_t Wc, float* d_dense_score,
                                             float* d_dense_desc_nhwc, float* d_dense_desc_nchw, void* stream) {
-  return superpoint_heads_any<true>(h, "superpoint_heads_rows", d_score_rows, ld_score, d_desc_rows, ld_desc, B, Hc, Wc, d_dense_score,
-                                    d_dense_desc_nhwc, d_dense_desc_nchw, stream);
+  return superpoint_heads_any<true>(h, "superpoint_heads_rows", d_score_rows, ld_score, d_desc_rows, ld_desc, MT_F32, B, Hc, Wc, d_dense_score,
+                                    d_dense_desc_nhwc, d_dense_desc_nchw, MT_F32, stream);
 }
 
 // =============================================================================================

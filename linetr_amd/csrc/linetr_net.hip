@@ -256,12 +256,25 @@ int k2s_table(const LinetrTokens& out, int n_images, int K, int N, const int32_t
 
 // The channel-last form of n_images dense descriptor maps of P positions: the map itself when it is NHWC already (the repo's producer:
 // read in place), otherwise its transpose, made in `buf`
-int nhwc_map(LinetrHandle* h, hipStream_t st, const float* dense_desc, int dense_is_nhwc, int n_images, int P, float* buf,
-             const float*& nhwc) {
+// One launch for whatever the map's element type is: the float32 kernel KF32, or the half kernel KTYPED, an expression in E (f16_t or
+// bf16_t) in parentheses.  The arguments may use E as well: `(const E*)map`.
+#define LT_LAUNCH_BY_ELEM(type, KF32, KTYPED, grid, block, lds, st, ...)                                             \
+  do {                                                                                                               \
+    if ((type) == MT_F32) { typedef float E; (void)sizeof(E); hipLaunchKernelGGL(KF32, grid, block, lds, st, __VA_ARGS__); }       \
+    else if ((type) == MT_F16) { typedef f16_t E; (void)sizeof(E); hipLaunchKernelGGL(KTYPED, grid, block, lds, st, __VA_ARGS__); } \
+    else { typedef bf16_t E; (void)sizeof(E); hipLaunchKernelGGL(KTYPED, grid, block, lds, st, __VA_ARGS__); }                      \
+  } while (0)
+
+int nhwc_map(LinetrHandle* h, hipStream_t st, const void* dense_desc, const MapFormat& mf, int n_images, int P, void* buf,
+             const void*& nhwc) {
   nhwc = dense_desc;
-  if (dense_is_nhwc) return LINETR_OK;
-  ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * n_images * P * D * 4);
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, n_images), dim3(256), 0, st, dense_desc, buf, D, P);
+  if (mf.nhwc) return LINETR_OK;
+  ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * n_images * P * D * mf.esize);
+  if (mf.type == MT_F32)
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 64), D / 64, n_images), dim3(256), 0, st, (const float*)dense_desc, (float*)buf, D, P);
+  else   // halves move as they are: one kernel for both half types
+    hipLaunchKernelGGL(nchw_to_nhwc_half_kernel, dim3(cdiv(P, 64), D / 64, n_images), dim3(256), 0, st, (const uint16_t*)dense_desc,
+                       (uint16_t*)buf, D, P);
   LT_LAUNCH_CHECK();
   nhwc = buf;
   return LINETR_OK;
@@ -270,12 +283,12 @@ int nhwc_map(LinetrHandle* h, hipStream_t st, const float* dense_desc, int dense
 // The token front end of linetr_tokenize and linetr_describe: line_fill -> tokenize -> layout pass -> (out.desc) sample_desc.
 struct TokenFront {
   const LinetrLineRec* recs; int K, N; double td; int T;
-  const float *dense_desc, *dense_score;
-  int n_images, height, width, align_corners, dense_is_nhwc;
+  const void* dense_desc; const float* dense_score;
+  int n_images, height, width, align_corners; MapFormat mf;   // mf: layout and element type of dense_desc (one for all images)
   double clip_x, clip_y;               // end points are clipped to the caller's clip size (tokenize) or the map's own (describe)
   float *sublines, *resp, *angle_sub;  // the caller's tensors, or workspace where it asked for none
   int* s2l_g;                          // workspace: sub-line -> key-line of the batch
-  float* nhwc_buf;                     // workspace: the transposed map
+  void* nhwc_buf;                      // workspace: the transposed map (in the map's element type)
   bool map_always;                     // the layout pass runs without out.desc too (describe: the pooling kernel reads the map)
   double tokenize_bytes;               // what the `tokenize` profile class is charged
   // describe only: the compact list of real tokens, closed by one padding row per image (written by cdiv(n_pad_images, 64) more blocks)
@@ -285,7 +298,7 @@ struct TokenFront {
   const RaggedImage* tab = nullptr; int max_cells = 0; double cells = 0;
 };
 int token_front(LinetrHandle* h, hipStream_t st, const TokenFront& a, const LinetrTokens& out, const K2sTable& k2s, int32_t* d_sub2line,
-                const float*& nhwc) {
+                const void*& nhwc) {
   {
     ProfScope ps(h, st, "line_fill", 0, (double)a.K * 80 + (double)a.N * 8);
     if (a.tab)
@@ -312,26 +325,29 @@ int token_front(LinetrHandle* h, hipStream_t st, const TokenFront& a, const Line
   const int64_t ntok = (int64_t)a.N * a.T;
   nhwc = nullptr;
   if (a.tab) {   // every image's channel-last map is where its table entry says: the caller's own, or the copy this pass makes
-    if (!a.dense_is_nhwc) {
-      ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * a.cells * D * 4);
-      hipLaunchKernelGGL(nchw_to_nhwc_ragged_kernel, dim3(cdiv(a.max_cells, 64), D / 64, a.n_images), dim3(256), 0, st, a.tab, D);
+    if (!a.mf.nhwc) {
+      ProfScope ps(h, st, "nchw_to_nhwc", 0, 2.0 * a.cells * D * a.mf.esize);
+      if (a.mf.type == MT_F32)
+        hipLaunchKernelGGL(nchw_to_nhwc_ragged_kernel, dim3(cdiv(a.max_cells, 64), D / 64, a.n_images), dim3(256), 0, st, a.tab, D);
+      else
+        hipLaunchKernelGGL(nchw_to_nhwc_half_ragged_kernel, dim3(cdiv(a.max_cells, 64), D / 64, a.n_images), dim3(256), 0, st, a.tab, D);
       LT_LAUNCH_CHECK();
     }
     if (out.desc) {
       ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
-      hipLaunchKernelGGL(sample_desc_ragged_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, a.s2l_g, a.recs, ntok, a.T,
-                         a.tab, a.align_corners, out.desc);
+      LT_LAUNCH_BY_ELEM(a.mf.type, sample_desc_ragged_kernel, (sample_desc_ragged_typed_kernel<E>), dim3((unsigned)((ntok + 3) / 4)),
+                        dim3(256), 0, st, out.pnt, a.s2l_g, a.recs, ntok, a.T, a.tab, a.align_corners, out.desc);
       LT_LAUNCH_CHECK();
     }
     return LINETR_OK;
   }
   const int Hc = a.height / 8, Wc = a.width / 8;
   if (a.map_always || out.desc)
-    if (int e = nhwc_map(h, st, a.dense_desc, a.dense_is_nhwc, a.n_images, Hc * Wc, a.nhwc_buf, nhwc)) return e;
+    if (int e = nhwc_map(h, st, a.dense_desc, a.mf, a.n_images, Hc * Wc, a.nhwc_buf, nhwc)) return e;
   if (out.desc) {   // the reference's dense [N, T, 256] tensor
     ProfScope ps(h, st, "sample_desc", 0, (double)ntok * D * 4 * 2);
-    hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st, out.pnt, a.s2l_g, a.recs, ntok, a.T, nhwc,
-                       Hc, Wc, a.align_corners, out.desc);
+    LT_LAUNCH_BY_ELEM(a.mf.type, sample_desc_kernel, (sample_desc_typed_kernel<E>), dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0, st,
+                      out.pnt, a.s2l_g, a.recs, ntok, a.T, (const E*)nhwc, Hc, Wc, a.align_corners, out.desc);
     LT_LAUNCH_CHECK();
   }
   return LINETR_OK;
@@ -354,7 +370,7 @@ extern "C" int64_t linetr_tokenize_workspace_bytes(int32_t n_images, int32_t hei
 }
 
 extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, double td,
-                               int32_t T, const float* d_dense_desc, const float* d_dense_score, int32_t n_images,
+                               int32_t T, const void* d_dense_desc, const float* d_dense_score, int32_t n_images,
                                int32_t height, int32_t width, int32_t clip_height, int32_t clip_width, int32_t align_corners,
                                int32_t dense_is_nhwc, LinetrTokens out, int32_t* d_sub2line, void* d_ws, int64_t ws_bytes,
                                void* stream) {
@@ -365,8 +381,10 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
       !out.score || (out.desc && !d_dense_desc))
     return fail(LINETR_E_ARG, "tokenize: null pointer");
   if (T < 1 || T > 4096 || height % 8 || width % 8) return fail(LINETR_E_ARG, "tokenize: bad max_tokens / image size");
-  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(out.desc) || !aligned16(d_ws))
-    return fail(LINETR_E_ARG, "tokenize: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned");
+  MapFormat mf;
+  if (int e = map_format(dense_is_nhwc, "tokenize", mf)) return e;
+  if (!mf.aligned(d_dense_desc) || !aligned16(out.desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "tokenize: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned (a half channel-last map: 8-byte)");
   if (out.mat && n_images != 1) return fail(LINETR_E_ARG, "tokenize: mat_klines2sublines of several images: use linetr_describe (it has the sub-line prefix sums)");
   K2sTable k2s;
   if (int e = k2s_table(out, n_images, K, N, nullptr, k2s, "tokenize")) return e;
@@ -374,40 +392,47 @@ extern "C" int linetr_tokenize(LinetrHandle* h, const LinetrLineRec* d_recs, int
   if (ws_bytes < L.total) return fail(LINETR_E_WORKSPACE, "tokenize: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));   // no weights involved: without a handle the current device is used
-  TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, dense_is_nhwc,
+  TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, mf,
                (double)clip_width - 0.6, (double)clip_height - 0.6, out.sublines, out.resp, out.angle_sub};
-  f.nhwc_buf = (float*)((char*)d_ws + L.o_nhwc);
+  f.nhwc_buf = (char*)d_ws + L.o_nhwc;
   f.s2l_g = (int*)((char*)d_ws + L.o_s2l);
   f.map_always = false;
   f.tokenize_bytes = (double)N * T * 16;
-  const float* nhwc;
+  const void* nhwc;
   return token_front(h, st, f, out, k2s, d_sub2line, nhwc);
 }
 
 // sample_descriptors (models/line_process.py:86-98) on its own: n points of ONE image
-static int64_t nhwc_copy_bytes(int B, int Hc, int Wc, int dense_is_nhwc) { return dense_is_nhwc ? 0 : align_up(sz_mul(B, Hc, Wc, D * 4), 256); }
+// (a format the calls refuse: SZ_LIMIT, which the queries answer with 0 and no workspace satisfies)
+static int64_t nhwc_copy_bytes(int B, int Hc, int Wc, int dense_is_nhwc) {
+  MapFormat mf;
+  if (!map_format_ok(dense_is_nhwc, mf)) return SZ_LIMIT;
+  return mf.nhwc ? 0 : align_up(sz_mul(B, Hc, Wc, D * mf.esize), 256);
+}
 extern "C" int64_t linetr_sample_descriptors_workspace_bytes(int32_t Hc, int32_t Wc, int32_t dense_is_nhwc) {
   return sz_answer(nhwc_copy_bytes(1, Hc, Wc, dense_is_nhwc));
 }
 
-extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points, int64_t n, const float* d_dense_desc, int32_t Hc,
+extern "C" int linetr_sample_descriptors(LinetrHandle* h, const float* d_points, int64_t n, const void* d_dense_desc, int32_t Hc,
                                          int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc, float* d_out, void* d_ws,
                                          int64_t ws_bytes, void* stream) {
   if (n < 0 || Hc <= 0 || Wc <= 0) return fail(LINETR_E_ARG, "sample_descriptors: bad shape");
   if (n == 0) return LINETR_OK;
   if (!d_points || !d_dense_desc || !d_out) return fail(LINETR_E_ARG, "sample_descriptors: null pointer");
-  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(d_out) || !aligned16(d_ws))
-    return fail(LINETR_E_ARG, "sample_descriptors: a channel-last descriptor map, the output and the workspace must be 16-byte aligned");
-  if (ws_bytes < nhwc_copy_bytes(1, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
+  MapFormat mf;
+  if (int e = map_format(dense_is_nhwc, "sample_descriptors", mf)) return e;
+  if (!mf.aligned(d_dense_desc) || !aligned16(d_out) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "sample_descriptors: a channel-last descriptor map, the output and the workspace must be 16-byte aligned (a half channel-last map: 8-byte)");
+  if (ws_bytes < nhwc_copy_bytes(1, Hc, Wc, dense_is_nhwc) || (!mf.nhwc && !d_ws))
     return fail(LINETR_E_WORKSPACE, "sample_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  const float* nhwc;
-  if (int e = nhwc_map(h, st, d_dense_desc, dense_is_nhwc, 1, Hc * Wc, (float*)d_ws, nhwc)) return e;
+  const void* nhwc;
+  if (int e = nhwc_map(h, st, d_dense_desc, mf, 1, Hc * Wc, d_ws, nhwc)) return e;
   ProfScope ps(h, st, "sample_desc", 0, (double)n * D * 4 * 2);
   // T = 1 and no records: every point is its own "sub-line" of image 0
-  hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_points, (const int*)nullptr,
-                     (const LinetrLineRec*)nullptr, n, 1, nhwc, Hc, Wc, align_corners, d_out);
+  LT_LAUNCH_BY_ELEM(mf.type, sample_desc_kernel, (sample_desc_typed_kernel<E>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_points,
+                    (const int*)nullptr, (const LinetrLineRec*)nullptr, n, 1, (const E*)nhwc, Hc, Wc, align_corners, d_out);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
@@ -418,23 +443,27 @@ extern "C" int64_t linetr_point_descriptors_workspace_bytes(int32_t B, int32_t H
 }
 
 extern "C" int linetr_point_descriptors(LinetrHandle* h, const float* d_keypoints, const int32_t* d_cu_kp, int32_t B, int64_t n_total,
-                                        const float* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
+                                        const void* d_dense_desc, int32_t Hc, int32_t Wc, int32_t align_corners, int32_t dense_is_nhwc,
                                         float* d_desc_cn, void* d_ws, int64_t ws_bytes, void* stream) {
   if (B < 0 || n_total < 0 || Hc <= 0 || Wc <= 0 || n_total > INT32_MAX) return fail(LINETR_E_ARG, "point_descriptors: bad shape");
   if (B == 0 || n_total == 0) return LINETR_OK;
   if (!d_keypoints || !d_cu_kp || !d_dense_desc || !d_desc_cn) return fail(LINETR_E_ARG, "point_descriptors: null pointer");
-  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(d_ws))
-    return fail(LINETR_E_ARG, "point_descriptors: a channel-last descriptor map and the workspace must be 16-byte aligned");
-  if (ws_bytes < nhwc_copy_bytes(B, Hc, Wc, dense_is_nhwc) || (!dense_is_nhwc && !d_ws))
+  MapFormat mf;
+  if (int e = map_format(dense_is_nhwc, "point_descriptors", mf)) return e;
+  if (!mf.aligned(d_dense_desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "point_descriptors: a channel-last descriptor map and the workspace must be 16-byte aligned (a half channel-last map: 8-byte)");
+  if (ws_bytes < nhwc_copy_bytes(B, Hc, Wc, dense_is_nhwc) || (!mf.nhwc && !d_ws))
     return fail(LINETR_E_WORKSPACE, "point_descriptors: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (h) LT_HIP(hipSetDevice(h->device));
-  LT_HIP(allow_dynamic_lds<sp_kp_desc_kernel>((int)KP_DESC_LDS));   // 65 KiB
-  const float* nhwc;
-  if (int e = nhwc_map(h, st, d_dense_desc, dense_is_nhwc, B, Hc * Wc, (float*)d_ws, nhwc)) return e;
+  if (mf.type == MT_F32) LT_HIP(allow_dynamic_lds<sp_kp_desc_kernel>((int)KP_DESC_LDS));   // 65 KiB
+  else if (mf.type == MT_F16) LT_HIP(allow_dynamic_lds<sp_kp_desc_typed_kernel<f16_t>>((int)KP_DESC_LDS));
+  else LT_HIP(allow_dynamic_lds<sp_kp_desc_typed_kernel<bf16_t>>((int)KP_DESC_LDS));
+  const void* nhwc;
+  if (int e = nhwc_map(h, st, d_dense_desc, mf, B, Hc * Wc, d_ws, nhwc)) return e;
   ProfScope ps(h, st, "sp_kp_desc", 0, (double)n_total * D * 4 * 5);
-  hipLaunchKernelGGL(sp_kp_desc_kernel, dim3((unsigned)((n_total + KP_DESC_N - 1) / KP_DESC_N + B)), dim3(256), KP_DESC_LDS, st, d_keypoints,
-                     d_cu_kp, B, nhwc, Hc, Wc, align_corners, d_desc_cn);
+  LT_LAUNCH_BY_ELEM(mf.type, sp_kp_desc_kernel, (sp_kp_desc_typed_kernel<E>), dim3((unsigned)((n_total + KP_DESC_N - 1) / KP_DESC_N + B)),
+                    dim3(256), KP_DESC_LDS, st, d_keypoints, d_cu_kp, B, (const E*)nhwc, Hc, Wc, align_corners, d_desc_cn);
   LT_LAUNCH_CHECK();
   return LINETR_OK;
 }
@@ -516,7 +545,7 @@ struct TokenStage {            // how the token stage (word MLP + CLS pooling) i
   // dense path (linetr_forward): [N,T] tensors of the reference
   const float *pnt = nullptr, *score = nullptr, *desc = nullptr;
   // fused path (linetr_describe): compact real-token list + NHWC map
-  const float *cpnt = nullptr, *cscore = nullptr, *nhwc = nullptr;
+  const float *cpnt = nullptr, *cscore = nullptr; const void* nhwc = nullptr; int map_type = MT_F32;   // (the map's element type)
   const LinetrLineRec* recs = nullptr;
   const int* sub2line_g = nullptr;
   int64_t rows = 0;            // rows of the word-MLP GEMMs (N*T dense, n_real + n_images fused)
@@ -712,20 +741,23 @@ int cls_pool_launch(LinetrHandle* h, hipStream_t st, int kernel, const TokenStag
   if (kernel != POOLK_DENSE) {
     // algorithmic bytes: the dense map once (or the four taps of every token, whichever is less), one a4 row per token, the pooled rows out
     const double map_cells = ts.tab ? ts.cells : (double)n_images * ts.Hc * ts.Wc;   // ragged: summed over the table
-    const double tap_bytes = std::min(map_cells * D * 4, (double)rows * D * 4 * 4);
+    const double esize = ts.map_type == MT_F32 ? 4 : 2;
+    const double tap_bytes = std::min(map_cells * D * esize, (double)rows * D * esize * 4);
     ProfScope ps(h, st, "cls_pool_online", 2.0 * rows * (2.0 * HEADS * D * 2), tap_bytes + (double)rows * D * 4 + (double)N * HEADS * POOLW * 4);
     if (ts.tab && kernel == POOLK_SPLIT4)
-      hipLaunchKernelGGL(cls_pool_online_ragged_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         a4, ts.first_pad, N, T, ts.tab, ts.align_corners, h->pool, pooled, 0);
+      LT_LAUNCH_BY_ELEM(ts.map_type, cls_pool_online_ragged_kernel<4>, (cls_pool_online_ragged_typed_kernel<4, E>), dim3(N), dim3(256), 0, st,
+                        ts.recs, ts.sub2line_g, ts.cpnt, a4, ts.first_pad, N, T, ts.tab, ts.align_corners, h->pool, pooled, 0);
     else if (ts.tab)
-      hipLaunchKernelGGL(cls_pool_online_ragged_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         a4, ts.first_pad, N, T, ts.tab, ts.align_corners, h->pool, pooled, kernel == POOLK_ONLINE_REV ? 1 : 0);
+      LT_LAUNCH_BY_ELEM(ts.map_type, cls_pool_online_ragged_kernel<1>, (cls_pool_online_ragged_typed_kernel<1, E>), dim3(cdiv(N, 4)), dim3(256),
+                        0, st, ts.recs, ts.sub2line_g, ts.cpnt, a4, ts.first_pad, N, T, ts.tab, ts.align_corners, h->pool, pooled,
+                        kernel == POOLK_ONLINE_REV ? 1 : 0);
     else if (kernel == POOLK_SPLIT4)
-      hipLaunchKernelGGL(cls_pool_online_kernel<4>, dim3(N), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, pooled, 0);
+      LT_LAUNCH_BY_ELEM(ts.map_type, cls_pool_online_kernel<4>, (cls_pool_online_typed_kernel<4, E>), dim3(N), dim3(256), 0, st, ts.recs,
+                        ts.sub2line_g, ts.cpnt, a4, ts.first_pad, N, T, (const E*)ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, pooled, 0);
     else
-      hipLaunchKernelGGL(cls_pool_online_kernel<1>, dim3(cdiv(N, 4)), dim3(256), 0, st, ts.recs, ts.sub2line_g, ts.cpnt,
-                         a4, ts.first_pad, N, T, ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool, pooled, kernel == POOLK_ONLINE_REV ? 1 : 0);
+      LT_LAUNCH_BY_ELEM(ts.map_type, cls_pool_online_kernel<1>, (cls_pool_online_typed_kernel<1, E>), dim3(cdiv(N, 4)), dim3(256), 0, st,
+                        ts.recs, ts.sub2line_g, ts.cpnt, a4, ts.first_pad, N, T, (const E*)ts.nhwc, ts.Hc, ts.Wc, ts.align_corners, h->pool,
+                        pooled, kernel == POOLK_ONLINE_REV ? 1 : 0);
     LT_LAUNCH_CHECK();
   } else {
     ProfScope ps(h, st, "cls_pool", 2.0 * rows * (2.0 * HEADS * D * 2), (double)rows * D * 8);
@@ -1004,13 +1036,13 @@ extern "C" int linetr_forward_train(LinetrHandle* h, const LinetrTokens* tok, co
 // =============================================================================================
 
 namespace {
-struct DescWs { float *nhwc, *cpnt, *cscore, *sublines, *resp, *angle_sub; int* s2l_g; int64_t fwd_off, total; };
+struct DescWs { void* nhwc; float *cpnt, *cscore, *sublines, *resp, *angle_sub; int* s2l_g; int64_t fwd_off, total; };
 DescWs desc_layout(int n_images, int height, int width, int N, int64_t rows, char* base) {
   DescWs d;
   int64_t off = 0;
   auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
   const int64_t P = (int64_t)(height / 8) * (width / 8);
-  d.nhwc = (float*)take(n_images * P * D * 4);
+  d.nhwc = take(n_images * P * D * 4);   // (sized for float32: a half copy fills half of it)
   d.cpnt = (float*)take(rows * 8);
   d.cscore = (float*)take(rows * 4);
   d.sublines = (float*)take((int64_t)N * 16);
@@ -1049,10 +1081,10 @@ int describe_launch(LinetrHandle* h, hipStream_t st, TokenFront f, const DescWs&
   f.map_always = true;
   f.tokenize_bytes = (double)n_real * 16;
   f.cpnt = dw.cpnt; f.cscore = dw.cscore; f.n_pad_images = n_images; f.first_pad = n_real;
-  const float* nhwc_map;
+  const void* nhwc_map;
   if (int e = token_front(h, st, f, out, k2s, d_sub2line, nhwc_map)) return e;
   TokenStage ts;
-  ts.cpnt = dw.cpnt; ts.cscore = dw.cscore; ts.nhwc = nhwc_map; ts.recs = f.recs; ts.sub2line_g = dw.s2l_g;
+  ts.cpnt = dw.cpnt; ts.cscore = dw.cscore; ts.nhwc = nhwc_map; ts.map_type = f.mf.type; ts.recs = f.recs; ts.sub2line_g = dw.s2l_g;
   ts.rows = rows; ts.first_pad = n_real; ts.Hc = f.height / 8; ts.Wc = f.width / 8; ts.align_corners = f.align_corners;
   ts.tab = f.tab; ts.cells = f.cells;
   ts.pipe = pipe;
@@ -1064,7 +1096,7 @@ int describe_launch(LinetrHandle* h, hipStream_t st, TokenFront f, const DescWs&
 // cut points; `st` is the first stage's stream.
 int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, int64_t n_real,
                   const int32_t* h_cu, const int32_t* d_cu, int32_t n_images, double td, int32_t T,
-                  const float* d_dense_desc, const float* d_dense_score, int32_t height, int32_t width,
+                  const void* d_dense_desc, const float* d_dense_score, int32_t height, int32_t width,
                   int32_t align_corners, int32_t dense_is_nhwc, const LinetrTokens& out, int32_t* d_sub2line,
                   float* d_line_desc, void* d_ws, int64_t ws_bytes, hipStream_t st, PipeStages* pipe) {
   if (!h) return fail(LINETR_E_ARG, "describe: null handle");
@@ -1076,8 +1108,10 @@ int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32
   if (T < 1 || T > 4096 || height % 8 || width % 8) return fail(LINETR_E_ARG, "describe: bad max_tokens / image size");
   if (n_real < N || n_real > (int64_t)N * T) return fail(LINETR_E_ARG, "describe: implausible real-token count");
   if (out.desc && !out.pnt) return fail(LINETR_E_ARG, "describe: out.desc requires out.pnt");
-  if ((dense_is_nhwc && !aligned16(d_dense_desc)) || !aligned16(out.desc) || !aligned16(d_ws))
-    return fail(LINETR_E_ARG, "describe: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned");
+  MapFormat mf;
+  if (int e = map_format(dense_is_nhwc, "describe", mf)) return e;
+  if (!mf.aligned(d_dense_desc) || !aligned16(out.desc) || !aligned16(d_ws))
+    return fail(LINETR_E_ARG, "describe: a channel-last descriptor map, out.desc and the workspace must be 16-byte aligned (a half channel-last map: 8-byte)");
   K2sTable k2s;
   if (int e = k2s_table(out, n_images, K, N, h_cu, k2s, "describe")) return e;
   if (ws_bytes < linetr_describe_workspace_bytes(h, n_images, height, width, N, n_real))
@@ -1086,7 +1120,7 @@ int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32
   if (rows > INT32_MAX / 8) return fail(LINETR_E_ARG, "describe: batch too large");
   LT_HIP(hipSetDevice(h->device));
   DescWs dw = desc_layout(n_images, height, width, N, rows, (char*)d_ws);
-  TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, dense_is_nhwc,
+  TokenFront f{d_recs, K, N, td, T, d_dense_desc, d_dense_score, n_images, height, width, align_corners, mf,
                (double)width - 0.6, (double)height - 0.6};
   return describe_launch(h, st, f, dw, (char*)d_ws + dw.fwd_off, out, k2s, d_sub2line, d_line_desc, h_cu, d_cu, n_real, pipe);
 }
@@ -1095,26 +1129,27 @@ int describe_impl(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32
 // map.  The ONE function that lays it out and the one that makes the table: the size query passes no table, the entry point the
 // host copy it uploads (`base`: where the workspace is on the device).
 struct RaggedFront { int64_t o_tab, total; int max_cells; double cells; };
-RaggedFront ragged_front(const LinetrImage* imgs, int n_images, int dense_is_nhwc, char* base, RaggedImage* tab) {
+RaggedFront ragged_front(const LinetrImage* imgs, int n_images, const MapFormat& mf, char* base, RaggedImage* tab) {
   RaggedFront L{};
   Carve c;
   L.o_tab = c.take(sz_mul(n_images, sizeof(RaggedImage)));
   for (int i = 0; i < n_images; ++i) {
     const LinetrImage& im = imgs[i];
     const int Hc = im.height / 8, Wc = im.width / 8;
-    const int64_t o_copy = dense_is_nhwc ? 0 : c.take(sz_mul(Hc, Wc, D * 4));
+    const int64_t o_copy = mf.nhwc ? 0 : c.take(sz_mul(Hc, Wc, D * mf.esize));
     L.max_cells = std::max(L.max_cells, Hc * Wc);
     L.cells += (double)Hc * Wc;
     if (tab)
-      tab[i] = RaggedImage{dense_is_nhwc ? im.d_dense_desc : (const float*)(base + o_copy), im.d_dense_score,
-                           dense_is_nhwc ? nullptr : im.d_dense_desc, im.height, im.width, Hc, Wc, im.token_distance,
+      tab[i] = RaggedImage{mf.nhwc ? im.d_dense_desc : (const void*)(base + o_copy), im.d_dense_score,
+                           mf.nhwc ? nullptr : im.d_dense_desc, im.height, im.width, Hc, Wc, im.token_distance,
                            (double)im.width - 0.6, (double)im.height - 0.6};
   }
   L.total = c.o;
   return L;
 }
 // what the table must be like for ragged_front's arithmetic to mean anything (the query answers 0 otherwise, the entry point refuses)
-int check_images(const LinetrImage* imgs, int n_images, int dense_is_nhwc) {
+int check_images(const LinetrImage* imgs, int n_images, int dense_is_nhwc, MapFormat& mf) {
+  if (int e = map_format(dense_is_nhwc, "describe_ragged", mf)) return e;
   if (!imgs || n_images < 1) return fail(LINETR_E_ARG, "describe_ragged: a NULL or empty image table");
   for (int i = 0; i < n_images; ++i) {
     const LinetrImage& im = imgs[i];
@@ -1122,8 +1157,8 @@ int check_images(const LinetrImage* imgs, int n_images, int dense_is_nhwc) {
       return fail(LINETR_E_ARG, "describe_ragged: image %d is %d x %d, not a positive multiple of 8 each way", i, im.height, im.width);
     if ((int64_t)(im.height / 8) * (im.width / 8) > INT32_MAX / D) return fail(LINETR_E_ARG, "describe_ragged: image %d is too large", i);
     if (!im.d_dense_desc || !im.d_dense_score) return fail(LINETR_E_ARG, "describe_ragged: image %d has a NULL map", i);
-    if (dense_is_nhwc && !aligned16(im.d_dense_desc))
-      return fail(LINETR_E_ARG, "describe_ragged: the channel-last descriptor map of image %d is not 16-byte aligned", i);
+    if (!mf.aligned(im.d_dense_desc))
+      return fail(LINETR_E_ARG, "describe_ragged: the channel-last descriptor map of image %d is not 16-byte aligned (a half channel-last map: 8-byte; an NCHW map: its element)", i);
     if (!(im.token_distance > 0)) return fail(LINETR_E_ARG, "describe_ragged: image %d: token_distance must be > 0", i);
   }
   return 0;
@@ -1131,16 +1166,17 @@ int check_images(const LinetrImage* imgs, int n_images, int dense_is_nhwc) {
 }  // namespace
 
 // the whole workspace of a checked table, saturating (SZ_LIMIT: a shape no call serves): what the query answers and the call compares
-static int64_t describe_ragged_total(const LinetrHandle* h, const LinetrImage* h_images, int n_images, int dense_is_nhwc, int N, int64_t n_real) {
+static int64_t describe_ragged_total(const LinetrHandle* h, const LinetrImage* h_images, int n_images, const MapFormat& mf, int N, int64_t n_real) {
   const int64_t rows = n_real + n_images;
-  return sz_add(ragged_front(h_images, n_images, dense_is_nhwc, nullptr, nullptr).total,
+  return sz_add(ragged_front(h_images, n_images, mf, nullptr, nullptr).total,
                 desc_layout(0, 0, 0, std::max(N, 1), rows, nullptr).total, fwd_layout(h, std::max(N, 1), rows, n_images, nullptr).total);
 }
 
 extern "C" int64_t linetr_describe_ragged_workspace_bytes(const LinetrHandle* h, const LinetrImage* h_images, int32_t n_images,
                                                           int32_t dense_is_nhwc, int32_t N, int64_t n_real) {
-  if (!h || check_images(h_images, n_images, dense_is_nhwc)) return -1;
-  return sz_answer(describe_ragged_total(h, h_images, n_images, dense_is_nhwc, N, n_real));
+  MapFormat mf;
+  if (!h || check_images(h_images, n_images, dense_is_nhwc, mf)) return -1;
+  return sz_answer(describe_ragged_total(h, h_images, n_images, mf, N, n_real));
 }
 
 extern "C" int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_recs, const LinetrLineRec* h_recs, int32_t K, int32_t N,
@@ -1151,7 +1187,8 @@ extern "C" int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_re
   if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "describe_ragged: a training-mode handle (bn_batch_stats = 1) runs linetr_forward_train only");
   if (int e = check_cu(h_cu, n_images)) return e;
   if (h_cu[n_images] != N) return fail(LINETR_E_ARG, "describe_ragged: cu_sub does not end at N");
-  if (int e = check_images(h_images, n_images, dense_is_nhwc)) return e;
+  MapFormat mf;
+  if (int e = check_images(h_images, n_images, dense_is_nhwc, mf)) return e;
   if (K <= 0 || N <= 0) return LINETR_OK;
   if (!d_recs || !d_line_desc || !d_ws) return fail(LINETR_E_ARG, "describe_ragged: null pointer");
   if (T < 1 || T > 4096) return fail(LINETR_E_ARG, "describe_ragged: bad max_tokens");
@@ -1165,7 +1202,7 @@ extern "C" int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_re
       return fail(LINETR_E_ARG, "describe_ragged: record %d belongs to image %d, outside the table of %d", k, h_recs[k].image, n_images);
   K2sTable k2s;
   if (int e = k2s_table(out, n_images, K, N, h_cu, k2s, "describe_ragged")) return e;
-  if (ws_bytes < describe_ragged_total(h, h_images, n_images, dense_is_nhwc, N, n_real))   // (a saturated total refuses every workspace)
+  if (ws_bytes < describe_ragged_total(h, h_images, n_images, mf, N, n_real))   // (a saturated total refuses every workspace)
     return fail(LINETR_E_WORKSPACE, "describe_ragged: workspace too small");
   const int64_t rows = n_real + n_images;
   if (rows > INT32_MAX / 8) return fail(LINETR_E_ARG, "describe_ragged: batch too large");
@@ -1175,13 +1212,13 @@ extern "C" int linetr_describe_ragged(LinetrHandle* h, const LinetrLineRec* d_re
   int slot = -1;
   RaggedImage* tab = (RaggedImage*)staging_ring().acquire((size_t)n_images * sizeof(RaggedImage), &slot);
   if (!tab) return fail(LINETR_E_HIP, "describe_ragged: pinned staging allocation failed");
-  const RaggedFront rf = ragged_front(h_images, n_images, dense_is_nhwc, (char*)d_ws, tab);
+  const RaggedFront rf = ragged_front(h_images, n_images, mf, (char*)d_ws, tab);
   RaggedImage* d_tab = (RaggedImage*)((char*)d_ws + rf.o_tab);
   LT_HIP(hipMemcpyAsync(d_tab, tab, (size_t)n_images * sizeof(RaggedImage), hipMemcpyHostToDevice, st));
   if (int e = staging_ring().commit(slot, st)) return e;
   char* rest = (char*)d_ws + rf.total;
   DescWs dw = desc_layout(0, 0, 0, N, rows, rest);
-  TokenFront f{d_recs, K, N, 0.0, T, nullptr, nullptr, n_images, 0, 0, align_corners, dense_is_nhwc, 0.0, 0.0};
+  TokenFront f{d_recs, K, N, 0.0, T, nullptr, nullptr, n_images, 0, 0, align_corners, mf, 0.0, 0.0};
   f.tab = d_tab; f.max_cells = rf.max_cells; f.cells = rf.cells;
   return describe_launch(h, st, f, dw, rest + dw.fwd_off, out, k2s, d_sub2line, d_line_desc, h_cu, d_cu, n_real, nullptr);
 }
@@ -1229,7 +1266,7 @@ PipePlan pipe_plan(const LinetrHandle* h, int n_slots) {
 
 extern "C" int linetr_describe(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, int64_t n_real,
                                const int32_t* h_cu, const int32_t* d_cu, int32_t n_images, double td, int32_t T,
-                               const float* d_dense_desc, const float* d_dense_score, int32_t height, int32_t width,
+                               const void* d_dense_desc, const float* d_dense_score, int32_t height, int32_t width,
                                int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out, int32_t* d_sub2line,
                                float* d_line_desc, void* d_ws, int64_t ws_bytes, void* stream) {
   return describe_impl(h, d_recs, K, N, n_real, h_cu, d_cu, n_images, td, T, d_dense_desc, d_dense_score, height, width, align_corners,
@@ -1240,7 +1277,7 @@ extern "C" int32_t linetr_pipeline_max_slots(void) { return LinetrHandle::PIPE_S
 
 extern "C" int linetr_describe_submit(LinetrHandle* h, const LinetrLineRec* d_recs, int32_t K, int32_t N, int64_t n_real,
                                       const int32_t* h_cu, const int32_t* d_cu, int32_t n_images, double td, int32_t T,
-                                      const float* d_dense_desc, const float* d_dense_score, int32_t height, int32_t width,
+                                      const void* d_dense_desc, const float* d_dense_score, int32_t height, int32_t width,
                                       int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out, int32_t* d_sub2line,
                                       float* d_line_desc, void* d_ws, int64_t ws_bytes, int32_t slot, int32_t n_slots, void* stream) {
   if (!h) return fail(LINETR_E_ARG, "describe_submit: null handle");
@@ -1568,7 +1605,7 @@ extern "C" int linetr_debug_bn_train(LinetrHandle* h, int32_t which, float* d_z,
 
 extern "C" int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const LinetrLineRec* d_recs, int32_t K, const int32_t* d_sub2line,
                                      int32_t N, int32_t T, const float* d_cpnt, const float* d_a4, int64_t first_pad, int32_t n_images,
-                                     const float* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
+                                     const void* d_map, int32_t dense_is_nhwc, int32_t Hc, int32_t Wc, int32_t align_corners,
                                      const float* d_desc_dense, float* d_pooled, int32_t* kernel_used, void* stream) {
   if (!h) return fail(LINETR_E_ARG, "debug_cls_pool: null handle");
   if (h->cfg.bn_batch_stats) return fail(LINETR_E_ARG, "debug_cls_pool: a training-mode handle (bn_batch_stats = 1) is not served");
@@ -1595,8 +1632,10 @@ extern "C" int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const Line
   if (!d_recs || !d_sub2line || !d_cpnt || !d_map) return fail(LINETR_E_ARG, "debug_cls_pool: null tensor");
   if (K < 1 || n_images < 1 || Hc < 1 || Wc < 1 || first_pad < 0 || first_pad > INT32_MAX / 8 || (int64_t)n_images * Hc * Wc > INT32_MAX / D)
     return fail(LINETR_E_ARG, "debug_cls_pool: bad shape");
-  if ((uintptr_t)d_recs % 8 || ((uintptr_t)d_sub2line | (uintptr_t)d_cpnt | (uintptr_t)d_map) % 4 || (dense_is_nhwc && (uintptr_t)d_map % 16))
-    return fail(LINETR_E_ARG, "debug_cls_pool: misaligned tensor (records 8 bytes, an NHWC map 16, the others 4)");
+  MapFormat mf;
+  if (int e = map_format(dense_is_nhwc, "debug_cls_pool", mf)) return e;
+  if ((uintptr_t)d_recs % 8 || ((uintptr_t)d_sub2line | (uintptr_t)d_cpnt) % 4 || !mf.aligned(d_map) || (mf.type == MT_F32 && (uintptr_t)d_map % 4))
+    return fail(LINETR_E_ARG, "debug_cls_pool: misaligned tensor (records 8 bytes, an NHWC map 16 (half: 8), an NCHW map its element, the others 4)");
   LT_HIP(hipSetDevice(h->device));
   {  // everything the kernel indexes with comes from the caller: checked on the host first
     std::vector<LinetrLineRec> recs(K);
@@ -1615,11 +1654,12 @@ extern "C" int linetr_debug_cls_pool(LinetrHandle* h, int32_t kernel, const Line
       if (r.image < 0 || r.image >= n_images) return fail(LINETR_E_ARG, "debug_cls_pool: key-line %d's image %d outside [0, %d)", s2l[n], r.image, n_images);
     }
   }
-  float* buf = nullptr;   // the transposed map of an NCHW caller, freed below
-  if (!dense_is_nhwc) LT_HIP(hipMalloc((void**)&buf, (size_t)n_images * Hc * Wc * D * sizeof(float)));
+  void* buf = nullptr;   // the transposed map of an NCHW caller, freed below
+  if (!mf.nhwc) LT_HIP(hipMalloc(&buf, (size_t)n_images * Hc * Wc * D * mf.esize));
   ts.cpnt = d_cpnt; ts.recs = d_recs; ts.sub2line_g = d_sub2line; ts.rows = first_pad + n_images; ts.first_pad = first_pad;
   ts.Hc = Hc; ts.Wc = Wc; ts.align_corners = align_corners;
-  int e = nhwc_map(h, st, d_map, dense_is_nhwc, n_images, Hc * Wc, buf, ts.nhwc);
+  ts.map_type = mf.type;
+  int e = nhwc_map(h, st, d_map, mf, n_images, Hc * Wc, buf, ts.nhwc);
   if (!e) e = cls_pool_launch(h, st, kernel, ts, n_images, N, T, d_a4, d_pooled);
   (void)hipStreamSynchronize(st);
   if (buf) (void)hipFree(buf);

@@ -1146,6 +1146,7 @@ bool fs_dims_ok(int B, int height, int width) {
 }  // namespace
 
 extern "C" int64_t linetr_fixed_size_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t dense_is_nhwc) {
+  if (dense_is_nhwc > 0 && (dense_is_nhwc & ~0xff)) return 0;   // float32 maps only (below): what the call refuses needs no workspace
   return fs_dims_ok(n_images, height, width) ? fs_layout(n_images, height, width, dense_is_nhwc).total : 0;
 }
 
@@ -1156,6 +1157,8 @@ extern "C" int linetr_fixed_size(LinetrHandle* h, const LinetrLineRec* d_recs, c
                                  int32_t pseudo_clip_width, int32_t align_corners, int32_t dense_is_nhwc, LinetrTokens out,
                                  int32_t* d_num_klns, int32_t* d_num_slns, void* d_ws, int64_t ws_bytes, void* stream) {
   // every refusal comes before the first launch
+  if (dense_is_nhwc > 0 && (dense_is_nhwc & ~0xff))   // the training samples are float32: a half map read as float32 would be silent garbage
+    return fail(LINETR_E_ARG, "fixed_size: dense_is_nhwc = 0x%x: the maps must be float32 (no LINETR_DENSE_F16 / LINETR_DENSE_BF16 here)", (unsigned)dense_is_nhwc);
   if (!fs_dims_ok(B, height, width)) return fail(LINETR_E_ARG, "fixed_size: bad shape B=%d height=%d width=%d", B, height, width);
   if (M < 1 || M > FS_MAX_M || T < 1 || T > 4096 || !(td > 0)) return fail(LINETR_E_ARG, "fixed_size: bad max_sublines / max_tokens / token_distance");
   if (((int64_t)B * M * T + 3) / 4 > INT32_MAX) return fail(LINETR_E_ARG, "fixed_size: B * max_sublines * max_tokens beyond 2^33 tokens");

@@ -2,10 +2,12 @@
 // guard.  The including file defines
 //   LT_POOL_KERNEL       the kernel's name
 //   LT_POOL_MAP_PARAMS   the parameters that say where the images' channel-last descriptor maps are
-//   LT_POOL_MAP(image)   statements that define `const float* nhwc_img` and `Hc`, `Wc` of the sub-line's image from them
+//   LT_POOL_MAP(image)   statements that define `const PoolElem* nhwc_img` and `Hc`, `Wc` of the sub-line's image from them, and
+//                        PoolElem itself: the map's element type (float, f16_t or bf16_t)
+//   LT_POOL_TPARAMS      further template parameters behind SPLIT (empty for the float32 kernels; `, class E` for the half ones)
 // The uniform instantiation expands to the very text the kernel had before the ragged one existed, so it compiles to the same code
 // (the shared-body-through-an-inlined-function form moved its FMA contraction and with it the last bits of the pooled rows).
-template <int SPLIT>
+template <int SPLIT LT_POOL_TPARAMS>
 __global__ __launch_bounds__(256, 3) void LT_POOL_KERNEL(   // 3 = waves per SIMD the register allocation must allow
     const LinetrLineRec* __restrict__ recs, const int* __restrict__ sub2line_g, const float* __restrict__ cpnt,
     const float* __restrict__ a4, int64_t first_pad, int N, int T, LT_POOL_MAP_PARAMS,
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256, 3) void LT_POOL_KERNEL(   // 3 = waves per SIM
     const int64_t row = row_of(jj < ntk ? jj : ntk - 1);
     tap_coords(cpnt[row * 2], cpnt[row * 2 + 1], Hc, Wc, align_corners, t_off, t_w);
   };
-  auto issue = [&](int jj, TapSet& t, f32x4& a) {
+  auto issue = [&](int jj, TapSetT<PoolElem>& t, f32x4& a) {
     int off[4];
     float wt[4];
 #pragma unroll
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256, 3) void LT_POOL_KERNEL(   // 3 = waves per SIM
     taps_load(nhwc_img, off, wt, lane, t);
     a = *reinterpret_cast<const f32x4*>(a4 + row_of(jj) * D + lane * 4);
   };
-  TapSet cur, nxt;
+  TapSetT<PoolElem> cur, nxt;
   f32x4 a_cur, a_nxt;
   const int jj0 = SPLIT == 1 ? 0 : wv;
   fill_taps(0);

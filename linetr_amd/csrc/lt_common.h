@@ -27,6 +27,47 @@ constexpr int BN_MAX_CHANNELS = 512;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Element types of a dense descriptor map or a raw head output (LINETR_DENSE_F16 / LINETR_DENSE_BF16, include/linetr_hip.h).  Arithmetic
+// is float32 throughout: Elem<E>::widen is exact (fp16 subnormals included), Elem<E>::narrow rounds to nearest-even as torch's
+// .half() / .bfloat16() do.  raw4 is what a lane holds of its 4 channels between the load and the first use: 16 bytes of float32, 8 of a
+// half type.
+typedef _Float16 f16_t;
+struct bf16_t { uint16_t bits; };
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+enum MapType { MT_F32 = 0, MT_F16 = 1, MT_BF16 = 2 };
+
+template <class E> struct Elem;
+template <> struct Elem<float> {
+  typedef f32x4 raw4;
+  static __device__ __forceinline__ f32x4 widen(f32x4 v) { return v; }
+  static __device__ __forceinline__ float widen(float v) { return v; }
+  static __device__ __forceinline__ float narrow(float v) { return v; }
+};
+template <> struct Elem<f16_t> {
+  typedef f16x4 raw4;
+  static __device__ __forceinline__ f32x4 widen(f16x4 v) { return __builtin_convertvector(v, f32x4); }
+  static __device__ __forceinline__ float widen(f16_t v) { return (float)v; }
+  static __device__ __forceinline__ f16_t narrow(float v) { return (f16_t)v; }
+};
+template <> struct Elem<bf16_t> {
+  typedef u16x4 raw4;
+  static __device__ __forceinline__ float widen(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v.bits << 16); }
+  static __device__ __forceinline__ f32x4 widen(u16x4 v) {
+    return f32x4{widen(bf16_t{v[0]}), widen(bf16_t{v[1]}), widen(bf16_t{v[2]}), widen(bf16_t{v[3]})};
+  }
+  static __device__ __forceinline__ bf16_t narrow(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return bf16_t{0x7fc0};            // NaN (torch's quiet NaN)
+    return bf16_t{(uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};    // round to nearest, ties to even
+  }
+};
+// this lane's 4 consecutive elements, `p` on the 4-element grid (16 bytes of float32, 8 of a half type): one load
+template <class E>
+__device__ __forceinline__ typename Elem<E>::raw4 load_raw4(const E* p) {
+  return *reinterpret_cast<const typename Elem<E>::raw4*>(p);
+}
+
 // The shipped library (liblinetr_hip.so) is built WITHOUT LINETR_EXPERIMENTS: no tuning switches, none of the kernels that
 // were measured and lost.  `python -m linetr_amd.build --experiments` builds liblinetr_hip_experiments.so from the same sources
 // plus experiments/csrc: the stream-K tail, the 256x256 tile, the fused signature MLP, the split-tile / LDS-DMA path, the
@@ -89,6 +130,31 @@ inline int64_t sz_answer(int64_t total) { return total >= SZ_LIMIT || total < 0 
 inline int64_t align_up(int64_t v, int64_t a) { return (v < 0 || v > SZ_LIMIT - a) ? SZ_LIMIT : (v + a - 1) / a * a; }
 // What every entry point asks of a pointer its kernels access with 16-byte vectors (NULL passes: an absent optional pointer).
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// An entry point's `dense_is_nhwc` argument taken apart (LINETR_DENSE_F16 / LINETR_DENSE_BF16, include/linetr_hip.h): layout, element
+// type, element size, and the alignment the kernels need of the caller's map (float32 NHWC 16 bytes and a float32 NCHW map anywhere, as
+// ever; a half NHWC map 8, a lane's 4 channels; a half NCHW map its element's 2, the layout pass chooses its vector path row by row).
+// Every value below 0x100 means what it always meant, the negative ones included: non-zero = NHWC float32.
+struct MapFormat {
+  bool nhwc = false; int type = MT_F32; int esize = 4;
+  bool aligned(const void* p) const {
+    const int need = nhwc ? 4 * esize : type == MT_F32 ? 1 : esize;
+    return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(need - 1)) == 0;
+  }
+};
+inline bool map_format_ok(int dense_is_nhwc, MapFormat& f) {
+  if (dense_is_nhwc < 0) { f = MapFormat{}; f.nhwc = true; return true; }
+  const int t = dense_is_nhwc & (LINETR_DENSE_F16 | LINETR_DENSE_BF16);
+  if ((dense_is_nhwc & ~0x3ff) || t == (LINETR_DENSE_F16 | LINETR_DENSE_BF16)) return false;
+  f.nhwc = (dense_is_nhwc & 0xff) != 0;
+  f.type = t == LINETR_DENSE_F16 ? MT_F16 : t == LINETR_DENSE_BF16 ? MT_BF16 : MT_F32;
+  f.esize = t ? 2 : 4;
+  return true;
+}
+inline int map_format(int dense_is_nhwc, const char* who, MapFormat& f) {
+  if (map_format_ok(dense_is_nhwc, f)) return 0;
+  return fail(LINETR_E_ARG, "%s: dense_is_nhwc = 0x%x: at most one of LINETR_DENSE_F16 / LINETR_DENSE_BF16 and no higher bit", who,
+              (unsigned)dense_is_nhwc);
+}
 // A workspace carved into 256-byte aligned segments: take(bytes) is the next segment's offset, `o` what has been handed out so far.
 struct Carve {
   int64_t o = 0;

@@ -333,23 +333,53 @@ __global__ __launch_bounds__(256) void cls_pool_kernel(const float* __restrict__
 // The kernel's text is lt_cls_pool_online_body.h, included once per geometry.  All images of one size: their channel-last maps lie back to
 // back, image i at i * Hc * Wc * 256 floats.
 #define LT_POOL_KERNEL cls_pool_online_kernel
+#define LT_POOL_TPARAMS
 #define LT_POOL_MAP_PARAMS const float* __restrict__ nhwc, int Hc, int Wc
-#define LT_POOL_MAP(image) const float* nhwc_img = nhwc + (int64_t)image * Hc * Wc * D;
+#define LT_POOL_MAP(image) typedef float PoolElem; const float* nhwc_img = nhwc + (int64_t)image * Hc * Wc * D;
 #include "lt_cls_pool_online_body.h"
 #undef LT_POOL_KERNEL
+#undef LT_POOL_TPARAMS
+#undef LT_POOL_MAP_PARAMS
+#undef LT_POOL_MAP
+
+// the same on a half map (E = f16_t or bf16_t): 8 bytes per lane and tap, widened where the tap set is first used
+#define LT_POOL_KERNEL cls_pool_online_typed_kernel
+#define LT_POOL_TPARAMS , class E
+#define LT_POOL_MAP_PARAMS const E* __restrict__ nhwc, int Hc, int Wc
+#define LT_POOL_MAP(image) typedef E PoolElem; const E* nhwc_img = nhwc + (int64_t)image * Hc * Wc * D;
+#include "lt_cls_pool_online_body.h"
+#undef LT_POOL_KERNEL
+#undef LT_POOL_TPARAMS
 #undef LT_POOL_MAP_PARAMS
 #undef LT_POOL_MAP
 
 // ragged (linetr_describe_ragged): the sub-line's image has its own map and size in the image table.  The entry is wave-uniform (a wave
 // works on one sub-line): it is loaded once per wave, through the scalar unit.
 #define LT_POOL_KERNEL cls_pool_online_ragged_kernel
+#define LT_POOL_TPARAMS
 #define LT_POOL_MAP_PARAMS const RaggedImage* __restrict__ tab
 #define LT_POOL_MAP(image)                                                  \
+  typedef float PoolElem;                                                   \
   const RaggedImage& im_ = tab[__builtin_amdgcn_readfirstlane(image)];      \
-  const float* nhwc_img = im_.nhwc;                                         \
+  const float* nhwc_img = (const float*)im_.nhwc;                           \
   const int Hc = im_.Hc, Wc = im_.Wc;
 #include "lt_cls_pool_online_body.h"
 #undef LT_POOL_KERNEL
+#undef LT_POOL_TPARAMS
+#undef LT_POOL_MAP_PARAMS
+#undef LT_POOL_MAP
+
+#define LT_POOL_KERNEL cls_pool_online_ragged_typed_kernel
+#define LT_POOL_TPARAMS , class E
+#define LT_POOL_MAP_PARAMS const RaggedImage* __restrict__ tab
+#define LT_POOL_MAP(image)                                                  \
+  typedef E PoolElem;                                                       \
+  const RaggedImage& im_ = tab[__builtin_amdgcn_readfirstlane(image)];      \
+  const E* nhwc_img = (const E*)im_.nhwc;                                   \
+  const int Hc = im_.Hc, Wc = im_.Wc;
+#include "lt_cls_pool_online_body.h"
+#undef LT_POOL_KERNEL
+#undef LT_POOL_TPARAMS
 #undef LT_POOL_MAP_PARAMS
 #undef LT_POOL_MAP
 

@@ -9,9 +9,9 @@ namespace lt {
 // One image of a ragged batch (linetr_describe_ragged: every image at its own size): what the kernels of the front of the pipeline read
 // from their arguments when all images have one size.  The table is built on the host and lives in the call's workspace.
 struct RaggedImage {
-  const float* nhwc;    // the image's channel-last descriptor map: the caller's own, or its copy in the workspace
+  const void* nhwc;     // the image's channel-last descriptor map: the caller's own, or its copy in the workspace (the call's element type)
   const float* score;   // its score map [height][width]
-  const float* nchw;    // the caller's [256][Hc][Wc] map the layout pass reads (NULL: the feed is channel-last)
+  const void* nchw;     // the caller's [256][Hc][Wc] map the layout pass reads (NULL: the feed is channel-last)
   int height, width, Hc, Wc;
   double td;            // token_distance
   double clip_x, clip_y;   // end-point clip (width - 0.6, height - 0.6)
@@ -73,7 +73,58 @@ static __global__ __launch_bounds__(256) void nchw_to_nhwc_ragged_kernel(const R
   const RaggedImage im = tab[blockIdx.z];
   const int P = im.Hc * im.Wc, p0 = blockIdx.x * 64;
   if (p0 >= P) return;
-  nchw_to_nhwc_tile(im.nchw, const_cast<float*>(im.nhwc), C, P, p0, blockIdx.y * 64);
+  nchw_to_nhwc_tile((const float*)im.nchw, (float*)const_cast<void*>(im.nhwc), C, P, p0, blockIdx.y * 64);
+}
+
+// The same pass on a half map (float16 or bfloat16: a transpose moves 2-byte elements and never looks into them): 8 bytes on both sides,
+// halves into a half channel-last scratch.  A half NCHW map may lie at any 2-byte address: the 8-byte load is chosen row by row.
+// LDS tile [64 c][64 p + 2] halves: rows 33 dwords apart.
+__device__ __forceinline__ void nchw_to_nhwc_tile(const uint16_t* src, uint16_t* dst, int C, int P, int p0, int c0) {
+  __shared__ uint16_t tile[64][66];
+  const int tid = threadIdx.x;
+  {
+    const int pq = (tid & 15) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = (tid >> 4) + i * 16;
+      const uint16_t* row = src + (int64_t)(c0 + c) * P + p0 + pq;
+      u16x4 v;
+      if (p0 + pq + 3 < P && (((uintptr_t)row) & 7) == 0) v = *reinterpret_cast<const u16x4*>(row);
+      else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = p0 + pq + k < P ? row[k] : (uint16_t)0;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) tile[c][pq + k] = v[k];
+    }
+  }
+  __syncthreads();
+  {
+    const int cq = (tid & 15) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int p = (tid >> 4) + i * 16;
+      if (p0 + p < P) {
+        u16x4 v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = tile[cq + k][p];
+        *reinterpret_cast<u16x4*>(dst + (int64_t)(p0 + p) * C + c0 + cq) = v;
+      }
+    }
+  }
+}
+
+static __global__ __launch_bounds__(256) void nchw_to_nhwc_half_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                                int C, int P) {
+  const int b = blockIdx.z;
+  nchw_to_nhwc_tile(in + (int64_t)b * C * P, out + (int64_t)b * C * P, C, P, blockIdx.x * 64, blockIdx.y * 64);
+}
+
+static __global__ __launch_bounds__(256) void nchw_to_nhwc_half_ragged_kernel(const RaggedImage* __restrict__ tab, int C) {
+  const RaggedImage im = tab[blockIdx.z];
+  const int P = im.Hc * im.Wc, p0 = blockIdx.x * 64;
+  if (p0 >= P) return;
+  nchw_to_nhwc_tile((const uint16_t*)im.nchw, (uint16_t*)const_cast<void*>(im.nhwc), C, P, p0, blockIdx.y * 64);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -284,7 +335,8 @@ static __global__ __launch_bounds__(64) void tokenize_ragged_kernel(
 // ---------------------------------------------------------------------------------------------
 // --- the same sampling split into "issue the 4 tap loads" and "finish", so a caller can keep the next
 // token's loads in flight while it works on the current one -----------------------------------------------
-struct TapSet { f32x4 v[4]; float w[4]; };   // nw, ne, sw, se values and weights
+template <class E> struct TapSetT { typename Elem<E>::raw4 v[4]; float w[4]; };   // nw, ne, sw, se values (as loaded) and weights
+typedef TapSetT<float> TapSet;
 
 // grid_sample's un-normalisation in the operation order of PyTorch's CPU kernel (the reference runs it on the CPU; its vectorised
 // grid sampler computes (g + 1) * (size / 2) - 0.5 with ONE rounding -- the compiler contracts the multiply-add of its vector
@@ -323,18 +375,20 @@ __device__ __forceinline__ void tap_coords(float px, float py, int Hc, int Wc, i
 }
 
 // loads of the 4 taps (this lane's 4 channels); the address is always valid, out-of-map taps carry weight 0
-__device__ __forceinline__ void taps_load(const float* __restrict__ nhwc_img, const int (&off)[4], const float (&wt)[4],
-                                          int lane, TapSet& t) {
-  const float* base = nhwc_img + lane * 4;
+template <class E>
+__device__ __forceinline__ void taps_load(const E* __restrict__ nhwc_img, const int (&off)[4], const float (&wt)[4],
+                                          int lane, TapSetT<E>& t) {
+  const E* base = nhwc_img + lane * 4;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    t.v[k] = *reinterpret_cast<const f32x4*>(base + (int64_t)off[k] * D);
+    t.v[k] = load_raw4(base + (int64_t)off[k] * D);
     t.w[k] = wt[k];
   }
 }
 
-__device__ __forceinline__ void taps_issue(float px, float py, const float* __restrict__ nhwc_img, int Hc, int Wc,
-                                           int align_corners, int lane, TapSet& t) {
+template <class E>
+__device__ __forceinline__ void taps_issue(float px, float py, const E* __restrict__ nhwc_img, int Hc, int Wc,
+                                           int align_corners, int lane, TapSetT<E>& t) {
   int off[4];
   float wt[4];
   tap_coords(px, py, Hc, Wc, align_corners, off, wt);
@@ -343,17 +397,19 @@ __device__ __forceinline__ void taps_issue(float px, float py, const float* __re
 
 // RCP = true: one division + 4 multiplies instead of 4 divisions (<= 1 ulp apart); only for consumers that never
 // expose the sampled descriptor itself (the pooling kernel), the reference's desc_sublines keeps the exact form.
-template <bool RCP = false>
-__device__ __forceinline__ f32x4 taps_finish(const TapSet& t) {
+// (a half tap set is widened here, at its first use: the loads stay in flight until then)
+template <bool RCP = false, class E>
+__device__ __forceinline__ f32x4 taps_finish(const TapSetT<E>& t) {
 #pragma clang fp contract(off)
+  const f32x4 t0 = Elem<E>::widen(t.v[0]), t1 = Elem<E>::widen(t.v[1]), t2 = Elem<E>::widen(t.v[2]), t3 = Elem<E>::widen(t.v[3]);
   f32x4 o;
   float sq = 0.f;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    float v = t.v[0][c] * t.w[0];                  // nw * w_nw, then one fused multiply-add per further tap: the CPU kernel's order
-    v = __builtin_fmaf(t.v[1][c], t.w[1], v);
-    v = __builtin_fmaf(t.v[2][c], t.w[2], v);
-    v = __builtin_fmaf(t.v[3][c], t.w[3], v);
+    float v = t0[c] * t.w[0];                      // nw * w_nw, then one fused multiply-add per further tap: the CPU kernel's order
+    v = __builtin_fmaf(t1[c], t.w[1], v);
+    v = __builtin_fmaf(t2[c], t.w[2], v);
+    v = __builtin_fmaf(t3[c], t.w[3], v);
     o[c] = v;
     sq += v * v;
   }
@@ -371,7 +427,8 @@ __device__ __forceinline__ f32x4 taps_finish(const TapSet& t) {
 }
 
 // bilinear sample (zero padding) + L2 normalisation of one token; every lane of the wave returns its 4 channels
-__device__ __forceinline__ f32x4 sample_one(float px, float py, const float* __restrict__ nhwc_img, int Hc, int Wc,
+template <class E>
+__device__ __forceinline__ f32x4 sample_one(float px, float py, const E* __restrict__ nhwc_img, int Hc, int Wc,
                                             int align_corners, int lane) {
 #pragma clang fp contract(off)
   const float s = 8.f;
@@ -385,10 +442,10 @@ __device__ __forceinline__ f32x4 sample_one(float px, float py, const float* __r
   const float w = ix - x_w, e = 1.f - w, nn = iy - y_n, ss = 1.f - nn;
   const float nw = ss * e, ne = ss * w, sw = nn * e, se = nn * w;
   const int x0 = (int)x_w, y0 = (int)y_n, x1 = x0 + 1, y1 = y0 + 1;
-  const float* base = nhwc_img + lane * 4;
+  const E* base = nhwc_img + lane * 4;
   auto tap = [&](int yy, int xx) -> f32x4 {
     if (xx < 0 || xx >= Wc || yy < 0 || yy >= Hc) return f32x4{0.f, 0.f, 0.f, 0.f};
-    return *reinterpret_cast<const f32x4*>(base + ((int64_t)yy * Wc + xx) * D);
+    return Elem<E>::widen(load_raw4(base + ((int64_t)yy * Wc + xx) * D));
   };
   const f32x4 v_nw = tap(y0, x0), v_ne = tap(y0, x1), v_sw = tap(y1, x0), v_se = tap(y1, x1);
   f32x4 o;
@@ -409,9 +466,11 @@ __device__ __forceinline__ f32x4 sample_one(float px, float py, const float* __r
   return o;
 }
 
-static __global__ __launch_bounds__(256) void sample_desc_kernel(
+// (the kernels below are written once as *_body<E>; the float32 kernels keep their names, the half ones are the *_typed_kernel<E>)
+template <class E>
+__device__ __forceinline__ void sample_desc_body(
     const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs,
-    int64_t n_tokens, int T, const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+    int64_t n_tokens, int T, const E* __restrict__ nhwc, int Hc, int Wc, int align_corners,
     float* __restrict__ desc) {
   const int64_t tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (tok >= n_tokens) return;
@@ -422,9 +481,23 @@ static __global__ __launch_bounds__(256) void sample_desc_kernel(
                              align_corners, lane);
   *reinterpret_cast<f32x4*>(desc + tok * D + lane * 4) = o;
 }
+static __global__ __launch_bounds__(256) void sample_desc_kernel(
+    const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs,
+    int64_t n_tokens, int T, const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+    float* __restrict__ desc) {
+  sample_desc_body(pnt, sub2line_g, recs, n_tokens, T, nhwc, Hc, Wc, align_corners, desc);
+}
+template <class E>
+static __global__ __launch_bounds__(256) void sample_desc_typed_kernel(
+    const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs,
+    int64_t n_tokens, int T, const E* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+    float* __restrict__ desc) {
+  sample_desc_body(pnt, sub2line_g, recs, n_tokens, T, nhwc, Hc, Wc, align_corners, desc);
+}
 
 // ragged: map and size from the table entry of the token's image
-static __global__ __launch_bounds__(256) void sample_desc_ragged_kernel(
+template <class E>
+__device__ __forceinline__ void sample_desc_ragged_body(
     const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs, int64_t n_tokens, int T,
     const RaggedImage* __restrict__ tab, int align_corners, float* __restrict__ desc) {
   const int64_t tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -432,8 +505,19 @@ static __global__ __launch_bounds__(256) void sample_desc_ragged_kernel(
   const int lane = threadIdx.x & 63;
   const int n = (int)(tok / T);
   const int img = __builtin_amdgcn_readfirstlane(recs[sub2line_g[n]].image);   // one token per wave: its image is wave-uniform
-  const f32x4 o = sample_one(pnt[tok * 2 + 0], pnt[tok * 2 + 1], tab[img].nhwc, tab[img].Hc, tab[img].Wc, align_corners, lane);
+  const f32x4 o = sample_one(pnt[tok * 2 + 0], pnt[tok * 2 + 1], (const E*)tab[img].nhwc, tab[img].Hc, tab[img].Wc, align_corners, lane);
   *reinterpret_cast<f32x4*>(desc + tok * D + lane * 4) = o;
+}
+static __global__ __launch_bounds__(256) void sample_desc_ragged_kernel(
+    const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs, int64_t n_tokens, int T,
+    const RaggedImage* __restrict__ tab, int align_corners, float* __restrict__ desc) {
+  sample_desc_ragged_body<float>(pnt, sub2line_g, recs, n_tokens, T, tab, align_corners, desc);
+}
+template <class E>
+static __global__ __launch_bounds__(256) void sample_desc_ragged_typed_kernel(
+    const float* __restrict__ pnt, const int* __restrict__ sub2line_g, const LinetrLineRec* __restrict__ recs, int64_t n_tokens, int T,
+    const RaggedImage* __restrict__ tab, int align_corners, float* __restrict__ desc) {
+  sample_desc_ragged_body<E>(pnt, sub2line_g, recs, n_tokens, T, tab, align_corners, desc);
 }
 
 constexpr int KP_DESC_N = 64;     // key points per block
@@ -444,9 +528,10 @@ constexpr size_t KP_DESC_LDS = (size_t)D * KP_DESC_LS * 4;
 // key point (sample_one), staged through LDS [256][65] so that the store along n is contiguous: image b owns [256][n_b] floats at
 // out + 256 cu_kp[b].  grid ceil(n_total / 64) + B (an upper bound of the chunks; the block finds its image in cu_kp), block 256,
 // dynamic LDS KP_DESC_LDS.
-static __global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
-                                                         const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
-                                                         float* __restrict__ out) {
+template <class E>
+__device__ __forceinline__ void sp_kp_desc_body(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
+                                                const E* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+                                                float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float kp_tile[];
   int chunk = blockIdx.x, b = 0, start = 0, n_b = 0;
   for (; b < B; ++b) {
@@ -459,7 +544,7 @@ static __global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __r
   if (b >= B) return;
   const int j0 = chunk * KP_DESC_N, nj = min(KP_DESC_N, n_b - j0);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const float* img = nhwc + (int64_t)b * Hc * Wc * D;
+  const E* img = nhwc + (int64_t)b * Hc * Wc * D;
   for (int j = w; j < nj; j += 4) {
     const int64_t g = (int64_t)start + j0 + j;
     const f32x4 o = sample_one(kp[g * 2 + 0], kp[g * 2 + 1], img, Hc, Wc, align_corners, lane);
@@ -470,6 +555,17 @@ static __global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __r
   float* dst = out + (int64_t)D * start + j0;
   if (lane < nj)
     for (int ch = w * 64; ch < w * 64 + 64; ++ch) dst[(int64_t)ch * n_b + lane] = kp_tile[ch * KP_DESC_LS + lane];
+}
+static __global__ __launch_bounds__(256) void sp_kp_desc_kernel(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
+                                                         const float* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+                                                         float* __restrict__ out) {
+  sp_kp_desc_body(kp, cu_kp, B, nhwc, Hc, Wc, align_corners, out);
+}
+template <class E>
+static __global__ __launch_bounds__(256) void sp_kp_desc_typed_kernel(const float* __restrict__ kp, const int* __restrict__ cu_kp, int B,
+                                                               const E* __restrict__ nhwc, int Hc, int Wc, int align_corners,
+                                                               float* __restrict__ out) {
+  sp_kp_desc_body(kp, cu_kp, B, nhwc, Hc, Wc, align_corners, out);
 }
 
 }  // namespace lt

@@ -201,6 +201,28 @@ class Engine(_TrainSurface, _DebugSurface):
             t = t.clone()
         return t
 
+    def _dense_map(self, t: torch.Tensor):
+        """A dense descriptor map (or a raw head output) as the kernels take it: (tensor, format bits).  A contiguous float16, bfloat16
+        or float32 tensor on this device is passed as it is and read in place, the half types with their LINETR_DENSE_* bit; anything
+        else -- another dtype, another device, a non-contiguous tensor -- becomes a float32 copy (_f32)."""
+        bits = self._half_bits(t)
+        if bits:
+            return (t if t.data_ptr() % 16 == 0 else t.clone()), bits
+        return self._f32(t), 0
+
+    def _half_bits(self, t: torch.Tensor) -> int:
+        """The LINETR_DENSE_* bit of a tensor the kernels would read in place as a half map (nothing is converted); 0 for every other"""
+        bits = nat.dense_type_bits(t.dtype)
+        return bits if bits and t.device == self.device and t.is_contiguous() else 0
+
+    def _dense_maps_typed(self, tensors):
+        """Tensors that one native call reads with ONE element type (the maps of a ragged batch, the two raw head outputs): (tensors,
+        format bits).  All of one half type: each as _dense_map passes it; anything else: every one through _f32.  Each tensor is
+        converted or cloned at most once."""
+        kinds = {self._half_bits(t) for t in tensors}
+        bits = kinds.pop() if len(kinds) == 1 else 0
+        return [self._dense_map(t)[0] if bits else self._f32(t) for t in tensors], bits
+
     # ------------------------------------------------------------------ host pre-filter
     def _pinned_slot(self, nbytes):
         """ring of pinned staging buffers; a slot is reused only after its last H2D copy has completed."""
@@ -357,10 +379,12 @@ class Engine(_TrainSurface, _DebugSurface):
         return recs[:K], cu_k.copy(), cu_n.copy()
 
     # ------------------------------------------------------------------ device stages
-    def _dense_maps(self, dense_desc, dense_score, B, dense_layout):
-        """The dense maps of a B-image call as float32 device tensors with a batch axis, checked against each other: dense_score
-        [B,H,W] and dense_desc [B,256,H/8,W/8] ('nchw') or [B,H/8,W/8,256] ('nhwc').  Returns (dense_desc, dense_score, H, W, nhwc)."""
-        dense_desc = self._f32(dense_desc)
+    def _dense_maps(self, dense_desc, dense_score, B, dense_layout, in_place=True):
+        """The dense maps of a B-image call as device tensors with a batch axis, checked against each other: dense_score [B,H,W]
+        (float32) and dense_desc [B,256,H/8,W/8] ('nchw') or [B,H/8,W/8,256] ('nhwc'), float32 or -- read in place, _dense_map -- float16 /
+        bfloat16.  in_place=False: for an entry point that takes float32 maps only (linetr_fixed_size), every map goes through _f32.
+        Returns (dense_desc, dense_score, H, W, the native `dense_is_nhwc`: layout flag | element-type bits)."""
+        dense_desc, bits = self._dense_map(dense_desc) if in_place else (self._f32(dense_desc), 0)
         dense_score = self._f32(dense_score)
         if dense_score.dim() == 2:
             dense_score = dense_score[None]
@@ -373,7 +397,7 @@ class Engine(_TrainSurface, _DebugSurface):
         want = (B, H // 8, W // 8, D) if nhwc else (B, D, H // 8, W // 8)
         if tuple(dense_desc.shape) != want:
             raise ValueError(f"dense_descriptor shape {tuple(dense_desc.shape)} does not match {want} ({dense_layout})")
-        return dense_desc, dense_score, H, W, nhwc
+        return dense_desc, dense_score, H, W, int(nhwc) | bits
 
     def _pooled(self, shapes):
         """Named float32 device tensors as views of ONE allocation, each on a 16-byte boundary (a dozen torch.empty calls are ~40 us of
@@ -425,7 +449,8 @@ class Engine(_TrainSurface, _DebugSurface):
     def describe(self, recs, cu_k, cu_n, dense_desc, dense_score, *, token_distance, max_tokens, align_corners=False,
                  want_tokens=False, dense_layout="nchw", want_mat=False, pipeline_slot=None):
         """Fused tokenise + descriptor network for a batch (linetr_describe): real tokens only, descriptors sampled
-        on the fly.  Returns (TokenBatch, line_desc [N,256]).  With want_tokens=False the dense [N,T,...] token
+        on the fly.  A contiguous float16 / bfloat16 dense_desc on this device is read in place (no float32 copy; the results are those
+        of its exact upcast); dense_score and every output are float32.  Returns (TokenBatch, line_desc [N,256]).  With want_tokens=False the dense [N,T,...] token
         tensors (pnt / mask / score / desc) are not materialised (zero-sized in the TokenBatch).
 
         pipeline_slot = (slot, n_slots): linetr_describe_submit -- the batch runs on the library's stage streams, overlapped with the
@@ -494,7 +519,8 @@ class Engine(_TrainSurface, _DebugSurface):
                         want_tokens=False, dense_layout="nchw", want_mat=False):
         """describe() for images of DIFFERENT sizes (linetr_describe_ragged).  `dense_descs` / `dense_scores` are lists with one map per
         image, each its own tensor of its own shape -- [256,H/8,W/8] ('nchw') or [H/8,W/8,256] ('nhwc'), and [H,W]; a leading batch axis
-        of 1 is accepted -- and need not be packed.  `token_distance`: one value, or one per image (what the records were made with:
+        of 1 is accepted -- and need not be packed.  A call has one element type: if every descriptor map is a contiguous float16 (or every
+        one a bfloat16) device tensor they are read in place, a batch of mixed element types is upcast to float32 together.  `token_distance`: one value, or one per image (what the records were made with:
         prefilter_ragged).  Returns (TokenBatch, line_desc [N,256]) like describe(); want_mat serves up to 8 images."""
         B = len(cu_k) - 1
         K, N, T = int(cu_k[-1]), int(cu_n[-1]), int(max_tokens)
@@ -504,8 +530,9 @@ class Engine(_TrainSurface, _DebugSurface):
         table = np.zeros(B, dtype=nat.IMAGE_DTYPE)
         table["token_distance"] = np.broadcast_to(np.asarray(token_distance, dtype=np.float64), (B,))
         maps = []
-        for i, (dd, ds) in enumerate(zip(dense_descs, dense_scores)):
-            dd, ds = self._f32(dd), self._f32(ds)
+        typed, bits = self._dense_maps_typed(list(dense_descs))
+        for i, (dd, ds) in enumerate(zip(typed, dense_scores)):
+            ds = self._f32(ds)
             dd, ds = (dd[0] if dd.dim() == 4 else dd), (ds[0] if ds.dim() == 3 else ds)
             H, W = int(ds.shape[-2]), int(ds.shape[-1])
             want = (H // 8, W // 8, D) if nhwc else (D, H // 8, W // 8)
@@ -520,7 +547,7 @@ class Engine(_TrainSurface, _DebugSurface):
         tb.extra["dense"] = maps          # the stream reads them after this call returns
         n_real = int(recs["n_tok"][:K].sum())
         d_recs, d_cu = self._upload_recs(recs, K, B, tb)
-        nbytes = self._L.linetr_describe_ragged_workspace_bytes(self._h, nat.np_ptr(table), B, int(nhwc), N, n_real)
+        nbytes = self._L.linetr_describe_ragged_workspace_bytes(self._h, nat.np_ptr(table), B, int(nhwc) | bits, N, n_real)
         if nbytes < 0:      # the table is refused: the call says why
             nbytes = 0
         ws = self._workspace("desc", nbytes)
@@ -529,7 +556,7 @@ class Engine(_TrainSurface, _DebugSurface):
         with torch.cuda.device(self.device):
             nat.check(self._L.linetr_describe_ragged(self._h, d_recs.data_ptr(), nat.np_ptr(recs_c), K, N, n_real, nat.np_ptr(cu),
                                                      d_cu.data_ptr() if d_cu is not None else None, nat.np_ptr(table), B, T,
-                                                     int(bool(align_corners)), int(nhwc), ct, tb.sub2line.data_ptr(), ld.data_ptr(),
+                                                     int(bool(align_corners)), int(nhwc) | bits, ct, tb.sub2line.data_ptr(), ld.data_ptr(),
                                                      ws.data_ptr(), ws.numel(), self._stream()), self._L)
         return tb, ld
 
@@ -800,11 +827,11 @@ class Engine(_TrainSurface, _DebugSurface):
 
     def sample_descriptors(self, points: torch.Tensor, dense_desc: torch.Tensor, *, align_corners=False, dense_layout="nchw"):
         """sample_descriptors (line_process.py:86-98) for n points [n,2] of one image; dense_desc [256,Hc,Wc] or
-        [Hc,Wc,256]; returns [n,256]."""
+        [Hc,Wc,256], float32 or (read in place) float16 / bfloat16; returns [n,256] float32."""
         pts = self._f32(points.reshape(-1, 2))
-        dd = self._f32(dense_desc)
-        nhwc = dense_layout == "nhwc"
-        Hc, Wc = (int(dd.shape[0]), int(dd.shape[1])) if nhwc else (int(dd.shape[1]), int(dd.shape[2]))
+        dd, bits = self._dense_map(dense_desc)
+        Hc, Wc = (int(dd.shape[0]), int(dd.shape[1])) if dense_layout == "nhwc" else (int(dd.shape[1]), int(dd.shape[2]))
+        nhwc = int(dense_layout == "nhwc") | bits          # the native `dense_is_nhwc`: layout flag | element-type bits
         n = int(pts.shape[0])
         out = torch.empty((n, D), dtype=torch.float32, device=self.device)
         if n == 0:
@@ -921,16 +948,24 @@ class Engine(_TrainSurface, _DebugSurface):
         return dist, m01
 
     def superpoint_heads(self, score_logits: torch.Tensor = None, desc_raw: torch.Tensor = None, *, nhwc=True,
-                         nchw=False):
+                         nchw=False, dense_dtype=None):
         """Fused SuperPoint head post-processing (models/superpoint.py:161-167, 190-193).
 
         score_logits [B,65,Hc,Wc] (convPb output) -> dense_score [B,8Hc,8Wc];
         desc_raw [B,256,Hc,Wc] (convDb output) -> L2-normalised descriptors as [B,Hc,Wc,256] (`nhwc`, the layout
         `describe_lines(..., dense_layout='nhwc')` consumes without a transposition pass) and/or [B,256,Hc,Wc]
         (`nchw`, the reference's 'dense_descriptor').  Returns (dense_score, desc_nhwc, desc_nchw), None where not
-        requested."""
-        sl = self._f32(score_logits) if score_logits is not None else None
-        dr = self._f32(desc_raw) if desc_raw is not None else None
+        requested.
+
+        The raw head outputs are read in the type the convolutions produced: contiguous float16 / bfloat16 device tensors (a SuperPoint
+        under autocast) in place, both heads in one type (a mixed pair is upcast to float32 together).  dense_dtype: the element type
+        of the two descriptor maps, None / torch.float32 (the default), torch.float16 or torch.bfloat16; dense_score is float32 always."""
+        out_bits = nat.dense_type_bits(dense_dtype or torch.float32)
+        if out_bits is None:
+            raise ValueError(f"dense_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got {dense_dtype}")
+        typed, in_bits = self._dense_maps_typed([t for t in (score_logits, desc_raw) if t is not None])
+        sl = typed[0] if score_logits is not None else None
+        dr = typed[-1] if desc_raw is not None else None
         ref = sl if sl is not None else dr
         if ref is None:
             raise ValueError("superpoint_heads needs at least one head")
@@ -940,11 +975,16 @@ class Engine(_TrainSurface, _DebugSurface):
         if dr is not None and tuple(dr.shape) != (B, D, Hc, Wc):
             raise ValueError(f"desc_raw must be [B,{D},Hc,Wc], got {tuple(dr.shape)}")
         score = torch.empty((B, Hc * 8, Wc * 8), dtype=torch.float32, device=self.device) if sl is not None else None
-        o_nhwc = torch.empty((B, Hc, Wc, D), dtype=torch.float32, device=self.device) if (dr is not None and nhwc) else None
-        o_nchw = torch.empty((B, D, Hc, Wc), dtype=torch.float32, device=self.device) if (dr is not None and nchw) else None
+        odt = dense_dtype or torch.float32
+        o_nhwc = torch.empty((B, Hc, Wc, D), dtype=odt, device=self.device) if (dr is not None and nhwc) else None
+        o_nchw = torch.empty((B, D, Hc, Wc), dtype=odt, device=self.device) if (dr is not None and nchw) else None
         with torch.cuda.device(self.device):     # a heads-only engine has no handle: the current device is used
-            nat.check(self._L.linetr_superpoint_heads(self._h, ptr(sl), ptr(dr), B, Hc, Wc, ptr(score), ptr(o_nhwc),
-                                                      ptr(o_nchw), self._stream()), self._L)
+            if in_bits or out_bits:
+                nat.check(self._L.linetr_superpoint_heads_typed(self._h, ptr(sl), ptr(dr), in_bits, B, Hc, Wc, ptr(score), ptr(o_nhwc),
+                                                                ptr(o_nchw), out_bits, self._stream()), self._L)
+            else:
+                nat.check(self._L.linetr_superpoint_heads(self._h, ptr(sl), ptr(dr), B, Hc, Wc, ptr(score), ptr(o_nhwc),
+                                                          ptr(o_nchw), self._stream()), self._L)
         return score, o_nhwc, o_nchw
 
     def superpoint_heads_rows(self, score_rows: torch.Tensor = None, desc_rows: torch.Tensor = None, shape=None, *, nhwc=True,
@@ -1299,7 +1339,8 @@ class Engine(_TrainSurface, _DebugSurface):
         """SuperPoint's key-point branch for a batch (models/superpoint.py:168-187, 195-197) in native calls: simple_nms,
         threshold, remove_borders, top_k_keypoints, (row, col) -> (x, y) and sample_descriptors.
 
-        dense_score [B,H,W]; dense_desc [B,Hc,Wc,256] ('nhwc', what superpoint_heads emits) or [B,256,Hc,Wc] ('nchw'), or None.
+        dense_score [B,H,W]; dense_desc [B,Hc,Wc,256] ('nhwc', what superpoint_heads emits) or [B,256,Hc,Wc] ('nchw'), float32 or (read
+        in place) float16 / bfloat16, or None.
         Returns three per-image lists: keypoints [n_b,2] (x, y), scores [n_b], descriptors [256,n_b] -- views into three batch
         buffers -- or None in place of the descriptors when no map is given.  Key points and scores are the reference's bit for
         bit, in its order (row-major; with max_keypoints and more candidates than that: descending score, equal scores by ascending
@@ -1322,7 +1363,7 @@ class Engine(_TrainSurface, _DebugSurface):
             raise ValueError("dense_layout must be 'nhwc' or 'nchw'")
         dd = None
         if dense_desc is not None:
-            dd = self._f32(dense_desc)
+            dd, bits = self._dense_map(dense_desc)
             nhwc = dense_layout == "nhwc"
             if dd.dim() != 4 or int(dd.shape[0]) != B or int(dd.shape[3 if nhwc else 1]) != D:
                 raise ValueError(f"dense_desc must be [B,Hc,Wc,{D}] (nhwc) or [B,{D},Hc,Wc] (nchw), got {tuple(dd.shape)}")
@@ -1352,9 +1393,9 @@ class Engine(_TrainSurface, _DebugSurface):
             if dd is not None:
                 desc = torch.empty((D * n_total,), dtype=torch.float32, device=self.device)
                 if n_total > 0:
-                    wd = self._workspace("sample", self._L.linetr_point_descriptors_workspace_bytes(B, Hc, Wc, int(nhwc)))
+                    wd = self._workspace("sample", self._L.linetr_point_descriptors_workspace_bytes(B, Hc, Wc, int(nhwc) | bits))
                     nat.check(self._L.linetr_point_descriptors(self._h, kp.data_ptr(), cu.data_ptr(), B, n_total, dd.data_ptr(), Hc, Wc,
-                                                               int(bool(align_corners)), int(nhwc), desc.data_ptr(), wd.data_ptr(),
+                                                               int(bool(align_corners)), int(nhwc) | bits, desc.data_ptr(), wd.data_ptr(),
                                                                wd.numel(), self._stream()), self._L)
         o = h_cu.tolist()
         kps = [kp[o[b]:o[b + 1]] for b in range(B)]

@@ -257,11 +257,13 @@ class _DebugSurface:
         """ONE CLS-pooling kernel alone (linetr_debug_cls_pool; diagnostics / unit tests).  kernel: -1 (the forward pass's choice)
         or an index into CLS_POOL_KERNELS.  Kernel 0 reads desc_dense [N, T, 256] and a4 [N * T, 256]; the online kernels the
         records `recs` (a uint8 device tensor holding LineRec[K]), sub2line [N] int32, cpnt [first_pad + n_images, 2], a4
-        [first_pad + n_images, 256] and n_images maps of Hc x Wc cells (`nhwc`: channel-last, else NCHW).  out: contiguous float32
-        [>= N, 4, 544].  Returns (out, kernel used)."""
+        [first_pad + n_images, 256] and n_images maps of Hc x Wc cells (`nhwc`: channel-last, else NCHW; float32, or float16 / bfloat16
+        read in place).  out: contiguous float32 [>= N, 4, 544].  Returns (out, kernel used)."""
         for t in (a4, out, cpnt, dense_map, desc_dense):
-            if t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
-                raise ValueError("contiguous float32 tensors on the engine's device expected")
+            if t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()) and \
+                    not (t is dense_map and nat.dense_type_bits(t.dtype) and t.device == self.device and t.is_contiguous()):
+                raise ValueError("contiguous float32 tensors (dense_map: or float16 / bfloat16) on the engine's device expected")
+        bits = nat.dense_type_bits(dense_map.dtype) if dense_map is not None else 0
         if out.numel() < N * 4 * 544:
             raise ValueError("out is smaller than [N, 4, 544]")
         if desc_dense is None:
@@ -273,7 +275,7 @@ class _DebugSurface:
             raise ValueError("a4 / desc_dense are smaller than [N * T, 256]")
         used = C.c_int32(-1)
         self._call("linetr_debug_cls_pool", int(kernel), ptr(recs), recs.numel() // nat.REC_DTYPE.itemsize if recs is not None else 0,
-                   ptr(sub2line), int(N), int(T), ptr(cpnt), ptr(a4), int(first_pad), int(n_images), ptr(dense_map), int(bool(nhwc)), int(Hc),
+                   ptr(sub2line), int(N), int(T), ptr(cpnt), ptr(a4), int(first_pad), int(n_images), ptr(dense_map), int(bool(nhwc)) | bits, int(Hc),
                    int(Wc), int(bool(align_corners)), ptr(desc_dense), ptr(out), C.byref(used))
         return out, used.value
 

@@ -684,7 +684,8 @@ class _TrainSurface:
         M, T = int(max_sublines), int(max_tokens)
         if B < 1 or len(cu_n32) != B + 1:
             raise ValueError("fixed_size_batch: cu_k and cu_n must hold B + 1 >= 2 prefix sums")
-        dense_desc, dense_score, H, W, nhwc = self._dense_maps(dense_desc, dense_score, B, dense_layout)
+        # (linetr_fixed_size takes float32 maps only: a half map is upcast, as every map of another type is)
+        dense_desc, dense_score, H, W, nhwc = self._dense_maps(dense_desc, dense_score, B, dense_layout, in_place=False)
         n_add = np.maximum(M - np.diff(cu_n32).astype(np.int64), 0)
         if pseudo_lines is None:
             pseudo_lines = [util_lines.find_line_attributes(util_lines.make_pseudo_lines(int(n), resize, seed=seed or 0, image=b), min_length, M)

@@ -45,11 +45,14 @@ class Matching(torch.nn.Module):
             # config['native_keypoints'] = True (default False) also moves the wrapper's key-point branch (NMS, threshold, border
             # filter, top-k, descriptor lookup) from the module's per-image torch helpers to one native call per batch.
             # config['native_encoder'] = True (default False) runs the twelve convolutions natively as well (inference only).
+            # config['dense_dtype'] = torch.float16 / torch.bfloat16 (default None: float32) makes the wrapper write half descriptor
+            # maps, which the tokeniser and the line network read in place.
             if config.get("fuse_superpoint_heads", True) and all(hasattr(superpoint, a) for a in
                                                                   ("convPa", "convPb", "convDa", "convDb", "relu", "pool")):
                 from .superpoint import FusedHeadSuperPoint
                 superpoint = FusedHeadSuperPoint(superpoint, native_keypoints=config.get("native_keypoints", False),
-                                                 native_encoder=config.get("native_encoder", False))
+                                                 native_encoder=config.get("native_encoder", False),
+                                                 dense_dtype=config.get("dense_dtype"))
         self.superpoint = superpoint
         self.lsd = lsd if lsd is not None else _frontend("line_detector", "LSD", config.get("lsd", {}))
         self.linetransformer = LineTransformer(config.get("linetransformer", {}))

@@ -14,6 +14,12 @@ dense_layout='nhwc')` skips its NCHW->NHWC pass.  The convolutions stay in PyTor
 module-level functions, image by image, unless `native_keypoints=True`: then it is one `Engine.superpoint_keypoints`
 call for the batch (`linetr_superpoint_keypoints` + `linetr_point_descriptors`), fed the channel-last map the heads call
 has just produced -- same key points and scores bit for bit, one host wait per batch instead of one per image.
+
+Half precision: the raw head outputs are read in the type the convolutions produced, so a wrapped module in `.half()` / `.bfloat16()`
+(or run under `torch.autocast`) costs no float32 copy.  `dense_dtype=None` writes float32 maps from them; `dense_dtype=torch.float16`
+or `torch.bfloat16` writes half 'dense_descriptor' / 'dense_descriptor_nhwc' (the float32 values rounded to nearest-even), which the
+line tokeniser, `Engine.describe*` and the native key-point branch read in place, and 'descriptors' follows that type as the wrapped
+module's would.  'dense_score', key points and scores are float32 always.
 """
 from __future__ import annotations
 
@@ -25,8 +31,13 @@ from torch import nn
 
 class FusedHeadSuperPoint(nn.Module):
     def __init__(self, superpoint: nn.Module, engine=None, helpers=None, want_nchw: bool = True,
-                 native_keypoints: bool = False, align_corners=None, native_encoder: bool = False):
+                 native_keypoints: bool = False, align_corners=None, native_encoder: bool = False, dense_dtype=None):
         super().__init__()
+        if dense_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"dense_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got {dense_dtype}")
+        if native_encoder and dense_dtype in (torch.float16, torch.bfloat16):
+            raise ValueError("native_encoder=True writes float32 maps only (its channel-last producer has no half output)")
+        self.dense_dtype = None if dense_dtype == torch.float32 else dense_dtype
         self.sp = superpoint
         self.config = superpoint.config
         self.want_nchw = want_nchw
@@ -71,14 +82,18 @@ class FusedHeadSuperPoint(nn.Module):
         else:
             score_logits, desc_raw = self.encode(data["image"])
             dense_score, d_nhwc, d_nchw = self.engine().superpoint_heads(score_logits, desc_raw, nhwc=True,
-                                                                         nchw=self.want_nchw)
+                                                                         nchw=self.want_nchw, dense_dtype=self.dense_dtype)
             hc, wc = int(score_logits.shape[2]), int(score_logits.shape[3])
         if d_nchw is None:                       # a view with the reference's shape (not contiguous)
             d_nchw = d_nhwc.permute(0, 3, 1, 2)
         if self.native_keypoints:
             keypoints, scores, descriptors = self._keypoints_native(dense_score, d_nhwc)
         else:
-            keypoints, scores, descriptors = self._keypoints(dense_score, d_nchw, hc * 8, wc * 8)
+            # (the wrapped module's grid_sample cannot mix a half map with its float32 grid: it is handed a float32 tensor made by torch)
+            keypoints, scores, descriptors = self._keypoints(dense_score, d_nchw if self.dense_dtype is None else d_nchw.float(),
+                                                             hc * 8, wc * 8)
+        if self.dense_dtype is not None:
+            descriptors = [d.to(self.dense_dtype) for d in descriptors]
         return {"keypoints": keypoints, "scores": scores, "descriptors": descriptors, "dense_descriptor": d_nchw,
                 "dense_score": dense_score, "dense_descriptor_nhwc": d_nhwc}
 
